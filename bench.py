@@ -27,6 +27,15 @@ this GPU (what N GPUs would give, fixed per-rank costs included).  `hard8192` = 
 configuration on UNSTRUCTURED N(0, I) embeddings (clustered spectrum: which eigen path
 finished, passes, restart cycles).  `autotune16_ttd` = config 4's Turn-to-Diarize variant.
 `--workload batch512|autotune16` makes one of them the `value`.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the
+result line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).
+Everything else above -- `resident`, the per-kernel and whole-call rooflines, the explicit fp64
+Diffuse route, the workload legs and their projections, the concurrent / pipelined legs, the CPU
+baselines, the parity checks against the stored reference labels -- runs with `--full`.
+`--dump-outputs DIR` writes what the last timed step returned as float64 .npy files: `labels`
+(n) and `eigenvalues` (the leading eigenvalues the call reports); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 
 import argparse
@@ -686,6 +695,56 @@ def kernel_roofline(stage_ms, passes):
   return rows
 
 
+def headline_record(args, world, elapsed, comm, multigpu):
+  """The keys of the result line that a plain run and --full share: the headline figure of the
+  K timed predict() calls and what it was measured on."""
+  k = args.steps
+  return {
+      "metric": "predict() calls/sec, n=8192 d=256 ICASSP2018 (GraphCut, eigengap "
+                "k in [2,20], cosine k-means)",
+      "value": world * k / elapsed, "unit": "calls/s", "n_gpus": world, "steps": k,
+      "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / k,
+      "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+      "dtype": "f64", "data": "synthetic",
+      "config": {"workload": "icassp2018_graphcut_n8192_d256_k8_max20",
+                 "n_samples": N_SAMPLES, "n_features": N_FEATURES,
+                 "speakers": N_SPEAKERS, "parallelism": "replicas x%d" % world,
+                 "step": "sc_predict = SpectralClusterer.predict(): H2D of X (16.8 MB, "
+                         "pageable numpy buffer), the device pipeline, D2H of the labels",
+                 "collectives": ("none" if world == 1 else
+                                 "RCCL via the C ABI (sc_comm_*)"
+                                 if isinstance(comm, multigpu.RcclComm) else
+                                 "TCP fallback (RCCL did not come up: %s)"
+                                 % getattr(comm, "note", ""))},
+  }
+
+
+def select_workload(out, extras, workload):
+  """--workload batch512 | autotune16: that leg's figure becomes `value` (the predict() figure
+  moves to `headline_predict8192`; `ms_per_step` stays that of the K timed steps)."""
+  out.update(extras)
+  if workload == "predict8192":
+    return
+  leg = extras[workload]
+  out["headline_predict8192"] = {"value": out["value"], "unit": out["unit"],
+                                 "ms_per_step": out["ms_per_step"]}
+  out["metric"] = ("BASELINE config 5: 512 utterances n in [300,3000] d=256, ICASSP2018"
+                   if workload == "batch512" else
+                   "BASELINE config 4: AutoTune 16-value sweep, n=4096 d=256, GraphCut")
+  out["value"], out["unit"] = leg["value"], leg["unit"]
+  out["scaling"] = "strong"
+  out["higher_is_better"] = workload == "batch512"
+  out["config"]["workload"] = workload
+
+
+def dump_outputs(directory, **arrays):
+  """--dump-outputs: each array as DIR/<name>.npy in float64 (labels and eigenvalues of one
+  n = 8192 call: 64 KB and 1 KB)."""
+  os.makedirs(directory, exist_ok=True)
+  for name, a in arrays.items():
+    np.save(os.path.join(directory, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument("--gpus", type=int, default=None,
@@ -695,13 +754,22 @@ def main():
   ap.add_argument("--warmup", type=int, default=3)
   ap.add_argument("--workload", default="predict8192",
                   choices=["predict8192", "batch512", "autotune16"])
-  ap.add_argument("--no-cpu-baseline", action="store_true")
+  ap.add_argument("--full", action="store_true",
+                  help="everything beside the headline: resident path, rooflines, explicit "
+                       "Diffuse route, workload legs and projections, concurrent / pipelined "
+                       "legs, CPU baselines, parity against the stored reference labels")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write the last timed step's outputs to DIR/<name>.npy (float64)")
+  ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full)")
   ap.add_argument("--cpu-baseline-sample-only", action="store_true",
-                  help="CPU baseline on the n=2048 sample only (skip the one n=8192 oracle call)")
-  ap.add_argument("--no-concurrent", action="store_true")
+                  help="(with --full) CPU baseline on the n=2048 sample only (skip the one "
+                       "n=8192 oracle call)")
+  ap.add_argument("--no-concurrent", action="store_true", help="(with --full)")
   ap.add_argument("--no-extras", action="store_true",
-                  help="skip the batch512 / autotune16 legs")
+                  help="(with --full) skip the batch512 / autotune16 legs")
   args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error("--steps must be >= 1 and --warmup >= 0")
 
   from spectralcluster_amd import multigpu
   if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
@@ -752,8 +820,6 @@ def main():
   x, truth = blobs(N_SAMPLES, N_FEATURES, N_SPEAKERS, SEED + rank)
   labels = np.empty(N_SAMPLES, dtype=np.int64)
   diag = _lib.ScDiag()
-  handle.check(lib.sc_set_embeddings(handle.raw, _lib.as_double_p(x), N_SAMPLES,
-                                     N_FEATURES))
 
   def step():
     handle.check(lib.sc_run_resident(handle.raw, cfg, _lib.as_int64_p(labels), diag))
@@ -787,7 +853,27 @@ def main():
     passes[0] += diag.eig_matvec_passes
 
   k = args.steps
-  elapsed = timed(step_h2d, k, collect)  # THE timed region: K predict() calls
+  # THE timed region: K predict() calls (the per-stage timers are summed for --full only)
+  elapsed = timed(step_h2d, k, collect if args.full else None)
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, labels=labels, eigenvalues=diag.eigenvalue_array())
+
+  if not args.full:
+    extras = {}
+    if args.workload == "batch512":
+      extras["batch512"] = batch512_leg(sca, multigpu, comm, fence, project=False)
+    elif args.workload == "autotune16":
+      extras["autotune16"] = autotune16_leg(sca, multigpu, comm, fence, project=False)
+    if rank == 0:
+      out = headline_record(args, world, elapsed, comm, multigpu)
+      select_workload(out, extras, args.workload)
+      print(json.dumps(out), flush=True)
+    comm.barrier()
+    comm.close()
+    return
+
+  handle.check(lib.sc_set_embeddings(handle.raw, _lib.as_double_p(x), N_SAMPLES,
+                                     N_FEATURES))
   stage_ms = {name: float(stage_sum[i] / k) for i, name in enumerate(names)}
   passes_per_call = passes[0] / k
   eig_info = {"matvec_passes_per_call": passes_per_call, "block": int(diag.eig_block),
@@ -945,23 +1031,8 @@ def main():
              "measured_over_explicit_route_floor": (elapsed / k) / x_floor,
              "note": "floors: MFMA time of the flops/ops at peak + algorithmic HBM bytes at "
                      "8 TB/s, stages data-dependent so they add; H2D of X inside measured_ms"}
-    out = {
-        "metric": "predict() calls/sec, n=8192 d=256 ICASSP2018 (GraphCut, eigengap "
-                  "k in [2,20], cosine k-means)",
-        "value": world * k / elapsed, "unit": "calls/s", "n_gpus": world, "steps": k,
-        "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / k,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "icassp2018_graphcut_n8192_d256_k8_max20",
-                   "n_samples": N_SAMPLES, "n_features": N_FEATURES,
-                   "speakers": N_SPEAKERS, "parallelism": "replicas x%d" % world,
-                   "step": "sc_predict = SpectralClusterer.predict(): H2D of X (16.8 MB, "
-                           "pageable numpy buffer), the device pipeline, D2H of the labels",
-                   "collectives": ("none" if world == 1 else
-                                   "RCCL via the C ABI (sc_comm_*)"
-                                   if isinstance(comm, multigpu.RcclComm) else
-                                   "TCP fallback (RCCL did not come up: %s)"
-                                   % getattr(comm, "note", ""))},
+    out = headline_record(args, world, elapsed, comm, multigpu)
+    out.update({
         "resident": {
             "value": world * k / elapsed_resident, "unit": "calls/s",
             "ms_per_step": 1e3 * elapsed_resident / k,
@@ -981,7 +1052,7 @@ def main():
         "parity": {"n_clusters": n_clusters, "ari_vs_truth": ari(predict_labels, truth),
                    "labels_equal_with_resident_path": bool(np.array_equal(resident_labels,
                                                                          predict_labels))},
-    }
+    })
     gpath = os.path.join(ROOT, "tests", "golden", "e2e_n8192_lap4_max20.npz")
     if os.path.exists(gpath):
       g = np.load(gpath)
@@ -1034,18 +1105,7 @@ def main():
       out["roofline"]["traffic_measured_on"] = {
           "commit": t.get("commit"), "gemm_f64_sha16": t.get("gemm_f64_sha16"),
           "kernel_source_unchanged_since": t.get("gemm_f64_sha16") == now}
-    out.update(extras)
-    if args.workload != "predict8192":
-      leg = extras[args.workload]
-      out["headline_predict8192"] = {"value": out["value"], "unit": out["unit"],
-                                     "ms_per_step": out["ms_per_step"]}
-      out["metric"] = ("BASELINE config 5: 512 utterances n in [300,3000] d=256, ICASSP2018"
-                       if args.workload == "batch512" else
-                       "BASELINE config 4: AutoTune 16-value sweep, n=4096 d=256, GraphCut")
-      out["value"], out["unit"] = leg["value"], leg["unit"]
-      out["scaling"] = "strong"
-      out["higher_is_better"] = args.workload == "batch512"
-      out["config"]["workload"] = args.workload
+    select_workload(out, extras, args.workload)
     if world == 1 and not args.no_concurrent:
       out["concurrent_streams"] = concurrent_leg(_lib, cfg, x, args.steps)
       out["pipelined_uploads"] = pipelined_leg(_lib, handle, cfg, x, args.steps)

@@ -3,7 +3,7 @@
 # extras) once per variant library and repetition, interleaved
 cd $GRAFT_REPO_ROOT
 REPS=${1:-2}
-B="python bench.py --steps 30 --warmup 5 --no-extras --no-concurrent --no-cpu-baseline"
+B="python bench.py --full --steps 30 --warmup 5 --no-extras --no-concurrent --no-cpu-baseline"
 for rep in $(seq $REPS); do
   for lib in spectralcluster_amd/csrc/libspectralcluster_amd.so tests/probes/ab/lib_*.so; do
     SPECTRALCLUSTER_AMD_LIB=$PWD/$lib $B 2>/dev/null | python -c "

@@ -7,7 +7,7 @@ for mode in ${MODES:-cost count cost count}; do
   if [ $mode = count ]; then export SC_GROUP_EQUAL_COUNT=1; else unset SC_GROUP_EQUAL_COUNT; fi
   echo "== groups by $mode"
   GROUP_ONLY_PASSES=4 timeout 300 python tests/probes/group_only.py 16 2>&1 | tail -3
-  timeout 400 python bench.py --workload batch512 --no-cpu-baseline --no-concurrent 2>/dev/null | python -c "
+  timeout 400 python bench.py --full --workload batch512 --no-cpu-baseline --no-concurrent 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 b=d['batch512']

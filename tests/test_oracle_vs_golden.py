@@ -11,6 +11,19 @@ import spectral_oracle as so
 from conftest import golden
 
 
+def assert_same_spectrum(w, ref, idx=None):
+  """The reference's eigenvalues as another host reproduces them.  np.linalg.eig's last bits
+  depend on the host's BLAS kernels and thread count, not on the code (the goldens were written
+  on one host); what any host must meet is a small multiple of the backward-error bound of the
+  solve: |lambda - lambda_ref| <= 20 n eps max |lambda| for every value (observed across BLAS
+  kernel sets and thread counts: <= 9 n eps max |lambda| at n = 6, <= 0.1 n eps at n = 1000)."""
+  w = np.real(np.asarray(w))
+  got = w if idx is None else w[idx]
+  tol = 20 * w.size * np.finfo(np.float64).eps * np.max(np.abs(w))
+  err = np.max(np.abs(got - ref))
+  assert got.shape == np.shape(ref) and err <= tol, (err, tol)
+
+
 def test_affinity_known_answer():
   # reference tests/utils_test.py:10-15
   m = np.array([[3, 4], [-4, 3], [6, 8], [-3, -4]], dtype=np.float64)
@@ -91,7 +104,7 @@ def test_toy_stage_dump(lap):
   assert np.array_equal(dump["affinity"], g["affinity"])
   for i, st in enumerate(dump["stages"]):
     assert np.array_equal(st, g["stage%d" % i])
-  assert np.array_equal(dump["eigenvalues"], g["eigenvalues"])
+  assert_same_spectrum(dump["eigenvalues"], g["eigenvalues"])
   assert dump["n_clusters"] == int(g["n_clusters_raw"])  # (min_clusters is None here)
   assert np.array_equal(labels, g["labels"])
   assert np.array_equal(so.ordered_labels(labels), [0, 0, 1, 1, 0, 1])
@@ -107,9 +120,9 @@ def test_n64_stage_dump(lap):
     assert np.array_equal(st, g["stage%d" % i]), "stage %d" % i
   if lap == 4:
     assert np.array_equal(dump["laplacian"], g["laplacian"])
-  assert np.array_equal(dump["eigenvalues"], g["eigenvalues"])
+  assert_same_spectrum(dump["eigenvalues"], g["eigenvalues"])
   assert np.array_equal(labels, g["labels"])
-  assert dump["max_delta"] == float(g["max_delta"])
+  np.testing.assert_allclose(dump["max_delta"], float(g["max_delta"]), rtol=1e-9)
 
 
 def test_kmeans_vs_sklearn_and_reference():
@@ -138,8 +151,8 @@ def test_e2e_small(name):
   dump = {}
   labels = so.predict(so.blobs(n, d, k, seed), cfg, dump)
   assert np.array_equal(labels, g["labels"])
-  assert np.array_equal(dump["eigenvalues"][g["consumed_index"]], g["consumed_eigenvalues"])
-  assert dump["max_delta"] == float(g["max_delta"])
+  assert_same_spectrum(dump["eigenvalues"], g["consumed_eigenvalues"], g["consumed_index"])
+  np.testing.assert_allclose(dump["max_delta"], float(g["max_delta"]), rtol=1e-9)
 
 
 @pytest.mark.parametrize("name", ["manyk_n1500_k90_lap0_max120.npz",
@@ -157,8 +170,8 @@ def test_e2e_more_than_64_clusters(name):
   labels = so.predict(so.blobs(n, d, k, seed), cfg, dump)
   assert dump["n_clusters"] == int(g["n_clusters_raw"])
   assert np.array_equal(labels, g["labels"])
-  assert np.array_equal(dump["eigenvalues"][g["consumed_index"]], g["consumed_eigenvalues"])
-  assert dump["max_delta"] == float(g["max_delta"])
+  assert_same_spectrum(dump["eigenvalues"], g["consumed_eigenvalues"], g["consumed_index"])
+  np.testing.assert_allclose(dump["max_delta"], float(g["max_delta"]), rtol=1e-9)
 
 
 def test_autotune_small():
@@ -379,7 +392,7 @@ def test_hard_inputs_n1000(kind, lap):
   dump = {}
   labels = so.predict(x, cfg, dump)
   w = np.real(dump["eigenvalues"])
-  assert np.array_equal(w[g["consumed_index"]], g["consumed_eigenvalues"])
-  assert dump["max_delta"] == float(g["max_delta"])
+  assert_same_spectrum(w, g["consumed_eigenvalues"], g["consumed_index"])
+  np.testing.assert_allclose(dump["max_delta"], float(g["max_delta"]), rtol=1e-9)
   assert dump["n_clusters"] == max(int(g["n_clusters_raw"]), 2)
   assert np.array_equal(labels, g["labels"])

@@ -57,7 +57,7 @@ w = write[main][0] + (write[red][0] if red in write else 0.0)
 print(json.dumps({
     "kernel": what,
     "hbm_bytes_per_launch": int(f * 1024 * 2 + w * 1024),
-    "source": "%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of `bench.py --steps 3 "
+    "source": "%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of `bench.py --full --steps 3 "
               "--no-extras`, per-dispatch average over %d launches of %s at n=8192: FETCH_SIZE "
               "%.4g KiB x 2 (gfx950 16 B/lane correction) + WRITE_SIZE %.4g KiB"
               % (label, fetch[main][1], what, f, w),
