@@ -993,8 +993,11 @@ int gemm_resident_slots() {
   }
   return slots_dev[dev];
 }
+// The split-K partials of up to one wave of work units, then the 16 counters of the persistent
+// plan's work queue (k_gemm_queue_init; 64-byte aligned: the partials are whole tiles).
+constexpr int kQueueWords = 16;
 size_t gemm_splitk_workspace_bytes() {
-  return (size_t)gemm_resident_slots() * BM * BN * sizeof(double);
+  return (size_t)gemm_resident_slots() * BM * BN * sizeof(double) + kQueueWords * sizeof(int);
 }
 
 template <int EPI, bool SYM>
@@ -1012,7 +1015,10 @@ static void launch_variant(hipStream_t s, const double* A, int lda, const double
   const int tn = (N + BN - 1) / BN;
   const int tiles = SYM ? tm * (tm + 1) / 2 : tm * tn;
   const int g_slots = gemm_resident_slots();
-  double* g_partial = splitk_ws;  // per-handle scratch: handles may run concurrently
+  // Per-handle scratch, partials and queue counters alike: handles (streams, threads) may run
+  // concurrently on one device, and a queue shared between two launches in flight would be
+  // reset by the second one's k_gemm_queue_init while the first still draws from it.
+  double* g_partial = splitk_ws;
   const int ktiles = (K + BK - 1) / BK;
   // full waves of workgroups run whole tiles; the ragged remainder is split over K
   int full = (tiles / g_slots) * g_slots;
@@ -1041,6 +1047,8 @@ static void launch_variant(hipStream_t s, const double* A, int lda, const double
     // shader clock -- the GEMM is power-managed, see DESIGN_HISTORY.md section 3.3.  Any other value is
     // a file that also receives "workgroup cycles ticks start_tick ..." per tile
     // (tools/gemm_tile_timeline.py reads it).  Off: one pointer compare per workgroup.
+    // (The probe buffer is process-wide: a diagnostic for one launch at a time, never on in
+    //  production runs.  Concurrent probed launches would mix their records, not their results.)
     static double* dbg = nullptr;
     static const char* probe_env = getenv("SC_GEMM_CLOCK");
     if (probe_env != nullptr && dbg == nullptr) (void)hipMalloc(&dbg, sizeof(double) * 7 * 8192);
@@ -1049,15 +1057,11 @@ static void launch_variant(hipStream_t s, const double* A, int lda, const double
     // next tile per XCD, [9] next split unit) -- no teardown / dispatch between tiles.  With
     // K = 256 a tile is 16 K-tiles and the draw costs more than the dispatch it saves
     // (affinity GEMM 0.395 -> 0.417 ms): one workgroup per item by block index there.
-    static int* queue_buf[16] = {nullptr};
+    // (rem > 0 implies a workspace: the counters sit after its g_slots partial tiles)
     int* queue = nullptr;
     if (K >= 1024 && xcd_chunk > 0 && rem > 0 && SYM) {
-      int dev = 0;
-      hipGetDevice(&dev);
-      dev &= 15;
-      if (queue_buf[dev] == nullptr) (void)hipMalloc(&queue_buf[dev], 16 * sizeof(int));
-      queue = queue_buf[dev];
-      hipLaunchKernelGGL(k_gemm_queue_init, dim3(1), dim3(16), 0, s, queue);
+      queue = reinterpret_cast<int*>(splitk_ws + (size_t)g_slots * BM * BN);
+      hipLaunchKernelGGL(k_gemm_queue_init, dim3(1), dim3(kQueueWords), 0, s, queue);
     }
     const int persist = queue != nullptr ? 1 : 0;
     const int grid = persist ? std::min(g_slots, full + rem * ksplit) : full + rem * ksplit;
