@@ -718,7 +718,6 @@ int eig_ncluster_impl(sc_handle h, const sc_config* cfg, sc_diag* diag, FrontRes
   const bool fine = h->profile_level >= 2;
   int eb0 = -1, eb1 = -1, et0 = -1, et1 = -1;  // blur / threshold+symmetrize (last of each)
   h->n_mv_ev = 0;
-  h->free_on = false;
   bool free_path = false;
   const double* amax_of = nullptr;  // matrix whose max|a| h->fscal[0] bounds (matrix-free Diffuse)
   const double* digits_of = nullptr;  // ... whose digits the threshold pass has already written
@@ -738,16 +737,12 @@ int eig_ncluster_impl(sc_handle h, const sc_config* cfg, sc_diag* diag, FrontRes
     symmetric = resume->symmetric;
     folded_rownorm = resume->folded_rownorm;
     which = resume->scratch == bufs[0] ? 0 : 1;
-    if (resume->free_op) {
-      // the front left A, not S = A A^T (a matrix-free member of a batch group or sweep handed
-      // back by the lockstep solve): sym_topk has to apply it twice, and its first host sync
-      // looks at the rows the candidate search could not prune (h_free came back behind the
-      // group's statistics; free_group_end left free_checked false)
-      h->free_on = true;
-      h->free_lap = cfg->laplacian_type;
-      h->free_rownorm = resume->folded_rownorm ? 1 : 0;
-      h->free_checked = false;  // (the stage timers of the statistics belong to the front)
-    }
+    // resume->free_op: the front left A, not S = A A^T (a matrix-free member of a batch group
+    // handed back by the lockstep solve): sym_topk has to apply it twice, and its first host
+    // sync looks at the rows the candidate search could not prune (h_free came back behind the
+    // group's statistics; free_group_end left free_checked false).  (The stage timers of the
+    // statistics belong to the front.)
+    if (resume->free_op) h->free_checked = false;
   }
   for (int i = 0; i < (resume ? 0 : cfg->n_ops); ++i) {
     const int op = cfg->ops[i];
@@ -852,9 +847,6 @@ int eig_ncluster_impl(sc_handle h, const sc_config* cfg, sc_diag* diag, FrontRes
       // S V (the eigensolver).  `cur` stays the symmetric A; `out` stays free.
       SC_TRY(ensure_eig(h, n));
       SC_TRY(free_diffuse_stats(h, cur, ld, n, amax_of == cur, digits_of == cur));
-      h->free_on = true;
-      h->free_lap = cfg->laplacian_type;
-      h->free_rownorm = next == SC_OP_ROW_WISE_NORMALIZE ? 1 : 0;
       free_path = true;
       have_row_stats = true;
       have_partials = false;
@@ -912,7 +904,6 @@ int eig_ncluster_impl(sc_handle h, const sc_config* cfg, sc_diag* diag, FrontRes
   ev_rec(h, &e_after_refine);
   // ---- scaling vectors (RowWiseNormalize fold + Laplacian)
   bool flags_by_kernel = false;
-  h->chain_flags_clean = false;
   if (resume) {
     SC_TRY(ensure_eig(h, n));  // (scaling vectors and the finite-ness flag are resident)
   } else if (!symmetric) {
@@ -932,7 +923,6 @@ int eig_ncluster_impl(sc_handle h, const sc_config* cfg, sc_diag* diag, FrontRes
                            ptr<double>(h->pvec), ptr<double>(h->tvec), ptr<int>(h->flags),
                            h->affinity_from_embeddings ? ptr<int>(h->symflag) : nullptr);
     flags_by_kernel = true;
-    h->chain_flags_clean = true;
   }
   // a NaN / inf anywhere in the refined matrix (zero embedding rows, an all-zero refined row
   // under RowWiseNormalize, ...) reaches its row sums, hence c / p: np.linalg.eig raises on
@@ -964,12 +954,19 @@ int eig_ncluster_impl(sc_handle h, const sc_config* cfg, sc_diag* diag, FrontRes
   }
   int e_after_scaling;
   ev_rec(h, &e_after_scaling);
+  // the refined matrix, and the operator a symmetric solve of it works on
+  FrontResult op;
+  op.matrix = cur;
+  op.scratch = bufs[which];
+  op.ld = ld;
+  op.symmetric = symmetric;
+  op.folded_rownorm = folded_rownorm;
+  op.free_op = free_path || (resume && resume->free_op);
+  op.laplacian_type = cfg->laplacian_type;
+  op.chain_flags_cleared = flags_by_kernel;  // (never on a resume: the group solve ran the chain)
+  op.skip_fused = resume && resume->skip_fused;
   if (front_only) {
-    front_only->matrix = cur;
-    front_only->scratch = bufs[which];
-    front_only->ld = ld;
-    front_only->symmetric = symmetric;
-    front_only->folded_rownorm = folded_rownorm;
+    *front_only = op;
     return SC_OK;
   }
   // ---- eigen + eigengap
@@ -977,11 +974,7 @@ int eig_ncluster_impl(sc_handle h, const sc_config* cfg, sc_diag* diag, FrontRes
   EigDecision dc;
   std::vector<double> w;
   if (symmetric) {
-    // (free_on describes THIS solve's operator: it must not outlive it -- sc_stage_sym_eig and
-    //  every other caller of sym_topk on this handle would apply A twice to their matrix)
-    const int rc_eig = sym_topk(h, cur, ld, n, rq, diag, &dc, &w, bufs[which]);
-    h->free_on = false;
-    SC_TRY(rc_eig);
+    SC_TRY(sym_topk(h, op, n, rq, diag, &dc, &w));
   } else {
     rq.decision_aware = 1;
     SC_TRY(gen_topk(h, cur, ld, n, cfg->laplacian_type, rq, diag, &dc, &w, bufs[which]));
@@ -1278,7 +1271,7 @@ int predict_sequence(sc_handle h, const int* idx, int count, const double* const
     smallest = std::min(smallest, (size_t)ns[i] * d * sizeof(double));
   }
   if (nmax > 0) SC_TRY(sc_reserve(h, nmax, d));  // one arena sized for the largest member
-  if (count < 2 || smallest < ((size_t)256 << 10) || sw::no_prefetch()) {
+  if (count < 2 || smallest < ((size_t)256 << 10)) {
     for (int k = 0; k < count; ++k) {
       const int i = at(k);
       SC_TRY(sc_predict(h, xs[i], ns[i], d, cfg, labels[i], diags ? diags + i : nullptr));
@@ -1568,9 +1561,12 @@ extern "C" int sc_stage_sym_eig(sc_handle h, const double* m, int n, int count, 
   h->nev = 0;
   SC_TRY(ensure_eig(h, n));
   SC_HIP(h, hipMemsetAsync(ptr<int>(h->flags) + 12, 0, sizeof(int), h->stream));
-  h->free_on = false;  // (a stage call solves the matrix it is given)
-  SC_TRY(sym_topk(h, S, ld, n, rq, dg, &dc, &w,
-                  S == ptr<double>(h->B1) ? ptr<double>(h->B2) : ptr<double>(h->B1)));
+  FrontResult op;  // (the matrix it is given, no scaling: c = 1, p = 0)
+  op.matrix = S;
+  op.scratch = S == ptr<double>(h->B1) ? ptr<double>(h->B2) : ptr<double>(h->B1);
+  op.ld = ld;
+  op.symmetric = true;
+  SC_TRY(sym_topk(h, op, n, rq, dg, &dc, &w));
   SC_HIP(h, hipStreamSynchronize(h->stream));
   for (int i = 0; i < count; ++i) values[i] = w[i];
   if (vectors) {

@@ -99,10 +99,9 @@ int upload_embeddings(sc_handle h, const double* x, int n, int d) {
 struct Member {
   int index = -1;        // utterance
   sc_handle h = nullptr;
-  FrontResult front;
+  FrontResult front;      // (front.free_op: matrix-free Diffuse, front.matrix is A)
   int state = 0;         // 0 in the group, 1 single-call path, 2 done
   int k = 0;
-  bool free_op = false;  // matrix-free Diffuse: front.matrix is A, the solver applies it twice
 };
 
 // Stages before the eigensolver of one group, member after member, each on its member's
@@ -244,11 +243,12 @@ int enqueue_front_grouped(sc_handle lead, const double* const* xs, const int* ns
     m.front.folded_rownorm = true;
     // Large members take the matrix-free Diffuse (free_api.hip): their n^3 product is most of
     // a batch's GEMM time (78 % of config 5's Diffuse flops sit in utterances of n >= 2048;
-    // members switch from n = 1536 on: free_diffuse_wanted)
-    m.free_op = free_diffuse_wanted(lead, cfg, n, make_eig_request(cfg), true) &&
-                cfg->soft_multiplier >= 0.0 && cfg->soft_multiplier <= 1.0 &&
-                cfg->p_percentile > 0.0;
-    if (m.free_op) {
+    // members switch from n = 1536 on: free_diffuse_wanted).  (A hand-back resumes on the
+    // two-pass operator: api.hip.)
+    m.front.free_op = free_diffuse_wanted(lead, cfg, n, make_eig_request(cfg), true) &&
+                      cfg->soft_multiplier >= 0.0 && cfg->soft_multiplier <= 1.0 &&
+                      cfg->p_percentile > 0.0;
+    if (m.front.free_op) {
       rc = ensure_free(h, n);
       if (rc != SC_OK) {
         lead->err = h->err;
@@ -257,7 +257,6 @@ int enqueue_front_grouped(sc_handle lead, const double* const* xs, const int* ns
       dif[z].n = 0;          // idle in the grouped fp64 product
       m.front.matrix = f.B2;  // the thresholded + symmetrised A stays the operand
       m.front.scratch = f.B1;
-      m.front.free_op = true;  // (a hand-back resumes on the two-pass operator: api.hip)
     }
   }
   launch_front_begin_group(s, fi, count, true);
@@ -274,7 +273,7 @@ int enqueue_front_grouped(sc_handle lead, const double* const* xs, const int* ns
   int nn[kGroupMax], ll[kGroupMax], nf = 0, fz[kGroupMax];
   FreeItem fitems[kGroupMax];
   for (int z = 0; z < count; ++z) {
-    if (!mb[z].free_op) continue;
+    if (!mb[z].front.free_op) continue;
     sc_handle h = mb[z].h;
     fh[nf] = h;
     fz[nf] = z;
@@ -285,13 +284,12 @@ int enqueue_front_grouped(sc_handle lead, const double* const* xs, const int* ns
     ll[nf] = h->ldn;
     ++nf;
   }
-  const double amax_floor = (cfg->binarize || cfg->preserve_diagonal) ? 1.0 : 0.0;
-  const bool fused_digits = nf > 0 && !sw::group_quantize_pass();
-  if (fused_digits) {
+  if (nf > 0) {
     // (the cuts first -- max|a| comes from them --, then the begin step, then the pass itself)
     launch_cut_from_partials_group(s, fi, count, cfg->p_percentile);
     TsDigits packed[kGroupMax], digits[kGroupMax];
     memset(digits, 0, sizeof(digits));
+    const double amax_floor = (cfg->binarize || cfg->preserve_diagonal) ? 1.0 : 0.0;
     SC_TRY(free_group_prepare(fh, mats, cuts, ps, nf, ll, nn, s, amax_floor, fitems, packed));
     for (int q = 0; q < nf; ++q) digits[fz[q]] = packed[q];
     launch_threshold_symmetrize_group(s, fi, count, cfg->p_percentile, cfg->soft_multiplier,
@@ -302,29 +300,24 @@ int enqueue_front_grouped(sc_handle lead, const double* const* xs, const int* ns
                                       cfg->binarize, cfg->symmetrize_type, cfg->preserve_diagonal);
   }
   launch_gemm_nt_group(s, dif, count, kEpiNone, 1);
-  {
-    if (nf > 0) {
-      if (fused_digits)
-        SC_TRY(free_group_digits(fh, fitems, nf, s));
-      else
-        SC_TRY(free_group_begin(fh, mats, cuts, ps, nf, ll, nn, s, amax_floor, fitems));
-      {  // the digit products of all of them: one launch (blockIdx.y = member)
-        const signed char* qs[kGroupMax];
-        float* ts[kGroupMax];
-        unsigned* ms[kGroupMax];
-        const int2* tms[kGroupMax];
-        const int* pls[kGroupMax];
-        for (int q = 0; q < nf; ++q) {
-          qs[q] = ptr<signed char>(fh[q]->fq);
-          ts[q] = ptr<float>(fh[q]->ft32);
-          ms[q] = ptr<unsigned>(fh[q]->fwords);
-          tms[q] = fh[q]->tilemap_cur;
-          pls[q] = fitems[q].plan;
-        }
-        launch_gemm_i8_sym_group(s, qs, ts, ms, nf, nn, tms, pls);
+  if (nf > 0) {
+    SC_TRY(free_group_digits(fh, fitems, nf, s));
+    {  // the digit products of all of them: one launch (blockIdx.y = member)
+      const signed char* qs[kGroupMax];
+      float* ts[kGroupMax];
+      unsigned* ms[kGroupMax];
+      const int2* tms[kGroupMax];
+      const int* pls[kGroupMax];
+      for (int q = 0; q < nf; ++q) {
+        qs[q] = ptr<signed char>(fh[q]->fq);
+        ts[q] = ptr<float>(fh[q]->ft32);
+        ms[q] = ptr<unsigned>(fh[q]->fwords);
+        tms[q] = fh[q]->tilemap_cur;
+        pls[q] = fitems[q].plan;
       }
-      SC_TRY(free_group_end(fh, fitems, nf, s));
+      launch_gemm_i8_sym_group(s, qs, ts, ms, nf, nn, tms, pls);
     }
+    SC_TRY(free_group_end(fh, fitems, nf, s));
   }
   launch_scaling_vectors_group(s, fi, count, cfg->laplacian_type, 1);
   SC_TRY(check_last(lead, "grouped front launch"));
@@ -354,7 +347,7 @@ int finish_group(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* c
     em[ne].ld = mb[z].front.ld;
     em[ne].n = ns[mb[z].index];
     em[ne].rq = rq;
-    em[ne].free_op = mb[z].free_op;
+    em[ne].free_op = mb[z].front.free_op;
     emz[ne++] = z;
   }
   if (ne > 0) SC_TRY(sym_topk_group(lead, em, ne));
@@ -395,6 +388,7 @@ int finish_group(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* c
     Member& m = mb[emz[e]];
     if (em[e].status != 0) {
       m.state = 1;
+      m.front.skip_fused = em[e].skip_fused;  // (what the resumed single-call solve starts from)
       continue;
     }
     sc_handle h = m.h;
@@ -426,7 +420,7 @@ int finish_group(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* c
       dg->eig_basis = em[e].basis;
       dg->eig_max_residual = em[e].dc.max_resid;
       dg->n_clusters = k;
-      if (m.free_op) {
+      if (m.front.free_op) {
         dg->diffuse_path = SC_DIFFUSE_PATH_FREE;
         dg->free_candidates = h->h_free[65];
         dg->free_tiles_run = h->h_free[67];
@@ -703,15 +697,15 @@ extern "C" int sc_predict_batch_grouped(sc_handle h, const double* const* xs, co
     // where the running cost passes total / G (at most `group` members), G a multiple of the lane
     // count with at least two groups per lane (a lane overlaps the front of its next group with
     // the chains of the current one), and the groups go to the lanes longest-first, each to the
-    // least loaded lane.  SC_GROUP_EQUAL_COUNT=1: round 5's slicing (A/B, profiles/r27).
+    // least loaded lane.  (Round 5's groups of equal count dealt round-robin: the A/B is
+    // profiles/r27.)
     auto unit_cost = [&](int i) { const double n = ns[i]; return 60.0 + 3.5e-5 * n * n; };
     std::vector<int> gstart;
     int width = std::min(group, (int)grouped.size());
-    const bool equal_count = sw::group_equal_count();
     const int min_groups = ((int)grouped.size() + width - 1) / width;
     const int lanes_wanted = std::max(
         1, std::min(kGroupLanes, grouped_front_covers(cfg) ? min_groups / kGroupBanks : 1));
-    if (equal_count || min_groups < 2) {
+    if (min_groups < 2) {
       for (int at = 0; at < (int)grouped.size(); at += width) gstart.push_back(at);
     } else {
       double total = 0.0;
@@ -751,9 +745,7 @@ extern "C" int sc_predict_batch_grouped(sc_handle h, const double* const* xs, co
     const int lanes =
         std::max(1, std::min(kGroupLanes, grouped_front_covers(cfg) ? ngroups / kGroupBanks : 1));
     std::vector<int> lane_groups[kGroupLanes];
-    if (equal_count) {
-      for (int g = 0; g < ngroups; ++g) lane_groups[g % lanes].push_back(g);
-    } else {  // longest group first, each to the least loaded lane (ties: the lower lane)
+    {  // longest group first, each to the least loaded lane (ties: the lower lane)
       std::vector<double> gcost(ngroups, 0.0);
       for (int g = 0; g < ngroups; ++g)
         for (int at = gstart[g]; at < gstart[g + 1]; ++at) gcost[g] += unit_cost(grouped[at]);
@@ -816,7 +808,7 @@ extern "C" int sc_predict_batch_grouped(sc_handle h, const double* const* xs, co
           return;
         }
         rcs[l] = run_group_lane(leads[l], xs, ns, d, cfg, labels, diags, grouped, gstart, width,
-                                lane_groups[l], rq, equal_count ? 0 : group);
+                                lane_groups[l], rq, group);
       };
       try {
         side.emplace_back(body);
@@ -825,11 +817,11 @@ extern "C" int sc_predict_batch_grouped(sc_handle h, const double* const* xs, co
       }
     }
     rcs[0] = run_group_lane(h, xs, ns, d, cfg, labels, diags, grouped, gstart, width,
-                            lane_groups[0], rq, equal_count ? 0 : group);
+                            lane_groups[0], rq, group);
     for (int l = 1; l < lanes; ++l)
       if (inline_lane[l])
         rcs[l] = run_group_lane(leads[l], xs, ns, d, cfg, labels, diags, grouped, gstart, width,
-                                lane_groups[l], rq, equal_count ? 0 : group);
+                                lane_groups[l], rq, group);
     for (auto& t : side) t.join();
     {  // member arenas that hold a large share of the device do not outlive the batch (the
        // lanes keep up to 3 x 2 x 16 of them warm otherwise: 21 GB after config 5)
@@ -1034,10 +1026,10 @@ extern "C" int sc_eig_ncluster_sweep(sc_handle h, const sc_config* cfg, const do
       }
     }
     // (round 6: with max|a| known from the cuts the threshold pass writes the members' digits
-    //  itself -- free_group_prepare / free_group_digits, free_api.hip)
+    //  itself -- free_group_prepare / free_group_digits, free_api.hip; amax_from_cut implies
+    //  icassp and free_route)
     FreeItem fitems[kGroupMax];
-    const bool fused_digits = icassp && free_route && amax_from_cut && !sw::group_quantize_pass();
-    if (fused_digits) {
+    if (amax_from_cut) {
       sc_handle fh0[kGroupMax];
       const double* mats[kGroupMax];
       const double* cuts[kGroupMax];
@@ -1073,22 +1065,8 @@ extern "C" int sc_eig_ncluster_sweep(sc_handle h, const sc_config* cfg, const do
       unsigned* ms[kGroupMax];
       sc_handle fh[kGroupMax];
       for (int z = 0; z < cnt; ++z) fh[z] = em[z].h;
-      if (fused_digits) {
+      if (amax_from_cut) {
         SC_TRY(free_group_digits(fh, fitems, cnt, s));
-      } else if (amax_from_cut) {
-        // begin, quantiser, scan and statistics of all members: one launch each
-        const double* mats[kGroupMax];
-        const double* cuts[kGroupMax];
-        for (int z = 0; z < cnt; ++z) {
-          mats[z] = em[z].S;
-          cuts[z] = ptr<double>(em[z].h->cut);
-        }
-        int nn[kGroupMax], ll[kGroupMax];
-        for (int z = 0; z < cnt; ++z) { nn[z] = n; ll[z] = ld; }
-        // (floor 1 when the pass writes ones: the same expression as the single call and the
-        //  grouped batch front; grouped_front_covers() has excluded a preserved diagonal)
-        SC_TRY(free_group_begin(fh, mats, cuts, p_values + base, cnt, ll, nn, s,
-                                (cfg->binarize || cfg->preserve_diagonal) ? 1.0 : 0.0, fitems));
       } else {
         for (int z = 0; z < cnt; ++z) SC_TRY(free_stats_begin(em[z].h, s, em[z].S, ld, n, false));
       }
@@ -1137,7 +1115,6 @@ extern "C" int sc_eig_ncluster_sweep(sc_handle h, const sc_config* cfg, const do
       if (em[z].status == 0) h->sweep_slot[base + z] = z;
       if (em[z].status != 0) {
         later.push_back(base + z);  // (after the rounds: it overwrites the shared blur)
-        em[z].h->eig_skip_fused = false;  // (a hint for a re-solve on that arena: none follows)
         continue;
       }
       memset(dg, 0, sizeof(*dg));

@@ -341,13 +341,6 @@ __global__ __launch_bounds__(256) void k_free_quantize(
     unsigned long long* __restrict__ rmax_bits, double* __restrict__ q2part) {
   free_quantize_body<PROBE>(A, n, ld, Q, pitch, Kp, scal, y1, R, rmax_bits, q2part);
 }
-__global__ __launch_bounds__(256) void k_free_quantize_g(const GroupOf<FreeItem> g) {
-  const FreeItem& a = g.s[blockIdx.y];
-  if (a.n <= 0 || (int)blockIdx.x >= (a.n + 127) / 128 * 128) return;  // rows padded to a product tile
-  const int Kp = (a.n + 63) / 64 * 64;
-  free_quantize_body<0>(a.A, a.n, a.ld, a.Q, (size_t)2 * Kp, Kp, a.scal, a.y1, a.R,
-                        reinterpret_cast<unsigned long long*>(a.scal) + 2, a.q2part);
-}
 
 // ---------------------------------------------------------------- tile skip list
 // Most 128 x 128 tiles of T = Q Q^T cannot hold a row maximum or a candidate, and a bound that
@@ -395,14 +388,6 @@ __device__ __forceinline__ void free_seg_reduce_body(const double* __restrict__ 
 __global__ __launch_bounds__(256) void k_free_seg_reduce(const double* __restrict__ R, int n,
                                                          int nblk, const FreeSegs segs) {
   free_seg_reduce_body(R, n, nblk, segs);
-}
-// segment maxima + tile flags of every member of a group: workgroups [0, nblk) of a member do
-// the former ... (two launches: the flags read what ALL of a member's segment workgroups wrote)
-__global__ __launch_bounds__(256) void k_free_seg_reduce_g(const GroupOf<FreeItem> g) {
-  const FreeItem& a = g.s[blockIdx.y];
-  const int nblk = (a.n + 63) / 64;
-  if (a.n <= 0 || a.plan == nullptr || (int)blockIdx.x >= nblk) return;
-  free_seg_reduce_body(a.R, a.n, nblk, FreeSegs{a.q2part, a.mx64, a.tau64});
 }
 
 // One workgroup per tile row I: plan[I] = number of surviving tiles (I, J >= I), their columns in
@@ -1304,21 +1289,10 @@ void launch_free_begin_group(hipStream_t s, const FreeItem* items, int count, do
   hipLaunchKernelGGL(k_free_begin_g, dim3(1 + (nwords + 1023) / 1024 + (pad_rows ? 32 : 0), count),
                      dim3(256), 0, s, g, floor_value, pad_rows ? 1 : 0);
 }
-void launch_free_quantize_group(hipStream_t s, const FreeItem* items, int count) {
+void launch_free_tile_flags_group(hipStream_t s, const FreeItem* items, int count, bool prune) {
   int nmax;
   const GroupOf<FreeItem> g = free_pack(items, count, &nmax);
   if (nmax == 0) return;
-  SC_OPT_IN_LDS(k_free_quantize_g, 2 * 65536);
-  hipLaunchKernelGGL(k_free_quantize_g, dim3(free_rows_padded(nmax), count), dim3(256),
-                     (size_t)2 * free_k_padded(nmax), s, g);
-}
-void launch_free_tile_flags_group(hipStream_t s, const FreeItem* items, int count, bool prune,
-                                  bool seg_reduce) {
-  int nmax;
-  const GroupOf<FreeItem> g = free_pack(items, count, &nmax);
-  if (nmax == 0) return;
-  if (seg_reduce)
-    hipLaunchKernelGGL(k_free_seg_reduce_g, dim3(free_k_padded(nmax) / 64, count), dim3(256), 0, s, g);
   hipLaunchKernelGGL(k_free_tile_flags_g, dim3((nmax + kI8Tile - 1) / kI8Tile, count),
                      dim3(kFlagThreads), 0, s, g, prune ? 1 : 0);
 }

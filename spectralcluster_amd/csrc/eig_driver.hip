@@ -119,20 +119,15 @@ static EigDecision analyze(const EigRequest& rq, const double* theta, const doub
   const bool aware = rq.decision_aware && rq.fixed_count == 0;
   const int kb = dc.n_clusters_raw;  // the maximum gap sits between w[kb - 1] and w[kb]
   for (int i = first; i <= last; ++i) {
-    const bool decisive = !aware || i == kb - 1 || i == kb ||
-                          (rq.eigengap_type == SC_EIGENGAP_NORMALIZED_DIFF && rq.descend && i == 0);
     // (round 6: EVERY consumed value is held to value_tol -- the parity bar is on all of them.
-    //  Rounds 3-5 held the non-decisive ones to 1e-3 only; SC_GEN_LOOSE_BULK=1 brings that
-    //  back for the pass-count A/B of profiles/r18.  Decision-awareness survives as the
-    //  ADDITIONAL interval proof below.)
-    const double rel = (decisive || !sw::gen_loose_bulk()) ? rq.value_tol
-                                                            : std::max(rq.value_tol, 1e-3);
-    const double tol = std::max(rel * std::fabs(w[i]), floor_abs);
+    //  Rounds 3-5 held the ones that cannot move the decision to 1e-3 only: the pass-count A/B
+    //  is profiles/r18.  Decision-awareness survives as the ADDITIONAL interval proof below.)
+    const double tol = std::max(rq.value_tol * std::fabs(w[i]), floor_abs);
     // (the proven part: the residual itself within the parity bar of 1e-5 -- the Kato-Temple
     //  estimate may accept a residual above `tol`, never one above this)
     //  (measured, profiles/r07b_passes_probe.txt: 2176 instead of 2115 block passes on config 5's
     //  512 utterances, +2.9 %, throughput inside the run-to-run spread; none on configs 3 and 4)
-    const double cap = std::max(std::max(rel, 1e-5) * std::fabs(w[i]), floor_abs);
+    const double cap = std::max(std::max(rq.value_tol, 1e-5) * std::fabs(w[i]), floor_abs);
     if (!(value_error_bound(theta, resid, m, i, symmetric_op) <= tol) || !(resid[i] <= cap)) {
       if (ok) { dc.fail_kind = 1; dc.fail_index = i; }
       ok = false;
@@ -296,16 +291,16 @@ static bool host_rayleigh_ritz_leading(const double* T, int ld, const double* G,
 }
 
 // One CholQR pass on W (n x 8) with the orthonormality-defect flag of its input armed
-// (flags[10]); stores the result into Q[:, store_col ...] and Vs when store_col >= 0.
-static int cholqr_pass(sc_handle h, int n, int store_col) {
+// (flags[10]); stores the result into Q[:, store_col ...] and Vs = vs_scale .* result when
+// store_col >= 0 (vs_scale: cvec, the general path's cr).
+static int cholqr_pass(sc_handle h, int n, int store_col, const double* vs_scale) {
   hipStream_t s = h->stream;
   double* W = ptr<double>(h->W);
   launch_proj_partial(s, W, kEigBlock, kEigBlock, W, n, ptr<double>(h->partial));
   launch_reduce_chol(s, ptr<double>(h->partial), proj_blocks(n), ptr<double>(h->Rinv), nullptr,
                      nullptr, ptr<int>(h->flags), ptr<int>(h->flags) + 10, 2);
   launch_apply_rinv(s, W, n, ptr<double>(h->Rinv), store_col >= 0 ? ptr<double>(h->Q) : nullptr,
-                    kLdq, store_col >= 0 ? store_col : 0,
-                    h->vs_scale ? h->vs_scale : ptr<double>(h->cvec), ptr<double>(h->Vs));
+                    kLdq, store_col >= 0 ? store_col : 0, vs_scale, ptr<double>(h->Vs));
   return SC_OK;
 }
 
@@ -313,9 +308,9 @@ static const char kNonFiniteMessage[] = "Array must not contain infs or NaNs";
 
 // Orthonormalise W (n x 16) against Q[:, 0:m] and within itself.
 //   record: accumulate the projection coefficients into T columns [col0, col0+16)
-//   store_col: column of Q to receive the result (< 0: do not store)
+//   store_col: column of Q to receive the result (< 0: do not store), Vs = vs_scale .* result
 static int orthonormalize(sc_handle h, int n, int m, bool record, int col0, int store_col,
-                          bool save_gram) {
+                          bool save_gram, const double* vs_scale) {
   hipStream_t s = h->stream;
   double* Q = ptr<double>(h->Q);
   double* W = ptr<double>(h->W);
@@ -336,7 +331,7 @@ static int orthonormalize(sc_handle h, int n, int m, bool record, int col0, int 
                      save_gram ? ptr<double>(h->G) : nullptr, hsq, ptr<int>(h->flags),
                      ptr<int>(h->flags) + 11, 1);
   launch_apply_rinv(s, W, n, ptr<double>(h->Rinv), nullptr, 0, 0, nullptr, nullptr);
-  SC_TRY(cholqr_pass(h, n, store_col));
+  SC_TRY(cholqr_pass(h, n, store_col, vs_scale));
   return check_last(h, "orthonormalize launch");
 }
 
@@ -358,7 +353,8 @@ static int read_flags(sc_handle h, int* mask) {
 
 // Make sure the block in W is a full-rank orthonormal block; repairs dependent
 // columns with random vectors (bounded retries).
-static int finish_block(sc_handle h, int n, int m, int store_col, uint64_t* seed) {
+static int finish_block(sc_handle h, int n, int m, int store_col, const double* vs_scale,
+                        uint64_t* seed) {
   for (int attempt = 0; attempt < 4; ++attempt) {
     int mask = 0;
     SC_TRY(read_flags(h, &mask));
@@ -368,12 +364,12 @@ static int finish_block(sc_handle h, int n, int m, int store_col, uint64_t* seed
          extra < 3 && mask == 0 && (h->h_flags[10] != 0 || h->h_flags[11] != 0); ++extra) {
       // (the projection coefficients already recorded in T stay: this round only removes
       // rounding-level components)
-      SC_TRY(orthonormalize(h, n, m, false, 0, store_col, false));
+      SC_TRY(orthonormalize(h, n, m, false, 0, store_col, false, vs_scale));
       SC_TRY(read_flags(h, &mask));
     }
     if (mask == 0) return SC_OK;
     launch_refill_deficient(h->stream, ptr<double>(h->W), n, ptr<int>(h->flags), ++(*seed));
-    SC_TRY(orthonormalize(h, n, m, false, 0, store_col, false));
+    SC_TRY(orthonormalize(h, n, m, false, 0, store_col, false, vs_scale));
   }
   return fail(h, SC_ERR_NOT_CONVERGED, "could not build a full-rank Krylov block");
 }
@@ -477,55 +473,49 @@ static EigWorkspace eig_workspace(sc_handle h) {
   return ws;
 }
 
-// S (n x n, ld) symmetric on the device; cvec/pvec/tvec already set.
-// With h->free_on (matrix-free Diffuse, free_api.hip) `S_in` is the symmetric matrix A BEFORE
+// op.matrix (n x n, op.ld) symmetric on the device; cvec/pvec/tvec already set.
+// With op.free_op (matrix-free Diffuse, free_api.hip) op.matrix is the symmetric matrix A BEFORE
 // Diffuse and the operator is diag(p) + diag(c) A A diag(c): two block products per pass,
 // S = A A^T is only formed if a dense route needs its entries.
-int sym_topk(sc_handle h, const double* S_in, int ld, int n, const EigRequest& rq_in,
-             sc_diag* diag, EigDecision* out_dc, std::vector<double>* out_w,
-             double* scratch_in) {
+int sym_topk(sc_handle h, const FrontResult& op_in, int n, const EigRequest& rq_in,
+             sc_diag* diag, EigDecision* out_dc, std::vector<double>* out_w) {
   hipStream_t s = h->stream;
   SC_TRY(ensure_eig(h, n));
-  const double* S = S_in;
-  double* scratch = scratch_in;
-  const bool free_at_entry = h->free_on;
-  // (set by eig_ncluster_impl when its scaling kernel has just cleared flags[13..15]; consumed
-  //  here whatever route this solve takes, so that it never outlives the call it was set for)
-  bool chain_flags_clean = h->chain_flags_clean;
-  h->chain_flags_clean = false;
+  FrontResult op = op_in;  // (free_materialize turns it into the explicit operator)
+  const int ld = op.ld;
   // S = A A^T after all (a dense route reads entries; or the exact-row route gave up): the fp64
   // MFMA product into the scratch matrix, A's buffer becomes the scratch
   auto free_materialize = [&](bool with_stats) -> int {
-    if (!h->free_on) return SC_OK;
-    if (scratch == nullptr || scratch == S)
+    if (!op.free_op) return SC_OK;
+    if (op.scratch == nullptr || op.scratch == op.matrix)
       return fail(h, SC_ERR_UNSUPPORTED, "no scratch matrix to form the Diffuse product in");
     SC_TRY(ensure_tilemap(h, n));
     GemmRowStats rs{1, ptr<double>(h->statp), ptr<double>(h->statp) + (size_t)n * gemm_tile_dim(n),
                     ptr<double>(h->rowmax), ptr<double>(h->rowsum)};
-    launch_gemm_nt(s, S, ld, S, ld, scratch, ld, n, n, n, kEpiNone, true, ptr<double>(h->splitk),
-                   h->tilemap_cur, with_stats ? &rs : nullptr);
+    launch_gemm_nt(s, op.matrix, ld, op.matrix, ld, op.scratch, ld, n, n, n, kEpiNone, true,
+                   ptr<double>(h->splitk), h->tilemap_cur, with_stats ? &rs : nullptr);
     SC_TRY(check_last(h, "diffuse launch"));
-    double* a_buffer = const_cast<double*>(S);
-    S = scratch;
-    scratch = a_buffer;
-    h->free_on = false;
+    double* a_buffer = const_cast<double*>(op.matrix);
+    op.matrix = op.scratch;
+    op.scratch = a_buffer;
+    op.free_op = false;
     return SC_OK;
   };
   // rows whose candidate list overflowed are evaluated in full once the stream has drained;
   // *restart: the scaling vectors changed under a solve that had already started
   auto free_check = [&](bool* restart) -> int {
     *restart = false;
-    if (!h->free_on || h->free_checked) return SC_OK;
+    if (!op.free_op || h->free_checked) return SC_OK;
     bool changed = false, too_many = false;
-    SC_TRY(free_fix_overflow(h, S, ld, n, &changed, &too_many));
+    SC_TRY(free_fix_overflow(h, op.matrix, ld, n, &changed, &too_many));
     if (too_many) {
       SC_TRY(free_materialize(true));
       changed = true;
     }
     if (changed) {
-      launch_scaling_vectors(s, ptr<double>(h->rowmax), ptr<double>(h->rowsum), n, h->free_lap,
-                             h->free_rownorm, ptr<double>(h->cvec), ptr<double>(h->pvec),
-                             ptr<double>(h->tvec));
+      launch_scaling_vectors(s, ptr<double>(h->rowmax), ptr<double>(h->rowsum), n,
+                             op.laplacian_type, op.folded_rownorm ? 1 : 0, ptr<double>(h->cvec),
+                             ptr<double>(h->pvec), ptr<double>(h->tvec));
       launch_check_finite(s, ptr<double>(h->cvec), ptr<double>(h->pvec), n, ptr<int>(h->flags) + 12);
       SC_TRY(check_last(h, "scaling launch"));
       *restart = true;
@@ -539,9 +529,8 @@ int sym_topk(sc_handle h, const double* S_in, int ld, int n, const EigRequest& r
   EigDecision dc;
   int m = 0, passes = 0, cycles = 0;
   EigRequest rq = rq_in;
-  // (eig_skip_fused: the lockstep group solve saw this problem latch the fused chain)
-  bool fused = !sw::eig_host_chain() && !h->eig_skip_fused;
-  h->eig_skip_fused = false;
+  // (skip_fused: the lockstep group solve saw this problem latch the fused chain)
+  bool fused = !sw::eig_host_chain() && !op.skip_fused;
   bool three_pass = false;  // second attempt of the fused chain, see LzChain::three_pass
   // upper-triangle matvec once the matrix no longer fits the caches (below that the full
   // read is served on-die and the second launch costs more than it saves)
@@ -555,7 +544,7 @@ int sym_topk(sc_handle h, const double* S_in, int ld, int n, const EigRequest& r
     bool unused = false;
     SC_TRY(free_check(&unused));
     SC_TRY(free_materialize(false));
-    SC_TRY(dense_spectrum(h, S, ld, n, scratch));
+    SC_TRY(dense_spectrum(h, op.matrix, ld, n, op.scratch));
     std::vector<double> zeros(n, 0.0);
     dense_dc = analyze(rq_in, h->spectrum.data(), zeros.data(), n, n, true);
     if (!dense_dc.enough) return fail(h, SC_ERR_UNSUPPORTED, "eigen request cannot be satisfied");
@@ -576,7 +565,7 @@ int sym_topk(sc_handle h, const double* S_in, int ld, int n, const EigRequest& r
   bool vectors_from_dense = false;
   int fallback_reason = 0;
   auto dense_fallback = [&](int reason) -> int {
-    if (scratch == nullptr || scratch == S)
+    if (op.scratch == nullptr || op.scratch == op.matrix)
       return fail(h, SC_ERR_NOT_CONVERGED,
                   "block Lanczos did not converge and no scratch matrix is free for the dense path");
     if (sw::eig_trace())
@@ -588,7 +577,7 @@ int sym_topk(sc_handle h, const double* S_in, int ld, int n, const EigRequest& r
     if (rq_in.fixed_count > 0 || rq_in.max_clusters > 0)
       cols = std::max(std::min(dense_dc.kw, kMaxVectors), cols);
     cols = std::max(1, cols);
-    SC_TRY(dense_vectors(h, scratch, ld, n, cols));
+    SC_TRY(dense_vectors(h, op.scratch, ld, n, cols));
     vectors_from_dense = true;
     fallback_reason = reason;
     return SC_OK;
@@ -596,7 +585,7 @@ int sym_topk(sc_handle h, const double* S_in, int ld, int n, const EigRequest& r
 
   if (n <= kDenseMax) {
     // ---- direct dense path: every eigenpair, one Jacobi launch
-    launch_jacobi(s, S, ld, n, 1, cvec, pvec, nullptr, theta_d, ptr<double>(h->Y), kLdq,
+    launch_jacobi(s, op.matrix, ld, n, 1, cvec, pvec, nullptr, theta_d, ptr<double>(h->Y), kLdq,
                   nullptr, ptr<double>(h->Yt), ptr<int>(h->flags));
     SC_TRY(check_last(h, "jacobi launch"));
     SC_HIP(h, hipMemcpyAsync(h->h_theta, theta_d, n * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -621,7 +610,6 @@ int sym_topk(sc_handle h, const double* S_in, int ld, int n, const EigRequest& r
     cycles = 0;
     bool done = false;
     uint64_t seed = 0x5eed5eedull;
-    const double* vscale = h->vs_scale ? h->vs_scale : cvec;
     LzChain chain;
     if (dense && many_vectors) {
       // the full spectrum is known and more than 64 vectors are wanted: all of them from the
@@ -634,21 +622,21 @@ int sym_topk(sc_handle h, const double* S_in, int ld, int n, const EigRequest& r
     } else if (fused) {
       // fused chain (k_lz_step): no host synchronisation until the first Rayleigh-Ritz
       // (the first start of a call: the scaling kernel has just cleared them, api.hip)
-      if (!chain_flags_clean)
+      if (!op.chain_flags_cleared)
         SC_HIP(h, hipMemsetAsync(ptr<int>(h->flags) + 13, 0, 3 * sizeof(int), s));
-      chain_flags_clean = false;
+      op.chain_flags_cleared = false;
       const EigWorkspace ws = eig_workspace(h);
       chain = LzChain();
       chain.three_pass = three_pass;
       // random block + its Gram | CholQR | CholQR again (Gram checked against I) + store
-      launch_lz_link(s, ws, &chain, n, 0, 0, 4, -1, vscale, 0, true, seed, false);
-      launch_lz_link(s, ws, &chain, n, 0, 4, 3, -1, vscale, 0, false, 0, true);
-      launch_lz_link(s, ws, &chain, n, 0, 3, 0, 0, vscale, 0, false, 0, false);
+      launch_lz_link(s, ws, &chain, n, 0, 0, 4, -1, cvec, 0, true, seed, false);
+      launch_lz_link(s, ws, &chain, n, 0, 4, 3, -1, cvec, 0, false, 0, true);
+      launch_lz_link(s, ws, &chain, n, 0, 3, 0, 0, cvec, 0, false, 0, false);
       SC_TRY(check_last(h, "start block launch"));
     } else {
       launch_random_block(s, ptr<double>(h->W), n, seed);
-      SC_TRY(orthonormalize(h, n, 0, false, 0, 0, false));
-      const int rc0 = finish_block(h, n, 0, 0, &seed);
+      SC_TRY(orthonormalize(h, n, 0, false, 0, 0, false, cvec));
+      const int rc0 = finish_block(h, n, 0, 0, cvec, &seed);
       if (rc0 == SC_ERR_NOT_CONVERGED) {
         SC_TRY(dense_fallback(3));
         done = true;
@@ -681,13 +669,13 @@ int sym_topk(sc_handle h, const double* S_in, int ld, int n, const EigRequest& r
     auto enqueue_step = [&](int m_before) -> int {
       const bool time_mv = h->profile_level >= 2 && h->n_mv_ev < 16;
       if (time_mv) ev_rec(h, &h->mv_ev[h->n_mv_ev][0]);
-      if (h->free_on)
-        free_apply_operator(h, S, ld, n, sym_mv, ptr<double>(h->Q) + m_before, kLdq);
+      if (op.free_op)
+        free_apply_operator(h, op.matrix, ld, n, sym_mv, ptr<double>(h->Q) + m_before, kLdq);
       else if (sym_mv)
-        launch_block_matvec_sym(s, S, ld, n, cvec, pvec, ptr<double>(h->Q) + m_before, kLdq,
+        launch_block_matvec_sym(s, op.matrix, ld, n, cvec, pvec, ptr<double>(h->Q) + m_before, kLdq,
                                 ptr<double>(h->Vs), ptr<double>(h->W), ptr<double>(h->mvsym));
       else
-        launch_block_matvec(s, S, ld, n, cvec, pvec, ptr<double>(h->Q) + m_before, kLdq,
+        launch_block_matvec(s, op.matrix, ld, n, cvec, pvec, ptr<double>(h->Q) + m_before, kLdq,
                             ptr<double>(h->Vs), ptr<double>(h->W));
       if (time_mv) ev_rec(h, &h->mv_ev[h->n_mv_ev++][1]);
       ++passes;
@@ -695,14 +683,14 @@ int sym_topk(sc_handle h, const double* S_in, int ld, int n, const EigRequest& r
       if (fused) {
         // CGS-1 | CGS-2 + CholQR | re-projection + CholQR on the normalised block | store
         const EigWorkspace ws = eig_workspace(h);
-        launch_lz_link(s, ws, &chain, n, mm, 0, 1, -1, vscale, mm - kEigBlock, false, 0, false);
-        launch_lz_link(s, ws, &chain, n, mm, 1, 2, -1, vscale, mm - kEigBlock, false, 0, false);
-        launch_lz_link(s, ws, &chain, n, mm, 2, 3, -1, vscale, mm - kEigBlock, false, 0, false);
-        if (three_pass) launch_lz_link(s, ws, &chain, n, mm, 3, 3, -1, vscale, 0, false, 0, false);
-        launch_lz_link(s, ws, &chain, n, mm, 3, 0, mm, vscale, 0, false, 0, false);
+        launch_lz_link(s, ws, &chain, n, mm, 0, 1, -1, cvec, mm - kEigBlock, false, 0, false);
+        launch_lz_link(s, ws, &chain, n, mm, 1, 2, -1, cvec, mm - kEigBlock, false, 0, false);
+        launch_lz_link(s, ws, &chain, n, mm, 2, 3, -1, cvec, mm - kEigBlock, false, 0, false);
+        if (three_pass) launch_lz_link(s, ws, &chain, n, mm, 3, 3, -1, cvec, 0, false, 0, false);
+        launch_lz_link(s, ws, &chain, n, mm, 3, 0, mm, cvec, 0, false, 0, false);
         return check_last(h, "block step launch");
       }
-      return orthonormalize(h, n, mm, true, mm - kEigBlock, mm, true);
+      return orthonormalize(h, n, mm, true, mm - kEigBlock, mm, true, cvec);
     };
     int ahead = 0;  // block steps already enqueued beyond m (run-ahead during a host solve)
     while (!done) {
@@ -732,7 +720,7 @@ int sym_topk(sc_handle h, const double* S_in, int ld, int n, const EigRequest& r
                                  hipMemcpyDeviceToHost, s));
       }
       if (!fused) {
-        const int rcb = finish_block(h, n, m, m, &seed);  // syncs the stream
+        const int rcb = finish_block(h, n, m, m, cvec, &seed);  // syncs the stream
         if (rcb == SC_ERR_NOT_CONVERGED) {
           SC_TRY(dense_fallback(3));
           break;
@@ -777,7 +765,7 @@ int sym_topk(sc_handle h, const double* S_in, int ld, int n, const EigRequest& r
           goto restart_lanczos;
         }
       }
-      if (h->free_on && !h->free_checked && (!fused || check)) {
+      if (op.free_op && !h->free_checked && (!fused || check)) {
         // (the stream has just drained) matrix-free Diffuse: rows the candidate search could
         // not prune get their exact maximum now; the solve starts over on the corrected operator
         bool restart = false;
@@ -925,8 +913,8 @@ int sym_topk(sc_handle h, const double* S_in, int ld, int n, const EigRequest& r
     diag->eig_max_residual = dc.max_resid;
     diag->eig_host_chain = (n > kDenseMax && !fused) ? 1 : 0;
     diag->eig_fallback = fallback_reason;
-    if (free_at_entry) {
-      diag->diffuse_path = h->free_on ? SC_DIFFUSE_PATH_FREE : SC_DIFFUSE_PATH_FREE_THEN_EXPLICIT;
+    if (op_in.free_op) {
+      diag->diffuse_path = op.free_op ? SC_DIFFUSE_PATH_FREE : SC_DIFFUSE_PATH_FREE_THEN_EXPLICIT;
       diag->free_candidates = h->free_checked ? h->h_free[65] : 0;
       diag->free_overflow_rows = h->free_checked ? h->h_free[0] : 0;
       diag->free_tiles_run = h->free_checked ? h->h_free[67] : 0;
@@ -997,13 +985,14 @@ int sym_topk_group(sc_handle lead, GroupEigMember* mem, int count, bool want_vec
     lz[z].chain = LzChain();
     lz[z].chain.three_pass = true;  // (one more tiny launch per block for the whole group)
     lz[z].n = mem[z].n;
-    lz[z].vs_scale = h->vs_scale ? h->vs_scale : ptr<double>(h->cvec);
+    lz[z].vs_scale = ptr<double>(h->cvec);
     lz[z].active = true;
     const int cap = std::min(kEigBasisCap, ((mem[z].n - kEigBlock) / kEigBlock) * kEigBlock);
     limit[z] = cap;
     mem[z].status = 0;
     mem[z].passes = 0;
     mem[z].basis = 0;
+    mem[z].skip_fused = false;
   }
   // upper-triangle matvec once the group's matrices no longer fit the caches together
   size_t matrix_bytes = 0;
@@ -1187,7 +1176,7 @@ int sym_topk_group(sc_handle lead, GroupEigMember* mem, int count, bool want_vec
         fprintf(stderr, "[sc]   member %d (n %d): chain latched at m=%d (code %d), check at m=%d\n",
                 z, mem[z].n, hflags[14], hflags[15], m);
       if (!rr_wanted[z]) {
-        if (latched) h->eig_skip_fused = true;
+        if (latched) mem[z].skip_fused = true;
         hand_back();
         continue;
       }
@@ -1220,7 +1209,7 @@ int sym_topk_group(sc_handle lead, GroupEigMember* mem, int count, bool want_vec
       }
       if (latched) {
         if (trace) fprintf(stderr, "[sc]   member %d: latched and not converged\n", z);
-        h->eig_skip_fused = true;
+        mem[z].skip_fused = true;
         hand_back();
         continue;
       }
@@ -1543,7 +1532,7 @@ int gen_topk(sc_handle h, const double* M, int ld, int n, int laplacian_type,
     // divides by that value instead of its own far-end Ritz value.  Tens of block passes where the
     // dense route is seconds at n = 2000.  Only a far-end solve that spends its restart budget
     // sends the request to the dense route (eig_fallback 9).
-    if (far_end && !sw::gen_loose_bulk()) {
+    if (far_end) {
       EigRequest fr = rq;
       fr.fixed_count = 1;
       fr.descend = 1;
@@ -1577,11 +1566,10 @@ int gen_topk(sc_handle h, const double* M, int ld, int n, int laplacian_type,
       }
       // (beyond the dense route's size limit: the far end as the main solve's basis has it)
     }
-    // Narrow form: basis <= 64, projected problems solved by the one-wavefront device kernel,
-    // up to 32 Ritz pairs.  WIDE form (a request for more -- max_clusters up to 63,
-    // min_clusters up to 64 -- or a descending request whose stop_eigenvalue turns out to lie
-    // deeper): basis <= 128, the projected problems (order <= 128) solved on the host
-    // (host_general_eig), up to 64 pairs.
+    // Narrow form: basis <= 64, up to 32 Ritz pairs.  WIDE form (a request for more --
+    // max_clusters up to 63, min_clusters up to 64 -- or a descending request whose
+    // stop_eigenvalue turns out to lie deeper): basis <= 128, up to 64 pairs.  The projected
+    // problems of both are solved on the host (host_general_eig).
     const int asked = rq.fixed_count > 0
                           ? rq.fixed_count
                           : std::max(rq.max_clusters > 0 ? rq.max_clusters + 1 : 0, rq.min_clusters);
@@ -1612,11 +1600,6 @@ int gen_topk(sc_handle h, const double* M, int ld, int n, int laplacian_type,
     double* Q = ptr<double>(h->Q);
     double* OpQ = ptr<double>(h->Q2);
     double* W = ptr<double>(h->W);
-    h->vs_scale = cr;
-    struct Restore {
-      sc_handle h;
-      ~Restore() { h->vs_scale = nullptr; }
-    } restore{h};
     const int cap = std::min(wide ? kEigBasisCap : kGenMax, ((n - kEigBlock) / kEigBlock) * kEigBlock);
     const int first_check = std::min(3 * kEigBlock, cap);
     uint64_t seed = 0x9e3779b97f4a7c15ull;
@@ -1637,13 +1620,13 @@ int gen_topk(sc_handle h, const double* M, int ld, int n, int laplacian_type,
       } else {
         launch_copy_block(s, OpQ + (m - kEigBlock), kLdq, W, kEigBlock, n, kEigBlock);
       }
-      SC_TRY(orthonormalize(h, n, m, false, 0, m, false));
-      SC_TRY(finish_block(h, n, m, m, &seed));
+      SC_TRY(orthonormalize(h, n, m, false, 0, m, false, cr));
+      SC_TRY(finish_block(h, n, m, m, cr, &seed));
       launch_block_matvec(s, M, ld, n, cl, pv, Q + m, kLdq, ptr<double>(h->Vs), W);
       launch_copy_block(s, W, kEigBlock, OpQ + m, kLdq, n, kEigBlock);
       ++passes;
       m += kEigBlock;
-      // Rayleigh-Ritz (a serial ~m^3 solve in one wavefront) is the expensive step: every
+      // Rayleigh-Ritz (a serial ~m^3 solve on the host) is the expensive step: every
       // block early in the first cycle, where convergence is expected, then every other
       // block, and only with a full basis once restarts have begun
       const bool check = next_start >= start_blocks.size() && m >= first_check &&
@@ -1660,42 +1643,36 @@ int gen_topk(sc_handle h, const double* M, int ld, int n, int laplacian_type,
           launch_copy_block(s, ptr<double>(h->Hbuf), kEigBlock, ptr<double>(h->T) + jb, kLdq,
                             m, kEigBlock);
         }
-        if (!wide && sw::gen_device_rr()) {
-          launch_gen_eig(s, ptr<double>(h->T), kLdq, m, 1.0, m, theta_d, thetai_d, Yre, Yim, kLdq,
-                         info_d);
-        } else {
-          // The projected problem (order <= 64 narrow, <= 128 wide) is solved on the HOST: T comes
-          // over, its eigenpairs go back to where k_gen_eig leaves them.  Round 6: in the narrow
-          // form too -- the one-wavefront device kernel takes 4.0 ms at m = 64 and was 77 % of the
-          // GPU time of a general-path call (profiles/r35_gen_kernel_stats.txt); real double-shift
-          // QR + inverse iteration for the vectors a restart keeps take 0.3-0.9 ms
-          // (host_general_eig_fast; the complex Schur form is its fallback).  SC_GEN_DEVICE_RR=1:
-          // the device kernel (narrow form).
-          SC_HIP(h, hipMemcpy2DAsync(h->h_rr, (size_t)m * sizeof(double), h->T.p,
-                                     (size_t)kLdq * sizeof(double), (size_t)m * sizeof(double), m,
-                                     hipMemcpyDeviceToHost, s));
-          SC_HIP(h, hipStreamSynchronize(s));
-          hy.assign(2 * (size_t)m * m, 0.0);
-          for (size_t e = 0; e < (size_t)m * m; ++e)
-            if (!std::isfinite(h->h_rr[e])) return fail(h, SC_ERR_NON_FINITE, kNonFiniteMessage);
-          // (vectors: the pairs whose residual is evaluated and a restart materialises; all of
-          //  them while the far end -- Ritz pair m - 1 -- is tracked)
-          const int nvec = far_end ? m : std::min(m, wide ? 104 : 40);
-          if (!host_general_eig_fast(h->h_rr, m, m, nvec, th, thi, hy.data(),
-                                     hy.data() + (size_t)m * m, m) &&
-              !host_general_eig(h->h_rr, m, m, m, th, thi, hy.data(), hy.data() + (size_t)m * m, m))
-            return fail(h, SC_ERR_NOT_CONVERGED, "QR iteration of the projected eigenproblem failed");
-          SC_HIP(h, hipMemcpyAsync(theta_d, th, m * sizeof(double), hipMemcpyHostToDevice, s));
-          SC_HIP(h, hipMemcpyAsync(thetai_d, thi, m * sizeof(double), hipMemcpyHostToDevice, s));
-          SC_HIP(h, hipMemcpy2DAsync(Yre, (size_t)kLdq * sizeof(double), hy.data(),
-                                     (size_t)m * sizeof(double), (size_t)m * sizeof(double), m,
-                                     hipMemcpyHostToDevice, s));
-          SC_HIP(h, hipMemcpy2DAsync(Yim, (size_t)kLdq * sizeof(double), hy.data() + (size_t)m * m,
-                                     (size_t)m * sizeof(double), (size_t)m * sizeof(double), m,
-                                     hipMemcpyHostToDevice, s));
-          SC_HIP(h, hipMemsetAsync(info_d, 0, 2 * sizeof(int), s));
-          SC_HIP(h, hipStreamSynchronize(s));  // (th / thi / hy are reused below)
-        }
+        // The projected problem (order <= 64 narrow, <= 128 wide) is solved on the HOST: T comes
+        // over, its eigenpairs go back to where k_gen_eig leaves them.  Round 6: in the narrow
+        // form too -- the one-wavefront device kernel takes 4.0 ms at m = 64 and was 77 % of the
+        // GPU time of a general-path call (profiles/r35_gen_kernel_stats.txt); real double-shift
+        // QR + inverse iteration for the vectors a restart keeps take 0.3-0.9 ms
+        // (host_general_eig_fast; the complex Schur form is its fallback).
+        SC_HIP(h, hipMemcpy2DAsync(h->h_rr, (size_t)m * sizeof(double), h->T.p,
+                                   (size_t)kLdq * sizeof(double), (size_t)m * sizeof(double), m,
+                                   hipMemcpyDeviceToHost, s));
+        SC_HIP(h, hipStreamSynchronize(s));
+        hy.assign(2 * (size_t)m * m, 0.0);
+        for (size_t e = 0; e < (size_t)m * m; ++e)
+          if (!std::isfinite(h->h_rr[e])) return fail(h, SC_ERR_NON_FINITE, kNonFiniteMessage);
+        // (vectors: the pairs whose residual is evaluated and a restart materialises; all of
+        //  them while the far end -- Ritz pair m - 1 -- is tracked)
+        const int nvec = far_end ? m : std::min(m, wide ? 104 : 40);
+        if (!host_general_eig_fast(h->h_rr, m, m, nvec, th, thi, hy.data(),
+                                   hy.data() + (size_t)m * m, m) &&
+            !host_general_eig(h->h_rr, m, m, m, th, thi, hy.data(), hy.data() + (size_t)m * m, m))
+          return fail(h, SC_ERR_NOT_CONVERGED, "QR iteration of the projected eigenproblem failed");
+        SC_HIP(h, hipMemcpyAsync(theta_d, th, m * sizeof(double), hipMemcpyHostToDevice, s));
+        SC_HIP(h, hipMemcpyAsync(thetai_d, thi, m * sizeof(double), hipMemcpyHostToDevice, s));
+        SC_HIP(h, hipMemcpy2DAsync(Yre, (size_t)kLdq * sizeof(double), hy.data(),
+                                   (size_t)m * sizeof(double), (size_t)m * sizeof(double), m,
+                                   hipMemcpyHostToDevice, s));
+        SC_HIP(h, hipMemcpy2DAsync(Yim, (size_t)kLdq * sizeof(double), hy.data() + (size_t)m * m,
+                                   (size_t)m * sizeof(double), (size_t)m * sizeof(double), m,
+                                   hipMemcpyHostToDevice, s));
+        SC_HIP(h, hipMemsetAsync(info_d, 0, 2 * sizeof(int), s));
+        SC_HIP(h, hipStreamSynchronize(s));  // (th / thi / hy are reused below)
         const int c1 = std::min(m, kMaxCheck);
         for (int c0 = 0; c0 < c1; c0 += 32)  // (the residual kernel takes 32 pairs per launch)
           launch_gen_residual(s, Q, OpQ, kLdq, m, n, Yre + c0, Yim + c0, kLdq, theta_d + c0,
@@ -1748,8 +1725,8 @@ int gen_topk(sc_handle h, const double* M, int ld, int n, int laplacian_type,
         // which the Arnoldi recurrence continues from the residual block)
         const int kStash = wide ? 112 : 48;  // Vre columns [kStash, kStash + 8): the residual block
         launch_copy_block(s, OpQ + (m - kEigBlock), kLdq, W, kEigBlock, n, kEigBlock);
-        SC_TRY(orthonormalize(h, n, m, false, 0, -1, false));
-        SC_TRY(finish_block(h, n, m, -1, &seed));
+        SC_TRY(orthonormalize(h, n, m, false, 0, -1, false, cr));
+        SC_TRY(finish_block(h, n, m, -1, cr, &seed));
         launch_rowmajor_to_colmajor(s, W, kEigBlock, n, kEigBlock, Vre + (size_t)kStash * ldv,
                                     ldv);
         const int want = dc.enough ? std::max(dc.kw, dc.kvec) : cap / 4;

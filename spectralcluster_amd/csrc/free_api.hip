@@ -109,43 +109,21 @@ int free_stats_end(sc_handle h, hipStream_t s, const double* A, int ld, int n, b
   return SC_OK;
 }
 
-// The same two pieces for a GROUP of matrices of ICASSP fronts (AutoTune sweep: 16 members of
-// one size): the begin step, quantiser, candidate scan and exact statistics of all members are
-// one launch each -- a member's own kernels of 20-100 us left most of the chip idle between
-// their tails, and 16 x 7 launches were 16 x 7 launch latencies.  The caller puts the digit
-// product (one grouped launch, or one per member) between the two.
-int free_group_begin(sc_handle* hs, const double* const* A, const double* const* cuts,
-                     const double* ps, int count, const int* lds, const int* ns, hipStream_t s,
-                     double floor_value, FreeItem* items) {
-  for (int z = 0; z < count; ++z) {
-    sc_handle h = hs[z];
-    const int n = ns[z], ld = lds[z];
-    SC_TRY(ensure_free(h, n));
-    items[z] = FreeItem{A[z], n, ld, ptr<signed char>(h->fq), ptr<float>(h->ft32),
-                        ptr<int>(h->fwords), ptr<double>(h->fscal), ptr<double>(h->fy1),
-                        ptr<double>(h->fR), ptr<int>(h->fcand), ptr<double>(h->rowmax),
-                        ptr<double>(h->rowsum), cuts[z], ps[z]};
-    items[z].q2part = ptr<double>(h->fq2part);
-    items[z].mx64 = ptr<double>(h->fmx64);
-    items[z].tau64 = ptr<float>(h->ftau64);
-    items[z].plan = ptr<int>(h->fplan);
-  }
-  launch_free_begin_group(s, items, count, floor_value);
-  launch_free_quantize_group(s, items, count);
-  // the members' skip lists (the caller hands items[z].plan to the grouped product)
-  launch_free_tile_flags_group(s, items, count, free_prune_on(hs[0]), true);
-  return SC_OK;
-}
-// Round 6: the grouped threshold + symmetrise pass writes the members' digits itself (what the
-// single call has done since round 4) -- the quantiser's extra read of every member's matrix goes
-// (k_free_quantize_g: 0.57 ms of a 16-value sweep at n = 4096, 3.3 % of config 5's GPU time).
+// The same pipeline for a GROUP of matrices of ICASSP fronts (AutoTune sweep: 16 members of one
+// size; the large members of a batch group): the begin step, candidate scan and exact statistics
+// of all members are one launch each -- a member's own kernels of 20-100 us left most of the chip
+// idle between their tails, and 16 x 7 launches were 16 x 7 launch latencies.  Round 6: the
+// grouped threshold + symmetrise pass writes the members' digits itself (what the single call has
+// done since round 4) -- the quantiser's extra read of every member's matrix is gone
+// (the grouped quantiser: 0.57 ms of a 16-value sweep at n = 4096, 3.3 % of config 5's GPU time;
+// profiles/r40_grouped_kernel_stats.txt, r44_* without it).
 //   free_group_prepare   BEFORE the threshold pass, once the cut vectors are there: buffers, max|a|
 //                        from the cuts, words cleared, the digit rows no tile writes cleared; fills
 //                        items[] and digits[] (what launch_threshold_symmetrize_group takes)
 //   free_group_digits    AFTER it: y1 / R / max R / the skip-list thresholds from the row partials,
 //                        then the members' skip lists
-// then the grouped product and free_group_end as before.  SC_GROUP_QUANTIZE_PASS=1: rounds 4-5's
-// separate quantiser (free_group_begin).
+// then the digit product (one grouped launch; items[z].plan is a member's skip list) and
+// free_group_end.
 int free_group_prepare(sc_handle* hs, const double* const* A, const double* const* cuts,
                        const double* ps, int count, const int* lds, const int* ns, hipStream_t s,
                        double floor_value, FreeItem* items, TsDigits* digits) {
@@ -175,7 +153,7 @@ int free_group_prepare(sc_handle* hs, const double* const* A, const double* cons
 }
 int free_group_digits(sc_handle* hs, const FreeItem* items, int count, hipStream_t s) {
   launch_free_partials_reduce_group(s, items, count);
-  launch_free_tile_flags_group(s, items, count, free_prune_on(hs[0]), false);
+  launch_free_tile_flags_group(s, items, count, free_prune_on(hs[0]));
   return SC_OK;
 }
 

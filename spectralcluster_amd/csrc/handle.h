@@ -49,8 +49,6 @@ struct sc_handle_s {
   int n_vec = 0;          // eigenvector columns resident in E
   // matrices
   DevBuf X, Xn, A0, B1, B2;
-  bool chain_flags_clean = false;    // flags[13..15] were cleared by the scaling kernel: the first
-                                     // start of sym_topk skips its fill
   DevBuf Xalt;                       // second embeddings buffer: the NEXT call's upload lands here
   hipStream_t copy_stream = nullptr; // ... on this stream (predict_sequence, api.hip)
   // n-vectors
@@ -81,7 +79,6 @@ struct sc_handle_s {
   // general (non-symmetric) eigen path: right scaling, Im(theta), complex Ritz vectors
   // (column-major), residual partials, restart codes, dense Laplacian scratch
   DevBuf crvec, thetai, Vre, Vim, gpart, gsrc, genL, gneg;
-  const double* vs_scale = nullptr;  // Vs = vs_scale .* V in orthonormalize (default cvec)
   DevBuf ahc_size, ahc_chain, ahc_Z, ahc_lab, ahc_cent;  // size reduction (AHC) scratch
   DevBuf fb_part, fb_small, fb_x, fb_cent, fb_int;      // fallback decisions scratch
   // k-means workspace
@@ -136,7 +133,6 @@ struct sc_handle_s {
   double blurw_host[2 * SC_MAX_BLUR_RADIUS + 1];
   int krnd_k = -1, krnd_trials = -1;
   int kfirst_n = -1, kfirst = 0;  // first k-means++ centre of the last n (RandomState(0) draw)
-  bool eig_skip_fused = false;  // next sym_topk: go straight to the host-driven chain
   // ---- matrix-free Diffuse (free_api.hip)
   int diffuse_mode = -1;   // sc_set_diffuse_mode: 0 auto, 1 explicit fp64 product, 2 matrix-free
                            // wherever the sequence allows it; -1: the environment's default
@@ -147,9 +143,7 @@ struct sc_handle_s {
                            // squared segment norms per (block, row), their maxima per 64-row
                            // group, the groups' thresholds, surviving tiles per tile row
   int* h_free = nullptr;   // pinned copy of the ovf words (80)
-  bool free_on = false;    // the operator of the current solve is c .* A (A (c .* v)) + p .* v
-  bool free_checked = false;  // ... and its overflow rows have been dealt with
-  int free_lap = 0, free_rownorm = 0;  // what the scaling vectors were built for
+  bool free_checked = false;  // the overflow rows of h_free have been dealt with
   int free_ev[5] = {-1, -1, -1, -1, -1};  // event slots: begin | quantised | product | scans | stats
 };
 
@@ -297,15 +291,24 @@ struct EigDecision {
   int fail_index = -1;
 };
 
-// where eig_ncluster_impl(front_only) left the refined matrix
+// Where eig_ncluster_impl(front_only) left the refined matrix -- and the operator a symmetric
+// solve works on: Op = diag(p) + diag(c) S diag(c), S = `matrix`, the scaling vectors c, p in
+// the handle (sym_topk).
 struct FrontResult {
   const double* matrix = nullptr;
-  double* scratch = nullptr;
+  double* scratch = nullptr;  // a free n x ld matrix (the dense routes materialise Op there)
   int ld = 0;
   bool symmetric = false, folded_rownorm = false;
   // matrix-free Diffuse: `matrix` is the symmetric A BEFORE Diffuse (the operator applies it
-  // twice), the row statistics of S = A A^T are in the handle, its overflow record in h_free
+  // twice), the row statistics of S = A A^T are in the handle, its overflow record in h_free;
+  // the scaling vectors were built for this Laplacian and folded_rownorm
   bool free_op = false;
+  int laplacian_type = 0;
+  // flags[13..15] were cleared by the scaling kernel: the first start of the fused chain skips
+  // its fill
+  bool chain_flags_cleared = false;
+  // the lockstep group solve saw this problem latch the fused chain: the host-driven chain
+  bool skip_fused = false;
 };
 EigRequest make_eig_request(const sc_config* cfg);
 int upload_blur_weights(sc_handle h, const sc_config* cfg);  // into h->blurw, on h->stream
@@ -328,6 +331,7 @@ struct GroupEigMember {
   EigDecision dc;
   std::vector<double> w;      // consumed eigenvalues (reference order)
   int basis = 0, passes = 0;
+  bool skip_fused = false;    // (status 1) the fused chain latched: a re-solve takes the host chain
   // matrix-free Diffuse: S is the symmetric A before Diffuse, the operator is
   // diag(p) + diag(c) A A diag(c) (two block products per step, through h->fY)
   bool free_op = false;
@@ -340,9 +344,9 @@ int sym_topk_group(sc_handle lead, GroupEigMember* mem, int count, bool want_vec
 // `any_size`: also n >= 4096 (the group takes the upper-triangle matvec there)
 bool sym_group_eligible(int n, const EigRequest& rq, bool any_size = false);
 
-// `scratch`: a free n x ld matrix (the dense full-spectrum path materialises Op there)
-int sym_topk(sc_handle h, const double* S, int ld, int n, const EigRequest& rq, sc_diag* diag,
-             EigDecision* out_dc, std::vector<double>* out_w, double* scratch);
+// the symmetric operator `op` (op.scratch: the dense routes' n x ld matrix)
+int sym_topk(sc_handle h, const FrontResult& op, int n, const EigRequest& rq, sc_diag* diag,
+             EigDecision* out_dc, std::vector<double>* out_w);
 // `scratch`: a free n x ld matrix (the dense Hessenberg route reduces a copy of M there; may be
 // null for n <= 64)
 int gen_topk(sc_handle h, const double* M, int ld, int n, int laplacian_type,
@@ -354,20 +358,18 @@ int gen_topk(sc_handle h, const double* M, int ld, int n, int laplacian_type,
 // RowWiseNormalize / the Laplacian?  (mode of the handle, problem size, request)
 bool free_diffuse_wanted(sc_handle h, const sc_config* cfg, int n, const EigRequest& rq,
                          bool in_group = false);
-// enqueue the statistics of S = A A^T (h->rowmax, h->rowsum) on h->stream; no synchronisation.
-// The overflow words travel to h->h_free behind them.
-// `have_amax`: h->fscal[0] already holds max|a| (or an upper bound of it) for this A
-int free_group_begin(sc_handle* hs, const double* const* A, const double* const* cuts,
-                     const double* ps, int count, const int* lds, const int* ns, hipStream_t s,
-                     double floor_value, struct FreeItem* items);
-int free_group_end(sc_handle* hs, const struct FreeItem* items, int count, hipStream_t s);
-// (the grouped threshold pass writes the digits: free_api.hip)
+// the statistics of a group (free_api.hip): prepare before the grouped threshold pass (which
+// writes the digits), digits after it, end after the grouped digit product
 int free_group_prepare(sc_handle* hs, const double* const* A, const double* const* cuts,
                        const double* ps, int count, const int* lds, const int* ns, hipStream_t s,
                        double floor_value, struct FreeItem* items, struct TsDigits* digits);
 int free_group_digits(sc_handle* hs, const struct FreeItem* items, int count, hipStream_t s);
+int free_group_end(sc_handle* hs, const struct FreeItem* items, int count, hipStream_t s);
 int free_fused_prepare(sc_handle h, hipStream_t s, int n, const double* cut, double p,
                        double floor_value);
+// enqueue the statistics of S = A A^T (h->rowmax, h->rowsum) on h->stream; no synchronisation.
+// The overflow words travel to h->h_free behind them.
+// `have_amax`: h->fscal[0] already holds max|a| (or an upper bound of it) for this A
 int free_diffuse_stats(sc_handle h, const double* A, int ld, int n, bool have_amax = false,
                        bool digits_ready = false);
 int ensure_free(sc_handle h, int n);

@@ -489,13 +489,9 @@ struct FreeItem {
 // y1, R, max R and the skip list's thresholds of every member from the partials of a grouped
 // threshold pass that wrote the digits (the group form of launch_free_partials_reduce)
 void launch_free_partials_reduce_group(hipStream_t s, const FreeItem* items, int count);
-// (seg_reduce: the members' digits came from the quantiser, whose segment maxima are not formed
-//  by the pass itself)
-void launch_free_tile_flags_group(hipStream_t s, const FreeItem* items, int count, bool prune,
-                                  bool seg_reduce);
+void launch_free_tile_flags_group(hipStream_t s, const FreeItem* items, int count, bool prune);
 void launch_free_begin_group(hipStream_t s, const FreeItem* items, int count, double floor_value,
                              bool pad_rows = false);
-void launch_free_quantize_group(hipStream_t s, const FreeItem* items, int count);
 void launch_free_scan_stats_group(hipStream_t s, const FreeItem* items, int count);
 void free_i8_split_plan(int n, int* tail_tiles, int* parts);
 size_t free_i8_split_bytes(int n);

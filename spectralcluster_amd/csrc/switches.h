@@ -5,7 +5,10 @@
 //                    the same goldens: tests/test_gpu_alternate_paths.py runs every one.
 // Each is read once per process.  (Round 2's experiment switches -- K-window throttle,
 // staggered CU partners, bank priorities, a third bank, row caps -- are gone with the code
-// they guarded; their measurements are in DESIGN_HISTORY.md and profiles/r02_*.)
+// they guarded; their measurements are in DESIGN_HISTORY.md and profiles/r02_*.  So are the
+// switches that brought back round 5's behaviour for round 6's A/B runs -- device Rayleigh-Ritz
+// and loose stop rule of the general path, groups of equal count, the grouped quantiser pass,
+// batches without prefetched uploads: profiles/r35, r18, r27, r40 / r44, r24.)
 #ifndef SPECTRALCLUSTER_AMD_SWITCHES_H_
 #define SPECTRALCLUSTER_AMD_SWITCHES_H_
 
@@ -92,41 +95,10 @@ inline int gen_dense_max_n() {
   static const int v = getenv("SC_GEN_DENSE_MAX_N") ? atoi(getenv("SC_GEN_DENSE_MAX_N")) : 512;
   return v;
 }
-// SC_GROUP_QUANTIZE_PASS=1: the matrix-free members of a grouped front / sweep get their digits from
-// a quantiser pass of their own (rounds 4-5) instead of from the grouped threshold pass
-inline bool group_quantize_pass() {
-  static const bool v = getenv("SC_GROUP_QUANTIZE_PASS") != nullptr;
-  return v;
-}
-// SC_GEN_DEVICE_RR=1: the Rayleigh-Ritz problems of the narrow block Arnoldi (order <= 64) on the
-// one-wavefront device kernel k_gen_eig (rounds 2-5) instead of the host
-inline bool gen_device_rr() {
-  static const bool v = getenv("SC_GEN_DEVICE_RR") != nullptr;
-  return v;
-}
-// SC_GROUP_EQUAL_COUNT=1: the grouped batch cuts its size-sorted list into groups of equal
-// COUNT dealt round-robin to the lanes (rounds 2-5) instead of groups of equal cost dealt
-// longest-first (A/B measurements)
-inline bool group_equal_count() {
-  static const bool v = getenv("SC_GROUP_EQUAL_COUNT") != nullptr;
-  return v;
-}
-// SC_NO_PREFETCH=1: the calls of a batch upload their embeddings themselves, one after the
-// other (what a sequence of sc_predict calls does) instead of under their predecessor's pipeline
-inline bool no_prefetch() {
-  static const bool v = getenv("SC_NO_PREFETCH") != nullptr;
-  return v;
-}
 // SC_FREE_NO_PRUNE=1: the digit product of the matrix-free Diffuse computes every tile (the
 // skip list keeps them all): what an unstructured input gets anyway
 inline bool free_no_prune() {
   static const bool v = getenv("SC_FREE_NO_PRUNE") != nullptr;
-  return v;
-}
-// SC_GEN_LOOSE_BULK=1: rounds 3-5's stop rule of the general path (consumed eigenvalues that
-// cannot move the eigengap decision held to 1e-3 instead of value_tol) -- A/B measurements only
-inline bool gen_loose_bulk() {
-  static const bool v = getenv("SC_GEN_LOOSE_BULK") != nullptr;
   return v;
 }
 // SC_SWEEP_ONE_BY_ONE=1: an AutoTune level as separate sc_eig_ncluster calls (what a level

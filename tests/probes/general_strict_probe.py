@@ -4,7 +4,6 @@ n in {600, 1000, 2000}.  Prints per case: eigen path, block
 cycles, stage time, worst consumed-eigenvalue error, cluster counts, ARI.
 
   python tests/probes/general_strict_probe.py [sizes...]
-  SC_GEN_LOOSE_BULK=1 python tests/probes/general_strict_probe.py     # rounds 3-5's stop rule
 """
 import os
 import sys

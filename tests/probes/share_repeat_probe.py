@@ -1,6 +1,6 @@
 """One rank's LPT share of config 5 (world 2 / 8) through predict_batch(group=16), five times in a
 row after one full-batch warm-up: is a slow share a warm-up effect or the share's own time?
-  python tests/probes/share_repeat_probe.py            (SC_GROUP_EQUAL_COUNT=1 for round 5's groups)"""
+  python tests/probes/share_repeat_probe.py"""
 import os
 import sys
 import time
