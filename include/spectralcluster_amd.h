@@ -524,6 +524,14 @@ int sc_stage_kmeans(sc_handle h, const double* e, int n, int k, int max_iter,
 int sc_stage_kmeans_metric(sc_handle h, const double* e, int n, int k, int max_iter,
                            int metric, int64_t* labels, double* centroids_out,
                            int* iterations);
+/* custom_distance_kmeans.run_kmeans (:13-52) / CustomKMeans.predict (:85-141) on an (n, dim)
+ * input, dim independent of k.  init_centroids (k, dim) row-major, or NULL = sklearn k-means++
+ * seeds + one Lloyd step.  centroids_out (k, dim) may be NULL: the centroids of the last
+ * assignment pass (what the reference leaves in self.centroids).  *iterations = distance
+ * passes run (1 = stopped by the rule after the first pass), as sc_stage_kmeans reports. */
+int sc_stage_kmeans_general(sc_handle h, const double* x, int n, int dim, int k, int max_iter,
+                            int metric, double tol, const double* init_centroids,
+                            int64_t* labels, double* centroids_out, int* iterations);
 
 /* ---- multi-GPU: replicas of the path over the GPUs of one node ------------------------
  * The reference has no distributed layer (a batch is a Python `for` over predict(),

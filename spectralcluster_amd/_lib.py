@@ -242,6 +242,10 @@ PROTOTYPES = {
     "sc_stage_kmeans_metric": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               _c_int64_p, _c_double_p, _c_int_p]),
+    "sc_stage_kmeans_general": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_double, _c_double_p,
+                                               _c_int64_p, _c_double_p, _c_int_p]),
     "sc_comm_available": (ctypes.c_int, []),
     "sc_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "sc_comm_init_rank": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.c_int,

@@ -252,6 +252,8 @@ extern "C" int sc_destroy(sc_handle h) {
                     &h->kbig, &h->kbigw, &h->fq, &h->ft32, &h->fy1, &h->fR, &h->fscal, &h->fwords, &h->fcand, &h->fY, &h->fsplit, &h->fypart, &h->frpart, &h->fq2part, &h->fmx64, &h->ftau64, &h->fplan, &h->Xalt, &h->gneg};
   for (DevBuf* b : bufs)
     if (b->p) hipFree(b->p);
+  for (DevBuf& b : h->kgen)
+    if (b.p) hipFree(b.p);
   for (int i = 0; i < 48; ++i) hipEventDestroy(h->ev[i]);
   if (h->h_theta) hipHostFree(h->h_theta);
   if (h->h_flags) hipHostFree(h->h_flags);

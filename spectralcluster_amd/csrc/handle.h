@@ -26,6 +26,7 @@ struct DevBuf {
   size_t bytes = 0;
 };
 
+constexpr int kKgenBufs = 12;   // workspace buffers of sc_stage_kmeans_general
 constexpr int kGroupBanks = 2;  // banks of member arenas of the grouped batch (groups in flight)
 constexpr int kGroupLanes = 3;  // leads of the grouped batch (host threads, each with its banks)
 
@@ -84,6 +85,7 @@ struct sc_handle_s {
   // k-means workspace
   DevBuf kXc, kxsq, kclosest, kcand, kenorm, krnd, kcent, klab32, klab64, kinfo, kchain;
   DevBuf kbig, kbigw;     // more than kMaxVectors clusters: per-cluster arrays of k_kmeans<true>
+  DevBuf kgen[kKgenBufs];  // sc_stage_kmeans_general (kmeans_general.hip): any (n, dim, k)
   // pinned host scratch
   double* h_theta = nullptr;  // 3 * kLdq doubles (theta, resid, Im theta)
   int* h_flags = nullptr;
