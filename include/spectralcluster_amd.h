@@ -330,10 +330,28 @@ int sc_cluster(sc_handle h, const sc_config* cfg, int n_clusters,
  * prod_j (I + (alpha A_norm)^(2^j)) with fp64 MFMA GEMMs, which needs |alpha| < 1 and
  * a non-negative affinity (spectral radius of A_norm <= 1) -- both hold for the
  * reference's cosine affinity and its 0.4 / 0.6 presets.
+ *
+ * The banded form.  ConstraintMatrix.compute_diagonals (constraint.py:188-201) builds an
+ * (n, n) matrix whose only non-zeros sit on the first super- and sub-diagonal;
+ * sc_set_constraint_band takes those n - 1 values instead: band[i] = Q[i, i+1] = Q[i+1, i],
+ * every other entry of Q (the diagonal included) is 0.  n - 1 doubles are uploaded (n = 1:
+ * none, band may be NULL); no (n, n) buffer, no symmetry kernel.  The two forms replace one
+ * another, sc_clear_constraint clears either, and everything above holds for both: a band
+ * behaves as the symmetric dense matrix it stands for.  AffinityIntegration reads band[min(i,
+ * j)] where |i - j| == 1; ConstraintPropagation forms T Q in one pass over T (two terms per
+ * entry) instead of an n^3 GEMM.
+ * sc_constraint_info reports the resident form -- kind 0 none / 1 dense / 2 band, its n (0 when
+ * none) -- and the current device sizes in bytes of the band buffer and of the (n, ld) dense
+ * buffer (buffers are kept across calls; one that was never needed stays 0).  Any out pointer
+ * may be NULL.
  */
 int sc_set_constraint(sc_handle h, const double* constraint_matrix, int n);
+/* constraint.py:167-207 (ConstraintMatrix) + sc_set_constraint, without the matrix */
+int sc_set_constraint_band(sc_handle h, const double* band, int n);
 int sc_clear_constraint(sc_handle h);
 int sc_apply_constraint(sc_handle h, const sc_config* cfg);
+int sc_constraint_info(sc_handle h, int* kind, int* n, size_t* band_bytes,
+                       size_t* dense_bytes);
 /* affinity + eig_ncluster + cluster on the resident embeddings (no H2D of X) */
 int sc_run_resident(sc_handle h, const sc_config* cfg, int64_t* labels,
                     sc_diag* diag);
@@ -417,6 +435,10 @@ int sc_stage_refine(sc_handle h, int op, const sc_config* cfg, const double* in,
  * and its options are read from cfg.  Any square affinity / constraint matrix. */
 int sc_stage_constraint(sc_handle h, const sc_config* cfg, const double* affinity,
                         const double* constraint_matrix, int n, double* out);
+/* the same with the constraint matrix of ConstraintMatrix.compute_diagonals
+ * (constraint.py:188-201) given as its band of n - 1 values (sc_set_constraint_band) */
+int sc_stage_constraint_band(sc_handle h, const sc_config* cfg, const double* affinity,
+                             const double* band, int n, double* out);
 /* rowmax / rowsum of Diffuse(a) = a a^T (refinement.py:232-234) for a SYMMETRIC (n, n) input --
  * what RowWiseNormalize (refinement.py:240-245) and the Laplacian degree (laplacian.py:41) read
  * of it -- by either route: mode 1 the explicit fp64 product, mode 2 the matrix-free search

@@ -164,10 +164,17 @@ PROTOTYPES = {
     "sc_cluster": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScConfig), ctypes.c_int,
                                   _c_int64_p, ctypes.POINTER(ScDiag)]),
     "sc_set_constraint": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int]),
+    "sc_set_constraint_band": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int]),
     "sc_clear_constraint": (ctypes.c_int, [_handle_t]),
+    "sc_constraint_info": (ctypes.c_int, [_handle_t, _c_int_p, _c_int_p,
+                                          ctypes.POINTER(ctypes.c_size_t),
+                                          ctypes.POINTER(ctypes.c_size_t)]),
     "sc_apply_constraint": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScConfig)]),
     "sc_stage_constraint": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScConfig), _c_double_p,
                                            _c_double_p, ctypes.c_int, _c_double_p]),
+    "sc_stage_constraint_band": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScConfig),
+                                                _c_double_p, _c_double_p, ctypes.c_int,
+                                                _c_double_p]),
     "sc_ahc": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                               ctypes.c_int, ctypes.c_double, _c_int64_p,
                               ctypes.POINTER(ctypes.c_int)]),

@@ -2,7 +2,11 @@
 
 `AffinityIntegration` and `ConstraintPropagation` run on the device through
 `sc_stage_constraint`; inside `SpectralClusterer.predict` the constraint matrix stays
-resident and the same kernels run in the pipeline (`sc_set_constraint`).  The E2CP
+resident and the same kernels run in the pipeline (`sc_set_constraint`).  Wherever a
+constraint matrix is accepted, a `ConstraintMatrix` instance is accepted too: its n - 1 band
+values travel instead of the (n, n) array of `compute_diagonals()`
+(`sc_set_constraint_band` / `sc_stage_constraint_band`).  An ndarray always takes the dense
+route, whatever it holds.  The E2CP
 inverse `(I - alpha * A_norm)^-1` is evaluated as a Neumann product of fp64 MFMA GEMMs
 (see `csrc/constraint_api.hip: constraint_propagation`), which needs |alpha| < 1 and a
 non-negative affinity; anything else raises `UnsupportedOnDeviceError`.
@@ -34,11 +38,13 @@ class IntegrationType(enum.Enum):
   Average = 2
 
 
-def _device_adjust(affinity: np.ndarray, constraint_matrix: np.ndarray, name: ConstraintName,
+def _device_adjust(affinity: np.ndarray, constraint_matrix, name: ConstraintName,
                    integration_type: typing.Optional[IntegrationType],
                    alpha: float) -> np.ndarray:
   src = np.ascontiguousarray(affinity, dtype=np.float64)
-  con = np.ascontiguousarray(constraint_matrix, dtype=np.float64)
+  banded = isinstance(constraint_matrix, ConstraintMatrix)
+  con = constraint_matrix.band() if banded else np.ascontiguousarray(
+      constraint_matrix, dtype=np.float64)
   cfg = _lib.ScConfig()
   _lib.load().sc_config_default(cfg)
   cfg.constraint_name = name.value
@@ -47,7 +53,8 @@ def _device_adjust(affinity: np.ndarray, constraint_matrix: np.ndarray, name: Co
   cfg.constraint_alpha = float(alpha)
   out = np.empty_like(src)
   handle = _lib.default_handle()
-  handle.check(handle.lib.sc_stage_constraint(
+  stage = handle.lib.sc_stage_constraint_band if banded else handle.lib.sc_stage_constraint
+  handle.check(stage(
       handle.raw, cfg, _lib.as_double_p(src), _lib.as_double_p(con), src.shape[0],
       _lib.as_double_p(out)))
   return out
@@ -56,8 +63,12 @@ def _device_adjust(affinity: np.ndarray, constraint_matrix: np.ndarray, name: Co
 class ConstraintOperation(metaclass=abc.ABCMeta):
   """Base class of the two operators (reference constraint.py:51-92)."""
 
-  def check_input(self, affinity: np.ndarray, constraint_matrix: np.ndarray):
-    """Same checks and messages as reference constraint.py:54-76."""
+  def check_input(self, affinity: np.ndarray, constraint_matrix):
+    """Same checks and messages as reference constraint.py:54-76.  A `ConstraintMatrix`
+    stands for the (n, n) matrix of its `compute_diagonals()`, n = its number of scores."""
+    if isinstance(constraint_matrix, ConstraintMatrix):
+      n = len(constraint_matrix.speaker_turn_scores)
+      constraint_matrix = np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0))
     for what, m in (("affinity", affinity), ("constraint matrix", constraint_matrix)):
       if len(m.shape) != 2:
         raise ValueError("%s must be 2-dimensional" % what)
@@ -142,6 +153,14 @@ class ConstraintMatrix:
       raise ValueError("Speaker turn score must be larger or equal to 0.")
     self.speaker_turn_scores = speaker_turn_scores
     self.threshold = threshold
+
+  def band(self) -> np.ndarray:
+    """The n - 1 values `compute_diagonals()` puts on the first super- and sub-diagonal:
+    band[i] = Q[i, i + 1] = Q[i + 1, i] (float64, shape (max(n - 1, 0),)).  What the device
+    needs of the matrix; pass the `ConstraintMatrix` itself wherever a constraint matrix is
+    accepted and only these travel."""
+    nxt = np.asarray(self.speaker_turn_scores, dtype=np.float64)[1:]
+    return np.where(nxt == 0, 1.0, np.where(nxt > self.threshold, -1.0, 0.0))
 
   def compute_diagonals(self) -> np.ndarray:
     scores = np.asarray(self.speaker_turn_scores, dtype=np.float64)

@@ -22,6 +22,21 @@ __global__ __launch_bounds__(256) void k_affinity_integration(const double* __re
                                        : 0.5 * (x + c);
 }
 
+// ---- the same against a banded Q (ConstraintMatrix.compute_diagonals, constraint.py:188-201):
+// Q[i, i+1] = Q[i+1, i] = band[i], 0 elsewhere -- no constraint matrix is read
+__global__ __launch_bounds__(256) void k_affinity_integration_band(
+    const double* __restrict__ a, const double* __restrict__ band, double* __restrict__ out,
+    int n, int ld, int type) {
+  const int row = blockIdx.y;
+  const int col = blockIdx.x * 256 + threadIdx.x;
+  if (col >= n) return;
+  const size_t at = (size_t)row * ld + col;
+  const double x = a[at];
+  const double c = col == row + 1 ? band[row] : (row == col + 1 ? band[col] : 0.0);
+  out[at] = type == SC_INTEGRATION_MAX ? ((x != x || c != c) ? (x + c) : (x > c ? x : c))
+                                       : 0.5 * (x + c);
+}
+
 // ---- ConstraintPropagation, step 1 (constraint.py:143-152) ----------------------
 // dn_i = 1 / (sqrt(deg_i) + EPS);  P = alpha * ((dn_i A_ij) dn_j);  T0 = I + P
 // (first factor of the Neumann product).  Padding columns are zero-filled so the GEMMs
@@ -44,6 +59,43 @@ __global__ __launch_bounds__(256) void k_cp_prepare(const double* __restrict__ a
   const double v = alpha * ((di * a[at]) * dj);
   p[at] = v;
   t0[at] = (row == col ? 1.0 : 0.0) + v;
+}
+
+// ---- ConstraintPropagation against a banded Q: X = Tt Q^T without the GEMM --------
+// X[i, j] = band[j-1] Tt[i, j-1] + band[j] Tt[i, j+1]  (terms outside [0, n) dropped), the
+// operand launch_gemm_nt(T, X) = T X^T = T Q T expects.  One read and one write of the matrix:
+// a thread owns two adjacent columns (one 16-byte load and store; rows start on 128-byte
+// lines and ld is even), the columns left and right of its pair come from the neighbouring
+// lanes' registers, and only the first / last lane of a wavefront fetch theirs (a line the next
+// wavefront loads anyway).  Padding columns [n, ld) are written as zero, as in k_cp_prepare.
+__global__ __launch_bounds__(256) void k_cp_band_product(const double* __restrict__ tt,
+                                                         const double* __restrict__ band,
+                                                         double* __restrict__ x, int n, int ld) {
+  const int row = blockIdx.y;
+  const int j0 = (blockIdx.x * 256 + threadIdx.x) * 2;
+  const bool live = j0 < ld;  // (no early return: every lane takes part in the shuffles)
+  const double* r = tt + (size_t)row * ld;
+  double2 v = make_double2(0.0, 0.0);
+  if (live) v = *reinterpret_cast<const double2*>(r + j0);
+  // band[j0] and band[j0 + 1]; an index outside [0, n - 1) marks a dropped term
+  const bool has0 = j0 < n - 1, has1 = j0 + 1 < n - 1;
+  const double b0 = has0 ? band[j0] : 0.0;
+  const double b1 = has1 ? band[j0 + 1] : 0.0;
+  double left = __shfl_up(v.y, 1);    // Tt[row, j0 - 1]
+  double bm = __shfl_up(b1, 1);       // band[j0 - 1]
+  double right = __shfl_down(v.x, 1);  // Tt[row, j0 + 2]
+  const int lane = threadIdx.x & 63;
+  const bool hasm = j0 >= 1 && j0 - 1 < n - 1;
+  if (lane == 0 && hasm) {
+    left = r[j0 - 1];
+    bm = band[j0 - 1];
+  }
+  if (lane == 63 && has1) right = r[j0 + 2];
+  if (!live) return;
+  double2 o;
+  o.x = j0 < n ? (hasm ? bm * left : 0.0) + (has0 ? b0 * v.y : 0.0) : 0.0;
+  o.y = j0 + 1 < n ? (has0 ? b0 * v.x : 0.0) + (has1 ? b1 * right : 0.0) : 0.0;
+  *reinterpret_cast<double2*>(x + (size_t)row * ld + j0) = o;
 }
 
 // ---- ConstraintPropagation, last step (constraint.py:153-163) -------------------
@@ -94,6 +146,16 @@ void launch_affinity_integration(hipStream_t s, const double* a, const double* q
                                  int n, int ld, int type) {
   hipLaunchKernelGGL(k_affinity_integration, dim3((n + 255) / 256, n), dim3(256), 0, s, a, q,
                      out, n, ld, type);
+}
+void launch_affinity_integration_band(hipStream_t s, const double* a, const double* band,
+                                      double* out, int n, int ld, int type) {
+  hipLaunchKernelGGL(k_affinity_integration_band, dim3((n + 255) / 256, n), dim3(256), 0, s, a,
+                     band, out, n, ld, type);
+}
+void launch_cp_band_product(hipStream_t s, const double* tt, const double* band, double* x,
+                            int n, int ld) {
+  hipLaunchKernelGGL(k_cp_band_product, dim3((ld / 2 + 255) / 256, n), dim3(256), 0, s, tt, band,
+                     x, n, ld);
 }
 void launch_cp_prepare(hipStream_t s, const double* a, const double* deg, double alpha,
                        double* p, double* t0, int n, int ld) {

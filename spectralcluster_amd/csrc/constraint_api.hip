@@ -1,6 +1,6 @@
 // Host side of the constraint operators (reference constraint.py:95-164): the resident
-// constraint matrix and the GEMM chain of ConstraintPropagation; kernels in constraint.hip
-// and gemm_f64.hip.
+// constraint (a dense matrix, or the band of ConstraintMatrix, constraint.py:167-207) and the
+// GEMM chain of ConstraintPropagation; kernels in constraint.hip and gemm_f64.hip.
 #include "handle.h"
 
 // ------------------------------------------------------------------------------
@@ -26,8 +26,11 @@ int device_is_symmetric(sc_handle h, const double* m, int n, int ld, bool* out) 
 // Every product runs on the fp64 MFMA GEMM (C = X Y^T).  For a symmetric A all factors
 // are symmetric and commute, so squarings and T updates compute the upper tile triangle
 // only; a general A carries explicit transposes instead.
+// `banded`: Q is the matrix sc_set_constraint_band describes by `band` (n - 1 values, none for
+// n = 1); q is not read and T^T Q^T is one streaming pass instead of a GEMM.
 static int constraint_propagation(sc_handle h, const double* a, bool sym_a, const double* q,
-                                  bool sym_q, double alpha, double* out, int n, int ld) {
+                                  bool sym_q, const double* band, bool banded, double alpha,
+                                  double* out, int n, int ld) {
   hipStream_t s = h->stream;
   const double mag = fabs(alpha);
   if (!(mag < 1.0))
@@ -81,26 +84,35 @@ static int constraint_propagation(sc_handle h, const double* a, bool sym_a, cons
     launch_transpose(s, T, Tn, n, ld);
     Tt = Tn;
   }
-  launch_gemm_nt(s, Tt, ld, q, ld, X, ld, n, n, n, kEpiNone, false, ws, nullptr);
+  if (banded)
+    launch_cp_band_product(s, Tt, band, X, n, ld);
+  else
+    launch_gemm_nt(s, Tt, ld, q, ld, X, ld, n, n, n, kEpiNone, false, ws, nullptr);
   const bool sym_f = sym_a && sym_q;
   launch_gemm_nt(s, T, ld, X, ld, Pn, ld, n, n, n, kEpiNone, sym_f, ws, sym_f ? tm : nullptr);
   launch_cp_adjust(s, Pn, a, (1.0 - alpha) * (1.0 - alpha), out, n, ld);
   return check_last(h, "constraint propagation launch");
 }
 
-// cfg's constraint operator on `a` with the resident constraint matrix; out may alias a
+// cfg's constraint operator on `a` with the resident constraint (dense or banded); out may
+// alias a
 int adjust_affinity(sc_handle h, const sc_config* cfg, const double* a, bool sym_a,
                            double* out, int n, int ld) {
   if (cfg->constraint_name == SC_CONSTRAINT_AFFINITY_INTEGRATION) {
     if (cfg->integration_type != SC_INTEGRATION_MAX &&
         cfg->integration_type != SC_INTEGRATION_AVERAGE)
       return fail(h, SC_ERR_INVALID, "Unsupported integration type");
-    launch_affinity_integration(h->stream, a, ptr<double>(h->Cq), out, n, ld,
-                                cfg->integration_type);
+    if (h->constraint_banded)
+      launch_affinity_integration_band(h->stream, a, ptr<double>(h->Cband), out, n, ld,
+                                       cfg->integration_type);
+    else
+      launch_affinity_integration(h->stream, a, ptr<double>(h->Cq), out, n, ld,
+                                  cfg->integration_type);
     return check_last(h, "affinity integration launch");
   }
   if (cfg->constraint_name == SC_CONSTRAINT_PROPAGATION)
     return constraint_propagation(h, a, sym_a, ptr<double>(h->Cq), h->constraint_symmetric,
+                                  ptr<double>(h->Cband), h->constraint_banded,
                                   cfg->constraint_alpha, out, n, ld);
   return fail(h, SC_ERR_INVALID, "constraint_name must be a ConstraintName");
 }
@@ -114,6 +126,28 @@ extern "C" int sc_set_constraint(sc_handle h, const double* q, int n) {
   SC_TRY(h2d_matrix(h, q, n, n, ptr<double>(h->Cq), ld));
   SC_TRY(device_is_symmetric(h, ptr<double>(h->Cq), n, ld, &h->constraint_symmetric));
   h->have_constraint = true;
+  h->constraint_banded = false;
+  h->qn = n;
+  return SC_OK;
+}
+
+// ConstraintMatrix.compute_diagonals (constraint.py:188-201) without the matrix: n - 1 doubles
+// up, nothing else (a band is symmetric by construction)
+extern "C" int sc_set_constraint_band(sc_handle h, const double* band, int n) {
+  if (!h) return SC_ERR_INVALID;
+  if (n <= 0 || (!band && n > 1))
+    return fail(h, SC_ERR_INVALID, "constraint band must hold n - 1 values");
+  SC_HIP(h, hipSetDevice(h->device));
+  const size_t bytes = (size_t)(n - 1) * sizeof(double);
+  SC_TRY(grow(h, h->Cband, bytes));
+  if (bytes > 0) {
+    SC_HIP(h, hipMemcpyAsync(h->Cband.p, band, bytes, hipMemcpyHostToDevice, h->stream));
+    // (pageable source: the caller's array may change once this returns)
+    SC_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  h->have_constraint = true;
+  h->constraint_banded = true;
+  h->constraint_symmetric = true;
   h->qn = n;
   return SC_OK;
 }
@@ -121,7 +155,18 @@ extern "C" int sc_set_constraint(sc_handle h, const double* q, int n) {
 extern "C" int sc_clear_constraint(sc_handle h) {
   if (!h) return SC_ERR_INVALID;
   h->have_constraint = false;
+  h->constraint_banded = false;
   h->qn = 0;
+  return SC_OK;
+}
+
+extern "C" int sc_constraint_info(sc_handle h, int* kind, int* n, size_t* band_bytes,
+                                  size_t* dense_bytes) {
+  if (!h) return SC_ERR_INVALID;
+  if (kind) *kind = !h->have_constraint ? 0 : (h->constraint_banded ? 2 : 1);
+  if (n) *n = h->have_constraint ? h->qn : 0;
+  if (band_bytes) *band_bytes = h->Cband.bytes;
+  if (dense_bytes) *dense_bytes = h->Cq.bytes;
   return SC_OK;
 }
 
@@ -161,6 +206,21 @@ extern "C" int sc_stage_constraint(sc_handle h, const sc_config* cfg, const doub
     return fail(h, SC_ERR_INVALID, "affinity and constraint matrix must be (n, n)");
   SC_TRY(sc_set_affinity(h, affinity, n));
   SC_TRY(sc_set_constraint(h, q, n));
+  const int rc = sc_apply_constraint(h, cfg);
+  sc_clear_constraint(h);
+  SC_TRY(rc);
+  return d2h_matrix(h, ptr<double>(h->A0), h->ldn, n, n, out);
+}
+
+extern "C" int sc_stage_constraint_band(sc_handle h, const sc_config* cfg,
+                                        const double* affinity, const double* band, int n,
+                                        double* out) {
+  if (!h) return SC_ERR_INVALID;
+  SC_TRY(validate_config(h, cfg));
+  if (!affinity || !out || n <= 0 || (!band && n > 1))
+    return fail(h, SC_ERR_INVALID, "affinity must be (n, n) and the band hold n - 1 values");
+  SC_TRY(sc_set_affinity(h, affinity, n));
+  SC_TRY(sc_set_constraint_band(h, band, n));
   const int rc = sc_apply_constraint(h, cfg);
   sc_clear_constraint(h);
   SC_TRY(rc);

@@ -57,7 +57,10 @@ struct sc_handle_s {
   DevBuf cropval, statp;  // fused GEMM row statistics: result + per-tile partials
   // constraints: Cq (resident constraint matrix), Neumann-product work matrices, flag word
   DevBuf Cq, cp[5], symflag;
+  // ... or its banded form (sc_set_constraint_band): the n - 1 values of the first off-diagonals
+  DevBuf Cband;
   bool have_constraint = false, constraint_symmetric = false, constraint_applied = false;
+  bool constraint_banded = false;  // the resident constraint is Cband, not Cq
   bool affinity_symmetric = true;
   bool affinity_from_embeddings = false;  // symflag[1] then says whether a row was NaN
   int qn = 0;

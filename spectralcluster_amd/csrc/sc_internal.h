@@ -140,6 +140,12 @@ void launch_symmetrize(hipStream_t s, const double* in, double* out, int n, int 
 // constraint.hip (reference constraint.py:95-164)
 void launch_affinity_integration(hipStream_t s, const double* a, const double* q, double* out,
                                  int n, int ld, int type);
+// ... against a banded Q: band[i] = Q[i, i+1] = Q[i+1, i], n - 1 values, 0 elsewhere
+void launch_affinity_integration_band(hipStream_t s, const double* a, const double* band,
+                                      double* out, int n, int ld, int type);
+// x = tt Q^T for that Q (tt: T, or its transpose for a general affinity); x must not alias tt
+void launch_cp_band_product(hipStream_t s, const double* tt, const double* band, double* x,
+                            int n, int ld);
 void launch_cp_prepare(hipStream_t s, const double* a, const double* deg, double alpha,
                        double* p, double* t0, int n, int ld);
 void launch_cp_adjust(hipStream_t s, const double* tqt, const double* a, double scale,

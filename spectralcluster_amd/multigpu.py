@@ -602,7 +602,8 @@ def predict_autotune_distributed(comm: Comm, clusterer, embeddings: np.ndarray,
   the rank that evaluated the winner adopts its eigenvectors from the sweep
   (sc_sweep_adopt), runs k-means and broadcasts the labels (n int32): identical labels
   everywhere, no n x n or n x k matrix ever crosses xGMI.  Constraints are handled as in
-  predict() (reference spectral_clusterer.py:259-264, 137-142)."""
+  predict() (reference spectral_clusterer.py:259-264, 137-142): `constraint_matrix` is an
+  (n, n) array, or a `ConstraintMatrix`, whose band of n - 1 values travels instead."""
   from spectralcluster_amd import _lib
   tuner = clusterer.autotune
   if tuner is None:

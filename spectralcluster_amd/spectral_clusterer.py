@@ -4,7 +4,8 @@ reference `spectralcluster/spectral_clusterer.py`, with the dense hot path
 executed on one MI355X through the C ABI in `include/spectralcluster_amd.h`.
 
 Constraints (`constraint_options` + `predict(embeddings, constraint_matrix)`) run on the
-device too, and refinement sequences whose result is not
+device too; `constraint_matrix` may be a `ConstraintMatrix`, whose
+band travels instead of an (n, n) array.  Refinement sequences whose result is not
 diagonally similar to a symmetric matrix take the general eigen path (8f-N2);
 `max_spectral_size` pre-clusters on the device (cosine complete-linkage AHC) and
 `fallback_options` (too-few-embeddings fallback, single-cluster test for min_clusters=1) run
@@ -131,10 +132,18 @@ class SpectralClusterer:
   def _set_constraint(self, handle: _lib.Handle, n: int, constraint_matrix) -> bool:
     """Make `constraint_matrix` resident (or clear a stale one).  Like the reference
     (spectral_clusterer.py:137-142, 259-264) it is used only when both
-    `constraint_options` and the matrix are given."""
+    `constraint_options` and the matrix are given.  A `ConstraintMatrix` goes up as its band
+    of n - 1 values (`sc_set_constraint_band`), anything else as a dense (n, n) array."""
     if self.constraint_options is None or constraint_matrix is None:
       handle.check(handle.lib.sc_clear_constraint(handle.raw))
       return False
+    if isinstance(constraint_matrix, constraint_lib.ConstraintMatrix):
+      self.constraint_options.constraint_operator.check_input(
+          np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)),
+          constraint_matrix)
+      band = np.ascontiguousarray(constraint_matrix.band(), dtype=np.float64)
+      handle.check(handle.lib.sc_set_constraint_band(handle.raw, _lib.as_double_p(band), n))
+      return True
     con = np.asarray(constraint_matrix)
     # ConstraintOperation.check_input against the (n, n) affinity: only its shape is read
     self.constraint_options.constraint_operator.check_input(
@@ -347,7 +356,9 @@ class SpectralClusterer:
   # -------------------------------------------------------------- batch (new)
   def predict_batch(self, utterances: typing.Sequence[np.ndarray],
                     streams: typing.Optional[int] = None,
-                    group: typing.Optional[int] = None) -> typing.List[np.ndarray]:
+                    group: typing.Optional[int] = None,
+                    constraint_matrices: typing.Optional[typing.Sequence] = None
+                    ) -> typing.List[np.ndarray]:
     """Independent predict() calls (the reference has no batch API: a batch is a
     Python loop).
 
@@ -367,7 +378,16 @@ class SpectralClusterer:
     with a different basis size (eigenvalues within 1e-6 relative, labels equal unless an
     eigengap decision is a near tie).  A batch call is deterministic: the same list gives
     the same results.
+
+    `constraint_matrices`: one `ConstraintMatrix` / ndarray / None per utterance.  With it (and
+    `constraint_options`) the batch runs as per-utterance `predict(u, c)` calls; without it a
+    batch carries no constraints.
     """
+    if constraint_matrices is not None:
+      if len(constraint_matrices) != len(utterances):
+        raise ValueError("constraint_matrices must be as long as the batch")
+      if self.constraint_options is not None:
+        return [self.predict(u, c) for u, c in zip(utterances, constraint_matrices)]
     if group is None:
       group = 16 if streams is None else 0
     if streams is None:
