@@ -1,7 +1,7 @@
 // C ABI (include/spectralcluster_amd.h) and host-side orchestration: device arena,
-// the refinement / Laplacian / eigen / k-means pipeline, the eigengap scalar loop and the
-// MT19937 stream that seeds k-means++.  (Eigen control loops: eig_driver.hip; constraints:
-// constraint_api.hip; size reduction and fallback decisions: callers_api.hip.)
+// the refinement / Laplacian / eigen pipeline, the eigengap scalar loop and the MT19937 stream
+// that seeds k-means++.  (Eigen control loops: eig_driver.hip; constraints: constraint_api.hip;
+// size reduction and fallback decisions: callers_api.hip; the k-means stage: kmeans_api.hip.)
 // Host code only decides and launches; every O(n) or larger computation runs in
 // the HIP kernels of this library.
 #include <algorithm>
@@ -131,28 +131,6 @@ int ensure_gen(sc_handle h, int n) {
   SC_TRY(grow(h, h->gpart, (size_t)gen_residual_blocks(n) * 32 * sizeof(double)));
   SC_TRY(grow(h, h->gsrc, 16 * sizeof(int)));
   SC_TRY(grow(h, h->genL, (size_t)kGenMax * kGenMax * sizeof(double)));
-  return SC_OK;
-}
-
-int ensure_kmeans(sc_handle h, int n, int k) {
-  const int cols = std::max(k, kMaxCols), kk = std::max(k, kMaxVectors);
-  SC_TRY(grow(h, h->Ek, (size_t)round_up(n, 16) * cols * sizeof(double)));
-  SC_TRY(grow(h, h->Eio, (size_t)n * cols * sizeof(double)));
-  SC_TRY(grow(h, h->kXc, (size_t)n * kk * sizeof(double)));
-  SC_TRY(grow(h, h->kxsq, (size_t)n * sizeof(double)));
-  SC_TRY(grow(h, h->kclosest, (size_t)n * sizeof(double)));
-  SC_TRY(grow(h, h->kcand, (size_t)(k > kMaxVectors ? 16 : 8) * n * sizeof(double)));
-  SC_TRY(grow(h, h->kenorm, (size_t)n * sizeof(double)));
-  SC_TRY(grow(h, h->krnd, (size_t)std::max(1024, 16 * kk) * sizeof(double)));
-  SC_TRY(grow(h, h->kcent, (size_t)kk * kk * sizeof(double)));
-  if (k > kMaxVectors) {  // the large-k form keeps its per-cluster arrays in global memory
-    SC_TRY(grow(h, h->kbig, kmeans_big_workspace_doubles(k) * sizeof(double)));
-    SC_TRY(grow(h, h->kbigw, (size_t)3 * k * sizeof(int)));
-  }
-  SC_TRY(grow(h, h->klab32, (size_t)n * sizeof(int)));
-  SC_TRY(grow(h, h->klab64, (size_t)n * sizeof(long long)));
-  SC_TRY(grow(h, h->kinfo, 16 * sizeof(int)));
-  SC_TRY(grow(h, h->kchain, kmeans_chain_workspace_doubles(n) * sizeof(double)));
   return SC_OK;
 }
 
@@ -1050,156 +1028,6 @@ extern "C" int sc_get_eigenvectors(sc_handle h, double* out, int n, int ncols) {
 }
 
 // ------------------------------------------------------------------------------
-// k-means tail
-// ------------------------------------------------------------------------------
-void kmeans_seed_constants(int k, double* u_first, int* trials, std::vector<double>* rnd) {
-  Mt19937 rng(0);
-  *u_first = rng.next_double();
-  *trials = 2 + (int)std::log((double)k);
-  const size_t nrnd = (size_t)std::max(1, (k - 1) * *trials);
-  rnd->resize(nrnd);
-  for (size_t i = 0; i < nrnd; ++i) (*rnd)[i] = rng.next_double();
-}
-
-KmeansWorkspace kmeans_workspace(sc_handle h) {
-  KmeansWorkspace ws;
-  ws.Xc = ptr<double>(h->kXc);
-  ws.xsq = ptr<double>(h->kxsq);
-  ws.closest = ptr<double>(h->kclosest);
-  ws.cand = ptr<double>(h->kcand);
-  ws.enorm = ptr<double>(h->kenorm);
-  ws.rnd = ptr<double>(h->krnd);
-  ws.centroids = ptr<double>(h->kcent);
-  ws.labels32 = ptr<int>(h->klab32);
-  ws.labels64 = ptr<long long>(h->klab64);
-  ws.info = ptr<int>(h->kinfo);
-  ws.chain = ptr<double>(h->kchain);
-  ws.big = ptr<double>(h->kbig);
-  ws.big_words = ptr<int>(h->kbigw);
-  return ws;
-}
-
-static int kmeans_on_device(sc_handle h, const double* E, int lde, int n, int k, int max_iter,
-                            int64_t* labels, double* centroids_out, int* iterations,
-                            int metric = kKmeansCosine) {
-  if (metric < kKmeansCosine || metric > kKmeansCanberra)
-    return fail(h, SC_ERR_UNSUPPORTED,
-                "custom_dist on the device: cosine, euclidean (minkowski), sqeuclidean, "
-                "cityblock, chebyshev, correlation, braycurtis, canberra");
-  if (max_iter <= 0)
-    return fail(h, SC_ERR_INVALID, "Number of iterations should be a positive number");
-  if (n < k) return fail(h, SC_ERR_INVALID, "n_samples should be >= n_clusters");
-  if (k < 1) return fail(h, SC_ERR_INVALID, "n_clusters must be positive");
-  SC_TRY(ensure_kmeans(h, n, k));
-  // RandomState(0): first centre via choice(n, p=uniform) = cdf.searchsorted(u, 'right')
-  Mt19937 rng(0);
-  const double u = rng.next_double();
-  if (h->kfirst_n != n) {  // (two passes of n dependent adds: ~20 us at n = 8192)
-    h->kfirst = sc_uniform_choice(n, u);
-    h->kfirst_n = n;
-  }
-  const int first = h->kfirst;
-  const int trials = 2 + (int)std::log((double)k);
-  const size_t nrnd = (size_t)std::max(1, (k - 1) * trials);
-  // k-means++ draws 2 + int(log k) candidates per centre (sklearn): at most 6 up to 64 centres
-  // (8 slots), 16 slots in the large-k form (any k an int holds)
-  if (trials > (k > kMaxVectors ? 16 : 8))
-    return fail(h, SC_ERR_UNSUPPORTED, "too many k-means++ trials");
-  if (h->krnd_k != k || h->krnd_trials != trials) {  // RandomState(0) doubles: a function of k
-    std::vector<double> rnd(nrnd);
-    for (size_t i = 0; i < nrnd; ++i) rnd[i] = rng.next_double();
-    SC_HIP(h, hipMemcpyAsync(h->krnd.p, rnd.data(), nrnd * sizeof(double),
-                             hipMemcpyHostToDevice, h->stream));
-    SC_HIP(h, hipStreamSynchronize(h->stream));  // rnd is a local
-    h->krnd_k = k;
-    h->krnd_trials = trials;
-  }
-  const KmeansWorkspace ws = kmeans_workspace(h);
-  int info[16] = {0};
-  if (metric == kKmeansCosine && kmeans_chain_supported(n, k, trials) &&
-      !sw::kmeans_single()) {
-    // chain of short multi-workgroup kernels; cosine iterations four launches at a time
-    // (the typical run stops after two or three), `done` comes back with the labels
-    for (int it = 0;; it += 4) {
-      launch_kmeans_chain(h->stream, E, lde, n, k, max_iter, first, trials, ws, it, 4);
-      SC_TRY(check_last(h, "kmeans launch"));
-      SC_HIP(h, hipMemcpyAsync(labels, h->klab64.p, (size_t)n * sizeof(int64_t),
-                               hipMemcpyDeviceToHost, h->stream));
-      SC_HIP(h, hipMemcpyAsync(info, h->kinfo.p, 9 * sizeof(int), hipMemcpyDeviceToHost,
-                               h->stream));
-      SC_HIP(h, hipStreamSynchronize(h->stream));
-      if (info[8] != 0) break;
-      if (it > max_iter + 4)
-        return fail(h, SC_ERR_HIP, "k-means chain did not reach its stop rule");
-    }
-    if (centroids_out) {
-      SC_HIP(h, hipMemcpyAsync(centroids_out, h->kcent.p, (size_t)k * k * sizeof(double),
-                               hipMemcpyDeviceToHost, h->stream));
-      SC_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    if (iterations) *iterations = info[0];
-    return SC_OK;
-  }
-  SC_HIP(h, hipMemsetAsync(h->kinfo.p, 0, 8 * sizeof(int), h->stream));
-  launch_kmeans(h->stream, E, lde, n, k, max_iter, first, trials, ws, metric);
-  SC_TRY(check_last(h, "kmeans launch"));
-  SC_HIP(h, hipMemcpyAsync(labels, h->klab64.p, (size_t)n * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, h->stream));
-  SC_HIP(h, hipMemcpyAsync(info, h->kinfo.p, 6 * sizeof(int), hipMemcpyDeviceToHost,
-                           h->stream));
-  if (centroids_out)
-    SC_HIP(h, hipMemcpyAsync(centroids_out, h->kcent.p, (size_t)k * k * sizeof(double),
-                             hipMemcpyDeviceToHost, h->stream));
-  SC_HIP(h, hipStreamSynchronize(h->stream));
-  if (iterations) *iterations = info[0];
-  if (sw::kmeans_trace())
-    fprintf(stderr, "[sc] kmeans n=%d k=%d iters=%d  us: centre %.1f  kmeans++ %.1f  lloyd %.1f"
-            "  cosine-loop %.1f\n", n, k, info[0], info[1] * 0.01, (info[2] - info[1]) * 0.01,
-            (info[3] - info[2]) * 0.01, (info[4] - info[3]) * 0.01);
-  if (sw::kmeans_trace() && k > kMaxVectors) {  // the large-k form keeps its seeds in global memory
-    std::vector<int> seeds(k);
-    hipMemcpy(seeds.data(), h->kbigw.p, (size_t)k * sizeof(int), hipMemcpyDeviceToHost);
-    fprintf(stderr, "[sc] kmeans++ seeds:");
-    for (int i = 0; i < k; ++i) fprintf(stderr, " %d", seeds[i]);
-    fprintf(stderr, "\n");
-  }
-  return SC_OK;
-}
-
-extern "C" int sc_cluster(sc_handle h, const sc_config* cfg, int n_clusters, int64_t* labels,
-                          sc_diag* diag) {
-  if (!h) return SC_ERR_INVALID;
-  if (!cfg || !labels) return fail(h, SC_ERR_INVALID, "NULL argument");
-  if (h->n_vec <= 0) return fail(h, SC_ERR_INVALID, "no eigenvectors resident");
-  if (n_clusters < 1 || n_clusters > h->n_vec)
-    return fail(h, SC_ERR_INVALID, "n_clusters exceeds the resident eigenvectors");
-  SC_HIP(h, hipSetDevice(h->device));
-  const int n = h->n;
-  int e0, e1;
-  ev_rec(h, &e0);
-  const double* E = ptr<double>(h->E);
-  const int lde = round_up(n, 16);
-  if (cfg->row_wise_renorm) {
-    SC_TRY(ensure_kmeans(h, n, n_clusters));
-    SC_HIP(h, hipMemcpyAsync(h->Ek.p, h->E.p, (size_t)lde * n_clusters * sizeof(double),
-                             hipMemcpyDeviceToDevice, h->stream));
-    launch_row_renorm(h->stream, ptr<double>(h->Ek), lde, n, n_clusters);
-    E = ptr<double>(h->Ek);
-  }
-  int iters = 0;
-  SC_TRY(kmeans_on_device(h, E, lde, n, n_clusters, cfg->max_iter, labels, nullptr, &iters,
-                          cfg->kmeans_metric));
-  ev_rec(h, &e1);
-  SC_HIP(h, hipStreamSynchronize(h->stream));
-  if (diag) {
-    diag->n_clusters = n_clusters;
-    diag->kmeans_iterations = iters;
-    diag->stage_ms[SC_STAGE_KMEANS] = ev_ms(h, e0, e1);
-  }
-  return SC_OK;
-}
-
-// ------------------------------------------------------------------------------
 // whole path
 // ------------------------------------------------------------------------------
 extern "C" int sc_run_resident(sc_handle h, const sc_config* cfg, int64_t* labels,
@@ -1632,25 +1460,4 @@ extern "C" int sc_stage_eig(sc_handle h, const double* m, int n, int count, int 
     SC_TRY(d2h_matrix(h, ptr<double>(h->Eio), count, n, count, vectors));
   }
   return SC_OK;
-}
-
-extern "C" int sc_stage_kmeans_metric(sc_handle h, const double* e, int n, int k, int max_iter,
-                                      int metric, int64_t* labels, double* centroids_out,
-                                      int* iterations) {
-  if (!h) return SC_ERR_INVALID;
-  if (!e || !labels || n <= 0 || k <= 0) return fail(h, SC_ERR_INVALID, "bad k-means input");
-  SC_HIP(h, hipSetDevice(h->device));
-  SC_TRY(ensure_kmeans(h, n, k));
-  SC_HIP(h, hipMemcpyAsync(h->Eio.p, e, (size_t)n * k * sizeof(double), hipMemcpyHostToDevice,
-                           h->stream));
-  launch_to_colmajor(h->stream, ptr<double>(h->Eio), n, k, ptr<double>(h->Ek),
-                     round_up(n, 16));
-  return kmeans_on_device(h, ptr<double>(h->Ek), round_up(n, 16), n, k, max_iter, labels,
-                          centroids_out, iterations, metric);
-}
-
-extern "C" int sc_stage_kmeans(sc_handle h, const double* e, int n, int k, int max_iter,
-                               int64_t* labels, double* centroids_out, int* iterations) {
-  return sc_stage_kmeans_metric(h, e, n, k, max_iter, SC_KMEANS_COSINE, labels, centroids_out,
-                                iterations);
 }

@@ -1,5 +1,5 @@
 // Internal to the host side of the library (api.hip, eig_driver.hip, constraint_api.hip,
-// callers_api.hip): the handle with its device arena, error plumbing, and the helpers those
+// callers_api.hip, kmeans_api.hip): the handle with its device arena, error plumbing, and the helpers those
 // translation units share.  Not installed; the public surface is
 // include/spectralcluster_amd.h.
 #ifndef SPECTRALCLUSTER_AMD_HANDLE_H_
@@ -88,7 +88,7 @@ struct sc_handle_s {
   // k-means workspace
   DevBuf kXc, kxsq, kclosest, kcand, kenorm, krnd, kcent, klab32, klab64, kinfo, kchain;
   DevBuf kbig, kbigw;     // more than kMaxVectors clusters: per-cluster arrays of k_kmeans<true>
-  DevBuf kgen[kKgenBufs];  // sc_stage_kmeans_general (kmeans_general.hip): any (n, dim, k)
+  DevBuf kgen[kKgenBufs];  // sc_stage_kmeans_general (kmeans_api.hip): any (n, dim, k)
   // pinned host scratch
   double* h_theta = nullptr;  // 3 * kLdq doubles (theta, resid, Im theta)
   int* h_flags = nullptr;
@@ -321,7 +321,7 @@ int upload_blur_weights(sc_handle h, const sc_config* cfg);  // into h->blurw, o
 int eig_ncluster_impl(sc_handle h, const sc_config* cfg, sc_diag* diag, FrontResult* front_only,
                       const FrontResult* resume = nullptr, bool defer_timing = false);
 // RandomState(0) stream of the k-means seeding: the uniform that picks the first centre, the
-// trial count 2 + int(log k), and the (k - 1) * trials doubles after it (api.hip)
+// trial count 2 + int(log k), and the (k - 1) * trials doubles after it (kmeans_api.hip)
 void kmeans_seed_constants(int k, double* u_first, int* trials, std::vector<double>* rnd);
 KmeansWorkspace kmeans_workspace(sc_handle h);
 

@@ -28,6 +28,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "kmeans_common.h"
 #include "sc_internal.h"
 
 namespace sc {
@@ -60,23 +61,6 @@ struct KmChain {
   int* cand[2];   // [8]
   int* info;      // [0] iterations, [8] done
 };
-
-__device__ __forceinline__ double km_wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-// sum over the workgroup, same value in every thread; sm: kKmW doubles
-__device__ __forceinline__ double km_bsum(double v, double* sm) {
-  v = km_wsum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < kKmW; ++w) t += sm[w];
-  return t;
-}
 
 // Sum of src[g * stride], g = 0 .. G-1, in that order.  The partials were written by
 // workgroups on other XCDs, so every load is a miss (~1 us): they are issued in independent
@@ -125,7 +109,7 @@ __device__ __forceinline__ void km_colsum_body(const KmChain& a) {
   km_load_row<KC>(a, r, v);
 #pragma unroll
   for (int j = 0; j < KC; ++j) {
-    const double s = km_wsum(v[j]);
+    const double s = wave_sum(v[j]);
     if ((tid & 63) == 0) sm[tid >> 6][j] = s;
   }
   __syncthreads();
@@ -192,7 +176,7 @@ __device__ __forceinline__ void km_first_body(const KmChain& a) {
     a.xsq[r] = xs;
     a.closest[r] = d;
   }
-  const double tot = km_bsum(d, sm);
+  const double tot = block_sum<kKmW>(d, sm);
   if (tid == 0) a.ppot[blockIdx.x] = tot;
   if (blockIdx.x == 0) {
     if (tid == 0) {
@@ -347,7 +331,7 @@ __device__ __forceinline__ void km_trials_body(const KmChain& a, int c) {
   for (int t = 0; t < a.trials; ++t) {
     double d = 0.0;
     if (r < a.n) d = fmin(cl, km_dist<KC>(v, mean, crow[t], csq[t], xs, a.k));
-    const double tot = km_bsum(d, sm);
+    const double tot = block_sum<kKmW>(d, sm);
     if (tid == 0) a.pT[(size_t)blockIdx.x * 8 + t] = tot;
   }
   if (blockIdx.x == 0 && tid < 8) a.cand[(c + 1) & 1][tid] = a.n - 1;
@@ -556,7 +540,7 @@ __device__ __forceinline__ void km_cosine_body(const KmChain& a, int it) {
     }
   }
   if (r < a.n) a.labels64[r] = best;
-  const double dsum = km_bsum(r < a.n ? bd : 0.0, sm);
+  const double dsum = block_sum<kKmW>(r < a.n ? bd : 0.0, sm);
   if (tid == 0) a.pD[(it + 1) & 1][blockIdx.x] = dsum;
   km_cluster_partials<KC>(a, v, zero, best, r, vals, labs,
                           a.pS[(it + 1) & 1] + (size_t)blockIdx.x * nsum);

@@ -21,113 +21,22 @@
 //   * the serial steps (k-means++ cumsum + searchsorted, argmin of the trial pots, the stop
 //     rule) are short single-workgroup launches.
 // Every sum is taken in a fixed order, so two calls give bit-identical results.  The library
-// is compiled with -ffp-contract=off; the per-metric arithmetic restates kmeans.hip's loop.
-#include <algorithm>
-#include <cmath>
-#include <vector>
-
-#include "handle.h"
+// is compiled with -ffp-contract=off; the per-metric arithmetic is kmeans_common.h's, shared with
+// kmeans.hip.  Kernels and launchers only: sc_stage_kmeans_general drives them (kmeans_api.hip).
+#include "kmeans_common.h"
+#include "sc_internal.h"
 
 namespace sc {
 namespace {
 
 constexpr int KG_ROWS = 64;   // rows (threads) per workgroup of the row passes: one wave
 constexpr int KG_JC = 256;    // centroid columns per LDS chunk
-constexpr int KG_TS = 16;     // k-means++ trial slots (2 + int(log k) used)
+constexpr int KG_TS = kKgenTrialSlots;  // k-means++ trial slots (2 + int(log k) used)
 constexpr int KG_UT = 256;    // threads of the column-parallel update / column means
 constexpr int KG_ST = 1024;   // threads of the k-means++ select launch
-constexpr int KG_ITERS = 4;   // loop iterations enqueued per host synchronisation
 
 enum { kModePP = 100, kModeLloyd = 101 };
-// int words: done, iterations, best trial of the last k-means++ pass
-enum { kWDone = 0, kWIters = 1, kWBest = 2, kWords = 4 };
-// double scalars: pot, prev mean distance
-enum { kSPot = 0, kSPrev = 1, kScalars = 4 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// numpy's pairwise sum (numpy/core/src/umath/loops_utils.h), as kmeans.hip restates it for
-// scipy's correlation row means: fewer than 8 elements one by one; up to 128 eight running sums
-// folded as a tree, then the tail; longer runs split at cnt / 2 rounded down to a multiple of 8
-template <typename At>
-__device__ double pw_leaf(At at, int lo, int cnt) {
-  double s;
-  if (cnt < 8) {
-    s = 0.0;
-    for (int j = 0; j < cnt; ++j) s += at(lo + j);
-  } else {
-    double a8[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) a8[q] = at(lo + q);
-    int j = 8;
-    for (; j < cnt - (cnt % 8); j += 8) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) a8[q] += at(lo + j + q);
-    }
-    s = ((a8[0] + a8[1]) + (a8[2] + a8[3])) + ((a8[4] + a8[5]) + (a8[6] + a8[7]));
-    for (; j < cnt; ++j) s += at(lo + j);
-  }
-  return s;
-}
-template <typename At>
-__device__ double pw_mean(At at, int m) {
-  if (m <= 128) return pw_leaf(at, 0, m) / (double)m;
-  int lo[32], cnt[32], stage[32];
-  double left[32];
-  int sp = 0;
-  lo[0] = 0;
-  cnt[0] = m;
-  stage[0] = 0;
-  double ret = 0.0;
-  while (sp >= 0) {
-    if (stage[sp] == 0) {
-      if (cnt[sp] <= 128) {
-        ret = pw_leaf(at, lo[sp], cnt[sp]);
-        --sp;
-        continue;
-      }
-      int half = cnt[sp] / 2;
-      half -= half % 8;
-      stage[sp] = 1;
-      lo[sp + 1] = lo[sp];
-      cnt[sp + 1] = half;
-      stage[sp + 1] = 0;
-      ++sp;
-    } else if (stage[sp] == 1) {
-      left[sp] = ret;
-      int half = cnt[sp] / 2;
-      half -= half % 8;
-      stage[sp] = 2;
-      lo[sp + 1] = lo[sp] + half;
-      cnt[sp + 1] = cnt[sp] - half;
-      stage[sp + 1] = 0;
-      ++sp;
-    } else {
-      ret = left[sp] + ret;
-      --sp;
-    }
-  }
-  return ret / (double)m;
-}
-
-// (n, dim) row-major -> column-major with leading dimension ld
-__global__ __launch_bounds__(256) void k_g_colmajor(const double* __restrict__ src, int n,
-                                                    int dim, double* __restrict__ dst,
-                                                    int ld) {
-  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= (size_t)n * dim) return;
-  const size_t r = e / dim, j = e - r * dim;
-  dst[j * ld + r] = src[e];
-}
+enum { kSPot = 0, kSPrev = 1 };  // double scalars: pot, prev mean distance (of kKgenScalars)
 
 // column means: one workgroup per column, thread-strided partials folded in a fixed order
 __global__ __launch_bounds__(KG_UT) void k_g_colmean(const double* __restrict__ X, int ld,
@@ -192,7 +101,7 @@ struct KgArgs {
   double* part;           // per-workgroup partial sums: (grid, KG_TS) k-means++, (grid) loop
   int* lab32;
   long long* lab64;
-  const int* words;       // kWBest (k-means++), kWDone (loop)
+  const int* words;       // kKgenBest (k-means++), kKgenDone (loop)
 };
 
 // Row pass: one row per thread against every centre, centres staged through LDS eight at a time.
@@ -203,7 +112,7 @@ template <int MODE>
 __global__ __launch_bounds__(KG_ROWS) void k_g_rows(KgArgs a) {
   constexpr bool kLoop = MODE != kModePP && MODE != kModeLloyd;
   constexpr bool kCentred = !kLoop;
-  if (kLoop && a.words[kWDone]) return;
+  if (kLoop && a.words[kKgenDone]) return;
   __shared__ double s_c[8 * KG_JC];
   __shared__ double s_m[KG_JC];
   __shared__ double s_cmx[8];
@@ -222,7 +131,7 @@ __global__ __launch_bounds__(KG_ROWS) void k_g_rows(KgArgs a) {
   if (MODE == kModePP) {
     xs = a.xsq[rr];
     if (a.cd_prev) {
-      closest = a.cd_prev + (size_t)a.words[kWBest] * a.n;
+      closest = a.cd_prev + (size_t)a.words[kKgenBest] * a.n;
       cl = closest[rr];
     }
   }
@@ -253,23 +162,11 @@ __global__ __launch_bounds__(KG_ROWS) void k_g_rows(KgArgs a) {
         for (int q = 0; q < 8; ++q) {
           if (c0 + q < a.m) {
             const double cv = s_c[q * KG_JC + jj];
-            if (kCentred || MODE == kKmeansCosine) {
+            if (kCentred)
               acc[q] += x * cv;
-            } else if (MODE == kKmeansCorrelation) {
-              acc[q] += x * (cv - s_cmx[q]);
-            } else if (MODE == kKmeansCityblock) {
-              acc[q] += fabs(x - cv);
-            } else if (MODE == kKmeansChebyshev) {
-              acc[q] = fmax(acc[q], fabs(x - cv));
-            } else if (MODE == kKmeansBraycurtis) {  // sum |u - v| / sum |u + v|
-              acc[q] += fabs(x - cv);
-              aux[q] += fabs(x + cv);
-            } else if (MODE == kKmeansCanberra) {  // sum |u - v| / (|u| + |v|), 0 / 0 = 0
-              const double den = fabs(x) + fabs(cv);
-              if (den > 0.0) acc[q] += fabs(x - cv) / den;
-            } else {  // (squared) Euclidean
-              acc[q] += (x - cv) * (x - cv);
-            }
+            else
+              metric_accumulate(MODE, x, cv, MODE == kKmeansCorrelation ? s_cmx[q] : 0.0, acc[q],
+                                aux[q]);
           }
         }
       };
@@ -297,20 +194,8 @@ __global__ __launch_bounds__(KG_ROWS) void k_g_rows(KgArgs a) {
         const double p = wave_sum(valid ? d : 0.0);
         if (tid == 0) a.part[(size_t)blockIdx.x * KG_TS + c] = p;
       } else {
-        double d;
-        if (MODE == kModeLloyd) {
-          d = a.cval[c] - 2.0 * acc[q];
-        } else if (MODE == kKmeansCosine || MODE == kKmeansCorrelation) {
-          double cosine = acc[q] / (nu * a.cval[c]);
-          if (fabs(cosine) > 1.0) cosine = copysign(1.0, cosine);
-          d = 1.0 - cosine;
-        } else if (MODE == kKmeansBraycurtis) {
-          d = acc[q] / aux[q];
-        } else if (MODE == kKmeansEuclidean) {
-          d = sqrt(acc[q]);
-        } else {
-          d = acc[q];
-        }
+        const double d = MODE == kModeLloyd ? a.cval[c] - 2.0 * acc[q]
+                                            : metric_finish(MODE, acc[q], aux[q], nu, a.cval[c]);
         if (d < bd) {  // argmin: first minimum
           bd = d;
           best = c;
@@ -357,7 +242,7 @@ __global__ __launch_bounds__(KG_ST) void k_g_select(
     for (int t = 1; t < ntr; ++t)
       if (pots[t] < pots[b]) b = t;  // np.argmin: first minimum
     s_best = b;
-    words[kWBest] = b;
+    words[kKgenBest] = b;
     seeds[c] = cand[b];
     scal[kSPot] = pots[b];
   }
@@ -447,7 +332,7 @@ __global__ __launch_bounds__(64) void k_g_cnorm(const double* __restrict__ cent,
                                                 double* __restrict__ cval,
                                                 double* __restrict__ cmx, int kind,
                                                 const int* __restrict__ words) {
-  if (words && words[kWDone]) return;
+  if (words && words[kKgenDone]) return;
   const int c = blockIdx.x * 64 + threadIdx.x;
   if (c >= k) return;
   const double* row = cent + (size_t)c * dim;
@@ -470,7 +355,7 @@ __global__ __launch_bounds__(KG_UT) void k_g_update(const double* __restrict__ X
                                                     double* __restrict__ cent,
                                                     const double* __restrict__ mean, int mode,
                                                     const int* __restrict__ words) {
-  if (mode == 1 && words[kWDone]) return;
+  if (mode == 1 && words[kKgenDone]) return;
   __shared__ double s_sum[KG_UT / 64][8];
   __shared__ int s_cnt[KG_UT / 64][8];
   const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -501,7 +386,7 @@ __global__ __launch_bounds__(KG_UT) void k_g_update(const double* __restrict__ X
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const double v = wave_sum(acc[q]);
-      const int cc = wave_sum_int(cnt[q]);
+      const int cc = wave_sum(cnt[q]);
       if (lane == 0) {
         s_sum[wave][q] = v;
         s_cnt[wave][q] = cc;
@@ -533,7 +418,7 @@ __global__ __launch_bounds__(64) void k_g_stop(const double* __restrict__ part, 
                                                int it, int max_iter, double tol,
                                                int* __restrict__ words,
                                                double* __restrict__ scal) {
-  if (words[kWDone]) return;
+  if (words[kKgenDone]) return;
   double s = 0.0;
   for (int g = threadIdx.x; g < grid; g += 64) s += part[g];
   s = wave_sum(s);
@@ -541,8 +426,8 @@ __global__ __launch_bounds__(64) void k_g_stop(const double* __restrict__ part, 
   const double mean_d = s / (double)n;
   const double prev = scal[kSPrev];
   if ((mean_d <= prev && mean_d >= (1.0 - tol) * prev) || it == max_iter) {
-    words[kWDone] = 1;
-    words[kWIters] = it + 1;
+    words[kKgenDone] = 1;
+    words[kKgenIters] = it + 1;
   } else {
     scal[kSPrev] = mean_d;
   }
@@ -566,175 +451,90 @@ void launch_loop_rows(hipStream_t s, int grid, const KgArgs& a, int metric) {
   }
 }
 
-}  // namespace
-}  // namespace sc
-
-// workspace of sc_stage_kmeans_general: the handle's kgen buffers, grown on demand, never shared
-// with the predict() path
-enum { kgX, kgIo, kgRow, kgVec, kgCd, kgPart, kgRnd, kgLab32, kgLab64, kgInt, kgCount };
-static_assert(kgCount <= kKgenBufs, "handle.h kgen buffers");
-
-static int ensure_kmeans_general(sc_handle h, int n, int dim, int k, int trials, int grid) {
-  const size_t ld = round_up(n, 16);
-  SC_TRY(grow(h, h->kgen[kgX], ld * dim * sizeof(double)));
-  SC_TRY(grow(h, h->kgen[kgIo], (size_t)n * dim * sizeof(double)));
-  SC_TRY(grow(h, h->kgen[kgRow], 4 * ld * sizeof(double)));
-  // mean (dim) | centroids (k dim) | cval (k) | cmx (k) | trial rows (KG_TS dim) | csq (KG_TS)
-  // | scalars
-  SC_TRY(grow(h, h->kgen[kgVec],
-              ((size_t)dim * (1 + k + KG_TS) + 2 * (size_t)k + KG_TS + kScalars) *
-                  sizeof(double)));
-  SC_TRY(grow(h, h->kgen[kgCd], 2 * (size_t)KG_TS * n * sizeof(double)));
-  SC_TRY(grow(h, h->kgen[kgPart], (size_t)grid * KG_TS * sizeof(double)));
-  SC_TRY(grow(h, h->kgen[kgRnd], (size_t)std::max(1, (k - 1) * trials) * sizeof(double)));
-  SC_TRY(grow(h, h->kgen[kgLab32], (size_t)n * sizeof(int)));
-  SC_TRY(grow(h, h->kgen[kgLab64], (size_t)n * sizeof(long long)));
-  // seeds (k) | trial rows' indices (KG_TS) | words
-  SC_TRY(grow(h, h->kgen[kgInt], ((size_t)k + KG_TS + kWords) * sizeof(int)));
-  return SC_OK;
-}
-
-extern "C" int sc_stage_kmeans_general(sc_handle h, const double* x, int n, int dim, int k,
-                                       int max_iter, int metric, double tol,
-                                       const double* init_centroids, int64_t* labels,
-                                       double* centroids_out, int* iterations) {
-  if (!h) return SC_ERR_INVALID;
-  if (!x || !labels || n <= 0 || dim <= 0 || k <= 0)
-    return fail(h, SC_ERR_INVALID, "bad k-means input");
-  if ((long long)n * dim > 0x7fffffffLL)
-    return fail(h, SC_ERR_INVALID, "k-means input larger than 2^31 elements");
-  if (metric < kKmeansCosine || metric > kKmeansCanberra)
-    return fail(h, SC_ERR_UNSUPPORTED,
-                "custom_dist on the device: cosine, euclidean (minkowski), sqeuclidean, "
-                "cityblock, chebyshev, correlation, braycurtis, canberra");
-  if (max_iter <= 0)
-    return fail(h, SC_ERR_INVALID, "Number of iterations should be a positive number");
-  if (n < k) return fail(h, SC_ERR_INVALID, "n_samples should be >= n_clusters");
-  const int trials = 2 + (int)std::log((double)k);
-  if (trials > KG_TS) return fail(h, SC_ERR_UNSUPPORTED, "too many k-means++ trials");
-  SC_HIP(h, hipSetDevice(h->device));
-  const int ld = round_up(n, 16);
-  const int grid = (n + KG_ROWS - 1) / KG_ROWS;
-  SC_TRY(ensure_kmeans_general(h, n, dim, k, trials, grid));
-  hipStream_t s = h->stream;
-  double* X = ptr<double>(h->kgen[kgX]);
-  double* row = ptr<double>(h->kgen[kgRow]);
-  double *xsq = row, *enorm = row + ld, *rmx = row + 2 * (size_t)ld, *cnu = row + 3 * (size_t)ld;
-  double* vec = ptr<double>(h->kgen[kgVec]);
-  double* mean = vec;
-  double* cent = mean + dim;
-  double* cval = cent + (size_t)k * dim;
-  double* cmx = cval + k;
-  double* crow = cmx + k;
-  double* csq = crow + (size_t)KG_TS * dim;
-  double* scal = csq + KG_TS;
-  double* cd = ptr<double>(h->kgen[kgCd]);
-  double* part = ptr<double>(h->kgen[kgPart]);
-  double* rnd = ptr<double>(h->kgen[kgRnd]);
-  int* lab32 = ptr<int>(h->kgen[kgLab32]);
-  long long* lab64 = ptr<long long>(h->kgen[kgLab64]);
-  int* seeds = ptr<int>(h->kgen[kgInt]);
-  int* cand = seeds + k;
-  int* words = cand + KG_TS;
-
-  SC_HIP(h, hipMemcpyAsync(h->kgen[kgIo].p, x, (size_t)n * dim * sizeof(double),
-                           hipMemcpyHostToDevice, s));
-  const size_t nel = (size_t)n * dim;
-  hipLaunchKernelGGL(k_g_colmajor, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, s,
-                     ptr<double>(h->kgen[kgIo]), n, dim, X, ld);
-  SC_HIP(h, hipMemsetAsync(words, 0, kWords * sizeof(int), s));
-  SC_HIP(h, hipMemsetAsync(scal, 0, kScalars * sizeof(double), s));
-  hipLaunchKernelGGL(k_g_colmean, dim3(dim), dim3(KG_UT), 0, s, X, ld, n, mean);
-  hipLaunchKernelGGL(k_g_rowstats, dim3(grid), dim3(KG_ROWS), 0, s, X, ld, n, dim, mean, xsq,
-                     enorm, rmx, cnu, metric == kKmeansCorrelation ? 1 : 0);
-
+KgArgs kg_args(const KmeansGeneralWorkspace& ws, int n, int dim) {
   KgArgs a{};
-  a.X = X;
-  a.ld = ld;
+  a.X = ws.X;
+  a.ld = ws.ld;
   a.n = n;
   a.dim = dim;
-  a.mean = mean;
-  a.xsq = xsq;
-  a.enorm = enorm;
-  a.rmx = rmx;
-  a.cnu = cnu;
-  a.part = part;
-  a.lab32 = lab32;
-  a.lab64 = lab64;
-  a.words = words;
-  std::vector<double> rv;  // RandomState(0) doubles: alive until the first synchronisation
-  if (init_centroids) {
-    SC_HIP(h, hipMemcpyAsync(cent, init_centroids, (size_t)k * dim * sizeof(double),
-                             hipMemcpyHostToDevice, s));
-  } else {
-    // k-means++ (sklearn _kmeans_plusplus, unit sample weights), RandomState(0) stream
-    double u_first;
-    int tr;
-    kmeans_seed_constants(k, &u_first, &tr, &rv);
-    SC_HIP(h, hipMemcpyAsync(rnd, rv.data(), rv.size() * sizeof(double), hipMemcpyHostToDevice,
-                             s));
-    const int first = sc_uniform_choice(n, u_first);
-    hipLaunchKernelGGL(k_g_first, dim3(1), dim3(256), 0, s, first, X, ld, dim, mean, xsq, cand,
-                       crow, csq);
-    KgArgs p = a;
-    p.C = crow;
-    p.cval = csq;
-    for (int c = 0; c < k; ++c) {
-      const int ntr = c == 0 ? 1 : trials;
-      p.m = ntr;
-      p.cd_prev = c == 0 ? nullptr : cd + (size_t)((c - 1) & 1) * KG_TS * n;
-      p.cd_out = cd + (size_t)(c & 1) * KG_TS * n;
-      launch_rows<kModePP>(s, grid, p);
-      hipLaunchKernelGGL(k_g_select, dim3(1), dim3(KG_ST), 0, s, c, k, ntr, trials, grid, part,
-                         p.cd_out, X, ld, n, dim, mean, xsq, rnd, seeds, cand, crow, csq,
-                         words, scal);
-    }
-    // one Euclidean Lloyd step on the centred data (max_iter = 1)
-    hipLaunchKernelGGL(k_g_seedrows, dim3(k), dim3(256), 0, s, X, ld, dim, mean, seeds, cent);
-    hipLaunchKernelGGL(k_g_cnorm, dim3((k + 63) / 64), dim3(64), 0, s, cent, k, dim, cval, cmx,
-                       0, nullptr);
-    KgArgs l = a;
-    l.C = cent;
-    l.m = k;
-    l.cval = cval;
-    launch_rows<kModeLloyd>(s, grid, l);
-    hipLaunchKernelGGL(k_g_update, dim3(dim), dim3(KG_UT), 0, s, X, ld, n, dim, k, lab32, cent,
-                       mean, 0, words);
-  }
-  SC_TRY(check_last(h, "k-means seeding launch"));
-
-  // the custom loop, KG_ITERS iterations per host synchronisation; kernels after the stop rule
-  // fired return at once, `done` comes back with the labels
-  KgArgs l = a;
-  l.C = cent;
-  l.m = k;
-  l.cval = cval;
-  l.cmx = cmx;
-  const int kind = metric == kKmeansCorrelation ? 2 : 1;
-  int w[kWords] = {0};
-  for (int it0 = 0;; it0 += KG_ITERS) {
-    for (int it = it0; it < it0 + KG_ITERS && it <= max_iter; ++it) {
-      if (metric == kKmeansCosine || metric == kKmeansCorrelation)
-        hipLaunchKernelGGL(k_g_cnorm, dim3((k + 63) / 64), dim3(64), 0, s, cent, k, dim, cval,
-                           cmx, kind, words);
-      launch_loop_rows(s, grid, l, metric);
-      hipLaunchKernelGGL(k_g_stop, dim3(1), dim3(64), 0, s, part, grid, n, it, max_iter, tol,
-                         words, scal);
-      hipLaunchKernelGGL(k_g_update, dim3(dim), dim3(KG_UT), 0, s, X, ld, n, dim, k, lab32,
-                         cent, mean, 1, words);
-    }
-    SC_TRY(check_last(h, "k-means loop launch"));
-    SC_HIP(h, hipMemcpyAsync(w, words, kWords * sizeof(int), hipMemcpyDeviceToHost, s));
-    SC_HIP(h, hipStreamSynchronize(s));
-    if (w[kWDone]) break;
-    if (it0 > max_iter) return fail(h, SC_ERR_HIP, "k-means loop did not reach its stop rule");
-  }
-  SC_HIP(h, hipMemcpyAsync(labels, lab64, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost,
-                           s));
-  if (centroids_out)
-    SC_HIP(h, hipMemcpyAsync(centroids_out, cent, (size_t)k * dim * sizeof(double),
-                             hipMemcpyDeviceToHost, s));
-  SC_HIP(h, hipStreamSynchronize(s));
-  if (iterations) *iterations = w[kWIters];
-  return SC_OK;
+  a.mean = ws.mean;
+  a.xsq = ws.xsq;
+  a.enorm = ws.enorm;
+  a.rmx = ws.rmx;
+  a.cnu = ws.cnu;
+  a.part = ws.part;
+  a.lab32 = ws.lab32;
+  a.lab64 = ws.lab64;
+  a.words = ws.words;
+  return a;
 }
+
+}  // namespace
+
+int kmeans_general_grid(int n) { return (n + KG_ROWS - 1) / KG_ROWS; }
+
+// column means and the per-row constants of X (ws.words and ws.scal are zero)
+void launch_kmeans_general_stats(hipStream_t s, const KmeansGeneralWorkspace& ws, int n, int dim,
+                                 int metric) {
+  hipLaunchKernelGGL(k_g_colmean, dim3(dim), dim3(KG_UT), 0, s, ws.X, ws.ld, n, ws.mean);
+  hipLaunchKernelGGL(k_g_rowstats, dim3(kmeans_general_grid(n)), dim3(KG_ROWS), 0, s, ws.X, ws.ld,
+                     n, dim, ws.mean, ws.xsq, ws.enorm, ws.rmx, ws.cnu,
+                     metric == kKmeansCorrelation ? 1 : 0);
+}
+
+// ws.cent <- sklearn's seeds: k-means++ (unit sample weights) from row `first` with the
+// RandomState(0) doubles in ws.rnd, then one Euclidean Lloyd step on the centred data
+void launch_kmeans_general_seed(hipStream_t s, const KmeansGeneralWorkspace& ws, int n, int dim,
+                                int k, int trials, int first) {
+  const int grid = kmeans_general_grid(n);
+  hipLaunchKernelGGL(k_g_first, dim3(1), dim3(256), 0, s, first, ws.X, ws.ld, dim, ws.mean,
+                     ws.xsq, ws.cand, ws.crow, ws.csq);
+  KgArgs p = kg_args(ws, n, dim);
+  p.C = ws.crow;
+  p.cval = ws.csq;
+  for (int c = 0; c < k; ++c) {
+    const int ntr = c == 0 ? 1 : trials;
+    p.m = ntr;
+    p.cd_prev = c == 0 ? nullptr : ws.cd + (size_t)((c - 1) & 1) * KG_TS * n;
+    p.cd_out = ws.cd + (size_t)(c & 1) * KG_TS * n;
+    launch_rows<kModePP>(s, grid, p);
+    hipLaunchKernelGGL(k_g_select, dim3(1), dim3(KG_ST), 0, s, c, k, ntr, trials, grid, ws.part,
+                       p.cd_out, ws.X, ws.ld, n, dim, ws.mean, ws.xsq, ws.rnd, ws.seeds, ws.cand,
+                       ws.crow, ws.csq, ws.words, ws.scal);
+  }
+  // one Euclidean Lloyd step on the centred data (max_iter = 1)
+  hipLaunchKernelGGL(k_g_seedrows, dim3(k), dim3(256), 0, s, ws.X, ws.ld, dim, ws.mean, ws.seeds,
+                     ws.cent);
+  hipLaunchKernelGGL(k_g_cnorm, dim3((k + 63) / 64), dim3(64), 0, s, ws.cent, k, dim, ws.cval,
+                     ws.cmx, 0, nullptr);
+  KgArgs l = kg_args(ws, n, dim);
+  l.C = ws.cent;
+  l.m = k;
+  l.cval = ws.cval;
+  launch_rows<kModeLloyd>(s, grid, l);
+  hipLaunchKernelGGL(k_g_update, dim3(dim), dim3(KG_UT), 0, s, ws.X, ws.ld, n, dim, k, ws.lab32,
+                     ws.cent, ws.mean, 0, ws.words);
+}
+
+// iteration `it` of the custom loop: assignment, stop rule, centroid update.  Once the stop rule
+// has fired (ws.words[kKgenDone]) every kernel returns at once.
+void launch_kmeans_general_iteration(hipStream_t s, const KmeansGeneralWorkspace& ws, int n,
+                                     int dim, int k, int metric, int it, int max_iter,
+                                     double tol) {
+  const int grid = kmeans_general_grid(n);
+  KgArgs l = kg_args(ws, n, dim);
+  l.C = ws.cent;
+  l.m = k;
+  l.cval = ws.cval;
+  l.cmx = ws.cmx;
+  if (metric == kKmeansCosine || metric == kKmeansCorrelation)
+    hipLaunchKernelGGL(k_g_cnorm, dim3((k + 63) / 64), dim3(64), 0, s, ws.cent, k, dim, ws.cval,
+                       ws.cmx, metric == kKmeansCorrelation ? 2 : 1, ws.words);
+  launch_loop_rows(s, grid, l, metric);
+  hipLaunchKernelGGL(k_g_stop, dim3(1), dim3(64), 0, s, ws.part, grid, n, it, max_iter, tol,
+                     ws.words, ws.scal);
+  hipLaunchKernelGGL(k_g_update, dim3(dim), dim3(KG_UT), 0, s, ws.X, ws.ld, n, dim, k, ws.lab32,
+                     ws.cent, ws.mean, 1, ws.words);
+}
+
+}  // namespace sc

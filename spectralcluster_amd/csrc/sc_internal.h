@@ -587,4 +587,35 @@ void launch_kmeans(hipStream_t s, const double* ET, int lde, int n, int k,
                    int max_iter, int first_center, int trials,
                    const KmeansWorkspace& ws, int metric = kKmeansCosine);
 
+
+// k-means on an (n, dim) input of any width as grids of short kernels (kmeans_general.hip).
+// X column-major (X[j * ld + r], ld = round_up(n, 16)), centroids row-major (k, dim).
+constexpr int kKgenTrialSlots = 16;  // k-means++ trial slots
+enum { kKgenDone = 0, kKgenIters = 1, kKgenBest = 2, kKgenWords = 4 };  // `words`: stop rule met,
+                                     // iterations, best trial of the last k-means++ pass
+constexpr int kKgenScalars = 4;      // `scal`: pot, previous mean distance
+int kmeans_general_grid(int n);      // workgroups of a row pass
+struct KmeansGeneralWorkspace {
+  double* X = nullptr;      // ld x dim
+  int ld = 0;
+  double *xsq = nullptr, *enorm = nullptr, *rmx = nullptr, *cnu = nullptr;  // per row, n each
+  double* mean = nullptr;   // dim
+  double* cent = nullptr;   // k x dim
+  double *cval = nullptr, *cmx = nullptr;  // per centre, k each
+  double *crow = nullptr, *csq = nullptr;  // k-means++ trial rows (slots x dim) and their |x|^2
+  double* scal = nullptr;   // kKgenScalars
+  double* cd = nullptr;     // 2 x slots x n trial distances
+  double* part = nullptr;   // grid x slots per-workgroup partial sums
+  double* rnd = nullptr;    // (k - 1) * trials RandomState(0) doubles
+  int* lab32 = nullptr;     // n
+  long long* lab64 = nullptr;  // n
+  int *seeds = nullptr, *cand = nullptr, *words = nullptr;  // k, slots, kKgenWords
+};
+void launch_kmeans_general_stats(hipStream_t s, const KmeansGeneralWorkspace& ws, int n, int dim,
+                                 int metric);
+void launch_kmeans_general_seed(hipStream_t s, const KmeansGeneralWorkspace& ws, int n, int dim,
+                                int k, int trials, int first);
+void launch_kmeans_general_iteration(hipStream_t s, const KmeansGeneralWorkspace& ws, int n,
+                                     int dim, int k, int metric, int it, int max_iter, double tol);
+
 }  // namespace sc
