@@ -389,11 +389,28 @@ int sc_predict_batch_streams(sc_handle h, const double* const* xs, const int* ns
  * flight; the call returns when all lanes are done.  Per-utterance results agree with
  * sc_predict to the solver's tolerance (whole-K tile sums where a short single call splits
  * K; the group's check schedule), not bit for bit; the same batch always gives the same
- * results.  Utterances outside the grouped path's range (n <= 128, n >= 4096, a
- * full-spectrum request, non-cosine k-means, constraints) take the single-call path. */
+ * results.  That is the route of 128 < n < 4096.  Utterances of n <= 128 take the short
+ * route: the dense Jacobi eigensolver of the single call with one workgroup per utterance,
+ * up to 64 utterances per launch and one synchronisation per launch, then the same lockstep
+ * k-means; the kernel body, its arguments and the LDS layout are sc_predict's (eigenvalues
+ * within 1e-10 relative of it, equal labels), full-spectrum requests included.  Everything
+ * else (n >= 4096, a full-spectrum request above 128, non-cosine k-means, constraints,
+ * group < 2) and every member that leaves its route (a refinement that is not symmetric,
+ * more than 32 clusters, a rare branch of the eigensolver) takes the single-call path.
+ * sc_last_batch_routes says what ran. */
 int sc_predict_batch_grouped(sc_handle h, const double* const* xs, const int* ns, int d,
                              int count, const sc_config* cfg, int64_t* const* labels,
                              sc_diag* diags, int group);
+/* What ran: one code per utterance of the last sc_predict_batch* call on this handle (a
+ * member of a grouped batch that was handed back to the single-call path reports
+ * SC_BATCH_ROUTE_SINGLE; after sc_predict_batch / sc_predict_batch_streams every code is).
+ * SC_ERR_INVALID for a NULL handle, NULL `routes`, or a `count` that is not the last batch's. */
+enum {
+  SC_BATCH_ROUTE_SINGLE = 0,         /* the single-call path, on the member's arena */
+  SC_BATCH_ROUTE_GROUP_LANCZOS = 1,  /* lockstep block Lanczos of a group (128 < n < 4096) */
+  SC_BATCH_ROUTE_GROUP_JACOBI = 2    /* short route: one Jacobi workgroup per member (n <= 128) */
+};
+int sc_last_batch_routes(sc_handle h, int32_t* routes, int count);
 
 /*
  * Size reduction before the spectral path (spectral_clusterer.py:170-199,

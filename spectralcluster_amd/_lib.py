@@ -30,6 +30,8 @@ STAGE_NAMES = ("affinity", "refine", "diffuse", "scaling", "eig", "kmeans",
                "total", "blur", "threshold_sym", "matvec", "affinity_gemm",
                "free_quantize", "free_product", "free_scan", "free_stats")
 
+# sc_last_batch_routes: what ran for an utterance of the last batch call
+BATCH_ROUTE_SINGLE, BATCH_ROUTE_GROUP_LANCZOS, BATCH_ROUTE_GROUP_JACOBI = range(3)
 DIFFUSE_PATH_NONE, DIFFUSE_PATH_EXPLICIT, DIFFUSE_PATH_FREE, DIFFUSE_PATH_FREE_THEN_EXPLICIT = range(4)
 
 _LIB_NAME = "libspectralcluster_amd.so"
@@ -209,6 +211,8 @@ PROTOTYPES = {
                                                 ctypes.POINTER(ScConfig),
                                                 ctypes.POINTER(_c_int64_p),
                                                 ctypes.POINTER(ScDiag), ctypes.c_int]),
+    "sc_last_batch_routes": (ctypes.c_int, [_handle_t, ctypes.POINTER(ctypes.c_int32),
+                                            ctypes.c_int]),
     "sc_stage_affinity": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int,
                                          ctypes.c_int, _c_double_p]),
     "sc_stage_refine": (ctypes.c_int, [_handle_t, ctypes.c_int,

@@ -217,6 +217,8 @@ extern "C" int sc_destroy(sc_handle h) {
   h->pool.clear();
   for (sc_handle sub : h->gslots) sc_destroy(sub);
   h->gslots.clear();
+  for (sc_handle sub : h->gshort) sc_destroy(sub);
+  h->gshort.clear();
   hipSetDevice(h->device);
   hipStreamSynchronize(h->stream);
   DevBuf* bufs[] = {&h->X,     &h->Xn,    &h->A0,     &h->B1,      &h->B2,    &h->rowmax,
@@ -226,7 +228,7 @@ extern "C" int sc_destroy(sc_handle h) {
                     &h->Hbuf,  &h->hsq,   &h->colnorm, &h->flags,  &h->E,     &h->Ek,   &h->Eio,
                     &h->td_d,  &h->td_e,  &h->td_theta, &h->td_work, &h->td_tau, &h->td_panel, &h->mvsym,
                     &h->kXc,   &h->kxsq,  &h->kclosest, &h->kcand, &h->kenorm, &h->krnd,
-                    &h->kcent, &h->klab32, &h->klab64, &h->kinfo, &h->kchain, &h->gkrnd, &h->gpack, &h->gypack, &h->ginfo, &h->glabels,
+                    &h->kcent, &h->klab32, &h->klab64, &h->kinfo, &h->kchain, &h->gkrnd, &h->gpack, &h->gypack, &h->ginfo, &h->glabels, &h->gjtab,
                     &h->kbig, &h->kbigw, &h->fq, &h->ft32, &h->fy1, &h->fR, &h->fscal, &h->fwords, &h->fcand, &h->fY, &h->fsplit, &h->fypart, &h->frpart, &h->fq2part, &h->fmx64, &h->ftau64, &h->fplan, &h->Xalt, &h->gneg};
   for (DevBuf* b : bufs)
     if (b->p) hipFree(b->p);
@@ -250,6 +252,7 @@ extern "C" int sc_destroy(sc_handle h) {
   delete h->gpool;
   if (h->h_gpack) hipHostFree(h->h_gpack);
   if (h->h_gypack) hipHostFree(h->h_gypack);
+  if (h->h_gjtab) hipHostFree(h->h_gjtab);
   if (h->h_ginfo) hipHostFree(h->h_ginfo);
   if (h->h_glabels) hipHostFree(h->h_glabels);
   hipStreamDestroy(h->stream);
@@ -1197,7 +1200,17 @@ extern "C" int sc_predict_batch(sc_handle h, const double* const* xs, const int*
                                 sc_diag* diags) {
   if (!h) return SC_ERR_INVALID;
   if (!xs || !ns || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  h->last_routes.assign(count, SC_BATCH_ROUTE_SINGLE);
   return predict_sequence(h, nullptr, count, xs, ns, d, cfg, labels, diags);
+}
+
+extern "C" int sc_last_batch_routes(sc_handle h, int32_t* routes, int count) {
+  if (!h) return SC_ERR_INVALID;
+  if (!routes) return fail(h, SC_ERR_INVALID, "routes is NULL");
+  if (count != (int)h->last_routes.size())
+    return fail(h, SC_ERR_INVALID, "count is not the last batch's");
+  for (int i = 0; i < count; ++i) routes[i] = h->last_routes[i];
+  return SC_OK;
 }
 
 // The batch over `streams` HIP streams of the handle's device: handle h plus streams - 1
@@ -1212,6 +1225,7 @@ extern "C" int sc_predict_batch_streams(sc_handle h, const double* const* xs, co
   if (!xs || !ns || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
   streams = std::max(1, std::min(streams, std::min(count, 32)));
   if (streams == 1) return sc_predict_batch(h, xs, ns, d, count, cfg, labels, diags);
+  h->last_routes.assign(count, SC_BATCH_ROUTE_SINGLE);
   while ((int)h->pool.size() < streams - 1) {
     sc_handle sub = nullptr;
     const int rc = sc_create(h->device, &sub);

@@ -20,7 +20,9 @@
 // too -- enqueue_front_grouped: both GEMMs take the tiles of all members in one launch.)
 // Each member runs the same kernel bodies with the same arguments as a single call; members
 // that leave the common path (rare branches of the eigensolver, k > 32, a non-symmetric
-// refinement, n <= 128 or n >= 4096) go through the single-call path.  Results agree with
+// refinement, n >= 4096) go through the single-call path.  Utterances of n <= 128 take the
+// short route further down: their eigensolver is the dense Jacobi solve, a workgroup per member,
+// up to kShortWidth members per launch (run_short_route).  Results agree with
 // sc_predict to the solver's tolerance (the grouped GEMMs sum whole K tiles, the group sets
 // the check schedule), and a batch call is a deterministic function of its input.
 #include <ctime>
@@ -38,8 +40,10 @@ double now_us() {
 
 constexpr int kRndStride = 256;  // doubles per k in the RandomState(0) table (k <= 32)
 
-int group_slot(sc_handle lead, int z, sc_handle* out) {
-  while ((int)lead->gslots.size() <= z) {
+int group_slot(sc_handle lead, int z, sc_handle* out,
+               std::vector<sc_handle_s*>* arenas = nullptr) {
+  std::vector<sc_handle_s*>& slots = arenas ? *arenas : lead->gslots;
+  while ((int)slots.size() <= z) {
     sc_handle sub = nullptr;
     const int rc = sc_create(lead->device, &sub);
     if (rc != SC_OK) return fail(lead, rc, "could not create a member arena for the group");
@@ -51,9 +55,9 @@ int group_slot(sc_handle lead, int z, sc_handle* out) {
       return fail(lead, SC_ERR_HIP, "could not create a member event");
     }
     sub->profile_level = 1;
-    lead->gslots.push_back(sub);
+    slots.push_back(sub);
   }
-  *out = lead->gslots[z];
+  *out = slots[z];
   // (weights of a blur radius above 32 live in the handle: members inherit the lead's)
   if ((*out)->blur_ext.size() != lead->blur_ext.size() || !lead->blur_ext.empty())
     (*out)->blur_ext = lead->blur_ext;
@@ -102,18 +106,20 @@ struct Member {
   FrontResult front;      // (front.free_op: matrix-free Diffuse, front.matrix is A)
   int state = 0;         // 0 in the group, 1 single-call path, 2 done
   int k = 0;
+  const GroupEigMember* eig = nullptr;  // what the group's eigensolver left for it
 };
 
 // Stages before the eigensolver of one group, member after member, each on its member's
 // stream: no synchronisation.  `slot0`: first member arena of the bank the group uses.
+// `arenas`: the member arenas to use (default: the lead's gslots).
 int enqueue_front(sc_handle lead, const double* const* xs, const int* ns, int d,
                   const sc_config* cfg, sc_diag* diags, const int* idx, int count, int slot0,
-                  Member* mb) {
+                  Member* mb, std::vector<sc_handle_s*>* arenas = nullptr) {
   for (int z = 0; z < count; ++z) {
     Member& m = mb[z];
     m = Member();
     m.index = idx[z];
-    SC_TRY(group_slot(lead, slot0 + z, &m.h));
+    SC_TRY(group_slot(lead, slot0 + z, &m.h, arenas));
     sc_handle h = m.h;
     h->err.clear();
     int rc = upload_embeddings(h, xs[m.index], ns[m.index], d);
@@ -325,47 +331,21 @@ int enqueue_front_grouped(sc_handle lead, const double* const* xs, const int* ns
   return SC_OK;
 }
 
-// Eigensolver and k-means of a group whose stages before are enqueued (enqueue_front), in
-// lockstep on the owner's stream; then the members that left the common path.
-int finish_group(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* const* labels,
-                 sc_diag* diags, Member* mb, int count, const EigRequest& rq, int front_bank) {
+// k-means of up to kGroupMax members whose eigensolver has finished (mb[zs[e]].eig), in lockstep
+// on the owner's stream, and their labels; both routes of the grouped batch end here.  A member
+// whose solve or cluster count left the common path gets state 1 (single_path_members below).
+// `eig_path` / `route`: what the members' diagnostics and route codes report.
+int cluster_members(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* const* labels,
+                    sc_diag* diags, Member* mb, const int* zs, int nz, const EigRequest& rq,
+                    int eig_path, int route, int* clustered) {
   hipStream_t s = lead->stream;
-  const bool trace = sw::group_trace();
-  if (front_bank >= 0) {
-    SC_HIP(lead, hipStreamWaitEvent(s, lead->gbank_ev[front_bank], 0));
-  } else {
-    for (int z = 0; z < count; ++z) SC_HIP(lead, hipStreamWaitEvent(s, mb[z].h->sync_ev, 0));
-  }
-  const double t1 = trace ? now_us() : 0.0;
-  // ---- eigen: lockstep over the symmetric members
-  GroupEigMember em[kGroupMax];
-  int emz[kGroupMax], ne = 0;
-  for (int z = 0; z < count; ++z) {
-    if (mb[z].state != 0) continue;
-    em[ne].h = mb[z].h;
-    em[ne].S = mb[z].front.matrix;
-    em[ne].ld = mb[z].front.ld;
-    em[ne].n = ns[mb[z].index];
-    em[ne].rq = rq;
-    em[ne].free_op = mb[z].front.free_op;
-    emz[ne++] = z;
-  }
-  if (ne > 0) SC_TRY(sym_topk_group(lead, em, ne));
-  for (int e = 0; e < ne; ++e) {
-    // a matrix-free member with rows the candidate search could not prune: the single-call
-    // path evaluates those rows exactly (its overflow words came back with the solver's syncs;
-    // eig_ncluster_impl's resume branch turns the two-pass operator back on: front.free_op)
-    if (em[e].free_op && em[e].status == 0 && em[e].h->h_free[0] != 0) em[e].status = 1;
-  }
-  const double t2 = trace ? now_us() : 0.0;
-  // ---- k-means: lockstep over the solved members
   KmGroupItem km[kGroupMax];
   int kmz[kGroupMax], label_n[kGroupMax];
   size_t label_off[kGroupMax], label_total = 0;
   int nk = 0;
-  {  // staging for the labels of this group (every member could end up in it)
+  {  // staging for the labels of these members (every one of them could end up in it)
     size_t need = 0;
-    for (int z = 0; z < count; ++z) need += (size_t)ns[mb[z].index];
+    for (int e = 0; e < nz; ++e) need += (size_t)ns[mb[zs[e]].index];
     // (never less than a full group of the largest utterances the grouped path takes -- 512 KB:
     //  a staging buffer that follows the batch's composition is a hipHostFree + hipHostMalloc,
     //  milliseconds, whenever a group's total grows)
@@ -384,16 +364,17 @@ int finish_group(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* c
       lead->h_glabels_count = need;
     }
   }
-  for (int e = 0; e < ne; ++e) {
-    Member& m = mb[emz[e]];
-    if (em[e].status != 0) {
+  for (int e = 0; e < nz; ++e) {
+    Member& m = mb[zs[e]];
+    const GroupEigMember& g = *m.eig;
+    if (g.status != 0) {
       m.state = 1;
-      m.front.skip_fused = em[e].skip_fused;  // (what the resumed single-call solve starts from)
+      m.front.skip_fused = g.skip_fused;  // (what the resumed single-call solve starts from)
       continue;
     }
     sc_handle h = m.h;
-    const int n = em[e].n;
-    int k = em[e].dc.n_clusters_raw;
+    const int n = g.n;
+    int k = g.dc.n_clusters_raw;
     if (cfg->min_clusters > 0 && k < cfg->min_clusters) k = cfg->min_clusters;  // :295-296
     m.k = k;
     double u = 0.0;
@@ -408,17 +389,17 @@ int finish_group(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* c
     if (diags) {
       sc_diag* dg = diags + m.index;
       dg->n = n;
-      dg->n_clusters_raw = em[e].dc.n_clusters_raw;
-      dg->max_delta = em[e].dc.max_delta;
+      dg->n_clusters_raw = g.dc.n_clusters_raw;
+      dg->max_delta = g.dc.max_delta;
       dg->eig_descending = rq.descend;
-      dg->n_eigenvalues = std::min((int)em[e].w.size(), SC_MAX_EIG);
-      for (int i = 0; i < dg->n_eigenvalues; ++i) dg->eigenvalues[i] = em[e].w[i];
+      dg->n_eigenvalues = std::min((int)g.w.size(), SC_MAX_EIG);
+      for (int i = 0; i < dg->n_eigenvalues; ++i) dg->eigenvalues[i] = g.w[i];
       dg->symmetry_state = m.front.folded_rownorm ? 2 : 1;
-      dg->eig_path = SC_EIG_PATH_BLOCK_LANCZOS;
-      dg->eig_matvec_passes = em[e].passes;
+      dg->eig_path = eig_path;
+      dg->eig_matvec_passes = g.passes;
       dg->eig_block = kEigBlock;
-      dg->eig_basis = em[e].basis;
-      dg->eig_max_residual = em[e].dc.max_resid;
+      dg->eig_basis = g.basis;
+      dg->eig_max_residual = g.dc.max_resid;
       dg->n_clusters = k;
       if (m.front.free_op) {
         dg->diffuse_path = SC_DIFFUSE_PATH_FREE;
@@ -453,7 +434,7 @@ int finish_group(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* c
     it.ws.labels64 = ptr<long long>(lead->glabels) + label_total;
     label_off[nk] = label_total;
     label_total += (size_t)n;
-    kmz[nk++] = emz[e];
+    kmz[nk++] = zs[e];
   }
   int running = nk;
   for (int it = 0; running > 0; it += 4) {
@@ -467,6 +448,7 @@ int finish_group(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* c
       Member& m = mb[kmz[q]];
       if (diags) diags[m.index].kmeans_iterations = lead->h_ginfo[16 * q];
       m.state = 2;
+      if (lead->groutes) lead->groutes[m.index] = route;
       label_n[q] = km[q].n;
       km[q].n = 0;  // idle from here on
       --running;
@@ -482,18 +464,21 @@ int finish_group(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* c
       memcpy(labels[mb[kmz[q]].index], lead->h_glabels + label_off[q],
              (size_t)label_n[q] * sizeof(int64_t));
   }
-  if (trace)
-    fprintf(stderr, "[sc] group of %d (n %d..%d): eigen %.0f us, k-means %.0f us (%d members)\n",
-            count, ns[mb[count - 1].index], ns[mb[0].index], t2 - t1, now_us() - t2, nk);
-  // ---- members that left the common path: the single-call pipeline on their own arena
+  if (clustered) *clustered = nk;
+  return SC_OK;
+}
+
+// The members of a group that left the common path (state 1): the single-call pipeline on their
+// own arena, from the refined matrix their front left -- only the solver and k-means again.
+int single_path_members(sc_handle lead, const sc_config* cfg, int64_t* const* labels,
+                        sc_diag* diags, Member* mb, int count) {
   bool any_back = false;
   for (int z = 0; z < count; ++z) any_back = any_back || mb[z].state == 1;
   // (their speculative block steps may still be running on this stream)
-  if (any_back) SC_HIP(lead, hipStreamSynchronize(s));
+  if (any_back) SC_HIP(lead, hipStreamSynchronize(lead->stream));
   for (int z = 0; z < count; ++z) {
     Member& m = mb[z];
     if (m.state != 1) continue;
-    // (from the refined matrix the member's front left: only the solver and k-means again)
     sc_diag local;
     sc_diag* dg = diags ? diags + m.index : &local;
     memset(dg, 0, sizeof(*dg));
@@ -512,6 +497,145 @@ int finish_group(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* c
   return SC_OK;
 }
 
+// Eigensolver and k-means of a group whose stages before are enqueued (enqueue_front), in
+// lockstep on the owner's stream; then the members that left the common path.
+int finish_group(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* const* labels,
+                 sc_diag* diags, Member* mb, int count, const EigRequest& rq, int front_bank) {
+  hipStream_t s = lead->stream;
+  const bool trace = sw::group_trace();
+  if (front_bank >= 0) {
+    SC_HIP(lead, hipStreamWaitEvent(s, lead->gbank_ev[front_bank], 0));
+  } else {
+    for (int z = 0; z < count; ++z) SC_HIP(lead, hipStreamWaitEvent(s, mb[z].h->sync_ev, 0));
+  }
+  const double t1 = trace ? now_us() : 0.0;
+  // ---- eigen: lockstep over the symmetric members
+  GroupEigMember em[kGroupMax];
+  int emz[kGroupMax], ne = 0;
+  for (int z = 0; z < count; ++z) {
+    if (mb[z].state != 0) continue;
+    em[ne].h = mb[z].h;
+    em[ne].S = mb[z].front.matrix;
+    em[ne].ld = mb[z].front.ld;
+    em[ne].n = ns[mb[z].index];
+    em[ne].rq = rq;
+    em[ne].free_op = mb[z].front.free_op;
+    mb[z].eig = &em[ne];
+    emz[ne++] = z;
+  }
+  if (ne > 0) SC_TRY(sym_topk_group(lead, em, ne));
+  for (int e = 0; e < ne; ++e) {
+    // a matrix-free member with rows the candidate search could not prune: the single-call
+    // path evaluates those rows exactly (its overflow words came back with the solver's syncs;
+    // eig_ncluster_impl's resume branch turns the two-pass operator back on: front.free_op)
+    if (em[e].free_op && em[e].status == 0 && em[e].h->h_free[0] != 0) em[e].status = 1;
+  }
+  const double t2 = trace ? now_us() : 0.0;
+  // ---- k-means: lockstep over the solved members
+  int nk = 0;
+  SC_TRY(cluster_members(lead, ns, cfg, labels, diags, mb, emz, ne, rq, SC_EIG_PATH_BLOCK_LANCZOS,
+                         SC_BATCH_ROUTE_GROUP_LANCZOS, &nk));
+  if (trace)
+    fprintf(stderr, "[sc] group of %d (n %d..%d): eigen %.0f us, k-means %.0f us (%d members)\n",
+            count, ns[mb[count - 1].index], ns[mb[0].index], t2 - t1, now_us() - t2, nk);
+  // ---- members that left the common path: the single-call pipeline on their own arena
+  return single_path_members(lead, cfg, labels, diags, mb, count);
+}
+
+// ------------------------------------------------------------------------------
+// short route: n <= kDenseMax
+// ------------------------------------------------------------------------------
+// An utterance of n <= 128 ends in the one-workgroup Jacobi solve -- 1.7 .. 6.4 ms on ONE CU at
+// n = 80 .. 128, longer than a whole call at n = 8192 -- and a batch of such utterances ran them
+// one after the other.  Here a wave of up to kShortWidth of them shares ONE Jacobi launch, a
+// workgroup (a CU) each (eig_driver.hip: dense_topk_group), and then the lockstep k-means chain
+// of the grouped route, kGroupMax members at a time.  The fronts are the single call's, member by
+// member on the member's stream, enqueued one wave ahead of the wave being solved.  Same kernel
+// bodies and arguments per member as its own sc_predict (eigenvalues within 1e-10 relative).
+// Eigensolver and k-means of one wave whose fronts are enqueued:
+int finish_short_wave(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* const* labels,
+                      sc_diag* diags, Member* mb, int count, const EigRequest& rq,
+                      GroupEigMember* em) {
+  hipStream_t s = lead->stream;
+  const bool trace = sw::group_trace();
+  for (int z = 0; z < count; ++z) SC_HIP(lead, hipStreamWaitEvent(s, mb[z].h->sync_ev, 0));
+  const double t1 = trace ? now_us() : 0.0;
+  std::vector<int> emz;
+  for (int z = 0; z < count; ++z) {
+    if (mb[z].state != 0) continue;  // (a front that is not symmetric: the general solver)
+    GroupEigMember& g = em[emz.size()];
+    g = GroupEigMember();
+    g.h = mb[z].h;
+    g.S = mb[z].front.matrix;
+    g.ld = mb[z].front.ld;
+    g.n = ns[mb[z].index];
+    g.rq = rq;
+    mb[z].eig = &g;
+    emz.push_back(z);
+  }
+  const int ne = (int)emz.size();
+  if (ne > 0) SC_TRY(dense_topk_group(lead, em, ne));
+  const double t2 = trace ? now_us() : 0.0;
+  int total = 0;
+  for (int at = 0; at < ne; at += kGroupMax) {
+    int nk = 0;
+    SC_TRY(cluster_members(lead, ns, cfg, labels, diags, mb, emz.data() + at,
+                           std::min(kGroupMax, ne - at), rq, SC_EIG_PATH_DENSE_JACOBI,
+                           SC_BATCH_ROUTE_GROUP_JACOBI, &nk));
+    total += nk;
+  }
+  if (trace)
+    fprintf(stderr, "[sc] short wave of %d (n %d..%d): eigen %.0f us, k-means %.0f us (%d members)\n",
+            count, ns[mb[count - 1].index], ns[mb[0].index], t2 - t1, now_us() - t2, total);
+  return single_path_members(lead, cfg, labels, diags, mb, count);
+}
+
+// The short members of a batch (`list`: indices sorted by n, descending) in waves of kShortWidth
+// on the caller's handle and host thread.
+int run_short_route(sc_handle h, const double* const* xs, const int* ns, int d,
+                    const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
+                    const std::vector<int>& list, const EigRequest& rq) {
+  if (list.empty()) return SC_OK;
+  SC_HIP(h, hipStreamSynchronize(h->stream));
+  SC_TRY(ensure_seed_table(h));
+  const int total = (int)list.size();
+  const int nwaves = (total + kShortWidth - 1) / kShortWidth;
+  const int banks = std::min(kGroupBanks, nwaves);
+  auto wave_count = [&](int j) { return std::min(kShortWidth, total - j * kShortWidth); };
+  // arenas once, every one for n = kDenseMax (1 MB or so): a position takes a member of any
+  // size of this route, and none of them ever holds a longer utterance of the batch
+  for (int b = 0; b < banks; ++b)
+    for (int z = 0; z < wave_count(b); ++z) {
+      sc_handle hz = nullptr;
+      SC_TRY(group_slot(h, b * kShortWidth + z, &hz, &h->gshort));
+      const int rc = sc_reserve(hz, kDenseMax, d);
+      if (rc != SC_OK) return fail(h, rc, hz->err);
+      hz->have_constraint = false;
+    }
+  std::vector<Member> mbs[kGroupBanks];
+  std::vector<GroupEigMember> em(kShortWidth);
+  for (int b = 0; b < banks; ++b) mbs[b].resize(kShortWidth);
+  auto front = [&](int j) -> int {
+    return enqueue_front(h, xs, ns, d, cfg, diags, list.data() + (size_t)j * kShortWidth,
+                         wave_count(j), (j % banks) * kShortWidth, mbs[j % banks].data(),
+                         &h->gshort);
+  };
+  int rc = front(0);
+  for (int j = 0; j < nwaves && rc == SC_OK; ++j) {
+    bool ahead = false;
+    if (j + 1 < nwaves) {
+      rc = front(j + 1);
+      ahead = true;
+    }
+    if (rc == SC_OK)
+      rc = finish_short_wave(h, ns, cfg, labels, diags, mbs[j % banks].data(), wave_count(j), rq,
+                             em.data());
+    if (rc != SC_OK && ahead)  // the next wave's uploads read the caller's arrays: let them land
+      for (int z = 0; z < wave_count(j + 1); ++z)
+        if (mbs[(j + 1) % banks][z].h) (void)hipStreamSynchronize(mbs[(j + 1) % banks][z].h->stream);
+  }
+  return rc;
+}
 
 // ---- streams on hardware queues of their own
 // The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (4 by
@@ -681,9 +805,20 @@ extern "C" int sc_predict_batch_grouped(sc_handle h, const double* const* xs, co
   const EigRequest rq = make_eig_request(cfg);
   const bool cfg_ok = group > 1 && cfg->kmeans_metric == kKmeansCosine &&
                       !constraint_active(h, cfg, true) && !constraint_active(h, cfg, false);
-  std::vector<int> grouped, single;
+  // what ran (sc_last_batch_routes): the routes below report into it while the call runs
+  h->last_routes.assign(count, SC_BATCH_ROUTE_SINGLE);
+  struct RouteReport {
+    sc_handle h;
+    ~RouteReport() {
+      h->groutes = nullptr;
+      for (sc_handle lane : h->glanes) lane->groutes = nullptr;
+    }
+  } report{h};
+  h->groutes = h->last_routes.data();
+  std::vector<int> grouped, shorts, single;
   for (int i = 0; i < count; ++i) {
     if (cfg_ok && xs[i] && ns[i] > 0 && sym_group_eligible(ns[i], rq)) grouped.push_back(i);
+    else if (cfg_ok && xs[i] && ns[i] > 0 && ns[i] <= kDenseMax) shorts.push_back(i);
     else single.push_back(i);
   }
   if (!grouped.empty()) {
@@ -773,6 +908,7 @@ extern "C" int sc_predict_batch_grouped(sc_handle h, const double* const* xs, co
       leads[l] = h->glanes[l - 1];
       leads[l]->blur_ext = h->blur_ext;
       leads[l]->err.clear();
+      leads[l]->groutes = h->groutes;
     }
     // The streams of the batch: per lane one for the lockstep chains and one per bank for the
     // fronts, on hardware queues of their own (independent_streams above); the leads' own streams
@@ -840,6 +976,12 @@ extern "C" int sc_predict_batch_grouped(sc_handle h, const double* const* xs, co
     if (rcs[0] != SC_OK) return rcs[0];
     for (int l = 1; l < lanes; ++l)
       if (rcs[l] != SC_OK) return fail(h, rcs[l], leads[l]->err.c_str());
+  }
+  // the short route (n <= kDenseMax), once the lanes of the Lanczos route are done: waves of
+  // kShortWidth members, largest first (a wave's Jacobi launch lasts as long as its largest member)
+  if (!shorts.empty()) {
+    std::stable_sort(shorts.begin(), shorts.end(), [&](int a, int b) { return ns[a] > ns[b]; });
+    SC_TRY(run_short_route(h, xs, ns, d, cfg, labels, diags, shorts, rq));
   }
   // (members outside the grouped path's range -- n >= 4096 above all: their uploads ride under
   //  the previous member's pipeline, api.hip predict_sequence)

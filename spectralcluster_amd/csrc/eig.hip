@@ -13,6 +13,7 @@
 //   k_jacobi         one-workgroup cyclic Jacobi, matrix in LDS: the dense solver for n <= 128
 //                    and the Rayleigh-Ritz problems above 64 (smaller ones are solved on the
 //                    host, eig_driver.hip)
+//   k_jacobi_g / _t  the same body, one matrix per workgroup: the short members of a batch
 // Everything except the matvec is tall-skinny (n x <= 136), L2-resident and latency-bound.
 #include <algorithm>
 #include <cstring>
@@ -857,8 +858,10 @@ __device__ __forceinline__ double fast_rsqrt(double x) {
 // two coalesced row updates.  Round-robin ordering: mp/2 disjoint rotations per
 // round, mp - 1 rounds per sweep.
 // mode 0: A = src (m x m).   mode 1: A_ij = c_i c_j src_ij + delta_ij p_i.
+// (the body is a device function: k_jacobi runs it for one matrix, k_jacobi_g / k_jacobi_t for
+//  one matrix per workgroup -- same code, same arithmetic)
 template <bool YT_LDS>
-__global__ __launch_bounds__(1024) void k_jacobi(
+__device__ __forceinline__ void jacobi_body(
     const double* __restrict__ src, int ldsrc, int m, int mode,
     const double* __restrict__ cvec, const double* __restrict__ pvec,
     const double* __restrict__ G, double* __restrict__ theta,
@@ -1093,6 +1096,40 @@ __global__ __launch_bounds__(1024) void k_jacobi(
 
 #undef Yt
 
+template <bool YT_LDS>
+__global__ __launch_bounds__(1024) void k_jacobi(
+    const double* __restrict__ src, int ldsrc, int m, int mode,
+    const double* __restrict__ cvec, const double* __restrict__ pvec,
+    const double* __restrict__ G, double* __restrict__ theta,
+    double* __restrict__ Y, int ldy, double* __restrict__ resid,
+    double* __restrict__ Yt_global, int* __restrict__ dbg) {
+  jacobi_body<YT_LDS>(src, ldsrc, m, mode, cvec, pvec, G, theta, Y, ldy, resid, Yt_global, dbg);
+}
+
+// One matrix per workgroup (blockIdx.x = member): the dense solve of up to 256 short problems
+// in one launch, a CU each.  After the solve the member's eigenvalues and its non-finite flag
+// word go to its slot of `pack`, so that one copy brings the whole launch's back.
+template <bool YT_LDS>
+__device__ __forceinline__ void jacobi_member(const JacobiItem& a) {
+  jacobi_body<YT_LDS>(a.src, a.ld, a.m, a.mode, a.cvec, a.pvec, nullptr, a.theta, a.Y, a.ldy,
+                      nullptr, a.Yt, a.flags);
+  if (a.pack == nullptr) return;
+  __syncthreads();  // theta[rank] was written by the thread that owns the diagonal entry
+  for (int i = threadIdx.x; i < a.m; i += blockDim.x) a.pack[i] = a.theta[i];
+  if (threadIdx.x == 0) a.pack[kEigBasisCap] = (double)a.flags[12];
+}
+// descriptors in the kernel arguments (up to kGroupMax members) ...
+template <bool YT_LDS>
+__global__ __launch_bounds__(1024) void k_jacobi_g(const GroupOf<JacobiItem> g) {
+  jacobi_member<YT_LDS>(g.s[blockIdx.x]);
+}
+// ... or in a table in device memory (64 of them do not fit the argument block)
+template <bool YT_LDS>
+__global__ __launch_bounds__(1024) void k_jacobi_t(const JacobiItem* __restrict__ table) {
+  const JacobiItem a = table[blockIdx.x];
+  jacobi_member<YT_LDS>(a);
+}
+
 __global__ void k_set_diag_T(double* T, int ldt, int mtot, const double* theta,
                              int keep) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1184,6 +1221,24 @@ __global__ __launch_bounds__(256) void k_back_transform_g(const GroupOf<RitzItem
   const RitzItem& a = g.s[blockIdx.y];
   if ((int)blockIdx.x >= a.cols || a.n <= 0) return;
   back_transform_body(a.E, a.lde, a.n, a.tvec);
+}
+// The dense route's eigenvectors of one member per blockIdx.y: column blockIdx.x of Y (row-major,
+// as the Jacobi kernel leaves it) becomes column blockIdx.x of E (k_rowmajor_to_colmajor), then
+// the back-transform of that column.
+__device__ __forceinline__ void dense_vectors_member(const JacobiItem& a) {
+  const int j = blockIdx.x;
+  if (j >= a.m) return;
+  for (int r = threadIdx.x; r < a.m; r += blockDim.x)
+    a.E[(size_t)j * a.lde + r] = a.Y[(size_t)r * a.ldy + j];
+  __syncthreads();
+  back_transform_body(a.E, a.lde, a.m, a.tvec);
+}
+__global__ __launch_bounds__(256) void k_dense_vectors_g(const GroupOf<JacobiItem> g) {
+  dense_vectors_member(g.s[blockIdx.y]);
+}
+__global__ __launch_bounds__(256) void k_dense_vectors_t(const JacobiItem* __restrict__ table) {
+  const JacobiItem a = table[blockIdx.y];
+  dense_vectors_member(a);
 }
 
 // dst (column-major, ldd) <- src (row-major, lds), n rows x cols
@@ -1440,14 +1495,20 @@ void launch_ritz_vectors_group(hipStream_t s, const RitzItem* items, int count) 
   hipLaunchKernelGGL(k_basis_times_Y_g, dim3((nmax + 15) / 16, count), dim3(256), lds, s, g);
   hipLaunchKernelGGL(k_back_transform_g, dim3(cmax, count), dim3(256), 0, s, g);
 }
-void launch_jacobi(hipStream_t s, const double* src, int ldsrc, int m, int mode,
-                   const double* cvec, const double* pvec, const double* G,
-                   double* theta, double* Y, int ldy, double* resid, double* Yt, int* dbg) {
+// LDS of one Jacobi workgroup and where its vector accumulator lives -- the one rule of
+// launch_jacobi and launch_jacobi_group
+static size_t jacobi_lds_bytes(int m, bool* yt_in_lds) {
   const int mp = (m + 1) & ~1;
   const size_t base = sizeof(double) * ((size_t)mp * (mp + 1) + 2 * mp + 2) + 64;
   const size_t with_yt = base + sizeof(double) * (size_t)mp * mp;
-  const int yt_in_lds = with_yt <= 150 * 1024;
-  const size_t lds = yt_in_lds ? with_yt : base;
+  *yt_in_lds = with_yt <= 150 * 1024;
+  return *yt_in_lds ? with_yt : base;
+}
+void launch_jacobi(hipStream_t s, const double* src, int ldsrc, int m, int mode,
+                   const double* cvec, const double* pvec, const double* G,
+                   double* theta, double* Y, int ldy, double* resid, double* Yt, int* dbg) {
+  bool yt_in_lds = false;
+  const size_t lds = jacobi_lds_bytes(m, &yt_in_lds);
   SC_OPT_IN_LDS(k_jacobi<true>, 160 * 1024 - 256);
   SC_OPT_IN_LDS(k_jacobi<false>, 160 * 1024 - 256);
   // always 16 waves: each round is a chain of dependent LDS round trips, so the time
@@ -1459,6 +1520,51 @@ void launch_jacobi(hipStream_t s, const double* src, int ldsrc, int m, int mode,
   else
     hipLaunchKernelGGL(k_jacobi<false>, dim3(1), dim3(threads), lds, s, src, ldsrc, m, mode,
                        cvec, pvec, G, theta, Y, ldy, resid, Yt, dbg);
+}
+bool jacobi_yt_in_lds(int m) {
+  bool in_lds = false;
+  (void)jacobi_lds_bytes(m, &in_lds);
+  return in_lds;
+}
+// The dense solve (mode 1) of `count` members, one workgroup each, and their eigenvectors into
+// E.  `items` must hold the members whose accumulator is in LDS apart from the others (either
+// kind first): every launch carries one kind.  `table` == nullptr: launches of up to kGroupMax
+// members, descriptors in the kernel arguments; otherwise a device copy of items[0..count)
+// (already on its way on `s`) and one launch per kind.
+void launch_jacobi_group(hipStream_t s, const JacobiItem* items, int count,
+                         const JacobiItem* table) {
+  SC_OPT_IN_LDS(k_jacobi_g<true>, 160 * 1024 - 256);
+  SC_OPT_IN_LDS(k_jacobi_g<false>, 160 * 1024 - 256);
+  SC_OPT_IN_LDS(k_jacobi_t<true>, 160 * 1024 - 256);
+  SC_OPT_IN_LDS(k_jacobi_t<false>, 160 * 1024 - 256);
+  const int step = table ? count : kGroupMax;
+  for (int at = 0; at < count;) {
+    bool kind = false;
+    size_t lds = jacobi_lds_bytes(items[at].m, &kind);
+    int end = at + 1;
+    for (; end < count && end - at < step; ++end) {
+      bool k2 = false;
+      const size_t l2 = jacobi_lds_bytes(items[end].m, &k2);
+      if (k2 != kind) break;
+      lds = std::max(lds, l2);
+    }
+    const int cnt = end - at;
+    int mmax = 0;
+    for (int z = at; z < end; ++z) mmax = std::max(mmax, items[z].m);
+    if (table) {
+      if (kind) hipLaunchKernelGGL(k_jacobi_t<true>, dim3(cnt), dim3(1024), lds, s, table + at);
+      else hipLaunchKernelGGL(k_jacobi_t<false>, dim3(cnt), dim3(1024), lds, s, table + at);
+      hipLaunchKernelGGL(k_dense_vectors_t, dim3(mmax, cnt), dim3(256), 0, s, table + at);
+    } else {
+      GroupOf<JacobiItem> g;
+      memset(&g, 0, sizeof(g));
+      for (int z = 0; z < cnt; ++z) g.s[z] = items[at + z];
+      if (kind) hipLaunchKernelGGL(k_jacobi_g<true>, dim3(cnt), dim3(1024), lds, s, g);
+      else hipLaunchKernelGGL(k_jacobi_g<false>, dim3(cnt), dim3(1024), lds, s, g);
+      hipLaunchKernelGGL(k_dense_vectors_g, dim3(mmax, cnt), dim3(256), 0, s, g);
+    }
+    at = end;
+  }
 }
 void launch_set_diag_T(hipStream_t s, double* T, int ldt, int mtot,
                        const double* theta, int keep) {

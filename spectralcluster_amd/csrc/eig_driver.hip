@@ -1308,6 +1308,98 @@ int sym_topk_group(sc_handle lead, GroupEigMember* mem, int count, bool want_vec
 }
 
 // ------------------------------------------------------------------------------
+// grouped dense solve (batch_group.hip: the short route, n <= kDenseMax)
+// ------------------------------------------------------------------------------
+// What the n <= kDenseMax branch of sym_topk does for one problem, for up to kShortWidth at
+// once: ONE Jacobi launch with a workgroup per member (a single call leaves 255 CUs idle), one
+// staged copy of every member's eigenvalues and non-finite word, one synchronisation; then per
+// member the same analyze() call on the host.  A member's kernel body, arguments and LDS layout
+// are those of launch_jacobi in its own single call.
+// status 1: the request cannot be satisfied (the single-call path states the error).
+int dense_topk_group(sc_handle lead, GroupEigMember* mem, int count) {
+  if (count < 1 || count > kShortWidth) return fail(lead, SC_ERR_INVALID, "group size");
+  hipStream_t s = lead->stream;
+  SC_TRY(ensure_group_staging(lead));
+  constexpr int kSlot = kEigBasisCap + 1;  // theta | flag word of a member in the staging
+  static_assert((size_t)kShortWidth * kSlot <=
+                    (size_t)kGroupMax * (kEigBasisCap * kEigBasisCap + 64 + 8),
+                "the group staging holds a launch's eigenvalues");
+  // a launch carries members of one kind: those whose accumulator lives in global memory first
+  std::vector<JacobiItem> items(count);
+  std::vector<int> order;
+  for (int pass = 0; pass < 2; ++pass)
+    for (int z = 0; z < count; ++z)
+      if (jacobi_yt_in_lds(mem[z].n) == (pass == 1)) order.push_back(z);
+  for (int q = 0; q < count; ++q) {
+    GroupEigMember& g = mem[order[q]];
+    sc_handle h = g.h;
+    if (g.n < 1 || g.n > kDenseMax) return fail(lead, SC_ERR_INVALID, "dense group member size");
+    SC_TRY(ensure_eig(h, g.n));
+    JacobiItem& a = items[q];
+    a.src = g.S;
+    a.ld = g.ld;
+    a.m = g.n;
+    a.mode = 1;
+    a.cvec = ptr<double>(h->cvec);
+    a.pvec = ptr<double>(h->pvec);
+    a.theta = ptr<double>(h->theta);
+    a.Y = ptr<double>(h->Y);
+    a.ldy = kLdq;
+    a.Yt = ptr<double>(h->Yt);
+    a.flags = ptr<int>(h->flags);
+    a.pack = ptr<double>(lead->gpack) + (size_t)q * kSlot;
+    a.E = ptr<double>(h->E);
+    a.lde = round_up(g.n, 16);
+    a.tvec = ptr<double>(h->tvec);
+    g.status = 0;
+    g.passes = 0;
+    g.basis = g.n;
+    g.skip_fused = false;
+  }
+  const JacobiItem* table = nullptr;
+  if (count > kGroupMax) {  // descriptors of a wide launch: a table in device memory
+    const size_t bytes = (size_t)kShortWidth * sizeof(JacobiItem);
+    SC_TRY(grow(lead, lead->gjtab, bytes));
+    if (!lead->h_gjtab)
+      SC_HIP(lead, hipHostMalloc(reinterpret_cast<void**>(&lead->h_gjtab), bytes));
+    memcpy(lead->h_gjtab, items.data(), (size_t)count * sizeof(JacobiItem));
+    SC_HIP(lead, hipMemcpyAsync(lead->gjtab.p, lead->h_gjtab, (size_t)count * sizeof(JacobiItem),
+                                hipMemcpyHostToDevice, s));
+    table = ptr<JacobiItem>(lead->gjtab);
+  }
+  launch_jacobi_group(s, items.data(), count, table);
+  SC_TRY(check_last(lead, "grouped jacobi launch"));
+  SC_HIP(lead, hipMemcpyAsync(lead->h_gpack, lead->gpack.p, (size_t)count * kSlot * sizeof(double),
+                              hipMemcpyDeviceToHost, s));
+  SC_HIP(lead, hipStreamSynchronize(s));
+  // A non-finite member fails the whole batch with the single call's code and message (the
+  // text is part of the contract, so it cannot name the member): no utterance of the batch has
+  // labels then, finished waves included.  The caller finds the input with sc_predict on each
+  // utterance, or by looking for a zero or non-finite embedding row.
+  for (int q = 0; q < count; ++q)
+    if (lead->h_gpack[(size_t)q * kSlot + kEigBasisCap] != 0.0)
+      return fail(lead, SC_ERR_NON_FINITE, kNonFiniteMessage);
+  for (int q = 0; q < count; ++q) {
+    GroupEigMember& g = mem[order[q]];
+    sc_handle h = g.h;
+    const int n = g.n;
+    memcpy(h->h_theta, lead->h_gpack + (size_t)q * kSlot, (size_t)n * sizeof(double));
+    for (int i = 0; i < n; ++i) h->h_theta[kLdq + i] = 0.0;
+    g.dc = analyze(g.rq, h->h_theta, h->h_theta + kLdq, n, n, true);
+    if (!g.dc.enough) {
+      g.status = 1;
+      continue;
+    }
+    h->n_vec = n;  // all eigenvectors, like np.linalg.eig
+    g.dc.kw = n;
+    g.w.resize(n);
+    for (int i = 0; i < n; ++i) g.w[i] = g.rq.descend ? h->h_theta[i] : -h->h_theta[i];
+    h->last_w = g.w;
+  }
+  return SC_OK;
+}
+
+// ------------------------------------------------------------------------------
 // general (non-symmetric) top-k eigensolver driver
 // ------------------------------------------------------------------------------
 // M (n x n, ld): the refined matrix, NOT diagonally similar to a symmetric one.

@@ -117,6 +117,16 @@ struct sc_handle_s {
   long long* h_glabels = nullptr;
   size_t h_glabels_count = 0;
   hipEvent_t gcheck_ev = nullptr;
+  // short route of a grouped batch (n <= kDenseMax, batch_group.hip): its member arenas
+  // (reserved for n = kDenseMax, whatever else the batch holds), the descriptor table of a
+  // wide Jacobi launch (device + pinned twin)
+  std::vector<sc_handle_s*> gshort;
+  DevBuf gjtab;
+  JacobiItem* h_gjtab = nullptr;
+  // route of every utterance of the last batch call (sc_last_batch_routes); `groutes`: where
+  // a lead of the running batch reports (the caller handle's last_routes)
+  std::vector<int32_t> last_routes;
+  int32_t* groutes = nullptr;
   std::vector<sc_handle_s*> glanes;  // the leads of lanes 1.. (batch_group.hip)
   class HostPool* gpool = nullptr;  // host workers of the group checks (host_pool.h)
   // grouped front: the stages before the eigensolver of a whole group as grouped launches on
@@ -346,6 +356,10 @@ struct GroupEigMember {
 // Leaves Ritz vectors in every solved member's h->E (h->n_vec set).
 // `want_vectors` false: eigenvalues and the eigengap decision only (AutoTune sweep).
 int sym_topk_group(sc_handle lead, GroupEigMember* mem, int count, bool want_vectors = true);
+// The dense Jacobi solve of up to kShortWidth members of n <= kDenseMax in one launch (a
+// workgroup each), one synchronisation: every eigenpair of each, eigenvectors in h->E.  Fills
+// status, dc, w, basis like sym_topk_group; SC_ERR_NON_FINITE when a member's front flagged it.
+int dense_topk_group(sc_handle lead, GroupEigMember* mem, int count);
 // `any_size`: also n >= 4096 (the group takes the upper-triangle matvec there)
 bool sym_group_eligible(int n, const EigRequest& rq, bool any_size = false);
 

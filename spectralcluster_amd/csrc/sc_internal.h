@@ -235,6 +235,17 @@ void launch_lz_link(hipStream_t s, const EigWorkspace& ws, LzChain* chain, int n
 // ---- grouped launches (batch_group.hip): up to kGroupMax independent problems per launch,
 //      their descriptors passed by value in the kernel arguments (<= 4 KB), blockIdx.y = member
 constexpr int kGroupMax = 16;
+// Members per launch of the short route of a batch (n <= kDenseMax: one Jacobi workgroup per
+// member, batch_group.hip).  Up to kGroupMax the descriptors travel in the kernel arguments,
+// above that as a table in device memory.  A compile-time choice (EXTRA_CXXFLAGS=
+// -DSC_SHORT_WIDTH=16 builds the narrow form): 64 measured 2.1-2.3x the throughput of 16 on a
+// batch of 512 short utterances (5767-6269 against 2441-2828 utterances/s) -- a
+// launch lasts as long as its largest member whatever its width.
+#ifndef SC_SHORT_WIDTH
+#define SC_SHORT_WIDTH 64
+#endif
+constexpr int kShortWidth = SC_SHORT_WIDTH;
+static_assert(kShortWidth >= 1 && kShortWidth <= 256, "one workgroup per CU");
 template <typename T>
 struct GroupOf {
   T s[kGroupMax];
@@ -257,6 +268,24 @@ struct RitzItem {    // E[:, 0:cols] (column-major, lde) = normalise(t .* (Q[:, 
   int ldy, cols;
   double* E;
   int lde, n;
+  const double* tvec;
+};
+// One member of a grouped dense solve (launch_jacobi_group): Op_ij = c_i c_j src_ij +
+// delta_ij p_i of order m <= kDenseMax, as launch_jacobi(mode 1) solves it.
+struct JacobiItem {
+  const double* src;   // m x m, row pitch ld
+  int ld, m, mode;
+  const double* cvec;
+  const double* pvec;
+  double* theta;       // m eigenvalues, descending
+  double* Y;           // eigenvectors, row-major, pitch ldy (column `rank` belongs to theta[rank])
+  int ldy;
+  double* Yt;          // m x m accumulator in global memory (orders whose LDS cannot hold it)
+  int* flags;          // the arena's flag words: [1..7] sweep count and cycle counters come back,
+                       // [12] is the front's non-finite word
+  double* pack;        // kEigBasisCap + 1 doubles of the launch's staging: theta | flags[12]
+  double* E;           // eigenvectors out: column-major, pitch lde, back-transformed by tvec
+  int lde;
   const double* tvec;
 };
 // One member of a batch group in the stages before its eigensolver (ICASSP2018 refinement
@@ -356,6 +385,9 @@ void launch_copy_block(hipStream_t s, const double* src, int ldsrc, double* dst,
 // ET[j] = t .* ET[j] / || t .* ET[j] ||   (LAPACK unit 2-norm columns)
 void launch_back_transform(hipStream_t s, double* ET, int ld, int n, int cols,
                            const double* tvec);
+bool jacobi_yt_in_lds(int m);
+void launch_jacobi_group(hipStream_t s, const JacobiItem* items, int count,
+                         const JacobiItem* table);
 void launch_rowmajor_to_colmajor(hipStream_t s, const double* src, int lds, int n, int cols,
                                  double* dst, int ldd);
 void launch_colmajor_to_rowmajor(hipStream_t s, const double* src, int lds, int n, int cols,

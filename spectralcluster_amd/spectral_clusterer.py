@@ -81,6 +81,8 @@ class SpectralClusterer:
     self.post_eigen_cluster_function = post_eigen_cluster_function
     self.device = device
     self.last_diag: typing.Optional[_lib.ScDiag] = None
+    # one route code per utterance of the last predict_batch (None before the first)
+    self.last_batch_routes: typing.Optional[typing.List[int]] = None
     # not in the reference: restart cycles block Lanczos may spend before the dense
     # eigensolver takes over (0 = the library default, 40); predict() returns either way
     self.eig_max_cycles = 0
@@ -368,7 +370,12 @@ class SpectralClusterer:
                   utterances per launch -- the eigensolver and k-means chains of a group
                   advance in lockstep on one stream while the GEMMs and refinement passes of
                   the next group run on another; the groups are dealt to three lanes (a host
-                  thread and a set of streams each) inside the call;
+                  thread and a set of streams each) inside the call.  That is the route of
+                  128 < n < 4096; utterances of n <= 128 take the short route of the same
+                  call (the dense Jacobi eigensolver, one workgroup per utterance, up to 64
+                  utterances per launch, then the lockstep k-means), and n >= 4096, a
+                  full-spectrum request above 128, or a member that leaves its route run as
+                  single calls inside it;
       streams     `sc_predict_batch_streams` (when `streams` is given and `group` is not):
                   the batch spread (longest-processing-time first) over `streams` HIP
                   streams, one host thread and arena per stream; streams=1 is a plain loop.
@@ -376,8 +383,13 @@ class SpectralClusterer:
     the grouped GEMMs sum K in whole tiles where a short single call splits K, and the
     lockstep eigensolver checks convergence on the group's schedule, so a member can leave
     with a different basis size (eigenvalues within 1e-6 relative, labels equal unless an
-    eigengap decision is a near tie).  A batch call is deterministic: the same list gives
-    the same results.
+    eigengap decision is a near tie; an utterance of n <= 128 runs the kernel body of its own
+    predict(): eigenvalues within 1e-10 relative).  A batch call is deterministic: the same
+    list gives the same results.
+
+    `last_batch_routes` (a list of ints, one per utterance) says what ran after the grouped and
+    the streams forms: 0 the single-call path, 1 the grouped block Lanczos, 2 the grouped short
+    route (`_lib.BATCH_ROUTE_*`).
 
     `constraint_matrices`: one `ConstraintMatrix` / ndarray / None per utterance.  With it (and
     `constraint_options`) the batch runs as per-utterance `predict(u, c)` calls; without it a
@@ -387,6 +399,7 @@ class SpectralClusterer:
       if len(constraint_matrices) != len(utterances):
         raise ValueError("constraint_matrices must be as long as the batch")
       if self.constraint_options is not None:
+        self.last_batch_routes = [_lib.BATCH_ROUTE_SINGLE] * len(utterances)
         return [self.predict(u, c) for u, c in zip(utterances, constraint_matrices)]
     if group is None:
       group = 16 if streams is None else 0
@@ -399,9 +412,11 @@ class SpectralClusterer:
       # anything sc_predict_batch does not cover (user-supplied affinity / clustering
       # functions, AutoTune, size reduction, fallback decisions) goes through predict().
       # A batch never carries a constraint matrix -- same as predict(u) without one.
+      self.last_batch_routes = [_lib.BATCH_ROUTE_SINGLE] * len(utterances)
       return [self.predict(u) for u in utterances]
     _lib.kmeans_metric_code(self.custom_dist)  # raises for metrics that are not on the device
     if not utterances:
+      self.last_batch_routes = []
       return []
     for u in utterances:
       if not isinstance(u, np.ndarray):
@@ -428,4 +443,13 @@ class SpectralClusterer:
           handle.raw, xp, ns, d, count, self.build_config(), lp, diags,
           max(1, int(streams))), TypeError)
     self.last_batch_diags = list(diags)
+    # The library always exports the report (_lib.load() fails without it).  Only a stand-in
+    # handle lacks it -- tests/test_host_logic.py drives this method with one that has the two
+    # batch calls and nothing else --, and then there is nothing to report.
+    report = getattr(handle.lib, "sc_last_batch_routes", None)
+    self.last_batch_routes = None
+    if report is not None:
+      routes = (ctypes.c_int32 * count)()
+      handle.check(report(handle.raw, routes, count))
+      self.last_batch_routes = [int(r) for r in routes]
     return labels
