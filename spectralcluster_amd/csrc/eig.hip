@@ -927,6 +927,7 @@ __device__ __forceinline__ void jacobi_body(
   }
   __syncthreads();
   const double tiny_abs = 1e-17 * s_scale, large_abs = 1e-13 * s_scale;
+  const double turn_abs = 1e-15 * s_scale;  // (128 entries of it in a row: 1.3e-13 * scale)
   const int half = mp / 2;
   int sweeps_done = 0;
   long long cyc_param = 0, cyc_bar1 = 0, cyc_upd = 0, cyc_bar2 = 0;
@@ -967,10 +968,19 @@ __device__ __forceinline__ void jacobi_body(
           const double rd = fast_rcp(den);
           double t = apq * rd;
           t = __builtin_fma(__builtin_fma(-den, t, apq), rd, t);
-          c = fast_rsqrt(__builtin_fma(t, t, 1.0));
-          s = t * c;
-          if (s != 0.0 && apq2 > 1e-18 * dd && fabs(apq) > large_abs)
-            atomicAdd(&s_rot, 1);  // still "large"
+          // a rotation that TURNS (|t| > 1e-9: between (nearly) equal diagonal entries any
+          // apq turns by up to 45 degrees) counts as large whatever its entry; one whose
+          // entry is below 1e-15 * scale is left out instead: it cannot move an eigenvalue
+          // by more than that, and turning rows p and q for it would undo what the sweep has
+          // done to their other entries
+          const bool turns = t * t > 1e-18;
+          if (!turns || fabs(apq) > turn_abs) {
+            c = fast_rsqrt(__builtin_fma(t, t, 1.0));
+            s = t * c;
+            // still "large": turns, or entry |apq| > 1e-9 sqrt(|app aqq|) above its floor
+            if (s != 0.0 && (turns || (apq2 > 1e-18 * dd && fabs(apq) > large_abs)))
+              atomicAdd(&s_rot, 1);
+          }
         }
         cs[tid] = c;
         sn[tid] = s;
@@ -1052,9 +1062,20 @@ __device__ __forceinline__ void jacobi_body(
       __syncthreads();
       if (tid == 0) { cyc_param += tr1 - tr0; cyc_bar1 += tr2 - tr1; cyc_upd += tr3 - tr2; cyc_bar2 += clock64() - tr3; }
     }
-    // s_rot counts rotations that were still "large" (|apq| > 1e-9 sqrt(app aqq)).
-    // A sweep made only of small rotations leaves off-diagonals ~1e-18 relative
-    // (quadratic convergence): done, without a further all-idle checking sweep.
+    // s_rot counts rotations that were still "large": angle |t| > 1e-9, or entry |apq| >
+    // 1e-9 sqrt(|app aqq|) above the 1e-13 * scale floor.  A sweep without one is the last:
+    // every rotation in it turned by at most 1e-9 (those that would have turned further over
+    // an entry below 1e-15 * scale were left out), so it moved the other entries of its two
+    // rows by 1e-9 of their size -- second order -- and what it leaves off the diagonal is
+    // ~1e-18 relative (quadratic convergence), beside the entries below 1e-15 * scale between
+    // (nearly) equal diagonal entries that were left where they are: done, without a further
+    // all-idle checking sweep.  The guarantee needs the small ANGLE.  A small entry alone does
+    // not give it: between (nearly) equal diagonal entries t ~ 1 for any apq, such a rotation
+    // mixes the rest of rows p and q at first order, and a matrix c I + 1e-10 P used to come
+    // back after ONE sweep with off-diagonals of the size it came in with
+    // (tests/test_gpu_jacobi_spectra.py).  The floors keep the Laplacian's null eigenvalue
+    // (entry rule) and rounding noise inside an eigenspace (angle rule) from keeping sweeps
+    // alive.
     if (s_rot == 0) break;
     __syncthreads();
   }

@@ -335,19 +335,23 @@ static int orthonormalize(sc_handle h, int n, int m, bool record, int col0, int 
   return check_last(h, "orthonormalize launch");
 }
 
+// SC_EIG_TRACE: what the last Jacobi launch left in h_flags[1..7] (jacobi_body's dbg words)
+static void trace_jacobi(sc_handle h) {
+  if (h->h_flags[1] <= 0 || !sw::eig_trace()) return;
+  fprintf(stderr, "[sc] jacobi sweeps=%d  %.1f us  %.0f MHz shader clock\n", h->h_flags[1],
+          h->h_flags[2] * 0.01, h->h_flags[3] * 1024.0 / (h->h_flags[2] * 0.01));
+  fprintf(stderr, "[sc]   thread-0 kcycles: param %d  barrier1 %d  update %d  barrier2 %d\n",
+          h->h_flags[4], h->h_flags[5], h->h_flags[6], h->h_flags[7]);
+  hipMemsetAsync(ptr<int>(h->flags) + 1, 0, 2 * sizeof(int), h->stream);
+}
+
 static int read_flags(sc_handle h, int* mask) {
   SC_HIP(h, hipMemcpyAsync(h->h_flags, h->flags.p, 16 * sizeof(int), hipMemcpyDeviceToHost,
                            h->stream));
   SC_HIP(h, hipStreamSynchronize(h->stream));
   *mask = h->h_flags[0];
   if (h->h_flags[12] != 0) return fail(h, SC_ERR_NON_FINITE, kNonFiniteMessage);
-  if (h->h_flags[1] > 0 && sw::eig_trace()) {
-    fprintf(stderr, "[sc] jacobi sweeps=%d  %.1f us  %.0f MHz shader clock\n", h->h_flags[1],
-            h->h_flags[2] * 0.01, h->h_flags[3] * 1024.0 / (h->h_flags[2] * 0.01));
-    fprintf(stderr, "[sc]   thread-0 kcycles: param %d  barrier1 %d  update %d  barrier2 %d\n",
-            h->h_flags[4], h->h_flags[5], h->h_flags[6], h->h_flags[7]);
-    hipMemsetAsync(ptr<int>(h->flags) + 1, 0, 2 * sizeof(int), h->stream);
-  }
+  trace_jacobi(h);
   return SC_OK;
 }
 
@@ -591,8 +595,12 @@ int sym_topk(sc_handle h, const FrontResult& op_in, int n, const EigRequest& rq_
     SC_HIP(h, hipMemcpyAsync(h->h_theta, theta_d, n * sizeof(double), hipMemcpyDeviceToHost, s));
     SC_HIP(h, hipMemcpyAsync(h->h_flags + 12, ptr<int>(h->flags) + 12, sizeof(int),
                              hipMemcpyDeviceToHost, s));
+    if (sw::eig_trace())  // sweep count and thread-0 cycle split of this launch
+      SC_HIP(h, hipMemcpyAsync(h->h_flags + 1, ptr<int>(h->flags) + 1, 7 * sizeof(int),
+                               hipMemcpyDeviceToHost, s));
     SC_HIP(h, hipStreamSynchronize(s));
     if (h->h_flags[12] != 0) return fail(h, SC_ERR_NON_FINITE, kNonFiniteMessage);
+    trace_jacobi(h);
     for (int i = 0; i < n; ++i) h->h_theta[kLdq + i] = 0.0;
     dc = analyze(rq, h->h_theta, h->h_theta + kLdq, n, n, true);
     if (!dc.enough) return fail(h, SC_ERR_UNSUPPORTED, "eigen request cannot be satisfied");

@@ -18,7 +18,8 @@
 namespace sc {
 namespace sw {
 
-// SC_EIG_TRACE=1|2|3: block Lanczos / Arnoldi log (2: Ritz values, 3: scaling vectors)
+// SC_EIG_TRACE=1|2|3: block Lanczos / Arnoldi log and the sweep count of a one-workgroup Jacobi
+// solve (2: Ritz values, 3: scaling vectors)
 inline int eig_trace() {
   static const int v = getenv("SC_EIG_TRACE") ? std::max(1, atoi(getenv("SC_EIG_TRACE"))) : 0;
   return v;

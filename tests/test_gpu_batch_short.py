@@ -122,6 +122,52 @@ def test_short_route_against_the_oracle(lap):
     assert np.max(np.abs(w - ref) / np.maximum(np.abs(ref), 1e-12)) < 1e-6, i
 
 
+def groups_of_identical_rows(n, groups, seed):
+  """`groups` runs of exactly identical embeddings (shares 3 : 2 or 5 : 3 : 2): the affinity has
+  rank `groups`, every other eigenvalue of it is an exact multiple one"""
+  rng = np.random.default_rng(seed)
+  centres = np.eye(groups, 24) + 0.2 * rng.random((groups, 24))
+  shares = {2: (0.6, 0.4), 3: (0.5, 0.3, 0.2)}[groups]
+  counts = [int(round(s * n)) for s in shares[:-1]]
+  counts.append(n - sum(counts))
+  return np.vstack([np.tile(c, (m, 1)) for c, m in zip(centres, counts)])
+
+
+def rows_repeated_three_times(n, k, seed):
+  return np.repeat(so.blobs((n + 2) // 3, 24, k, seed=seed), 3, axis=0)[:n]
+
+
+DEGENERATE_SIZES = [40, 96, 97, 128]
+
+
+def degenerate_utterances():
+  """exact duplicates at both accumulator placements of the kernel, ordinary members between
+  them"""
+  utts = []
+  for n in DEGENERATE_SIZES:
+    utts += [groups_of_identical_rows(n, 2, seed=n), so.blobs(n - 3, 24, 3, seed=8000 + n),
+             groups_of_identical_rows(n, 3, seed=n + 1), rows_repeated_three_times(n, 3, seed=n + 2)]
+  return utts
+
+
+@pytest.mark.parametrize("lap", LAPS)
+def test_exact_duplicates_on_the_short_route(lap):
+  """predict_batch takes no matrix: spectra with exact multiplicities reach the kernel as
+  embeddings with exact duplicates.  Same labels and eigenvalues as each member's own predict(),
+  and the oracle's clustering."""
+  utts = degenerate_utterances()
+  maxc = 7 if lap is None else 12
+  code = so.LAPLACIAN_NONE if lap is None else so.LAPLACIAN_GRAPH_CUT
+  c = icassp(laplacian_type=lap, max_clusters=maxc)
+  got = c.predict_batch(utts, group=16)
+  assert c.last_batch_routes == [_lib.BATCH_ROUTE_GROUP_JACOBI] * len(utts)
+  assert all(d.eig_path == JACOBI for d in c.last_batch_diags)
+  assert_same_as_single_calls(c, utts, got)
+  for i, u in enumerate(utts):
+    want = so.predict(u, so.icassp2018_config(laplacian_type=code, max_clusters=maxc))
+    assert so.adjusted_rand_index(got[i], want) == 1.0, (i, u.shape)
+
+
 def option_utterances(seed, count=7, d=16):
   rng = np.random.default_rng(seed)
   return [so.blobs(int(n), d, int(k), seed=100 * seed + i)

@@ -77,6 +77,25 @@ def test_identical_embeddings_and_duplicates():
   assert so.adjusted_rand_index(lab, want) == 1.0
 
 
+def test_identical_embeddings_and_duplicates_on_the_jacobi_path():
+  """The same at 60 + 40 rows, n <= 128: the one-workgroup Jacobi solve, every eigenvalue but a
+  handful a multiple one.  At this size the reference's eigengap reads two more eigenvalues above
+  stop_eigenvalue (the blur's edge rows, 1.5e-2 and 1.0e-2) and finds 4 clusters -- the two
+  groups less their boundary rows, and those two rows alone -- so the clustering is held to the
+  oracle's, and the two groups to that."""
+  a = np.tile(np.array([[1.0, 0.2, 0.0]]), (60, 1))
+  b = np.tile(np.array([[0.0, 0.3, 1.0]]), (40, 1))
+  x = np.vstack([a, b])
+  c = sca.SpectralClusterer(min_clusters=2, max_clusters=5, refinement_options=icassp())
+  lab = c.predict(x)
+  assert c.last_diag.eig_path == 1  # SC_EIG_PATH_DENSE_JACOBI
+  dump = {}
+  want = so.predict(x, so.icassp2018_config(max_clusters=5), dump)
+  assert c.last_diag.n_clusters_raw == dump["n_clusters"] == 4
+  assert so.adjusted_rand_index(lab, want) == 1.0
+  assert len(set(lab[:59])) == 1 and len(set(lab[61:])) == 1 and lab[0] != lab[99]
+
+
 def test_float32_and_noncontiguous_inputs():
   x64 = so.blobs(200, 16, 3, seed=1)
   c = sca.configs.icassp2018_clusterer
