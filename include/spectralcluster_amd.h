@@ -233,6 +233,29 @@ typedef struct sc_diag {
 int sc_abi_version(void);
 /* sizeof(sc_config) / sizeof(sc_diag) as compiled, so a binding can verify its mirror */
 int sc_struct_sizes(int* config_bytes, int* diag_bytes);
+
+/* ---- described arrays (additions to ABI 7) --------------------------------
+ * Where the embeddings are and what they look like.  The library reads them in place: a
+ * device array by a kernel of its own (any element strides; 16-byte loads when col_stride is 1
+ * and the base address and the row pitch in bytes are multiples of 16), a host array of a
+ * narrow dtype by a copy at its own width into a staging buffer of the handle and the same
+ * kernel.  All arithmetic stays fp64: widening fp32 / fp16 / bf16 is exact for every bit
+ * pattern (subnormals, +-0, +-inf; a NaN stays a NaN), so every result is bit for bit what the
+ * caller would get from the values converted to double on the host. */
+enum { SC_DTYPE_F64 = 0, SC_DTYPE_F32 = 1, SC_DTYPE_F16 = 2, SC_DTYPE_BF16 = 3 };
+enum { SC_MEM_HOST = 0, SC_MEM_DEVICE = 1 };
+typedef struct sc_array {
+  const void* data;    /* first element (a byte offset of the owner already applied) */
+  int32_t dtype;       /* SC_DTYPE_* */
+  int32_t location;    /* SC_MEM_HOST: pageable or pinned host memory; SC_MEM_DEVICE: memory of
+                          the handle's device */
+  int64_t rows, cols;  /* (n, d) */
+  int64_t row_stride;  /* elements (not bytes) from one row to the next, >= 0 */
+  int64_t col_stride;  /* elements from one column to the next, >= 0 (1: rows are contiguous) */
+} sc_array;
+/* sizeof(sc_array) and the byte offsets of its seven fields in declaration order, as compiled
+ * (a binding checks its mirror; sc_struct_sizes keeps its signature) */
+int sc_array_layout(int* array_bytes, int* field_offsets);
 /* number of visible HIP devices (0 if none / runtime unavailable) */
 int sc_device_count(void);
 /* copies the device name (e.g. "AMD Instinct MI355X") and gcnArchName */
@@ -246,6 +269,11 @@ int sc_destroy(sc_handle h);
 int sc_reserve(sc_handle h, int n_max, int d_max);
 const char* sc_last_error(sc_handle h);
 int sc_synchronize(sc_handle h);
+/* The handle's hipStream_t.  Every *_array call reads a device source on this stream (a batch:
+ * after one synchronisation of it, see sc_predict_batch_arrays), so a producer orders its
+ * writes before the call by making this stream wait for them -- the `stream` argument of
+ * __dlpack__ does exactly that.  NULL for a NULL handle. */
+void* sc_stream(sc_handle h);
 /* hipEvent timers in sc_diag.stage_ms: 1 (default) = one pair per stage, 2 = additionally
  * around the individual hot kernels (bench.py's per-kernel roofline list) */
 int sc_set_profiling(sc_handle h, int level);
@@ -287,9 +315,20 @@ int sc_set_blur_weights(sc_handle h, int radius, const double* weights);
 int sc_predict(sc_handle h, const double* x, int n, int d, const sc_config* cfg,
                int64_t* labels, sc_diag* diag);
 
+/* sc_predict on a described source (device or host, fp64 / fp32 / fp16 / bf16, any strides).
+ * SC_ERR_INVALID before any launch for: NULL data, rows or cols <= 0, an unknown dtype or
+ * location, a negative stride, and a SC_MEM_DEVICE pointer that hipPointerGetAttributes does not
+ * report as device memory of the handle's device.  sc_predict(h, x, n, d, ...) is this call on
+ * {x, SC_DTYPE_F64, SC_MEM_HOST, n, d, d, 1}. */
+int sc_predict_array(sc_handle h, const sc_array* x, const sc_config* cfg, int64_t* labels,
+                     sc_diag* diag);
+
 /* Split form, used for device-resident timing and by AutoTune:            */
 /* H2D of the embeddings into the handle's arena. */
 int sc_set_embeddings(sc_handle h, const double* x, int n, int d);
+/* ... of a described source.  Like sc_set_embeddings it returns with the handle's stream
+ * synchronised: the source may be overwritten or freed at once. */
+int sc_set_embeddings_array(sc_handle h, const sc_array* x);
 /* utils.compute_affinity_matrix (utils.py:20-41) on the resident embeddings. */
 int sc_compute_affinity(sc_handle h);
 /* H2D of a caller-supplied (n, n) affinity (custom affinity_function /
@@ -401,6 +440,16 @@ int sc_predict_batch_streams(sc_handle h, const double* const* xs, const int* ns
 int sc_predict_batch_grouped(sc_handle h, const double* const* xs, const int* ns, int d,
                              int count, const sc_config* cfg, int64_t* const* labels,
                              sc_diag* diags, int group);
+/* A batch of described sources (all with the same cols): group > 1 is sc_predict_batch_grouped
+ * with that group size, anything else sc_predict_batch_streams with `streams`.  Every
+ * descriptor is validated before the first launch.  When a source is SC_MEM_DEVICE the call
+ * synchronises the handle's stream ONCE at entry; after that the member streams, lanes and
+ * banks of the batch read the sources freely -- so work that the caller ordered before
+ * sc_stream(h) is complete before anything of the batch reads it.  The upload that rides under
+ * the previous call's pipeline (sc_predict_batch) is for host fp64 sources; device sources are
+ * widened by a kernel on the call's own stream, narrow host sources are copied per call. */
+int sc_predict_batch_arrays(sc_handle h, const sc_array* xs, int count, const sc_config* cfg,
+                            int64_t* const* labels, sc_diag* diags, int group, int streams);
 /* What ran: one code per utterance of the last sc_predict_batch* call on this handle (a
  * member of a grouped batch that was handed back to the single-call path reports
  * SC_BATCH_ROUTE_SINGLE; after sc_predict_batch / sc_predict_batch_streams every code is).
@@ -442,6 +491,8 @@ int sc_naive_cluster(sc_handle h, const double* x, int n, int d, double threshol
 
 /* ---- single stages (ndarray in / ndarray out; parity tests and the
  *      per-op Python classes use these) ------------------------------------- */
+/* the ingest alone: out receives the (rows, cols) fp64 values the pipeline sees for `x` */
+int sc_stage_ingest(sc_handle h, const sc_array* x, double* out);
 /* utils.compute_affinity_matrix (utils.py:20-41) */
 int sc_stage_affinity(sc_handle h, const double* x, int n, int d, double* out);
 /* AffinityRefinementOperation.refine (refinement.py:136-245); op = sc_op,

@@ -1,0 +1,182 @@
+"""Embeddings as the caller holds them -> an `sc_array` descriptor (include/spectralcluster_amd.h).
+
+A NumPy array of float64 / float32 / float16 is described in its own dtype (other dtypes are
+promoted to float64 on the host, as always); anything with `__dlpack__` / `__dlpack_device__` --
+a PyTorch tensor on the GPU, say, float64 / float32 / float16 / bfloat16 -- is read where it
+is, strides and all, through the legacy "dltensor" capsule.  The capsule is parsed with ctypes:
+this package imports no tensor library.
+
+For a device object the producer is asked to order its work before the library's stream
+(`__dlpack__(stream=<the handle's hipStream_t>)`), so the caller synchronises nothing.
+"""
+
+from __future__ import annotations
+
+import ctypes
+import typing
+
+import numpy as np
+
+from spectralcluster_amd import _lib
+
+# DLDeviceType
+KDL_CPU, KDL_CUDA, KDL_ROCM, KDL_ROCM_HOST = 1, 2, 10, 11
+HOST_DEVICE_TYPES = (KDL_CPU, KDL_ROCM_HOST)
+# (a ROCm build of PyTorch may report its device memory as kDLCUDA)
+DEVICE_DEVICE_TYPES = (KDL_ROCM, KDL_CUDA)
+# DLDataTypeCode
+KDL_FLOAT, KDL_BFLOAT = 2, 4
+
+_NUMPY_DTYPES = {np.dtype(np.float64): _lib.SC_DTYPE_F64, np.dtype(np.float32): _lib.SC_DTYPE_F32,
+                 np.dtype(np.float16): _lib.SC_DTYPE_F16}
+_DLPACK_DTYPES = {(KDL_FLOAT, 64): _lib.SC_DTYPE_F64, (KDL_FLOAT, 32): _lib.SC_DTYPE_F32,
+                  (KDL_FLOAT, 16): _lib.SC_DTYPE_F16, (KDL_BFLOAT, 16): _lib.SC_DTYPE_BF16}
+
+
+class DLDevice(ctypes.Structure):
+  _fields_ = [("device_type", ctypes.c_int32), ("device_id", ctypes.c_int32)]
+
+
+class DLDataType(ctypes.Structure):
+  _fields_ = [("code", ctypes.c_uint8), ("bits", ctypes.c_uint8), ("lanes", ctypes.c_uint16)]
+
+
+class DLTensor(ctypes.Structure):
+  _fields_ = [("data", ctypes.c_void_p), ("device", DLDevice), ("ndim", ctypes.c_int32),
+              ("dtype", DLDataType), ("shape", ctypes.POINTER(ctypes.c_int64)),
+              ("strides", ctypes.POINTER(ctypes.c_int64)), ("byte_offset", ctypes.c_uint64)]
+
+
+class DLManagedTensor(ctypes.Structure):
+  pass
+
+
+_deleter_t = ctypes.CFUNCTYPE(None, ctypes.POINTER(DLManagedTensor))
+DLManagedTensor._fields_ = [("dl_tensor", DLTensor), ("manager_ctx", ctypes.c_void_p),
+                            ("deleter", _deleter_t)]
+
+# (PyCapsule_SetName keeps the pointer, not a copy: the names live as long as the module)
+_NAME = b"dltensor"
+_USED_NAME = b"used_dltensor"
+_get_pointer = ctypes.pythonapi.PyCapsule_GetPointer
+_get_pointer.restype = ctypes.c_void_p
+_get_pointer.argtypes = [ctypes.py_object, ctypes.c_char_p]
+_set_name = ctypes.pythonapi.PyCapsule_SetName
+_set_name.restype = ctypes.c_int
+_set_name.argtypes = [ctypes.py_object, ctypes.c_char_p]
+
+
+class Source:
+  """An `sc_array` and what keeps its memory alive until `release()`.
+
+  `array`    the descriptor (pass `ctypes.byref(src.array)`),
+  `numpy`    the caller's ndarray when the input was one (host branches use it as it is),
+  `capsule`  the consumed DLPack capsule otherwise.
+  """
+
+  def __init__(self, array: _lib.ScArray, keep, numpy=None, capsule=None, managed=None):
+    self.array = array
+    self.keep = keep
+    self.numpy = numpy
+    self.capsule = capsule
+    self._managed = managed
+
+  @property
+  def shape(self) -> typing.Tuple[int, int]:
+    return int(self.array.rows), int(self.array.cols)
+
+  @property
+  def is_host_f64(self) -> bool:
+    """Compact float64 rows in host memory: what the `double*` entry points take."""
+    a = self.array
+    return (a.location == _lib.SC_MEM_HOST and a.dtype == _lib.SC_DTYPE_F64 and
+            a.col_stride == 1 and a.row_stride == a.cols)
+
+  def host_f64(self, handle: "_lib.Handle") -> np.ndarray:
+    """The values as a host float64 array, for the branches that compute on the host side of
+    the API (fallback clusterer, size reduction, a user's affinity function): the caller's own
+    ndarray, or one copy through `sc_stage_ingest`."""
+    if self.numpy is not None:
+      return self.numpy
+    out = np.empty(self.shape, dtype=np.float64)
+    handle.check(handle.lib.sc_stage_ingest(handle.raw, ctypes.byref(self.array),
+                                            _lib.as_double_p(out)))
+    return out
+
+  def release(self) -> None:
+    """The library call has returned: hand a DLPack tensor back to its producer."""
+    managed, self._managed = self._managed, None
+    if managed is not None and managed.contents.deleter:
+      managed.contents.deleter(managed)
+    self.keep = None
+
+  def __del__(self):
+    try:
+      self.release()
+    except Exception:  # interpreter shutdown
+      pass
+
+
+def _from_numpy(a: np.ndarray) -> Source:
+  if a.ndim != 2:
+    raise ValueError("embeddings must be 2-dimensional")
+  dtype = _NUMPY_DTYPES.get(a.dtype)
+  if dtype is None:  # ints, bools, longdouble, other byte orders: promoted on the host
+    x = np.ascontiguousarray(a, dtype=np.float64)
+    dtype = _lib.SC_DTYPE_F64
+  else:
+    x = np.ascontiguousarray(a)
+  arr = _lib.ScArray(x.ctypes.data, dtype, _lib.SC_MEM_HOST, x.shape[0], x.shape[1],
+                     x.shape[1], 1)
+  return Source(arr, x, numpy=a)
+
+
+def _from_capsule(capsule, location: int) -> Source:
+  address = _get_pointer(capsule, _NAME)  # raises ValueError for a capsule of another name
+  managed = ctypes.cast(address, ctypes.POINTER(DLManagedTensor))
+  _set_name(capsule, _USED_NAME)  # consumed: the deleter is ours to call now
+  src = Source(_lib.ScArray(), None, capsule=capsule, managed=managed)
+  try:
+    t = managed.contents.dl_tensor
+    if t.ndim != 2:
+      raise ValueError("embeddings must be 2-dimensional")
+    dtype = _DLPACK_DTYPES.get((t.dtype.code, t.dtype.bits)) if t.dtype.lanes == 1 else None
+    if dtype is None:
+      raise TypeError("embeddings must be float64, float32, float16 or bfloat16 "
+                      "(DLPack type code %d, %d bits, %d lanes)"
+                      % (t.dtype.code, t.dtype.bits, t.dtype.lanes))
+    rows, cols = int(t.shape[0]), int(t.shape[1])
+    row_stride, col_stride = (int(t.strides[0]), int(t.strides[1])) if t.strides else (cols, 1)
+    if row_stride < 0 or col_stride < 0:
+      raise ValueError("embeddings with negative strides are not supported")
+    itemsize = t.dtype.bits // 8
+    assert int(t.byte_offset) % itemsize == 0
+    src.array = _lib.ScArray((t.data or 0) + int(t.byte_offset), dtype, location, rows, cols,
+                             row_stride, col_stride)
+  except Exception:
+    src.release()
+    raise
+  return src
+
+
+def describe(embeddings, get_handle: typing.Callable[[], "_lib.Handle"]) -> Source:
+  """`embeddings` -> Source.  TypeError / ValueError for what cannot be taken, before any
+  device call (`get_handle` is only called for an object that says it lives on a GPU: its
+  device must be the handle's, and the handle's stream goes to `__dlpack__`)."""
+  if isinstance(embeddings, np.ndarray):
+    return _from_numpy(embeddings)
+  if not (hasattr(embeddings, "__dlpack__") and hasattr(embeddings, "__dlpack_device__")):
+    raise TypeError("embeddings must be a numpy array")
+  device_type, device_id = embeddings.__dlpack_device__()
+  device_type = int(device_type)
+  if device_type in HOST_DEVICE_TYPES:
+    return _from_capsule(embeddings.__dlpack__(), _lib.SC_MEM_HOST)
+  if device_type not in DEVICE_DEVICE_TYPES:
+    raise TypeError("embeddings live on DLPack device type %d: host memory and ROCm device "
+                    "memory are supported" % device_type)
+  handle = get_handle()
+  if int(device_id) != handle.device:
+    raise ValueError("embeddings are on device %d, the clusterer runs on device %d"
+                     % (int(device_id), handle.device))
+  # the producer makes the library's stream wait for whatever still writes the tensor
+  return _from_capsule(embeddings.__dlpack__(stream=handle.stream()), _lib.SC_MEM_DEVICE)

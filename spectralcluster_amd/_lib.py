@@ -120,6 +120,24 @@ class ScDiag(ctypes.Structure):
     return {name: float(self.stage_ms[i]) for i, name in enumerate(STAGE_NAMES)}
 
 
+# sc_array.dtype / .location
+SC_DTYPE_F64, SC_DTYPE_F32, SC_DTYPE_F16, SC_DTYPE_BF16 = range(4)
+SC_MEM_HOST, SC_MEM_DEVICE = range(2)
+
+
+class ScArray(ctypes.Structure):
+  """Mirror of `sc_array`: where a matrix of embeddings is and what it looks like."""
+  _fields_ = [
+      ("data", ctypes.c_void_p),
+      ("dtype", ctypes.c_int32),
+      ("location", ctypes.c_int32),
+      ("rows", ctypes.c_int64),
+      ("cols", ctypes.c_int64),
+      ("row_stride", ctypes.c_int64),
+      ("col_stride", ctypes.c_int64),
+  ]
+
+
 _c_double_p = ctypes.POINTER(ctypes.c_double)
 _c_int64_p = ctypes.POINTER(ctypes.c_int64)
 _c_int_p = ctypes.POINTER(ctypes.c_int)
@@ -129,6 +147,8 @@ _handle_t = ctypes.c_void_p
 PROTOTYPES = {
     "sc_abi_version": (ctypes.c_int, []),
     "sc_struct_sizes": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int),
+                                       ctypes.POINTER(ctypes.c_int)]),
+    "sc_array_layout": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int),
                                        ctypes.POINTER(ctypes.c_int)]),
     "sc_device_count": (ctypes.c_int, []),
     "sc_device_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_char_p, ctypes.c_int,
@@ -154,6 +174,16 @@ PROTOTYPES = {
                                   ctypes.POINTER(ScDiag)]),
     "sc_set_embeddings": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int,
                                          ctypes.c_int]),
+    "sc_predict_array": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),
+                                        ctypes.POINTER(ScConfig), _c_int64_p,
+                                        ctypes.POINTER(ScDiag)]),
+    "sc_set_embeddings_array": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray)]),
+    "sc_predict_batch_arrays": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray), ctypes.c_int,
+                                               ctypes.POINTER(ScConfig),
+                                               ctypes.POINTER(_c_int64_p),
+                                               ctypes.POINTER(ScDiag), ctypes.c_int,
+                                               ctypes.c_int]),
+    "sc_stage_ingest": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray), _c_double_p]),
     "sc_compute_affinity": (ctypes.c_int, [_handle_t]),
     "sc_set_affinity": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int]),
     "sc_eig_ncluster": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScConfig),
@@ -275,6 +305,11 @@ PROTOTYPES = {
     "sc_comm_barrier": (ctypes.c_int, [_handle_t]),
 }
 
+# ... and the one that returns a pointer (the header test reads the `int` / `const char*` ones)
+POINTER_PROTOTYPES = {
+    "sc_stream": (ctypes.c_void_p, [_handle_t]),
+}
+
 # custom_dist values that run on the device (scipy cdist names)
 KMEANS_METRICS = {"cosine": 0, "euclidean": 1, "sqeuclidean": 2, "cityblock": 3,
                   "chebyshev": 4, "correlation": 5, "braycurtis": 6, "canberra": 7,
@@ -341,7 +376,7 @@ def load() -> ctypes.CDLL:
       lib = ctypes.CDLL(path)
     except OSError as exc:  # missing libamdhip64 etc.
       raise DeviceLibraryError("cannot load %s: %s" % (path, exc)) from exc
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(POINTER_PROTOTYPES.items()):
       fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
       fn.restype = restype
       fn.argtypes = argtypes
@@ -352,6 +387,11 @@ def load() -> ctypes.CDLL:
     if (cfg_bytes.value != ctypes.sizeof(ScConfig) or
         diag_bytes.value != ctypes.sizeof(ScDiag)):
       raise DeviceLibraryError("sc_config / sc_diag layout mismatch in %s" % path)
+    arr_bytes, offsets = ctypes.c_int(0), (ctypes.c_int * len(ScArray._fields_))()
+    lib.sc_array_layout(ctypes.byref(arr_bytes), offsets)
+    if (arr_bytes.value != ctypes.sizeof(ScArray) or
+        list(offsets) != [getattr(ScArray, name).offset for name, _ in ScArray._fields_]):
+      raise DeviceLibraryError("sc_array layout mismatch in %s" % path)
     _lib = lib
     return lib
 
@@ -412,6 +452,10 @@ class Handle:
   @property
   def lib(self):
     return self._lib
+
+  def stream(self) -> int:
+    """The handle's hipStream_t as an integer (what `__dlpack__(stream=...)` takes)."""
+    return int(self._lib.sc_stream(self._h) or 0)
 
   def last_error(self) -> str:
     msg = self._lib.sc_last_error(self._h)

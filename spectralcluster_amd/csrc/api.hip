@@ -229,7 +229,7 @@ extern "C" int sc_destroy(sc_handle h) {
                     &h->td_d,  &h->td_e,  &h->td_theta, &h->td_work, &h->td_tau, &h->td_panel, &h->mvsym,
                     &h->kXc,   &h->kxsq,  &h->kclosest, &h->kcand, &h->kenorm, &h->krnd,
                     &h->kcent, &h->klab32, &h->klab64, &h->kinfo, &h->kchain, &h->gkrnd, &h->gpack, &h->gypack, &h->ginfo, &h->glabels, &h->gjtab,
-                    &h->kbig, &h->kbigw, &h->fq, &h->ft32, &h->fy1, &h->fR, &h->fscal, &h->fwords, &h->fcand, &h->fY, &h->fsplit, &h->fypart, &h->frpart, &h->fq2part, &h->fmx64, &h->ftau64, &h->fplan, &h->Xalt, &h->gneg};
+                    &h->kbig, &h->kbigw, &h->fq, &h->ft32, &h->fy1, &h->fR, &h->fscal, &h->fwords, &h->fcand, &h->fY, &h->fsplit, &h->fypart, &h->frpart, &h->fq2part, &h->fmx64, &h->ftau64, &h->fplan, &h->Xalt, &h->Xstage, &h->gneg};
   for (DevBuf* b : bufs)
     if (b->p) hipFree(b->p);
   for (DevBuf& b : h->kgen)
@@ -567,24 +567,7 @@ static int run_refine_op(sc_handle h, int op, const sc_config* cfg, const double
 // ------------------------------------------------------------------------------
 // embeddings / affinity
 // ------------------------------------------------------------------------------
-extern "C" int sc_set_embeddings(sc_handle h, const double* x, int n, int d) {
-  if (!h) return SC_ERR_INVALID;
-  if (!x || n <= 0 || d <= 0) return fail(h, SC_ERR_INVALID, "embeddings must be (n, d)");
-  SC_HIP(h, hipSetDevice(h->device));
-  SC_TRY(ensure_matrices(h, n, d));
-  h->n = n;
-  h->d = d;
-  h->ldn = matrix_ld(n);
-  h->ldx = round_up(d, 16);
-  h->have_affinity = h->have_cropval = false;
-  h->n_vec = 0;
-  h->sweep_slot.clear();  // (eigenvectors of a sweep on the previous affinity)
-  SC_TRY(h2d_matrix(h, x, n, d, ptr<double>(h->X), h->ldx));
-  SC_HIP(h, hipStreamSynchronize(h->stream));  // caller may reuse x immediately
-  h->have_x = true;
-  return SC_OK;
-}
-
+// (sc_set_embeddings and the other entry points that take embeddings in: ingest.hip)
 extern "C" int sc_compute_affinity(sc_handle h) {
   if (!h) return SC_ERR_INVALID;
   if (!h->have_x) return fail(h, SC_ERR_INVALID, "no embeddings resident");
@@ -1074,13 +1057,11 @@ extern "C" int sc_set_profiling(sc_handle h, int level) {
   return SC_OK;
 }
 
-extern "C" int sc_predict(sc_handle h, const double* x, int n, int d, const sc_config* cfg,
-                          int64_t* labels, sc_diag* diag) {
-  if (!h) return SC_ERR_INVALID;
-  SC_TRY(validate_config(h, cfg));
-  SC_TRY(sc_set_embeddings(h, x, n, d));
-  return sc_run_resident(h, cfg, labels, diag);  // (the upload is outside stage_ms: it is
-                                                 // host-synchronous, time it on the host)
+// what the double* batch entry points describe: compact host fp64 rows, one per utterance
+std::vector<sc_array> host_f64_arrays(const double* const* xs, const int* ns, int d, int count) {
+  std::vector<sc_array> arrays(std::max(count, 0));
+  for (int i = 0; i < count; ++i) arrays[i] = host_f64_array(xs[i], ns[i], d);
+  return arrays;
 }
 
 // Independent calls on ONE handle, one after the other -- with the upload of call i + 1 taken
@@ -1091,24 +1072,33 @@ extern "C" int sc_predict(sc_handle h, const double* x, int n, int d, const sc_c
 // link idles 89 % of the time and the GPU 11 %.  Two buffers: no call ever waits for a buffer
 // its predecessor still reads.  Same kernels, same arguments, same results as sc_predict.
 // (Utterances below 256 KB gain nothing from a second thread: plain loop.)
-int predict_sequence(sc_handle h, const int* idx, int count, const double* const* xs,
+int predict_sequence(sc_handle h, const int* idx, int count, const sc_array* xs,
                      const int* ns, int d, const sc_config* cfg, int64_t* const* labels,
                      sc_diag* diags) {
   auto at = [&](int k) { return idx ? idx[k] : k; };
+  // one call that ingests for itself.  A host source is waited for like sc_predict does; a
+  // device source needs no wait: it outlives the batch call, and the pipeline behind the ingest
+  // kernel synchronises the stream before the next call touches the arena
+  auto one_call = [&](int i) -> int {
+    SC_TRY(validate_config(h, cfg));
+    SC_HIP(h, hipSetDevice(h->device));
+    h->sweep_slot.clear();
+    SC_TRY(ingest_embeddings(h, xs[i], xs[i].location == SC_MEM_HOST));
+    return sc_run_resident(h, cfg, labels[i], diags ? diags + i : nullptr);
+  };
   int nmax = 0;
   size_t smallest = ~(size_t)0;
+  bool prefetchable = true;  // the helper thread's copy is for host fp64 rows
   for (int k = 0; k < count; ++k) {
     const int i = at(k);
-    if (!xs[i] || ns[i] <= 0 || d <= 0) { smallest = 0; continue; }
+    if (!xs[i].data || ns[i] <= 0 || d <= 0) { smallest = 0; continue; }
     nmax = std::max(nmax, ns[i]);
     smallest = std::min(smallest, (size_t)ns[i] * d * sizeof(double));
+    prefetchable = prefetchable && array_is_host_f64_rows(xs[i]);
   }
   if (nmax > 0) SC_TRY(sc_reserve(h, nmax, d));  // one arena sized for the largest member
-  if (count < 2 || smallest < ((size_t)256 << 10)) {
-    for (int k = 0; k < count; ++k) {
-      const int i = at(k);
-      SC_TRY(sc_predict(h, xs[i], ns[i], d, cfg, labels[i], diags ? diags + i : nullptr));
-    }
+  if (count < 2 || smallest < ((size_t)256 << 10) || !prefetchable) {
+    for (int k = 0; k < count; ++k) SC_TRY(one_call(at(k)));
     return SC_OK;
   }
   SC_TRY(validate_config(h, cfg));
@@ -1134,9 +1124,10 @@ int predict_sequence(sc_handle h, const int* idx, int count, const double* const
         if (stop) return;
       }
       const int i = at(k);
-      hipError_t e = hipMemcpy2DAsync(slot[k & 1].p, ldx * sizeof(double), xs[i],
-                                      (size_t)d * sizeof(double), (size_t)d * sizeof(double),
-                                      ns[i], hipMemcpyHostToDevice, h->copy_stream);
+      hipError_t e = hipMemcpy2DAsync(slot[k & 1].p, ldx * sizeof(double), xs[i].data,
+                                      (size_t)(ns[i] == 1 ? d : xs[i].row_stride) * sizeof(double),
+                                      (size_t)d * sizeof(double), ns[i], hipMemcpyHostToDevice,
+                                      h->copy_stream);
       if (e == hipSuccess) e = hipStreamSynchronize(h->copy_stream);
       std::lock_guard<std::mutex> lock(mu);
       if (e != hipSuccess) {
@@ -1153,10 +1144,7 @@ int predict_sequence(sc_handle h, const int* idx, int count, const double* const
   try {
     helper = std::thread(upload_loop);
   } catch (...) {  // (no thread to be had: every call uploads for itself)
-    for (int k = 0; k < count; ++k) {
-      const int i = at(k);
-      SC_TRY(sc_predict(h, xs[i], ns[i], d, cfg, labels[i], diags ? diags + i : nullptr));
-    }
+    for (int k = 0; k < count; ++k) SC_TRY(one_call(at(k)));
     return SC_OK;
   }
   int rc = SC_OK;
@@ -1201,7 +1189,8 @@ extern "C" int sc_predict_batch(sc_handle h, const double* const* xs, const int*
   if (!h) return SC_ERR_INVALID;
   if (!xs || !ns || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
   h->last_routes.assign(count, SC_BATCH_ROUTE_SINGLE);
-  return predict_sequence(h, nullptr, count, xs, ns, d, cfg, labels, diags);
+  const std::vector<sc_array> arrays = host_f64_arrays(xs, ns, d, count);
+  return predict_sequence(h, nullptr, count, arrays.data(), ns, d, cfg, labels, diags);
 }
 
 extern "C" int sc_last_batch_routes(sc_handle h, int32_t* routes, int count) {
@@ -1223,9 +1212,16 @@ extern "C" int sc_predict_batch_streams(sc_handle h, const double* const* xs, co
                                         int64_t* const* labels, sc_diag* diags, int streams) {
   if (!h) return SC_ERR_INVALID;
   if (!xs || !ns || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  const std::vector<sc_array> arrays = host_f64_arrays(xs, ns, d, count);
+  return predict_batch_streams_impl(h, arrays.data(), ns, d, count, cfg, labels, diags, streams);
+}
+
+int predict_batch_streams_impl(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
+                               const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
+                               int streams) {
   streams = std::max(1, std::min(streams, std::min(count, 32)));
-  if (streams == 1) return sc_predict_batch(h, xs, ns, d, count, cfg, labels, diags);
   h->last_routes.assign(count, SC_BATCH_ROUTE_SINGLE);
+  if (streams == 1) return predict_sequence(h, nullptr, count, xs, ns, d, cfg, labels, diags);
   while ((int)h->pool.size() < streams - 1) {
     sc_handle sub = nullptr;
     const int rc = sc_create(h->device, &sub);

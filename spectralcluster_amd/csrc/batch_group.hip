@@ -82,24 +82,6 @@ int ensure_seed_table(sc_handle lead) {
   return SC_OK;
 }
 
-// sc_set_embeddings without its synchronisation: the caller's arrays stay valid for the whole
-// batch call
-int upload_embeddings(sc_handle h, const double* x, int n, int d) {
-  if (!x || n <= 0 || d <= 0) return fail(h, SC_ERR_INVALID, "embeddings must be (n, d)");
-  SC_TRY(ensure_matrices(h, n, d));
-  h->n = n;
-  h->d = d;
-  h->ldn = matrix_ld(n);
-  h->ldx = round_up(d, 16);
-  h->have_affinity = h->have_cropval = false;
-  h->n_vec = 0;
-  SC_HIP(h, hipMemcpy2DAsync(h->X.p, (size_t)h->ldx * sizeof(double), x,
-                             (size_t)d * sizeof(double), (size_t)d * sizeof(double), n,
-                             hipMemcpyHostToDevice, h->stream));
-  h->have_x = true;
-  return SC_OK;
-}
-
 struct Member {
   int index = -1;        // utterance
   sc_handle h = nullptr;
@@ -112,7 +94,7 @@ struct Member {
 // Stages before the eigensolver of one group, member after member, each on its member's
 // stream: no synchronisation.  `slot0`: first member arena of the bank the group uses.
 // `arenas`: the member arenas to use (default: the lead's gslots).
-int enqueue_front(sc_handle lead, const double* const* xs, const int* ns, int d,
+int enqueue_front(sc_handle lead, const sc_array* xs, const int* ns, int d,
                   const sc_config* cfg, sc_diag* diags, const int* idx, int count, int slot0,
                   Member* mb, std::vector<sc_handle_s*>* arenas = nullptr) {
   for (int z = 0; z < count; ++z) {
@@ -122,7 +104,8 @@ int enqueue_front(sc_handle lead, const double* const* xs, const int* ns, int d,
     SC_TRY(group_slot(lead, slot0 + z, &m.h, arenas));
     sc_handle h = m.h;
     h->err.clear();
-    int rc = upload_embeddings(h, xs[m.index], ns[m.index], d);
+    // (no wait: the caller's arrays stay valid for the whole batch call)
+    int rc = ingest_embeddings(h, xs[m.index], false);
     h->nev = 0;
     sc_diag local;
     sc_diag* dg = diags ? diags + m.index : &local;
@@ -161,7 +144,7 @@ bool grouped_front_covers(const sc_config* cfg) {
 // blockIdx.y / z = member.  Same kernel bodies and arguments per member as
 // sc_compute_affinity + eig_ncluster_impl; the GEMMs compute every tile whole (a single call
 // splits the tiles of a short utterance over K: the sums differ in the last bits).
-int enqueue_front_grouped(sc_handle lead, const double* const* xs, const int* ns, int d,
+int enqueue_front_grouped(sc_handle lead, const sc_array* xs, const int* ns, int d,
                           const sc_config* cfg, sc_diag* diags, const int* idx, int count,
                           int slot0, Member* mb, int bank) {
   hipStream_t s = lead->gbank_stream[bank];
@@ -176,8 +159,9 @@ int enqueue_front_grouped(sc_handle lead, const double* const* xs, const int* ns
     sc_handle h = m.h;
     h->err.clear();
     const int n = ns[m.index];
-    if (!xs[m.index] || n <= 0 || d <= 0) return fail(lead, SC_ERR_INVALID, "embeddings must be (n, d)");
-    int rc = ensure_matrices(h, n, d);
+    // the rows go in on the bank's stream, ahead of the front's launches (arena and problem
+    // size are set by the same call)
+    int rc = ingest_embeddings(h, xs[m.index], false, s);
     if (rc == SC_OK) rc = ensure_eig(h, n);
     if (rc == SC_OK) rc = ensure_tilemap(h, n);
     if (rc == SC_OK) rc = grow(h, h->symflag, 16);
@@ -195,9 +179,6 @@ int enqueue_front_grouped(sc_handle lead, const double* const* xs, const int* ns
     h->affinity_symmetric = h->affinity_from_embeddings = true;
     h->constraint_applied = false;
     if (diags) memset(diags + m.index, 0, sizeof(sc_diag));
-    SC_HIP(lead, hipMemcpy2DAsync(h->X.p, (size_t)h->ldx * sizeof(double), xs[m.index],
-                                  (size_t)d * sizeof(double), (size_t)d * sizeof(double), n,
-                                  hipMemcpyHostToDevice, s));
     FrontItem& f = fi[z];
     f.X = ptr<double>(h->X);
     f.Xn = ptr<double>(h->Xn);
@@ -592,7 +573,7 @@ int finish_short_wave(sc_handle lead, const int* ns, const sc_config* cfg, int64
 
 // The short members of a batch (`list`: indices sorted by n, descending) in waves of kShortWidth
 // on the caller's handle and host thread.
-int run_short_route(sc_handle h, const double* const* xs, const int* ns, int d,
+int run_short_route(sc_handle h, const sc_array* xs, const int* ns, int d,
                     const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
                     const std::vector<int>& list, const EigRequest& rq) {
   if (list.empty()) return SC_OK;
@@ -708,7 +689,7 @@ int independent_streams(sc_handle h, std::vector<hipStream_t> have, hipStream_t*
 
 // One lane of the grouped batch: the groups `mine` (indices into the size-sorted list, `width`
 // members each) on the lead's streams and member arenas.
-int run_group_lane(sc_handle h, const double* const* xs, const int* ns, int d,
+int run_group_lane(sc_handle h, const sc_array* xs, const int* ns, int d,
                    const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
                    const std::vector<int>& grouped, const std::vector<int>& gstart, int width,
                    const std::vector<int>& mine, const EigRequest& rq, int group_limit) {
@@ -796,6 +777,13 @@ extern "C" int sc_predict_batch_grouped(sc_handle h, const double* const* xs, co
                                         int64_t* const* labels, sc_diag* diags, int group) {
   if (!h) return SC_ERR_INVALID;
   if (!xs || !ns || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  const std::vector<sc_array> arrays = host_f64_arrays(xs, ns, d, count);
+  return predict_batch_grouped_impl(h, arrays.data(), ns, d, count, cfg, labels, diags, group);
+}
+
+int predict_batch_grouped_impl(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
+                               const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
+                               int group) {
   SC_TRY(validate_config(h, cfg));
   SC_HIP(h, hipSetDevice(h->device));
   group = std::max(1, std::min(group, kGroupMax));
@@ -817,8 +805,8 @@ extern "C" int sc_predict_batch_grouped(sc_handle h, const double* const* xs, co
   h->groutes = h->last_routes.data();
   std::vector<int> grouped, shorts, single;
   for (int i = 0; i < count; ++i) {
-    if (cfg_ok && xs[i] && ns[i] > 0 && sym_group_eligible(ns[i], rq)) grouped.push_back(i);
-    else if (cfg_ok && xs[i] && ns[i] > 0 && ns[i] <= kDenseMax) shorts.push_back(i);
+    if (cfg_ok && xs[i].data && ns[i] > 0 && sym_group_eligible(ns[i], rq)) grouped.push_back(i);
+    else if (cfg_ok && xs[i].data && ns[i] > 0 && ns[i] <= kDenseMax) shorts.push_back(i);
     else single.push_back(i);
   }
   if (!grouped.empty()) {

@@ -52,6 +52,7 @@ struct sc_handle_s {
   DevBuf X, Xn, A0, B1, B2;
   DevBuf Xalt;                       // second embeddings buffer: the NEXT call's upload lands here
   hipStream_t copy_stream = nullptr; // ... on this stream (predict_sequence, api.hip)
+  DevBuf Xstage;                     // host fp32 / fp16 / bf16 rows at their own width (ingest.hip)
   // n-vectors
   DevBuf rowmax, rowsum, cvec, pvec, tvec, deg, dvec, cut, rmpart, splitk, tilemap;
   DevBuf cropval, statp;  // fused GEMM row statistics: result + per-tile partials
@@ -235,9 +236,29 @@ int ensure_matrices(sc_handle h, int n, int d, bool affinity_copy = true);
 int ensure_tilemap(sc_handle h, int n);
 // `count` independent calls (indices idx[0..count) into xs / ns / labels / diags; idx == nullptr:
 // 0..count-1) one after the other on handle h, each call's upload under its predecessor's pipeline
-int predict_sequence(sc_handle h, const int* idx, int count, const double* const* xs,
+// (the upload under the predecessor's pipeline is for host fp64 rows; a device source is widened
+// by a kernel on the call's stream, a narrow host source copied per call)
+int predict_sequence(sc_handle h, const int* idx, int count, const sc_array* xs,
                      const int* ns, int d, const sc_config* cfg, int64_t* const* labels,
                      sc_diag* diags);
+// ---- described sources (ingest.hip) ---------------------------------------------------
+// every check of a descriptor, before any launch or copy (SC_ERR_INVALID + message)
+int validate_array(sc_handle h, const sc_array* a);
+// what the double* entry points describe: compact host fp64 rows
+sc_array host_f64_array(const double* x, int n, int d);
+std::vector<sc_array> host_f64_arrays(const double* const* xs, const int* ns, int d, int count);
+// host fp64 rows that one hipMemcpy2DAsync moves (col_stride 1, rows that do not overlap)
+bool array_is_host_f64_rows(const sc_array& a);
+// sc_set_embeddings for a described source, on `stream` (nullptr: the handle's): sizes the
+// arena, sets the problem, widens the rows into h->X; `sync` waits for the stream
+int ingest_embeddings(sc_handle h, const sc_array& a, bool sync, hipStream_t stream = nullptr);
+// the bodies of sc_predict_batch_streams / sc_predict_batch_grouped on described sources
+int predict_batch_streams_impl(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
+                               const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
+                               int streams);
+int predict_batch_grouped_impl(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
+                               const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
+                               int group);
 
 int ensure_eig(sc_handle h, int n);
 

@@ -22,6 +22,7 @@ import typing
 
 import numpy as np
 
+from spectralcluster_amd import _dlpack
 from spectralcluster_amd import _lib
 from spectralcluster_amd import autotune as autotune_lib
 from spectralcluster_amd import constraint as constraint_lib
@@ -154,15 +155,22 @@ class SpectralClusterer:
     handle.check(handle.lib.sc_set_constraint(handle.raw, _lib.as_double_p(con), n))
     return True
 
-  def _upload(self, handle: _lib.Handle, embeddings: np.ndarray):
-    """Embeddings -> resident affinity (device GEMM, or the user's function)."""
+  def _upload(self, handle: _lib.Handle, embeddings):
+    """Embeddings (anything predict() takes, or an already described `_dlpack.Source`) ->
+    resident affinity (device GEMM, or the user's function, which gets them as a host array)."""
+    if not isinstance(embeddings, _dlpack.Source):
+      source = _dlpack.describe(embeddings, lambda: handle)
+      try:
+        return self._upload(handle, source)
+      finally:
+        source.release()
+    source = embeddings
     if self.affinity_function is utils.compute_affinity_matrix:
-      x = np.ascontiguousarray(embeddings, dtype=np.float64)
-      handle.check(handle.lib.sc_set_embeddings(
-          handle.raw, _lib.as_double_p(x), x.shape[0], x.shape[1]))
+      handle.check(handle.lib.sc_set_embeddings_array(handle.raw, ctypes.byref(source.array)))
       handle.check(handle.lib.sc_compute_affinity(handle.raw))
     else:
-      a = np.ascontiguousarray(self.affinity_function(embeddings), dtype=np.float64)
+      a = np.ascontiguousarray(self.affinity_function(source.host_f64(handle)),
+                               dtype=np.float64)
       handle.check(handle.lib.sc_set_affinity(handle.raw, _lib.as_double_p(a),
                                               a.shape[0]))
 
@@ -252,21 +260,30 @@ class SpectralClusterer:
     spectral_labels = self.predict(ahc_centroids)
     return utils.chain_labels(ahc_labels, spectral_labels)
 
-  def predict(self, embeddings: np.ndarray, constraint_matrix=None) -> np.ndarray:
-    """Cluster `embeddings` (n_samples, n_features); returns int64 labels
-    (reference spectral_clusterer.py:201-314)."""
-    with _lib.use_device(self.device):  # helpers without a device argument follow self.device
-      return self._predict(embeddings, constraint_matrix)
+  def predict(self, embeddings, constraint_matrix=None) -> np.ndarray:
+    """Cluster `embeddings` (n_samples, n_features); returns int64 labels as a host array
+    (reference spectral_clusterer.py:201-314).
 
-  def _predict(self, embeddings: np.ndarray, constraint_matrix=None) -> np.ndarray:
-    if not isinstance(embeddings, np.ndarray):
-      raise TypeError("embeddings must be a numpy array")
-    if len(embeddings.shape) != 2:
-      raise ValueError("embeddings must be 2-dimensional")
-    n = embeddings.shape[0]
+    `embeddings`: a NumPy array, or any object with `__dlpack__` / `__dlpack_device__` -- a
+    PyTorch tensor, say -- of float64, float32, float16 or bfloat16, in host memory or on the
+    clusterer's GPU, contiguous or a strided view.  It is read where it is and widened to
+    float64 on the device (exactly: labels and eigenvalues are those of
+    `predict(x.astype(np.float64))`).  A device tensor needs no synchronisation by the caller:
+    its producer orders its pending writes before the library's stream, and the tensor may be
+    overwritten or freed when predict() has returned."""
+    with _lib.use_device(self.device):  # helpers without a device argument follow self.device
+      source = _dlpack.describe(embeddings, self._handle)
+      try:
+        return self._predict(source, constraint_matrix)
+      finally:
+        source.release()
+
+  def _predict(self, source: _dlpack.Source, constraint_matrix=None) -> np.ndarray:
+    n = source.shape[0]
     if n < self.fallback_options.spectral_min_embeddings:
       # too few embeddings for spectral clustering (reference :229-233)
-      return fallback_clusterer.FallbackClusterer(self.fallback_options).predict(embeddings)
+      return fallback_clusterer.FallbackClusterer(self.fallback_options).predict(
+          source.host_f64(self._handle()))
     if self.max_spectral_size is not None and n > self.max_spectral_size:
       # reference spectral_clusterer.py:236-248
       if constraint_matrix is not None:
@@ -276,7 +293,7 @@ class SpectralClusterer:
           (self.max_clusters and self.max_spectral_size <= self.max_clusters) or
           (self.min_clusters and self.max_spectral_size <= self.min_clusters)):
         raise ValueError("max_spectral_size should be a relatively big number")
-      return self._reduce_size_and_predict(embeddings)
+      return self._reduce_size_and_predict(source.host_f64(self._handle()))
     handle = self._handle()
     default_tail = (self.post_eigen_cluster_function is custom_distance_kmeans.run_kmeans)
     if default_tail:
@@ -289,25 +306,26 @@ class SpectralClusterer:
     if single_check and by_fallback:
       # this condition only needs the embeddings; it runs on the same device handle, so
       # it goes first and the affinity is built afterwards (reference :253-256)
-      if fallback_clusterer.check_single_cluster(self.fallback_options, embeddings, None):
+      if fallback_clusterer.check_single_cluster(self.fallback_options,
+                                                 source.host_f64(handle), None):
         return np.array([0] * n)
 
     if (self.autotune is None and default_tail and not single_check
         and self.affinity_function is utils.compute_affinity_matrix):
-      # the whole path in one call: H2D(X), device pipeline, D2H(labels)
-      x = np.ascontiguousarray(embeddings, dtype=np.float64)
+      # the whole path in one call: ingest(X), device pipeline, D2H(labels)
       labels = np.empty(n, dtype=np.int64)
       diag = _lib.ScDiag()
-      handle.check(handle.lib.sc_predict(
-          handle.raw, _lib.as_double_p(x), n, x.shape[1], self.build_config(),
+      handle.check(handle.lib.sc_predict_array(
+          handle.raw, ctypes.byref(source.array), self.build_config(),
           _lib.as_int64_p(labels), diag), TypeError)
       self.last_diag = diag
       return labels
 
-    self._upload(handle, embeddings)
+    self._upload(handle, source)
     if single_check and not by_fallback:
-      # single-vs-multi cluster(s) decision on the resident affinity (reference :253-256)
-      if fallback_clusterer.check_single_cluster(self.fallback_options, embeddings, None,
+      # single-vs-multi cluster(s) decision on the resident affinity (reference :253-256; the
+      # affinity conditions do not read the embeddings)
+      if fallback_clusterer.check_single_cluster(self.fallback_options, None, None,
                                                  _resident_on=handle):
         return np.array([0] * n)
     if constrained and self.constraint_options.apply_before_refinement:
@@ -356,7 +374,7 @@ class SpectralClusterer:
         custom_dist=self.custom_dist, max_iter=self.max_iter)
 
   # -------------------------------------------------------------- batch (new)
-  def predict_batch(self, utterances: typing.Sequence[np.ndarray],
+  def predict_batch(self, utterances: typing.Sequence,
                     streams: typing.Optional[int] = None,
                     group: typing.Optional[int] = None,
                     constraint_matrices: typing.Optional[typing.Sequence] = None
@@ -391,6 +409,12 @@ class SpectralClusterer:
     the streams forms: 0 the single-call path, 1 the grouped block Lanczos, 2 the grouped short
     route (`_lib.BATCH_ROUTE_*`).
 
+    An utterance is whatever predict() takes: NumPy arrays and DLPack objects (device tensors,
+    float64 / float32 / float16 / bfloat16) may be mixed.  With a device tensor in the batch the
+    library synchronises its own stream once at entry -- the producers have ordered their work
+    before it -- and the streams of the batch read the tensors from then on; they may be
+    overwritten or freed when the call has returned.
+
     `constraint_matrices`: one `ConstraintMatrix` / ndarray / None per utterance.  With it (and
     `constraint_options`) the batch runs as per-utterance `predict(u, c)` calls; without it a
     batch carries no constraints.
@@ -419,29 +443,44 @@ class SpectralClusterer:
       self.last_batch_routes = []
       return []
     for u in utterances:
-      if not isinstance(u, np.ndarray):
-        raise TypeError("embeddings must be a numpy array")
-    xs = [np.ascontiguousarray(u, dtype=np.float64) for u in utterances]
-    d = xs[0].shape[1] if xs[0].ndim == 2 else -1
-    for x in xs:
-      if x.ndim != 2 or x.shape[1] != d:
+      if isinstance(u, np.ndarray) and u.ndim != 2:
         raise ValueError("all utterances must be (n_i, d) with the same d")
-    count = len(xs)
-    labels = [np.empty(x.shape[0], dtype=np.int64) for x in xs]
-    handle = self._handle()
-    handle.check(handle.lib.sc_clear_constraint(handle.raw))  # a batch carries none
-    xp = (ctypes.POINTER(ctypes.c_double) * count)(*[_lib.as_double_p(x) for x in xs])
-    lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
-    ns = (ctypes.c_int * count)(*[x.shape[0] for x in xs])
-    diags = (_lib.ScDiag * count)()
-    if int(group) > 1:
-      handle.check(handle.lib.sc_predict_batch_grouped(
-          handle.raw, xp, ns, d, count, self.build_config(), lp, diags, int(group)),
-          TypeError)
-    else:
-      handle.check(handle.lib.sc_predict_batch_streams(
-          handle.raw, xp, ns, d, count, self.build_config(), lp, diags,
-          max(1, int(streams))), TypeError)
+    sources = []
+    try:
+      with _lib.use_device(self.device):
+        for u in utterances:
+          sources.append(_dlpack.describe(u, self._handle))
+      d = sources[0].shape[1]
+      if any(src.shape[1] != d for src in sources):
+        raise ValueError("all utterances must be (n_i, d) with the same d")
+      count = len(sources)
+      labels = [np.empty(src.shape[0], dtype=np.int64) for src in sources]
+      handle = self._handle()
+      handle.check(handle.lib.sc_clear_constraint(handle.raw))  # a batch carries none
+      lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
+      diags = (_lib.ScDiag * count)()
+      if all(src.is_host_f64 for src in sources):
+        # compact float64 host rows: the `double*` forms (sc_predict_batch_arrays runs the same
+        # code on the descriptors of exactly these arrays)
+        xp = (ctypes.POINTER(ctypes.c_double) * count)(
+            *[_lib.as_double_p(src.keep) for src in sources])
+        ns = (ctypes.c_int * count)(*[src.shape[0] for src in sources])
+        if int(group) > 1:
+          handle.check(handle.lib.sc_predict_batch_grouped(
+              handle.raw, xp, ns, d, count, self.build_config(), lp, diags, int(group)),
+              TypeError)
+        else:
+          handle.check(handle.lib.sc_predict_batch_streams(
+              handle.raw, xp, ns, d, count, self.build_config(), lp, diags,
+              max(1, int(streams))), TypeError)
+      else:
+        arrays = (_lib.ScArray * count)(*[src.array for src in sources])
+        handle.check(handle.lib.sc_predict_batch_arrays(
+            handle.raw, arrays, count, self.build_config(), lp, diags, int(group),
+            max(1, int(streams))), TypeError)
+    finally:
+      for src in sources:
+        src.release()
     self.last_batch_diags = list(diags)
     # The library always exports the report (_lib.load() fails without it).  Only a stand-in
     # handle lacks it -- tests/test_host_logic.py drives this method with one that has the two
