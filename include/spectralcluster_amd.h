@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 7
+#define SC_ABI_VERSION 8
 #define SC_MAX_OPS 16
 #define SC_MAX_BLUR_RADIUS 32
 #define SC_MAX_EIG 128 /* max eigenvalues reported in sc_diag */
@@ -515,6 +515,47 @@ int sc_stage_constraint_band(sc_handle h, const sc_config* cfg, const double* af
  * all, tiles of the digit product computed, tiles in its upper triangle. */
 int sc_stage_diffuse_rowstats(sc_handle h, const double* a, int n, int mode, double* rowmax,
                               double* rowsum, int32_t* info);
+/* Test entries of the symmetric eigensolver's inner kernels (additions of ABI 8; no reference
+ * equivalent -- the reference calls LAPACK).
+ *
+ * sc_stage_block_operator: ONE application of the solver's block operator, through the launchers
+ * the solver itself uses, for `count` (1 .. 16) independent problems, so that tests can hold the
+ * product kernels to a high-precision product entry by entry.  Problem z: ns[z] rows (0 = an idle
+ * member, grouped form only), matrices[z] (n, n) row-major, vs[z] the block V (n, 8) row-major,
+ * ws[z] (n, 8) receives W; cvecs / pvecs / vs_scales (each array, or an entry, may be NULL) hold
+ * n-vectors c, p, s with NULL standing for c = 1, p = 0, s = c.  route is an OR of
+ * SC_BLOCK_ROUTE_*:
+ *   0                          W = p .* V + c .* (M (s .* V)), the full-matrix kernel
+ *   SC_BLOCK_ROUTE_SYM         the same from the upper triangle of a symmetric M (slab kernel +
+ *                              its reduce)
+ *   SC_BLOCK_ROUTE_TWO_PRODUCT W = p .* V + c .* (M (M (s .* V))), the matrix-free Diffuse operator
+ *   SC_BLOCK_ROUTE_GROUPED     all problems in one grouped launch instead of one launch each
+ * The call allocates device memory shaped like the solver's arena (row pitch, slab workspace),
+ * fills every padding element and workspace with quiet NaNs before the inputs are copied in --
+ * anything outside the matrix that reaches an accumulator shows in W -- runs, and frees. */
+enum {
+  SC_BLOCK_ROUTE_SYM = 1,
+  SC_BLOCK_ROUTE_TWO_PRODUCT = 2,
+  SC_BLOCK_ROUTE_GROUPED = 4
+};
+int sc_stage_block_operator(sc_handle h, int count, const int32_t* ns,
+                            const double* const* matrices, const double* const* cvecs,
+                            const double* const* pvecs, const double* const* vs_scales,
+                            const double* const* vs, double* const* ws, int route);
+/* sc_stage_krylov_state: a read-only copy of what the last block Lanczos solve on this handle
+ * (sc_stage_sym_eig, sc_eig_ncluster, sc_predict ... at n > 128 on a symmetric operator; not the
+ * members of a grouped batch) left on the device, so that tests can check the chain's invariants
+ * at rounding level: the orthonormal basis Q[:, 0:m] -> q (n, m) row-major, the projected operator
+ * T = Q^T Op Q -> t (m, m), the Gram matrix of the last residual block -> g (8, 8), and the
+ * scaling vectors of Op = diag(p) + diag(c) S diag(c) -> c, p (n each).  info (8 ints): [0] m,
+ * [1] n, [2] 1 when S was applied as A A (matrix-free Diffuse: S = A A^T is never formed), [3]
+ * block steps the device had run beyond m when the solve ended (then g belongs to block m + 8 *
+ * info[3]), [4] restart cycles; the rest 0.  q, t, g, c, p may each be NULL (a first call with
+ * info alone sizes the buffers).  SC_ERR_INVALID with a message when the last solve on the handle
+ * did not end in block Lanczos (n <= 128: dense Jacobi; the dense tridiagonal routes; the general
+ * path) or when no solve has run since the handle was given a new problem. */
+int sc_stage_krylov_state(sc_handle h, int32_t* info, double* q, double* t, double* g, double* c,
+                          double* p);
 /* laplacian.compute_laplacian (laplacian.py:24-60) */
 int sc_stage_laplacian(sc_handle h, int laplacian_type, const double* in, int n,
                        double* out);

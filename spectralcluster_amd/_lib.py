@@ -50,7 +50,7 @@ class EigenSolverNotConverged(RuntimeError):
   """The block-Lanczos eigensolver did not reach its tolerance."""
 
 
-SC_ABI_VERSION = 7
+SC_ABI_VERSION = 8
 
 
 class ScConfig(ctypes.Structure):
@@ -165,6 +165,17 @@ PROTOTYPES = {
     "sc_stage_diffuse_rowstats": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int,
                                                  ctypes.c_int, _c_double_p, _c_double_p,
                                                  ctypes.POINTER(ctypes.c_int32)]),
+    "sc_stage_block_operator": (ctypes.c_int, [_handle_t, ctypes.c_int,
+                                               ctypes.POINTER(ctypes.c_int32),
+                                               ctypes.POINTER(_c_double_p),
+                                               ctypes.POINTER(_c_double_p),
+                                               ctypes.POINTER(_c_double_p),
+                                               ctypes.POINTER(_c_double_p),
+                                               ctypes.POINTER(_c_double_p),
+                                               ctypes.POINTER(_c_double_p), ctypes.c_int]),
+    "sc_stage_krylov_state": (ctypes.c_int, [_handle_t, ctypes.POINTER(ctypes.c_int32),
+                                             _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                             _c_double_p]),
     "sc_config_default": (ctypes.c_int, [ctypes.POINTER(ScConfig)]),
     "sc_gaussian_weights": (ctypes.c_int, [ctypes.c_double,
                                            ctypes.POINTER(ctypes.c_int32),

@@ -484,6 +484,7 @@ static EigWorkspace eig_workspace(sc_handle h) {
 int sym_topk(sc_handle h, const FrontResult& op_in, int n, const EigRequest& rq_in,
              sc_diag* diag, EigDecision* out_dc, std::vector<double>* out_w) {
   hipStream_t s = h->stream;
+  h->krylov_m = 0;  // (sc_stage_krylov_state: nothing to report until this solve leaves it)
   SC_TRY(ensure_eig(h, n));
   FrontResult op = op_in;  // (free_materialize turns it into the explicit operator)
   const int ld = op.ld;
@@ -896,6 +897,13 @@ int sym_topk(sc_handle h, const FrontResult& op_in, int n, const EigRequest& rq_
       SC_TRY(check_last(h, "ritz vector launch"));
       h->n_vec = cols;
       if (diag) diag->eig_path = dense ? SC_EIG_PATH_DENSE_TRIDIAG : SC_EIG_PATH_BLOCK_LANCZOS;
+      if (!dense) {  // what sc_stage_krylov_state reports: values this function already has
+        h->krylov_m = m;
+        h->krylov_n = n;
+        h->krylov_cycles = cycles;
+        h->krylov_ahead = ahead;
+        h->krylov_free = op.free_op;
+      }
     }
   }
   if (dense) {
@@ -929,6 +937,58 @@ int sym_topk(sc_handle h, const FrontResult& op_in, int n, const EigRequest& rq_
     }
   }
   *out_dc = dc;
+  return SC_OK;
+}
+
+// What the last block Lanczos solve of sym_topk on this handle left on the device, copied out
+// (tests: the chain's invariants -- orthonormal basis, T = Q^T Op Q, Krylov property -- at
+// rounding level instead of through a converged spectrum).  Read-only: it copies from h->Q,
+// h->T, h->G, h->cvec, h->pvec and changes nothing.
+//
+// Why Q[:, 0:m] and T[0:m, 0:m] are still what the solve's last check saw:
+//   * the block step from a basis of m' vectors (enqueue_step(m')) writes Q[:, m' + 8 .. m' + 15]
+//     (the store link, store_col = m' + 8) and T[0 : m' + 8, m' .. m' + 7] with its mirror
+//     T[m' .. m' + 7, 0 : m' + 8] (lz_rows_body, col0 = m'; the host chain's reduce_H the same).
+//     Steps enqueued ahead of the check that ended the solve have m' >= m: columns and rows >= m
+//     of T, columns >= m + 8 of Q.  (They do overwrite W, Vs and G: with info[3] > 0 the G
+//     returned belongs to block m + 8 * info[3], not to the check.)
+//   * the exit path reads Q (launch_basis_times_Y into E, back_transform_cols on E) and Y; it
+//     writes neither Q nor T.
+//   * a thick restart writes Q2, swaps the handles' buffers and resets T before the next step;
+//     h->Q is the current basis whenever the loop exits.
+//   * every entry point that brings a new problem (ensure_matrices), a solve that does not end
+//     in block Lanczos, the general path (which uses Q2 as scratch) and a regrown arena
+//     (ensure_eig) reset krylov_m, so stale buffers are never reported.
+// info (8 ints): [0] m, [1] n, [2] 1 when the operator was the two-product form diag(p) +
+// diag(c) A A diag(c), [3] block steps enqueued beyond m, [4] restart cycles.  q (n, m)
+// row-major, t (m, m), g (8, 8), c, p (n each); any of them may be NULL (info alone sizes a
+// second call).
+extern "C" int sc_stage_krylov_state(sc_handle h, int32_t* info, double* q, double* t, double* g,
+                                     double* c, double* p) {
+  if (!h) return SC_ERR_INVALID;
+  if (!info) return fail(h, SC_ERR_INVALID, "krylov state: info is NULL");
+  if (h->krylov_m <= 0)
+    return fail(h, SC_ERR_INVALID,
+                "krylov state: the last solve on this handle was not block Lanczos (dense "
+                "Jacobi, tridiagonal or general path), or none has run");
+  SC_HIP(h, hipSetDevice(h->device));
+  const int m = h->krylov_m, n = h->krylov_n;
+  memset(info, 0, 8 * sizeof(int32_t));
+  info[0] = m;
+  info[1] = n;
+  info[2] = h->krylov_free ? 1 : 0;
+  info[3] = h->krylov_ahead;
+  info[4] = h->krylov_cycles;
+  hipStream_t s = h->stream;
+  const size_t row = (size_t)m * sizeof(double), pitch = (size_t)kLdq * sizeof(double);
+  if (q) SC_HIP(h, hipMemcpy2DAsync(q, row, h->Q.p, pitch, row, n, hipMemcpyDeviceToHost, s));
+  if (t) SC_HIP(h, hipMemcpy2DAsync(t, row, h->T.p, pitch, row, m, hipMemcpyDeviceToHost, s));
+  if (g)
+    SC_HIP(h, hipMemcpyAsync(g, h->G.p, kEigBlock * kEigBlock * sizeof(double),
+                             hipMemcpyDeviceToHost, s));
+  if (c) SC_HIP(h, hipMemcpyAsync(c, h->cvec.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (p) SC_HIP(h, hipMemcpyAsync(p, h->pvec.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+  SC_HIP(h, hipStreamSynchronize(s));
   return SC_OK;
 }
 
@@ -1553,6 +1613,7 @@ static int gen_dense_large(sc_handle h, const double* M, int ld, int n, int lapl
 int gen_topk(sc_handle h, const double* M, int ld, int n, int laplacian_type,
                     const EigRequest& rq_in, sc_diag* diag, EigDecision* out_dc,
                     std::vector<double>* out_w, double* scratch) {
+  h->krylov_m = 0;  // (sc_stage_krylov_state: the Arnoldi chain reuses Q / Q2)
   EigRequest rq = rq_in;
   hipStream_t s = h->stream;
   SC_TRY(ensure_eig(h, n));

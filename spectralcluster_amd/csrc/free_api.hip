@@ -1,6 +1,8 @@
 // Host side of the matrix-free Diffuse (kernels: diffuse_free.hip): when the
 // route is taken, the statistics pipeline, the exact evaluation of rows the candidate search
 // cannot prune, and the two-pass operator the eigensolver applies instead of reading S.
+#include <limits>
+
 #include "handle.h"
 
 namespace {
@@ -209,13 +211,12 @@ int free_diffuse_stats(sc_handle h, const double* A, int ld, int n, bool have_am
 }
 
 // plain product W = A Vs by the solver's own block matvec (c = 1, p = 0)
-static void plain_matvec(sc_handle h, const double* A, int ld, int n, bool sym_mv,
-                         const double* Vs, double* W) {
+static void plain_matvec(hipStream_t s, const double* A, int ld, int n, bool sym_mv,
+                         const double* Vs, double* W, double* slabs) {
   if (sym_mv)
-    launch_block_matvec_sym(h->stream, A, ld, n, nullptr, nullptr, Vs, kEigBlock, Vs, W,
-                            ptr<double>(h->mvsym));
+    launch_block_matvec_sym(s, A, ld, n, nullptr, nullptr, Vs, kEigBlock, Vs, W, slabs);
   else
-    launch_block_matvec(h->stream, A, ld, n, nullptr, nullptr, Vs, kEigBlock, Vs, W);
+    launch_block_matvec(s, A, ld, n, nullptr, nullptr, Vs, kEigBlock, Vs, W);
 }
 
 int free_fix_overflow(sc_handle h, const double* A, int ld, int n, bool* changed,
@@ -237,7 +238,8 @@ int free_fix_overflow(sc_handle h, const double* A, int ld, int n, bool* changed
   for (int r0 = 0; r0 < rows; r0 += kEigBlock) {
     const int nr = std::min(kEigBlock, rows - r0);
     launch_free_gather_rows(s, A, n, ld, ids + r0, nr, ptr<double>(h->Vs));
-    plain_matvec(h, A, ld, n, sym_mv, ptr<double>(h->Vs), ptr<double>(h->W));
+    plain_matvec(s, A, ld, n, sym_mv, ptr<double>(h->Vs), ptr<double>(h->W),
+                 ptr<double>(h->mvsym));
     launch_free_colmax(s, ptr<double>(h->W), n, ids + r0, nr, ptr<double>(h->rowmax));
   }
   SC_TRY(check_last(h, "matrix-free diffuse: exact rows"));
@@ -245,16 +247,21 @@ int free_fix_overflow(sc_handle h, const double* A, int ld, int n, bool* changed
   return SC_OK;
 }
 
+void free_apply_operator(hipStream_t s, const double* A, int ld, int n, bool sym_mv,
+                         const double* cvec, const double* pvec, const double* V, int ldv,
+                         const double* Vs, double* fY, double* W, double* slabs) {
+  // fY = A Vs (Vs = c .* V, left by the chain), then W = p .* V + c .* (A fY)
+  plain_matvec(s, A, ld, n, sym_mv, Vs, fY, slabs);
+  if (sym_mv)
+    launch_block_matvec_sym(s, A, ld, n, cvec, pvec, V, ldv, fY, W, slabs);
+  else
+    launch_block_matvec(s, A, ld, n, cvec, pvec, V, ldv, fY, W);
+}
 void free_apply_operator(sc_handle h, const double* A, int ld, int n, bool sym_mv,
                          const double* V, int ldv) {
-  // fY = A Vs (Vs = c .* V, left by the chain), then W = p .* V + c .* (A fY)
-  plain_matvec(h, A, ld, n, sym_mv, ptr<double>(h->Vs), ptr<double>(h->fY));
-  if (sym_mv)
-    launch_block_matvec_sym(h->stream, A, ld, n, ptr<double>(h->cvec), ptr<double>(h->pvec), V,
-                            ldv, ptr<double>(h->fY), ptr<double>(h->W), ptr<double>(h->mvsym));
-  else
-    launch_block_matvec(h->stream, A, ld, n, ptr<double>(h->cvec), ptr<double>(h->pvec), V, ldv,
-                        ptr<double>(h->fY), ptr<double>(h->W));
+  free_apply_operator(h->stream, A, ld, n, sym_mv, ptr<double>(h->cvec), ptr<double>(h->pvec), V,
+                      ldv, ptr<double>(h->Vs), ptr<double>(h->fY), ptr<double>(h->W),
+                      ptr<double>(h->mvsym));
 }
 
 // rowmax(S), rowsum(S) of S = a a^T for a symmetric (n, n) input by either route (parity
@@ -309,5 +316,137 @@ extern "C" int sc_stage_diffuse_rowstats(sc_handle h, const double* a, int n, in
   SC_HIP(h, hipMemcpyAsync(rowsum, h->rowsum.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
   SC_HIP(h, hipStreamSynchronize(s));
   if (info) memcpy(info, inf, sizeof(inf));
+  return SC_OK;
+}
+
+// One application of the solver's block operator through the production launchers (tests: the
+// kernels against a high-precision product, position by position).  Owns its device memory.
+//
+// Sizing.  What the launched kernels index, from their own expressions (eig.hip):
+//   matrix   rows are clamped to n - 1 and a 16-byte load is issued only while its second column
+//            is < ld (k_block_matvec: kb + 8 q + 1 < ld; k_block_matvec_sym: c0 + 32 cs + 8 q +
+//            2 lg + 1 < ld), so the largest element read is (n - 1) * ld + ld - 1: n * ld doubles,
+//            what ensure_matrices gives a matrix (pitch matrix_ld(n), no rows beyond n);
+//   Vs, fY   row k < n only (k < n / row < n selects): n * 8 doubles, as ensure_eig;
+//   V        row < n at pitch ldv = 8: n * 8;   c, p: row < n: n;   W: row < n: n * 8;
+//   slabs    direct slab (item * 128 + local row) * 8 + column with item < nt (nt + 1) / 2, then as
+//            many mirror slabs: 2 * nt (nt + 1) / 2 * 128 * 8 = matvec_sym_workspace_doubles(n),
+//            for the grouped launch too (a member's workgroups beyond ITS tile count return).
+// The matrix allocation (padding columns included), the slabs, fY and W start as quiet NaNs: the
+// kernels mask what lies outside the matrix by select, so a padding column, a clamped row or a
+// slab row nobody wrote that reaches an accumulator shows in W.
+extern "C" int sc_stage_block_operator(sc_handle h, int count, const int32_t* ns,
+                                       const double* const* matrices, const double* const* cvecs,
+                                       const double* const* pvecs,
+                                       const double* const* vs_scales, const double* const* vs,
+                                       double* const* ws, int route) {
+  if (!h) return SC_ERR_INVALID;
+  const int known = SC_BLOCK_ROUTE_SYM | SC_BLOCK_ROUTE_TWO_PRODUCT | SC_BLOCK_ROUTE_GROUPED;
+  if (count < 1 || count > kGroupMax || !ns || !matrices || !vs || !ws || (route & ~known))
+    return fail(h, SC_ERR_INVALID, "bad block operator request");
+  const bool sym = (route & SC_BLOCK_ROUTE_SYM) != 0;
+  const bool two = (route & SC_BLOCK_ROUTE_TWO_PRODUCT) != 0;
+  const bool grouped = (route & SC_BLOCK_ROUTE_GROUPED) != 0;
+  for (int z = 0; z < count; ++z) {
+    if (ns[z] < 0 || (ns[z] == 0 && !grouped))
+      return fail(h, SC_ERR_INVALID, "block operator: n must be positive (0: idle, grouped only)");
+    if (ns[z] > 0 && (!matrices[z] || !vs[z] || !ws[z]))
+      return fail(h, SC_ERR_INVALID, "block operator: NULL matrix, block or result");
+  }
+  SC_HIP(h, hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  struct Owned {  // freed however the function returns
+    std::vector<void*> p;
+    ~Owned() {
+      for (void* q : p) (void)hipFree(q);
+    }
+  } owned;
+  const double qnan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<double> stage;
+  // a device buffer of `count` doubles: quiet NaNs when src == nullptr, else a copy of src
+  auto device = [&](size_t doubles, const double* src, double** out) -> int {
+    void* d = nullptr;
+    SC_HIP(h, hipMalloc(&d, std::max<size_t>(doubles, 1) * sizeof(double)));
+    owned.p.push_back(d);
+    if (!src) {
+      stage.assign(doubles, qnan);
+      src = stage.data();
+    }
+    SC_HIP(h, hipMemcpyAsync(d, src, doubles * sizeof(double), hipMemcpyHostToDevice, s));
+    SC_HIP(h, hipStreamSynchronize(s));  // (`stage` and `scaled` are reused)
+    *out = reinterpret_cast<double*>(d);
+    return SC_OK;
+  };
+  MatvecItem mv[kGroupMax];
+  double* fY[kGroupMax] = {nullptr};
+  memset(mv, 0, sizeof(mv));
+  std::vector<double> scaled;
+  for (int z = 0; z < count; ++z) {
+    const int n = ns[z];
+    if (n == 0) continue;
+    const int ld = matrix_ld(n);
+    double *S, *V, *Vs, *W, *c = nullptr, *p = nullptr, *slabs = nullptr;
+    SC_TRY(device((size_t)n * ld, nullptr, &S));
+    SC_TRY(h2d_matrix(h, matrices[z], n, n, S, ld));  // (same stream: after the fill)
+    const double* cz = cvecs ? cvecs[z] : nullptr;
+    const double* pz = pvecs ? pvecs[z] : nullptr;
+    const double* sz = (vs_scales && vs_scales[z]) ? vs_scales[z] : cz;
+    if (cz) SC_TRY(device(n, cz, &c));
+    if (pz) SC_TRY(device(n, pz, &p));
+    SC_TRY(device((size_t)n * kEigBlock, vs[z], &V));
+    // Vs = s .* V: one rounding per entry, as the chain's store (k_lz_rows: vs_scale[r] * v)
+    scaled.assign(vs[z], vs[z] + (size_t)n * kEigBlock);
+    if (sz)
+      for (int r = 0; r < n; ++r)
+        for (int j = 0; j < kEigBlock; ++j) scaled[(size_t)r * kEigBlock + j] *= sz[r];
+    SC_TRY(device((size_t)n * kEigBlock, scaled.data(), &Vs));
+    SC_TRY(device((size_t)n * kEigBlock, nullptr, &W));
+    if (two) SC_TRY(device((size_t)n * kEigBlock, nullptr, &fY[z]));
+    if (sym) SC_TRY(device(matvec_sym_workspace_doubles(n), nullptr, &slabs));
+    mv[z].S = S;
+    mv[z].ld = ld;
+    mv[z].n = n;
+    mv[z].cvec = c;
+    mv[z].pvec = p;
+    mv[z].V = V;
+    mv[z].ldv = kEigBlock;
+    mv[z].Vs = Vs;
+    mv[z].W = W;
+    mv[z].slabs = slabs;
+  }
+  if (grouped) {
+    if (two) {
+      // the group solver's sequence (sym_topk_group's block step): fY = A Vs for every member in
+      // one launch (c = 1, p = 0), then W = p .* V + c .* (A fY) in the next
+      MatvecItem inner[kGroupMax];
+      memcpy(inner, mv, sizeof(mv));
+      for (int z = 0; z < count; ++z) {
+        if (mv[z].n == 0) continue;
+        inner[z].cvec = inner[z].pvec = nullptr;
+        inner[z].V = mv[z].Vs;
+        inner[z].W = fY[z];
+        mv[z].Vs = fY[z];
+      }
+      launch_block_matvec_group(s, inner, count, sym);
+    }
+    launch_block_matvec_group(s, mv, count, sym);
+  } else {
+    for (int z = 0; z < count; ++z) {
+      const MatvecItem& a = mv[z];
+      if (two)
+        free_apply_operator(s, a.S, a.ld, a.n, sym, a.cvec, a.pvec, a.V, a.ldv, a.Vs, fY[z], a.W,
+                            a.slabs);
+      else if (sym)
+        launch_block_matvec_sym(s, a.S, a.ld, a.n, a.cvec, a.pvec, a.V, a.ldv, a.Vs, a.W, a.slabs);
+      else
+        launch_block_matvec(s, a.S, a.ld, a.n, a.cvec, a.pvec, a.V, a.ldv, a.Vs, a.W);
+    }
+  }
+  SC_TRY(check_last(h, "block operator launch"));
+  for (int z = 0; z < count; ++z)
+    if (mv[z].n > 0)
+      SC_HIP(h, hipMemcpyAsync(ws[z], mv[z].W, (size_t)mv[z].n * kEigBlock * sizeof(double),
+                               hipMemcpyDeviceToHost, s));
+  SC_HIP(h, hipStreamSynchronize(s));
   return SC_OK;
 }

@@ -161,6 +161,11 @@ struct sc_handle_s {
   int* h_free = nullptr;   // pinned copy of the ovf words (80)
   bool free_checked = false;  // the overflow rows of h_free have been dealt with
   int free_ev[5] = {-1, -1, -1, -1, -1};  // event slots: begin | quantised | product | scans | stats
+  // What the last block Lanczos solve of sym_topk left in Q / T / G / cvec / pvec, for
+  // sc_stage_krylov_state: basis size at exit (0: no such solve, or the arena has moved on), its
+  // n, restart cycles, block steps enqueued beyond the basis (run-ahead), two-product operator
+  int krylov_m = 0, krylov_n = 0, krylov_cycles = 0, krylov_ahead = 0;
+  bool krylov_free = false;
 };
 
 // hipEvent slots of the current call (reset by the entry points); -1 when exhausted
@@ -427,6 +432,11 @@ int free_fix_overflow(sc_handle h, const double* A, int ld, int n, bool* changed
 // W = p .* V + c .* (A (A Vs)) through h->fY (both halves on h->stream)
 void free_apply_operator(sc_handle h, const double* A, int ld, int n, bool sym_mv,
                          const double* V, int ldv);
+// ... on explicit buffers (what the form above passes from the handle): fY n x 8 scratch,
+// slabs matvec_sym_workspace_doubles(n) doubles when sym_mv
+void free_apply_operator(hipStream_t s, const double* A, int ld, int n, bool sym_mv,
+                         const double* cvec, const double* pvec, const double* V, int ldv,
+                         const double* Vs, double* fY, double* W, double* slabs);
 bool wants_full_spectrum(const EigRequest& rq);
 
 // constraints (constraint_api.hip)
