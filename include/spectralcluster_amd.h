@@ -433,7 +433,9 @@ int sc_predict_batch_streams(sc_handle h, const double* const* xs, const int* ns
  * up to 64 utterances per launch and one synchronisation per launch, then the same lockstep
  * k-means; the kernel body, its arguments and the LDS layout are sc_predict's (eigenvalues
  * within 1e-10 relative of it, equal labels), full-spectrum requests included.  Everything
- * else (n >= 4096, a full-spectrum request above 128, non-cosine k-means, constraints,
+ * else (n >= 4096, a full-spectrum request above 128, non-cosine k-means, constraints -- a
+ * resident constraint with a configured operator: this entry carries one for the whole batch or
+ * none; sc_predict_batch_constrained carries one band per utterance through the grouped routes --,
  * group < 2) and every member that leaves its route (a refinement that is not symmetric,
  * more than 32 clusters, a rare branch of the eigensolver) takes the single-call path.
  * sc_last_batch_routes says what ran. */
@@ -450,6 +452,25 @@ int sc_predict_batch_grouped(sc_handle h, const double* const* xs, const int* ns
  * widened by a kernel on the call's own stream, narrow host sources are copied per call. */
 int sc_predict_batch_arrays(sc_handle h, const sc_array* xs, int count, const sc_config* cfg,
                             int64_t* const* labels, sc_diag* diags, int group, int streams);
+/* sc_predict_batch_arrays in its grouped form (group >= 2, else SC_ERR_INVALID) with speaker-turn
+ * constraints: bands[i] is the band of utterance i's ConstraintMatrix (constraint.py:167-207;
+ * xs[i].rows - 1 values as sc_set_constraint_band takes them, host memory, valid for the call), or
+ * NULL for an utterance without a constraint; bands == NULL: none has one.  The operator and its
+ * position come from cfg (constraint_name NONE: the bands are not read).  Routes, groups, banks and
+ * short waves are those of sc_predict_batch_grouped, on one lane with member-by-member fronts:
+ * each member's band becomes the resident constraint of its member arena.  ConstraintPropagation
+ * before refinement runs as ONE chain of grouped launches per group (up to 16 members per launch,
+ * a short wave of 64 in four chunks): the Neumann products of all members share a launch, each tile
+ * with its whole K.  AffinityIntegration, and ConstraintPropagation after refinement, run per
+ * member as in sc_predict.  Members without a band are idle in the chain and otherwise unchanged.
+ * The chain's work matrices are reserved with the member arenas before the first front; when
+ * hipMemGetInfo says they do not fit, the members that carry a band run as single calls (route 0).
+ * The resident constraint of h itself is not read; none is resident in h or in any member arena
+ * when the call returns, whatever it returns.  Every descriptor is validated before the first
+ * launch.  A band of the wrong length cannot be detected here. */
+int sc_predict_batch_constrained(sc_handle h, const sc_array* xs, const double* const* bands,
+                                 int count, const sc_config* cfg, int64_t* const* labels,
+                                 sc_diag* diags, int group);
 /* What ran: one code per utterance of the last sc_predict_batch* call on this handle (a
  * member of a grouped batch that was handed back to the single-call path reports
  * SC_BATCH_ROUTE_SINGLE; after sc_predict_batch / sc_predict_batch_streams every code is).
@@ -507,6 +528,16 @@ int sc_stage_constraint(sc_handle h, const sc_config* cfg, const double* affinit
  * (constraint.py:188-201) given as its band of n - 1 values (sc_set_constraint_band) */
 int sc_stage_constraint_band(sc_handle h, const sc_config* cfg, const double* affinity,
                              const double* band, int n, double* out);
+/* Test entry: ConstraintPropagation (alpha from cfg) of `count` (1 .. 16) SYMMETRIC affinities with
+ * banded constraints as ONE grouped chain, through the launchers sc_predict_batch_constrained uses.
+ * Member z: affinities[z] (ns[z], ns[z]) row-major, bands[z] its ns[z] - 1 values, outs[z] receives
+ * the adjusted affinity.  ns[z] = 0, or bands[z] = NULL with ns[z] > 1, marks an idle member: its
+ * outs[z] is not written.  The call allocates device memory shaped like a member arena (row pitch,
+ * work matrices), fills every padding element and workspace with quiet NaNs before the inputs are
+ * copied in, runs, and frees.  ns[z] <= 8192. */
+int sc_stage_constraint_band_group(sc_handle h, const sc_config* cfg, int count, const int32_t* ns,
+                                   const double* const* affinities, const double* const* bands,
+                                   double* const* outs);
 /* rowmax / rowsum of Diffuse(a) = a a^T (refinement.py:232-234) for a SYMMETRIC (n, n) input --
  * what RowWiseNormalize (refinement.py:240-245) and the Laplacian degree (laplacian.py:41) read
  * of it -- by either route: mode 1 the explicit fp64 product, mode 2 the matrix-free search

@@ -194,6 +194,11 @@ PROTOTYPES = {
                                                ctypes.POINTER(_c_int64_p),
                                                ctypes.POINTER(ScDiag), ctypes.c_int,
                                                ctypes.c_int]),
+    "sc_predict_batch_constrained": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),
+                                                    ctypes.POINTER(_c_double_p), ctypes.c_int,
+                                                    ctypes.POINTER(ScConfig),
+                                                    ctypes.POINTER(_c_int64_p),
+                                                    ctypes.POINTER(ScDiag), ctypes.c_int]),
     "sc_stage_ingest": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray), _c_double_p]),
     "sc_compute_affinity": (ctypes.c_int, [_handle_t]),
     "sc_set_affinity": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int]),
@@ -218,6 +223,12 @@ PROTOTYPES = {
     "sc_stage_constraint_band": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScConfig),
                                                 _c_double_p, _c_double_p, ctypes.c_int,
                                                 _c_double_p]),
+    "sc_stage_constraint_band_group": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScConfig),
+                                                      ctypes.c_int,
+                                                      ctypes.POINTER(ctypes.c_int32),
+                                                      ctypes.POINTER(_c_double_p),
+                                                      ctypes.POINTER(_c_double_p),
+                                                      ctypes.POINTER(_c_double_p)]),
     "sc_ahc": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                               ctypes.c_int, ctypes.c_double, _c_int64_p,
                               ctypes.POINTER(ctypes.c_int)]),

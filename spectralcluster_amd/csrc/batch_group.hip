@@ -25,6 +25,10 @@
 // up to kShortWidth members per launch (run_short_route).  Results agree with
 // sc_predict to the solver's tolerance (the grouped GEMMs sum whole K tiles, the group sets
 // the check schedule), and a batch call is a deterministic function of its input.
+// A batch may carry one speaker-turn band per utterance (sc_predict_batch_constrained): the same
+// routes on one lane with member-by-member fronts, each member's band resident in its arena, and
+// ConstraintPropagation before refinement as one chain of grouped launches per group
+// (enqueue_front; constraint_api.hip: constraint_propagation_group).
 #include <ctime>
 #include <thread>
 
@@ -91,12 +95,64 @@ struct Member {
   const GroupEigMember* eig = nullptr;  // what the group's eigensolver left for it
 };
 
+// What a constrained batch carries (sc_predict_batch_constrained): per utterance the band of its
+// ConstraintMatrix (host memory, n_i - 1 values; nullptr: that utterance has no constraint).
+struct Bands {
+  const double* const* band = nullptr;
+  bool chain = false;  // ConstraintPropagation before refinement: the grouped Neumann chain
+  int ncp = 0;         // cp[] work matrices a member arena holds for the configured operator
+};
+Bands make_bands(const double* const* band, const sc_config* cfg) {
+  Bands b;
+  if (cfg->constraint_name == SC_CONSTRAINT_NONE) return b;  // (nothing would read them)
+  b.band = band;
+  if (cfg->constraint_name == SC_CONSTRAINT_PROPAGATION) {
+    b.chain = cfg->constraint_before_refinement != 0;
+    // the grouped chain works in B1 / B2 (idle until refinement starts) + two more matrices; after
+    // refinement the member's own constraint_propagation() takes its five
+    b.ncp = b.chain ? 2 : 5;
+  }
+  return b;
+}
+// ... and what a member arena holds for it, reserved with the arena (never inside a front)
+int reserve_constraint(sc_handle hz, const Bands* bands, int n_max) {
+  if (!bands || !bands->band) return SC_OK;
+  SC_TRY(grow(hz, hz->Cband, (size_t)std::max(n_max - 1, 1) * sizeof(double)));
+  const size_t nn = (size_t)n_max * matrix_ld(n_max) * sizeof(double);
+  for (int i = 0; i < bands->ncp; ++i) SC_TRY(grow(hz, hz->cp[i], nn));
+  return SC_OK;
+}
+
 // Stages before the eigensolver of one group, member after member, each on its member's
 // stream: no synchronisation.  `slot0`: first member arena of the bank the group uses.
 // `arenas`: the member arenas to use (default: the lead's gslots).
+// `bands`: a member's band goes up behind its affinity and becomes the arena's resident
+// constraint; AffinityIntegration and the after-refinement operators then run per member as in a
+// single call.  ConstraintPropagation before refinement is ONE grouped chain per 16 members on
+// `chain_stream`: it waits for the members' affinities, `chain_ev` hands the adjusted affinities
+// back to the member streams, which go on into the refinement.
 int enqueue_front(sc_handle lead, const sc_array* xs, const int* ns, int d,
                   const sc_config* cfg, sc_diag* diags, const int* idx, int count, int slot0,
-                  Member* mb, std::vector<sc_handle_s*>* arenas = nullptr) {
+                  Member* mb, std::vector<sc_handle_s*>* arenas = nullptr,
+                  const Bands* bands = nullptr, hipStream_t chain_stream = nullptr,
+                  hipEvent_t chain_ev = nullptr) {
+  // refinement, scaling vectors and the hand-over event of member z
+  auto refine = [&](int z) -> int {
+    Member& m = mb[z];
+    sc_handle h = m.h;
+    sc_diag local;
+    sc_diag* dg = diags ? diags + m.index : &local;
+    if (!diags) memset(&local, 0, sizeof(local));
+    const int rc = eig_ncluster_impl(h, cfg, dg, &m.front);
+    if (rc != SC_OK) {
+      lead->err = h->err;
+      return rc;
+    }
+    if (!m.front.symmetric) m.state = 1;
+    SC_HIP(lead, hipEventRecord(h->sync_ev, h->stream));
+    return SC_OK;
+  };
+  std::vector<int> chained;  // members whose affinity the grouped chain adjusts
   for (int z = 0; z < count; ++z) {
     Member& m = mb[z];
     m = Member();
@@ -107,17 +163,65 @@ int enqueue_front(sc_handle lead, const sc_array* xs, const int* ns, int d,
     // (no wait: the caller's arrays stay valid for the whole batch call)
     int rc = ingest_embeddings(h, xs[m.index], false);
     h->nev = 0;
-    sc_diag local;
-    sc_diag* dg = diags ? diags + m.index : &local;
-    memset(dg, 0, sizeof(*dg));
+    if (diags) memset(diags + m.index, 0, sizeof(sc_diag));
     if (rc == SC_OK) rc = sc_compute_affinity(h);
-    if (rc == SC_OK) rc = eig_ncluster_impl(h, cfg, dg, &m.front);
+    // the arena's resident constraint is this member's band, or none
+    h->have_constraint = h->constraint_banded = false;
+    h->qn = 0;
+    const double* band = bands && bands->band ? bands->band[m.index] : nullptr;
+    if (rc == SC_OK && band) {
+      const size_t bytes = (size_t)(h->n - 1) * sizeof(double);
+      rc = grow(h, h->Cband, std::max<size_t>(bytes, sizeof(double)));
+      if (rc == SC_OK && bytes > 0 &&
+          hipMemcpyAsync(h->Cband.p, band, bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+        rc = fail(h, SC_ERR_HIP, "could not upload a constraint band");
+      h->have_constraint = h->constraint_banded = h->constraint_symmetric = true;
+      h->qn = h->n;
+    }
+    if (rc == SC_OK && band && bands->chain) {
+      chained.push_back(z);
+      SC_HIP(lead, hipEventRecord(h->sync_ev, h->stream));  // "affinity and band are there"
+      continue;
+    }
+    if (rc == SC_OK && constraint_active(h, cfg, true)) rc = sc_apply_constraint(h, cfg);
     if (rc != SC_OK) {
       lead->err = h->err;
       return rc;
     }
-    if (!m.front.symmetric) m.state = 1;
-    SC_HIP(lead, hipEventRecord(h->sync_ev, h->stream));
+    SC_TRY(refine(z));
+  }
+  if (chained.empty()) return SC_OK;
+  for (int z : chained) SC_HIP(lead, hipStreamWaitEvent(chain_stream, mb[z].h->sync_ev, 0));
+  for (size_t at = 0; at < chained.size(); at += kGroupMax) {
+    CpGroupMember cm[kGroupMax];
+    const int cnt = (int)std::min<size_t>(kGroupMax, chained.size() - at);
+    for (int q = 0; q < cnt; ++q) {
+      sc_handle h = mb[chained[at + q]].h;
+      const size_t nn = (size_t)h->n * h->ldn * sizeof(double);
+      if (h->cp[0].bytes < nn || h->cp[1].bytes < nn || h->B1.bytes < nn || h->B2.bytes < nn)
+        return fail(lead, SC_ERR_INVALID, "member arena without the chain's work matrices");
+      cm[q].n = h->n;
+      cm[q].ld = h->ldn;
+      cm[q].A = ptr<double>(h->A0);
+      cm[q].P = ptr<double>(h->B1);
+      cm[q].T = ptr<double>(h->B2);
+      cm[q].Pn = ptr<double>(h->cp[0]);
+      cm[q].Tn = ptr<double>(h->cp[1]);
+      cm[q].deg = ptr<double>(h->deg);
+      cm[q].rowmax = ptr<double>(h->cut);
+      cm[q].band = ptr<double>(h->Cband);
+      cm[q].tilemap = h->tilemap_cur;
+    }
+    SC_TRY(constraint_propagation_group(lead, chain_stream, cm, cnt, cfg->constraint_alpha));
+  }
+  SC_HIP(lead, hipEventRecord(chain_ev, chain_stream));
+  for (int z : chained) {
+    sc_handle h = mb[z].h;
+    SC_HIP(lead, hipStreamWaitEvent(h->stream, chain_ev, 0));
+    h->have_cropval = false;  // (what sc_apply_constraint leaves: the epilogue's crop values are stale)
+    h->constraint_applied = true;
+    h->n_vec = 0;
+    SC_TRY(refine(z));
   }
   return SC_OK;
 }
@@ -575,7 +679,7 @@ int finish_short_wave(sc_handle lead, const int* ns, const sc_config* cfg, int64
 // on the caller's handle and host thread.
 int run_short_route(sc_handle h, const sc_array* xs, const int* ns, int d,
                     const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
-                    const std::vector<int>& list, const EigRequest& rq) {
+                    const std::vector<int>& list, const EigRequest& rq, const Bands* bands) {
   if (list.empty()) return SC_OK;
   SC_HIP(h, hipStreamSynchronize(h->stream));
   SC_TRY(ensure_seed_table(h));
@@ -589,9 +693,17 @@ int run_short_route(sc_handle h, const sc_array* xs, const int* ns, int d,
     for (int z = 0; z < wave_count(b); ++z) {
       sc_handle hz = nullptr;
       SC_TRY(group_slot(h, b * kShortWidth + z, &hz, &h->gshort));
-      const int rc = sc_reserve(hz, kDenseMax, d);
+      int rc = sc_reserve(hz, kDenseMax, d);
+      if (rc == SC_OK) rc = reserve_constraint(hz, bands, kDenseMax);
       if (rc != SC_OK) return fail(h, rc, hz->err);
       hz->have_constraint = false;
+    }
+  if (bands && bands->chain)  // the grouped chain of a wave runs on a stream of the wave's bank
+    for (int b = 0; b < banks; ++b) {
+      if (!h->gbank_stream[b])
+        SC_HIP(h, hipStreamCreateWithFlags(&h->gbank_stream[b], hipStreamNonBlocking));
+      if (!h->gbank_ev[b])
+        SC_HIP(h, hipEventCreateWithFlags(&h->gbank_ev[b], hipEventDisableTiming));
     }
   std::vector<Member> mbs[kGroupBanks];
   std::vector<GroupEigMember> em(kShortWidth);
@@ -599,7 +711,7 @@ int run_short_route(sc_handle h, const sc_array* xs, const int* ns, int d,
   auto front = [&](int j) -> int {
     return enqueue_front(h, xs, ns, d, cfg, diags, list.data() + (size_t)j * kShortWidth,
                          wave_count(j), (j % banks) * kShortWidth, mbs[j % banks].data(),
-                         &h->gshort);
+                         &h->gshort, bands, h->gbank_stream[j % banks], h->gbank_ev[j % banks]);
   };
   int rc = front(0);
   for (int j = 0; j < nwaves && rc == SC_OK; ++j) {
@@ -692,7 +804,8 @@ int independent_streams(sc_handle h, std::vector<hipStream_t> have, hipStream_t*
 int run_group_lane(sc_handle h, const sc_array* xs, const int* ns, int d,
                    const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
                    const std::vector<int>& grouped, const std::vector<int>& gstart, int width,
-                   const std::vector<int>& mine, const EigRequest& rq, int group_limit) {
+                   const std::vector<int>& mine, const EigRequest& rq, int group_limit,
+                   const Bands* bands) {
   if (mine.empty()) return SC_OK;
   // (the lead's lockstep chains run on its dedicated stream for the duration of the batch)
   struct StreamSwap {
@@ -735,13 +848,16 @@ int run_group_lane(sc_handle h, const sc_array* xs, const int* ns, int d,
       // (... and the buffers of the matrix-free Diffuse, which a member arena otherwise grows the
       //  first time a member of n >= 1536 lands in it)
       if (rc == SC_OK && free_diffuse_wanted(hz, cfg, largest, rq, true)) rc = ensure_free(hz, largest);
+      if (rc == SC_OK) rc = reserve_constraint(hz, bands, largest);
       if (rc != SC_OK) return fail(h, rc, hz->err);
       hz->have_constraint = false;
     }
   Member mbs[kGroupBanks][kGroupMax];
   int front_bank[kGroupBanks];
   const bool trace = sw::group_trace();
-  const bool covers = grouped_front_covers(cfg);
+  // (a constrained batch never takes the grouped front: its crop value comes out of the affinity
+  //  epilogue, which an adjusted affinity invalidates)
+  const bool covers = grouped_front_covers(cfg) && !bands;
   if (covers) {
     SC_TRY(grow(h, h->blurw, (2 * SC_MAX_BLUR_RADIUS + 1) * sizeof(double)));
     SC_TRY(upload_blur_weights(h, cfg));
@@ -757,7 +873,8 @@ int run_group_lane(sc_handle h, const sc_array* xs, const int* ns, int d,
       return enqueue_front_grouped(h, xs, ns, d, cfg, diags, idx, cnt, b * kGroupMax, mbs[b], b);
     }
     front_bank[b] = -1;
-    return enqueue_front(h, xs, ns, d, cfg, diags, idx, cnt, b * kGroupMax, mbs[b]);
+    return enqueue_front(h, xs, ns, d, cfg, diags, idx, cnt, b * kGroupMax, mbs[b], nullptr, bands,
+                         h->gbank_stream[b], h->gbank_ev[b]);
   };
   for (int j = 0; j < std::min(banks - 1, ngroups); ++j) SC_TRY(front(j));
   for (int j = 0; j < ngroups; ++j) {
@@ -770,7 +887,104 @@ int run_group_lane(sc_handle h, const sc_array* xs, const int* ns, int d,
   return SC_OK;
 }
 
+// The members of a constrained batch that run as single calls on the caller's handle: each with
+// its own band resident for the call (sc_predict with sc_set_constraint_band in front).
+int predict_single_banded(sc_handle h, const std::vector<int>& list, const sc_array* xs,
+                          const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
+                          const Bands& bands) {
+  for (int i : list) {
+    if (bands.band[i]) SC_TRY(sc_set_constraint_band(h, bands.band[i], (int)xs[i].rows));
+    else SC_TRY(sc_clear_constraint(h));
+    h->sweep_slot.clear();
+    SC_TRY(ingest_embeddings(h, xs[i], xs[i].location == SC_MEM_HOST));
+    SC_TRY(sc_run_resident(h, cfg, labels[i], diags ? diags + i : nullptr));
+  }
+  return sc_clear_constraint(h);
+}
+
+// Do the cp[] work matrices of a constrained batch fit?  Worst case: every position of both
+// banks of the Lanczos route at the largest grouped member, every position of both wave banks of
+// the short route at kDenseMax (what the arenas below reserve); what the arenas already hold counts.
+bool constraint_workspace_fits(sc_handle h, const Bands& bands, int largest, bool any_short) {
+  if (bands.ncp == 0) return true;
+  auto need = [&](const std::vector<sc_handle_s*>& slots, int positions, int n) {
+    const size_t nn = (size_t)n * matrix_ld(n) * sizeof(double);
+    size_t bytes = 0;
+    for (int z = 0; z < positions; ++z)
+      for (int i = 0; i < bands.ncp; ++i) {
+        const size_t have = z < (int)slots.size() ? slots[z]->cp[i].bytes : 0;
+        if (have < nn) bytes += nn;
+      }
+    return bytes;
+  };
+  size_t bytes = 0;
+  if (largest > 0) bytes += need(h->gslots, kGroupBanks * kGroupMax, largest);
+  if (any_short) bytes += need(h->gshort, kGroupBanks * kShortWidth, kDenseMax);
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
+  return (double)bytes <= 0.85 * (double)free_b;
+}
+
+int predict_batch_core(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
+                       const sc_config* cfg, int64_t* const* labels, sc_diag* diags, int group,
+                       const Bands& band_set);
+
 }  // namespace
+
+extern "C" int sc_predict_batch_constrained(sc_handle h, const sc_array* xs,
+                                            const double* const* bands, int count,
+                                            const sc_config* cfg, int64_t* const* labels,
+                                            sc_diag* diags, int group) {
+  if (!h) return SC_ERR_INVALID;
+  if (!xs || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  if (group < 2)
+    return fail(h, SC_ERR_INVALID, "sc_predict_batch_constrained is the grouped form: group >= 2");
+  SC_TRY(validate_config(h, cfg));
+  SC_HIP(h, hipSetDevice(h->device));
+  bool device_source = false;
+  std::vector<int> ns(count);
+  for (int i = 0; i < count; ++i) {
+    SC_TRY(validate_array(h, xs + i));
+    if (xs[i].cols != xs[0].cols)
+      return fail(h, SC_ERR_INVALID, "all utterances must be (n_i, d) with the same d");
+    ns[i] = (int)xs[i].rows;
+    device_source |= xs[i].location == SC_MEM_DEVICE;
+  }
+  SC_TRY(sc_clear_constraint(h));  // the handle's own resident constraint takes no part
+  if (count == 0) {
+    h->last_routes.clear();
+    return SC_OK;
+  }
+  if (device_source) SC_HIP(h, hipStreamSynchronize(h->stream));  // (as sc_predict_batch_arrays)
+  return predict_batch_constrained_impl(h, xs, bands, ns.data(), (int)xs[0].cols, count, cfg,
+                                        labels, diags, group);
+}
+
+int predict_batch_constrained_impl(sc_handle h, const sc_array* xs, const double* const* bands,
+                                   const int* ns, int d, int count, const sc_config* cfg,
+                                   int64_t* const* labels, sc_diag* diags, int group) {
+  // no band stays resident in a member arena, and none of them is still on its way up from the
+  // caller's memory, however the batch ends
+  struct Cleanup {
+    sc_handle h;
+    int rc = SC_OK;
+    ~Cleanup() {
+      auto clear = [&](const std::vector<sc_handle_s*>& slots) {
+        for (sc_handle sub : slots) {
+          if (rc != SC_OK) (void)hipStreamSynchronize(sub->stream);
+          (void)sc_clear_constraint(sub);
+        }
+      };
+      clear(h->gslots);
+      clear(h->gshort);
+      for (sc_handle lane : h->glanes) clear(lane->gslots);
+      (void)sc_clear_constraint(h);
+    }
+  } cleanup{h};
+  cleanup.rc = predict_batch_core(h, xs, ns, d, count, cfg, labels, diags, group,
+                                  make_bands(bands, cfg));
+  return cleanup.rc;
+}
 
 extern "C" int sc_predict_batch_grouped(sc_handle h, const double* const* xs, const int* ns,
                                         int d, int count, const sc_config* cfg,
@@ -784,6 +998,16 @@ extern "C" int sc_predict_batch_grouped(sc_handle h, const double* const* xs, co
 int predict_batch_grouped_impl(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
                                const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
                                int group) {
+  return predict_batch_core(h, xs, ns, d, count, cfg, labels, diags, group, Bands());
+}
+
+namespace {
+// partition, groups, lanes, banks and short waves of a grouped batch; `band_set.band` non-null:
+// the constrained batch (one lane, member-by-member fronts, enqueue_front's band handling)
+int predict_batch_core(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
+                       const sc_config* cfg, int64_t* const* labels, sc_diag* diags, int group,
+                       const Bands& band_set) {
+  const Bands* bands = band_set.band ? &band_set : nullptr;
   SC_TRY(validate_config(h, cfg));
   SC_HIP(h, hipSetDevice(h->device));
   group = std::max(1, std::min(group, kGroupMax));
@@ -793,6 +1017,7 @@ int predict_batch_grouped_impl(sc_handle h, const sc_array* xs, const int* ns, i
   const EigRequest rq = make_eig_request(cfg);
   const bool cfg_ok = group > 1 && cfg->kmeans_metric == kKmeansCosine &&
                       !constraint_active(h, cfg, true) && !constraint_active(h, cfg, false);
+  const bool covered = grouped_front_covers(cfg) && !bands;
   // what ran (sc_last_batch_routes): the routes below report into it while the call runs
   h->last_routes.assign(count, SC_BATCH_ROUTE_SINGLE);
   struct RouteReport {
@@ -808,6 +1033,24 @@ int predict_batch_grouped_impl(sc_handle h, const sc_array* xs, const int* ns, i
     if (cfg_ok && xs[i].data && ns[i] > 0 && sym_group_eligible(ns[i], rq)) grouped.push_back(i);
     else if (cfg_ok && xs[i].data && ns[i] > 0 && ns[i] <= kDenseMax) shorts.push_back(i);
     else single.push_back(i);
+  }
+  if (bands) {
+    // the chain's work matrices are reserved with the arenas, before the first front: when they
+    // do not fit, the members that carry a band run as single calls instead
+    int largest = 0;
+    bool any_short = false;
+    for (int i : grouped) largest = std::max(largest, ns[i]);
+    for (int i : shorts) any_short = any_short || bands->band[i];
+    if (!constraint_workspace_fits(h, *bands, largest, any_short)) {
+      auto hand_over = [&](std::vector<int>& list) {
+        std::vector<int> keep;
+        for (int i : list) (bands->band[i] ? single : keep).push_back(i);
+        list.swap(keep);
+      };
+      hand_over(grouped);
+      hand_over(shorts);
+      std::sort(single.begin(), single.end());
+    }
   }
   if (!grouped.empty()) {
     // similar sizes together: a group's launches are sized by its largest member
@@ -827,7 +1070,7 @@ int predict_batch_grouped_impl(sc_handle h, const sc_array* xs, const int* ns, i
     int width = std::min(group, (int)grouped.size());
     const int min_groups = ((int)grouped.size() + width - 1) / width;
     const int lanes_wanted = std::max(
-        1, std::min(kGroupLanes, grouped_front_covers(cfg) ? min_groups / kGroupBanks : 1));
+        1, std::min(kGroupLanes, covered ? min_groups / kGroupBanks : 1));
     if (min_groups < 2) {
       for (int at = 0; at < (int)grouped.size(); at += width) gstart.push_back(at);
     } else {
@@ -866,7 +1109,7 @@ int predict_batch_grouped_impl(sc_handle h, const sc_array* xs, const int* ns, i
     // 4020, 3 lanes 4200, 4 lanes 4150; the second lane's groups in ascending order of size
     // (a GEMM-heavy lane beside a latency-bound one) 3920 against 4020.
     const int lanes =
-        std::max(1, std::min(kGroupLanes, grouped_front_covers(cfg) ? ngroups / kGroupBanks : 1));
+        std::max(1, std::min(kGroupLanes, covered ? ngroups / kGroupBanks : 1));
     std::vector<int> lane_groups[kGroupLanes];
     {  // longest group first, each to the least loaded lane (ties: the lower lane)
       std::vector<double> gcost(ngroups, 0.0);
@@ -932,7 +1175,7 @@ int predict_batch_grouped_impl(sc_handle h, const sc_array* xs, const int* ns, i
           return;
         }
         rcs[l] = run_group_lane(leads[l], xs, ns, d, cfg, labels, diags, grouped, gstart, width,
-                                lane_groups[l], rq, group);
+                                lane_groups[l], rq, group, bands);
       };
       try {
         side.emplace_back(body);
@@ -941,18 +1184,21 @@ int predict_batch_grouped_impl(sc_handle h, const sc_array* xs, const int* ns, i
       }
     }
     rcs[0] = run_group_lane(h, xs, ns, d, cfg, labels, diags, grouped, gstart, width,
-                            lane_groups[0], rq, group);
+                            lane_groups[0], rq, group, bands);
     for (int l = 1; l < lanes; ++l)
       if (inline_lane[l])
         rcs[l] = run_group_lane(leads[l], xs, ns, d, cfg, labels, diags, grouped, gstart, width,
-                                lane_groups[l], rq, group);
+                                lane_groups[l], rq, group, bands);
     for (auto& t : side) t.join();
     {  // member arenas that hold a large share of the device do not outlive the batch (the
        // lanes keep up to 3 x 2 x 16 of them warm otherwise: 21 GB after config 5)
       size_t free_b = 0, total_b = 0, held = 0;
       if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
         for (int l = 0; l < lanes; ++l)
-          for (sc_handle sub : leads[l]->gslots) held += sub->A0.bytes + sub->B1.bytes + sub->B2.bytes;
+          for (sc_handle sub : leads[l]->gslots) {
+            held += sub->A0.bytes + sub->B1.bytes + sub->B2.bytes;
+            for (const DevBuf& w : sub->cp) held += w.bytes;  // (a constrained batch's work matrices)
+          }
         if (held > total_b / 4)
           for (int l = 0; l < lanes; ++l) {
             for (sc_handle sub : leads[l]->gslots) sc_destroy(sub);
@@ -969,14 +1215,17 @@ int predict_batch_grouped_impl(sc_handle h, const sc_array* xs, const int* ns, i
   // kShortWidth members, largest first (a wave's Jacobi launch lasts as long as its largest member)
   if (!shorts.empty()) {
     std::stable_sort(shorts.begin(), shorts.end(), [&](int a, int b) { return ns[a] > ns[b]; });
-    SC_TRY(run_short_route(h, xs, ns, d, cfg, labels, diags, shorts, rq));
+    SC_TRY(run_short_route(h, xs, ns, d, cfg, labels, diags, shorts, rq, bands));
   }
   // (members outside the grouped path's range -- n >= 4096 above all: their uploads ride under
   //  the previous member's pipeline, api.hip predict_sequence)
-  if (!single.empty())
+  if (!single.empty() && bands)
+    SC_TRY(predict_single_banded(h, single, xs, cfg, labels, diags, *bands));
+  else if (!single.empty())
     SC_TRY(predict_sequence(h, single.data(), (int)single.size(), xs, ns, d, cfg, labels, diags));
   return SC_OK;
 }
+}  // namespace
 
 // ------------------------------------------------------------------------------
 // AutoTune: one search level as a group (reference autotune.py:98-111)

@@ -3,6 +3,9 @@
 // ConstraintPropagation is composed from these and the fp64 MFMA GEMM in constraint_api.hip.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstring>
+
 #include "sc_internal.h"
 
 namespace sc {
@@ -41,10 +44,10 @@ __global__ __launch_bounds__(256) void k_affinity_integration_band(
 // dn_i = 1 / (sqrt(deg_i) + EPS);  P = alpha * ((dn_i A_ij) dn_j);  T0 = I + P
 // (first factor of the Neumann product).  Padding columns are zero-filled so the GEMMs
 // may read whole 16-wide K tiles.
-__global__ __launch_bounds__(256) void k_cp_prepare(const double* __restrict__ a,
-                                                    const double* __restrict__ deg,
-                                                    double alpha, double* __restrict__ p,
-                                                    double* __restrict__ t0, int n, int ld) {
+__device__ __forceinline__ void cp_prepare_body(const double* __restrict__ a,
+                                                const double* __restrict__ deg, double alpha,
+                                                double* __restrict__ p, double* __restrict__ t0,
+                                                int n, int ld) {
   const int row = blockIdx.y;
   const int col = blockIdx.x * 256 + threadIdx.x;
   if (col >= ld) return;
@@ -60,6 +63,19 @@ __global__ __launch_bounds__(256) void k_cp_prepare(const double* __restrict__ a
   p[at] = v;
   t0[at] = (row == col ? 1.0 : 0.0) + v;
 }
+__global__ __launch_bounds__(256) void k_cp_prepare(const double* __restrict__ a,
+                                                    const double* __restrict__ deg,
+                                                    double alpha, double* __restrict__ p,
+                                                    double* __restrict__ t0, int n, int ld) {
+  cp_prepare_body(a, deg, alpha, p, t0, n, ld);
+}
+// ... of every member of a group (blockIdx.z = member; CpItem: src = A, vec = deg, dst = P,
+// dst2 = T0)
+__global__ __launch_bounds__(256) void k_cp_prepare_g(const GroupOf<CpItem> g, double alpha) {
+  const CpItem& m = g.s[blockIdx.z];
+  if ((int)blockIdx.y >= m.n || (int)blockIdx.x * 256 >= m.ld) return;
+  cp_prepare_body(m.src, m.vec, alpha, m.dst, m.dst2, m.n, m.ld);
+}
 
 // ---- ConstraintPropagation against a banded Q: X = Tt Q^T without the GEMM --------
 // X[i, j] = band[j-1] Tt[i, j-1] + band[j] Tt[i, j+1]  (terms outside [0, n) dropped), the
@@ -68,9 +84,9 @@ __global__ __launch_bounds__(256) void k_cp_prepare(const double* __restrict__ a
 // lines and ld is even), the columns left and right of its pair come from the neighbouring
 // lanes' registers, and only the first / last lane of a wavefront fetch theirs (a line the next
 // wavefront loads anyway).  Padding columns [n, ld) are written as zero, as in k_cp_prepare.
-__global__ __launch_bounds__(256) void k_cp_band_product(const double* __restrict__ tt,
-                                                         const double* __restrict__ band,
-                                                         double* __restrict__ x, int n, int ld) {
+__device__ __forceinline__ void cp_band_product_body(const double* __restrict__ tt,
+                                                     const double* __restrict__ band,
+                                                     double* __restrict__ x, int n, int ld) {
   const int row = blockIdx.y;
   const int j0 = (blockIdx.x * 256 + threadIdx.x) * 2;
   const bool live = j0 < ld;  // (no early return: every lane takes part in the shuffles)
@@ -97,12 +113,24 @@ __global__ __launch_bounds__(256) void k_cp_band_product(const double* __restric
   o.y = j0 + 1 < n ? (has0 ? b0 * v.x : 0.0) + (has1 ? b1 * right : 0.0) : 0.0;
   *reinterpret_cast<double2*>(x + (size_t)row * ld + j0) = o;
 }
+__global__ __launch_bounds__(256) void k_cp_band_product(const double* __restrict__ tt,
+                                                         const double* __restrict__ band,
+                                                         double* __restrict__ x, int n, int ld) {
+  cp_band_product_body(tt, band, x, n, ld);
+}
+// (CpItem: src = Tt, vec = band, dst = X; whole workgroups leave, so every lane of a wavefront
+// that stays takes part in the shuffles)
+__global__ __launch_bounds__(256) void k_cp_band_product_g(const GroupOf<CpItem> g) {
+  const CpItem& m = g.s[blockIdx.z];
+  if ((int)blockIdx.y >= m.n || (int)blockIdx.x * 512 >= m.ld) return;
+  cp_band_product_body(m.src, m.vec, m.dst, m.n, m.ld);
+}
 
 // ---- ConstraintPropagation, last step (constraint.py:153-163) -------------------
 // F = (1 - alpha)^2 (T Q T);  F > 0: 1 - (1 - F)(1 - A);  else: (1 + F) A
-__global__ __launch_bounds__(256) void k_cp_adjust(const double* __restrict__ tqt,
-                                                   const double* __restrict__ a, double scale,
-                                                   double* __restrict__ out, int n, int ld) {
+__device__ __forceinline__ void cp_adjust_body(const double* __restrict__ tqt,
+                                               const double* __restrict__ a, double scale,
+                                               double* __restrict__ out, int n, int ld) {
   const int row = blockIdx.y;
   const int col = blockIdx.x * 256 + threadIdx.x;
   if (col >= n) return;
@@ -112,6 +140,17 @@ __global__ __launch_bounds__(256) void k_cp_adjust(const double* __restrict__ tq
   // the reference evaluates both branches on masked operands and adds them; the
   // inactive branch contributes exactly 0 (1 - 1*1, or (1 + 0) * 0)
   out[at] = f > 0.0 ? (1.0 - (1.0 - f) * (1.0 - x)) + 0.0 : 0.0 + (1.0 + f) * x;
+}
+__global__ __launch_bounds__(256) void k_cp_adjust(const double* __restrict__ tqt,
+                                                   const double* __restrict__ a, double scale,
+                                                   double* __restrict__ out, int n, int ld) {
+  cp_adjust_body(tqt, a, scale, out, n, ld);
+}
+// (CpItem: src = T Q T, vec = A, dst = the adjusted affinity -- may be A itself)
+__global__ __launch_bounds__(256) void k_cp_adjust_g(const GroupOf<CpItem> g, double scale) {
+  const CpItem& m = g.s[blockIdx.z];
+  if ((int)blockIdx.y >= m.n || (int)blockIdx.x * 256 >= m.n) return;
+  cp_adjust_body(m.src, m.vec, scale, m.dst, m.n, m.ld);
 }
 
 // ---- out = in^T (32x32 tiles through LDS), padding columns zeroed ----------------
@@ -166,6 +205,40 @@ void launch_cp_adjust(hipStream_t s, const double* tqt, const double* a, double 
                       double* out, int n, int ld) {
   hipLaunchKernelGGL(k_cp_adjust, dim3((n + 255) / 256, n), dim3(256), 0, s, tqt, a, scale,
                      out, n, ld);
+}
+// grouped forms: one launch for up to kGroupMax members, blockIdx.z = member (n = 0: idle)
+static GroupOf<CpItem> cp_pack(const CpItem* items, int count, int* nmax, int* ldmax) {
+  GroupOf<CpItem> g;
+  memset(&g, 0, sizeof(g));
+  *nmax = *ldmax = 0;
+  for (int z = 0; z < count && z < kGroupMax; ++z) {
+    if (items[z].n <= 0) continue;
+    g.s[z] = items[z];
+    *nmax = std::max(*nmax, items[z].n);
+    *ldmax = std::max(*ldmax, items[z].ld);
+  }
+  return g;
+}
+void launch_cp_prepare_group(hipStream_t s, const CpItem* items, int count, double alpha) {
+  int nmax, ldmax;
+  const GroupOf<CpItem> g = cp_pack(items, count, &nmax, &ldmax);
+  if (nmax == 0) return;
+  hipLaunchKernelGGL(k_cp_prepare_g, dim3((ldmax + 255) / 256, nmax, count), dim3(256), 0, s, g,
+                     alpha);
+}
+void launch_cp_band_product_group(hipStream_t s, const CpItem* items, int count) {
+  int nmax, ldmax;
+  const GroupOf<CpItem> g = cp_pack(items, count, &nmax, &ldmax);
+  if (nmax == 0) return;
+  hipLaunchKernelGGL(k_cp_band_product_g, dim3((ldmax / 2 + 255) / 256, nmax, count), dim3(256), 0,
+                     s, g);
+}
+void launch_cp_adjust_group(hipStream_t s, const CpItem* items, int count, double scale) {
+  int nmax, ldmax;
+  const GroupOf<CpItem> g = cp_pack(items, count, &nmax, &ldmax);
+  if (nmax == 0) return;
+  hipLaunchKernelGGL(k_cp_adjust_g, dim3((nmax + 255) / 256, nmax, count), dim3(256), 0, s, g,
+                     scale);
 }
 void launch_transpose(hipStream_t s, const double* in, double* out, int n, int ld) {
   const int t = (n + 31) / 32, tc = (ld + 31) / 32;

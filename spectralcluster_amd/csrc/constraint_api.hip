@@ -1,6 +1,8 @@
 // Host side of the constraint operators (reference constraint.py:95-164): the resident
 // constraint (a dense matrix, or the band of ConstraintMatrix, constraint.py:167-207) and the
 // GEMM chain of ConstraintPropagation; kernels in constraint.hip and gemm_f64.hip.
+#include <limits>
+
 #include "handle.h"
 
 // ------------------------------------------------------------------------------
@@ -28,15 +30,13 @@ int device_is_symmetric(sc_handle h, const double* m, int n, int ld, bool* out) 
 // only; a general A carries explicit transposes instead.
 // `banded`: Q is the matrix sc_set_constraint_band describes by `band` (n - 1 values, none for
 // n = 1); q is not read and T^T Q^T is one streaming pass instead of a GEMM.
-static int constraint_propagation(sc_handle h, const double* a, bool sym_a, const double* q,
-                                  bool sym_q, const double* band, bool banded, double alpha,
-                                  double* out, int n, int ld) {
-  hipStream_t s = h->stream;
+// factors (I + P^(2^j)), j = 0 .. steps-1, of the Neumann product for this alpha (they leave a
+// remainder of P^(2^steps)); the refusals of the device route
+static int neumann_steps(sc_handle h, double alpha, int* out) {
   const double mag = fabs(alpha);
   if (!(mag < 1.0))
     return fail(h, SC_ERR_UNSUPPORTED,
                 "ConstraintPropagation on the device needs |constraint_propagation_alpha| < 1");
-  // factors (I + P^(2^j)), j = 0 .. steps-1, leave a remainder of P^(2^steps)
   int steps = 0;
   if (mag > 0.0) {
     double rem = mag;
@@ -48,6 +48,16 @@ static int constraint_propagation(sc_handle h, const double* a, bool sym_a, cons
       return fail(h, SC_ERR_UNSUPPORTED,
                   "constraint_propagation_alpha too close to 1 for the Neumann product");
   }
+  *out = steps;
+  return SC_OK;
+}
+
+static int constraint_propagation(sc_handle h, const double* a, bool sym_a, const double* q,
+                                  bool sym_q, const double* band, bool banded, double alpha,
+                                  double* out, int n, int ld) {
+  hipStream_t s = h->stream;
+  int steps = 0;
+  SC_TRY(neumann_steps(h, alpha, &steps));
   const size_t bytes = (size_t)n * ld * sizeof(double);
   for (int i = 0; i < 5; ++i) SC_TRY(grow(h, h->cp[i], bytes));
   SC_TRY(ensure_tilemap(h, n));
@@ -92,6 +102,75 @@ static int constraint_propagation(sc_handle h, const double* a, bool sym_a, cons
   launch_gemm_nt(s, T, ld, X, ld, Pn, ld, n, n, n, kEpiNone, sym_f, ws, sym_f ? tm : nullptr);
   launch_cp_adjust(s, Pn, a, (1.0 - alpha) * (1.0 - alpha), out, n, ld);
   return check_last(h, "constraint propagation launch");
+}
+
+// The same for up to kGroupMax symmetric affinities with banded constraints as ONE chain of
+// grouped launches on stream s (a batch group's members, batch_group.hip): row sums, prepare,
+// steps - 1 x (P <- P P, T <- T + T P), band product, T X^T, adjust -- 2 steps + 3 launches for
+// the whole group where the members one by one take 13 each (and split their few tiles over K).
+// `steps` depends on alpha alone.  Per member the elementwise arithmetic is the single route's;
+// the products sum every tile's K whole.  The adjusted affinity replaces mem[z].A.  No
+// allocation, no synchronisation.
+int constraint_propagation_group(sc_handle lead, hipStream_t s, const CpGroupMember* mem,
+                                 int count, double alpha) {
+  int steps = 0;
+  SC_TRY(neumann_steps(lead, alpha, &steps));
+  if (count < 1 || count > kGroupMax)
+    return fail(lead, SC_ERR_INVALID, "a constraint group holds 1 .. 16 members");
+  FrontItem rs[kGroupMax];
+  CpItem it[kGroupMax];
+  GemmPairItem gm[kGroupMax];
+  double *P[kGroupMax], *T[kGroupMax], *Pn[kGroupMax], *Tn[kGroupMax];
+  memset(rs, 0, sizeof(rs));
+  memset(it, 0, sizeof(it));
+  bool any = false;
+  for (int z = 0; z < count; ++z) {
+    const CpGroupMember& m = mem[z];
+    if (m.n <= 0) continue;
+    any = true;
+    P[z] = m.P;
+    T[z] = m.T;
+    Pn[z] = m.Pn;
+    Tn[z] = m.Tn;
+    rs[z].B2 = m.A;  // (launch_row_stats_group reads B2)
+    rs[z].n = m.n;
+    rs[z].ldn = m.ld;
+    rs[z].rowmax = m.rowmax;
+    rs[z].rowsum = m.deg;
+    it[z] = CpItem{m.A, m.deg, m.P, m.T, m.n, m.ld};
+  }
+  if (!any) return SC_OK;
+  auto product = [&](int z, const double* X, const double* Y, double* C, const double* add) {
+    gm[z] = GemmPairItem();
+    if (mem[z].n <= 0) return;
+    gm[z].A = X;
+    gm[z].B = Y;
+    gm[z].lda = gm[z].ldb = gm[z].ldc = mem[z].ld;
+    gm[z].C = C;
+    gm[z].n = mem[z].n;
+    gm[z].tilemap = mem[z].tilemap;
+    gm[z].addend = add;
+  };
+  launch_row_stats_group(s, rs, count);           // deg = rowsum
+  launch_cp_prepare_group(s, it, count, alpha);   // T = I + P
+  for (int j = 1; j < steps; ++j) {
+    for (int z = 0; z < count; ++z) product(z, P[z], nullptr, Pn[z], nullptr);  // Pn = P P
+    launch_gemm_nt_pair_group(s, gm, count, kEpiNone);
+    for (int z = 0; z < count; ++z) std::swap(P[z], Pn[z]);
+    for (int z = 0; z < count; ++z) product(z, T[z], P[z], Tn[z], T[z]);        // Tn = T + T P
+    launch_gemm_nt_pair_group(s, gm, count, kEpiAdd);
+    for (int z = 0; z < count; ++z) std::swap(T[z], Tn[z]);
+  }
+  // X = T Q^T into the idle partner of T,  T Q T = T X^T into the idle partner of P
+  for (int z = 0; z < count; ++z)
+    if (mem[z].n > 0) it[z] = CpItem{T[z], mem[z].band, Tn[z], nullptr, mem[z].n, mem[z].ld};
+  launch_cp_band_product_group(s, it, count);
+  for (int z = 0; z < count; ++z) product(z, T[z], Tn[z], Pn[z], nullptr);
+  launch_gemm_nt_pair_group(s, gm, count, kEpiNone);
+  for (int z = 0; z < count; ++z)
+    if (mem[z].n > 0) it[z] = CpItem{Pn[z], mem[z].A, mem[z].A, nullptr, mem[z].n, mem[z].ld};
+  launch_cp_adjust_group(s, it, count, (1.0 - alpha) * (1.0 - alpha));
+  return check_last(lead, "grouped constraint propagation launch");
 }
 
 // cfg's constraint operator on `a` with the resident constraint (dense or banded); out may
@@ -227,3 +306,78 @@ extern "C" int sc_stage_constraint_band(sc_handle h, const sc_config* cfg,
   return d2h_matrix(h, ptr<double>(h->A0), h->ldn, n, n, out);
 }
 
+// ConstraintPropagation of `count` affinities with banded constraints as ONE grouped chain,
+// through the launchers a constrained batch uses (tests).  Owns its device memory: per member the
+// affinity and the four work matrices at the arena's row pitch, all of it -- padding columns and
+// workspaces -- quiet NaNs before the inputs go in, so a read outside a matrix shows in the result.
+extern "C" int sc_stage_constraint_band_group(sc_handle h, const sc_config* cfg, int count,
+                                              const int32_t* ns, const double* const* affinities,
+                                              const double* const* bands, double* const* outs) {
+  if (!h) return SC_ERR_INVALID;
+  SC_TRY(validate_config(h, cfg));
+  if (count < 1 || count > kGroupMax || !ns || !affinities || !bands || !outs)
+    return fail(h, SC_ERR_INVALID, "a constraint group holds 1 .. 16 members");
+  for (int z = 0; z < count; ++z) {
+    if (ns[z] < 0) return fail(h, SC_ERR_INVALID, "n must not be negative (0: idle member)");
+    // (larger tile grids get their order uploaded per size: one per handle at a time)
+    if (gemm_tile_dim(ns[z]) > kTilemapTableMax)
+      return fail(h, SC_ERR_UNSUPPORTED, "a member of the constraint group is larger than 8192");
+    const bool idle = ns[z] == 0 || (!bands[z] && ns[z] > 1);
+    if (!idle && (!affinities[z] || !outs[z]))
+      return fail(h, SC_ERR_INVALID, "affinity must be (n, n) and the band hold n - 1 values");
+  }
+  int steps = 0;
+  SC_TRY(neumann_steps(h, cfg->constraint_alpha, &steps));  // (before anything is allocated)
+  SC_HIP(h, hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  struct Owned {  // freed however the function returns
+    std::vector<void*> p;
+    ~Owned() {
+      for (void* q : p) (void)hipFree(q);
+    }
+  } owned;
+  size_t largest = 16;
+  for (int z = 0; z < count; ++z) largest = std::max(largest, (size_t)ns[z] * matrix_ld(ns[z]));
+  // (one source for every fill, sized once: the copies out of it are in flight together)
+  const std::vector<double> nans(largest, std::numeric_limits<double>::quiet_NaN());
+  auto device_nan = [&](size_t doubles, double** out) -> int {
+    void* d = nullptr;
+    doubles = std::max<size_t>(doubles, 1);
+    SC_HIP(h, hipMalloc(&d, doubles * sizeof(double)));
+    owned.p.push_back(d);
+    SC_HIP(h, hipMemcpyAsync(d, nans.data(), doubles * sizeof(double), hipMemcpyHostToDevice, s));
+    *out = reinterpret_cast<double*>(d);
+    return SC_OK;
+  };
+  CpGroupMember mem[kGroupMax];
+  for (int z = 0; z < count; ++z) {
+    const int n = ns[z];
+    if (n == 0 || (!bands[z] && n > 1)) continue;  // idle
+    const int ld = matrix_ld(n);
+    CpGroupMember& m = mem[z];
+    double* band = nullptr;
+    SC_TRY(device_nan((size_t)n * ld, &m.A));
+    SC_TRY(device_nan((size_t)n * ld, &m.P));
+    SC_TRY(device_nan((size_t)n * ld, &m.T));
+    SC_TRY(device_nan((size_t)n * ld, &m.Pn));
+    SC_TRY(device_nan((size_t)n * ld, &m.Tn));
+    SC_TRY(device_nan(round_up(n, 16), &m.deg));
+    SC_TRY(device_nan(round_up(n, 16), &m.rowmax));
+    SC_TRY(device_nan(n - 1, &band));
+    SC_TRY(h2d_matrix(h, affinities[z], n, n, m.A, ld));  // (same stream: after the fill)
+    if (n > 1)
+      SC_HIP(h, hipMemcpyAsync(band, bands[z], (size_t)(n - 1) * sizeof(double),
+                               hipMemcpyHostToDevice, s));
+    SC_TRY(ensure_tilemap(h, n));
+    m.band = band;
+    m.tilemap = h->tilemap_cur;
+    m.n = n;
+    m.ld = ld;
+  }
+  SC_HIP(h, hipStreamSynchronize(s));  // (`nans` and the caller's bands are pageable)
+  SC_TRY(constraint_propagation_group(h, s, mem, count, cfg->constraint_alpha));
+  for (int z = 0; z < count; ++z)
+    if (mem[z].n > 0) SC_TRY(d2h_matrix(h, mem[z].A, mem[z].ld, mem[z].n, mem[z].n, outs[z]));
+  SC_HIP(h, hipStreamSynchronize(s));
+  return SC_OK;
+}

@@ -366,12 +366,26 @@ struct GemmGroup {
   GemmMember m[kGroupMax];
   int first[kGroupMax + 1];
 };
+// ... and of the two-operand form C_z = A_z B_z^T (+ addend_z), K = n (k_gemm_nt_pg): the
+// Neumann chain of a group's ConstraintPropagation (constraint_api.hip)
+struct GemmPairMember {
+  const double* A;
+  const double* B;
+  const double* addend;
+  double* C;
+  const int2* tilemap;
+  int lda, ldb, ldc, n, nt;
+};
+struct GemmPairGroup {
+  GemmPairMember m[kGroupMax];
+  int first[kGroupMax + 1];
+};
 
 // prologue / epilogue at the top issue priority (bit 0) and non-temporal C stores (bit 1):
 // 7.85 -> 7.78-7.83 ms on the Diffuse product (profiles/r02)
 constexpr int kEdgePrio = 3;
 
-template <int EPI, bool SYM, bool GROUPED>
+template <int EPI, bool SYM, bool GROUPED, class GRP>
 __device__ __forceinline__ void gemm_nt_body(const double* __restrict__ A,
                                                  int lda,
                                                  const double* __restrict__ B,
@@ -385,7 +399,7 @@ __device__ __forceinline__ void gemm_nt_body(const double* __restrict__ A,
                                                  int xcd_chunk, GemmStats stats,
                                                  int* __restrict__ queue,
                                                  int nunits, int persist,
-                                                 const GemmGroup* __restrict__ grp) {
+                                                 const GRP* __restrict__ grp) {
   // one 64 KB block: As[2] | Bs[2] in the K loop, reduction scratch + the transposed
   // staging of the mirror tile in the epilogue
   __shared__ __attribute__((aligned(16))) double smem[2 * BM * BK + 2 * BN * BK];
@@ -426,18 +440,27 @@ __device__ __forceinline__ void gemm_nt_body(const double* __restrict__ A,
     if (item_blk >= grp->first[kGroupMax]) continue;  // (the runs' ragged end)
     int z = 0;
     while (item_blk >= grp->first[z + 1]) ++z;  // (uniform: scalar loads from the kernel arguments)
-    const GemmMember& g = grp->m[z];
+    const auto& g = grp->m[z];
     item_blk -= grp->first[z];
-    A = B = g.A;
-    lda = ldb = g.lda;
     C = g.C;
     ldc = g.ldc;
     M = N = g.n;
-    K = g.K;
     ntiles_m = ntiles_n = g.nt;
     tilemap = g.tilemap;
-    stats.pmax = g.pmax;
-    stats.psum = g.psum;
+    if constexpr (std::is_same<GRP, GemmPairGroup>::value) {
+      A = g.A;
+      B = g.B;
+      lda = g.lda;
+      ldb = g.ldb;
+      K = g.n;
+      stats.addend = g.addend;
+    } else {
+      A = B = g.A;
+      lda = ldb = g.lda;
+      K = g.K;
+      stats.pmax = g.pmax;
+      stats.psum = g.psum;
+    }
   }
   if (queue != nullptr) {
     int* s_item = reinterpret_cast<int*>(smem);  // (one LDS object per kernel: no second array)
@@ -835,18 +858,26 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(const double* __restrict__ A
                                                  int xcd_chunk, GemmStats stats,
                                                  int* __restrict__ queue,
                                                  int nunits, int persist) {
-  gemm_nt_body<EPI, SYM, false>(A, lda, B, ldb, C, ldc, M, N, K, ntiles_m, ntiles_n, full_tiles,
-                                ksplit_tail, partial, probe_out, tilemap, xcd_chunk, stats,
-                                queue, nunits, persist, nullptr);
+  gemm_nt_body<EPI, SYM, false, GemmGroup>(A, lda, B, ldb, C, ldc, M, N, K, ntiles_m, ntiles_n,
+                                           full_tiles, ksplit_tail, partial, probe_out, tilemap,
+                                           xcd_chunk, stats, queue, nunits, persist, nullptr);
 }
 // every workgroup: one whole tile of one member (no queue, no split, no probe)
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void k_gemm_nt_g(const GemmGroup grp, int stats_mode,
                                                      int xcd_chunk) {
   GemmStats stats{nullptr, nullptr, stats_mode, nullptr};
-  gemm_nt_body<EPI, true, true>(nullptr, 0, nullptr, 0, nullptr, 0, 0, 0, 0, 0, 0, 0x7fffffff, 1,
-                                nullptr, nullptr, nullptr, xcd_chunk, stats, nullptr,
-                                0, 0, &grp);
+  gemm_nt_body<EPI, true, true, GemmGroup>(nullptr, 0, nullptr, 0, nullptr, 0, 0, 0, 0, 0, 0,
+                                           0x7fffffff, 1, nullptr, nullptr, nullptr, xcd_chunk,
+                                           stats, nullptr, 0, 0, &grp);
+}
+// the same for two operands per member (EPI: kEpiNone or kEpiAdd; no row statistics)
+template <int EPI>
+__global__ __launch_bounds__(256, 2) void k_gemm_nt_pg(const GemmPairGroup grp, int xcd_chunk) {
+  GemmStats stats{nullptr, nullptr, 0, nullptr};
+  gemm_nt_body<EPI, true, true, GemmPairGroup>(nullptr, 0, nullptr, 0, nullptr, 0, 0, 0, 0, 0, 0,
+                                               0x7fffffff, 1, nullptr, nullptr, nullptr,
+                                               xcd_chunk, stats, nullptr, 0, 0, &grp);
 }
 
 // rowmax / rowsum of every member from its per-tile partials (k_gemm_stats_reduce, grouped)
@@ -1185,6 +1216,34 @@ void launch_gemm_nt_group(hipStream_t s, const GemmGroupItem* items, int count, 
                        2 * kStatRows * (size_t)(std::min((nmax + BM - 1) / BM, kStatMaxTiles) + 1) *
                            sizeof(double),
                        s, red, stats_mode);
+}
+
+// C_z = A_z B_z^T (+ addend_z) of every member in ONE launch, for commuting symmetric operands:
+// the upper-triangle tiles of all members, each with its whole K = n, the mirror tile written
+// transposed -- what launch_gemm_nt(symmetric) computes for one member, without the split over K
+// a single short product takes.  items[z].n = 0: idle member.
+void launch_gemm_nt_pair_group(hipStream_t s, const GemmPairItem* items, int count, int epilogue) {
+  GemmPairGroup grp;
+  memset(&grp, 0, sizeof(grp));
+  int total = 0;
+  for (int z = 0; z < kGroupMax; ++z) {
+    grp.first[z] = total;
+    if (z >= count || items[z].n <= 0) continue;
+    const GemmPairItem& it = items[z];
+    const int nt = (it.n + BM - 1) / BM;
+    const bool self = it.B == nullptr;
+    grp.m[z] = GemmPairMember{it.A, self ? it.A : it.B, it.addend, it.C, it.tilemap,
+                              it.lda, self ? it.lda : it.ldb, it.ldc, it.n, nt};
+    total += nt * (nt + 1) / 2;
+  }
+  grp.first[kGroupMax] = total;
+  if (total == 0) return;
+  const int xcd_chunk = (total + 7) / 8;
+  const int grid = 8 * xcd_chunk;
+  if (epilogue == kEpiAdd)
+    hipLaunchKernelGGL((k_gemm_nt_pg<kEpiAdd>), dim3(grid), dim3(256), 0, s, grp, xcd_chunk);
+  else
+    hipLaunchKernelGGL((k_gemm_nt_pg<kEpiNone>), dim3(grid), dim3(256), 0, s, grp, xcd_chunk);
 }
 
 }  // namespace sc

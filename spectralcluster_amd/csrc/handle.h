@@ -444,5 +444,22 @@ int device_is_symmetric(sc_handle h, const double* m, int n, int ld, bool* out);
 int adjust_affinity(sc_handle h, const sc_config* cfg, const double* a, bool sym_a, double* out,
                     int n, int ld);
 bool constraint_active(sc_handle h, const sc_config* cfg, bool before);
+// One member of a grouped ConstraintPropagation chain (constraint_propagation_group): a symmetric
+// affinity A (n x ld, adjusted in place), four n x ld work matrices, two n-vectors, the band of
+// n - 1 values and the tile order of the symmetric GEMM for n, all on the device.  n = 0: idle.
+struct CpGroupMember {
+  int n = 0, ld = 0;
+  double* A = nullptr;
+  double *P = nullptr, *T = nullptr, *Pn = nullptr, *Tn = nullptr;
+  double *deg = nullptr, *rowmax = nullptr;
+  const double* band = nullptr;
+  const int2* tilemap = nullptr;
+};
+int constraint_propagation_group(sc_handle lead, hipStream_t s, const CpGroupMember* mem,
+                                 int count, double alpha);
+// the body of sc_predict_batch_constrained (batch_group.hip)
+int predict_batch_constrained_impl(sc_handle h, const sc_array* xs, const double* const* bands,
+                                   const int* ns, int d, int count, const sc_config* cfg,
+                                   int64_t* const* labels, sc_diag* diags, int group);
 
 #endif  // SPECTRALCLUSTER_AMD_HANDLE_H_

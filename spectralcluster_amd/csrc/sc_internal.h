@@ -88,6 +88,23 @@ struct GemmGroupItem {
 };
 void launch_gemm_nt_group(hipStream_t s, const GemmGroupItem* items, int count, int epilogue,
                           int stats_mode);
+// One member of a grouped symmetric two-operand product C = A B^T (+ addend), K = n, for
+// commuting symmetric A and B (launch_gemm_nt_pair_group); n = 0: idle.  B == nullptr: B = A.
+// addend (kEpiAdd): pitch ldc, must not alias C.
+struct GemmPairItem {
+  const double* A = nullptr;
+  int lda = 0;
+  const double* B = nullptr;
+  int ldb = 0;
+  double* C = nullptr;
+  int ldc = 0;
+  int n = 0;
+  const int2* tilemap = nullptr;
+  const double* addend = nullptr;
+};
+// epilogue: kEpiNone or kEpiAdd.  Upper-triangle tiles of all members in one launch, whole K per
+// tile, the mirror tile written transposed.
+void launch_gemm_nt_pair_group(hipStream_t s, const GemmPairItem* items, int count, int epilogue);
 // patch-ordered (ti, tj) list of the upper triangle, for `tilemap` (symmetric launches)
 void gemm_build_sym_tilemap(int nt, std::vector<int2>* out);
 int gemm_tile_dim(int n);
@@ -312,6 +329,21 @@ struct FrontItem {
 };
 void launch_front_begin_group(hipStream_t s, const FrontItem* items, int count,
                               bool normalize_rows);
+// One member of a grouped ConstraintPropagation pass (constraint.hip); which matrix / vector is
+// which is said at each launcher.  n = 0: idle.
+struct CpItem {
+  const double* src;  // n x ld
+  const double* vec;
+  double* dst;        // n x ld
+  double* dst2;       // n x ld (prepare only)
+  int n, ld;
+};
+// launch_cp_prepare per member: src = A, vec = its row sums, dst = P, dst2 = T0 = I + P
+void launch_cp_prepare_group(hipStream_t s, const CpItem* items, int count, double alpha);
+// launch_cp_band_product per member: src = T, vec = band (n - 1 values), dst = X
+void launch_cp_band_product_group(hipStream_t s, const CpItem* items, int count);
+// launch_cp_adjust per member: src = T Q T, vec = A (n x ld), dst = out (may be A)
+void launch_cp_adjust_group(hipStream_t s, const CpItem* items, int count, double scale);
 void launch_cut_percentile_group(hipStream_t s, const FrontItem* items, int count, int zero_diag);
 void launch_row_stats_group(hipStream_t s, const FrontItem* items, int count);
 bool blur_group_supported(int n_min, int radius);

@@ -415,24 +415,45 @@ class SpectralClusterer:
     before it -- and the streams of the batch read the tensors from then on; they may be
     overwritten or freed when the call has returned.
 
-    `constraint_matrices`: one `ConstraintMatrix` / ndarray / None per utterance.  With it (and
-    `constraint_options`) the batch runs as per-utterance `predict(u, c)` calls; without it a
-    batch carries no constraints.
+    `constraint_matrices`: one `ConstraintMatrix` / ndarray / None per utterance, used when
+    `constraint_options` is set (without it a batch carries no constraints).  When every entry
+    is a `ConstraintMatrix` or None, the batch is the grouped form (`group` > 1, no `streams`),
+    k-means is the cosine one and nothing above sends it through predict(), it is ONE `sc_predict_batch_constrained` call:
+    the same routes as an unconstrained batch, each utterance's band (`ConstraintMatrix.band()`,
+    n - 1 values) resident in its member arena.  ConstraintPropagation before refinement then runs
+    as one chain of grouped launches per group of up to 16 utterances; AffinityIntegration and
+    the after-refinement operators run per utterance inside the group's front; an utterance
+    whose entry is None is clustered as in a batch without constraints.  A `ConstraintMatrix`
+    whose length is not its utterance's raises the ValueError of predict() before anything is
+    launched.  Anything else -- a dense ndarray among the entries, AutoTune (the Turn-to-Diarize
+    preset), group=1, `streams` -- runs as per-utterance `predict(u, c)` calls (routes all 0).
     """
+    library_batch = not (
+        self.autotune is not None or self.max_spectral_size is not None or
+        self.min_clusters == 1 or self.fallback_options.spectral_min_embeddings > 1 or
+        self.affinity_function is not utils.compute_affinity_matrix or
+        self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans)
+    banded = None  # the ConstraintMatrix (or None) of every utterance of a constrained batch
     if constraint_matrices is not None:
       if len(constraint_matrices) != len(utterances):
         raise ValueError("constraint_matrices must be as long as the batch")
       if self.constraint_options is not None:
-        self.last_batch_routes = [_lib.BATCH_ROUTE_SINGLE] * len(utterances)
-        return [self.predict(u, c) for u, c in zip(utterances, constraint_matrices)]
+        try:  # (a metric that is not on the device raises in predict(), as it does today)
+          cosine = _lib.kmeans_metric_code(self.custom_dist) == _lib.KMEANS_METRICS["cosine"]
+        except (ValueError, _lib.UnsupportedOnDeviceError):
+          cosine = False
+        if not (library_batch and cosine and streams is None and
+                (group is None or int(group) > 1) and
+                all(c is None or isinstance(c, constraint_lib.ConstraintMatrix)
+                    for c in constraint_matrices)):
+          self.last_batch_routes = [_lib.BATCH_ROUTE_SINGLE] * len(utterances)
+          return [self.predict(u, c) for u, c in zip(utterances, constraint_matrices)]
+        banded = list(constraint_matrices)
     if group is None:
       group = 16 if streams is None else 0
     if streams is None:
       streams = 1
-    if (self.autotune is not None or self.max_spectral_size is not None or
-        self.min_clusters == 1 or self.fallback_options.spectral_min_embeddings > 1 or
-        self.affinity_function is not utils.compute_affinity_matrix or
-        self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans):
+    if not library_batch:
       # anything sc_predict_batch does not cover (user-supplied affinity / clustering
       # functions, AutoTune, size reduction, fallback decisions) goes through predict().
       # A batch never carries a constraint matrix -- same as predict(u) without one.
@@ -454,12 +475,31 @@ class SpectralClusterer:
       if any(src.shape[1] != d for src in sources):
         raise ValueError("all utterances must be (n_i, d) with the same d")
       count = len(sources)
+      bands = []
+      if banded is not None:
+        for src, cm in zip(sources, banded):
+          if cm is None:
+            bands.append(None)
+            continue
+          n = src.shape[0]
+          # (predict()'s check and message: _set_constraint)
+          self.constraint_options.constraint_operator.check_input(
+              np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)), cm)
+          band = np.zeros(max(n - 1, 1), dtype=np.float64)  # (n = 1: no values, a valid pointer)
+          band[:n - 1] = cm.band()
+          bands.append(band)
       labels = [np.empty(src.shape[0], dtype=np.int64) for src in sources]
       handle = self._handle()
       handle.check(handle.lib.sc_clear_constraint(handle.raw))  # a batch carries none
       lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
       diags = (_lib.ScDiag * count)()
-      if all(src.is_host_f64 for src in sources):
+      if banded is not None:
+        arrays = (_lib.ScArray * count)(*[src.array for src in sources])
+        bp = (ctypes.POINTER(ctypes.c_double) * count)(
+            *[None if b is None else _lib.as_double_p(b) for b in bands])
+        handle.check(handle.lib.sc_predict_batch_constrained(
+            handle.raw, arrays, bp, count, self.build_config(), lp, diags, int(group)), TypeError)
+      elif all(src.is_host_f64 for src in sources):
         # compact float64 host rows: the `double*` forms (sc_predict_batch_arrays runs the same
         # code on the descriptors of exactly these arrays)
         xp = (ctypes.POINTER(ctypes.c_double) * count)(
