@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 8
+#define SC_ABI_VERSION 9
 #define SC_MAX_OPS 16
 #define SC_MAX_BLUR_RADIUS 32
 #define SC_MAX_EIG 128 /* max eigenvalues reported in sc_diag */
@@ -587,6 +587,68 @@ int sc_stage_block_operator(sc_handle h, int count, const int32_t* ns,
  * path) or when no solve has run since the handle was given a new problem. */
 int sc_stage_krylov_state(sc_handle h, int32_t* info, double* q, double* t, double* g, double* c,
                           double* p);
+/* Test entry of the fused refinement front (addition of ABI 9; no reference equivalent): what
+ * the stages between the affinity and the eigensolver leave behind, on each of the three drivers
+ * that run them.  It runs the product's own front -- the same functions, the same launch
+ * sequence, every routing decision as a full call takes it -- stops before the eigensolver and
+ * copies out, per member, into outs[z] (any pointer may be NULL):
+ *   a0 (n, n)        the affinity the route computed (or was given)
+ *   cropval (n)      CropDiagonal's value vector, from the affinity GEMM's epilogue or from
+ *                    k_crop_value (not written when the op ran unfused or is not in the sequence)
+ *   cut (n)          the cut vector of RowWiseThreshold
+ *   a (n, n)         the refined matrix before Diffuse (thresholded and symmetrised)
+ *   s (n, n)         Diffuse(a) = a a^T, where the route formed it
+ *   rowmax, rowsum   the row statistics the scaling kernel read
+ *   c, p, t (n)      the scaling vectors of Op = diag(p) + diag(c) S diag(c)
+ *   info             SC_FRONT_INFO_* below
+ * route:
+ *   SC_FRONT_ROUTE_SINGLE   count = 1.  xs[0] (ns[0], d): sc_set_embeddings + sc_compute_affinity
+ *                           + the front of sc_eig_ncluster.  xs == NULL: `affinity` (ns[0], ns[0])
+ *                           through sc_set_affinity instead (no epilogue crop value then).
+ *   SC_FRONT_ROUTE_GROUPED  count 1 .. 16 embeddings matrices xs[z] (ns[z], d): the grouped front
+ *                           of sc_predict_batch_grouped, one call, members in the order given.
+ *   SC_FRONT_ROUTE_SWEEP    one problem xs[0] (ns[0], d) and count (2 .. 16) values p_values[z] of
+ *                           p_percentile: the front of one round of sc_eig_ncluster_sweep; outs[z]
+ *                           belongs to p_values[z] (a0 and cropval are the shared ones).
+ * A configuration the route's grouped code does not cover (a group member below n = 256 or a
+ * sequence other than ICASSP2018's; a sweep the product would evaluate one by one) returns
+ * SC_ERR_UNSUPPORTED: the entry never takes another path quietly. */
+enum { SC_FRONT_ROUTE_SINGLE = 0, SC_FRONT_ROUTE_GROUPED = 1, SC_FRONT_ROUTE_SWEEP = 2 };
+enum {
+  SC_FRONT_INFO_DIFFUSE_PATH = 0,   /* SC_DIFFUSE_PATH_NONE / _EXPLICIT / _FREE */
+  SC_FRONT_INFO_SYMMETRIC = 1,
+  SC_FRONT_INFO_FOLDED_ROWNORM = 2, /* RowWiseNormalize folded into the scaling vectors */
+  SC_FRONT_INFO_FREE_OP = 3,        /* the solver would apply `a` twice */
+  SC_FRONT_INFO_DIGITS_FUSED = 4,   /* the threshold pass wrote the 8-bit digits */
+  SC_FRONT_INFO_BLUR_KERNEL = 5,    /* 0 generic, 1 tile, 2 streaming; -1 no blur ran */
+  SC_FRONT_INFO_BLUR_ROWS = 6,      /* rows per wave of the streaming kernel, else 0 */
+  SC_FRONT_INFO_FREE_CANDIDATES = 7,
+  SC_FRONT_INFO_FREE_OVERFLOW_ROWS = 8, /* rows whose statistics the solver's first
+                                           synchronisation would still correct */
+  SC_FRONT_INFO_FREE_FORMS_S = 9,   /* more of them than the exact-row route takes: the solver
+                                       would form S after all */
+  SC_FRONT_INFO_CROP_SOURCE = 10,   /* 0 no value vector, 1 GEMM epilogue, 2 k_crop_value */
+  SC_FRONT_INFO_CUT_KERNEL = 11,    /* 0 none, 1 k_cut_from_partials, 2 k_cut_from_rows,
+                                       3 k_row_percentile_cut */
+  SC_FRONT_INFO_WRITTEN = 12,       /* bit i: the i-th pointer of sc_front_out was filled */
+  SC_FRONT_INFO_COUNT = 16
+};
+typedef struct sc_front_out {
+  double* a0;
+  double* cropval;
+  double* cut;
+  double* a;
+  double* s;
+  double* rowmax;
+  double* rowsum;
+  double* c;
+  double* p;
+  double* t;
+  int32_t info[SC_FRONT_INFO_COUNT];
+} sc_front_out;
+int sc_stage_front(sc_handle h, int route, const sc_config* cfg, int count, const int32_t* ns,
+                   int d, const double* const* xs, const double* affinity,
+                   const double* p_values, sc_front_out* outs);
 /* laplacian.compute_laplacian (laplacian.py:24-60) */
 int sc_stage_laplacian(sc_handle h, int laplacian_type, const double* in, int n,
                        double* out);

@@ -50,7 +50,7 @@ class EigenSolverNotConverged(RuntimeError):
   """The block-Lanczos eigensolver did not reach its tolerance."""
 
 
-SC_ABI_VERSION = 8
+SC_ABI_VERSION = 9
 
 
 class ScConfig(ctypes.Structure):
@@ -139,6 +139,24 @@ class ScArray(ctypes.Structure):
 
 
 _c_double_p = ctypes.POINTER(ctypes.c_double)
+
+
+# sc_stage_front: route, and the slots of sc_front_out.info
+SC_FRONT_ROUTE_SINGLE, SC_FRONT_ROUTE_GROUPED, SC_FRONT_ROUTE_SWEEP = range(3)
+SC_FRONT_INFO_COUNT = 16
+FRONT_INFO_NAMES = ("diffuse_path", "symmetric", "folded_rownorm", "free_op", "digits_fused",
+                    "blur_kernel", "blur_rows", "free_candidates", "free_overflow_rows",
+                    "free_forms_s", "crop_source", "cut_kernel", "written")
+FRONT_OUTPUTS = ("a0", "cropval", "cut", "a", "s", "rowmax", "rowsum", "c", "p", "t")
+
+
+class ScFrontOut(ctypes.Structure):
+  """Mirror of `sc_front_out`: where sc_stage_front writes one member's front (NULL: not
+  wanted) and what it reports about the branches taken."""
+  _fields_ = [(name, _c_double_p) for name in FRONT_OUTPUTS] + [
+      ("info", ctypes.c_int32 * SC_FRONT_INFO_COUNT)]
+
+
 _c_int64_p = ctypes.POINTER(ctypes.c_int64)
 _c_int_p = ctypes.POINTER(ctypes.c_int)
 _handle_t = ctypes.c_void_p
@@ -176,6 +194,10 @@ PROTOTYPES = {
     "sc_stage_krylov_state": (ctypes.c_int, [_handle_t, ctypes.POINTER(ctypes.c_int32),
                                              _c_double_p, _c_double_p, _c_double_p, _c_double_p,
                                              _c_double_p]),
+    "sc_stage_front": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.POINTER(ScConfig),
+                                      ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
+                                      ctypes.POINTER(_c_double_p), _c_double_p, _c_double_p,
+                                      ctypes.POINTER(ScFrontOut)]),
     "sc_config_default": (ctypes.c_int, [ctypes.POINTER(ScConfig)]),
     "sc_gaussian_weights": (ctypes.c_int, [ctypes.c_double,
                                            ctypes.POINTER(ctypes.c_int32),

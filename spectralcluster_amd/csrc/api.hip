@@ -535,7 +535,9 @@ static int run_refine_op(sc_handle h, int op, const sc_config* cfg, const double
         launch_gaussian_blur_any_radius(s, in, ptr<double>(h->blur_tmp), out, n, ld,
                                         cfg->blur_radius, ptr<double>(h->blurw));
       } else {
-        launch_gaussian_blur(s, in, out, n, ld, cfg->blur_radius, ptr<double>(h->blurw));
+        // (launch_gaussian_blur, with the kernel it takes reported)
+        launch_gaussian_blur_fused(s, in, out, n, ld, cfg->blur_radius, ptr<double>(h->blurw),
+                                   nullptr, nullptr, &h->last_blur);
       }
       break;
     case SC_OP_ROW_WISE_THRESHOLD:
@@ -673,7 +675,8 @@ static void resolve_stage_times(sc_handle h, sc_diag* diag) {
 // `defer_timing`: return without waiting for the stream (the caller enqueues k-means right
 // behind the Ritz vectors and resolves the stage timers after its own synchronisation)
 int eig_ncluster_impl(sc_handle h, const sc_config* cfg, sc_diag* diag, FrontResult* front_only,
-                      const FrontResult* resume, bool defer_timing) {
+                      const FrontResult* resume, bool defer_timing,
+                      FrontResult* stop_before_solver) {
   const int n = h->n, ld = h->ldn;
   hipStream_t s = h->stream;
   const double* cur = ptr<double>(h->A0);
@@ -700,6 +703,8 @@ int eig_ncluster_impl(sc_handle h, const sc_config* cfg, sc_diag* diag, FrontRes
   const double* pending_diag = nullptr;
   bool have_partials = false;
   bool have_row_stats = false;
+  int crop_source = 0, cut_kernel = 0;  // (what sc_stage_front reports)
+  h->last_blur = BlurLaunch();
   if (resume) {
     cur = resume->matrix;
     symmetric = resume->symmetric;
@@ -727,9 +732,11 @@ int eig_ncluster_impl(sc_handle h, const sc_config* cfg, sc_diag* diag, FrontRes
     if (op == SC_OP_CROP_DIAGONAL && next == SC_OP_GAUSSIAN_BLUR && blur_fast) {
       if (cur == ptr<double>(h->A0) && h->have_cropval) {
         pending_diag = ptr<double>(h->cropval);
+        crop_source = 1;
       } else {
         launch_crop_value(s, cur, n, ld, ptr<double>(h->dvec));
         pending_diag = ptr<double>(h->dvec);
+        crop_source = 2;
       }
       have_partials = false;
       continue;  // symmetry unchanged; the blur applies the new diagonal on load
@@ -746,7 +753,8 @@ int eig_ncluster_impl(sc_handle h, const sc_config* cfg, sc_diag* diag, FrontRes
       if (fine) ev_rec(h, &eb0);
       have_partials = launch_gaussian_blur_fused(s, cur, out, n, ld, cfg->blur_radius,
                                                  ptr<double>(h->blurw), pending_diag,
-                                                 want ? ptr<double>(h->rmpart) : nullptr);
+                                                 want ? ptr<double>(h->rmpart) : nullptr,
+                                                 &h->last_blur);
       if (fine) ev_rec(h, &eb1);
       pending_diag = nullptr;
       SC_TRY(check_last(h, "blur launch"));
@@ -761,6 +769,8 @@ int eig_ncluster_impl(sc_handle h, const sc_config* cfg, sc_diag* diag, FrontRes
       else
         launch_cut_from_rows(s, cur, n, ld, cfg->p_percentile, ptr<double>(h->cut),
                              cfg->preserve_diagonal);
+      cut_kernel = cfg->threshold_type == SC_THRESHOLD_PERCENTILE
+                       ? 3 : (have_partials && partials_usable ? 1 : 2);
       // the matrix-free Diffuse quantises this pass's result: when it is non-negative by
       // construction (cosine affinity, no constraint applied to it) and thresholded by RowMax
       // with a multiplier in [0, 1], its maximum is known from the cut vector ...
@@ -933,6 +943,14 @@ int eig_ncluster_impl(sc_handle h, const sc_config* cfg, sc_diag* diag, FrontRes
   op.laplacian_type = cfg->laplacian_type;
   op.chain_flags_cleared = flags_by_kernel;  // (never on a resume: the group solve ran the chain)
   op.skip_fused = resume && resume->skip_fused;
+  op.digits_fused = free_path && digits_of == cur;
+  op.diffuse_explicit = !free_path && n_diffuse > 0;
+  op.crop_source = crop_source;
+  op.cut_kernel = cut_kernel;
+  if (stop_before_solver) {
+    *stop_before_solver = op;
+    return SC_OK;
+  }
   if (front_only) {
     *front_only = op;
     return SC_OK;

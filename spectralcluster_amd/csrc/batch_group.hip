@@ -68,6 +68,15 @@ int group_slot(sc_handle lead, int z, sc_handle* out,
   return SC_OK;
 }
 
+// A bank's stream and hand-over event, where the batch has not placed them on queues of their own
+int ensure_bank_stream(sc_handle h, int b) {
+  if (!h->gbank_stream[b])
+    SC_HIP(h, hipStreamCreateWithFlags(&h->gbank_stream[b], hipStreamNonBlocking));
+  if (!h->gbank_ev[b])
+    SC_HIP(h, hipEventCreateWithFlags(&h->gbank_ev[b], hipEventDisableTiming));
+  return SC_OK;
+}
+
 int ensure_seed_table(sc_handle lead) {
   if (lead->gkrnd_ready) return SC_OK;
   std::vector<double> table((size_t)33 * kRndStride, 0.0), rnd;
@@ -315,6 +324,7 @@ int enqueue_front_grouped(sc_handle lead, const sc_array* xs, const int* ns, int
     aff[z].tilemap = h->tilemap_cur;
     aff[z].partial_max = ptr<double>(h->statp);
     aff[z].rowmax = ptr<double>(h->cropval);
+    m.front.crop_source = 1;  // (the affinity epilogue writes the value the blur reads)
     dif[z] = GemmGroupItem();
     dif[z].A = f.B2;
     dif[z].lda = h->ldn;
@@ -352,7 +362,8 @@ int enqueue_front_grouped(sc_handle lead, const sc_array* xs, const int* ns, int
   }
   launch_front_begin_group(s, fi, count, true);
   launch_gemm_nt_group(s, aff, count, kEpiAffinity, 2);
-  launch_gaussian_blur_group(s, fi, count, cfg->blur_radius, ptr<double>(lead->blurw));
+  launch_gaussian_blur_group(s, fi, count, cfg->blur_radius, ptr<double>(lead->blurw),
+                             &lead->last_blur);
   // rowmax / rowsum of S = A A^T without forming it, for the members that take that route (the
   // cut vector bounds max|a|: the grouped front is the ICASSP2018 sequence on a cosine affinity):
   // begin, scan and statistics are one launch each for all of them, the digit products one
@@ -386,10 +397,14 @@ int enqueue_front_grouped(sc_handle lead, const sc_array* xs, const int* ns, int
     launch_threshold_symmetrize_group(s, fi, count, cfg->p_percentile, cfg->soft_multiplier,
                                       cfg->binarize, cfg->symmetrize_type, cfg->preserve_diagonal,
                                       true, digits);
+    for (int z = 0; z < count; ++z) mb[z].front.digits_fused = digits[z].Q != nullptr;
   } else {
+    // (the cuts come from the blur's partials inside this launcher)
     launch_threshold_symmetrize_group(s, fi, count, cfg->p_percentile, cfg->soft_multiplier,
                                       cfg->binarize, cfg->symmetrize_type, cfg->preserve_diagonal);
   }
+  for (int z = 0; z < count; ++z) mb[z].front.cut_kernel = 1;  // k_cut_from_partials_g either way
+  for (int z = 0; z < count; ++z) mb[z].front.diffuse_explicit = dif[z].n > 0;
   launch_gemm_nt_group(s, dif, count, kEpiNone, 1);
   if (nf > 0) {
     SC_TRY(free_group_digits(fh, fitems, nf, s));
@@ -699,12 +714,7 @@ int run_short_route(sc_handle h, const sc_array* xs, const int* ns, int d,
       hz->have_constraint = false;
     }
   if (bands && bands->chain)  // the grouped chain of a wave runs on a stream of the wave's bank
-    for (int b = 0; b < banks; ++b) {
-      if (!h->gbank_stream[b])
-        SC_HIP(h, hipStreamCreateWithFlags(&h->gbank_stream[b], hipStreamNonBlocking));
-      if (!h->gbank_ev[b])
-        SC_HIP(h, hipEventCreateWithFlags(&h->gbank_ev[b], hipEventDisableTiming));
-    }
+    for (int b = 0; b < banks; ++b) SC_TRY(ensure_bank_stream(h, b));
   std::vector<Member> mbs[kGroupBanks];
   std::vector<GroupEigMember> em(kShortWidth);
   for (int b = 0; b < banks; ++b) mbs[b].resize(kShortWidth);
@@ -799,6 +809,34 @@ int independent_streams(sc_handle h, std::vector<hipStream_t> have, hipStream_t*
   return rc;
 }
 
+// The member arenas of one bank, before its first front.  Groups of equal cost put a member of
+// any size at any position z (five utterances of n ~ 3000 in one batch's first group, seven of
+// n ~ 2800 in the next batch's), so every position of a bank that is used at all is reserved for
+// the largest member: an arena that has to grow is a hipFree + hipMalloc in the middle of a
+// batch (the 8-GPU shares of config 5 ran 3x slower on arenas sized position by position).
+int reserve_bank_arenas(sc_handle h, const sc_config* cfg, const EigRequest& rq, int bank,
+                        int positions, int largest, int d, const Bands* bands) {
+  for (int z = 0; z < positions; ++z) {
+    sc_handle hz = nullptr;
+    SC_TRY(group_slot(h, bank * kGroupMax + z, &hz));  // (a stride that does not move with the batch)
+    int rc = sc_reserve(hz, largest, d);
+    // (... and the buffers of the matrix-free Diffuse, which a member arena otherwise grows the
+    //  first time a member of n >= 1536 lands in it)
+    if (rc == SC_OK && free_diffuse_wanted(hz, cfg, largest, rq, true)) rc = ensure_free(hz, largest);
+    if (rc == SC_OK) rc = reserve_constraint(hz, bands, largest);
+    if (rc != SC_OK) return fail(h, rc, hz->err);
+    hz->have_constraint = false;
+  }
+  return SC_OK;
+}
+// The blur weights of the grouped front, resident in the lead before a bank stream reads them.
+int upload_group_blur_weights(sc_handle h, const sc_config* cfg) {
+  SC_TRY(grow(h, h->blurw, (2 * SC_MAX_BLUR_RADIUS + 1) * sizeof(double)));
+  SC_TRY(upload_blur_weights(h, cfg));
+  SC_HIP(h, hipStreamSynchronize(h->stream));  // the bank streams read them
+  return SC_OK;
+}
+
 // One lane of the grouped batch: the groups `mine` (indices into the size-sorted list, `width`
 // members each) on the lead's streams and member arenas.
 int run_group_lane(sc_handle h, const sc_array* xs, const int* ns, int d,
@@ -828,11 +866,7 @@ int run_group_lane(sc_handle h, const sc_array* xs, const int* ns, int d,
   // (group g of the size-sorted list = [gstart[g], gstart[g + 1]); `width` = the largest group)
   auto group_count = [&](int j) { return gstart[mine[j] + 1] - gstart[mine[j]]; };
   auto group_members = [&](int j) { return grouped.data() + gstart[mine[j]]; };
-  // arenas once.  Groups of equal cost put a member of any size at any position z (five
-  // utterances of n ~ 3000 in one batch's first group, seven of n ~ 2800 in the next batch's), so
-  // every position of a bank that is used at all is reserved for the largest member of the
-  // lane: an arena that has to grow is a hipFree + hipMalloc in the middle of a batch (the 8-GPU
-  // shares of config 5 ran 3x slower on arenas sized position by position).
+  // arenas once (reserve_bank_arenas), every position for the largest member of the lane
   // (the largest grouped member of the BATCH, not of this lane's groups: which lane draws the
   //  large groups changes from batch to batch too)
   const int lane_largest = ns[grouped[0]];
@@ -840,29 +874,14 @@ int run_group_lane(sc_handle h, const sc_array* xs, const int* ns, int d,
   //  batch -- or the next rank's share -- cuts its list elsewhere, and a position that does not
   //  exist yet is an sc_create: streams, events, pinned buffers, milliseconds)
   for (int b = 0; b < std::min(banks, ngroups); ++b)
-    for (int z = 0; z < std::max(width, group_limit); ++z) {
-      const int largest = lane_largest;
-      sc_handle hz = nullptr;
-      SC_TRY(group_slot(h, b * kGroupMax + z, &hz));  // (a stride that does not move with the batch)
-      int rc = sc_reserve(hz, largest, d);
-      // (... and the buffers of the matrix-free Diffuse, which a member arena otherwise grows the
-      //  first time a member of n >= 1536 lands in it)
-      if (rc == SC_OK && free_diffuse_wanted(hz, cfg, largest, rq, true)) rc = ensure_free(hz, largest);
-      if (rc == SC_OK) rc = reserve_constraint(hz, bands, largest);
-      if (rc != SC_OK) return fail(h, rc, hz->err);
-      hz->have_constraint = false;
-    }
+    SC_TRY(reserve_bank_arenas(h, cfg, rq, b, std::max(width, group_limit), lane_largest, d, bands));
   Member mbs[kGroupBanks][kGroupMax];
   int front_bank[kGroupBanks];
   const bool trace = sw::group_trace();
   // (a constrained batch never takes the grouped front: its crop value comes out of the affinity
   //  epilogue, which an adjusted affinity invalidates)
   const bool covers = grouped_front_covers(cfg) && !bands;
-  if (covers) {
-    SC_TRY(grow(h, h->blurw, (2 * SC_MAX_BLUR_RADIUS + 1) * sizeof(double)));
-    SC_TRY(upload_blur_weights(h, cfg));
-    SC_HIP(h, hipStreamSynchronize(h->stream));  // the bank streams read them
-  }
+  if (covers) SC_TRY(upload_group_blur_weights(h, cfg));
   auto front = [&](int j) -> int {
     const int b = j % banks, cnt = group_count(j);
     const int* idx = group_members(j);
@@ -1227,6 +1246,242 @@ int predict_batch_core(sc_handle h, const sc_array* xs, const int* ns, int d, in
 }
 }  // namespace
 
+namespace {
+// What sc_eig_ncluster_sweep decides before its rounds: which of the two sequences it groups,
+// whether the level runs as a group at all, and the route of its Diffuse.
+struct SweepPlan {
+  bool icassp = false, thr_sym_only = false, grouped = false;
+  bool free_route = false, amax_from_cut = false;
+};
+SweepPlan sweep_plan(sc_handle h, const sc_config* cfg, int count, const EigRequest& rq) {
+  const int n = h->n;
+  SweepPlan plan;
+  // Two sequences are swept as groups: the ICASSP2018 one, and [RowWiseThreshold, Symmetrize]
+  // alone -- the Turn-to-Diarize refinement (reference configs.py:49-59: Percentile cut,
+  // binarisation, preserved diagonal, Average), whose values are the thresholded affinity
+  // itself: no blur to share, no Diffuse, the lockstep solver works on the symmetrised matrix.
+  plan.icassp = grouped_front_covers(cfg);
+  plan.thr_sym_only = cfg->n_ops == 2 && cfg->ops[0] == SC_OP_ROW_WISE_THRESHOLD &&
+                      cfg->ops[1] == SC_OP_SYMMETRIZE;
+  plan.grouped = count > 1 && (plan.icassp || plan.thr_sym_only) && h->affinity_symmetric &&
+                 !constraint_active(h, cfg, false) &&
+                 (!plan.icassp || blur_group_supported(n, cfg->blur_radius)) &&
+                 sym_group_eligible(n, rq, true) && !sw::sweep_one_by_one();
+  // Matrix-free Diffuse (free_api.hip): a member then holds the thresholded matrix, its digits
+  // and the fp32 tiles of their product instead of S, and the lockstep solver applies A twice.
+  // The cut vector bounds max|a| when the affinity is non-negative by construction.
+  plan.free_route = plan.icassp && free_diffuse_wanted(h, cfg, n, rq);
+  plan.amax_from_cut = plan.free_route && h->affinity_from_embeddings &&
+                       !h->constraint_applied && cfg->soft_multiplier >= 0.0 &&
+                       cfg->soft_multiplier <= 1.0;
+  return plan;
+}
+
+// The part of the ICASSP2018 front every value of a level shares: CropDiagonal's value and the
+// blurred matrix (+ per-strip row maxima) of the resident affinity, on the handle's stream.
+// `crop` (may be null): where the value vector the blur read lies; `crop_source`: as FrontResult's.
+int sweep_shared_blur(sc_handle h, const sc_config* cfg, const double** crop_out = nullptr,
+                      int* crop_source = nullptr) {
+  const int n = h->n, ld = h->ldn;
+  hipStream_t s = h->stream;
+  // ---- shared by every value: CropDiagonal's value and the blurred matrix (+ row maxima)
+  const double* crop = ptr<double>(h->cropval);
+  if (crop_source) *crop_source = 1;
+  if (!h->have_cropval) {
+    launch_crop_value(s, ptr<double>(h->A0), n, ld, ptr<double>(h->dvec));
+    crop = ptr<double>(h->dvec);
+    if (crop_source) *crop_source = 2;
+  }
+  if (crop_out) *crop_out = crop;
+  SC_TRY(upload_blur_weights(h, cfg));
+  if (!launch_gaussian_blur_fused(s, ptr<double>(h->A0), ptr<double>(h->B1), n, ld,
+                                  cfg->blur_radius, ptr<double>(h->blurw), crop,
+                                  ptr<double>(h->rmpart), &h->last_blur))
+    return fail(h, SC_ERR_HIP, "fused blur not taken");
+  SC_TRY(check_last(h, "sweep blur launch"));
+  return SC_OK;
+}
+
+// The members of one round (value ps[z] in member arena z): arenas sized, launch descriptors
+// filled.  *out_of_memory (with SC_OK): an arena's buffers did not fit -- the sweep runs the rest
+// one by one.  Any other failure, creating an arena included, is returned.
+int sweep_round_members(sc_handle h, const sc_config* cfg, const SweepPlan& plan,
+                        const EigRequest& rq, const double* ps, int cnt, FrontItem* fi,
+                        GemmGroupItem* dif, GroupEigMember* em, bool* out_of_memory) {
+  *out_of_memory = false;
+  const int n = h->n, ld = h->ldn;
+  const bool icassp = plan.icassp, free_route = plan.free_route;
+  const int nt = gemm_tile_dim(n);
+  for (int z = 0; z < cnt; ++z) {
+    sc_handle hz = nullptr;
+    SC_TRY(group_slot(h, z, &hz));
+    int rc = ensure_matrices(hz, n, 0, false);
+    if (rc == SC_OK) rc = ensure_eig(hz, n);
+    if (rc == SC_OK) rc = ensure_tilemap(hz, n);
+    if (rc == SC_OK && free_route) rc = ensure_free(hz, n);
+    if (rc == SC_ERR_OOM) {  // the caller's estimate was optimistic: the rest one by one
+      *out_of_memory = true;
+      return SC_OK;
+    }
+    if (rc != SC_OK) return fail(h, rc, hz->err);
+    hz->n = n;
+    hz->ldn = ld;
+    hz->n_vec = 0;
+    FrontItem& f = fi[z];
+    f.n = n;
+    f.ldn = ld;
+    // the matrix every value thresholds: the shared blurred one, or the affinity itself
+    f.B1 = icassp ? ptr<double>(h->B1) : ptr<double>(h->A0);  // read only
+    f.B2 = ptr<double>(hz->B2);
+    f.rmpart = ptr<double>(h->rmpart);
+    f.blur_cols = blur_tile_columns(n, cfg->blur_radius);
+    f.cut = ptr<double>(hz->cut);
+    f.rowmax = ptr<double>(hz->rowmax);
+    f.rowsum = ptr<double>(hz->rowsum);
+    f.cvec = ptr<double>(hz->cvec);
+    f.pvec = ptr<double>(hz->pvec);
+    f.tvec = ptr<double>(hz->tvec);
+    f.symflag = h->affinity_from_embeddings ? ptr<int>(h->symflag) : nullptr;
+    f.flags = ptr<int>(hz->flags);
+    f.p_own = ps[z];
+    dif[z] = GemmGroupItem();
+    dif[z].A = f.B2;
+    dif[z].lda = ld;
+    dif[z].C = ptr<double>(hz->B1);
+    dif[z].ldc = ld;
+    dif[z].n = n;
+    dif[z].K = n;
+    dif[z].tilemap = hz->tilemap_cur;
+    dif[z].partial_max = ptr<double>(hz->statp);
+    dif[z].partial_sum = ptr<double>(hz->statp) + (size_t)n * nt;
+    dif[z].rowmax = ptr<double>(hz->rowmax);
+    dif[z].rowsum = ptr<double>(hz->rowsum);
+    em[z] = GroupEigMember();
+    em[z].h = hz;
+    em[z].S = (free_route || !icassp) ? ptr<double>(hz->B2) : ptr<double>(hz->B1);
+    em[z].ld = ld;
+    em[z].n = n;
+    em[z].rq = rq;
+    em[z].free_op = free_route;
+  }
+  return SC_OK;
+}
+
+// The front of one round, for its `cnt` members: cuts (p_own per member), the grouped threshold +
+// symmetrise pass with or without digits, Diffuse or its statistics, the scaling vectors -- all on
+// the handle's stream.  sc_eig_ncluster_sweep runs the lockstep solver behind it; sc_stage_front
+// copies out what it left.
+// `taken` (may be null): per member, which kernel made its cut, whether the threshold pass wrote
+// its digits and whether the fp64 product formed its S (FrontResult's fields), set where each
+// launch happens.
+int sweep_round_front(sc_handle h, const sc_config* cfg, const SweepPlan& plan, const double* ps,
+                      int cnt, FrontItem* fi, GemmGroupItem* dif, GroupEigMember* em,
+                      FrontResult* taken = nullptr) {
+  const int n = h->n, ld = h->ldn;
+  hipStream_t s = h->stream;
+  const bool icassp = plan.icassp, free_route = plan.free_route;
+  const bool amax_from_cut = plan.amax_from_cut;
+  {  // (the init kernel must not clear the shared symflag word)
+    FrontItem init[kGroupMax];
+    memcpy(init, fi, sizeof(init));
+    for (int z = 0; z < cnt; ++z) init[z].symflag = nullptr;
+    launch_front_begin_group(s, init, cnt, false);
+  }
+  const bool own_cuts = !icassp;  // (RowMax cuts of the ICASSP front come from the blur's partials)
+  if (own_cuts) {
+    if (cfg->threshold_type == SC_THRESHOLD_PERCENTILE) {
+      launch_cut_percentile_group(s, fi, cnt, cfg->preserve_diagonal);  // (p_own per member)
+      for (int z = 0; taken && z < cnt; ++z) taken[z].cut_kernel = 3;
+    } else {
+      for (int z = 0; z < cnt; ++z)
+        launch_cut_from_rows(s, fi[z].B1, n, ld, ps[z], fi[z].cut,
+                             cfg->preserve_diagonal);
+      for (int z = 0; taken && z < cnt; ++z) taken[z].cut_kernel = 2;
+    }
+  }
+  // (round 6: with max|a| known from the cuts the threshold pass writes the members' digits
+  //  itself -- free_group_prepare / free_group_digits, free_api.hip; amax_from_cut implies
+  //  icassp and free_route)
+  FreeItem fitems[kGroupMax];
+  if (amax_from_cut) {
+    sc_handle fh0[kGroupMax];
+    const double* mats[kGroupMax];
+    const double* cuts[kGroupMax];
+    int nn[kGroupMax], ll[kGroupMax];
+    for (int z = 0; z < cnt; ++z) {
+      fh0[z] = em[z].h;
+      mats[z] = em[z].S;
+      cuts[z] = ptr<double>(em[z].h->cut);
+      nn[z] = n;
+      ll[z] = ld;
+    }
+    if (!own_cuts) launch_cut_from_partials_group(s, fi, cnt, cfg->p_percentile);
+    TsDigits digits[kGroupMax];
+    SC_TRY(free_group_prepare(fh0, mats, cuts, ps, cnt, ll, nn, s,
+                              (cfg->binarize || cfg->preserve_diagonal) ? 1.0 : 0.0, fitems,
+                              digits));
+    launch_threshold_symmetrize_group(s, fi, cnt, cfg->p_percentile, cfg->soft_multiplier,
+                                      cfg->binarize, cfg->symmetrize_type,
+                                      cfg->preserve_diagonal, true, digits);
+    for (int z = 0; taken && z < cnt; ++z) {
+      if (!own_cuts) taken[z].cut_kernel = 1;  // launch_cut_from_partials_group above
+      taken[z].digits_fused = digits[z].Q != nullptr;
+    }
+  } else {
+    launch_threshold_symmetrize_group(s, fi, cnt, cfg->p_percentile, cfg->soft_multiplier,
+                                      cfg->binarize, cfg->symmetrize_type,
+                                      cfg->preserve_diagonal, own_cuts);
+    // (cut_ready false: the launcher takes the cuts from the blur's partials itself)
+    for (int z = 0; taken && !own_cuts && z < cnt; ++z) taken[z].cut_kernel = 1;
+  }
+  if (!icassp) {
+    // no Diffuse: the row sums of the symmetrised matrix are the degrees
+    launch_row_stats_group(s, fi, cnt);
+  } else if (free_route) {
+    // rowmax / rowsum of every member's S = A A^T without forming it: digits per member,
+    // ONE launch for the digit products of all members, candidates + exact recheck per member
+    const signed char* qs[kGroupMax];
+    float* ts[kGroupMax];
+    unsigned* ms[kGroupMax];
+    sc_handle fh[kGroupMax];
+    for (int z = 0; z < cnt; ++z) fh[z] = em[z].h;
+    if (amax_from_cut) {
+      SC_TRY(free_group_digits(fh, fitems, cnt, s));
+    } else {
+      for (int z = 0; z < cnt; ++z) SC_TRY(free_stats_begin(em[z].h, s, em[z].S, ld, n, false));
+    }
+    for (int z = 0; z < cnt; ++z) {
+      sc_handle hz = em[z].h;
+      qs[z] = ptr<signed char>(hz->fq);
+      ts[z] = ptr<float>(hz->ft32);
+      ms[z] = ptr<unsigned>(hz->fwords);
+    }
+    {
+      int nn[kGroupMax];
+      const int2* tms[kGroupMax];
+      const int* pls[kGroupMax];
+      for (int z = 0; z < cnt; ++z) {
+        nn[z] = n;
+        tms[z] = em[0].h->tilemap_cur;
+        pls[z] = amax_from_cut ? fitems[z].plan : nullptr;
+      }
+      launch_gemm_i8_sym_group(s, qs, ts, ms, cnt, nn, tms, pls);
+    }
+    if (amax_from_cut) {
+      SC_TRY(free_group_end(fh, fitems, cnt, s));
+    } else {
+      for (int z = 0; z < cnt; ++z) SC_TRY(free_stats_end(em[z].h, s, em[z].S, ld, n, false));
+    }
+  } else {
+    launch_gemm_nt_group(s, dif, cnt, kEpiNone, 1);
+    for (int z = 0; taken && z < cnt; ++z) taken[z].diffuse_explicit = dif[z].n > 0;
+  }
+  launch_scaling_vectors_group(s, fi, cnt, cfg->laplacian_type, icassp ? 1 : 0);
+  SC_TRY(check_last(h, "sweep launch"));
+  return SC_OK;
+}
+}  // namespace
+
 // ------------------------------------------------------------------------------
 // AutoTune: one search level as a group (reference autotune.py:98-111)
 // ------------------------------------------------------------------------------
@@ -1255,36 +1510,14 @@ extern "C" int sc_eig_ncluster_sweep(sc_handle h, const sc_config* cfg, const do
     c.p_percentile = p_values[i];
     return sc_eig_ncluster(h, &c, diags + i);
   };
-  // Two sequences are swept as groups: the ICASSP2018 one, and [RowWiseThreshold, Symmetrize]
-  // alone -- the Turn-to-Diarize refinement (reference configs.py:49-59: Percentile cut,
-  // binarisation, preserved diagonal, Average), whose values are the thresholded affinity
-  // itself: no blur to share, no Diffuse, the lockstep solver works on the symmetrised matrix.
-  const bool icassp = grouped_front_covers(cfg);
-  const bool thr_sym_only = cfg->n_ops == 2 && cfg->ops[0] == SC_OP_ROW_WISE_THRESHOLD &&
-                            cfg->ops[1] == SC_OP_SYMMETRIZE;
-  const bool grouped = count > 1 && (icassp || thr_sym_only) && h->affinity_symmetric &&
-                       !constraint_active(h, cfg, false) &&
-                       (!icassp || blur_group_supported(n, cfg->blur_radius)) &&
-                       sym_group_eligible(n, rq, true) && !sw::sweep_one_by_one();
-  if (!grouped) {
+  const SweepPlan plan = sweep_plan(h, cfg, count, rq);
+  const bool icassp = plan.icassp, free_route = plan.free_route;
+  if (!plan.grouped) {
     for (int i = 0; i < count; ++i) SC_TRY(one_by_one(i));
     return SC_OK;
   }
   hipStream_t s = h->stream;
-  if (icassp) {
-    // ---- shared by every value: CropDiagonal's value and the blurred matrix (+ row maxima)
-    const double* crop = ptr<double>(h->cropval);
-    if (!h->have_cropval) {
-      launch_crop_value(s, ptr<double>(h->A0), n, ld, ptr<double>(h->dvec));
-      crop = ptr<double>(h->dvec);
-    }
-    SC_TRY(upload_blur_weights(h, cfg));
-    if (!launch_gaussian_blur_fused(s, ptr<double>(h->A0), ptr<double>(h->B1), n, ld,
-                                    cfg->blur_radius, ptr<double>(h->blurw), crop,
-                                    ptr<double>(h->rmpart)))
-      return fail(h, SC_ERR_HIP, "fused blur not taken");
-    SC_TRY(check_last(h, "sweep blur launch"));
-  }
+  if (icassp) SC_TRY(sweep_shared_blur(h, cfg));
   memset(h->gconv_hist, 0, sizeof(h->gconv_hist));
   h->gconv_seen = 0;
   std::vector<int> later;  // values whose solve left the common path
@@ -1296,12 +1529,6 @@ extern "C" int sc_eig_ncluster_sweep(sc_handle h, const sc_config* cfg, const do
   // the n-vectors and the eigensolver workspace -- no affinity copy, no k-means workspace.
   // The group is as wide as free memory allows (16 members of n = 16384 are 69 GB); whatever
   // does not fit is evaluated one value at a time on this handle, like before the grouping.
-  // Matrix-free Diffuse (free_api.hip): a member then holds the thresholded matrix, its digits
-  // and the fp32 tiles of their product instead of S, and the lockstep solver applies A twice.
-  // The cut vector bounds max|a| when the affinity is non-negative by construction.
-  const bool free_route = icassp && free_diffuse_wanted(h, cfg, n, rq);
-  const bool amax_from_cut = free_route && h->affinity_from_embeddings && !h->constraint_applied &&
-                             cfg->soft_multiplier >= 0.0 && cfg->soft_multiplier <= 1.0;
   const size_t member_bytes = 2 * (size_t)n * ld * sizeof(double) + (size_t)n * 8192 +
                               (free_route ? free_q_bytes(n) + free_t32_bytes(n) : 0);
   int width = 0;
@@ -1330,152 +1557,14 @@ extern "C" int sc_eig_ncluster_sweep(sc_handle h, const sc_config* cfg, const do
     GemmGroupItem dif[kGroupMax];
     GroupEigMember em[kGroupMax];
     memset(fi, 0, sizeof(fi));
-    const int nt = gemm_tile_dim(n);
-    for (int z = 0; z < cnt; ++z) {
-      sc_handle hz = nullptr;
-      SC_TRY(group_slot(h, z, &hz));
-      int rc = ensure_matrices(hz, n, 0, false);
-      if (rc == SC_OK) rc = ensure_eig(hz, n);
-      if (rc == SC_OK) rc = ensure_tilemap(hz, n);
-      if (rc == SC_OK && free_route) rc = ensure_free(hz, n);
-      if (rc == SC_ERR_OOM) {  // the estimate above was optimistic: the rest one by one
-        out_of_memory = true;
-        break;
-      }
-      if (rc != SC_OK) return fail(h, rc, hz->err);
-      hz->n = n;
-      hz->ldn = ld;
-      hz->n_vec = 0;
-      FrontItem& f = fi[z];
-      f.n = n;
-      f.ldn = ld;
-      // the matrix every value thresholds: the shared blurred one, or the affinity itself
-      f.B1 = icassp ? ptr<double>(h->B1) : ptr<double>(h->A0);  // read only
-      f.B2 = ptr<double>(hz->B2);
-      f.rmpart = ptr<double>(h->rmpart);
-      f.blur_cols = blur_tile_columns(n, cfg->blur_radius);
-      f.cut = ptr<double>(hz->cut);
-      f.rowmax = ptr<double>(hz->rowmax);
-      f.rowsum = ptr<double>(hz->rowsum);
-      f.cvec = ptr<double>(hz->cvec);
-      f.pvec = ptr<double>(hz->pvec);
-      f.tvec = ptr<double>(hz->tvec);
-      f.symflag = h->affinity_from_embeddings ? ptr<int>(h->symflag) : nullptr;
-      f.flags = ptr<int>(hz->flags);
-      f.p_own = p_values[base + z];
-      dif[z] = GemmGroupItem();
-      dif[z].A = f.B2;
-      dif[z].lda = ld;
-      dif[z].C = ptr<double>(hz->B1);
-      dif[z].ldc = ld;
-      dif[z].n = n;
-      dif[z].K = n;
-      dif[z].tilemap = hz->tilemap_cur;
-      dif[z].partial_max = ptr<double>(hz->statp);
-      dif[z].partial_sum = ptr<double>(hz->statp) + (size_t)n * nt;
-      dif[z].rowmax = ptr<double>(hz->rowmax);
-      dif[z].rowsum = ptr<double>(hz->rowsum);
-      em[z] = GroupEigMember();
-      em[z].h = hz;
-      em[z].S = (free_route || !icassp) ? ptr<double>(hz->B2) : ptr<double>(hz->B1);
-      em[z].ld = ld;
-      em[z].n = n;
-      em[z].rq = rq;
-      em[z].free_op = free_route;
-    }
+    SC_TRY(sweep_round_members(h, cfg, plan, rq, p_values + base, cnt, fi, dif, em,
+                               &out_of_memory));
     if (out_of_memory) {
       (void)hipGetLastError();
       for (int i = base; i < count; ++i) later.push_back(i);
       break;
     }
-    {  // (the init kernel must not clear the shared symflag word)
-      FrontItem init[kGroupMax];
-      memcpy(init, fi, sizeof(init));
-      for (int z = 0; z < cnt; ++z) init[z].symflag = nullptr;
-      launch_front_begin_group(s, init, cnt, false);
-    }
-    const bool own_cuts = !icassp;  // (RowMax cuts of the ICASSP front come from the blur's partials)
-    if (own_cuts) {
-      if (cfg->threshold_type == SC_THRESHOLD_PERCENTILE) {
-        launch_cut_percentile_group(s, fi, cnt, cfg->preserve_diagonal);  // (p_own per member)
-      } else {
-        for (int z = 0; z < cnt; ++z)
-          launch_cut_from_rows(s, fi[z].B1, n, ld, p_values[base + z], fi[z].cut,
-                               cfg->preserve_diagonal);
-      }
-    }
-    // (round 6: with max|a| known from the cuts the threshold pass writes the members' digits
-    //  itself -- free_group_prepare / free_group_digits, free_api.hip; amax_from_cut implies
-    //  icassp and free_route)
-    FreeItem fitems[kGroupMax];
-    if (amax_from_cut) {
-      sc_handle fh0[kGroupMax];
-      const double* mats[kGroupMax];
-      const double* cuts[kGroupMax];
-      int nn[kGroupMax], ll[kGroupMax];
-      for (int z = 0; z < cnt; ++z) {
-        fh0[z] = em[z].h;
-        mats[z] = em[z].S;
-        cuts[z] = ptr<double>(em[z].h->cut);
-        nn[z] = n;
-        ll[z] = ld;
-      }
-      if (!own_cuts) launch_cut_from_partials_group(s, fi, cnt, cfg->p_percentile);
-      TsDigits digits[kGroupMax];
-      SC_TRY(free_group_prepare(fh0, mats, cuts, p_values + base, cnt, ll, nn, s,
-                                (cfg->binarize || cfg->preserve_diagonal) ? 1.0 : 0.0, fitems,
-                                digits));
-      launch_threshold_symmetrize_group(s, fi, cnt, cfg->p_percentile, cfg->soft_multiplier,
-                                        cfg->binarize, cfg->symmetrize_type,
-                                        cfg->preserve_diagonal, true, digits);
-    } else {
-      launch_threshold_symmetrize_group(s, fi, cnt, cfg->p_percentile, cfg->soft_multiplier,
-                                        cfg->binarize, cfg->symmetrize_type,
-                                        cfg->preserve_diagonal, own_cuts);
-    }
-    if (!icassp) {
-      // no Diffuse: the row sums of the symmetrised matrix are the degrees
-      launch_row_stats_group(s, fi, cnt);
-    } else if (free_route) {
-      // rowmax / rowsum of every member's S = A A^T without forming it: digits per member,
-      // ONE launch for the digit products of all members, candidates + exact recheck per member
-      const signed char* qs[kGroupMax];
-      float* ts[kGroupMax];
-      unsigned* ms[kGroupMax];
-      sc_handle fh[kGroupMax];
-      for (int z = 0; z < cnt; ++z) fh[z] = em[z].h;
-      if (amax_from_cut) {
-        SC_TRY(free_group_digits(fh, fitems, cnt, s));
-      } else {
-        for (int z = 0; z < cnt; ++z) SC_TRY(free_stats_begin(em[z].h, s, em[z].S, ld, n, false));
-      }
-      for (int z = 0; z < cnt; ++z) {
-        sc_handle hz = em[z].h;
-        qs[z] = ptr<signed char>(hz->fq);
-        ts[z] = ptr<float>(hz->ft32);
-        ms[z] = ptr<unsigned>(hz->fwords);
-      }
-      {
-        int nn[kGroupMax];
-        const int2* tms[kGroupMax];
-        const int* pls[kGroupMax];
-        for (int z = 0; z < cnt; ++z) {
-          nn[z] = n;
-          tms[z] = em[0].h->tilemap_cur;
-          pls[z] = amax_from_cut ? fitems[z].plan : nullptr;
-        }
-        launch_gemm_i8_sym_group(s, qs, ts, ms, cnt, nn, tms, pls);
-      }
-      if (amax_from_cut) {
-        SC_TRY(free_group_end(fh, fitems, cnt, s));
-      } else {
-        for (int z = 0; z < cnt; ++z) SC_TRY(free_stats_end(em[z].h, s, em[z].S, ld, n, false));
-      }
-    } else {
-      launch_gemm_nt_group(s, dif, cnt, kEpiNone, 1);
-    }
-    launch_scaling_vectors_group(s, fi, cnt, cfg->laplacian_type, icassp ? 1 : 0);
-    SC_TRY(check_last(h, "sweep launch"));
+    SC_TRY(sweep_round_front(h, cfg, plan, p_values + base, cnt, fi, dif, em));
     // (with the Ritz vectors: the level's winner is then adopted, not evaluated again --
     //  one upload and one launch for the whole group against a Diffuse + a solve)
     SC_TRY(sym_topk_group(h, em, cnt, true));
@@ -1567,3 +1656,251 @@ extern "C" int sc_sweep_adopt(sc_handle h, const sc_config* cfg, int index, sc_d
   return SC_OK;
 }
 
+
+// ------------------------------------------------------------------------------
+// sc_stage_front: what the fused refinement front leaves behind (tests)
+// ------------------------------------------------------------------------------
+namespace {
+// where one member's front left things, and which branches it took
+struct FrontWhere {
+  sc_handle h = nullptr;  // arena of the n-vectors (rowmax .. tvec, cut) and the overflow record
+  int n = 0, ld = 0;
+  const double* a0 = nullptr;
+  const double* cropval = nullptr;
+  const double* cut = nullptr;
+  const double* a = nullptr;
+  const double* s = nullptr;
+  int diffuse_path = SC_DIFFUSE_PATH_NONE;
+  bool symmetric = true, folded_rownorm = false, free_op = false, digits_fused = false;
+  BlurLaunch blur;
+  int crop_source = 0, cut_kernel = 0;
+};
+
+// (every stream of the front has been synchronised: plain blocking copies)
+int front_copy_out(sc_handle lead, const FrontWhere& w, sc_front_out* out) {
+  const int n = w.n;
+  int written = 0;
+  auto matrix = [&](const double* src, double* dst, int bit) -> int {
+    if (!src || !dst) return SC_OK;
+    SC_HIP(lead, hipMemcpy2D(dst, (size_t)n * sizeof(double), src, (size_t)w.ld * sizeof(double),
+                             (size_t)n * sizeof(double), n, hipMemcpyDeviceToHost));
+    written |= 1 << bit;
+    return SC_OK;
+  };
+  auto vec = [&](const void* src, double* dst, int bit) -> int {
+    if (!src || !dst) return SC_OK;
+    SC_HIP(lead, hipMemcpy(dst, src, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    written |= 1 << bit;
+    return SC_OK;
+  };
+  SC_TRY(matrix(w.a0, out->a0, 0));
+  SC_TRY(vec(w.cropval, out->cropval, 1));
+  SC_TRY(vec(w.cut, out->cut, 2));
+  SC_TRY(matrix(w.a, out->a, 3));
+  SC_TRY(matrix(w.s, out->s, 4));
+  SC_TRY(vec(w.h->rowmax.p, out->rowmax, 5));
+  SC_TRY(vec(w.h->rowsum.p, out->rowsum, 6));
+  SC_TRY(vec(w.h->cvec.p, out->c, 7));
+  SC_TRY(vec(w.h->pvec.p, out->p, 8));
+  SC_TRY(vec(w.h->tvec.p, out->t, 9));
+  int32_t* info = out->info;
+  memset(info, 0, sizeof(out->info));
+  info[SC_FRONT_INFO_DIFFUSE_PATH] = w.diffuse_path;
+  info[SC_FRONT_INFO_SYMMETRIC] = w.symmetric;
+  info[SC_FRONT_INFO_FOLDED_ROWNORM] = w.folded_rownorm;
+  info[SC_FRONT_INFO_FREE_OP] = w.free_op;
+  info[SC_FRONT_INFO_DIGITS_FUSED] = w.digits_fused;
+  info[SC_FRONT_INFO_BLUR_KERNEL] = w.blur.kernel;
+  info[SC_FRONT_INFO_BLUR_ROWS] = w.blur.rows;
+  if (w.free_op) {
+    int cand, ovf, forms;
+    free_front_info(w.h, &cand, &ovf, &forms);
+    info[SC_FRONT_INFO_FREE_CANDIDATES] = cand;
+    info[SC_FRONT_INFO_FREE_OVERFLOW_ROWS] = ovf;
+    info[SC_FRONT_INFO_FREE_FORMS_S] = forms;
+  }
+  info[SC_FRONT_INFO_CROP_SOURCE] = w.crop_source;
+  info[SC_FRONT_INFO_CUT_KERNEL] = w.cut_kernel;
+  info[SC_FRONT_INFO_WRITTEN] = written;
+  return SC_OK;
+}
+
+// sc_set_embeddings / sc_set_affinity + sc_compute_affinity + the front of sc_eig_ncluster
+int stage_front_single(sc_handle h, const sc_config* cfg, int n, int d, const double* x,
+                       const double* affinity, sc_front_out* out) {
+  if (x) {
+    SC_TRY(sc_set_embeddings(h, x, n, d));
+    SC_TRY(sc_compute_affinity(h));
+  } else {
+    SC_TRY(sc_set_affinity(h, affinity, n));
+  }
+  h->nev = 0;
+  sc_diag diag;
+  memset(&diag, 0, sizeof(diag));
+  FrontResult fr;
+  SC_TRY(eig_ncluster_impl(h, cfg, &diag, nullptr, nullptr, false, &fr));
+  SC_HIP(h, hipStreamSynchronize(h->stream));
+  if (!fr.symmetric)
+    return fail(h, SC_ERR_UNSUPPORTED, "sc_stage_front: the refined matrix is not symmetric");
+  FrontWhere w;
+  w.h = h;
+  w.n = n;
+  w.ld = h->ldn;
+  w.a0 = ptr<double>(h->A0);
+  w.cropval = fr.crop_source == 1 ? ptr<double>(h->cropval)
+                                  : (fr.crop_source == 2 ? ptr<double>(h->dvec) : nullptr);
+  w.cut = fr.cut_kernel != 0 ? ptr<double>(h->cut) : nullptr;
+  // (the explicit product wrote S into the buffer after A's: `scratch` is still A)
+  w.a = fr.diffuse_explicit ? fr.scratch : fr.matrix;
+  w.s = fr.diffuse_explicit ? fr.matrix : nullptr;
+  w.diffuse_path = fr.free_op ? SC_DIFFUSE_PATH_FREE
+                              : (fr.diffuse_explicit ? SC_DIFFUSE_PATH_EXPLICIT
+                                                     : SC_DIFFUSE_PATH_NONE);
+  w.symmetric = fr.symmetric;
+  w.folded_rownorm = fr.folded_rownorm;
+  w.free_op = fr.free_op;
+  w.digits_fused = fr.digits_fused;
+  w.blur = h->last_blur;
+  w.crop_source = fr.crop_source;
+  w.cut_kernel = fr.cut_kernel;
+  return front_copy_out(h, w, out);
+}
+
+// the members as run_group_lane builds them, then ONE enqueue_front_grouped on bank 0
+int stage_front_grouped(sc_handle h, const sc_config* cfg, int count, const int32_t* ns32, int d,
+                        const double* const* xs, sc_front_out* outs) {
+  const EigRequest rq = make_eig_request(cfg);
+  std::vector<int> ns(ns32, ns32 + count), idx(count);
+  int largest = 0, smallest = ns[0];
+  for (int z = 0; z < count; ++z) {
+    idx[z] = z;
+    largest = std::max(largest, ns[z]);
+    smallest = std::min(smallest, ns[z]);
+    // (what predict_batch_core asks of a member of the Lanczos route)
+    if (!sym_group_eligible(ns[z], rq))
+      return fail(h, SC_ERR_UNSUPPORTED, "sc_stage_front: a member outside the grouped route");
+  }
+  if (constraint_active(h, cfg, true) || constraint_active(h, cfg, false) ||
+      !grouped_front_covers(cfg) || !blur_group_front_supported(smallest, cfg->blur_radius))
+    return fail(h, SC_ERR_UNSUPPORTED,
+                "sc_stage_front: the grouped front covers the ICASSP2018 sequence (blur radius 4 "
+                "or 8, RowMax) on members of n >= 256");
+  h->sweep_slot.clear();  // (the member arenas are reused)
+  const std::vector<sc_array> arrays = host_f64_arrays(xs, ns.data(), d, count);
+  SC_TRY(ensure_bank_stream(h, 0));
+  SC_TRY(reserve_bank_arenas(h, cfg, rq, 0, count, largest, d, nullptr));
+  SC_TRY(upload_group_blur_weights(h, cfg));
+  Member mb[kGroupMax];
+  h->last_blur = BlurLaunch();
+  const int rc = enqueue_front_grouped(h, arrays.data(), ns.data(), d, cfg, nullptr, idx.data(),
+                                       count, 0, mb, 0);
+  // (the uploads read the caller's arrays and the statistics write pinned words: drain first)
+  SC_HIP(h, hipStreamSynchronize(h->gbank_stream[0]));
+  SC_TRY(rc);
+  for (int z = 0; z < count; ++z) {
+    sc_handle hz = mb[z].h;
+    const FrontResult& fr = mb[z].front;
+    FrontWhere w;
+    w.h = hz;
+    w.n = ns[z];
+    w.ld = hz->ldn;
+    w.a0 = ptr<double>(hz->A0);
+    w.cropval = ptr<double>(hz->cropval);
+    w.cut = ptr<double>(hz->cut);
+    w.a = ptr<double>(hz->B2);
+    w.s = fr.diffuse_explicit ? ptr<double>(hz->B1) : nullptr;
+    w.diffuse_path = fr.free_op ? SC_DIFFUSE_PATH_FREE
+                                : (fr.diffuse_explicit ? SC_DIFFUSE_PATH_EXPLICIT
+                                                       : SC_DIFFUSE_PATH_NONE);
+    w.symmetric = fr.symmetric;
+    w.folded_rownorm = fr.folded_rownorm;
+    w.free_op = fr.free_op;
+    w.digits_fused = fr.digits_fused;
+    w.blur = h->last_blur;
+    w.crop_source = fr.crop_source;
+    w.cut_kernel = fr.cut_kernel;
+    SC_TRY(front_copy_out(h, w, outs + z));
+  }
+  return SC_OK;
+}
+
+// the front of one round of sc_eig_ncluster_sweep on the affinity of x
+int stage_front_sweep(sc_handle h, const sc_config* cfg, int count, int n, int d, const double* x,
+                      const double* p_values, sc_front_out* outs) {
+  SC_TRY(sc_set_embeddings(h, x, n, d));
+  SC_TRY(sc_compute_affinity(h));
+  const EigRequest rq = make_eig_request(cfg);
+  const SweepPlan plan = sweep_plan(h, cfg, count, rq);
+  if (!plan.grouped)
+    return fail(h, SC_ERR_UNSUPPORTED,
+                "sc_stage_front: sc_eig_ncluster_sweep would evaluate this level one by one");
+  h->last_blur = BlurLaunch();
+  const double* crop = nullptr;
+  int crop_source = 0;
+  if (plan.icassp) SC_TRY(sweep_shared_blur(h, cfg, &crop, &crop_source));
+  FrontItem fi[kGroupMax];
+  GemmGroupItem dif[kGroupMax];
+  GroupEigMember em[kGroupMax];
+  FrontResult taken[kGroupMax];
+  memset(fi, 0, sizeof(fi));
+  bool out_of_memory = false;
+  SC_TRY(sweep_round_members(h, cfg, plan, rq, p_values, count, fi, dif, em, &out_of_memory));
+  if (out_of_memory)
+    return fail(h, SC_ERR_OOM, "sc_stage_front: the round's member arenas do not fit");
+  SC_TRY(sweep_round_front(h, cfg, plan, p_values, count, fi, dif, em, taken));
+  SC_HIP(h, hipStreamSynchronize(h->stream));
+  for (int z = 0; z < count; ++z) {
+    sc_handle hz = em[z].h;
+    FrontWhere w;
+    w.h = hz;
+    w.n = n;
+    w.ld = h->ldn;
+    w.a0 = ptr<double>(h->A0);
+    w.cropval = crop;
+    w.cut = taken[z].cut_kernel != 0 ? ptr<double>(hz->cut) : nullptr;
+    w.a = ptr<double>(hz->B2);
+    w.s = taken[z].diffuse_explicit ? ptr<double>(hz->B1) : nullptr;
+    w.diffuse_path = em[z].free_op ? SC_DIFFUSE_PATH_FREE
+                                   : (taken[z].diffuse_explicit ? SC_DIFFUSE_PATH_EXPLICIT
+                                                                : SC_DIFFUSE_PATH_NONE);
+    w.folded_rownorm = plan.icassp;  // (launch_scaling_vectors_group's row_normalized)
+    w.free_op = em[z].free_op;
+    w.digits_fused = taken[z].digits_fused;
+    w.blur = h->last_blur;
+    w.crop_source = crop_source;
+    w.cut_kernel = taken[z].cut_kernel;
+    SC_TRY(front_copy_out(h, w, outs + z));
+  }
+  return SC_OK;
+}
+}  // namespace
+
+extern "C" int sc_stage_front(sc_handle h, int route, const sc_config* cfg, int count,
+                              const int32_t* ns, int d, const double* const* xs,
+                              const double* affinity, const double* p_values,
+                              sc_front_out* outs) {
+  if (!h) return SC_ERR_INVALID;
+  SC_TRY(validate_config(h, cfg));
+  if (!ns || !outs || count < 1) return fail(h, SC_ERR_INVALID, "sc_stage_front: NULL argument");
+  if (count > kGroupMax)
+    return fail(h, SC_ERR_UNSUPPORTED, "sc_stage_front: at most 16 members / values per call");
+  SC_HIP(h, hipSetDevice(h->device));
+  const int members = route == SC_FRONT_ROUTE_GROUPED ? count : 1;
+  for (int z = 0; z < members; ++z)
+    if (ns[z] <= 0 || (xs && !xs[z]))
+      return fail(h, SC_ERR_INVALID, "sc_stage_front: every member needs rows");
+  if (xs ? d <= 0 : (route != SC_FRONT_ROUTE_SINGLE || !affinity))
+    return fail(h, SC_ERR_INVALID,
+                "sc_stage_front: embeddings (n, d), or an affinity on the single route");
+  switch (route) {
+    case SC_FRONT_ROUTE_SINGLE:
+      if (count != 1) return fail(h, SC_ERR_INVALID, "sc_stage_front: the single route takes one");
+      return stage_front_single(h, cfg, ns[0], d, xs ? xs[0] : nullptr, affinity, outs);
+    case SC_FRONT_ROUTE_GROUPED:
+      return stage_front_grouped(h, cfg, count, ns, d, xs, outs);
+    case SC_FRONT_ROUTE_SWEEP:
+      if (!p_values) return fail(h, SC_ERR_INVALID, "sc_stage_front: p_values is NULL");
+      return stage_front_sweep(h, cfg, count, ns[0], d, xs[0], p_values, outs);
+  }
+  return fail(h, SC_ERR_INVALID, "sc_stage_front: unknown route");
+}

@@ -374,8 +374,9 @@ int blur_tile_columns(int n, int radius) {
 // Returns true if the row-max partials were produced (fast path taken).
 bool launch_gaussian_blur_fused(hipStream_t s, const double* in, double* out, int n, int ld,
                                 int radius, const double* weights_dev, const double* diag,
-                                double* rowmax_partials) {
+                                double* rowmax_partials, BlurLaunch* taken) {
   dim3 grid((n + TW - 1) / TW, (n + TH - 1) / TH);
+  if (taken) *taken = BlurLaunch{0, 0};
   if ((radius == 4 || radius == 8) && n >= kStreamMinN) {
     // A wave walks its rows one after the other (a chain of dependent row loads); the rows
     // per wave make the grid a whole number of rounds of resident workgroups (above)
@@ -390,6 +391,7 @@ bool launch_gaussian_blur_fused(hipStream_t s, const double* in, double* out, in
       ++rows;
     }
     dim3 sgrid(strips, (n + 4 * rows - 1) / (4 * rows));
+    if (taken) *taken = BlurLaunch{2, rows};
     if (radius == 4)
       hipLaunchKernelGGL((k_gaussian_blur_stream<4>), sgrid, dim3(256), 0, s, in, out, n, ld,
                          weights_dev, diag, rowmax_partials, rows);
@@ -400,6 +402,7 @@ bool launch_gaussian_blur_fused(hipStream_t s, const double* in, double* out, in
   }
   if ((radius == 4 || radius == 8) && n >= 128) {
     dim3 fgrid(blur_tile_columns(n, radius), (n + kBlurRows - 1) / kBlurRows);
+    if (taken) *taken = BlurLaunch{1, 0};
     if (radius == 4)
       hipLaunchKernelGGL((k_gaussian_blur_r<4>), fgrid, dim3(256), 0, s, in, out, n, ld,
                          weights_dev, diag, rowmax_partials);
@@ -440,7 +443,7 @@ int blur_stream_columns(int n, int radius) {
   return (n + ow - 1) / ow;
 }
 void launch_gaussian_blur_group(hipStream_t s, const FrontItem* items, int count, int radius,
-                                const double* weights_dev) {
+                                const double* weights_dev, BlurLaunch* taken) {
   GroupOf<FrontItem> g;
   memset(&g, 0, sizeof(g));
   int nmax = 0, cmax = 0;
@@ -455,6 +458,7 @@ void launch_gaussian_blur_group(hipStream_t s, const FrontItem* items, int count
   for (int z = 0; z < count; ++z)
     if (items[z].n > 0) total += (long long)items[z].blur_cols * items[z].n;
   const int rows = stream_rows_per_wave(total, radius);
+  if (taken) *taken = BlurLaunch{2, rows};
   dim3 grid(cmax, (nmax + 4 * rows - 1) / (4 * rows), count);
   if (radius == 4)
     hipLaunchKernelGGL((k_gaussian_blur_stream_g<4>), grid, dim3(256), 0, s, g, weights_dev,

@@ -210,6 +210,15 @@ int free_diffuse_stats(sc_handle h, const double* A, int ld, int n, bool have_am
   return free_stats_end(h, s, A, ld, n, true, ptr<int>(h->fplan));
 }
 
+// what the statistics pipeline left in h->h_free, once the stream it ran on has drained
+// (sc_stage_front): candidates evaluated, rows over the candidate cap, and whether free_fix_overflow
+// would give up on them (the solver then forms S after all)
+void free_front_info(sc_handle h, int* candidates, int* overflow_rows, int* forms_s) {
+  *candidates = h->h_free[65];
+  *overflow_rows = h->h_free[0];
+  *forms_s = h->h_free[0] > kOvfRowsMax ? 1 : 0;
+}
+
 // plain product W = A Vs by the solver's own block matvec (c = 1, p = 0)
 static void plain_matvec(hipStream_t s, const double* A, int ld, int n, bool sym_mv,
                          const double* Vs, double* W, double* slabs) {

@@ -166,6 +166,9 @@ struct sc_handle_s {
   // n, restart cycles, block steps enqueued beyond the basis (run-ahead), two-product operator
   int krylov_m = 0, krylov_n = 0, krylov_cycles = 0, krylov_ahead = 0;
   bool krylov_free = false;
+  // What the last front on this handle launched, for sc_stage_front: the blur kernel (and the
+  // rows per wave of the streaming one)
+  BlurLaunch last_blur;
 };
 
 // hipEvent slots of the current call (reset by the entry points); -1 when exhausted
@@ -350,12 +353,23 @@ struct FrontResult {
   bool chain_flags_cleared = false;
   // the lockstep group solve saw this problem latch the fused chain: the host-driven chain
   bool skip_fused = false;
+  // which branches the front took (sc_stage_front reports them; nothing else reads them):
+  // the threshold pass wrote the digits of the matrix-free Diffuse; S = A A^T was formed by the
+  // fp64 product (then `scratch` still holds A); where the CropDiagonal value came from (0: no
+  // value vector -- the op ran unfused or not at all, 1: the affinity epilogue, 2: k_crop_value);
+  // which kernel made the cut vector (0: none, 1: k_cut_from_partials, 2: k_cut_from_rows,
+  // 3: k_row_percentile_cut)
+  bool digits_fused = false, diffuse_explicit = false;
+  int crop_source = 0, cut_kernel = 0;
 };
 EigRequest make_eig_request(const sc_config* cfg);
 int upload_blur_weights(sc_handle h, const sc_config* cfg);  // into h->blurw, on h->stream
 // `resume`: the stages before the eigensolver already ran (a FrontResult of this handle)
+// `stop_before_solver`: run the front exactly as a full call does -- every routing decision as
+// it is, unlike `front_only` -- then report where it left things and return before the solver
 int eig_ncluster_impl(sc_handle h, const sc_config* cfg, sc_diag* diag, FrontResult* front_only,
-                      const FrontResult* resume = nullptr, bool defer_timing = false);
+                      const FrontResult* resume = nullptr, bool defer_timing = false,
+                      FrontResult* stop_before_solver = nullptr);
 // RandomState(0) stream of the k-means seeding: the uniform that picks the first centre, the
 // trial count 2 + int(log k), and the (k - 1) * trials doubles after it (kmeans_api.hip)
 void kmeans_seed_constants(int k, double* u_first, int* trials, std::vector<double>* rnd);
@@ -412,6 +426,8 @@ int free_group_digits(sc_handle* hs, const struct FreeItem* items, int count, hi
 int free_group_end(sc_handle* hs, const struct FreeItem* items, int count, hipStream_t s);
 int free_fused_prepare(sc_handle h, hipStream_t s, int n, const double* cut, double p,
                        double floor_value);
+// what the statistics left in h->h_free, once their stream has drained (sc_stage_front)
+void free_front_info(sc_handle h, int* candidates, int* overflow_rows, int* forms_s);
 // enqueue the statistics of S = A A^T (h->rowmax, h->rowsum) on h->stream; no synchronisation.
 // The overflow words travel to h->h_free behind them.
 // `have_amax`: h->fscal[0] already holds max|a| (or an upper bound of it) for this A

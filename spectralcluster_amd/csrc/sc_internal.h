@@ -118,10 +118,15 @@ void launch_crop_diagonal(hipStream_t s, const double* in, double* out, int n,
                           int ld);
 void launch_gaussian_blur(hipStream_t s, const double* in, double* out, int n,
                           int ld, int radius, const double* weights_dev);
+// which kernel a blur launch took, for the test entry sc_stage_front to report: 0 generic,
+// 1 tile (k_gaussian_blur_r), 2 streaming (rows: its rows per wave); -1: none was launched
+struct BlurLaunch {
+  int kernel = -1, rows = 0;
+};
 // fused forms used by the predict() pipeline
 bool launch_gaussian_blur_fused(hipStream_t s, const double* in, double* out, int n, int ld,
                                 int radius, const double* weights_dev, const double* diag,
-                                double* rowmax_partials);
+                                double* rowmax_partials, BlurLaunch* taken = nullptr);
 int blur_tile_columns(int n, int radius);
 // radius above SC_MAX_BLUR_RADIUS (sigma > 8): two global passes, tmp = an n x ld scratch
 void launch_gaussian_blur_any_radius(hipStream_t s, const double* in, double* tmp, double* out,
@@ -351,7 +356,7 @@ bool blur_group_supported(int n_min, int radius);
 bool blur_group_front_supported(int n_min, int radius);
 int blur_stream_columns(int n, int radius);
 void launch_gaussian_blur_group(hipStream_t s, const FrontItem* items, int count, int radius,
-                                const double* weights_dev);
+                                const double* weights_dev, BlurLaunch* taken = nullptr);
 // What the threshold + symmetrise pass leaves for the matrix-free Diffuse when it writes the digits
 // itself (rowops.hip threshold_symmetrize_body<true>; Q == nullptr: this matrix gets none): the
 // two 8-bit digits of q = rint(sigma a) in the product's layout (a 64 x 64 tile is one 128-byte

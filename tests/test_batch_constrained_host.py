@@ -1,5 +1,5 @@
 """Host side of the constrained batch: `sc_predict_batch_constrained` and its test entry
-`sc_stage_constraint_band_group` are additions to ABI 8 -- declared in the header, mirrored in
+`sc_stage_constraint_band_group` were additions to ABI 8 (now 9) -- declared in the header, mirrored in
 `_lib.PROTOTYPES`, exported by the library, and safe to call with a NULL handle.  No GPU."""
 
 import ctypes
@@ -28,11 +28,11 @@ def test_new_symbols_are_declared_mirrored_and_exported():
   assert declared == set(_lib.PROTOTYPES)
 
 
-def test_abi_version_is_still_8():
-  assert _lib.SC_ABI_VERSION == 8
-  assert _lib.load().sc_abi_version() == 8
+def test_abi_version_is_9():
+  assert _lib.SC_ABI_VERSION == 9
+  assert _lib.load().sc_abi_version() == 9
   text = open(HEADER).read()
-  assert re.search(r"#define\s+SC_ABI_VERSION\s+8\b", text)
+  assert re.search(r"#define\s+SC_ABI_VERSION\s+9\b", text)
 
 
 def test_null_handle_is_invalid():

@@ -23,8 +23,8 @@ def test_library_exports_the_batch_route_report():
   for name, value in (("SINGLE", 0), ("GROUP_LANCZOS", 1), ("GROUP_JACOBI", 2)):
     assert re.search(r"SC_BATCH_ROUTE_%s\s*=\s*%d\b" % (name, value), header), name
     assert getattr(_lib, "BATCH_ROUTE_" + name) == value
-  # an addition only: the structs are the parent's (ABI 8: the two test entries of the eigensolver)
-  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 8
+  # an addition only: the structs are the parent's (ABI 9: the test entry of the refinement front)
+  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 9
 
 
 def test_null_handle_is_invalid():
