@@ -496,6 +496,41 @@ int sc_cluster_centroids(sc_handle h, const double* x, int n, int d, const int64
                          int k, double* out);
 
 /*
+ * Stream pool: up to `capacity` streaming sessions (multi_stage_clusterer.py:128-180) whose
+ * caches stay on the device.  A session lives in a slot 0 .. capacity - 1 and holds up to u2
+ * rows of d values; its pre-clusterer reduces them to u1 centroids (2 <= u1 < u2).  All device
+ * memory is taken by sc_pool_create, as slabs indexed by slot; SC_ERR_OOM when they do not fit
+ * in 85 % of the free memory, so a pool never runs out of memory mid-stream.  A pool works on
+ * its handle's stream and, like the handle, is used by one thread at a time; destroy it before
+ * the handle.
+ */
+typedef struct sc_pool_s* sc_pool;
+enum { SC_POOL_CACHE = 0, SC_POOL_CENTROIDS = 1 };
+int sc_pool_create(sc_handle h, int capacity, int d, int u1, int u2, sc_pool* out);
+int sc_pool_destroy(sc_pool pool);
+/* the session of `slot` starts again with no rows */
+int sc_pool_reset(sc_pool pool, int slot);
+/* rows of slot (count of cached rows), or a negative sc_status */
+int sc_pool_rows(sc_pool pool, int slot);
+/* counts[i] consecutive rows of `rows` (any sc_array with d columns) are appended to the cache
+ * of slots[i] (distinct slots), each with its unit-norm copy: one transfer, one launch.  Returns
+ * when the source may be reused.  SC_ERR_INVALID, before anything moves, when a cache would
+ * exceed u2 rows. */
+int sc_pool_append(sc_pool pool, const int32_t* slots, const int32_t* counts, int count,
+                   const sc_array* rows);
+/* Complete-linkage cosine clustering of every listed slot's cache (more than u1 rows each) down
+ * to u1 clusters: labels_out[i] receives the rows(slots[i]) labels, numbered as sklearn numbers
+ * them (what sc_ahc returns for those rows); the u1 centroids of each slot stay on the device.
+ * One distance pass, one chain launch (a workgroup per slot) and one centroid launch for all. */
+int sc_pool_precluster(sc_pool pool, const int32_t* slots, int count, int64_t* const* labels_out);
+/* device descriptor (u1 x d, float64) of the centroids the last sc_pool_precluster left */
+int sc_pool_centroids(sc_pool pool, int slot, sc_array* out);
+/* what = SC_POOL_CACHE: the rows(slot) x d cache; SC_POOL_CENTROIDS: the u1 x d centroids */
+int sc_pool_get(sc_pool pool, int slot, int what, double* out);
+/* dynamic compression: the cache of slot becomes its u1 centroids (copied on the device) */
+int sc_pool_compress(sc_pool pool, int slot);
+
+/*
  * Fallback decisions of the callers (fallback_clusterer.py, naive_clusterer.py).
  * sc_affinity_stats: out[4] = {affinity.min(), np.diag(affinity, 1).min(), mean,
  *   np.std(affinity)} of the RESIDENT affinity (fallback_clusterer.py:137-153).

@@ -16,7 +16,7 @@ _PUBLIC = {
     "fallback_clusterer": ("FallbackOptions", "SingleClusterCondition",
                            "FallbackClustererType"),
     "laplacian": ("LaplacianType",),
-    "multi_stage_clusterer": ("Deflicker", "MultiStageClusterer"),
+    "multi_stage_clusterer": ("Deflicker", "MultiStageClusterer", "MultiStageStreamPool"),
     "naive_clusterer": ("NaiveClusterer",),
     "refinement": ("RefinementName", "RefinementOptions", "ThresholdType", "SymmetrizeType"),
     "spectral_clusterer": ("SpectralClusterer",),

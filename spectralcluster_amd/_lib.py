@@ -123,6 +123,8 @@ class ScDiag(ctypes.Structure):
 # sc_array.dtype / .location
 SC_DTYPE_F64, SC_DTYPE_F32, SC_DTYPE_F16, SC_DTYPE_BF16 = range(4)
 SC_MEM_HOST, SC_MEM_DEVICE = range(2)
+# sc_pool_get: what
+SC_POOL_CACHE, SC_POOL_CENTROIDS = range(2)
 
 
 class ScArray(ctypes.Structure):
@@ -256,6 +258,19 @@ PROTOTYPES = {
                               ctypes.POINTER(ctypes.c_int)]),
     "sc_cluster_centroids": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int, ctypes.c_int,
                                             _c_int64_p, ctypes.c_int, _c_double_p]),
+    "sc_pool_create": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, ctypes.POINTER(_handle_t)]),
+    "sc_pool_destroy": (ctypes.c_int, [_handle_t]),
+    "sc_pool_reset": (ctypes.c_int, [_handle_t, ctypes.c_int]),
+    "sc_pool_rows": (ctypes.c_int, [_handle_t, ctypes.c_int]),
+    "sc_pool_append": (ctypes.c_int, [_handle_t, ctypes.POINTER(ctypes.c_int32),
+                                      ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
+                                      ctypes.POINTER(ScArray)]),
+    "sc_pool_precluster": (ctypes.c_int, [_handle_t, ctypes.POINTER(ctypes.c_int32),
+                                          ctypes.c_int, ctypes.POINTER(_c_int64_p)]),
+    "sc_pool_centroids": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.POINTER(ScArray)]),
+    "sc_pool_get": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.c_int, _c_double_p]),
+    "sc_pool_compress": (ctypes.c_int, [_handle_t, ctypes.c_int]),
     "sc_affinity_stats": (ctypes.c_int, [_handle_t, _c_double_p]),
     "sc_affinity_gmm_bic": (ctypes.c_int, [_handle_t, ctypes.c_int, _c_double_p, _c_double_p]),
     "sc_naive_cluster": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int, ctypes.c_int,

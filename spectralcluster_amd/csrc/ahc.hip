@@ -12,7 +12,10 @@
 //     inherently sequential (about 3 n steps); each step is a coalesced scan of one row of
 //     the n x n distance matrix (first index of the minimum, the previous chain element wins
 //     ties, exactly scipy's loop) or a Lance-Williams update of one row + column;
-//   * the O(n log n) tree bookkeeping (sort, relabel, heap cut) runs on the host in callers_api.hip.
+//   * the O(n log n) tree bookkeeping (sort, relabel, heap cut) runs on the host: ahc_tree.cpp;
+//   * a stream pool (pool_api.hip) runs the three device steps for all its sessions in one launch
+//     each: k_pool_cosine_distance, k_ahc_nn_chain_pool (a workgroup per session),
+//     k_pool_centroids.
 #include <hip/hip_runtime.h>
 
 #include "sc_internal.h"
@@ -62,13 +65,12 @@ __device__ __forceinline__ void block_argmin(double& v, int& idx, double* s_val,
 
 // method 1: complete linkage (max), 2: average linkage (size-weighted mean).
 // Z[k] = (x, y, height, size) in merge order, x < y slot indices (slot y keeps the cluster).
-__global__ __launch_bounds__(kAhcThreads) void k_ahc_nn_chain(double* __restrict__ D, int ld,
-                                                              int n, int method,
-                                                              int* __restrict__ size,
-                                                              int* __restrict__ chain,
-                                                              double* __restrict__ Z) {
-  __shared__ double s_val[kAhcThreads / 64];
-  __shared__ int s_idx[kAhcThreads / 64];
+// The whole chain of one problem on the calling workgroup (kAhcThreads threads); n >= 2.
+__device__ __forceinline__ void ahc_nn_chain_body(double* __restrict__ D, int ld, int n,
+                                                  int method, int* __restrict__ size,
+                                                  int* __restrict__ chain,
+                                                  double* __restrict__ Z, double* s_val,
+                                                  int* s_idx) {
   const int tid = threadIdx.x;
   const double inf = __builtin_huge_val();
   for (int i = tid; i < n; i += kAhcThreads) size[i] = 1;
@@ -146,15 +148,52 @@ __global__ __launch_bounds__(kAhcThreads) void k_ahc_nn_chain(double* __restrict
   }
 }
 
+__global__ __launch_bounds__(kAhcThreads) void k_ahc_nn_chain(double* __restrict__ D, int ld,
+                                                              int n, int method,
+                                                              int* __restrict__ size,
+                                                              int* __restrict__ chain,
+                                                              double* __restrict__ Z) {
+  __shared__ double s_val[kAhcThreads / 64];
+  __shared__ int s_idx[kAhcThreads / 64];
+  ahc_nn_chain_body(D, ld, n, method, size, chain, Z, s_val, s_idx);
+}
+
+// ---- stream pool: the same three steps for every session of a step in one launch each ----
+// (PoolSlabs, sc_internal.h; position z of the launch works on slot slots[z] with rows[z] rows)
+__global__ __launch_bounds__(256) void k_pool_cosine_distance(const PoolSlabs p,
+                                                              const int* __restrict__ slots,
+                                                              const int* __restrict__ rows) {
+  const int n = rows[blockIdx.z];
+  const int row = blockIdx.y;
+  const int col = blockIdx.x * 256 + threadIdx.x;
+  if (row >= n || col >= n) return;
+  double* c = p.D + (size_t)slots[blockIdx.z] * p.stride_d;
+  double v = c[(size_t)row * p.ldd + col];
+  v = v > 1.0 ? 1.0 : (v < -1.0 ? -1.0 : v);
+  c[(size_t)row * p.ldd + col] = 1.0 - v;
+}
+
+// One persistent workgroup per session: sessions of different sizes share the launch, each
+// workgroup runs its own chain to the end.
+__global__ __launch_bounds__(kAhcThreads) void k_ahc_nn_chain_pool(const PoolSlabs p,
+                                                                   const int* __restrict__ slots,
+                                                                   const int* __restrict__ rows,
+                                                                   int method) {
+  __shared__ double s_val[kAhcThreads / 64];
+  __shared__ int s_idx[kAhcThreads / 64];
+  const int b = blockIdx.x;
+  const int n = rows[b];
+  if (n < 2) return;
+  ahc_nn_chain_body(p.D + (size_t)slots[b] * p.stride_d, p.ldd, n, method,
+                    p.size + (size_t)b * p.stride_n, p.chain + (size_t)b * p.stride_n,
+                    p.Z + (size_t)b * p.stride_z, s_val, s_idx);
+}
+
 // utils.get_cluster_centroids: out[c][f] = mean over members (rows in index order, the
 // order np.mean(axis=0) adds them) of X[i][f]
-__global__ __launch_bounds__(256) void k_cluster_centroids(const double* __restrict__ X, int ldx,
-                                                           int n, int d,
-                                                           const int* __restrict__ labels,
-                                                           double* __restrict__ out) {
-  const int c = blockIdx.y;
-  const int f = blockIdx.x * 256 + threadIdx.x;
-  if (f >= d) return;
+__device__ __forceinline__ double cluster_centroid_value(const double* __restrict__ X, int ldx,
+                                                         int n, const int* __restrict__ labels,
+                                                         int c, int f) {
   double acc = 0.0;
   int count = 0;
   for (int i = 0; i < n; ++i) {
@@ -163,8 +202,31 @@ __global__ __launch_bounds__(256) void k_cluster_centroids(const double* __restr
       ++count;
     }
   }
-  out[(size_t)c * d + f] = acc / (double)count;  // empty cluster: 0 / 0 = NaN, as np.mean
+  return acc / (double)count;  // empty cluster: 0 / 0 = NaN, as np.mean
 }
+
+__global__ __launch_bounds__(256) void k_pool_centroids(const PoolSlabs p,
+                                                        const int* __restrict__ slots,
+                                                        const int* __restrict__ rows) {
+  const int z = blockIdx.z;
+  const int c = blockIdx.y;
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= p.d) return;
+  const int slot = slots[z];
+  p.cent[(size_t)slot * p.stride_c + (size_t)c * p.d + f] = cluster_centroid_value(
+      p.X + (size_t)slot * p.stride_x, p.ldx, rows[z], p.labels + (size_t)z * p.stride_n, c, f);
+}
+
+__global__ __launch_bounds__(256) void k_cluster_centroids(const double* __restrict__ X, int ldx,
+                                                           int n, int d,
+                                                           const int* __restrict__ labels,
+                                                           double* __restrict__ out) {
+  const int c = blockIdx.y;
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= d) return;
+  out[(size_t)c * d + f] = cluster_centroid_value(X, ldx, n, labels, c, f);
+}
+
 
 void launch_cosine_distance(hipStream_t s, double* c, int n, int ld) {
   hipLaunchKernelGGL(k_cosine_distance, dim3((n + 255) / 256, n), dim3(256), 0, s, c, n, ld);
@@ -178,6 +240,21 @@ void launch_cluster_centroids(hipStream_t s, const double* X, int ldx, int n, in
                               const int* labels, int k, double* out) {
   hipLaunchKernelGGL(k_cluster_centroids, dim3((d + 255) / 256, k), dim3(256), 0, s, X, ldx, n,
                      d, labels, out);
+}
+void launch_pool_cosine_distance(hipStream_t s, const PoolSlabs& p, const int* slots,
+                                 const int* rows, int count, int max_rows) {
+  hipLaunchKernelGGL(k_pool_cosine_distance, dim3((max_rows + 255) / 256, max_rows, count),
+                     dim3(256), 0, s, p, slots, rows);
+}
+void launch_pool_nn_chain(hipStream_t s, const PoolSlabs& p, const int* slots, const int* rows,
+                          int count, int method) {
+  hipLaunchKernelGGL(k_ahc_nn_chain_pool, dim3(count), dim3(kAhcThreads), 0, s, p, slots, rows,
+                     method);
+}
+void launch_pool_centroids(hipStream_t s, const PoolSlabs& p, const int* slots, const int* rows,
+                           int count, int k) {
+  hipLaunchKernelGGL(k_pool_centroids, dim3((p.d + 255) / 256, k, count), dim3(256), 0, s, p,
+                     slots, rows);
 }
 
 }  // namespace sc

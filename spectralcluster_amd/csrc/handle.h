@@ -260,6 +260,10 @@ bool array_is_host_f64_rows(const sc_array& a);
 // sc_set_embeddings for a described source, on `stream` (nullptr: the handle's): sizes the
 // arena, sets the problem, widens the rows into h->X; `sync` waits for the stream
 int ingest_embeddings(sc_handle h, const sc_array& a, bool sync, hipStream_t stream = nullptr);
+// its copy / widening step alone, into any buffer of row pitch ldx doubles (the stream pool's
+// staging rows): *sync is set when the caller must wait for s before the source may go
+int ingest_rows_into(sc_handle h, const sc_array& a, double* X, int ldx, hipStream_t s,
+                     bool* sync);
 // the bodies of sc_predict_batch_streams / sc_predict_batch_grouped on described sources
 int predict_batch_streams_impl(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
                                const sc_config* cfg, int64_t* const* labels, sc_diag* diags,

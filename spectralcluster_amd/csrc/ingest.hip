@@ -189,10 +189,23 @@ int ingest_embeddings(sc_handle h, const sc_array& a, bool sync, hipStream_t str
   h->have_affinity = h->have_cropval = false;
   h->have_x = false;
   h->n_vec = 0;
-  double* X = ptr<double>(h->X);
+  SC_TRY(ingest_rows_into(h, a, ptr<double>(h->X), h->ldx, s, &sync));
+  if (sync) SC_HIP(h, hipStreamSynchronize(s));
+  h->have_x = true;
+  return SC_OK;
+}
+
+// The rows of a validated source, widened, into X (row pitch ldx doubles) on stream s; nothing
+// else of the handle changes.  *sync is set when the source was packed into a local, so the
+// caller must wait for s before it returns.  (A host fp64 source leaves the columns d..ldx of
+// X as they were; every other source zeroes them.)
+int ingest_rows_into(sc_handle h, const sc_array& a, double* X, int ldx, hipStream_t s,
+                     bool* sync_out) {
+  const int n = (int)a.rows, d = (int)a.cols;
+  bool sync = false;
   const size_t eb = dtype_bytes(a.dtype);
   if (a.location == SC_MEM_DEVICE) {
-    launch_ingest_rows(s, a.dtype, a.data, a.row_stride, a.col_stride, n, d, X, h->ldx);
+    launch_ingest_rows(s, a.dtype, a.data, a.row_stride, a.col_stride, n, d, X, ldx);
     SC_TRY(check_last(h, "ingest launch"));
   } else {
     std::vector<unsigned char> packed;
@@ -206,7 +219,7 @@ int ingest_embeddings(sc_handle h, const sc_array& a, bool sync, hipStream_t str
     }
     if (n == 1) spitch = (size_t)d * eb;
     if (a.dtype == SC_DTYPE_F64) {
-      SC_HIP(h, hipMemcpy2DAsync(X, (size_t)h->ldx * sizeof(double), src, spitch,
+      SC_HIP(h, hipMemcpy2DAsync(X, (size_t)ldx * sizeof(double), src, spitch,
                                  (size_t)d * sizeof(double), n, hipMemcpyHostToDevice, s));
     } else {
       // staging rows on a 16-byte pitch (the kernel's wide loads); sized with the X buffer, so
@@ -219,12 +232,11 @@ int ingest_embeddings(sc_handle h, const sc_array& a, bool sync, hipStream_t str
       }
       SC_HIP(h, hipMemcpy2DAsync(h->Xstage.p, pitch, src, spitch, (size_t)d * eb, n,
                                  hipMemcpyHostToDevice, s));
-      launch_ingest_rows(s, a.dtype, h->Xstage.p, (long long)(pitch / eb), 1, n, d, X, h->ldx);
+      launch_ingest_rows(s, a.dtype, h->Xstage.p, (long long)(pitch / eb), 1, n, d, X, ldx);
       SC_TRY(check_last(h, "ingest launch"));
     }
   }
-  if (sync) SC_HIP(h, hipStreamSynchronize(s));
-  h->have_x = true;
+  if (sync) *sync_out = true;
   return SC_OK;
 }
 

@@ -47,13 +47,11 @@ __device__ __forceinline__ double block_sum(double v, double* sm) {
 // keeps the order of the 256-thread form it replaces -- accumulator w of lane l adds the
 // elements 64 w + l + 256 i, each accumulator is reduced across the wave, then
 // (s0 + s1) + (s2 + s3) -- so the norms are bit-identical to it.
-__device__ __forceinline__ void normalize_rows_body(
-    const double* __restrict__ X, int ldx, int n, int d, double* __restrict__ Xn,
-    int* __restrict__ bad_rows) {
+// (one row on the calling wave: x its d values, o its ldx outputs)
+__device__ __forceinline__ void normalize_one_row(const double* __restrict__ x, int ldx, int d,
+                                                  double* __restrict__ o,
+                                                  int* __restrict__ bad_rows) {
   const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= n) return;
-  const double* x = X + (size_t)row * ldx;
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
   for (int j0 = 0; j0 < d; j0 += kRowThreads) {
 #pragma unroll
@@ -68,8 +66,34 @@ __device__ __forceinline__ void normalize_rows_body(
   // a zero (or non-finite) row turns into NaNs below, like utils.py:33; later max-type
   // kernels would drop them where np.maximum keeps them, so the fact is recorded here
   if (bad_rows != nullptr && lane == 0 && !(norm > 0.0 && isfinite(norm))) *bad_rows = 1;
-  double* o = Xn + (size_t)row * ldx;
   for (int j = lane; j < ldx; j += 64) o[j] = j < d ? x[j] / norm : 0.0;
+}
+__device__ __forceinline__ void normalize_rows_body(
+    const double* __restrict__ X, int ldx, int n, int d, double* __restrict__ Xn,
+    int* __restrict__ bad_rows) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;
+  normalize_one_row(X + (size_t)row * ldx, ldx, d, Xn + (size_t)row * ldx, bad_rows);
+}
+// ---- stream pool (sc_internal.h PoolSlabs): a step's new rows into their sessions' caches,
+//      each with its unit-norm copy beside it.  blockIdx.y = entry of the append, one wave per
+//      row; the staged row is read, never the cache row just written.
+__global__ __launch_bounds__(kRowThreads) void k_pool_append(
+    const PoolSlabs p, const double* __restrict__ stage, const PoolAppendItem* __restrict__ items) {
+  const PoolAppendItem it = items[blockIdx.y];
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= it.count) return;
+  const int lane = threadIdx.x & 63;
+  const double* x = stage + (size_t)(it.src + r) * p.ldx;
+  const size_t at = (size_t)it.slot * p.stride_x + (size_t)(it.dst + r) * p.ldx;
+  double* o = p.X + at;
+  for (int j = lane; j < p.ldx; j += 64) o[j] = j < p.d ? x[j] : 0.0;
+  normalize_one_row(x, p.ldx, p.d, p.Xn + at, nullptr);
+}
+__global__ __launch_bounds__(kRowThreads) void k_pool_renormalize(const PoolSlabs p, int slot,
+                                                                  int rows) {
+  normalize_rows_body(p.X + (size_t)slot * p.stride_x, p.ldx, rows, p.d,
+                      p.Xn + (size_t)slot * p.stride_x, nullptr);
 }
 __global__ __launch_bounds__(kRowThreads) void k_normalize_rows(
     const double* __restrict__ X, int ldx, int n, int d, double* __restrict__ Xn,
@@ -869,6 +893,15 @@ void launch_normalize_rows(hipStream_t s, const double* X, int ldx, int n, int d
                            double* Xn, int* bad_rows) {
   hipLaunchKernelGGL(k_normalize_rows, dim3((n + 3) / 4), dim3(kRowThreads), 0, s, X, ldx, n,
                      d, Xn, bad_rows);
+}
+void launch_pool_append(hipStream_t s, const PoolSlabs& p, const double* stage,
+                        const PoolAppendItem* items, int count, int max_rows) {
+  hipLaunchKernelGGL(k_pool_append, dim3((max_rows + 3) / 4, count), dim3(kRowThreads), 0, s, p,
+                     stage, items);
+}
+void launch_pool_renormalize(hipStream_t s, const PoolSlabs& p, int slot, int rows) {
+  hipLaunchKernelGGL(k_pool_renormalize, dim3((rows + 3) / 4), dim3(kRowThreads), 0, s, p, slot,
+                     rows);
 }
 void launch_crop_diagonal(hipStream_t s, const double* in, double* out, int n,
                           int ld) {

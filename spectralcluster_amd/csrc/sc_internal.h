@@ -594,6 +594,48 @@ void launch_ahc_nn_chain(hipStream_t s, double* D, int ld, int n, int method, in
                          int* chain, double* Z);
 void launch_cluster_centroids(hipStream_t s, const double* X, int ldx, int n, int d,
                               const int* labels, int k, double* out);
+// ---- stream pool (ahc.hip, rowops.hip; host side pool_api.hip) ---------------------------
+// Device slabs of a pool of streaming sessions.  What a session keeps between steps is indexed
+// by its SLOT (stride_* elements apart): cache rows X, their unit-norm copies Xn, the distance
+// matrix D, the centroids.  The scratch of one pre-cluster launch is indexed by the session's
+// POSITION in that launch: cluster sizes, chain, merge list Z, labels.  Kernels take the slot
+// list and the row-count list of the launch (device arrays), blockIdx.z or .x = position.
+struct PoolSlabs {
+  double* X;
+  double* Xn;
+  size_t stride_x;  // u2 * ldx
+  int ldx, d;
+  double* D;
+  size_t stride_d;  // u2 * ldd
+  int ldd;
+  double* cent;
+  size_t stride_c;  // u1 * d
+  int* size;
+  int* chain;
+  int* labels;
+  int stride_n;     // u2
+  double* Z;
+  size_t stride_z;  // 4 * (u2 - 1)
+};
+// one entry of an append: `count` staged rows from row `src` on go to rows `dst`.. of `slot`
+struct PoolAppendItem {
+  int slot, dst, src, count;
+};
+// cache row + its unit-norm copy (launch_normalize_rows' arithmetic) for every entry;
+// stage: rows of pitch slabs.ldx doubles, columns >= d ignored
+void launch_pool_append(hipStream_t s, const PoolSlabs& p, const double* stage,
+                        const PoolAppendItem* items, int count, int max_rows);
+// Xn rows [0, rows) of one slot again from its X rows (after a compression)
+void launch_pool_renormalize(hipStream_t s, const PoolSlabs& p, int slot, int rows);
+// D = 1 - clip(D) of every listed session (launch_cosine_distance per member)
+void launch_pool_cosine_distance(hipStream_t s, const PoolSlabs& p, const int* slots,
+                                 const int* rows, int count, int max_rows);
+// launch_ahc_nn_chain for every listed session: one workgroup each, grid = count
+void launch_pool_nn_chain(hipStream_t s, const PoolSlabs& p, const int* slots, const int* rows,
+                          int count, int method);
+// launch_cluster_centroids (k clusters) for every listed session, into the slot's centroids
+void launch_pool_centroids(hipStream_t s, const PoolSlabs& p, const int* slots, const int* rows,
+                           int count, int k);
 
 // ---- fallback decisions (fallback.hip) ---------------------------------------------------
 void launch_naive_cluster(hipStream_t s, const double* X, int n, int d, double threshold,

@@ -13,10 +13,14 @@ bookkeeping around them, plus the label de-flickering.
 
 from __future__ import annotations
 
+import ctypes
 import enum
+import typing
 
 import numpy as np
 
+from spectralcluster_amd import _dlpack
+from spectralcluster_amd import _lib
 from spectralcluster_amd import fallback_clusterer
 from spectralcluster_amd import spectral_clusterer
 from spectralcluster_amd import utils
@@ -176,22 +180,267 @@ class MultiStageClusterer:
       self.previous_output = labels
       return labels
 
-    if self.compression_labels is not None:
-      self.compression_labels = np.append(self.compression_labels,
-                                          max(self.compression_labels) + 1)
     pre_labels = self._pre_cluster(self.cache)
     pre_centroids = utils.get_cluster_centroids(self.cache, pre_labels)
     main_labels = self.main.predict(pre_centroids)
-    labels = utils.chain_labels(self.compression_labels,
-                                utils.chain_labels(pre_labels, main_labels))
-
-    if self.cache.shape[0] == self.U2:             # dynamic compression
+    compress = self.cache.shape[0] == self.U2      # dynamic compression
+    if compress:
       self.cache = pre_centroids
-      self.compression_labels = utils.chain_labels(self.compression_labels, pre_labels)
+    return finish_stream_step(self, self.deflicker, pre_labels, main_labels, compress)
 
-    if self.deflicker == Deflicker.OrderBased:
-      labels = utils.enforce_ordered_labels(labels)
-    elif self.deflicker == Deflicker.Hungarian:
-      labels = match_labels(labels, self.previous_output)
-    self.previous_output = labels
-    return labels
+
+def finish_stream_step(state, deflicker: Deflicker, pre_labels: np.ndarray,
+                       main_labels: np.ndarray, compress: bool) -> np.ndarray:
+  """The host bookkeeping of one step beyond U1, after its two clustering calls (reference
+  :150-180): the labels of every embedding of the stream from the pre-cluster labels of the
+  cache and the main labels of its centroids, chained through `state.compression_labels`
+  (original embedding -> cache row); that map extended by the new row and, when the cache is
+  being replaced by its centroids (`compress`), rewritten to point at them; the de-flickering
+  against `state.previous_output`.  `state`: a MultiStageClusterer or a session of a
+  MultiStageStreamPool -- both streams go through this one function."""
+  if state.compression_labels is not None:
+    state.compression_labels = np.append(state.compression_labels,
+                                         max(state.compression_labels) + 1)
+  labels = utils.chain_labels(state.compression_labels,
+                              utils.chain_labels(pre_labels, main_labels))
+  if compress:
+    state.compression_labels = utils.chain_labels(state.compression_labels, pre_labels)
+  if deflicker == Deflicker.OrderBased:
+    labels = utils.enforce_ordered_labels(labels)
+  elif deflicker == Deflicker.Hungarian and state.previous_output is not None:
+    labels = match_labels(labels, state.previous_output)
+  state.previous_output = labels
+  return labels
+
+
+class _PoolSession:
+  """Host state of one session of a MultiStageStreamPool (the cache itself is on the device)."""
+
+  def __init__(self):
+    self.num_embeddings = 0
+    self.mirror = None                 # host copy of the cache while it has at most U1 rows
+    self.compression_labels = None
+    self.previous_output = None
+
+
+ROUTE_MAIN_ONLY, ROUTE_POOLED_GROUPED, ROUTE_POOLED_SINGLE = range(3)
+
+
+class MultiStageStreamPool:
+  """Up to `capacity` independent MultiStageClusterer streams advanced together.
+
+  The caches live on the device (`sc_pool_*`).  One `streaming_predict(sessions, embeddings)`
+  call appends one embedding to each listed session and returns, per session, exactly what
+  that session's own `MultiStageClusterer.streaming_predict` would have returned.  Sessions
+  beyond U1 rows share their launches: one append, one distance pass, one nearest-neighbour-
+  chain launch with a workgroup per session, one centroid launch, and -- when the main
+  clusterer is one the library batch covers -- one grouped call over the resident centroid
+  buffers.  Constructor arguments as MultiStageClusterer's, plus `capacity` and `device`
+  (default: the main clusterer's).  The embedding width is fixed by the first rows a pool sees.
+  """
+
+  def __init__(self,
+               main_clusterer: spectral_clusterer.SpectralClusterer,
+               fallback_threshold: float = 0.5,
+               L: int = 50,
+               U1: int = 100,
+               U2: int = 600,
+               deflicker: Deflicker = Deflicker.NoDeflicker,
+               capacity: int = 64,
+               device: typing.Optional[int] = None,
+               d: typing.Optional[int] = None):
+    # (the option changes and the max_spectral_size check of the per-stream class)
+    MultiStageClusterer(main_clusterer, fallback_threshold, L, U1, U2, deflicker)
+    self.main = main_clusterer
+    self.deflicker = deflicker
+    self.L, self.U1, self.U2 = int(L), int(U1), int(U2)
+    self.capacity = int(capacity)
+    self.device = device if device is not None else main_clusterer.device
+    self.d = None
+    self._pool = None
+    self._sessions = {}                # id -> _PoolSession
+    self.last_routes = []
+    # All device memory is taken up front.  With `d` that is now; without it the slabs are
+    # taken when the first rows show their width, and the constructor only takes (and gives
+    # back) those of d = 1 -- the distance matrices, which do not depend on d, are most of
+    # them -- so a capacity that cannot fit raises its MemoryError here, not mid-stream.
+    with _lib.use_device(self.device):
+      self._ensure_pool(1 if d is None else int(d))
+    if d is None:
+      self._free()
+      self.d = None
+
+  # ---------------------------------------------------------------- plumbing
+  def _handle(self) -> _lib.Handle:
+    return _lib.default_handle(self.device)
+
+  def _ensure_pool(self, d: int) -> None:
+    if self._pool is not None:
+      if d != self.d:
+        raise ValueError("embeddings have %d features, the pool holds %d" % (d, self.d))
+      return
+    handle = self._handle()
+    pool = ctypes.c_void_p()
+    handle.check(handle.lib.sc_pool_create(handle.raw, self.capacity, int(d), self.U1, self.U2,
+                                           ctypes.byref(pool)))
+    self._pool, self._pool_handle, self.d = pool, handle, int(d)
+
+  def _free(self):
+    pool, self._pool = getattr(self, "_pool", None), None
+    if pool is not None and getattr(self._pool_handle, "raw", None):
+      self._pool_handle.lib.sc_pool_destroy(pool)
+
+  def __del__(self):
+    try:
+      self._free()
+    except Exception:  # interpreter shutdown
+      pass
+
+  def _session(self, session) -> _PoolSession:
+    state = self._sessions.get(session) if isinstance(session, (int, np.integer)) else None
+    if state is None:
+      raise ValueError("session %r is not open" % (session,))
+    return state
+
+  def _append(self, sessions, counts, source) -> None:
+    handle, n = self._pool_handle, len(sessions)
+    handle.check(handle.lib.sc_pool_append(
+        self._pool, (ctypes.c_int32 * n)(*[int(s) for s in sessions]),
+        (ctypes.c_int32 * n)(*counts), n, ctypes.byref(source.array)))
+
+  # ---------------------------------------------------------------- sessions
+  def open(self) -> int:
+    for slot in range(self.capacity):
+      if slot not in self._sessions:
+        self._sessions[slot] = _PoolSession()
+        if self._pool is not None:
+          self._pool_handle.check(self._pool_handle.lib.sc_pool_reset(self._pool, slot))
+        return slot
+    raise RuntimeError("all %d sessions of the pool are open" % self.capacity)
+
+  def close(self, session) -> None:
+    self._session(session)
+    del self._sessions[int(session)]
+
+  def reset(self, session) -> None:
+    self._session(session)
+    self._sessions[int(session)] = _PoolSession()
+    if self._pool is not None:
+      self._pool_handle.check(self._pool_handle.lib.sc_pool_reset(self._pool, int(session)))
+
+  def load(self, session, rows) -> None:
+    """Append `rows` (anything streaming_predict takes, (k, d)) to the session's cache without
+    clustering them: resumes a stream.  Only while the cache stays within U2 rows and has not
+    been compressed yet (ValueError otherwise); the next step has no previous output to
+    de-flicker against."""
+    state = self._session(session)
+    with _lib.use_device(self.device):
+      source = _dlpack.describe(rows, self._handle)
+      try:
+        k, d = source.shape
+        if state.compression_labels is not None or state.num_embeddings + k > self.U2:
+          raise ValueError("load() needs an uncompressed cache that stays within U2 = %d rows"
+                           % self.U2)
+        self._ensure_pool(d)
+        self._append([session], [k], source)
+        total = state.num_embeddings + k
+        if total <= self.U1:
+          host = np.asarray(source.host_f64(self._pool_handle), dtype=np.float64)
+          state.mirror = host.copy() if state.mirror is None else np.vstack([state.mirror, host])
+        else:
+          state.mirror = None
+        state.num_embeddings = total
+        state.previous_output = None
+      finally:
+        source.release()
+
+  # -------------------------------------------------------------------- step
+  def streaming_predict(self, sessions: typing.Sequence[int],
+                        embeddings) -> typing.List[np.ndarray]:
+    """One step of every listed session (distinct ids): row i of `embeddings`
+    ((len(sessions), d); NumPy or DLPack, float64 / float32 / float16 / bfloat16, host or
+    device) is the next embedding of sessions[i].  Element i of the result is what that
+    stream's MultiStageClusterer.streaming_predict would return, values and dtype.
+    `last_routes`: per session, 0 main.predict on its own (at most U1 rows), 1 pooled
+    pre-cluster + the grouped main call, 2 pooled pre-cluster + a main.predict of its own."""
+    sessions = [int(s) if isinstance(s, (int, np.integer)) else s for s in sessions]
+    states = [self._session(s) for s in sessions]
+    if len(set(sessions)) != len(sessions):
+      raise ValueError("a session is listed twice")
+    if not sessions:
+      self.last_routes = []
+      return []
+    with _lib.use_device(self.device):
+      source = _dlpack.describe(embeddings, self._handle)
+      try:
+        if source.shape[0] != len(sessions):
+          raise ValueError("embeddings must be (len(sessions), d)")
+        self._ensure_pool(source.shape[1])
+        self._append(sessions, [1] * len(sessions), source)
+        host = None
+        if any(st.num_embeddings < self.U1 for st in states):
+          host = np.asarray(source.host_f64(self._pool_handle), dtype=np.float64)
+      finally:
+        source.release()
+      return self._step(sessions, states, host)
+
+  def _step(self, sessions, states, host) -> typing.List[np.ndarray]:
+    handle = self._pool_handle
+    out = [None] * len(sessions)
+    routes = [ROUTE_MAIN_ONLY] * len(sessions)
+    pooled = []
+    for i, st in enumerate(states):
+      st.num_embeddings += 1
+      if st.num_embeddings <= self.U1:
+        row = host[i:i + 1]
+        st.mirror = row.copy() if st.mirror is None else np.vstack([st.mirror, row])
+        if st.num_embeddings == 1:
+          out[i] = np.array([0])
+        else:
+          out[i] = self.main.predict(st.mirror)   # fallback or main clusterer only
+        st.previous_output = out[i]
+      else:
+        st.mirror = None
+        pooled.append(i)
+    if pooled:
+      count = len(pooled)
+      slots = (ctypes.c_int32 * count)(*[sessions[i] for i in pooled])
+      pre = [np.empty(handle.lib.sc_pool_rows(self._pool, sessions[i]), dtype=np.int64)
+             for i in pooled]
+      handle.check(handle.lib.sc_pool_precluster(
+          self._pool, slots, count,
+          (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in pre])))
+      if self._main_is_batchable():
+        arrays = []
+        for i in pooled:
+          arrays.append(_lib.ScArray())
+          handle.check(handle.lib.sc_pool_centroids(self._pool, sessions[i],
+                                                    ctypes.byref(arrays[-1])))
+        main = self.main.predict_device_batch(arrays)
+        route = ROUTE_POOLED_GROUPED
+      else:
+        main = []
+        for i in pooled:
+          centroids = np.empty((self.U1, self.d), dtype=np.float64)
+          handle.check(handle.lib.sc_pool_get(self._pool, sessions[i], _lib.SC_POOL_CENTROIDS,
+                                              _lib.as_double_p(centroids)))
+          main.append(self.main.predict(centroids))
+        route = ROUTE_POOLED_SINGLE
+      for i, pre_labels, main_labels in zip(pooled, pre, main):
+        compress = pre_labels.shape[0] == self.U2   # dynamic compression, on the device
+        if compress:
+          handle.check(handle.lib.sc_pool_compress(self._pool, sessions[i]))
+        out[i] = finish_stream_step(states[i], self.deflicker, pre_labels, main_labels, compress)
+        routes[i] = route
+    self.last_routes = routes
+    return out
+
+  def _main_is_batchable(self) -> bool:
+    """predict_batch's conditions; spectral_min_embeddings (= L) is met by the U1 centroids."""
+    if not self.main._library_batch_covers(min_embeddings_met=self.L <= self.U1):
+      return False
+    try:
+      _lib.kmeans_metric_code(self.main.custom_dist)
+    except (ValueError, NotImplementedError):
+      return False   # main.predict raises what it raises today
+    return True

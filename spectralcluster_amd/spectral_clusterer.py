@@ -428,11 +428,7 @@ class SpectralClusterer:
     launched.  Anything else -- a dense ndarray among the entries, AutoTune (the Turn-to-Diarize
     preset), group=1, `streams` -- runs as per-utterance `predict(u, c)` calls (routes all 0).
     """
-    library_batch = not (
-        self.autotune is not None or self.max_spectral_size is not None or
-        self.min_clusters == 1 or self.fallback_options.spectral_min_embeddings > 1 or
-        self.affinity_function is not utils.compute_affinity_matrix or
-        self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans)
+    library_batch = self._library_batch_covers()
     banded = None  # the ConstraintMatrix (or None) of every utterance of a constrained batch
     if constraint_matrices is not None:
       if len(constraint_matrices) != len(utterances):
@@ -514,13 +510,39 @@ class SpectralClusterer:
               handle.raw, xp, ns, d, count, self.build_config(), lp, diags,
               max(1, int(streams))), TypeError)
       else:
-        arrays = (_lib.ScArray * count)(*[src.array for src in sources])
-        handle.check(handle.lib.sc_predict_batch_arrays(
-            handle.raw, arrays, count, self.build_config(), lp, diags, int(group),
-            max(1, int(streams))), TypeError)
+        self._batch_arrays_call(handle, [src.array for src in sources], labels, diags,
+                                int(group), max(1, int(streams)))
     finally:
       for src in sources:
         src.release()
+    self._batch_report(handle, diags, count)
+    return labels
+
+  def _library_batch_covers(self, min_embeddings_met: bool = False) -> bool:
+    """Is this clusterer one whose predict() the library batch calls reproduce?  (What is not:
+    AutoTune, size reduction, the fallback decisions, user-supplied functions -- those go
+    through predict().)  `min_embeddings_met`: the caller knows every utterance to hold at
+    least `fallback_options.spectral_min_embeddings` rows (the centroids of a stream pool)."""
+    return not (
+        self.autotune is not None or self.max_spectral_size is not None or
+        self.min_clusters == 1 or
+        (self.fallback_options.spectral_min_embeddings > 1 and not min_embeddings_met) or
+        self.affinity_function is not utils.compute_affinity_matrix or
+        self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans)
+
+  def _batch_arrays_call(self, handle: _lib.Handle, arrays: typing.Sequence[_lib.ScArray],
+                         labels: typing.Sequence[np.ndarray], diags, group: int,
+                         streams: int) -> None:
+    """One `sc_predict_batch_arrays` call on described sources (host or device memory) into
+    the given int64 label arrays and `sc_diag` array."""
+    count = len(arrays)
+    lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
+    handle.check(handle.lib.sc_predict_batch_arrays(
+        handle.raw, (_lib.ScArray * count)(*arrays), count, self.build_config(), lp, diags,
+        group, streams), TypeError)
+
+  def _batch_report(self, handle: _lib.Handle, diags, count: int) -> None:
+    """`last_batch_diags` / `last_batch_routes` after a library batch call."""
     self.last_batch_diags = list(diags)
     # The library always exports the report (_lib.load() fails without it).  Only a stand-in
     # handle lacks it -- tests/test_host_logic.py drives this method with one that has the two
@@ -531,4 +553,18 @@ class SpectralClusterer:
       routes = (ctypes.c_int32 * count)()
       handle.check(report(handle.raw, routes, count))
       self.last_batch_routes = [int(r) for r in routes]
+
+  def predict_device_batch(self, arrays: typing.Sequence[_lib.ScArray],
+                           group: int = 16) -> typing.List[np.ndarray]:
+    """predict_batch for utterances that are already described (`sc_array`s, e.g. the resident
+    centroid buffers of a stream pool) on a clusterer `_library_batch_covers`: one grouped
+    library call, `last_batch_routes` / `last_batch_diags` as after predict_batch."""
+    _lib.kmeans_metric_code(self.custom_dist)  # raises for metrics that are not on the device
+    count = len(arrays)
+    labels = [np.empty(int(a.rows), dtype=np.int64) for a in arrays]
+    handle = self._handle()
+    handle.check(handle.lib.sc_clear_constraint(handle.raw))  # a batch carries none
+    diags = (_lib.ScDiag * count)()
+    self._batch_arrays_call(handle, arrays, labels, diags, int(group), 1)
+    self._batch_report(handle, diags, count)
     return labels
