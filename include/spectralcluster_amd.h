@@ -525,6 +525,21 @@ int sc_pool_append(sc_pool pool, const int32_t* slots, const int32_t* counts, in
 int sc_pool_precluster(sc_pool pool, const int32_t* slots, int count, int64_t* const* labels_out);
 /* device descriptor (u1 x d, float64) of the centroids the last sc_pool_precluster left */
 int sc_pool_centroids(sc_pool pool, int slot, sc_array* out);
+/* The agglomerative fallback of a stream that is still short (fallback_clusterer.py:108-113):
+ * average-linkage cosine clustering of every listed slot's cache, cut at distance_threshold.
+ * labels_out[i] receives the rows(slots[i]) labels: what sc_ahc(x, n, d, SC_LINKAGE_AVERAGE,
+ * n_clusters = 0, distance_threshold) returns for those rows; a slot of one row gets label 0.
+ * One distance pass and one linkage launch for all slots of up to 128 rows (the distance matrix
+ * of each in LDS, a wavefront per slot); larger ones share the pre-clusterer's two kernels in the
+ * same call.  Computes no centroids and leaves those of sc_pool_precluster as they are.
+ * SC_ERR_INVALID, before anything is launched, for a slot without rows, a slot listed twice or a
+ * NULL argument. */
+int sc_pool_fallback(sc_pool pool, const int32_t* slots, int count, double distance_threshold,
+                     int64_t* const* labels_out);
+/* device descriptor (rows(slot) x d, float64, row_stride = d rounded up to 16) of the slot's
+ * cache itself, the twin of sc_pool_centroids: valid until the slot is next appended to,
+ * compressed or reset.  SC_ERR_INVALID for a slot without rows. */
+int sc_pool_cache(sc_pool pool, int slot, sc_array* out);
 /* what = SC_POOL_CACHE: the rows(slot) x d cache; SC_POOL_CENTROIDS: the u1 x d centroids */
 int sc_pool_get(sc_pool pool, int slot, int what, double* out);
 /* dynamic compression: the cache of slot becomes its u1 centroids (copied on the device) */

@@ -269,6 +269,9 @@ PROTOTYPES = {
     "sc_pool_precluster": (ctypes.c_int, [_handle_t, ctypes.POINTER(ctypes.c_int32),
                                           ctypes.c_int, ctypes.POINTER(_c_int64_p)]),
     "sc_pool_centroids": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.POINTER(ScArray)]),
+    "sc_pool_fallback": (ctypes.c_int, [_handle_t, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
+                                        ctypes.c_double, ctypes.POINTER(_c_int64_p)]),
+    "sc_pool_cache": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.POINTER(ScArray)]),
     "sc_pool_get": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.c_int, _c_double_p]),
     "sc_pool_compress": (ctypes.c_int, [_handle_t, ctypes.c_int]),
     "sc_affinity_stats": (ctypes.c_int, [_handle_t, _c_double_p]),

@@ -15,9 +15,11 @@
 //   * the O(n log n) tree bookkeeping (sort, relabel, heap cut) runs on the host: ahc_tree.cpp;
 //   * a stream pool (pool_api.hip) runs the three device steps for all its sessions in one launch
 //     each: k_pool_cosine_distance, k_ahc_nn_chain_pool (a workgroup per session),
-//     k_pool_centroids.
+//     k_pool_centroids; its fallback stage (sessions of up to 128 rows, average linkage) runs the
+//     first two as k_pool_linkage_lds: the distance matrix in LDS, a wavefront per session.
 #include <hip/hip_runtime.h>
 
+#include "dpp.h"
 #include "sc_internal.h"
 
 namespace sc {
@@ -189,6 +191,151 @@ __global__ __launch_bounds__(kAhcThreads) void k_ahc_nn_chain_pool(const PoolSla
                     p.Z + (size_t)b * p.stride_z, s_val, s_idx);
 }
 
+#if SC_POOL_LDS_LINKAGE_MAX > 0
+// ---- stream pool, short sessions: the distance matrix in LDS, one wavefront per session ----
+// A session of n <= kPoolLdsLinkageMax rows (the fallback stage of a stream: n < L) is about
+// 3 n strictly dependent steps on a matrix of a few KB.  k_ahc_nn_chain_pool pays a global-memory
+// row read, two 1024-thread reductions and four barriers for each of them; here the matrix, the
+// cluster sizes and the chain stay in LDS, a lane scans columns lane and lane + 64, and the
+// argmin is a DPP reduction inside the wave.  The arithmetic and every tie rule are
+// ahc_nn_chain_body's (method 2), so the merge list is the one k_pool_cosine_distance +
+// k_ahc_nn_chain_pool write for the same GEMM output, bit for bit.
+
+// (value, index) minimum over the wave, in every lane: smallest value, then smallest index.
+// The order of the combining steps does not matter: the pairs are totally ordered.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ void argmin_step(double& v, int& idx) {
+  const double ov = dpp_f64<CTRL, ROW_MASK>(v, v);
+  const int oi = dpp_i32<CTRL, ROW_MASK>(idx, idx);
+  if (ov < v || (ov == v && oi < idx)) {
+    v = ov;
+    idx = oi;
+  }
+}
+__device__ __forceinline__ void wave_argmin(double& v, int& idx) {
+  argmin_step<kDppRowShr1, 0xf>(v, idx);
+  argmin_step<kDppRowShr2, 0xf>(v, idx);
+  argmin_step<kDppRowShr4, 0xf>(v, idx);
+  argmin_step<kDppRowShr8, 0xf>(v, idx);
+  argmin_step<kDppRowBcast15, 0xa>(v, idx);
+  argmin_step<kDppRowBcast31, 0xc>(v, idx);
+  const long long b = __double_as_longlong(v);  // lane 63 holds the wave's minimum
+  const int lo = __builtin_amdgcn_readlane((int)b, 63);
+  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), 63);
+  v = __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+  idx = __builtin_amdgcn_readlane(idx, 63);
+}
+
+// Workgroup blockIdx.x works on position first + blockIdx.x of the launch's lists.  The dynamic
+// LDS is sized for the largest session of the launch (pool_linkage_lds_bytes); a session lays
+// its matrix out with its own odd pitch n | 1.
+__global__ __launch_bounds__(64) void k_pool_linkage_lds(const PoolSlabs p,
+                                                         const int* __restrict__ slots,
+                                                         const int* __restrict__ rows,
+                                                         int first) {
+  extern __shared__ __attribute__((aligned(16))) double lds_d[];
+  const int b = first + blockIdx.x;
+  const int n = rows[b];
+  if (n < 2 || n > kPoolLdsLinkageMax) return;
+  const int lane = threadIdx.x;
+  const int pitch = n | 1;  // odd: a column walk touches every bank pair once
+  double* D = lds_d;                                   // n x pitch
+  int* size = reinterpret_cast<int*>(D + n * pitch);   // n
+  int* chain = size + n;                               // n
+  double* Z = p.Z + (size_t)b * p.stride_z;
+  const double inf = __builtin_huge_val();
+  {  // the GEMM's cosines -> distances (k_pool_cosine_distance's expression)
+    const double* c = p.D + (size_t)slots[b] * p.stride_d;
+    for (int e = lane; e < n * n; e += 64) {
+      const int i = e / n, j = e - i * n;
+      double v = c[(size_t)i * p.ldd + j];
+      v = v > 1.0 ? 1.0 : (v < -1.0 ? -1.0 : v);
+      D[i * pitch + j] = 1.0 - v;
+    }
+  }
+  const int i0 = lane, i1 = lane + 64;  // the two columns of this lane
+  if (i0 < n) size[i0] = 1;
+  if (i1 < n) size[i1] = 1;
+  __syncthreads();
+  int chain_len = 0;
+  for (int k = 0; k < n - 1; ++k) {
+    if (chain_len == 0) {  // first slot that is still a cluster
+      int f = 0x7fffffff;
+      if (i1 < n && size[i1] > 0) f = i1;
+      if (i0 < n && size[i0] > 0) f = i0;
+      double fv = (double)f;
+      wave_argmin(fv, f);
+      if (lane == 0) chain[0] = f;
+      chain_len = 1;
+      __syncthreads();
+    }
+    int x, y;
+    double cur;
+    while (true) {
+      x = chain[chain_len - 1];
+      const int y0 = chain_len > 1 ? chain[chain_len - 2] : -1;
+      const double* row = D + x * pitch;
+      cur = y0 >= 0 ? row[y0] : inf;
+      double best = inf;
+      int besti = 0x7fffffff;
+      if (i0 < n && size[i0] > 0 && i0 != x) {
+        const double v = row[i0];
+        if (v < best) {
+          best = v;
+          besti = i0;
+        }
+      }
+      if (i1 < n && size[i1] > 0 && i1 != x) {
+        const double v = row[i1];
+        if (v < best) {
+          best = v;
+          besti = i1;
+        }
+      }
+      wave_argmin(best, besti);
+      y = y0;
+      if (best < cur) {
+        cur = best;
+        y = besti;
+      }
+      if (chain_len > 1 && y == y0) break;
+      if (lane == 0) chain[chain_len] = y;
+      ++chain_len;
+      __syncthreads();
+    }
+    chain_len -= 2;
+    if (x > y) {
+      const int t = x;
+      x = y;
+      y = t;
+    }
+    const int nx = size[x], ny = size[y];
+    __syncthreads();  // every lane has read the sizes
+    if (lane == 0) {
+      Z[(size_t)k * 4 + 0] = (double)x;
+      Z[(size_t)k * 4 + 1] = (double)y;
+      Z[(size_t)k * 4 + 2] = cur;
+      Z[(size_t)k * 4 + 3] = (double)(nx + ny);
+      size[x] = 0;
+      size[y] = nx + ny;
+    }
+    const double* rx = D + x * pitch;
+    double* ry = D + y * pitch;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int i = lane + 64 * h;
+      if (i >= n || i == x || i == y) continue;
+      if (size[i] <= 0) continue;  // x and y are excluded above, the rest is unchanged
+      const double dx = rx[i], dy = ry[i];
+      const double nv = ((double)nx * dx + (double)ny * dy) / (double)(nx + ny);
+      ry[i] = nv;
+      D[i * pitch + y] = nv;
+    }
+    __syncthreads();
+  }
+}
+#endif  // SC_POOL_LDS_LINKAGE_MAX > 0
+
 // utils.get_cluster_centroids: out[c][f] = mean over members (rows in index order, the
 // order np.mean(axis=0) adds them) of X[i][f]
 __device__ __forceinline__ double cluster_centroid_value(const double* __restrict__ X, int ldx,
@@ -251,6 +398,20 @@ void launch_pool_nn_chain(hipStream_t s, const PoolSlabs& p, const int* slots, c
   hipLaunchKernelGGL(k_ahc_nn_chain_pool, dim3(count), dim3(kAhcThreads), 0, s, p, slots, rows,
                      method);
 }
+#if SC_POOL_LDS_LINKAGE_MAX > 0
+static_assert(kPoolLdsLinkageMax <= 128, "k_pool_linkage_lds: a lane scans two columns");
+static size_t pool_linkage_lds_bytes(int n) {
+  return (size_t)n * (n | 1) * sizeof(double) + 2 * (size_t)n * sizeof(int);
+}
+void launch_pool_linkage_lds(hipStream_t s, const PoolSlabs& p, const int* slots, const int* rows,
+                             int first, int count, int max_rows) {
+  // 128 rows: 128 * 129 * 8 B + 1 KB = 130 KB of the CU's 160 KB
+  SC_OPT_IN_LDS(k_pool_linkage_lds, pool_linkage_lds_bytes(kPoolLdsLinkageMax));
+  hipLaunchKernelGGL(k_pool_linkage_lds, dim3(count), dim3(64),
+                     pool_linkage_lds_bytes(std::min(max_rows, kPoolLdsLinkageMax)), s, p, slots,
+                     rows, first);
+}
+#endif
 void launch_pool_centroids(hipStream_t s, const PoolSlabs& p, const int* slots, const int* rows,
                            int count, int k) {
   hipLaunchKernelGGL(k_pool_centroids, dim3((p.d + 255) / 256, k, count), dim3(256), 0, s, p,

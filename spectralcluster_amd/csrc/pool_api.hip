@@ -8,6 +8,10 @@
 //               + 1 copy back (all merge lists) + 1 synchronisation
 //               + the tree cuts on the handle's host workers (ahc_tree.cpp)
 //               + 1 copy (all labels) + k_pool_centroids
+//   fallback    the same copies, GEMMs, synchronisation and tree cuts (average linkage, cut at a
+//               distance threshold, no centroids); the linkage of the sessions of up to
+//               SC_POOL_LDS_LINKAGE_MAX rows is k_pool_linkage_lds (grid = S, the distance pass
+//               included), larger ones take the two kernels of the pre-clusterer
 // whatever S is.  Kernels: ahc.hip, rowops.hip.
 #include "ahc_tree.h"
 #include "handle.h"
@@ -226,6 +230,64 @@ extern "C" int sc_pool_append(sc_pool pool, const int32_t* slots, const int32_t*
   return SC_OK;
 }
 
+// What sc_pool_precluster and sc_pool_fallback share: the sessions of the call are the `count`
+// (slot, rows) entries of h_lists, position by position.  One copy of the lists, the grouped
+// Xn Xn^T products kGroupMax sessions per launch, the linkage of every session, one copy back of
+// the merge lists (z_doubles of each session's stride_z), one synchronisation; on return h_Z
+// holds them and the handle's host workers exist.  Positions [0, n_chain) (at most chain_rows
+// rows) take k_pool_cosine_distance + k_ahc_nn_chain_pool with `method`; positions
+// [n_chain, count) (at most lds_rows rows, average linkage) take k_pool_linkage_lds.
+static int pool_linkage(sc_pool pool, int count, int n_chain, int chain_rows, int lds_rows,
+                        int method, size_t z_doubles, const char* what) {
+  sc_handle h = pool->h;
+  const PoolSlabs& sl = pool->slabs;
+  SC_HIP(h, hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  int* slots_d = pool->lists;
+  int* rows_d = pool->lists + pool->capacity;
+  SC_HIP(h, hipMemcpyAsync(pool->lists, pool->h_lists, 2 * (size_t)pool->capacity * sizeof(int),
+                           hipMemcpyHostToDevice, s));
+  // cosine distances: sc_ahc's unit rows and symmetric product (whole K per tile, as its
+  // single-call plan runs a product of this size), 16 sessions per launch, then 1 - clip
+  for (int base = 0; base < count; base += kGroupMax) {
+    GemmGroupItem items[kGroupMax];
+    const int cnt = std::min(kGroupMax, count - base);
+    for (int z = 0; z < cnt; ++z) {
+      const size_t slot = (size_t)pool->h_lists[base + z];
+      items[z].A = sl.Xn + slot * sl.stride_x;
+      items[z].lda = sl.ldx;
+      items[z].C = sl.D + slot * sl.stride_d;
+      items[z].ldc = sl.ldd;
+      items[z].n = pool->rows[slot];
+      items[z].K = pool->d;
+    }
+    launch_gemm_nt_group(s, items, cnt, kEpiNone, 0);
+  }
+  if (n_chain > 0) {
+    launch_pool_cosine_distance(s, sl, slots_d, rows_d, n_chain, chain_rows);
+    launch_pool_nn_chain(s, sl, slots_d, rows_d, n_chain, method);
+  }
+#if SC_POOL_LDS_LINKAGE_MAX > 0
+  if (count > n_chain)
+    launch_pool_linkage_lds(s, sl, slots_d, rows_d, n_chain, count - n_chain, lds_rows);
+#endif
+  SC_TRY(check_last(h, what));
+  if (z_doubles == sl.stride_z)
+    SC_HIP(h, hipMemcpyAsync(pool->h_Z, sl.Z, (size_t)count * sl.stride_z * sizeof(double),
+                             hipMemcpyDeviceToHost, s));
+  else  // short sessions: the head of every merge list
+    SC_HIP(h, hipMemcpy2DAsync(pool->h_Z, sl.stride_z * sizeof(double), sl.Z,
+                               sl.stride_z * sizeof(double), z_doubles * sizeof(double), count,
+                               hipMemcpyDeviceToHost, s));
+  SC_HIP(h, hipStreamSynchronize(s));
+  // sort, relabel, heap cut: independent per session
+  if (!h->gpool) {
+    const unsigned hw = std::thread::hardware_concurrency();
+    h->gpool = new HostPool(hw >= 64 ? kGroupMax - 1 : (hw >= 8 ? 6 : (hw >= 4 ? 2 : 0)));
+  }
+  return SC_OK;
+}
+
 extern "C" int sc_pool_precluster(sc_pool pool, const int32_t* slots, int count,
                                   int64_t* const* labels_out) {
   if (!pool) return SC_ERR_INVALID;
@@ -246,39 +308,11 @@ extern "C" int sc_pool_precluster(sc_pool pool, const int32_t* slots, int count,
     pool->h_lists[pool->capacity + i] = n;
     max_rows = std::max(max_rows, n);
   }
-  SC_HIP(h, hipSetDevice(h->device));
+  SC_TRY(pool_linkage(pool, count, count, max_rows, 0, SC_LINKAGE_COMPLETE, sl.stride_z,
+                      "stream pool pre-cluster launch"));
   hipStream_t s = h->stream;
   int* slots_d = pool->lists;
   int* rows_d = pool->lists + pool->capacity;
-  SC_HIP(h, hipMemcpyAsync(pool->lists, pool->h_lists, 2 * (size_t)pool->capacity * sizeof(int),
-                           hipMemcpyHostToDevice, s));
-  // cosine distances: sc_ahc's unit rows and symmetric product (whole K per tile, as its
-  // single-call plan runs a product of this size), 16 sessions per launch, then 1 - clip
-  for (int base = 0; base < count; base += kGroupMax) {
-    GemmGroupItem items[kGroupMax];
-    const int cnt = std::min(kGroupMax, count - base);
-    for (int z = 0; z < cnt; ++z) {
-      const size_t slot = (size_t)slots[base + z];
-      items[z].A = sl.Xn + slot * sl.stride_x;
-      items[z].lda = sl.ldx;
-      items[z].C = sl.D + slot * sl.stride_d;
-      items[z].ldc = sl.ldd;
-      items[z].n = pool->rows[slot];
-      items[z].K = pool->d;
-    }
-    launch_gemm_nt_group(s, items, cnt, kEpiNone, 0);
-  }
-  launch_pool_cosine_distance(s, sl, slots_d, rows_d, count, max_rows);
-  launch_pool_nn_chain(s, sl, slots_d, rows_d, count, SC_LINKAGE_COMPLETE);
-  SC_TRY(check_last(h, "stream pool pre-cluster launch"));
-  SC_HIP(h, hipMemcpyAsync(pool->h_Z, sl.Z, (size_t)count * sl.stride_z * sizeof(double),
-                           hipMemcpyDeviceToHost, s));
-  SC_HIP(h, hipStreamSynchronize(s));
-  // sort, relabel, heap cut: independent per session
-  if (!h->gpool) {
-    const unsigned hw = std::thread::hardware_concurrency();
-    h->gpool = new HostPool(hw >= 64 ? kGroupMax - 1 : (hw >= 8 ? 6 : (hw >= 4 ? 2 : 0)));
-  }
   h->gpool->run(count, [&](int i) {
     const int n = pool->h_lists[pool->capacity + i];
     ahc_tree_cut(pool->h_Z + (size_t)i * sl.stride_z, n, pool->u1, 0.0, labels_out[i]);
@@ -295,6 +329,50 @@ extern "C" int sc_pool_precluster(sc_pool pool, const int32_t* slots, int count,
   return SC_OK;
 }
 
+extern "C" int sc_pool_fallback(sc_pool pool, const int32_t* slots, int count,
+                                double distance_threshold, int64_t* const* labels_out) {
+  if (!pool) return SC_ERR_INVALID;
+  sc_handle h = pool->h;
+  SC_TRY(check_slot_list(pool, slots, count));
+  if (!labels_out) return fail(h, SC_ERR_INVALID, "stream pool: labels_out is NULL");
+  for (int i = 0; i < count; ++i)
+    if (pool->rows[slots[i]] < 1 || !labels_out[i])
+      return fail(h, SC_ERR_INVALID, "stream pool: slot " + std::to_string(slots[i]) +
+                                         " holds no rows, or its labels_out entry is NULL");
+  // positions: the sessions of the global-memory chain first, then those of the LDS kernel;
+  // a session of one row is label 0 and takes no position
+  std::vector<int> at;  // position -> index into slots
+  int chain_rows = 0, lds_rows = 0;
+  for (int i = 0; i < count; ++i)
+    if (pool->rows[slots[i]] >= 2 && pool->rows[slots[i]] > kPoolLdsLinkageMax) {
+      at.push_back(i);
+      chain_rows = std::max(chain_rows, pool->rows[slots[i]]);
+    }
+  const int n_chain = (int)at.size();
+  for (int i = 0; i < count; ++i) {
+    const int n = pool->rows[slots[i]];
+    if (n == 1) labels_out[i][0] = 0;
+    if (n < 2 || n > kPoolLdsLinkageMax) continue;
+    at.push_back(i);
+    lds_rows = std::max(lds_rows, n);
+  }
+  const int listed = (int)at.size();
+  if (listed == 0) return SC_OK;
+  for (int z = 0; z < listed; ++z) {
+    pool->h_lists[z] = slots[at[z]];
+    pool->h_lists[pool->capacity + z] = pool->rows[slots[at[z]]];
+  }
+  const PoolSlabs& sl = pool->slabs;
+  SC_TRY(pool_linkage(pool, listed, n_chain, chain_rows, lds_rows, SC_LINKAGE_AVERAGE,
+                      4 * (size_t)(std::max(chain_rows, lds_rows) - 1),
+                      "stream pool fallback launch"));
+  h->gpool->run(listed, [&](int z) {
+    ahc_tree_cut(pool->h_Z + (size_t)z * sl.stride_z, pool->h_lists[pool->capacity + z], 0,
+                 distance_threshold, labels_out[at[z]]);
+  });
+  return SC_OK;
+}
+
 extern "C" int sc_pool_centroids(sc_pool pool, int slot, sc_array* out) {
   if (!pool) return SC_ERR_INVALID;
   SC_TRY(check_slot(pool, slot));
@@ -307,6 +385,22 @@ extern "C" int sc_pool_centroids(sc_pool pool, int slot, sc_array* out) {
   out->rows = pool->u1;
   out->cols = pool->d;
   out->row_stride = pool->d;
+  out->col_stride = 1;
+  return SC_OK;
+}
+
+extern "C" int sc_pool_cache(sc_pool pool, int slot, sc_array* out) {
+  if (!pool) return SC_ERR_INVALID;
+  SC_TRY(check_slot(pool, slot));
+  if (!out) return fail(pool->h, SC_ERR_INVALID, "stream pool: out is NULL");
+  if (pool->rows[slot] < 1)
+    return fail(pool->h, SC_ERR_INVALID, "stream pool: the slot holds no rows");
+  out->data = pool->slabs.X + (size_t)slot * pool->slabs.stride_x;
+  out->dtype = SC_DTYPE_F64;
+  out->location = SC_MEM_DEVICE;
+  out->rows = pool->rows[slot];
+  out->cols = pool->d;
+  out->row_stride = pool->slabs.ldx;
   out->col_stride = 1;
   return SC_OK;
 }

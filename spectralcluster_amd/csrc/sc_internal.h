@@ -633,6 +633,20 @@ void launch_pool_cosine_distance(hipStream_t s, const PoolSlabs& p, const int* s
 // launch_ahc_nn_chain for every listed session: one workgroup each, grid = count
 void launch_pool_nn_chain(hipStream_t s, const PoolSlabs& p, const int* slots, const int* rows,
                           int count, int method);
+// Average linkage of the listed sessions of 2 <= n <= kPoolLdsLinkageMax rows (others are left
+// alone) straight from the GEMM output in D: 1 - clip while loading, the whole chain in LDS on
+// one wavefront per session, Z as launch_pool_nn_chain(method 2) writes it (bit for bit).
+// Positions first .. first + count - 1 of the lists; max_rows: the largest of them.
+// -DSC_POOL_LDS_LINKAGE_MAX=0 builds the library without the kernel: every session then takes
+// launch_pool_cosine_distance + launch_pool_nn_chain.
+#ifndef SC_POOL_LDS_LINKAGE_MAX
+#define SC_POOL_LDS_LINKAGE_MAX 128
+#endif
+constexpr int kPoolLdsLinkageMax = SC_POOL_LDS_LINKAGE_MAX;
+#if SC_POOL_LDS_LINKAGE_MAX > 0
+void launch_pool_linkage_lds(hipStream_t s, const PoolSlabs& p, const int* slots, const int* rows,
+                             int first, int count, int max_rows);
+#endif
 // launch_cluster_centroids (k clusters) for every listed session, into the slot's centroids
 void launch_pool_centroids(hipStream_t s, const PoolSlabs& p, const int* slots, const int* rows,
                            int count, int k);

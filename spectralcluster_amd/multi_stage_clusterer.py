@@ -218,12 +218,14 @@ class _PoolSession:
 
   def __init__(self):
     self.num_embeddings = 0
-    self.mirror = None                 # host copy of the cache while it has at most U1 rows
+    # host copy of the cache while it has at most U1 rows (none with pool_early_stage)
+    self.mirror = None
     self.compression_labels = None
     self.previous_output = None
 
 
-ROUTE_MAIN_ONLY, ROUTE_POOLED_GROUPED, ROUTE_POOLED_SINGLE = range(3)
+(ROUTE_MAIN_ONLY, ROUTE_POOLED_GROUPED, ROUTE_POOLED_SINGLE, ROUTE_EARLY_FALLBACK,
+ ROUTE_EARLY_MAIN) = range(5)
 
 
 class MultiStageStreamPool:
@@ -237,6 +239,15 @@ class MultiStageStreamPool:
   clusterer is one the library batch covers -- one grouped call over the resident centroid
   buffers.  Constructor arguments as MultiStageClusterer's, plus `capacity` and `device`
   (default: the main clusterer's).  The embedding width is fixed by the first rows a pool sees.
+
+  `pool_early_stage` (keyword only, default False): sessions of at most U1 rows share their
+  launches too, when the main clusterer is one the library batch covers.  Fewer than L rows: one
+  `sc_pool_fallback` call per step, the average-linkage fallback of all such sessions on their
+  resident caches.  L to U1 rows: the cache itself (`sc_pool_cache`) joins the step's one
+  grouped main call next to the centroid buffers of the sessions beyond U1.  No host copy of a
+  cache is kept then and no embedding is downloaded.  Without the flag, or with a main clusterer
+  outside the library batch, each such session runs `main.predict` on a host mirror of its
+  cache, one after the other.
   """
 
   def __init__(self,
@@ -248,13 +259,16 @@ class MultiStageStreamPool:
                deflicker: Deflicker = Deflicker.NoDeflicker,
                capacity: int = 64,
                device: typing.Optional[int] = None,
-               d: typing.Optional[int] = None):
+               d: typing.Optional[int] = None,
+               *,
+               pool_early_stage: bool = False):
     # (the option changes and the max_spectral_size check of the per-stream class)
     MultiStageClusterer(main_clusterer, fallback_threshold, L, U1, U2, deflicker)
     self.main = main_clusterer
     self.deflicker = deflicker
     self.L, self.U1, self.U2 = int(L), int(U1), int(U2)
     self.capacity = int(capacity)
+    self.pool_early_stage = bool(pool_early_stage)
     self.device = device if device is not None else main_clusterer.device
     self.d = None
     self._pool = None
@@ -344,10 +358,11 @@ class MultiStageStreamPool:
         self._ensure_pool(d)
         self._append([session], [k], source)
         total = state.num_embeddings + k
-        if total <= self.U1:
+        mirrored = 0 if state.mirror is None else state.mirror.shape[0]
+        if total <= self.U1 and mirrored == state.num_embeddings and not self._early_pooled():
           host = np.asarray(source.host_f64(self._pool_handle), dtype=np.float64)
           state.mirror = host.copy() if state.mirror is None else np.vstack([state.mirror, host])
-        else:
+        else:   # (a step that needs the mirror after all fetches the cache: _step)
           state.mirror = None
         state.num_embeddings = total
         state.previous_output = None
@@ -361,8 +376,11 @@ class MultiStageStreamPool:
     ((len(sessions), d); NumPy or DLPack, float64 / float32 / float16 / bfloat16, host or
     device) is the next embedding of sessions[i].  Element i of the result is what that
     stream's MultiStageClusterer.streaming_predict would return, values and dtype.
-    `last_routes`: per session, 0 main.predict on its own (at most U1 rows), 1 pooled
-    pre-cluster + the grouped main call, 2 pooled pre-cluster + a main.predict of its own."""
+    `last_routes`: per session, 0 main.predict on its own (at most U1 rows; with
+    `pool_early_stage` only a session's first row, which runs nothing), 1 pooled pre-cluster +
+    the grouped main call, 2 pooled pre-cluster + a main.predict of its own, and with
+    `pool_early_stage` 3 the pooled fallback (2 .. L - 1 rows), 4 the cache in the grouped main
+    call (L .. U1 rows)."""
     sessions = [int(s) if isinstance(s, (int, np.integer)) else s for s in sessions]
     states = [self._session(s) for s in sessions]
     if len(set(sessions)) != len(sessions):
@@ -377,46 +395,89 @@ class MultiStageStreamPool:
           raise ValueError("embeddings must be (len(sessions), d)")
         self._ensure_pool(source.shape[1])
         self._append(sessions, [1] * len(sessions), source)
+        early = self._early_pooled()
         host = None
-        if any(st.num_embeddings < self.U1 for st in states):
+        if not early and any(st.num_embeddings < self.U1 for st in states):
           host = np.asarray(source.host_f64(self._pool_handle), dtype=np.float64)
       finally:
         source.release()
-      return self._step(sessions, states, host)
+      return self._step(sessions, states, host, early)
 
-  def _step(self, sessions, states, host) -> typing.List[np.ndarray]:
+  def _mirror_row(self, session, st, row) -> None:
+    """The host mirror of a cache of at most U1 rows after its append: the mirror plus the new
+    row, or -- when the mirror is missing or behind, after steps or a load() that kept none --
+    the cache as the device holds it."""
+    mirrored = 0 if st.mirror is None else st.mirror.shape[0]
+    if mirrored == st.num_embeddings - 1:
+      st.mirror = row.copy() if st.mirror is None else np.vstack([st.mirror, row])
+    else:
+      st.mirror = np.empty((st.num_embeddings, self.d), dtype=np.float64)
+      self._pool_handle.check(self._pool_handle.lib.sc_pool_get(
+          self._pool, session, _lib.SC_POOL_CACHE, _lib.as_double_p(st.mirror)))
+
+  def _step(self, sessions, states, host, early) -> typing.List[np.ndarray]:
     handle = self._pool_handle
     out = [None] * len(sessions)
     routes = [ROUTE_MAIN_ONLY] * len(sessions)
-    pooled = []
+    pooled, early_fallback, early_main = [], [], []
     for i, st in enumerate(states):
       st.num_embeddings += 1
-      if st.num_embeddings <= self.U1:
-        row = host[i:i + 1]
-        st.mirror = row.copy() if st.mirror is None else np.vstack([st.mirror, row])
+      if st.num_embeddings > self.U1:
+        st.mirror = None
+        pooled.append(i)
+      elif early:                                 # the cache stays where it is
+        st.mirror = None
+        if st.num_embeddings == 1:
+          out[i] = np.array([0])
+          st.previous_output = out[i]
+        elif st.num_embeddings < self.L:
+          early_fallback.append(i)
+        else:
+          early_main.append(i)
+      else:
+        self._mirror_row(sessions[i], st, host[i:i + 1])
         if st.num_embeddings == 1:
           out[i] = np.array([0])
         else:
           out[i] = self.main.predict(st.mirror)   # fallback or main clusterer only
         st.previous_output = out[i]
-      else:
-        st.mirror = None
-        pooled.append(i)
-    if pooled:
+    if early_fallback:                            # main.predict below L rows, for all of them
+      count = len(early_fallback)
+      labels = [np.empty(states[i].num_embeddings, dtype=np.int64) for i in early_fallback]
+      handle.check(handle.lib.sc_pool_fallback(
+          self._pool, (ctypes.c_int32 * count)(*[sessions[i] for i in early_fallback]), count,
+          float(self.main.fallback_options.agglomerative_threshold),
+          (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])))
+      for i, fallback_labels in zip(early_fallback, labels):
+        out[i] = fallback_labels
+        states[i].previous_output = out[i]
+        routes[i] = ROUTE_EARLY_FALLBACK
+    if pooled or early_main:
       count = len(pooled)
-      slots = (ctypes.c_int32 * count)(*[sessions[i] for i in pooled])
       pre = [np.empty(handle.lib.sc_pool_rows(self._pool, sessions[i]), dtype=np.int64)
              for i in pooled]
-      handle.check(handle.lib.sc_pool_precluster(
-          self._pool, slots, count,
-          (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in pre])))
-      if self._main_is_batchable():
+      if pooled:
+        slots = (ctypes.c_int32 * count)(*[sessions[i] for i in pooled])
+        handle.check(handle.lib.sc_pool_precluster(
+            self._pool, slots, count,
+            (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in pre])))
+      if early or self._main_is_batchable():
+        # one grouped call per step: the caches of L .. U1 rows and the centroids beyond U1
         arrays = []
+        for i in early_main:
+          arrays.append(_lib.ScArray())
+          handle.check(handle.lib.sc_pool_cache(self._pool, sessions[i],
+                                                ctypes.byref(arrays[-1])))
         for i in pooled:
           arrays.append(_lib.ScArray())
           handle.check(handle.lib.sc_pool_centroids(self._pool, sessions[i],
                                                     ctypes.byref(arrays[-1])))
         main = self.main.predict_device_batch(arrays)
+        for i, main_labels in zip(early_main, main):
+          out[i] = main_labels
+          states[i].previous_output = out[i]
+          routes[i] = ROUTE_EARLY_MAIN
+        main = main[len(early_main):]
         route = ROUTE_POOLED_GROUPED
       else:
         main = []
@@ -434,6 +495,13 @@ class MultiStageStreamPool:
         routes[i] = route
     self.last_routes = routes
     return out
+
+  def _early_pooled(self) -> bool:
+    """Do sessions of at most U1 rows take the pooled routes 3 and 4?  (The fallback of the
+    per-stream class is the agglomerative one: its constructor sets it on the main clusterer.)"""
+    return (self.pool_early_stage and self._main_is_batchable() and
+            self.main.fallback_options.fallback_clusterer_type ==
+            fallback_clusterer.FallbackClustererType.Agglomerative)
 
   def _main_is_batchable(self) -> bool:
     """predict_batch's conditions; spectral_min_embeddings (= L) is met by the U1 centroids."""
