@@ -397,8 +397,10 @@ int sc_run_resident(sc_handle h, const sc_config* cfg, int64_t* labels,
 /* one AutoTune search level (autotune.py:98-111): sc_eig_ncluster for `count` values of
  * p_percentile on the resident affinity; diags[i] reports what sc_eig_ncluster would for
  * p_values[i].  The values of a level differ only in the row threshold: the stages after it
- * run as grouped launches, the eigensolvers in lockstep.  Leaves no eigenvectors resident
- * in the handle itself (sc_sweep_adopt fetches a value's). */
+ * run as grouped launches, the eigensolvers in lockstep.  At n <= 128 the values are
+ * (matrix, p) pairs: one front launch and ONE dense Jacobi launch, a workgroup per value, for up
+ * to 64 of them (the two sequences the larger sizes group; anything else one by one).  Leaves no
+ * eigenvectors resident in the handle itself (sc_sweep_adopt fetches a value's). */
 int sc_eig_ncluster_sweep(sc_handle h, const sc_config* cfg, const double* p_values, int count,
                           sc_diag* diags);
 /* The eigenvectors of value `index` of the last sweep become the resident ones -- what
@@ -660,10 +662,15 @@ int sc_stage_krylov_state(sc_handle h, int32_t* info, double* q, double* t, doub
  *   SC_FRONT_ROUTE_SWEEP    one problem xs[0] (ns[0], d) and count (2 .. 16) values p_values[z] of
  *                           p_percentile: the front of one round of sc_eig_ncluster_sweep; outs[z]
  *                           belongs to p_values[z] (a0 and cropval are the shared ones).
+ *   SC_FRONT_ROUTE_SHORT_SWEEP  the same for a problem of ns[0] <= 128 rows: the front of one
+ *                           launch of (matrix, p) pairs of a short level (k_short_sweep_front,
+ *                           cut kernel 4), the Diffuse product through the grouped launcher;
+ *                           count 2 .. 64.
  * A configuration the route's grouped code does not cover (a group member below n = 256 or a
  * sequence other than ICASSP2018's; a sweep the product would evaluate one by one) returns
  * SC_ERR_UNSUPPORTED: the entry never takes another path quietly. */
-enum { SC_FRONT_ROUTE_SINGLE = 0, SC_FRONT_ROUTE_GROUPED = 1, SC_FRONT_ROUTE_SWEEP = 2 };
+enum { SC_FRONT_ROUTE_SINGLE = 0, SC_FRONT_ROUTE_GROUPED = 1, SC_FRONT_ROUTE_SWEEP = 2,
+       SC_FRONT_ROUTE_SHORT_SWEEP = 3 };
 enum {
   SC_FRONT_INFO_DIFFUSE_PATH = 0,   /* SC_DIFFUSE_PATH_NONE / _EXPLICIT / _FREE */
   SC_FRONT_INFO_SYMMETRIC = 1,
@@ -679,7 +686,7 @@ enum {
                                        would form S after all */
   SC_FRONT_INFO_CROP_SOURCE = 10,   /* 0 no value vector, 1 GEMM epilogue, 2 k_crop_value */
   SC_FRONT_INFO_CUT_KERNEL = 11,    /* 0 none, 1 k_cut_from_partials, 2 k_cut_from_rows,
-                                       3 k_row_percentile_cut */
+                                       3 k_row_percentile_cut, 4 k_short_sweep_front */
   SC_FRONT_INFO_WRITTEN = 12,       /* bit i: the i-th pointer of sc_front_out was filled */
   SC_FRONT_INFO_COUNT = 16
 };
@@ -784,6 +791,55 @@ int sc_host_hessenberg_eig(const double* packed, const double* tau, int n, int c
  * Returns the bound through *bound. */
 int sc_host_value_error_bound(const double* theta, const double* resid, int m, int i,
                               double* bound);
+/* AutoTune's search state (autotune.py:29-38): the p_percentile range, the step of its grid, the
+ * number of search levels and the proxy that is minimised. */
+#define SC_AUTOTUNE_PERCENTILE_OVER_NME 1      /* (1 - p) / g, g the largest eigengap */
+#define SC_AUTOTUNE_PERCENTILE_SQRT_OVER_NME 2 /* sqrt(1 - p) / g */
+typedef struct sc_autotune {
+  double p_min, p_max, step;
+  int32_t levels, proxy;
+} sc_autotune;
+/* One level's values, evaluated by the caller: ratios_out[i] = the proxy at ps[i].  Returns
+ * SC_OK, or a status that ends the search and is returned from it. */
+typedef int (*sc_autotune_evaluate)(const double* ps, int count, double* ratios_out, void* user);
+/* AutoTune.ratio (spectral_clusterer.py:281-286): the proxy of one evaluation whose largest
+ * eigengap is max_delta.  Host-only. */
+int sc_host_autotune_ratio(const sc_autotune* at, double p, double max_delta, double* ratio);
+/* AutoTune.tune (autotune.py:76-132) from the state *at: the grid of a level is
+ * np.linspace(p_min, p_max, ceil((p_max - p_min) / step)) to the last bit, values already
+ * searched (exact double equality) are not evaluated again, the first strict minimum of a level
+ * wins, and unless the grid is empty, holds one value or step < 1e-4 the range narrows to
+ * max(2, len / 8) grid points either side of the winner with half the step.  *best_p /
+ * *best_index: the winner and its index in its level's grid; *last_p: the last value evaluated;
+ * *narrowed: the state tune() leaves in the AutoTune object (*at itself is not written).  Any of
+ * the four may be NULL.  SC_ERR_INVALID where tune() raises (no level, no finite ratio, a
+ * non-finite grid size).  Host-only; exported so the search can be pinned against
+ * AutoTune.tune without a GPU. */
+int sc_host_autotune_search(const sc_autotune* at, sc_autotune_evaluate evaluate_many, void* user,
+                            double* best_p, int* best_index, double* last_p,
+                            sc_autotune* narrowed);
+/* A batch in which every utterance is an AutoTune search (a Python loop of predict(u, c) on a fresh
+ * clusterer per utterance): every utterance is searched from the state *at, which is not written.
+ * bands: NULL, or per utterance the band of its ConstraintMatrix (n_i - 1 values; NULL: none), used
+ * when cfg names a constraint.  best_p / last_p (either may be NULL): per utterance the winning
+ * p_percentile and the last value its search evaluated.  Routes (sc_last_batch_routes):
+ *   2  n <= 128, the two sequences sc_eig_ncluster_sweep groups: waves of up to 64 utterances,
+ *      level by level -- fronts per utterance on the member streams (the band applied per
+ *      utterance), then ALL (utterance, p) pairs of the wave's current level in launches of up
+ *      to 64 (one front launch, one Jacobi launch, a workgroup per pair),
+ *      sc_host_autotune_search per utterance on the ratios; the winners' eigenvectors from one
+ *      more launch, then the lockstep k-means
+ *   1  128 < n < 4096: dealt longest-first to three lanes, each a handle, stream and host thread of
+ *      its own running per utterance what predict() runs (ingest, sc_apply_constraint, the levels
+ *      through sc_eig_ncluster_sweep, sc_sweep_adopt or one evaluation, sc_cluster)
+ *   0  n >= 4096, other sequences, members that left their route: the same per-utterance function
+ *      on h; and everything when hipMemGetInfo says the arenas do not fit
+ * Every descriptor is validated before the first launch; no constraint is resident in h or in any
+ * arena when the call returns, whatever it returns.  group: >= 2 (the grouped form). */
+int sc_predict_batch_autotune(sc_handle h, const sc_array* xs, const double* const* bands,
+                              int count, const sc_config* cfg, const sc_autotune* at,
+                              int64_t* const* labels, sc_diag* diags, double* best_p, int group,
+                              double* last_p);
 /* utils.compute_number_of_clusters (utils.py:74-130) -- host scalar loop */
 int sc_eigengap(const double* eigenvalues, int count, int max_clusters,
                 double stop_eigenvalue, int eigengap_type, int descend,

@@ -145,6 +145,7 @@ _c_double_p = ctypes.POINTER(ctypes.c_double)
 
 # sc_stage_front: route, and the slots of sc_front_out.info
 SC_FRONT_ROUTE_SINGLE, SC_FRONT_ROUTE_GROUPED, SC_FRONT_ROUTE_SWEEP = range(3)
+SC_FRONT_ROUTE_SHORT_SWEEP = 3  # a level of n <= 128: (matrix, p) pairs, one front launch
 SC_FRONT_INFO_COUNT = 16
 FRONT_INFO_NAMES = ("diffuse_path", "symmetric", "folded_rownorm", "free_op", "digits_fused",
                     "blur_kernel", "blur_rows", "free_candidates", "free_overflow_rows",
@@ -158,6 +159,25 @@ class ScFrontOut(ctypes.Structure):
   _fields_ = [(name, _c_double_p) for name in FRONT_OUTPUTS] + [
       ("info", ctypes.c_int32 * SC_FRONT_INFO_COUNT)]
 
+
+# sc_autotune.proxy (the values of autotune.AutoTuneProxy)
+SC_AUTOTUNE_PERCENTILE_OVER_NME, SC_AUTOTUNE_PERCENTILE_SQRT_OVER_NME = 1, 2
+
+
+class ScAutoTune(ctypes.Structure):
+  """Mirror of `sc_autotune`: the state of an `AutoTune` object."""
+  _fields_ = [
+      ("p_min", ctypes.c_double),
+      ("p_max", ctypes.c_double),
+      ("step", ctypes.c_double),
+      ("levels", ctypes.c_int32),
+      ("proxy", ctypes.c_int32),
+  ]
+
+
+# sc_autotune_evaluate: (ps, count, ratios_out, user) -> sc_status
+AUTOTUNE_EVALUATE = ctypes.CFUNCTYPE(ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p,
+                                     ctypes.c_void_p)
 
 _c_int64_p = ctypes.POINTER(ctypes.c_int64)
 _c_int_p = ctypes.POINTER(ctypes.c_int)
@@ -336,6 +356,18 @@ PROTOTYPES = {
                                               _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "sc_host_value_error_bound": (ctypes.c_int, [_c_double_p, _c_double_p, ctypes.c_int,
                                                  ctypes.c_int, _c_double_p]),
+    "sc_host_autotune_ratio": (ctypes.c_int, [ctypes.POINTER(ScAutoTune), ctypes.c_double,
+                                              ctypes.c_double, _c_double_p]),
+    "sc_host_autotune_search": (ctypes.c_int, [ctypes.POINTER(ScAutoTune), AUTOTUNE_EVALUATE,
+                                               ctypes.c_void_p, _c_double_p, _c_int_p,
+                                               _c_double_p, ctypes.POINTER(ScAutoTune)]),
+    "sc_predict_batch_autotune": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),
+                                                 ctypes.POINTER(_c_double_p), ctypes.c_int,
+                                                 ctypes.POINTER(ScConfig),
+                                                 ctypes.POINTER(ScAutoTune),
+                                                 ctypes.POINTER(_c_int64_p),
+                                                 ctypes.POINTER(ScDiag), _c_double_p, ctypes.c_int,
+                                                 _c_double_p]),
     "sc_eigengap": (ctypes.c_int, [_c_double_p, ctypes.c_int, ctypes.c_int,
                                    ctypes.c_double, ctypes.c_int, ctypes.c_int,
                                    _c_int_p, _c_double_p]),

@@ -50,6 +50,13 @@ class AutoTune:
     self.search_step = search_step
     return self.get_percentile_range()
 
+  def to_struct(self):
+    """The object's state as an `sc_autotune` (what `sc_host_autotune_search` starts from)."""
+    from spectralcluster_amd import _lib
+    return _lib.ScAutoTune(float(self.p_percentile_min), float(self.p_percentile_max),
+                           float(self.search_step), int(self.search_level),
+                           int(self.proxy.value))
+
   def ratio(self, p_percentile: float, max_delta_norm: float) -> float:
     """The proxy value for one evaluation (reference
     spectral_clusterer.py:281-286)."""

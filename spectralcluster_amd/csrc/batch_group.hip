@@ -30,7 +30,9 @@
 // ConstraintPropagation before refinement as one chain of grouped launches per group
 // (enqueue_front; constraint_api.hip: constraint_propagation_group).
 #include <ctime>
+#include <map>
 #include <thread>
+#include <utility>
 
 #include "handle.h"
 
@@ -1252,6 +1254,9 @@ namespace {
 struct SweepPlan {
   bool icassp = false, thr_sym_only = false, grouped = false;
   bool free_route = false, amax_from_cut = false;
+  // n <= kDenseMax: the level's values as (matrix, p) pairs -- one front launch and ONE Jacobi
+  // launch for up to kShortWidth of them (sweep_short_level)
+  bool short_level = false;
 };
 SweepPlan sweep_plan(sc_handle h, const sc_config* cfg, int count, const EigRequest& rq) {
   const int n = h->n;
@@ -1274,6 +1279,13 @@ SweepPlan sweep_plan(sc_handle h, const sc_config* cfg, int count, const EigRequ
   plan.amax_from_cut = plan.free_route && h->affinity_from_embeddings &&
                        !h->constraint_applied && cfg->soft_multiplier >= 0.0 &&
                        cfg->soft_multiplier <= 1.0;
+  // A level of a short utterance ends in the one-workgroup Jacobi solve per value: evaluated one
+  // by one that is count launches on ONE CU each.  The same two sequences, under the same
+  // conditions, go through the short front and dense_topk_group instead.
+  plan.short_level = !plan.grouped && count > 1 && n <= kDenseMax &&
+                     (plan.icassp || plan.thr_sym_only) && h->affinity_symmetric &&
+                     !constraint_active(h, cfg, false) && !plan.free_route &&
+                     !sw::sweep_one_by_one();
   return plan;
 }
 
@@ -1303,18 +1315,21 @@ int sweep_shared_blur(sc_handle h, const sc_config* cfg, const double** crop_out
 }
 
 // The members of one round (value ps[z] in member arena z): arenas sized, launch descriptors
-// filled.  *out_of_memory (with SC_OK): an arena's buffers did not fit -- the sweep runs the rest
-// one by one.  Any other failure, creating an arena included, is returned.
+// filled.  `slot0`: the first member arena to use; `owner`: the handle whose arenas they are
+// (default: h's own -- an AutoTune batch keeps the pairs of many utterances in the lead's).
+// *out_of_memory (with SC_OK): an arena's buffers did not fit -- the sweep runs the rest one by
+// one.  Any other failure, creating an arena included, is returned.
 int sweep_round_members(sc_handle h, const sc_config* cfg, const SweepPlan& plan,
                         const EigRequest& rq, const double* ps, int cnt, FrontItem* fi,
-                        GemmGroupItem* dif, GroupEigMember* em, bool* out_of_memory) {
+                        GemmGroupItem* dif, GroupEigMember* em, bool* out_of_memory,
+                        int slot0 = 0, sc_handle owner = nullptr) {
   *out_of_memory = false;
   const int n = h->n, ld = h->ldn;
   const bool icassp = plan.icassp, free_route = plan.free_route;
   const int nt = gemm_tile_dim(n);
   for (int z = 0; z < cnt; ++z) {
     sc_handle hz = nullptr;
-    SC_TRY(group_slot(h, z, &hz));
+    SC_TRY(group_slot(owner ? owner : h, slot0 + z, &hz));
     int rc = ensure_matrices(hz, n, 0, false);
     if (rc == SC_OK) rc = ensure_eig(hz, n);
     if (rc == SC_OK) rc = ensure_tilemap(hz, n);
@@ -1480,6 +1495,173 @@ int sweep_round_front(sc_handle h, const sc_config* cfg, const SweepPlan& plan, 
   SC_TRY(check_last(h, "sweep launch"));
   return SC_OK;
 }
+
+// ---- a level of a short utterance (n <= kDenseMax, plan.short_level)
+// What every value of the level shares, with the single call's kernels: nothing for
+// [RowWiseThreshold, Symmetrize]; CropDiagonal + GaussianBlur for the ICASSP2018 sequence -- the
+// two unfused kernels below n = 128 (crop into B1, blur into B2), value vector + fused blur at 128.
+struct ShortShared {
+  const double* src = nullptr;   // the matrix every value thresholds
+  const double* crop = nullptr;  // CropDiagonal's value vector (fused form only)
+  int crop_source = 0;
+};
+int sweep_short_shared(sc_handle h, const sc_config* cfg, const SweepPlan& plan, ShortShared* sh) {
+  const int n = h->n, ld = h->ldn;
+  *sh = ShortShared();
+  sh->src = ptr<double>(h->A0);
+  if (!plan.icassp) return SC_OK;
+  if (n >= 128) {  // (eig_ncluster_impl's blur_fast; the radius is 4 or 8: grouped_front_covers)
+    SC_TRY(sweep_shared_blur(h, cfg, &sh->crop, &sh->crop_source));
+    sh->src = ptr<double>(h->B1);
+    return SC_OK;
+  }
+  SC_TRY(run_refine_op(h, SC_OP_CROP_DIAGONAL, cfg, ptr<double>(h->A0), ptr<double>(h->B1), n, ld));
+  SC_TRY(run_refine_op(h, SC_OP_GAUSSIAN_BLUR, cfg, ptr<double>(h->B1), ptr<double>(h->B2), n, ld));
+  sh->src = ptr<double>(h->B2);
+  return SC_OK;
+}
+
+// The per-value front of up to kShortWidth (matrix, p) pairs whose member arenas are set up (fi,
+// dif: pair z thresholds srcs[z] at ps[z]) on the lead's stream: ONE k_short_sweep_front launch;
+// for the ICASSP2018 sequence the Diffuse product and the scaling vectors follow through the
+// grouped launchers, kGroupMax pairs per launch.  The pairs may belong to different utterances.
+int short_pairs_launch(sc_handle h, const sc_config* cfg, const SweepPlan& plan,
+                       const double* const* srcs, const double* ps, int cnt, const FrontItem* fi,
+                       const GemmGroupItem* dif) {
+  hipStream_t s = h->stream;
+  const size_t bytes = (size_t)kShortWidth * sizeof(ShortFrontItem);
+  SC_TRY(grow(h, h->gsftab, bytes));
+  if (!h->h_gsftab) {
+    SC_HIP(h, hipHostMalloc(reinterpret_cast<void**>(&h->h_gsftab), bytes));
+    SC_HIP(h, hipEventCreateWithFlags(&h->gsftab_ev, hipEventDisableTiming));
+  } else {
+    // the pinned table is rewritten: the copy of the launch before must have read it (it has,
+    // wherever a Jacobi launch and its synchronisation followed: no stall then)
+    SC_HIP(h, hipEventSynchronize(h->gsftab_ev));
+  }
+  for (int z = 0; z < cnt; ++z) {
+    ShortFrontItem& it = h->h_gsftab[z];
+    it = ShortFrontItem();
+    it.src = srcs[z];
+    it.n = fi[z].n;
+    it.ld = fi[z].ldn;
+    it.p = ps[z];
+    it.out = fi[z].B2;
+    it.cut = fi[z].cut;
+    if (!plan.icassp) {  // no Diffuse: the kernel leaves the statistics and the operator's vectors
+      it.rowmax = const_cast<double*>(fi[z].rowmax);
+      it.rowsum = const_cast<double*>(fi[z].rowsum);
+      it.cvec = fi[z].cvec;
+      it.pvec = fi[z].pvec;
+      it.tvec = fi[z].tvec;
+    }
+    it.flags = fi[z].flags;
+    it.symflag = fi[z].symflag;
+  }
+  SC_HIP(h, hipMemcpyAsync(h->gsftab.p, h->h_gsftab, (size_t)cnt * sizeof(ShortFrontItem),
+                           hipMemcpyHostToDevice, s));
+  SC_HIP(h, hipEventRecord(h->gsftab_ev, s));
+  launch_short_sweep_front(s, ptr<ShortFrontItem>(h->gsftab), cnt, cfg->threshold_type,
+                           cfg->soft_multiplier, cfg->binarize, cfg->symmetrize_type,
+                           cfg->preserve_diagonal, cfg->laplacian_type);
+  for (int at = 0; plan.icassp && at < cnt; at += kGroupMax) {
+    const int c = std::min(kGroupMax, cnt - at);
+    FrontItem init[kGroupMax];  // (the init kernel must not clear the shared symflag word)
+    memset(init, 0, sizeof(init));
+    for (int z = 0; z < c; ++z) {
+      init[z] = fi[at + z];
+      init[z].symflag = nullptr;
+    }
+    launch_front_begin_group(s, init, c, false);
+    launch_gemm_nt_group(s, dif + at, c, kEpiNone, 1);
+    launch_scaling_vectors_group(s, fi + at, c, cfg->laplacian_type, 1);
+  }
+  SC_TRY(check_last(h, "short sweep launch"));
+  return SC_OK;
+}
+
+// ... of one utterance's level: value ps[z] in member arena z.  fi / dif / em: kShortWidth entries
+// each.  *out_of_memory as sweep_round_members'.
+int sweep_short_front(sc_handle h, const sc_config* cfg, const SweepPlan& plan,
+                      const EigRequest& rq, const ShortShared& sh, const double* ps, int cnt,
+                      FrontItem* fi, GemmGroupItem* dif, GroupEigMember* em, bool* out_of_memory) {
+  *out_of_memory = false;
+  for (int at = 0; at < cnt && !*out_of_memory; at += kGroupMax)
+    SC_TRY(sweep_round_members(h, cfg, plan, rq, ps + at, std::min(kGroupMax, cnt - at), fi + at,
+                               dif + at, em + at, out_of_memory, at));
+  if (*out_of_memory) return SC_OK;
+  const double* srcs[kShortWidth];
+  for (int z = 0; z < cnt; ++z) srcs[z] = sh.src;
+  return short_pairs_launch(h, cfg, plan, srcs, ps, cnt, fi, dif);
+}
+
+// sc_eig_ncluster_sweep for plan.short_level: the level's values in launches of up to kShortWidth
+// pairs, each ONE front launch and ONE Jacobi launch (dense_topk_group: a workgroup per pair, the
+// kernel body of the value's own sc_eig_ncluster).  Every solved value's eigenvectors stay in its
+// member arena (sc_sweep_adopt).  *handled false: nothing was evaluated, the caller goes one by
+// one.
+int sweep_short_level(sc_handle h, const sc_config* cfg, const SweepPlan& plan,
+                      const EigRequest& rq, const double* p_values, int count, sc_diag* diags,
+                      bool* handled) {
+  const int n = h->n;
+  *handled = false;
+  ShortShared sh;
+  SC_TRY(sweep_short_shared(h, cfg, plan, &sh));
+  std::vector<FrontItem> fi(kShortWidth);
+  std::vector<GemmGroupItem> dif(kShortWidth);
+  std::vector<GroupEigMember> em(kShortWidth);
+  h->sweep_slot.assign(count, -1);
+  h->sweep_n = n;
+  h->sweep_p.assign(p_values, p_values + count);
+  h->sweep_cfg = *cfg;
+  std::vector<int> later;  // values whose request the dense solve could not satisfy
+  for (int base = 0; base < count; base += kShortWidth) {
+    const int cnt = std::min(kShortWidth, count - base);
+    memset(fi.data(), 0, fi.size() * sizeof(FrontItem));
+    bool out_of_memory = false;
+    SC_TRY(sweep_short_front(h, cfg, plan, rq, sh, p_values + base, cnt, fi.data(), dif.data(),
+                             em.data(), &out_of_memory));
+    if (out_of_memory) {
+      (void)hipGetLastError();
+      if (base == 0) {
+        h->sweep_slot.clear();
+        return SC_OK;
+      }
+      for (int i = base; i < count; ++i) later.push_back(i);
+      break;
+    }
+    SC_TRY(dense_topk_group(h, em.data(), cnt));
+    for (int& slot : h->sweep_slot)
+      if (slot >= 0 && slot < cnt) slot = -1;  // an earlier launch's member: arena reused
+    for (int z = 0; z < cnt; ++z) {
+      if (em[z].status != 0) {
+        later.push_back(base + z);
+        continue;
+      }
+      h->sweep_slot[base + z] = z;
+      sc_diag* dg = diags + base + z;
+      memset(dg, 0, sizeof(*dg));
+      dg->n = n;
+      dg->n_clusters_raw = em[z].dc.n_clusters_raw;
+      dg->max_delta = em[z].dc.max_delta;
+      dg->eig_descending = rq.descend;
+      dg->n_eigenvalues = std::min((int)em[z].w.size(), SC_MAX_EIG);
+      for (int i = 0; i < dg->n_eigenvalues; ++i) dg->eigenvalues[i] = em[z].w[i];
+      dg->symmetry_state = plan.icassp ? 2 : 1;
+      dg->eig_path = SC_EIG_PATH_DENSE_JACOBI;
+      dg->diffuse_path = plan.icassp ? SC_DIFFUSE_PATH_EXPLICIT : SC_DIFFUSE_PATH_NONE;
+    }
+  }
+  *handled = true;
+  for (int i : later) {  // (the single call states the error, or finds what the group did not)
+    sc_config c = *cfg;
+    c.p_percentile = p_values[i];
+    SC_TRY(sc_eig_ncluster(h, &c, diags + i));
+  }
+  h->n_vec = 0;  // nothing of any member is resident in this handle
+  h->sweep_diags.assign(diags, diags + count);
+  return SC_OK;
+}
 }  // namespace
 
 // ------------------------------------------------------------------------------
@@ -1491,8 +1673,9 @@ int sweep_round_front(sc_handle h, const sc_config* cfg, const SweepPlan& plan, 
 // the Diffuse GEMM (all members' tiles in one launch) and the scaling vectors as grouped
 // launches and through ONE lockstep block Lanczos (sym_topk_group, eigenvalues + eigengap
 // decision only).  diags[i] is what sc_eig_ncluster would report for p_values[i]; no
-// eigenvectors are left resident (evaluate the winner with sc_eig_ncluster).  Configurations
-// the grouped stages do not cover are evaluated one by one.
+// eigenvectors are left resident (evaluate the winner with sc_eig_ncluster).  At n <= kDenseMax
+// the values are (matrix, p) pairs of one front launch and one dense Jacobi launch
+// (sweep_short_level).  Configurations the grouped stages do not cover are evaluated one by one.
 extern "C" int sc_eig_ncluster_sweep(sc_handle h, const sc_config* cfg, const double* p_values,
                                      int count, sc_diag* diags) {
   if (!h) return SC_ERR_INVALID;
@@ -1512,6 +1695,11 @@ extern "C" int sc_eig_ncluster_sweep(sc_handle h, const sc_config* cfg, const do
   };
   const SweepPlan plan = sweep_plan(h, cfg, count, rq);
   const bool icassp = plan.icassp, free_route = plan.free_route;
+  if (plan.short_level) {
+    bool handled = false;
+    SC_TRY(sweep_short_level(h, cfg, plan, rq, p_values, count, diags, &handled));
+    if (handled) return SC_OK;
+  }
   if (!plan.grouped) {
     for (int i = 0; i < count; ++i) SC_TRY(one_by_one(i));
     return SC_OK;
@@ -1873,6 +2061,51 @@ int stage_front_sweep(sc_handle h, const sc_config* cfg, int count, int n, int d
   }
   return SC_OK;
 }
+
+// the front of one launch of a short level (n <= kDenseMax) of sc_eig_ncluster_sweep
+int stage_front_short_sweep(sc_handle h, const sc_config* cfg, int count, int n, int d,
+                            const double* x, const double* p_values, sc_front_out* outs) {
+  SC_TRY(sc_set_embeddings(h, x, n, d));
+  SC_TRY(sc_compute_affinity(h));
+  const EigRequest rq = make_eig_request(cfg);
+  const SweepPlan plan = sweep_plan(h, cfg, count, rq);
+  if (!plan.short_level)
+    return fail(h, SC_ERR_UNSUPPORTED,
+                "sc_stage_front: sc_eig_ncluster_sweep would not run this level as short pairs");
+  h->sweep_slot.clear();  // (the member arenas are reused)
+  h->last_blur = BlurLaunch();
+  ShortShared sh;
+  SC_TRY(sweep_short_shared(h, cfg, plan, &sh));
+  std::vector<FrontItem> fi(kShortWidth);
+  std::vector<GemmGroupItem> dif(kShortWidth);
+  std::vector<GroupEigMember> em(kShortWidth);
+  memset(fi.data(), 0, fi.size() * sizeof(FrontItem));
+  bool out_of_memory = false;
+  SC_TRY(sweep_short_front(h, cfg, plan, rq, sh, p_values, count, fi.data(), dif.data(),
+                           em.data(), &out_of_memory));
+  if (out_of_memory)
+    return fail(h, SC_ERR_OOM, "sc_stage_front: the level's member arenas do not fit");
+  SC_HIP(h, hipStreamSynchronize(h->stream));
+  for (int z = 0; z < count; ++z) {
+    sc_handle hz = em[z].h;
+    FrontWhere w;
+    w.h = hz;
+    w.n = n;
+    w.ld = h->ldn;
+    w.a0 = ptr<double>(h->A0);
+    w.cropval = sh.crop;
+    w.cut = ptr<double>(hz->cut);
+    w.a = ptr<double>(hz->B2);
+    w.s = plan.icassp ? ptr<double>(hz->B1) : nullptr;
+    w.diffuse_path = plan.icassp ? SC_DIFFUSE_PATH_EXPLICIT : SC_DIFFUSE_PATH_NONE;
+    w.folded_rownorm = plan.icassp;
+    w.blur = h->last_blur;
+    w.crop_source = sh.crop_source;
+    w.cut_kernel = 4;
+    SC_TRY(front_copy_out(h, w, outs + z));
+  }
+  return SC_OK;
+}
 }  // namespace
 
 extern "C" int sc_stage_front(sc_handle h, int route, const sc_config* cfg, int count,
@@ -1882,8 +2115,10 @@ extern "C" int sc_stage_front(sc_handle h, int route, const sc_config* cfg, int 
   if (!h) return SC_ERR_INVALID;
   SC_TRY(validate_config(h, cfg));
   if (!ns || !outs || count < 1) return fail(h, SC_ERR_INVALID, "sc_stage_front: NULL argument");
-  if (count > kGroupMax)
-    return fail(h, SC_ERR_UNSUPPORTED, "sc_stage_front: at most 16 members / values per call");
+  if (count > (route == SC_FRONT_ROUTE_SHORT_SWEEP ? kShortWidth : kGroupMax))
+    return fail(h, SC_ERR_UNSUPPORTED,
+                "sc_stage_front: at most 16 members / values per call (a short level: one launch "
+                "of pairs)");
   SC_HIP(h, hipSetDevice(h->device));
   const int members = route == SC_FRONT_ROUTE_GROUPED ? count : 1;
   for (int z = 0; z < members; ++z)
@@ -1901,6 +2136,396 @@ extern "C" int sc_stage_front(sc_handle h, int route, const sc_config* cfg, int 
     case SC_FRONT_ROUTE_SWEEP:
       if (!p_values) return fail(h, SC_ERR_INVALID, "sc_stage_front: p_values is NULL");
       return stage_front_sweep(h, cfg, count, ns[0], d, xs[0], p_values, outs);
+    case SC_FRONT_ROUTE_SHORT_SWEEP:
+      if (!p_values) return fail(h, SC_ERR_INVALID, "sc_stage_front: p_values is NULL");
+      return stage_front_short_sweep(h, cfg, count, ns[0], d, xs[0], p_values, outs);
   }
   return fail(h, SC_ERR_INVALID, "sc_stage_front: unknown route");
+}
+
+// ------------------------------------------------------------------------------
+// sc_predict_batch_autotune: a batch in which every utterance is an AutoTune search
+// ------------------------------------------------------------------------------
+namespace {
+// One utterance on one handle and stream: the AutoTune branch of SpectralClusterer._predict --
+// ingest, the band resident and applied before refinement, the levels through
+// sc_eig_ncluster_sweep under the host search, the winner adopted from the last level (a single
+// evaluation when it left it), sc_cluster.  No constraint is resident in `h` afterwards.
+struct SearchOnHandle {
+  sc_handle h;
+  const sc_config* cfg;
+  const sc_autotune* at;
+  std::vector<double> last_ps;  // the values of the level evaluated last
+};
+int search_level_on_handle(const double* ps, int count, double* ratios, void* user) {
+  SearchOnHandle* c = static_cast<SearchOnHandle*>(user);
+  std::vector<sc_diag> diags(count);
+  const int rc = sc_eig_ncluster_sweep(c->h, c->cfg, ps, count, diags.data());
+  if (rc != SC_OK) return rc;
+  c->last_ps.assign(ps, ps + count);
+  for (int i = 0; i < count; ++i)
+    if (sc_host_autotune_ratio(c->at, ps[i], diags[i].max_delta, ratios + i) != SC_OK)
+      return SC_ERR_INVALID;
+  return SC_OK;
+}
+int autotune_one(sc_handle h, const sc_array& x, const double* band, const sc_config* cfg,
+                 const sc_autotune* at, int64_t* labels, sc_diag* diag, double* best_p,
+                 double* last_p) {
+  struct NoConstraintLeft {
+    sc_handle h;
+    ~NoConstraintLeft() { (void)sc_clear_constraint(h); }
+  } cleanup{h};
+  const int n = (int)x.rows;
+  if (band && cfg->constraint_name != SC_CONSTRAINT_NONE)
+    SC_TRY(sc_set_constraint_band(h, band, n));
+  else
+    SC_TRY(sc_clear_constraint(h));
+  SC_TRY(ingest_embeddings(h, x, x.location == SC_MEM_HOST));
+  SC_TRY(sc_compute_affinity(h));
+  if (constraint_active(h, cfg, true)) SC_TRY(sc_apply_constraint(h, cfg));
+  SearchOnHandle ctx{h, cfg, at, {}};
+  double win = 0.0, last = 0.0;
+  int rc = sc_host_autotune_search(at, search_level_on_handle, &ctx, &win, nullptr, &last, nullptr);
+  if (rc != SC_OK) {
+    if (h->err.empty())
+      fail(h, rc, "the AutoTune search has no winner (no level, or no finite ratio)");
+    return rc;
+  }
+  sc_config c = *cfg;
+  c.p_percentile = win;
+  sc_diag local;
+  sc_diag* dg = diag ? diag : &local;
+  int index = -1;
+  for (int i = 0; i < (int)ctx.last_ps.size(); ++i)
+    if (ctx.last_ps[i] == win) index = i;
+  if (index < 0 || sc_sweep_adopt(h, &c, index, dg) != SC_OK) SC_TRY(sc_eig_ncluster(h, &c, dg));
+  int k = dg->n_clusters_raw;
+  if (cfg->min_clusters > 0 && k < cfg->min_clusters) k = cfg->min_clusters;
+  SC_TRY(sc_cluster(h, &c, k, labels, dg));
+  if (best_p) *best_p = win;
+  if (last_p) *last_p = last;
+  return SC_OK;
+}
+
+// ---- the short route: utterances of n <= kDenseMax in waves, level by level
+// The host search is driven by a callback; here the levels of many utterances are evaluated
+// together, so a search is REPLAYED: it runs from the entry state on the ratios known so far and
+// stops at the first level that needs a value nobody has evaluated -- those values join the wave's
+// next launches -- until it runs through.  (A search is a few hundred flops.)
+constexpr int kSearchPending = 1;  // (no sc_status is positive)
+struct Replay {
+  const std::map<double, double>* known;
+  std::vector<double> pending;
+};
+int replay_level(const double* ps, int count, double* ratios, void* user) {
+  Replay* r = static_cast<Replay*>(user);
+  r->pending.clear();
+  for (int i = 0; i < count; ++i) {
+    const auto it = r->known->find(ps[i]);
+    if (it == r->known->end()) r->pending.push_back(ps[i]);
+    else ratios[i] = it->second;
+  }
+  return r->pending.empty() ? SC_OK : kSearchPending;
+}
+
+struct ShortUtterance {
+  int index = -1;        // utterance of the batch
+  sc_handle h = nullptr;  // its arena: affinity (adjusted by its band), what its values share
+  SweepPlan plan;
+  ShortShared shared;
+  std::map<double, double> ratio;  // proxy per evaluated p_percentile
+  std::vector<double> pending;
+  bool done = false, left = false;  // `left`: goes through autotune_one on the caller's handle
+  double best_p = 0.0, last_p = 0.0;
+};
+
+// (utterance, p) pairs in launches of up to kShortWidth: ONE front launch, ONE Jacobi launch each.
+// `on_pair(q, em)`: called per solved pair of a launch, q its position in `pairs`.
+template <typename F>
+int short_pairs_run(sc_handle lead, const sc_config* cfg, const EigRequest& rq,
+                    std::vector<ShortUtterance>& us,
+                    const std::vector<std::pair<int, double>>& pairs,
+                    std::vector<FrontItem>& fi, std::vector<GemmGroupItem>& dif,
+                    std::vector<GroupEigMember>& em, F on_launch) {
+  // (pairs of one sequence only: a wave's utterances share the configuration, hence the plan)
+  for (size_t base = 0; base < pairs.size(); base += kShortWidth) {
+    const int cnt = (int)std::min<size_t>(kShortWidth, pairs.size() - base);
+    memset(fi.data(), 0, fi.size() * sizeof(FrontItem));
+    const double* srcs[kShortWidth];
+    double ps[kShortWidth];
+    for (int q = 0; q < cnt; ++q) {
+      ShortUtterance& u = us[pairs[base + q].first];
+      ps[q] = pairs[base + q].second;
+      srcs[q] = u.shared.src;
+      bool out_of_memory = false;
+      const int rc = sweep_round_members(u.h, cfg, u.plan, rq, ps + q, 1, fi.data() + q,
+                                         dif.data() + q, em.data() + q, &out_of_memory, q, lead);
+      if (rc != SC_OK) return fail(lead, rc, u.h->err);
+      if (out_of_memory)
+        return fail(lead, SC_ERR_OOM, "a pair arena of the AutoTune batch does not fit");
+    }
+    SC_TRY(short_pairs_launch(lead, cfg, us[pairs[base].first].plan, srcs, ps, cnt, fi.data(),
+                              dif.data()));
+    SC_TRY(dense_topk_group(lead, em.data(), cnt));
+    SC_TRY(on_launch((int)base, cnt));
+  }
+  return SC_OK;
+}
+
+int autotune_short_wave(sc_handle lead, const sc_array* xs, const double* const* bands,
+                        const int* ns, int d, const sc_config* cfg, const sc_autotune* at,
+                        const EigRequest& rq, const int* idx, int count, int64_t* const* labels,
+                        sc_diag* diags, double* best_p, double* last_p, std::vector<int>* left) {
+  hipStream_t s = lead->stream;
+  std::vector<ShortUtterance> us(count);
+  // ---- fronts per utterance on the member streams: affinity, band, the part its values share
+  for (int z = 0; z < count; ++z) {
+    ShortUtterance& u = us[z];
+    u.index = idx[z];
+    SC_TRY(group_slot(lead, z, &u.h, &lead->gshort));
+    sc_handle h = u.h;
+    h->err.clear();
+    int rc = sc_reserve(h, kDenseMax, d);
+    const double* band = bands ? bands[u.index] : nullptr;
+    if (rc == SC_OK)
+      rc = band && cfg->constraint_name != SC_CONSTRAINT_NONE
+               ? sc_set_constraint_band(h, band, ns[u.index]) : sc_clear_constraint(h);
+    if (rc == SC_OK) rc = ingest_embeddings(h, xs[u.index], false);
+    if (rc == SC_OK) rc = sc_compute_affinity(h);
+    if (rc == SC_OK && constraint_active(h, cfg, true)) rc = sc_apply_constraint(h, cfg);
+    if (rc == SC_OK) {
+      u.plan = sweep_plan(h, cfg, 2, rq);
+      if (!u.plan.short_level) u.left = u.done = true;  // (a sequence the sweep does not group)
+      else rc = sweep_short_shared(h, cfg, u.plan, &u.shared);
+    }
+    if (rc != SC_OK) return fail(lead, rc, h->err);
+    SC_HIP(lead, hipEventRecord(h->sync_ev, h->stream));
+    SC_HIP(lead, hipStreamWaitEvent(s, h->sync_ev, 0));
+  }
+  std::vector<FrontItem> fi(kShortWidth);
+  std::vector<GemmGroupItem> dif(kShortWidth);
+  std::vector<GroupEigMember> em(kShortWidth);
+  // ---- the levels: replay every open search, evaluate what they ask for, again
+  for (;;) {
+    std::vector<std::pair<int, double>> pairs;
+    for (int z = 0; z < count; ++z) {
+      ShortUtterance& u = us[z];
+      if (u.done) continue;
+      Replay replay{&u.ratio, {}};
+      const int rc = sc_host_autotune_search(at, replay_level, &replay, &u.best_p, nullptr,
+                                             &u.last_p, nullptr);
+      if (rc == SC_OK) {
+        u.done = true;
+      } else if (rc == kSearchPending) {
+        for (double p : replay.pending) pairs.emplace_back(z, p);
+      } else {
+        return fail(lead, rc, "the AutoTune search has no winner (no level, or no finite ratio)");
+      }
+    }
+    if (pairs.empty()) break;
+    SC_TRY(short_pairs_run(lead, cfg, rq, us, pairs, fi, dif, em, [&](int base, int cnt) -> int {
+      for (int q = 0; q < cnt; ++q) {
+        ShortUtterance& u = us[pairs[base + q].first];
+        if (em[q].status != 0) {  // the single call states the error
+          u.left = u.done = true;
+          continue;
+        }
+        double ratio = 0.0;
+        if (sc_host_autotune_ratio(at, pairs[base + q].second, em[q].dc.max_delta, &ratio) != SC_OK)
+          return fail(lead, SC_ERR_INVALID, "AutoTune proxy");
+        u.ratio[pairs[base + q].second] = ratio;
+      }
+      return SC_OK;
+    }));
+  }
+  // ---- the winners: their eigenvectors (one pair per utterance), then the lockstep k-means
+  std::vector<std::pair<int, double>> winners;
+  for (int z = 0; z < count; ++z)
+    if (!us[z].left) winners.emplace_back(z, us[z].best_p);
+  std::vector<Member> mb(kShortWidth);
+  SC_TRY(short_pairs_run(lead, cfg, rq, us, winners, fi, dif, em, [&](int base, int cnt) -> int {
+    std::vector<int> zs;
+    for (int q = 0; q < cnt; ++q) {
+      ShortUtterance& u = us[winners[base + q].first];
+      Member& m = mb[q];
+      m = Member();
+      m.index = u.index;
+      m.h = em[q].h;
+      m.eig = &em[q];
+      m.front.folded_rownorm = u.plan.icassp;
+      if (diags) memset(diags + u.index, 0, sizeof(sc_diag));
+      zs.push_back(q);
+    }
+    for (int at0 = 0; at0 < cnt; at0 += kGroupMax)
+      SC_TRY(cluster_members(lead, ns, cfg, labels, diags, mb.data(), zs.data() + at0,
+                             std::min(kGroupMax, cnt - at0), rq, SC_EIG_PATH_DENSE_JACOBI,
+                             SC_BATCH_ROUTE_GROUP_JACOBI, nullptr));
+    for (int q = 0; q < cnt; ++q) {
+      ShortUtterance& u = us[winners[base + q].first];
+      if (mb[q].state != 2) {
+        u.left = true;
+        continue;
+      }
+      if (diags && !u.plan.icassp) diags[u.index].diffuse_path = SC_DIFFUSE_PATH_NONE;
+      if (best_p) best_p[u.index] = u.best_p;
+      if (last_p) last_p[u.index] = u.last_p;
+    }
+    return SC_OK;
+  }));
+  for (int z = 0; z < count; ++z)
+    if (us[z].left) left->push_back(us[z].index);
+  return SC_OK;
+}
+}  // namespace
+
+extern "C" int sc_predict_batch_autotune(sc_handle h, const sc_array* xs,
+                                         const double* const* bands, int count,
+                                         const sc_config* cfg, const sc_autotune* at,
+                                         int64_t* const* labels, sc_diag* diags, double* best_p,
+                                         int group, double* last_p) {
+  if (!h) return SC_ERR_INVALID;
+  if (!xs || !labels || !at || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  if (group < 2)
+    return fail(h, SC_ERR_INVALID, "sc_predict_batch_autotune is the grouped form: group >= 2");
+  SC_TRY(validate_config(h, cfg));
+  if (at->proxy != SC_AUTOTUNE_PERCENTILE_OVER_NME &&
+      at->proxy != SC_AUTOTUNE_PERCENTILE_SQRT_OVER_NME)
+    return fail(h, SC_ERR_INVALID, "Unsupported value of AutoTuneProxy");
+  {
+    bool has_threshold = false;
+    for (int i = 0; i < cfg->n_ops; ++i) has_threshold |= cfg->ops[i] == SC_OP_ROW_WISE_THRESHOLD;
+    if (!has_threshold)
+      return fail(h, SC_ERR_INVALID,
+                  "AutoTune is only effective when the refinement sequence"
+                  "contains RowWiseThreshold");
+  }
+  SC_HIP(h, hipSetDevice(h->device));
+  bool device_source = false;
+  std::vector<int> ns(count);
+  for (int i = 0; i < count; ++i) {  // every descriptor before the first launch
+    SC_TRY(validate_array(h, xs + i));
+    if (!labels[i]) return fail(h, SC_ERR_INVALID, "NULL labels");
+    if (xs[i].cols != xs[0].cols)
+      return fail(h, SC_ERR_INVALID, "all utterances must be (n_i, d) with the same d");
+    ns[i] = (int)xs[i].rows;
+    device_source |= xs[i].location == SC_MEM_DEVICE;
+  }
+  SC_TRY(sc_clear_constraint(h));  // the handle's own resident constraint takes no part
+  h->last_routes.assign(count, SC_BATCH_ROUTE_SINGLE);
+  if (count == 0) return SC_OK;
+  if (device_source) SC_HIP(h, hipStreamSynchronize(h->stream));  // (as sc_predict_batch_arrays)
+  const int d = (int)xs[0].cols;
+  const EigRequest rq = make_eig_request(cfg);
+  // no band stays resident in any arena, and none is still on its way up, however the batch ends
+  struct Cleanup {
+    sc_handle h;
+    int rc = SC_OK;
+    ~Cleanup() {
+      for (sc_handle sub : h->gshort) {
+        if (rc != SC_OK) (void)hipStreamSynchronize(sub->stream);
+        (void)sc_clear_constraint(sub);
+      }
+      for (sc_handle lane : h->glanes) (void)sc_clear_constraint(lane);
+      (void)sc_clear_constraint(h);
+    }
+  } cleanup{h};
+  // ---- partition
+  SweepPlan probe;  // (which sequences the sweep groups: the configuration alone decides)
+  probe.icassp = grouped_front_covers(cfg);
+  probe.thr_sym_only = cfg->n_ops == 2 && cfg->ops[0] == SC_OP_ROW_WISE_THRESHOLD &&
+                       cfg->ops[1] == SC_OP_SYMMETRIZE;
+  const bool swept = (probe.icassp || probe.thr_sym_only) && cfg->kmeans_metric == kKmeansCosine &&
+                     !(cfg->constraint_name != SC_CONSTRAINT_NONE && !cfg->constraint_before_refinement);
+  std::vector<int> shorts, mids, single;
+  for (int i = 0; i < count; ++i) {
+    if (swept && ns[i] > 0 && ns[i] <= kDenseMax) shorts.push_back(i);
+    else if (swept && sym_group_eligible(ns[i], rq)) mids.push_back(i);
+    else single.push_back(i);
+  }
+  {  // do the arenas fit?  the short route: 2 x kShortWidth arenas of n = kDenseMax; a lane: a
+     // level's members (two matrices each) at its largest utterance.  Otherwise: route 0.
+    size_t free_b = 0, total_b = 0;
+    SC_HIP(h, hipMemGetInfo(&free_b, &total_b));
+    int largest = 0;
+    for (int i : mids) largest = std::max(largest, ns[i]);
+    const size_t arena = (size_t)80 << 20;  // (the allocator's granule per small arena)
+    size_t need = shorts.empty() ? 0 : 2 * (size_t)kShortWidth * arena;
+    need += (size_t)kGroupLanes * kGroupMax * (2 * (size_t)largest * matrix_ld(std::max(largest, 1)) *
+                                               sizeof(double) + (size_t)largest * 8192);
+    if ((double)need > 0.85 * (double)free_b) {
+      single.insert(single.end(), shorts.begin(), shorts.end());
+      single.insert(single.end(), mids.begin(), mids.end());
+      shorts.clear();
+      mids.clear();
+      std::sort(single.begin(), single.end());
+    }
+  }
+  // ---- 128 < n < 4096: dealt longest-first to the lanes, each its own handle, stream and thread
+  std::stable_sort(mids.begin(), mids.end(), [&](int a, int b) { return ns[a] > ns[b]; });
+  const int lanes = std::max(1, std::min(kGroupLanes, (int)mids.size()));
+  std::vector<int> lane_list[kGroupLanes];
+  {
+    double load[kGroupLanes] = {0.0};
+    for (int i : mids) {
+      int best = 0;
+      for (int l = 1; l < lanes; ++l)
+        if (load[l] < load[best]) best = l;
+      lane_list[best].push_back(i);
+      load[best] += 60.0 + 3.5e-5 * (double)ns[i] * ns[i];
+    }
+  }
+  sc_handle leads[kGroupLanes] = {h};
+  for (int l = 1; l < lanes; ++l) {
+    while ((int)h->glanes.size() < l) {
+      sc_handle lane = nullptr;
+      const int rc = sc_create(h->device, &lane);
+      if (rc != SC_OK) return cleanup.rc = fail(h, rc, "could not create a lane of the AutoTune batch");
+      lane->profile_level = 1;
+      h->glanes.push_back(lane);
+    }
+    leads[l] = h->glanes[l - 1];
+    leads[l]->blur_ext = h->blur_ext;
+    leads[l]->err.clear();
+  }
+  int32_t* routes = h->last_routes.data();
+  auto run_lane = [&](int l) -> int {
+    sc_handle lead = leads[l];
+    if (hipSetDevice(lead->device) != hipSuccess) return SC_ERR_HIP;
+    for (int i : lane_list[l]) {
+      const int rc = autotune_one(lead, xs[i], bands ? bands[i] : nullptr, cfg, at, labels[i],
+                                  diags ? diags + i : nullptr, best_p ? best_p + i : nullptr,
+                                  last_p ? last_p + i : nullptr);
+      if (rc != SC_OK) return rc;
+      routes[i] = SC_BATCH_ROUTE_GROUP_LANCZOS;
+    }
+    return SC_OK;
+  };
+  int lane_rc[kGroupLanes] = {SC_OK, SC_OK, SC_OK};
+  std::vector<std::thread> workers;
+  for (int l = 1; l < lanes; ++l) workers.emplace_back([&, l] { lane_rc[l] = run_lane(l); });
+  // ---- n <= 128 on the caller's thread: waves of kShortWidth utterances, largest first
+  int rc = SC_OK;
+  std::stable_sort(shorts.begin(), shorts.end(), [&](int a, int b) { return ns[a] > ns[b]; });
+  if (!shorts.empty()) rc = ensure_seed_table(h);
+  h->sweep_slot.clear();  // (the pair arenas are the sweep's member arenas)
+  h->groutes = routes;
+  for (size_t at0 = 0; at0 < shorts.size() && rc == SC_OK; at0 += kShortWidth)
+    rc = autotune_short_wave(h, xs, bands, ns.data(), d, cfg, at, rq, shorts.data() + at0,
+                             (int)std::min<size_t>(kShortWidth, shorts.size() - at0), labels, diags,
+                             best_p, last_p, &single);
+  h->groutes = nullptr;
+  if (rc == SC_OK && !mids.empty()) rc = lane_rc[0] = run_lane(0);
+  for (std::thread& t : workers) t.join();
+  for (int l = 1; l < lanes && rc == SC_OK; ++l)
+    if (lane_rc[l] != SC_OK) rc = fail(h, lane_rc[l], leads[l]->err);
+  // ---- n >= 4096, sequences the sweep does not group, members that left their route
+  std::sort(single.begin(), single.end());
+  for (size_t q = 0; q < single.size() && rc == SC_OK; ++q) {
+    const int i = single[q];
+    rc = autotune_one(h, xs[i], bands ? bands[i] : nullptr, cfg, at, labels[i],
+                      diags ? diags + i : nullptr, best_p ? best_p + i : nullptr,
+                      last_p ? last_p + i : nullptr);
+    routes[i] = SC_BATCH_ROUTE_SINGLE;
+  }
+  return cleanup.rc = rc;
 }

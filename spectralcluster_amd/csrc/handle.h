@@ -124,6 +124,10 @@ struct sc_handle_s {
   std::vector<sc_handle_s*> gshort;
   DevBuf gjtab;
   JacobiItem* h_gjtab = nullptr;
+  // a short AutoTune level (n <= kDenseMax, sc_eig_ncluster_sweep): the pair table of its front
+  DevBuf gsftab;
+  ShortFrontItem* h_gsftab = nullptr;
+  hipEvent_t gsftab_ev = nullptr;  // "the copy of the pinned table has been made"
   // route of every utterance of the last batch call (sc_last_batch_routes); `groutes`: where
   // a lead of the running batch reports (the caller handle's last_routes)
   std::vector<int32_t> last_routes;
@@ -368,6 +372,9 @@ struct FrontResult {
 };
 EigRequest make_eig_request(const sc_config* cfg);
 int upload_blur_weights(sc_handle h, const sc_config* cfg);  // into h->blurw, on h->stream
+// one refinement op `in` -> `out` (distinct buffers) with the single call's unfused kernel
+int run_refine_op(sc_handle h, int op, const sc_config* cfg, const double* in, double* out, int n,
+                  int ld);
 // `resume`: the stages before the eigensolver already ran (a FrontResult of this handle)
 // `stop_before_solver`: run the front exactly as a full call does -- every routing decision as
 // it is, unlike `front_only` -- then report where it left things and return before the solver

@@ -760,18 +760,13 @@ __global__ __launch_bounds__(kRowThreads) void k_row_stats_g(const GroupOf<Front
 //   GraphCut      : h = 1/(sqrt(deg)+eps)     c = h sqrt(a), p = -h^2 deg, t = sqrt(a)
 // with deg = a * rowsum(S) (laplacian.py:41 on W).  Eigenvector of the
 // reference matrix = normalise(t .* u) for an eigenvector u of Op.
-__device__ __forceinline__ void scaling_vectors_body(const double* __restrict__ rowmax,
-                                                     const double* __restrict__ rowsum, int n,
-                                                     int lap, int rownorm,
-                                                     double* __restrict__ c,
-                                                     double* __restrict__ p,
-                                                     double* __restrict__ t) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+// (one row: its maximum and sum in, c / p / t out)
+__device__ __forceinline__ void scaling_vectors_row(double rmax, double rsum, int lap, int rownorm,
+                                                    double* c, double* p, double* t) {
   const double eps = 1e-10;  // laplacian.py:6
-  const double a = rownorm ? 1.0 / rowmax[i] : 1.0;
+  const double a = rownorm ? 1.0 / rmax : 1.0;
   const double sa = sqrt(a);
-  const double deg = rownorm ? rowsum[i] / rowmax[i] : rowsum[i];
+  const double deg = rownorm ? rsum / rmax : rsum;
   double cv = sa, pv = 0.0, tv = sa;
   if (lap == SC_LAPLACIAN_UNNORMALIZED) {
     pv = -deg;
@@ -785,9 +780,19 @@ __device__ __forceinline__ void scaling_vectors_body(const double* __restrict__ 
     cv = h * sa;
     pv = -((h * deg) * h);
   }
-  c[i] = cv;
-  p[i] = pv;
-  t[i] = tv;
+  *c = cv;
+  *p = pv;
+  *t = tv;
+}
+__device__ __forceinline__ void scaling_vectors_body(const double* __restrict__ rowmax,
+                                                     const double* __restrict__ rowsum, int n,
+                                                     int lap, int rownorm,
+                                                     double* __restrict__ c,
+                                                     double* __restrict__ p,
+                                                     double* __restrict__ t) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  scaling_vectors_row(rownorm ? rowmax[i] : 1.0, rowsum[i], lap, rownorm, c + i, p + i, t + i);
 }
 // flags (may be nullptr): thread 0 also prepares the solver's flag words -- flags[12] (non-finite
 // input) starts from the zero-embedding-row word of the affinity stage (symflag[1], left as it is:
@@ -825,6 +830,145 @@ __global__ void k_check_finite(const double* __restrict__ a, const double* __res
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   if (!isfinite(a[i]) || !isfinite(b[i])) *flag = 1;
+}
+
+// ---- the per-value front of a short AutoTune level (n <= kDenseMax) ---------------------
+// One workgroup per (matrix, p) pair, descriptors from a table in device memory.  The n x n
+// source (the blurred matrix of the ICASSP2018 sequence, or the affinity itself) is staged in LDS
+// once and read from there by the three steps the single call runs as three or four launches:
+//   cut      RowMax: max of the row (diagonal zeroed first when it is preserved) times p;
+//            Percentile: the ranks prev / prev + 1 of the row by counting -- every lane counts
+//            the keys below and up to its own two -- and numpy's _lerp (k_row_percentile_cut)
+//   entries  thr + sym with the argument order of threshold_symmetrize_body: the entry whose
+//            64-row block comes first is the first argument
+//   stats    (no Diffuse behind it) row maximum and sum in the order of row_stats_body -- a lane
+//            adds its column pair, the wave folds by xor, the three idle waves of the 256-thread
+//            form add their zeros -- then scaling_vectors_row and the solver's flag words
+// Plain vector stores, no atomics; every result is what the kernels it replaces store.
+constexpr int kShortFrontMatrix = kDenseMax * (kDenseMax + 1);  // doubles: n rows of pitch n | 1
+constexpr int kShortFrontLdsBytes = (kShortFrontMatrix + 3 * kDenseMax) * (int)sizeof(double);
+__global__ __launch_bounds__(256) void k_short_sweep_front(
+    const ShortFrontItem* __restrict__ table, int threshold_type, double mult, int binarize,
+    int symtype, int preserve_diag, int lap) {
+  extern __shared__ __attribute__((aligned(16))) double sf_lds[];
+  const ShortFrontItem it = table[blockIdx.x];
+  const int n = it.n, ld = it.ld;
+  if (n < 1 || n > kDenseMax) return;  // (workgroup-uniform)
+  const int P = n | 1;                 // odd pitch: the transposed reads spread over the banks
+  double* L = sf_lds;
+  double* cutv = sf_lds + kShortFrontMatrix;
+  double* rmax = cutv + kDenseMax;
+  double* rsum = rmax + kDenseMax;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int e = tid; e < n * n; e += 256) {
+    const int i = e / n, j = e - i * n;
+    L[i * P + j] = it.src[(size_t)i * ld + j];
+  }
+  __syncthreads();
+  // ---- cut: one wave per row, lane l holds the columns l and l + 64
+  int prev = 0, next = 0;
+  double gamma = 0.0;
+  if (threshold_type == SC_THRESHOLD_PERCENTILE) percentile_position(n, it.p, &prev, &next, &gamma);
+  for (int row = wave; row < n; row += 4) {
+    const double* x = L + row * P;
+    auto at = [&](int j) { return (preserve_diag && j == row) ? 0.0 : x[j]; };
+    const int j0 = lane, j1 = lane + 64;
+    double c;
+    if (threshold_type == SC_THRESHOLD_PERCENTILE) {
+      const unsigned long long k0 = j0 < n ? f64_key(at(j0)) : 0ull;
+      const unsigned long long k1 = j1 < n ? f64_key(at(j1)) : 0ull;
+      int lt0 = 0, le0 = 0, lt1 = 0, le1 = 0;
+      for (int j = 0; j < n; ++j) {
+        const unsigned long long k = f64_key(at(j));
+        lt0 += k < k0;
+        le0 += k <= k0;
+        lt1 += k < k1;
+        le1 += k <= k1;
+      }
+      // the key of rank r: the one with (keys below it) <= r < (keys up to it)
+      auto rank_key = [&](int r) -> unsigned long long {
+        const bool hit0 = j0 < n && lt0 <= r && r < le0;
+        const bool hit1 = j1 < n && lt1 <= r && r < le1;
+        const unsigned long long mine = hit0 ? k0 : k1;
+        const unsigned long long who = __ballot(hit0 || hit1);
+        return __shfl(mine, who != 0ull ? __ffsll((long long)who) - 1 : 0);  // (0 <= r < n: a hit)
+      };
+      const double a = key_f64(rank_key(prev));
+      const double b = next != prev ? key_f64(rank_key(next)) : a;
+      const double diff = b - a;
+      c = gamma >= 0.5 ? b - diff * (1.0 - gamma) : a + diff * gamma;
+    } else {
+      double m = -INFINITY;
+      if (j0 < n) m = fmax(m, at(j0));
+      if (j1 < n) m = fmax(m, at(j1));
+      c = wave_max(m) * it.p;
+    }
+    if (lane == 0) {
+      cutv[row] = c;
+      it.cut[row] = c;
+    }
+  }
+  __syncthreads();
+  // ---- entries (+ row statistics): one wave per row, lane l holds the columns 2l and 2l + 1
+  const bool stats = it.rowmax != nullptr;
+  auto thr = [&](int r, int c) {
+    double v = L[r * P + c];
+    v = v < cutv[r] ? v * mult : (binarize ? 1.0 : v);
+    if (preserve_diag && r == c) v = 1.0;
+    return v;
+  };
+  auto entry = [&](int i, int j) {
+    const bool upper = (i >> 6) <= (j >> 6);
+    const double a = upper ? thr(i, j) : thr(j, i);
+    const double b = upper ? thr(j, i) : thr(i, j);
+    return symtype == SC_SYMMETRIZE_MAX ? fmax(a, b) : 0.5 * (a + b);
+  };
+  for (int row = wave; row < n; row += 4) {
+    const int j = 2 * lane;
+    double m = -INFINITY, s = 0.0;
+    if (j < n) {
+      double2 o;
+      o.x = entry(row, j);
+      m = fmax(m, o.x);
+      s += o.x;
+      if (j + 1 < n) {
+        o.y = entry(row, j + 1);
+        m = fmax(m, o.y);
+        s += o.y;
+        *reinterpret_cast<double2*>(it.out + (size_t)row * ld + j) = o;
+      } else {
+        it.out[(size_t)row * ld + j] = o.x;
+      }
+    }
+    if (stats) {
+      m = wave_max(m);
+      s = wave_sum(s);
+      if (lane == 0) {
+        rmax[row] = fmax(fmax(m, -INFINITY), fmax(-INFINITY, -INFINITY));
+        rsum[row] = (s + 0.0) + (0.0 + 0.0);
+      }
+    }
+  }
+  if (!stats) return;  // (workgroup-uniform)
+  __syncthreads();
+  int bad = 0;
+  if (tid < n) {
+    double cv, pv, tv;
+    scaling_vectors_row(1.0, rsum[tid], lap, 0, &cv, &pv, &tv);
+    it.rowmax[tid] = rmax[tid];
+    it.rowsum[tid] = rsum[tid];
+    it.cvec[tid] = cv;
+    it.pvec[tid] = pv;
+    it.tvec[tid] = tv;
+    bad = !isfinite(cv) || !isfinite(pv);
+  }
+  bad = __syncthreads_or(bad);
+  if (tid == 0) {
+    it.flags[12] = (bad || (it.symflag != nullptr && it.symflag[1] != 0)) ? 1 : 0;
+    it.flags[13] = 0;
+    it.flags[14] = 0;
+    it.flags[15] = 0;
+  }
 }
 
 // ---- L1: materialised Laplacian for the stage API (laplacian.py:24-60) --------
@@ -1078,6 +1222,14 @@ void launch_scaling_vectors_group(hipStream_t s, const FrontItem* items, int cou
   if (nmax == 0) return;
   hipLaunchKernelGGL(k_scaling_vectors_g, dim3((nmax + 255) / 256, count), dim3(256), 0, s, g,
                      laplacian_type, row_normalized);
+}
+void launch_short_sweep_front(hipStream_t s, const ShortFrontItem* table, int count,
+                              int threshold_type, double mult, int binarize, int symtype,
+                              int preserve_diag, int laplacian_type) {
+  if (count < 1) return;
+  SC_OPT_IN_LDS(k_short_sweep_front, kShortFrontLdsBytes);
+  hipLaunchKernelGGL(k_short_sweep_front, dim3(count), dim3(256), kShortFrontLdsBytes, s, table,
+                     threshold_type, mult, binarize, symtype, preserve_diag, laplacian_type);
 }
 void launch_check_finite(hipStream_t s, const double* a, const double* b, int n, int* flag) {
   hipLaunchKernelGGL(k_check_finite, dim3((n + 255) / 256), dim3(256), 0, s, a, b, n, flag);

@@ -382,6 +382,27 @@ void launch_threshold_symmetrize_group(hipStream_t s, const FrontItem* items, in
                                        int preserve_diag, bool cut_ready = false,
                                        const TsDigits* digits = nullptr);
 void launch_cut_from_partials_group(hipStream_t s, const FrontItem* items, int count, double p);
+// One (matrix, p) pair of a short AutoTune level (n <= kDenseMax, batch_group.hip): the per-value
+// part of the front in ONE workgroup -- row cut at the pair's own p, threshold, symmetrise and,
+// where no Diffuse follows (rowmax != nullptr), row statistics, scaling vectors and the solver's
+// flag words.  The descriptors of a launch are a table in device memory.
+struct ShortFrontItem {
+  const double* src;  // n x n, row pitch ld: the matrix every value of the level thresholds
+  int n, ld;
+  double p;           // this pair's p_percentile
+  double* out;        // thresholded + symmetrised, row pitch ld
+  double* cut;
+  double* rowmax;     // nullptr: a Diffuse follows, its launchers leave the statistics
+  double* rowsum;
+  double* cvec;
+  double* pvec;
+  double* tvec;
+  int* flags;         // [12] non-finite word, [13..15] the chain's latch (cleared)
+  const int* symflag; // [1]: a zero / non-finite embedding row was seen (may be null)
+};
+void launch_short_sweep_front(hipStream_t s, const ShortFrontItem* table, int count,
+                              int threshold_type, double mult, int binarize, int symtype,
+                              int preserve_diag, int laplacian_type);
 void launch_scaling_vectors_group(hipStream_t s, const FrontItem* items, int count,
                                   int laplacian_type, int row_normalized);
 struct GatherItem {  // T == nullptr: idle

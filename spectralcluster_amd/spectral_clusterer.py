@@ -17,6 +17,7 @@ than the two vectors and callables are out of the device scope.  Those raise
 
 from __future__ import annotations
 
+import copy
 import ctypes
 import typing
 
@@ -377,7 +378,8 @@ class SpectralClusterer:
   def predict_batch(self, utterances: typing.Sequence,
                     streams: typing.Optional[int] = None,
                     group: typing.Optional[int] = None,
-                    constraint_matrices: typing.Optional[typing.Sequence] = None
+                    constraint_matrices: typing.Optional[typing.Sequence] = None,
+                    autotune_from_entry_state: bool = False
                     ) -> typing.List[np.ndarray]:
     """Independent predict() calls (the reference has no batch API: a batch is a
     Python loop).
@@ -427,7 +429,27 @@ class SpectralClusterer:
     whose length is not its utterance's raises the ValueError of predict() before anything is
     launched.  Anything else -- a dense ndarray among the entries, AutoTune (the Turn-to-Diarize
     preset), group=1, `streams` -- runs as per-utterance `predict(u, c)` calls (routes all 0).
+
+    `autotune_from_entry_state` (a clusterer without AutoTune ignores it).  `AutoTune.tune`
+    leaves the object's range and step narrowed, so the default loop searches utterance i + 1 on
+    the grid utterance i left behind: results depend on the order of the batch.  With the flag
+    every utterance is searched from the state the `AutoTune` object has when the call is
+    entered -- what a fresh clusterer per utterance gives -- and the object is left as it was
+    found.  The missing-RowWiseThreshold ValueError and the ValueError of a `ConstraintMatrix`
+    of the wrong length are raised before anything is launched.  Afterwards `last_batch_best_p`
+    holds the winning p_percentile per utterance, `last_batch_diags` the winner's diagnostics,
+    and `refinement_options.p_percentile` the last value evaluated for the last utterance.  It
+    is ONE `sc_predict_batch_autotune` call when the clusterer is otherwise one the library batch
+    covers, the metric is cosine, `group` is not 1, `streams` is not given and every constraint
+    is a `ConstraintMatrix` or None: utterances of n <= 128 in waves whose (utterance, p) pairs
+    share one front launch and one Jacobi launch per 64 pairs and level (route 2), 128 < n < 4096
+    dealt to three lanes that each run the per-utterance search on a handle, stream and thread
+    of their own (route 1), the rest per utterance on the caller's handle (route 0).  Otherwise
+    -- a dense ndarray constraint among them -- every utterance runs predict() on a copy of the
+    AutoTune object (routes all 0), with the same results.
     """
+    if autotune_from_entry_state and self.autotune is not None:
+      return self._predict_batch_entry_state(utterances, constraint_matrices, streams, group)
     library_batch = self._library_batch_covers()
     banded = None  # the ConstraintMatrix (or None) of every utterance of a constrained batch
     if constraint_matrices is not None:
@@ -516,6 +538,112 @@ class SpectralClusterer:
       for src in sources:
         src.release()
     self._batch_report(handle, diags, count)
+    return labels
+
+  def _predict_batch_entry_state(self, utterances: typing.Sequence,
+                                 constraint_matrices: typing.Optional[typing.Sequence],
+                                 streams: typing.Optional[int] = None,
+                                 group: typing.Optional[int] = None
+                                 ) -> typing.List[np.ndarray]:
+    """predict_batch(autotune_from_entry_state=True) on a clusterer with AutoTune: every
+    utterance searched from the state the AutoTune object has now -- ONE
+    `sc_predict_batch_autotune` call where the library batch covers the clusterer, else
+    predict() per utterance on a copy of the object."""
+    count = len(utterances)
+    if constraint_matrices is None:
+      constraint_matrices = [None] * count
+    elif len(constraint_matrices) != count:
+      raise ValueError("constraint_matrices must be as long as the batch")
+    sequence = self.refinement_options.refinement_sequence or []
+    if RefinementName.RowWiseThreshold not in sequence:
+      raise ValueError(
+          "AutoTune is only effective when the refinement sequence"
+          "contains RowWiseThreshold")
+    if self.constraint_options is not None:
+      for u, cm in zip(utterances, constraint_matrices):
+        if isinstance(cm, constraint_lib.ConstraintMatrix):
+          n = int(np.shape(u)[0])
+          # (predict()'s check and message: _set_constraint)
+          self.constraint_options.constraint_operator.check_input(
+              np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)), cm)
+    entry = self.autotune
+    try:  # (a metric that is not on the device raises in predict(), as it does today)
+      cosine = _lib.kmeans_metric_code(self.custom_dist) == _lib.KMEANS_METRICS["cosine"]
+    except (ValueError, _lib.UnsupportedOnDeviceError):
+      cosine = False
+    self.autotune = None
+    try:
+      covered = self._library_batch_covers()
+    finally:
+      self.autotune = entry
+    if (covered and cosine and streams is None and (group is None or int(group) > 1) and count and
+        all(c is None or isinstance(c, constraint_lib.ConstraintMatrix)
+            for c in constraint_matrices)):
+      return self._autotune_library_batch(utterances, constraint_matrices,
+                                          16 if group is None else int(group))
+    labels, best_p, diags = [], [], []
+    try:
+      for u, cm in zip(utterances, constraint_matrices):
+        self.autotune = copy.deepcopy(entry)
+        self.last_best_p = None
+        labels.append(self.predict(u, cm))
+        # (None: the utterance left predict() before the search -- fallback, size reduction)
+        best_p.append(self.last_best_p)
+        diags.append(self.last_diag)
+    finally:
+      self.autotune = entry
+    self.last_batch_best_p = best_p
+    self.last_batch_diags = diags
+    self.last_batch_routes = [_lib.BATCH_ROUTE_SINGLE] * count
+    return labels
+
+  def _autotune_library_batch(self, utterances: typing.Sequence,
+                              constraint_matrices: typing.Sequence,
+                              group: int) -> typing.List[np.ndarray]:
+    """ONE `sc_predict_batch_autotune` call; the checks of _predict_batch_entry_state passed."""
+    for u in utterances:
+      if isinstance(u, np.ndarray) and u.ndim != 2:
+        raise ValueError("all utterances must be (n_i, d) with the same d")
+    count = len(utterances)
+    sources = []
+    try:
+      with _lib.use_device(self.device):
+        for u in utterances:
+          sources.append(_dlpack.describe(u, self._handle))
+      d = sources[0].shape[1]
+      if any(src.shape[1] != d for src in sources):
+        raise ValueError("all utterances must be (n_i, d) with the same d")
+      bands = []
+      for src, cm in zip(sources, constraint_matrices):
+        if cm is None or self.constraint_options is None:
+          bands.append(None)
+          continue
+        n = src.shape[0]
+        band = np.zeros(max(n - 1, 1), dtype=np.float64)  # (n = 1: no values, a valid pointer)
+        band[:n - 1] = cm.band()
+        bands.append(band)
+      labels = [np.empty(src.shape[0], dtype=np.int64) for src in sources]
+      handle = self._handle()
+      lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
+      diags = (_lib.ScDiag * count)()
+      arrays = (_lib.ScArray * count)(*[src.array for src in sources])
+      bp = (ctypes.POINTER(ctypes.c_double) * count)(
+          *[None if b is None else _lib.as_double_p(b) for b in bands])
+      best_p = np.zeros(count, dtype=np.float64)
+      last_p = np.zeros(count, dtype=np.float64)
+      state = self.autotune.to_struct()
+      handle.check(handle.lib.sc_predict_batch_autotune(
+          handle.raw, arrays, bp, count, self.build_config(), ctypes.byref(state), lp, diags,
+          _lib.as_double_p(best_p), int(group), _lib.as_double_p(last_p)), TypeError)
+    finally:
+      for src in sources:
+        src.release()
+    self._batch_report(handle, diags, count)
+    self.last_batch_best_p = [float(p) for p in best_p]
+    # reference closure: p_percentile stays at the last value evaluated (spectral_clusterer.py:277)
+    self.refinement_options.p_percentile = float(last_p[-1])
+    self.last_best_p = float(best_p[-1])
+    self.last_diag = diags[count - 1]
     return labels
 
   def _library_batch_covers(self, min_embeddings_met: bool = False) -> bool:
