@@ -666,11 +666,19 @@ int sc_stage_krylov_state(sc_handle h, int32_t* info, double* q, double* t, doub
  *                           launch of (matrix, p) pairs of a short level (k_short_sweep_front,
  *                           cut kernel 4), the Diffuse product through the grouped launcher;
  *                           count 2 .. 64.
+ *   SC_FRONT_ROUTE_SHORT_WAVE   count 1 .. 64 embeddings matrices xs[z] (ns[z] <= 128, d <= 512):
+ *                           the front of one wave of the short route of sc_predict_batch_grouped
+ *                           (k_short_wave_front, cut kernel 5: one launch for the wave between the
+ *                           grouped GEMMs), members in the order given.  Every array is bit for
+ *                           bit the SINGLE route's for that member alone; cropval is written
+ *                           where the single call writes it.  A member above 128 rows, d > 512,
+ *                           or a sequence other than [CropDiagonal] [GaussianBlur] RowWiseThreshold
+ *                           Symmetrize [Diffuse] [RowWiseNormalize]: SC_ERR_UNSUPPORTED.
  * A configuration the route's grouped code does not cover (a group member below n = 256 or a
  * sequence other than ICASSP2018's; a sweep the product would evaluate one by one) returns
  * SC_ERR_UNSUPPORTED: the entry never takes another path quietly. */
 enum { SC_FRONT_ROUTE_SINGLE = 0, SC_FRONT_ROUTE_GROUPED = 1, SC_FRONT_ROUTE_SWEEP = 2,
-       SC_FRONT_ROUTE_SHORT_SWEEP = 3 };
+       SC_FRONT_ROUTE_SHORT_SWEEP = 3, SC_FRONT_ROUTE_SHORT_WAVE = 4 };
 enum {
   SC_FRONT_INFO_DIFFUSE_PATH = 0,   /* SC_DIFFUSE_PATH_NONE / _EXPLICIT / _FREE */
   SC_FRONT_INFO_SYMMETRIC = 1,
@@ -686,8 +694,12 @@ enum {
                                        would form S after all */
   SC_FRONT_INFO_CROP_SOURCE = 10,   /* 0 no value vector, 1 GEMM epilogue, 2 k_crop_value */
   SC_FRONT_INFO_CUT_KERNEL = 11,    /* 0 none, 1 k_cut_from_partials, 2 k_cut_from_rows,
-                                       3 k_row_percentile_cut, 4 k_short_sweep_front */
+                                       3 k_row_percentile_cut, 4 k_short_sweep_front,
+                                       5 k_short_wave_front */
   SC_FRONT_INFO_WRITTEN = 12,       /* bit i: the i-th pointer of sc_front_out was filled */
+  SC_FRONT_INFO_LAUNCHES = 13,      /* SC_FRONT_ROUTE_SHORT_WAVE: kernel launches the route
+                                       enqueued for the whole front of the call (ingest apart);
+                                       0 on the other routes */
   SC_FRONT_INFO_COUNT = 16
 };
 typedef struct sc_front_out {

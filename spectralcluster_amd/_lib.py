@@ -146,10 +146,13 @@ _c_double_p = ctypes.POINTER(ctypes.c_double)
 # sc_stage_front: route, and the slots of sc_front_out.info
 SC_FRONT_ROUTE_SINGLE, SC_FRONT_ROUTE_GROUPED, SC_FRONT_ROUTE_SWEEP = range(3)
 SC_FRONT_ROUTE_SHORT_SWEEP = 3  # a level of n <= 128: (matrix, p) pairs, one front launch
+SC_FRONT_ROUTE_SHORT_WAVE = 4   # a wave of the short route of a batch: up to 64 members of n <= 128
 SC_FRONT_INFO_COUNT = 16
 FRONT_INFO_NAMES = ("diffuse_path", "symmetric", "folded_rownorm", "free_op", "digits_fused",
                     "blur_kernel", "blur_rows", "free_candidates", "free_overflow_rows",
-                    "free_forms_s", "crop_source", "cut_kernel", "written")
+                    "free_forms_s", "crop_source", "cut_kernel", "written", "launches")
+SC_FRONT_INFO_CUT_KERNEL = FRONT_INFO_NAMES.index("cut_kernel")  # 5: k_short_wave_front
+SC_FRONT_INFO_LAUNCHES = FRONT_INFO_NAMES.index("launches")      # (the short wave route only)
 FRONT_OUTPUTS = ("a0", "cropval", "cut", "a", "s", "rowmax", "rowsum", "c", "p", "t")
 
 

@@ -230,7 +230,7 @@ extern "C" int sc_destroy(sc_handle h) {
                     &h->Hbuf,  &h->hsq,   &h->colnorm, &h->flags,  &h->E,     &h->Ek,   &h->Eio,
                     &h->td_d,  &h->td_e,  &h->td_theta, &h->td_work, &h->td_tau, &h->td_panel, &h->mvsym,
                     &h->kXc,   &h->kxsq,  &h->kclosest, &h->kcand, &h->kenorm, &h->krnd,
-                    &h->kcent, &h->klab32, &h->klab64, &h->kinfo, &h->kchain, &h->gkrnd, &h->gpack, &h->gypack, &h->ginfo, &h->glabels, &h->gjtab, &h->gsftab,
+                    &h->kcent, &h->klab32, &h->klab64, &h->kinfo, &h->kchain, &h->gkrnd, &h->gpack, &h->gypack, &h->ginfo, &h->glabels, &h->gjtab, &h->gsftab, &h->gswtab,
                     &h->kbig, &h->kbigw, &h->fq, &h->ft32, &h->fy1, &h->fR, &h->fscal, &h->fwords, &h->fcand, &h->fY, &h->fsplit, &h->fypart, &h->frpart, &h->fq2part, &h->fmx64, &h->ftau64, &h->fplan, &h->Xalt, &h->Xstage, &h->gneg};
   for (DevBuf* b : bufs)
     if (b->p) hipFree(b->p);
@@ -256,6 +256,7 @@ extern "C" int sc_destroy(sc_handle h) {
   if (h->h_gypack) hipHostFree(h->h_gypack);
   if (h->h_gjtab) hipHostFree(h->h_gjtab);
   if (h->h_gsftab) hipHostFree(h->h_gsftab);
+  if (h->h_gswtab) hipHostFree(h->h_gswtab);
   if (h->gsftab_ev) hipEventDestroy(h->gsftab_ev);
   if (h->h_ginfo) hipHostFree(h->h_ginfo);
   if (h->h_glabels) hipHostFree(h->h_glabels);

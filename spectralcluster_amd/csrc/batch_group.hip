@@ -433,6 +433,174 @@ int enqueue_front_grouped(sc_handle lead, const sc_array* xs, const int* ns, int
   return SC_OK;
 }
 
+// What the wave front of the short route covers: an in-order CropDiagonal, GaussianBlur (weights
+// in the config: radius <= 32), then RowWiseThreshold + Symmetrize (every option of the two),
+// optionally Diffuse, optionally a last RowWiseNormalize, which folds into the scaling vectors.
+// The result is symmetric by construction.  (Sequences without the threshold + symmetrise pair
+// keep the member-by-member front.)
+bool short_wave_covers(const sc_config* cfg, ShortWaveOps* ops) {
+  ShortWaveOps o;
+  memset(&o, 0, sizeof(o));
+  int i = 0;
+  auto take = [&](int op) { return i < cfg->n_ops && cfg->ops[i] == op ? (++i, true) : false; };
+  o.crop = take(SC_OP_CROP_DIAGONAL);
+  if (take(SC_OP_GAUSSIAN_BLUR)) {
+    if (cfg->blur_radius > SC_MAX_BLUR_RADIUS) return false;
+    o.blur_radius = cfg->blur_radius;  // (0: gaussian_filter degenerates to a copy)
+  }
+  if (!take(SC_OP_ROW_WISE_THRESHOLD) || !take(SC_OP_SYMMETRIZE)) return false;
+  o.diffuse = take(SC_OP_DIFFUSE);
+  o.rownorm = take(SC_OP_ROW_WISE_NORMALIZE);
+  if (i != cfg->n_ops) return false;
+  o.threshold_type = cfg->threshold_type;
+  o.binarize = cfg->binarize;
+  o.symtype = cfg->symmetrize_type;
+  o.preserve_diag = cfg->preserve_diagonal;
+  o.p = cfg->p_percentile;
+  o.mult = cfg->soft_multiplier;
+  o.lap = cfg->laplacian_type;
+  if (ops) *ops = o;
+  return true;
+}
+// d <= kShortWaveMaxD: a single call of n <= 128 runs its affinity product as whole-K tiles
+// (gemm_f64.hip launch_variant: "if (K <= 512 && full == 0) ksplit = 1"), which is what the
+// grouped product computes -- the wave front's bits are then the single call's.  The Diffuse
+// product has K = n <= 128.
+constexpr int kShortWaveMaxD = 512;
+
+// Stages before the eigensolver of one WAVE of the short route (up to kShortWidth members of
+// n <= kDenseMax) on the bank's stream: the row normalisation and the two GEMMs through the group
+// launchers, kGroupMax members per launch; everything between them ONE launch for the wave
+// (k_short_wave_front, a workgroup per member), descriptors from a table that goes up in one copy
+// (half `bank` of lead->gswtab).  3 ceil(count / 16) + 3 kernel launches with a Diffuse,
+// 2 ceil(count / 16) + 2 without, besides the members' ingest.  Per member the values a single
+// call stores (tests/test_gpu_short_wave_front.py).
+int enqueue_front_short_wave(sc_handle lead, const sc_array* xs, const int* ns, int d,
+                             const sc_config* cfg, sc_diag* diags, const int* idx, int count,
+                             int slot0, Member* mb, int bank, const ShortWaveOps& ops) {
+  hipStream_t s = lead->gbank_stream[bank];
+  const size_t half = (size_t)kShortWidth * sizeof(ShortWaveItem);
+  SC_TRY(grow(lead, lead->gswtab, kGroupBanks * half));
+  if (!lead->h_gswtab)
+    SC_HIP(lead, hipHostMalloc(reinterpret_cast<void**>(&lead->h_gswtab), kGroupBanks * half));
+  // (the pinned half is rewritten: the wave that used it last has been solved, its copy read)
+  ShortWaveItem* htab = lead->h_gswtab + (size_t)bank * kShortWidth;
+  ShortWaveItem* dtab = ptr<ShortWaveItem>(lead->gswtab) + (size_t)bank * kShortWidth;
+  std::vector<FrontItem> fi(count);
+  std::vector<GemmGroupItem> aff(count), dif(count);
+  memset(fi.data(), 0, fi.size() * sizeof(FrontItem));
+  for (int z = 0; z < count; ++z) {
+    Member& m = mb[z];
+    m = Member();
+    m.index = idx[z];
+    SC_TRY(group_slot(lead, slot0 + z, &m.h, &lead->gshort));
+    sc_handle h = m.h;
+    h->err.clear();
+    const int n = ns[m.index];
+    if (n > kDenseMax) return fail(lead, SC_ERR_INVALID, "short wave: a member above 128 rows");
+    int rc = ingest_embeddings(h, xs[m.index], false, s);
+    if (rc == SC_OK) rc = ensure_eig(h, n);
+    if (rc == SC_OK) rc = ensure_tilemap(h, n);
+    if (rc == SC_OK) rc = grow(h, h->symflag, 16);
+    if (rc != SC_OK) {
+      lead->err = h->err;
+      return rc;
+    }
+    h->n = n;
+    h->d = d;
+    h->ldn = matrix_ld(n);
+    h->ldx = round_up(d, 16);
+    h->n_vec = 0;
+    h->nev = 0;
+    h->have_x = h->have_affinity = true;
+    h->have_cropval = ops.crop != 0;  // (the front kernel writes the vector only then)
+    h->affinity_symmetric = h->affinity_from_embeddings = true;
+    h->constraint_applied = false;
+    h->have_constraint = h->constraint_banded = false;
+    h->qn = 0;
+    if (diags) memset(diags + m.index, 0, sizeof(sc_diag));
+    FrontItem& f = fi[z];
+    f.X = ptr<double>(h->X);
+    f.Xn = ptr<double>(h->Xn);
+    f.ldx = h->ldx;
+    f.n = n;
+    f.d = d;
+    f.ldn = h->ldn;
+    f.symflag = ptr<int>(h->symflag);
+    f.flags = ptr<int>(h->flags);
+    aff[z] = GemmGroupItem();
+    aff[z].A = f.Xn;
+    aff[z].lda = h->ldx;
+    aff[z].C = ptr<double>(h->A0);
+    aff[z].ldc = h->ldn;
+    aff[z].n = n;
+    aff[z].K = d;
+    aff[z].tilemap = h->tilemap_cur;
+    aff[z].partial_max = ptr<double>(h->statp);
+    dif[z] = GemmGroupItem();
+    dif[z].A = ptr<double>(h->B2);
+    dif[z].lda = h->ldn;
+    dif[z].C = ptr<double>(h->B1);
+    dif[z].ldc = h->ldn;
+    dif[z].n = n;
+    dif[z].K = n;
+    dif[z].tilemap = h->tilemap_cur;
+    dif[z].partial_max = ptr<double>(h->statp);
+    dif[z].partial_sum = ptr<double>(h->statp) + n;  // (one tile: gemm_tile_dim(n) = 1)
+    ShortWaveItem& it = htab[z];
+    it.n = n;
+    it.ld = h->ldn;
+    it.a0 = ptr<double>(h->A0);
+    it.stat0 = ptr<double>(h->statp);
+    it.cropval = ptr<double>(h->cropval);
+    it.out = ptr<double>(h->B2);
+    it.cut = ptr<double>(h->cut);
+    it.stat1 = ptr<double>(h->statp);
+    it.rowmax = ptr<double>(h->rowmax);
+    it.rowsum = ptr<double>(h->rowsum);
+    it.cvec = ptr<double>(h->cvec);
+    it.pvec = ptr<double>(h->pvec);
+    it.tvec = ptr<double>(h->tvec);
+    it.flags = ptr<int>(h->flags);
+    it.symflag = ptr<int>(h->symflag);
+    m.front.matrix = ops.diffuse ? ptr<double>(h->B1) : ptr<double>(h->B2);
+    m.front.scratch = ops.diffuse ? ptr<double>(h->B2) : ptr<double>(h->B1);
+    m.front.ld = h->ldn;
+    m.front.symmetric = true;
+    m.front.folded_rownorm = ops.rownorm != 0;
+    m.front.laplacian_type = cfg->laplacian_type;
+    m.front.chain_flags_cleared = true;
+    m.front.diffuse_explicit = ops.diffuse != 0;
+    m.front.crop_source = ops.crop ? 1 : 0;  // (the affinity epilogue's partials)
+    m.front.cut_kernel = 5;                  // k_short_wave_front
+  }
+  int launches = 0;
+  SC_HIP(lead, hipMemcpyAsync(dtab, htab, (size_t)count * sizeof(ShortWaveItem),
+                              hipMemcpyHostToDevice, s));
+  launch_short_wave_init(s, dtab, count);
+  ++launches;
+  for (int at = 0; at < count; at += kGroupMax) {
+    const int c = std::min(kGroupMax, count - at);
+    launch_front_begin_group(s, fi.data() + at, c, true, false);
+    launch_gemm_nt_group(s, aff.data() + at, c, kEpiAffinity, 2, false);
+    launches += 2;
+  }
+  launch_short_wave_front(s, dtab, count, ops, ptr<double>(lead->blurw));
+  ++launches;
+  if (ops.diffuse) {
+    for (int at = 0; at < count; at += kGroupMax) {
+      launch_gemm_nt_group(s, dif.data() + at, std::min(kGroupMax, count - at), kEpiNone, 1, false);
+      ++launches;
+    }
+    launch_short_wave_scaling(s, dtab, count, cfg->laplacian_type, ops.rownorm);
+    ++launches;
+  }
+  lead->gsw_launches = launches;
+  SC_TRY(check_last(lead, "short wave front launch"));
+  SC_HIP(lead, hipEventRecord(lead->gbank_ev[bank], s));
+  return SC_OK;
+}
+
 // k-means of up to kGroupMax members whose eigensolver has finished (mb[zs[e]].eig), in lockstep
 // on the owner's stream, and their labels; both routes of the grouped batch end here.  A member
 // whose solve or cluster count left the common path gets state 1 (single_path_members below).
@@ -651,16 +819,24 @@ int finish_group(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* c
 // n = 80 .. 128, longer than a whole call at n = 8192 -- and a batch of such utterances ran them
 // one after the other.  Here a wave of up to kShortWidth of them shares ONE Jacobi launch, a
 // workgroup (a CU) each (eig_driver.hip: dense_topk_group), and then the lockstep k-means chain
-// of the grouped route, kGroupMax members at a time.  The fronts are the single call's, member by
-// member on the member's stream, enqueued one wave ahead of the wave being solved.  Same kernel
-// bodies and arguments per member as its own sc_predict (eigenvalues within 1e-10 relative).
+// of the grouped route, kGroupMax members at a time.  The front of a wave is enqueued one wave
+// ahead of the wave being solved: ONE chain of launches for the wave on its bank's stream
+// (enqueue_front_short_wave) when the batch has no constraint bands, d <= 512 and the refinement
+// sequence is one short_wave_covers() names; else the single call's front, member by member on the
+// member's stream (also with SC_SHORT_FRONT_MEMBERWISE=1).  Same kernel bodies and arguments per
+// member as its own sc_predict (eigenvalues within 1e-10 relative; the wave front's bits are the
+// single call's).
 // Eigensolver and k-means of one wave whose fronts are enqueued:
 int finish_short_wave(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* const* labels,
                       sc_diag* diags, Member* mb, int count, const EigRequest& rq,
-                      GroupEigMember* em) {
+                      GroupEigMember* em, int front_bank = -1) {
   hipStream_t s = lead->stream;
   const bool trace = sw::group_trace();
-  for (int z = 0; z < count; ++z) SC_HIP(lead, hipStreamWaitEvent(s, mb[z].h->sync_ev, 0));
+  if (front_bank >= 0) {  // the wave front: one event for the wave
+    SC_HIP(lead, hipStreamWaitEvent(s, lead->gbank_ev[front_bank], 0));
+  } else {
+    for (int z = 0; z < count; ++z) SC_HIP(lead, hipStreamWaitEvent(s, mb[z].h->sync_ev, 0));
+  }
   const double t1 = trace ? now_us() : 0.0;
   std::vector<int> emz;
   for (int z = 0; z < count; ++z) {
@@ -692,6 +868,7 @@ int finish_short_wave(sc_handle lead, const int* ns, const sc_config* cfg, int64
   return single_path_members(lead, cfg, labels, diags, mb, count);
 }
 
+int upload_group_blur_weights(sc_handle h, const sc_config* cfg);  // (further down)
 // The short members of a batch (`list`: indices sorted by n, descending) in waves of kShortWidth
 // on the caller's handle and host thread.
 int run_short_route(sc_handle h, const sc_array* xs, const int* ns, int d,
@@ -715,12 +892,21 @@ int run_short_route(sc_handle h, const sc_array* xs, const int* ns, int d,
       if (rc != SC_OK) return fail(h, rc, hz->err);
       hz->have_constraint = false;
     }
-  if (bands && bands->chain)  // the grouped chain of a wave runs on a stream of the wave's bank
+  ShortWaveOps wave_ops;
+  const bool wave = !sw::short_front_memberwise() && !(bands && bands->band) &&
+                    d <= kShortWaveMaxD && short_wave_covers(cfg, &wave_ops);
+  if (wave || (bands && bands->chain))  // (the grouped chain of a wave: a stream of the wave's bank)
     for (int b = 0; b < banks; ++b) SC_TRY(ensure_bank_stream(h, b));
+  if (wave && wave_ops.blur_radius > 0) SC_TRY(upload_group_blur_weights(h, cfg));
   std::vector<Member> mbs[kGroupBanks];
   std::vector<GroupEigMember> em(kShortWidth);
   for (int b = 0; b < banks; ++b) mbs[b].resize(kShortWidth);
   auto front = [&](int j) -> int {
+    if (wave)
+      return enqueue_front_short_wave(h, xs, ns, d, cfg, diags,
+                                      list.data() + (size_t)j * kShortWidth, wave_count(j),
+                                      (j % banks) * kShortWidth, mbs[j % banks].data(), j % banks,
+                                      wave_ops);
     return enqueue_front(h, xs, ns, d, cfg, diags, list.data() + (size_t)j * kShortWidth,
                          wave_count(j), (j % banks) * kShortWidth, mbs[j % banks].data(),
                          &h->gshort, bands, h->gbank_stream[j % banks], h->gbank_ev[j % banks]);
@@ -734,10 +920,12 @@ int run_short_route(sc_handle h, const sc_array* xs, const int* ns, int d,
     }
     if (rc == SC_OK)
       rc = finish_short_wave(h, ns, cfg, labels, diags, mbs[j % banks].data(), wave_count(j), rq,
-                             em.data());
-    if (rc != SC_OK && ahead)  // the next wave's uploads read the caller's arrays: let them land
-      for (int z = 0; z < wave_count(j + 1); ++z)
+                             em.data(), wave ? j % banks : -1);
+    if (rc != SC_OK && ahead) {  // the next wave's uploads read the caller's arrays: let them land
+      if (wave) (void)hipStreamSynchronize(h->gbank_stream[(j + 1) % banks]);
+      for (int z = 0; !wave && z < wave_count(j + 1); ++z)
         if (mbs[(j + 1) % banks][z].h) (void)hipStreamSynchronize(mbs[(j + 1) % banks][z].h->stream);
+    }
   }
   return rc;
 }
@@ -2106,6 +2294,66 @@ int stage_front_short_sweep(sc_handle h, const sc_config* cfg, int count, int n,
   }
   return SC_OK;
 }
+
+// the front of one wave of the short route of a batch: the members in the order given, arenas and
+// table of bank 0 -- enqueue_front_short_wave as run_short_route calls it
+int stage_front_short_wave(sc_handle h, const sc_config* cfg, int count, const int32_t* ns32,
+                           int d, const double* const* xs, sc_front_out* outs) {
+  std::vector<int> ns(ns32, ns32 + count), idx(count);
+  for (int z = 0; z < count; ++z) {
+    idx[z] = z;
+    if (ns[z] > kDenseMax)
+      return fail(h, SC_ERR_UNSUPPORTED, "sc_stage_front: a member above 128 rows");
+  }
+  ShortWaveOps ops;
+  if (d > kShortWaveMaxD || constraint_active(h, cfg, true) || constraint_active(h, cfg, false) ||
+      !short_wave_covers(cfg, &ops))
+    return fail(h, SC_ERR_UNSUPPORTED,
+                "sc_stage_front: the short wave front covers d <= 512 and [CropDiagonal] "
+                "[GaussianBlur, radius <= 32] RowWiseThreshold Symmetrize [Diffuse] "
+                "[RowWiseNormalize] without constraints");
+  h->sweep_slot.clear();
+  const std::vector<sc_array> arrays = host_f64_arrays(xs, ns.data(), d, count);
+  SC_TRY(ensure_bank_stream(h, 0));
+  for (int z = 0; z < count; ++z) {
+    sc_handle hz = nullptr;
+    SC_TRY(group_slot(h, z, &hz, &h->gshort));
+    const int rc = sc_reserve(hz, kDenseMax, d);
+    if (rc != SC_OK) return fail(h, rc, hz->err);
+  }
+  if (ops.blur_radius > 0) SC_TRY(upload_group_blur_weights(h, cfg));
+  std::vector<Member> mb(count);
+  h->gsw_launches = 0;
+  const int rc = enqueue_front_short_wave(h, arrays.data(), ns.data(), d, cfg, nullptr, idx.data(),
+                                          count, 0, mb.data(), 0, ops);
+  SC_HIP(h, hipStreamSynchronize(h->gbank_stream[0]));  // (the uploads read the caller's arrays)
+  SC_TRY(rc);
+  for (int z = 0; z < count; ++z) {
+    sc_handle hz = mb[z].h;
+    const FrontResult& fr = mb[z].front;
+    FrontWhere w;
+    w.h = hz;
+    w.n = ns[z];
+    w.ld = hz->ldn;
+    w.a0 = ptr<double>(hz->A0);
+    // (the vector is reported where a single call reports one: its fused crop + blur, which it
+    //  takes from n = 128 on at radius 4 or 8 -- below, its CropDiagonal leaves a matrix only)
+    const bool single_reports = ops.crop && (ops.blur_radius == 4 || ops.blur_radius == 8) &&
+                                ns[z] >= 128;
+    w.cropval = single_reports ? ptr<double>(hz->cropval) : nullptr;
+    w.cut = ptr<double>(hz->cut);
+    w.a = ptr<double>(hz->B2);
+    w.s = fr.diffuse_explicit ? ptr<double>(hz->B1) : nullptr;
+    w.diffuse_path = fr.diffuse_explicit ? SC_DIFFUSE_PATH_EXPLICIT : SC_DIFFUSE_PATH_NONE;
+    w.symmetric = fr.symmetric;
+    w.folded_rownorm = fr.folded_rownorm;
+    w.crop_source = single_reports ? fr.crop_source : 0;
+    w.cut_kernel = fr.cut_kernel;
+    SC_TRY(front_copy_out(h, w, outs + z));
+    outs[z].info[SC_FRONT_INFO_LAUNCHES] = h->gsw_launches;
+  }
+  return SC_OK;
+}
 }  // namespace
 
 extern "C" int sc_stage_front(sc_handle h, int route, const sc_config* cfg, int count,
@@ -2115,12 +2363,14 @@ extern "C" int sc_stage_front(sc_handle h, int route, const sc_config* cfg, int 
   if (!h) return SC_ERR_INVALID;
   SC_TRY(validate_config(h, cfg));
   if (!ns || !outs || count < 1) return fail(h, SC_ERR_INVALID, "sc_stage_front: NULL argument");
-  if (count > (route == SC_FRONT_ROUTE_SHORT_SWEEP ? kShortWidth : kGroupMax))
+  const bool wide = route == SC_FRONT_ROUTE_SHORT_SWEEP || route == SC_FRONT_ROUTE_SHORT_WAVE;
+  if (count > (wide ? kShortWidth : kGroupMax))
     return fail(h, SC_ERR_UNSUPPORTED,
-                "sc_stage_front: at most 16 members / values per call (a short level: one launch "
-                "of pairs)");
+                "sc_stage_front: at most 16 members / values per call (a short level or wave: one "
+                "launch of up to 64)");
   SC_HIP(h, hipSetDevice(h->device));
-  const int members = route == SC_FRONT_ROUTE_GROUPED ? count : 1;
+  const int members =
+      (route == SC_FRONT_ROUTE_GROUPED || route == SC_FRONT_ROUTE_SHORT_WAVE) ? count : 1;
   for (int z = 0; z < members; ++z)
     if (ns[z] <= 0 || (xs && !xs[z]))
       return fail(h, SC_ERR_INVALID, "sc_stage_front: every member needs rows");
@@ -2139,6 +2389,9 @@ extern "C" int sc_stage_front(sc_handle h, int route, const sc_config* cfg, int 
     case SC_FRONT_ROUTE_SHORT_SWEEP:
       if (!p_values) return fail(h, SC_ERR_INVALID, "sc_stage_front: p_values is NULL");
       return stage_front_short_sweep(h, cfg, count, ns[0], d, xs[0], p_values, outs);
+    case SC_FRONT_ROUTE_SHORT_WAVE:
+      if (!xs) return fail(h, SC_ERR_INVALID, "sc_stage_front: the short wave takes embeddings");
+      return stage_front_short_wave(h, cfg, count, ns, d, xs, outs);
   }
   return fail(h, SC_ERR_INVALID, "sc_stage_front: unknown route");
 }

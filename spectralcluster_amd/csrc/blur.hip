@@ -19,13 +19,7 @@ namespace sc {
 constexpr int TH = 32;
 constexpr int TW = 64;
 
-__device__ __forceinline__ int reflect_index(int j, int n) {
-  // scipy "reflect": period 2n, second half mirrored, edge sample repeated
-  const int period = 2 * n;
-  j %= period;
-  if (j < 0) j += period;
-  return j < n ? j : period - 1 - j;
-}
+// (reflect_index and blur_line_point, the one-line body of the any-radius form: sc_internal.h)
 
 __global__ __launch_bounds__(256) void k_gaussian_blur(
     const double* __restrict__ in, double* __restrict__ out, int n, int ld,
@@ -336,19 +330,9 @@ __global__ __launch_bounds__(256) void k_gaussian_blur_axis(
   const int j = blockIdx.x * 256 + threadIdx.x;
   const int i = blockIdx.y;
   if (j >= n) return;
-  double t = in[(size_t)i * ld + j] * weights[radius];
-  for (int q = radius; q >= 1; --q) {
-    double lo, hi;
-    if (AXIS == 0) {
-      lo = in[(size_t)reflect_index(i - q, n) * ld + j];
-      hi = in[(size_t)reflect_index(i + q, n) * ld + j];
-    } else {
-      lo = in[(size_t)i * ld + reflect_index(j - q, n)];
-      hi = in[(size_t)i * ld + reflect_index(j + q, n)];
-    }
-    t += (lo + hi) * weights[radius - q];
-  }
-  out[(size_t)i * ld + j] = t;
+  // the line through (i, j) along AXIS, element e of it
+  auto at = [&](int e) { return AXIS == 0 ? in[(size_t)e * ld + j] : in[(size_t)i * ld + e]; };
+  out[(size_t)i * ld + j] = blur_line_point(at, AXIS == 0 ? i : j, n, radius, weights);
 }
 
 void launch_gaussian_blur_any_radius(hipStream_t s, const double* in, double* tmp, double* out,

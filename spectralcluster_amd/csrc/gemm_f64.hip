@@ -895,12 +895,9 @@ __global__ __launch_bounds__(256) void k_gemm_stats_reduce_g(const GroupOf<Stats
   if (a.nt > kStatMaxTiles) {  // (very large members: one thread per row, straight from memory)
     const int i = blockIdx.x * kStatRows + threadIdx.x;
     if ((int)threadIdx.x >= kStatRows || i >= a.n) return;
-    double mx = -INFINITY, sm = 0.0;
-    for (int t = 0; t < a.nt; ++t) {
-      mx = fmax(mx, a.pmax[(size_t)i * a.nt + t]);
-      if (mode == 1) sm += a.psum[(size_t)i * a.nt + t];
-    }
-    if (mode == 2) mx = fmax(mx, 0.0);
+    double mx, sm;
+    gemm_stats_fold_row(a.pmax + (size_t)i * a.nt,
+                        mode == 1 ? a.psum + (size_t)i * a.nt : nullptr, a.nt, mode, &mx, &sm);
     a.rowmax[i] = mx;
     if (mode == 1) a.rowsum[i] = sm;
     return;
@@ -1181,7 +1178,7 @@ void launch_gemm_nt(hipStream_t s, const double* A, int lda, const double* B,
 // the tile epilogues (`stats_mode` 1: row max and sum, 2: CropDiagonal's value) reduced by one
 // more grouped launch.  items[z].n = 0: idle member.
 void launch_gemm_nt_group(hipStream_t s, const GemmGroupItem* items, int count, int epilogue,
-                          int stats_mode) {
+                          int stats_mode, bool reduce_stats) {
   GemmGroup grp;
   memset(&grp, 0, sizeof(grp));
   GroupOf<StatsReduceItem> red;
@@ -1210,7 +1207,7 @@ void launch_gemm_nt_group(hipStream_t s, const GemmGroupItem* items, int count, 
   else
     hipLaunchKernelGGL((k_gemm_nt_g<kEpiNone>), dim3(grid), dim3(256), 0, s, grp, stats_mode,
                        xcd_chunk);
-  if (stats_mode != 0)
+  if (stats_mode != 0 && reduce_stats)
     hipLaunchKernelGGL(k_gemm_stats_reduce_g, dim3((nmax + kStatRows - 1) / kStatRows, count),
                        dim3(256),
                        2 * kStatRows * (size_t)(std::min((nmax + BM - 1) / BM, kStatMaxTiles) + 1) *

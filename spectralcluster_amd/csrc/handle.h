@@ -128,6 +128,11 @@ struct sc_handle_s {
   DevBuf gsftab;
   ShortFrontItem* h_gsftab = nullptr;
   hipEvent_t gsftab_ev = nullptr;  // "the copy of the pinned table has been made"
+  // the wave front of the short route (enqueue_front_short_wave): the member table of a wave,
+  // one half per bank (device + pinned twin), and the kernel launches the last wave front enqueued
+  DevBuf gswtab;
+  ShortWaveItem* h_gswtab = nullptr;
+  int gsw_launches = 0;
   // route of every utterance of the last batch call (sc_last_batch_routes); `groutes`: where
   // a lead of the running batch reports (the caller handle's last_routes)
   std::vector<int32_t> last_routes;

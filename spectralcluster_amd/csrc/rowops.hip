@@ -847,24 +847,21 @@ __global__ void k_check_finite(const double* __restrict__ a, const double* __res
 // Plain vector stores, no atomics; every result is what the kernels it replaces store.
 constexpr int kShortFrontMatrix = kDenseMax * (kDenseMax + 1);  // doubles: n rows of pitch n | 1
 constexpr int kShortFrontLdsBytes = (kShortFrontMatrix + 3 * kDenseMax) * (int)sizeof(double);
-__global__ __launch_bounds__(256) void k_short_sweep_front(
-    const ShortFrontItem* __restrict__ table, int threshold_type, double mult, int binarize,
-    int symtype, int preserve_diag, int lap) {
-  extern __shared__ __attribute__((aligned(16))) double sf_lds[];
-  const ShortFrontItem it = table[blockIdx.x];
+// The steps above on a matrix that is staged in LDS (sf_lds: n rows of pitch n | 1, then the
+// cut / row maximum / row sum vectors), for the calling workgroup of 256 threads: the per-value
+// front of a short AutoTune level and the wave front of a short batch are this body.
+// `rownorm`: RowWiseNormalize folded into the scaling vectors (scaling_vectors_body's reading).
+__device__ __forceinline__ void short_front_tail(const ShortFrontItem& it, double* sf_lds,
+                                                 int threshold_type, double mult, int binarize,
+                                                 int symtype, int preserve_diag, int lap,
+                                                 int rownorm) {
   const int n = it.n, ld = it.ld;
-  if (n < 1 || n > kDenseMax) return;  // (workgroup-uniform)
-  const int P = n | 1;                 // odd pitch: the transposed reads spread over the banks
+  const int P = n | 1;
   double* L = sf_lds;
   double* cutv = sf_lds + kShortFrontMatrix;
   double* rmax = cutv + kDenseMax;
   double* rsum = rmax + kDenseMax;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int e = tid; e < n * n; e += 256) {
-    const int i = e / n, j = e - i * n;
-    L[i * P + j] = it.src[(size_t)i * ld + j];
-  }
-  __syncthreads();
   // ---- cut: one wave per row, lane l holds the columns l and l + 64
   int prev = 0, next = 0;
   double gamma = 0.0;
@@ -954,7 +951,7 @@ __global__ __launch_bounds__(256) void k_short_sweep_front(
   int bad = 0;
   if (tid < n) {
     double cv, pv, tv;
-    scaling_vectors_row(1.0, rsum[tid], lap, 0, &cv, &pv, &tv);
+    scaling_vectors_row(rownorm ? rmax[tid] : 1.0, rsum[tid], lap, rownorm, &cv, &pv, &tv);
     it.rowmax[tid] = rmax[tid];
     it.rowsum[tid] = rsum[tid];
     it.cvec[tid] = cv;
@@ -969,6 +966,129 @@ __global__ __launch_bounds__(256) void k_short_sweep_front(
     it.flags[14] = 0;
     it.flags[15] = 0;
   }
+}
+__global__ __launch_bounds__(256) void k_short_sweep_front(
+    const ShortFrontItem* __restrict__ table, int threshold_type, double mult, int binarize,
+    int symtype, int preserve_diag, int lap) {
+  extern __shared__ __attribute__((aligned(16))) double sf_lds[];
+  const ShortFrontItem it = table[blockIdx.x];
+  const int n = it.n, ld = it.ld;
+  if (n < 1 || n > kDenseMax) return;  // (workgroup-uniform)
+  const int P = n | 1;                 // odd pitch: the transposed reads spread over the banks
+  double* L = sf_lds;
+  const int tid = threadIdx.x;
+  for (int e = tid; e < n * n; e += 256) {
+    const int i = e / n, j = e - i * n;
+    L[i * P + j] = it.src[(size_t)i * ld + j];
+  }
+  __syncthreads();
+  short_front_tail(it, sf_lds, threshold_type, mult, binarize, symtype, preserve_diag, lap, 0);
+}
+
+// ---- the front of one wave of the short route of a batch (n <= kDenseMax) -----------------
+// One workgroup per member, descriptors from a table in device memory (ShortWaveItem).  The
+// member's affinity -- as the grouped GEMM left it -- is staged in LDS once, and everything the
+// single call runs between the affinity and Diffuse (or the eigensolver) as five to seven launches
+// happens there:
+//   crop     the diagonal takes the value the GEMM epilogue found (its one tile's partials, folded
+//            as k_gemm_stats_reduce folds them); the vector goes out for the arena as well
+//   blur     the two 1-D passes in place, axis 0 then axis 1: a wave takes a line, lane l its
+//            elements l and l + 64, every tap is read before the line is written back; a barrier
+//            between the passes.  blur_line_point: scipy's order, `reflect` with as many
+//            reflections as n <= radius needs -- the values k_gaussian_blur / k_gaussian_blur_r
+//            store
+//   tail     short_front_tail: cut, threshold + symmetrise and (no Diffuse behind it) statistics,
+//            scaling vectors, flag words
+// The blur weights sit in the row-statistics vectors, which nothing reads before the tail writes
+// them.  No atomics, no scratch; plain vector stores.
+__global__ void k_short_wave_init(const ShortWaveItem* __restrict__ table) {
+  const ShortWaveItem& a = table[blockIdx.x];
+  if (a.n <= 0) return;
+  if (threadIdx.x == 0) a.symflag[1] = 0;
+  if (threadIdx.x >= 12 && threadIdx.x < 16) a.flags[threadIdx.x] = 0;
+}
+static_assert(2 * SC_MAX_BLUR_RADIUS + 1 <= 2 * kDenseMax, "blur weights in the statistics vectors");
+__global__ __launch_bounds__(256) void k_short_wave_front(
+    const ShortWaveItem* __restrict__ table, const ShortWaveOps ops,
+    const double* __restrict__ blur_weights) {
+  extern __shared__ __attribute__((aligned(16))) double sf_lds[];
+  const ShortWaveItem a = table[blockIdx.x];
+  const int n = a.n, ld = a.ld;
+  if (n < 1 || n > kDenseMax) return;  // (workgroup-uniform)
+  const int P = n | 1;                 // odd pitch: the transposed reads spread over the banks
+  double* L = sf_lds;
+  double* wts = sf_lds + kShortFrontMatrix + kDenseMax;  // (rmax | rsum of short_front_tail)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int R = ops.blur_radius;
+  for (int e = tid; e < n * n; e += 256) {
+    const int i = e / n, j = e - i * n;
+    L[i * P + j] = a.a0[(size_t)i * ld + j];
+  }
+  if (R > 0 && tid < 2 * R + 1) wts[tid] = blur_weights[tid];
+  __syncthreads();
+  if (ops.crop && tid < n) {
+    double m, unused;
+    gemm_stats_fold_row(a.stat0 + tid, nullptr, 1, 2, &m, &unused);
+    a.cropval[tid] = m;
+    L[tid * P + tid] = m;
+  }
+  if (ops.crop) __syncthreads();
+  if (R > 0) {
+    for (int axis = 0; axis < 2; ++axis) {
+      const int step = axis == 0 ? P : 1;  // along the line
+      for (int line = wave; line < n; line += 4) {
+        double* x = L + (axis == 0 ? line : line * P);
+        auto at = [&](int e) { return x[e * step]; };
+        const int e0 = lane, e1 = lane + 64;
+        double t0 = 0.0, t1 = 0.0;
+        if (e0 < n) t0 = blur_line_point(at, e0, n, R, wts);
+        if (e1 < n) t1 = blur_line_point(at, e1, n, R, wts);
+        // (the wave runs in lockstep: every lane has its taps before the first store is issued)
+        __builtin_amdgcn_wave_barrier();
+        if (e0 < n) x[e0 * step] = t0;
+        if (e1 < n) x[e1 * step] = t1;
+      }
+      __syncthreads();
+    }
+  }
+  ShortFrontItem it;
+  it.src = a.a0;
+  it.n = n;
+  it.ld = ld;
+  it.p = ops.p;
+  it.out = a.out;
+  it.cut = a.cut;
+  it.rowmax = ops.diffuse ? nullptr : a.rowmax;
+  it.rowsum = a.rowsum;
+  it.cvec = a.cvec;
+  it.pvec = a.pvec;
+  it.tvec = a.tvec;
+  it.flags = a.flags;
+  it.symflag = a.symflag;
+  short_front_tail(it, sf_lds, ops.threshold_type, ops.mult, ops.binarize, ops.symtype,
+                   ops.preserve_diag, ops.lap, ops.rownorm);
+}
+// Behind the Diffuse product of the wave: rowmax / rowsum of S out of the product's one-tile
+// partials (k_gemm_stats_reduce's fold), then what k_scaling_vectors + k_check_finite leave.
+__global__ __launch_bounds__(128) void k_short_wave_scaling(
+    const ShortWaveItem* __restrict__ table, int lap, int rownorm) {
+  const ShortWaveItem& a = table[blockIdx.x];
+  const int n = a.n, tid = threadIdx.x;
+  if (n < 1 || n > kDenseMax) return;  // (workgroup-uniform)
+  int bad = 0;
+  if (tid < n) {
+    double mx, sm, cv, pv, tv;
+    gemm_stats_fold_row(a.stat1 + tid, a.stat1 + n + tid, 1, 1, &mx, &sm);
+    scaling_vectors_row(rownorm ? mx : 1.0, sm, lap, rownorm, &cv, &pv, &tv);
+    a.rowmax[tid] = mx;
+    a.rowsum[tid] = sm;
+    a.cvec[tid] = cv;
+    a.pvec[tid] = pv;
+    a.tvec[tid] = tv;
+    bad = !isfinite(cv) || !isfinite(pv);
+  }
+  bad = __syncthreads_or(bad);
+  if (tid == 0) a.flags[12] = (bad || a.symflag[1] != 0) ? 1 : 0;
 }
 
 // ---- L1: materialised Laplacian for the stage API (laplacian.py:24-60) --------
@@ -1148,11 +1268,11 @@ static GroupOf<FrontItem> front_pack(const FrontItem* items, int count, int* nma
   return g;
 }
 void launch_front_begin_group(hipStream_t s, const FrontItem* items, int count,
-                              bool normalize_rows) {
+                              bool normalize_rows, bool init_words) {
   int nmax;
   const GroupOf<FrontItem> g = front_pack(items, count, &nmax);
   if (nmax == 0) return;
-  hipLaunchKernelGGL(k_front_words_init_g, dim3(count), dim3(64), 0, s, g);
+  if (init_words) hipLaunchKernelGGL(k_front_words_init_g, dim3(count), dim3(64), 0, s, g);
   if (normalize_rows)
     hipLaunchKernelGGL(k_normalize_rows_g, dim3((nmax + 3) / 4, count), dim3(kRowThreads), 0, s,
                        g);
@@ -1230,6 +1350,22 @@ void launch_short_sweep_front(hipStream_t s, const ShortFrontItem* table, int co
   SC_OPT_IN_LDS(k_short_sweep_front, kShortFrontLdsBytes);
   hipLaunchKernelGGL(k_short_sweep_front, dim3(count), dim3(256), kShortFrontLdsBytes, s, table,
                      threshold_type, mult, binarize, symtype, preserve_diag, laplacian_type);
+}
+void launch_short_wave_init(hipStream_t s, const ShortWaveItem* table, int count) {
+  if (count < 1) return;
+  hipLaunchKernelGGL(k_short_wave_init, dim3(count), dim3(64), 0, s, table);
+}
+void launch_short_wave_front(hipStream_t s, const ShortWaveItem* table, int count,
+                             const ShortWaveOps& ops, const double* blur_weights) {
+  if (count < 1) return;
+  SC_OPT_IN_LDS(k_short_wave_front, kShortFrontLdsBytes);
+  hipLaunchKernelGGL(k_short_wave_front, dim3(count), dim3(256), kShortFrontLdsBytes, s, table,
+                     ops, blur_weights);
+}
+void launch_short_wave_scaling(hipStream_t s, const ShortWaveItem* table, int count, int lap,
+                               int rownorm) {
+  if (count < 1) return;
+  hipLaunchKernelGGL(k_short_wave_scaling, dim3(count), dim3(128), 0, s, table, lap, rownorm);
 }
 void launch_check_finite(hipStream_t s, const double* a, const double* b, int n, int* flag) {
   hipLaunchKernelGGL(k_check_finite, dim3((n + 255) / 256), dim3(256), 0, s, a, b, n, flag);

@@ -86,8 +86,24 @@ struct GemmGroupItem {
   double* rowmax = nullptr;
   double* rowsum = nullptr;
 };
+// `reduce_stats` false: the per-tile partials stay as the epilogues wrote them (a caller whose
+// members have ONE tile reads them with gemm_stats_fold_row in a kernel of its own)
 void launch_gemm_nt_group(hipStream_t s, const GemmGroupItem* items, int count, int epilogue,
-                          int stats_mode);
+                          int stats_mode, bool reduce_stats = true);
+// one row of k_gemm_stats_reduce: the row's per-tile partials folded in slot order (`mode` 1: row
+// max and sum, 2: CropDiagonal's value -- the zero-filled diagonal takes part)
+__device__ __forceinline__ void gemm_stats_fold_row(const double* __restrict__ pmax,
+                                                    const double* __restrict__ psum, int ntiles,
+                                                    int mode, double* mx_out, double* sm_out) {
+  double mx = -INFINITY, sm = 0.0;
+  for (int t = 0; t < ntiles; ++t) {
+    mx = fmax(mx, pmax[t]);
+    if (mode == 1) sm += psum[t];
+  }
+  if (mode == 2) mx = fmax(mx, 0.0);
+  *mx_out = mx;
+  *sm_out = sm;
+}
 // One member of a grouped symmetric two-operand product C = A B^T (+ addend), K = n, for
 // commuting symmetric A and B (launch_gemm_nt_pair_group); n = 0: idle.  B == nullptr: B = A.
 // addend (kEpiAdd): pitch ldc, must not alias C.
@@ -123,6 +139,26 @@ void launch_gaussian_blur(hipStream_t s, const double* in, double* out, int n,
 struct BlurLaunch {
   int kernel = -1, rows = 0;
 };
+// scipy "reflect" (d c b a | a b c d | d c b a): period 2n, second half mirrored, edge sample
+// repeated; as many reflections as the index needs (n <= radius)
+__device__ __forceinline__ int reflect_index(int j, int n) {
+  const int period = 2 * n;
+  j %= period;
+  if (j < 0) j += period;
+  return j < n ? j : period - 1 - j;
+}
+// Element e of one 1-D pass of the blur over a line of n elements at(0 .. n-1): scipy's
+// NI_Correlate1D order -- the centre tap, then the pairs from the outermost inwards --
+// weights[radius - q] the weight at distance q.  The any-radius kernels of blur.hip and the
+// in-LDS blur of the short wave front (rowops.hip) are this body.
+template <class At>
+__device__ __forceinline__ double blur_line_point(At at, int e, int n, int radius,
+                                                  const double* __restrict__ weights) {
+  double t = at(e) * weights[radius];
+  for (int q = radius; q >= 1; --q)
+    t += (at(reflect_index(e - q, n)) + at(reflect_index(e + q, n))) * weights[radius - q];
+  return t;
+}
 // fused forms used by the predict() pipeline
 bool launch_gaussian_blur_fused(hipStream_t s, const double* in, double* out, int n, int ld,
                                 int radius, const double* weights_dev, const double* diag,
@@ -332,8 +368,9 @@ struct FrontItem {
   int* flags;
   double p_own;      // > 0: this member's own p_percentile (AutoTune sweep)
 };
+// (`init_words` false: the caller has cleared the members' latch words itself)
 void launch_front_begin_group(hipStream_t s, const FrontItem* items, int count,
-                              bool normalize_rows);
+                              bool normalize_rows, bool init_words = true);
 // One member of a grouped ConstraintPropagation pass (constraint.hip); which matrix / vector is
 // which is said at each launcher.  n = 0: idle.
 struct CpItem {
@@ -403,6 +440,44 @@ struct ShortFrontItem {
 void launch_short_sweep_front(hipStream_t s, const ShortFrontItem* table, int count,
                               int threshold_type, double mult, int binarize, int symtype,
                               int preserve_diag, int laplacian_type);
+// One member of a wave of the short route of a batch (n <= kDenseMax, batch_group.hip
+// enqueue_front_short_wave): where its arena keeps what.  The table of a wave lives in device
+// memory; the three launches below take every member of the wave (a workgroup each).
+struct ShortWaveItem {
+  int n, ld;
+  const double* a0;     // affinity as the grouped GEMM left it, row pitch ld
+  const double* stat0;  // that GEMM's per-tile partials (one tile: n row maxima off the diagonal)
+  double* cropval;      // CropDiagonal's value vector, written by the front kernel
+  double* out;          // thresholded + symmetrised, row pitch ld
+  double* cut;
+  const double* stat1;  // the Diffuse GEMM's partials: n row maxima, then n row sums
+  double* rowmax;
+  double* rowsum;
+  double* cvec;
+  double* pvec;
+  double* tvec;
+  int* flags;           // [12] non-finite word, [13..15] the chain's latch
+  int* symflag;         // [1]: a zero / non-finite embedding row was seen
+};
+// What of the refinement sequence the wave front runs (batch_group.hip short_wave_covers)
+struct ShortWaveOps {
+  int crop, blur_radius;  // CropDiagonal; GaussianBlur (0: none)
+  int threshold_type, binarize, symtype, preserve_diag;
+  double p, mult;
+  int diffuse;            // a Diffuse follows: the front kernel stops at the refined matrix
+  int rownorm;            // RowWiseNormalize folded into the scaling vectors
+  int lap;
+};
+// symflag[1] and flags[12..15] of every member cleared (ahead of the row normalisation)
+void launch_short_wave_init(hipStream_t s, const ShortWaveItem* table, int count);
+// affinity -> crop, blur, cut, threshold + symmetrise in LDS -> `out` (and, without a Diffuse,
+// row statistics, scaling vectors and the flag words); blur_weights: 2 * radius + 1 doubles
+void launch_short_wave_front(hipStream_t s, const ShortWaveItem* table, int count,
+                             const ShortWaveOps& ops, const double* blur_weights);
+// behind the Diffuse product: its row statistics out of the partials, the scaling vectors and
+// the non-finite word
+void launch_short_wave_scaling(hipStream_t s, const ShortWaveItem* table, int count, int lap,
+                               int rownorm);
 void launch_scaling_vectors_group(hipStream_t s, const FrontItem* items, int count,
                                   int laplacian_type, int row_normalized);
 struct GatherItem {  // T == nullptr: idle

@@ -108,6 +108,14 @@ inline bool sweep_one_by_one() {
   static const bool v = getenv("SC_SWEEP_ONE_BY_ONE") != nullptr;
   return v;
 }
+// SC_SHORT_FRONT_MEMBERWISE=1: the short route of a batch (n <= 128) enqueues its fronts member
+// by member, each on its own stream, as it does for every batch the wave front does not cover
+// (d > 512, constraint bands, other refinement sequences); tests/test_gpu_short_wave_front.py
+// runs a batch under it in a process of its own
+inline bool short_front_memberwise() {
+  static const bool v = getenv("SC_SHORT_FRONT_MEMBERWISE") != nullptr;
+  return v;
+}
 
 }  // namespace sw
 }  // namespace sc
