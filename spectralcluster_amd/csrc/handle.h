@@ -124,7 +124,7 @@ struct sc_handle_s {
   std::vector<sc_handle_s*> gshort;
   DevBuf gjtab;
   JacobiItem* h_gjtab = nullptr;
-  // a short AutoTune level (n <= kDenseMax, sc_eig_ncluster_sweep): the pair table of its front
+  // a short AutoTune level (n <= kDenseMax, batch_sweep.hip): the pair table of its front
   DevBuf gsftab;
   ShortFrontItem* h_gsftab = nullptr;
   hipEvent_t gsftab_ev = nullptr;  // "the copy of the pinned table has been made"
@@ -137,7 +137,7 @@ struct sc_handle_s {
   // a lead of the running batch reports (the caller handle's last_routes)
   std::vector<int32_t> last_routes;
   int32_t* groutes = nullptr;
-  std::vector<sc_handle_s*> glanes;  // the leads of lanes 1.. (batch_group.hip)
+  std::vector<sc_handle_s*> glanes;  // the leads of lanes 1.. (batch_group.hip: ensure_lanes)
   class HostPool* gpool = nullptr;  // host workers of the group checks (host_pool.h)
   // grouped front: the stages before the eigensolver of a whole group as grouped launches on
   // the stream of the group's bank, handed to this handle's stream through the bank's event
@@ -261,6 +261,11 @@ int predict_sequence(sc_handle h, const int* idx, int count, const sc_array* xs,
 // ---- described sources (ingest.hip) ---------------------------------------------------
 // every check of a descriptor, before any launch or copy (SC_ERR_INVALID + message)
 int validate_array(sc_handle h, const sc_array* a);
+// ... of every utterance of a batch, and that they share one d: fills ns[i] = rows of xs[i], *d
+// (0 for an empty batch) and whether any source lies on the device (the caller then waits for its
+// stream before other streams read one).  `labels` (may be null): labels[i] is checked too.
+int validate_batch_arrays(sc_handle h, const sc_array* xs, int count, std::vector<int>* ns, int* d,
+                          bool* device_source, int64_t* const* labels = nullptr);
 // what the double* entry points describe: compact host fp64 rows
 sc_array host_f64_array(const double* x, int n, int d);
 std::vector<sc_array> host_f64_arrays(const double* const* xs, const int* ns, int d, int count);

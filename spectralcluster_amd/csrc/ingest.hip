@@ -154,6 +154,22 @@ int validate_array(sc_handle h, const sc_array* a) {
   return SC_OK;
 }
 
+int validate_batch_arrays(sc_handle h, const sc_array* xs, int count, std::vector<int>* ns, int* d,
+                          bool* device_source, int64_t* const* labels) {
+  *device_source = false;
+  ns->assign(count, 0);
+  for (int i = 0; i < count; ++i) {  // every descriptor before the first launch
+    SC_TRY(validate_array(h, xs + i));
+    if (labels && !labels[i]) return fail(h, SC_ERR_INVALID, "NULL labels");
+    if (xs[i].cols != xs[0].cols)
+      return fail(h, SC_ERR_INVALID, "all utterances must be (n_i, d) with the same d");
+    (*ns)[i] = (int)xs[i].rows;
+    *device_source |= xs[i].location == SC_MEM_DEVICE;
+  }
+  *d = count > 0 ? (int)xs[0].cols : 0;
+  return SC_OK;
+}
+
 sc_array host_f64_array(const double* x, int n, int d) {
   sc_array a;
   a.data = x;
@@ -306,14 +322,9 @@ extern "C" int sc_predict_batch_arrays(sc_handle h, const sc_array* xs, int coun
   SC_TRY(validate_config(h, cfg));
   SC_HIP(h, hipSetDevice(h->device));
   bool device_source = false;
-  std::vector<int> ns(count);
-  for (int i = 0; i < count; ++i) {
-    SC_TRY(validate_array(h, xs + i));
-    if (xs[i].cols != xs[0].cols)
-      return fail(h, SC_ERR_INVALID, "all utterances must be (n_i, d) with the same d");
-    ns[i] = (int)xs[i].rows;
-    device_source |= xs[i].location == SC_MEM_DEVICE;
-  }
+  std::vector<int> ns;
+  int d = 0;
+  SC_TRY(validate_batch_arrays(h, xs, count, &ns, &d, &device_source));
   if (count == 0) {
     h->last_routes.clear();
     return SC_OK;
@@ -321,7 +332,6 @@ extern "C" int sc_predict_batch_arrays(sc_handle h, const sc_array* xs, int coun
   // what the caller ordered before this handle's stream is done before any other stream of the
   // batch (pooled handles, lanes, banks, member arenas) reads a device source
   if (device_source) SC_HIP(h, hipStreamSynchronize(h->stream));
-  const int d = (int)xs[0].cols;
   if (group > 1)
     return predict_batch_grouped_impl(h, xs, ns.data(), d, count, cfg, labels, diags, group);
   return predict_batch_streams_impl(h, xs, ns.data(), d, count, cfg, labels, diags, streams);

@@ -419,7 +419,7 @@ void launch_threshold_symmetrize_group(hipStream_t s, const FrontItem* items, in
                                        int preserve_diag, bool cut_ready = false,
                                        const TsDigits* digits = nullptr);
 void launch_cut_from_partials_group(hipStream_t s, const FrontItem* items, int count, double p);
-// One (matrix, p) pair of a short AutoTune level (n <= kDenseMax, batch_group.hip): the per-value
+// One (matrix, p) pair of a short AutoTune level (n <= kDenseMax, batch_sweep.hip): the per-value
 // part of the front in ONE workgroup -- row cut at the pair's own p, threshold, symmetrise and,
 // where no Diffuse follows (rowmax != nullptr), row statistics, scaling vectors and the solver's
 // flag words.  The descriptors of a launch are a table in device memory.
