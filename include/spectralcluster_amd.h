@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 9
+#define SC_ABI_VERSION 10
 #define SC_MAX_OPS 16
 #define SC_MAX_BLUR_RADIUS 32
 #define SC_MAX_EIG 128 /* max eigenvalues reported in sc_diag */
@@ -718,6 +718,34 @@ typedef struct sc_front_out {
 int sc_stage_front(sc_handle h, int route, const sc_config* cfg, int count, const int32_t* ns,
                    int d, const double* const* xs, const double* affinity,
                    const double* p_values, sc_front_out* outs);
+/* Test entries of the dense symmetric route (additions of ABI 10; no reference equivalent -- the
+ * reference calls LAPACK): Householder tridiagonalisation, Sturm-count multisection and the
+ * reflector back-transform, each alone and through the launchers the route itself uses, so that
+ * tests can tell an error of one from an error of another.  Like sc_stage_block_operator each
+ * call allocates device memory shaped like the solver's arena (row pitch, panel, work vectors,
+ * the GEMM's split-K scratch), fills all of it -- padding, workspaces, results -- with quiet NaNs
+ * before the inputs are copied in, runs, copies out and frees.
+ *
+ * sc_stage_tridiag: T = Q^T Op Q for Op = diag(p) + diag(c) m diag(c), m (n, n) symmetric, n >= 32.
+ *   c, p (n each) may be NULL: c = 1 / p = 0; both NULL: Op = m, the materialising kernel does
+ *   not run.  Outputs (each may be NULL): d (n) the diagonal of T, e (n) its off-diagonal with
+ *   e[n-1] = 0, tau (n) the reflector scalars (tau[n-1] = 0), reflectors (n, n) the matrix the
+ *   reduction leaves: row j holds v_j in columns j+1 .. n-1 (v_j[j+1] = 1), Q = H_0 ... H_{n-2},
+ *   H_j = I - tau_j v_j v_j^T; what the rest of it holds is unspecified.
+ * sc_stage_tridiag_values: every eigenvalue of the tridiagonal d (n), e (n - 1; NULL at n = 1),
+ *   n >= 1, DESCENDING into values_desc (n).
+ * sc_stage_td_backtransform: z (n, cols) row-major <- Q z, with reflectors (n, n) and tau (n) as
+ *   sc_stage_tridiag writes them (only columns j+1 .. n-1 of row j are read).  The columns go to
+ *   the device column-major and come back through the transposition of sc_get_eigenvectors, as
+ *   in a solve.  flags: SC_TD_BACKTRANSFORM_GLOBAL runs the kernel that keeps the column in
+ *   global memory -- the product's choice above n = 16384 -- whatever n is. */
+enum { SC_TD_BACKTRANSFORM_GLOBAL = 1 };
+int sc_stage_tridiag(sc_handle h, const double* m, int n, const double* c, const double* p,
+                     double* d, double* e, double* tau, double* reflectors);
+int sc_stage_tridiag_values(sc_handle h, const double* d, const double* e, int n,
+                            double* values_desc);
+int sc_stage_td_backtransform(sc_handle h, const double* reflectors, const double* tau, int n,
+                              double* z, int cols, int flags);
 /* laplacian.compute_laplacian (laplacian.py:24-60) */
 int sc_stage_laplacian(sc_handle h, int laplacian_type, const double* in, int n,
                        double* out);

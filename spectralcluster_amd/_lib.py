@@ -50,7 +50,7 @@ class EigenSolverNotConverged(RuntimeError):
   """The block-Lanczos eigensolver did not reach its tolerance."""
 
 
-SC_ABI_VERSION = 9
+SC_ABI_VERSION = 10
 
 
 class ScConfig(ctypes.Structure):
@@ -223,6 +223,14 @@ PROTOTYPES = {
                                       ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
                                       ctypes.POINTER(_c_double_p), _c_double_p, _c_double_p,
                                       ctypes.POINTER(ScFrontOut)]),
+    "sc_stage_tridiag": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int, _c_double_p,
+                                        _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                        _c_double_p]),
+    "sc_stage_tridiag_values": (ctypes.c_int, [_handle_t, _c_double_p, _c_double_p, ctypes.c_int,
+                                               _c_double_p]),
+    "sc_stage_td_backtransform": (ctypes.c_int, [_handle_t, _c_double_p, _c_double_p,
+                                                 ctypes.c_int, _c_double_p, ctypes.c_int,
+                                                 ctypes.c_int]),
     "sc_config_default": (ctypes.c_int, [ctypes.POINTER(ScConfig)]),
     "sc_gaussian_weights": (ctypes.c_int, [ctypes.c_double,
                                            ctypes.POINTER(ctypes.c_int32),

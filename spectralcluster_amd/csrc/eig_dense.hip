@@ -577,11 +577,11 @@ void launch_tridiagonalize_blocked(hipStream_t s, double* A, int ld, int n, doub
 }
 
 // Z (column-major, `cols` columns of n, ldz) <- Q Z with the reflectors launch_tridiagonalize_blocked
-// left in A / taus.
+// left in A / taus.  `force_global` (tests): the in-place kernel of n > kTdLdsRows at any n.
 void launch_td_backtransform(hipStream_t s, const double* A, int ld, int n, const double* taus,
-                             double* Z, int ldz, int cols) {
+                             double* Z, int ldz, int cols, bool force_global) {
   if (cols <= 0) return;
-  if (n <= kTdLdsRows) {
+  if (n <= kTdLdsRows && !force_global) {
     const size_t lds = (size_t)n * sizeof(double);
     // above the 64 KB default of dynamic LDS: opt in once per device (handles of several
     // devices / host threads share the process)

@@ -537,9 +537,11 @@ void launch_td_materialize(hipStream_t s, const double* S, int ld, int n, const 
 void launch_tridiagonalize_blocked(hipStream_t s, double* A, int ld, int n, double* d, double* e,
                                    double* taus, double* panel, double* work,
                                    double* splitk_ws);
-// Z (column-major: column q at Z + q * ldz) <- Q Z, Q = H_0 ... H_{n-2} from the above
+// Z (column-major: column q at Z + q * ldz) <- Q Z, Q = H_0 ... H_{n-2} from the above: the
+// column in LDS up to n = 16384, in place in global memory above (`force_global`: at any n --
+// sc_stage_td_backtransform; the same operations in the same order)
 void launch_td_backtransform(hipStream_t s, const double* A, int ld, int n, const double* taus,
-                             double* Z, int ldz, int cols);
+                             double* Z, int ldz, int cols, bool force_global = false);
 // all eigenvalues of the tridiagonal (d, e) by Sturm bisection, DESCENDING; work: n + 4
 void launch_tridiagonal_eigenvalues(hipStream_t s, const double* d, const double* e, int n,
                                     double* theta_desc, double* work);

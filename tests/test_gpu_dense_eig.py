@@ -1,7 +1,11 @@
 """GPU: the dense full-spectrum symmetric eigenvalue path (E1; eig_dense.hip: Householder
-tridiagonalisation + Sturm bisection, vectors from block Lanczos) through the C ABI.
+tridiagonalisation + Sturm bisection; vectors by inverse iteration on the tridiagonal form and the
+Householder back-transform, or from block Lanczos where only values come from here) through the
+C ABI.
 
   * every eigenvalue vs numpy's eigvalsh on the same matrix (stage API, values only);
+  * 80 eigenpairs of the dense route itself (eig_path 6) on multiple and clustered spectra, held
+    to the bars of test_gpu_jacobi_spectra.py (the kernels alone: test_gpu_tridiag_kernels.py);
   * the reference's DEFAULT max_clusters=None with a Laplacian, where the eigengap reads
     all n eigenvalues (spectral_clusterer.py:32, utils.py:100-115), and the ascending
     NormalizedDiff gap with its np.max(eigenvalues) (utils.py:110) -- against goldens
@@ -15,6 +19,7 @@ import os
 import numpy as np
 import pytest
 
+import _tridiag_ref as tr
 import spectral_oracle as so
 import spectralcluster_amd as sca
 from spectralcluster_amd import _lib
@@ -81,6 +86,34 @@ def test_structured_spectra(handle):
   got, _ = all_eigenvalues(handle, t, False)
   want = 2 - 2 * np.cos(np.arange(1, n + 1) * np.pi / (n + 1))
   np.testing.assert_allclose(got, want, rtol=0, atol=1e-13)
+
+
+@pytest.mark.parametrize("n", tr.SPECTRA_SIZES)
+@pytest.mark.parametrize("name", tr.SPECTRA)
+def test_dense_route_vectors_on_hard_spectra(handle, name, n):
+  """More than 64 vectors: values, inverse iteration and the back-transform all come from the
+  dense route.  Bars of test_gpu_jacobi_spectra.py; host_tridiag_eigvectors alone stays 100x
+  inside them on these spectra (residual <= 3.2e-15 ||T||, |V^T V - I| <= 1.4e-14)."""
+  m, descend = tr.spectrum_case(name, n)
+  count = tr.SPECTRA_COUNT
+  values = np.full(count, np.nan)
+  vectors = np.full((n, count), np.nan)
+  diag = _lib.ScDiag()
+  handle.check(handle.lib.sc_stage_sym_eig(
+      handle.raw, _lib.as_double_p(np.ascontiguousarray(m)), n, count, int(descend),
+      _lib.as_double_p(values), _lib.as_double_p(vectors), diag))
+  assert diag.eig_path == 6 and diag.eig_fallback == 5   # SC_EIG_PATH_DENSE_FULL, > 64 vectors
+  ref = np.linalg.eigvalsh(m)
+  ref = ref[::-1] if descend else ref
+  scale = np.abs(ref).max()
+  err = np.abs(values - ref[:count]).max()
+  res = np.abs(m @ vectors - vectors * values).max()
+  orth = np.abs(vectors.T @ vectors - np.eye(count)).max()
+  print("%s n=%d: eigenvalue error %.3g  residual %.3g  (of max|w| = %.3g)  |V^T V - I| %.3g" % (
+      name, n, err / scale, res / scale, scale, orth))
+  assert err <= 1e-12 * scale
+  assert res < 1e-11 * scale
+  assert orth <= 1e-12
 
 
 def _dense_goldens():
