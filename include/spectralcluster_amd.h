@@ -480,7 +480,8 @@ int sc_predict_batch_constrained(sc_handle h, const sc_array* xs, const double* 
 enum {
   SC_BATCH_ROUTE_SINGLE = 0,         /* the single-call path, on the member's arena */
   SC_BATCH_ROUTE_GROUP_LANCZOS = 1,  /* lockstep block Lanczos of a group (128 < n < 4096) */
-  SC_BATCH_ROUTE_GROUP_JACOBI = 2    /* short route: one Jacobi workgroup per member (n <= 128) */
+  SC_BATCH_ROUTE_GROUP_JACOBI = 2,   /* short route: one Jacobi workgroup per member (n <= 128) */
+  SC_BATCH_ROUTE_FALLBACK = 3        /* sc_predict_batch_reduced: the agglomerative fallback */
 };
 int sc_last_batch_routes(sc_handle h, int32_t* routes, int count);
 
@@ -496,6 +497,37 @@ int sc_ahc(sc_handle h, const double* x, int n, int d, int linkage, int n_cluste
 /* utils.get_cluster_centroids (utils.py:159-176): out is (k, d), k = max(labels) + 1 */
 int sc_cluster_centroids(sc_handle h, const double* x, int n, int d, const int64_t* labels,
                          int k, double* out);
+/* sc_ahc for every listed array (any dtype, host or device memory, the same cols; each at least
+ * 2 rows) in one call, and optionally utils.get_cluster_centroids of each: centroids (may be NULL,
+ * or hold NULL entries) receives (k_i, cols) doubles, k_i = n_clusters, or at most rows_i when
+ * the tree is cut at distance_threshold.  Every descriptor is validated before the first launch.
+ * The call works in waves: the longest remaining members whose buffers fit the wave budget share
+ * one allocation, one launch per step (a workgroup per member in the chain, a wavefront per member
+ * of up to 128 rows under average linkage) and ONE synchronisation before their trees are cut on
+ * host threads.  A member that alone exceeds the budget, or has 4096 rows or more, runs sc_ahc's
+ * own path inside the call.  A member with a zero or non-finite row fails the call with
+ * SC_ERR_INVALID; the message names its index. */
+int sc_batch_ahc(sc_handle h, const sc_array* xs, int count, int linkage, int n_clusters,
+                 double distance_threshold, int64_t* const* labels, double* const* centroids);
+/* Bytes of device memory a wave of sc_batch_ahc / sc_predict_batch_reduced may take; 0 (the
+ * default): half of what hipMemGetInfo reports free when the wave is planned. */
+int sc_set_reduce_wave_bytes(sc_handle h, size_t bytes);
+/* sc_predict_batch_arrays in its grouped form for a clusterer with max_spectral_size and / or
+ * fallback_options.spectral_min_embeddings (spectral_clusterer.py:170-199, 229-248;
+ * fallback_clusterer.py:108-124).  Utterance i is of kind
+ *   2  rows < spectral_min_embeddings: average-linkage AHC cut at agglomerative_threshold,
+ *   1  max_spectral_size > 0 and rows > max_spectral_size: complete-linkage AHC down to
+ *      max_spectral_size clusters, the spectral path on their centroids (which stay on the
+ *      device), labels[i][r] = spectral label of row r's cluster,
+ *   0  everything else: the spectral path on the rows.
+ * Kinds 1 and 2 run as sc_batch_ahc runs them; then ONE grouped batch clusters the rows of kind 0
+ * and the centroids of kind 1.  diags[i] is the spectral run's (zeroed for kind 2),
+ * sc_last_batch_routes reports its route, SC_BATCH_ROUTE_FALLBACK for kind 2.  kinds (may be
+ * NULL) receives the kind of every utterance. */
+int sc_predict_batch_reduced(sc_handle h, const sc_array* xs, int count, const sc_config* cfg,
+                             int max_spectral_size, int spectral_min_embeddings,
+                             double agglomerative_threshold, int64_t* const* labels,
+                             sc_diag* diags, int group, int32_t* kinds);
 
 /*
  * Stream pool: up to `capacity` streaming sessions (multi_stage_clusterer.py:128-180) whose

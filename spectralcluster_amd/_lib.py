@@ -32,6 +32,9 @@ STAGE_NAMES = ("affinity", "refine", "diffuse", "scaling", "eig", "kmeans",
 
 # sc_last_batch_routes: what ran for an utterance of the last batch call
 BATCH_ROUTE_SINGLE, BATCH_ROUTE_GROUP_LANCZOS, BATCH_ROUTE_GROUP_JACOBI = range(3)
+BATCH_ROUTE_FALLBACK = 3  # sc_predict_batch_reduced: the agglomerative fallback clustered it
+# sc_predict_batch_reduced: what an utterance of the batch was
+BATCH_KIND_SPECTRAL, BATCH_KIND_REDUCED, BATCH_KIND_FALLBACK = range(3)
 DIFFUSE_PATH_NONE, DIFFUSE_PATH_EXPLICIT, DIFFUSE_PATH_FREE, DIFFUSE_PATH_FREE_THEN_EXPLICIT = range(4)
 
 _LIB_NAME = "libspectralcluster_amd.so"
@@ -289,6 +292,16 @@ PROTOTYPES = {
                               ctypes.POINTER(ctypes.c_int)]),
     "sc_cluster_centroids": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int, ctypes.c_int,
                                             _c_int64_p, ctypes.c_int, _c_double_p]),
+    "sc_batch_ahc": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray), ctypes.c_int,
+                                    ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                    ctypes.POINTER(_c_int64_p), ctypes.POINTER(_c_double_p)]),
+    "sc_set_reduce_wave_bytes": (ctypes.c_int, [_handle_t, ctypes.c_size_t]),
+    "sc_predict_batch_reduced": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray), ctypes.c_int,
+                                                ctypes.POINTER(ScConfig), ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_double,
+                                                ctypes.POINTER(_c_int64_p),
+                                                ctypes.POINTER(ScDiag), ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_int32)]),
     "sc_pool_create": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, ctypes.POINTER(_handle_t)]),
     "sc_pool_destroy": (ctypes.c_int, [_handle_t]),

@@ -16,7 +16,10 @@
 //   * a stream pool (pool_api.hip) runs the three device steps for all its sessions in one launch
 //     each: k_pool_cosine_distance, k_ahc_nn_chain_pool (a workgroup per session),
 //     k_pool_centroids; its fallback stage (sessions of up to 128 rows, average linkage) runs the
-//     first two as k_pool_linkage_lds: the distance matrix in LDS, a wavefront per session.
+//     first two as k_pool_linkage_lds: the distance matrix in LDS, a wavefront per session;
+//   * a batch of utterances of any size (batch_reduce.hip: sc_batch_ahc, sc_predict_batch_reduced)
+//     runs them from a table of per-member descriptors: k_batch_cosine_distance,
+//     k_ahc_nn_chain_batch (a workgroup per member), k_batch_linkage_lds, k_batch_centroids.
 #include <hip/hip_runtime.h>
 
 #include "dpp.h"
@@ -154,10 +157,41 @@ __global__ __launch_bounds__(kAhcThreads) void k_ahc_nn_chain(double* __restrict
                                                               int n, int method,
                                                               int* __restrict__ size,
                                                               int* __restrict__ chain,
-                                                              double* __restrict__ Z) {
+                                                              double* __restrict__ Z,
+                                                              const int* __restrict__ bad) {
   __shared__ double s_val[kAhcThreads / 64];
   __shared__ int s_idx[kAhcThreads / 64];
+  // a NaN row of D leaves the last scans without a neighbour (index -1): the body needs finite
+  // distances, the host reports the word
+  if (bad != nullptr && *bad != 0) return;
   ahc_nn_chain_body(D, ld, n, method, size, chain, Z, s_val, s_idx);
+}
+
+// ---- a batch of problems of any size (sc_batch_ahc): a table of descriptors in device memory,
+//      position z of a launch works on table[first + z] ----
+// rows blockIdx.x, blockIdx.x + gridDim.x, ... of member blockIdx.y
+__global__ __launch_bounds__(256) void k_batch_cosine_distance(
+    const AhcBatchItem* __restrict__ table, int first) {
+  const AhcBatchItem& it = table[first + blockIdx.y];
+  const int n = it.n, ld = it.ld;
+  double* __restrict__ c = it.D;
+  for (int row = blockIdx.x; row < n; row += gridDim.x)
+    for (int col = threadIdx.x; col < n; col += 256) {
+      double v = c[(size_t)row * ld + col];
+      v = v > 1.0 ? 1.0 : (v < -1.0 ? -1.0 : v);  // k_cosine_distance's expression
+      c[(size_t)row * ld + col] = 1.0 - v;
+    }
+}
+
+// One persistent workgroup per member; the workgroups are independent (no wait between them),
+// so the grid may exceed what the device holds at once.
+__global__ __launch_bounds__(kAhcThreads) void k_ahc_nn_chain_batch(
+    const AhcBatchItem* __restrict__ table, int first) {
+  __shared__ double s_val[kAhcThreads / 64];
+  __shared__ int s_idx[kAhcThreads / 64];
+  const AhcBatchItem& it = table[first + blockIdx.x];
+  if (it.n < 2 || *it.bad != 0) return;  // before D is touched
+  ahc_nn_chain_body(it.D, it.ld, it.n, it.method, it.size, it.chain, it.Z, s_val, s_idx);
 }
 
 // ---- stream pool: the same three steps for every session of a step in one launch each ----
@@ -226,29 +260,22 @@ __device__ __forceinline__ void wave_argmin(double& v, int& idx) {
   idx = __builtin_amdgcn_readlane(idx, 63);
 }
 
-// Workgroup blockIdx.x works on position first + blockIdx.x of the launch's lists.  The dynamic
-// LDS is sized for the largest session of the launch (pool_linkage_lds_bytes); a session lays
-// its matrix out with its own odd pitch n | 1.
-__global__ __launch_bounds__(64) void k_pool_linkage_lds(const PoolSlabs p,
-                                                         const int* __restrict__ slots,
-                                                         const int* __restrict__ rows,
-                                                         int first) {
-  extern __shared__ __attribute__((aligned(16))) double lds_d[];
-  const int b = first + blockIdx.x;
-  const int n = rows[b];
-  if (n < 2 || n > kPoolLdsLinkageMax) return;
+// The whole linkage of one problem of 2 <= n <= kPoolLdsLinkageMax rows on the calling wavefront
+// (a 64-thread workgroup): c the GEMM's cosines (pitch ldc), Z the merge list, lds_d the
+// workgroup's dynamic LDS (pool_linkage_lds_bytes(n) at least).  A problem lays its matrix out
+// with its own odd pitch n | 1.
+__device__ __forceinline__ void linkage_lds_body(const double* __restrict__ c, int ldc, int n,
+                                                 double* __restrict__ Z, double* lds_d) {
   const int lane = threadIdx.x;
   const int pitch = n | 1;  // odd: a column walk touches every bank pair once
   double* D = lds_d;                                   // n x pitch
   int* size = reinterpret_cast<int*>(D + n * pitch);   // n
   int* chain = size + n;                               // n
-  double* Z = p.Z + (size_t)b * p.stride_z;
   const double inf = __builtin_huge_val();
   {  // the GEMM's cosines -> distances (k_pool_cosine_distance's expression)
-    const double* c = p.D + (size_t)slots[b] * p.stride_d;
     for (int e = lane; e < n * n; e += 64) {
       const int i = e / n, j = e - i * n;
-      double v = c[(size_t)i * p.ldd + j];
+      double v = c[(size_t)i * ldc + j];
       v = v > 1.0 ? 1.0 : (v < -1.0 ? -1.0 : v);
       D[i * pitch + j] = 1.0 - v;
     }
@@ -334,6 +361,30 @@ __global__ __launch_bounds__(64) void k_pool_linkage_lds(const PoolSlabs p,
     __syncthreads();
   }
 }
+
+// Workgroup blockIdx.x works on position first + blockIdx.x of the launch's lists.  The dynamic
+// LDS is sized for the largest session of the launch (pool_linkage_lds_bytes).
+__global__ __launch_bounds__(64) void k_pool_linkage_lds(const PoolSlabs p,
+                                                         const int* __restrict__ slots,
+                                                         const int* __restrict__ rows,
+                                                         int first) {
+  extern __shared__ __attribute__((aligned(16))) double lds_d[];
+  const int b = first + blockIdx.x;
+  const int n = rows[b];
+  if (n < 2 || n > kPoolLdsLinkageMax) return;
+  linkage_lds_body(p.D + (size_t)slots[b] * p.stride_d, p.ldd, n, p.Z + (size_t)b * p.stride_z,
+                   lds_d);
+}
+
+// ... and on member first + blockIdx.x of a batch table (sc_batch_ahc)
+__global__ __launch_bounds__(64) void k_batch_linkage_lds(const AhcBatchItem* __restrict__ table,
+                                                          int first) {
+  extern __shared__ __attribute__((aligned(16))) double lds_d[];
+  const AhcBatchItem& it = table[first + blockIdx.x];
+  const int n = it.n;
+  if (n < 2 || n > kPoolLdsLinkageMax || *it.bad != 0) return;
+  linkage_lds_body(it.D, it.ld, n, it.Z, lds_d);
+}
 #endif  // SC_POOL_LDS_LINKAGE_MAX > 0
 
 // utils.get_cluster_centroids: out[c][f] = mean over members (rows in index order, the
@@ -374,14 +425,53 @@ __global__ __launch_bounds__(256) void k_cluster_centroids(const double* __restr
   out[(size_t)c * d + f] = cluster_centroid_value(X, ldx, n, labels, c, f);
 }
 
+// The same means for every member of a batch from a CSR of its rows grouped by cluster (rows
+// ascending inside a cluster): an output adds its own rows only, in index order, from 0.0 --
+// cluster_centroid_value's bits without its scan of all n labels.  blockIdx.y = member, a
+// thread per (cluster, feature).
+__global__ __launch_bounds__(256) void k_batch_centroids(const AhcBatchItem* __restrict__ table,
+                                                         int first) {
+  const AhcBatchItem& it = table[first + blockIdx.y];
+  if (it.cent == nullptr) return;
+  const int* __restrict__ csr = it.csr;
+  const int k = csr[0], d = it.d;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= k * d) return;
+  const int c = t / d, f = t - c * d;
+  const int* __restrict__ rows = csr + it.kcap + 2;
+  const int begin = csr[1 + c], end = csr[2 + c];
+  double acc = 0.0;
+  for (int r = begin; r < end; ++r) acc += it.X[(size_t)rows[r] * it.ldx + f];
+  it.cent[(size_t)c * d + f] = acc / (double)(end - begin);  // empty: 0 / 0 = NaN, as np.mean
+}
 
 void launch_cosine_distance(hipStream_t s, double* c, int n, int ld) {
   hipLaunchKernelGGL(k_cosine_distance, dim3((n + 255) / 256, n), dim3(256), 0, s, c, n, ld);
 }
 void launch_ahc_nn_chain(hipStream_t s, double* D, int ld, int n, int method, int* size,
-                         int* chain, double* Z) {
+                         int* chain, double* Z, const int* bad) {
   hipLaunchKernelGGL(k_ahc_nn_chain, dim3(1), dim3(kAhcThreads), 0, s, D, ld, n, method, size,
-                     chain, Z);
+                     chain, Z, bad);
+}
+constexpr int kBatchGridY = 32768;  // members per launch where the member is blockIdx.y
+void launch_batch_cosine_distance(hipStream_t s, const AhcBatchItem* table, int first, int count,
+                                  int max_rows) {
+  // 64 workgroups walk the rows of a member: enough to fill the device with a few members,
+  // and a batch of hundreds launches no workgroup that finds nothing to do
+  for (int at = 0; at < count; at += kBatchGridY)
+    hipLaunchKernelGGL(k_batch_cosine_distance,
+                       dim3(std::min(max_rows, 64), std::min(kBatchGridY, count - at)), dim3(256),
+                       0, s, table, first + at);
+}
+void launch_batch_nn_chain(hipStream_t s, const AhcBatchItem* table, int first, int count) {
+  hipLaunchKernelGGL(k_ahc_nn_chain_batch, dim3(count), dim3(kAhcThreads), 0, s, table, first);
+}
+void launch_batch_centroids(hipStream_t s, const AhcBatchItem* table, int first, int count,
+                            int max_outputs) {
+  for (int at = 0; at < count; at += kBatchGridY)
+    hipLaunchKernelGGL(k_batch_centroids,
+                       dim3((max_outputs + 255) / 256, std::min(kBatchGridY, count - at)),
+                       dim3(256), 0, s, table, first + at);
 }
 void launch_cluster_centroids(hipStream_t s, const double* X, int ldx, int n, int d,
                               const int* labels, int k, double* out) {
@@ -410,6 +500,13 @@ void launch_pool_linkage_lds(hipStream_t s, const PoolSlabs& p, const int* slots
   hipLaunchKernelGGL(k_pool_linkage_lds, dim3(count), dim3(64),
                      pool_linkage_lds_bytes(std::min(max_rows, kPoolLdsLinkageMax)), s, p, slots,
                      rows, first);
+}
+void launch_batch_linkage_lds(hipStream_t s, const AhcBatchItem* table, int first, int count,
+                              int max_rows) {
+  SC_OPT_IN_LDS(k_batch_linkage_lds, pool_linkage_lds_bytes(kPoolLdsLinkageMax));
+  hipLaunchKernelGGL(k_batch_linkage_lds, dim3(count), dim3(64),
+                     pool_linkage_lds_bytes(std::min(max_rows, kPoolLdsLinkageMax)), s, table,
+                     first);
 }
 #endif
 void launch_pool_centroids(hipStream_t s, const PoolSlabs& p, const int* slots, const int* rows,

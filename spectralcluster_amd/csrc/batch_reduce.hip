@@ -1,0 +1,451 @@
+// Size reduction and the too-few-embeddings fallback for a whole batch (include/
+// spectralcluster_amd.h sc_batch_ahc, sc_predict_batch_reduced): the host side of many
+// agglomerative clusterings of any size per call.  The members are taken longest first in WAVES:
+// a wave is the longest remaining members whose buffers fit the wave budget, in ONE allocation
+// carved per member, and runs
+//   ingest      every member's rows into its X (ingest_rows_into: host or device, any dtype)
+//   table       1 copy (the descriptors, AhcBatchItem) + the members' `bad` words cleared
+//   distances   k_batch_normalize_rows + ceil(count / 16) grouped fp64 GEMMs (Xn Xn^T)
+//               + k_batch_cosine_distance
+//   linkage     k_ahc_nn_chain_batch (grid = members, a workgroup each); average-linkage members
+//               of up to SC_POOL_LDS_LINKAGE_MAX rows take k_batch_linkage_lds instead (a
+//               wavefront each, the distance pass included)
+//   back        1 copy (all merge lists + all `bad` words) + 1 synchronisation
+//   cut         ahc_tree_cut + the CSR of rows by cluster on the handle's host workers
+//   centroids   1 copy (all CSRs) + k_batch_centroids
+// whatever the members' sizes are.  A member of n >= kReduceSingleMin rows, or one that alone
+// exceeds the budget, runs sc_ahc's own path (callers_api.hip) inside the call.
+// Kernels: ahc.hip, rowops.hip.
+#include "ahc_tree.h"
+#include "handle.h"
+#include "host_pool.h"
+
+#include <numeric>
+#include <thread>
+
+namespace {
+
+constexpr int kReduceSingleMin = 4096;  // from here on a chain has the device to itself anyway
+constexpr double kReduceWaveShare = 0.5;  // of the free memory (the pool and the sweep: <= 0.85)
+
+size_t align256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+struct ReduceMember {
+  int index = 0;  // into the caller's lists
+  int n = 0, linkage = 0, n_clusters = 0;
+  double threshold = 0.0;
+  bool keep_centroids = false;       // centroids stay on the device: dev_cent
+  double* host_centroids = nullptr;  // ... or / and go to the caller
+  // results
+  int k = 0;
+  double* dev_cent = nullptr;
+
+  bool centroids() const { return keep_centroids || host_centroids != nullptr; }
+  int kcap() const { return n_clusters > 0 ? n_clusters : n; }
+  bool lds() const {
+    return kPoolLdsLinkageMax > 0 && linkage == SC_LINKAGE_AVERAGE && n <= kPoolLdsLinkageMax;
+  }
+  size_t csr_ints() const { return centroids() ? (size_t)kcap() + 2 + (size_t)n : 0; }
+  // device bytes of the member's own buffers, and with its share of the wave's slabs
+  size_t own_bytes(int d) const {
+    const size_t rows = align256((size_t)n * round_up(d, 16) * sizeof(double));
+    return 2 * rows + align256((size_t)n * matrix_ld(n) * sizeof(double)) +
+           2 * align256((size_t)n * sizeof(int)) +
+           (centroids() ? align256((size_t)kcap() * d * sizeof(double)) : 0);
+  }
+  size_t wave_bytes(int d) const {
+    return own_bytes(d) + 4 * (size_t)(n - 1) * sizeof(double) + sizeof(int) +
+           sizeof(AhcBatchItem) + csr_ints() * sizeof(int);
+  }
+};
+
+// device allocations of the call: a wave's block, the centroids of a single-path member
+struct DeviceBlocks {
+  std::vector<void*> blocks;
+  void release() {
+    for (void* p : blocks) (void)hipFree(p);
+    blocks.clear();
+  }
+  ~DeviceBlocks() { release(); }
+};
+
+std::string bad_rows_message(int index) {
+  return "utterance " + std::to_string(index) + ": embeddings contain a zero or non-finite row";
+}
+
+// one member on sc_ahc's path: the handle's arena, its split-K product, its chain launch
+int reduce_single(sc_handle h, const sc_array& a, ReduceMember* m, int64_t* labels,
+                  DeviceBlocks* blocks) {
+  h->sweep_slot.clear();
+  SC_TRY(ingest_embeddings(h, a, true));
+  const int n = m->n, d = h->d;
+  const int rc = ahc_resident(h, m->linkage, m->n_clusters, m->threshold, labels, &m->k);
+  if (rc == SC_ERR_INVALID) return fail(h, rc, "utterance " + std::to_string(m->index) + ": " + h->err);
+  SC_TRY(rc);
+  if (!m->centroids()) return SC_OK;
+  hipStream_t s = h->stream;
+  const size_t bytes = (size_t)m->k * d * sizeof(double);
+  void* out = nullptr;
+  SC_HIP(h, hipMalloc(&out, bytes));
+  blocks->blocks.push_back(out);
+  SC_TRY(grow(h, h->ahc_lab, (size_t)n * sizeof(int)));
+  std::vector<int> lab32(n);
+  for (int r = 0; r < n; ++r) lab32[r] = (int)labels[r];
+  SC_HIP(h, hipMemcpyAsync(h->ahc_lab.p, lab32.data(), (size_t)n * sizeof(int),
+                           hipMemcpyHostToDevice, s));
+  launch_cluster_centroids(s, ptr<double>(h->X), h->ldx, n, d, ptr<int>(h->ahc_lab), m->k,
+                           static_cast<double*>(out));
+  SC_TRY(check_last(h, "centroid launch"));
+  if (m->host_centroids)
+    SC_HIP(h, hipMemcpyAsync(m->host_centroids, out, bytes, hipMemcpyDeviceToHost, s));
+  SC_HIP(h, hipStreamSynchronize(s));  // (lab32 is a local)
+  m->dev_cent = static_cast<double*>(out);
+  return SC_OK;
+}
+
+// One wave: `wave` lists its members, those of the chain kernel first, then those of the LDS
+// kernel, each part longest first.  The block joins `blocks`; on return the stream has drained.
+int reduce_wave(sc_handle h, const sc_array* xs, int d, const std::vector<ReduceMember*>& wave,
+                int64_t* const* labels, DeviceBlocks* blocks) {
+  const int count = (int)wave.size();
+  const int ldx = round_up(d, 16);
+  hipStream_t s = h->stream;
+  std::vector<size_t> z_at(count), csr_at(count);
+  size_t z_doubles = 0, csr_ints = 0, own = 0;
+  int n_chain = 0, chain_rows = 0, lds_rows = 0, max_outputs = 0;
+  for (int i = 0; i < count; ++i) {
+    const ReduceMember& m = *wave[i];
+    z_at[i] = z_doubles;
+    z_doubles += 4 * (size_t)(m.n - 1);
+    csr_at[i] = csr_ints;
+    csr_ints += m.csr_ints();
+    own += m.own_bytes(d);
+    if (m.lds()) {
+      lds_rows = std::max(lds_rows, m.n);
+    } else {
+      n_chain = i + 1;
+      chain_rows = std::max(chain_rows, m.n);
+    }
+    if (m.centroids()) max_outputs = std::max(max_outputs, m.kcap() * d);
+  }
+  // the slabs every member has a share of: descriptors | merge lists + bad words | CSRs
+  const size_t table_bytes = align256((size_t)count * sizeof(AhcBatchItem));
+  const size_t back_bytes = align256(z_doubles * sizeof(double) + (size_t)count * sizeof(int));
+  const size_t csr_bytes = align256(csr_ints * sizeof(int));
+  const size_t staged = table_bytes + back_bytes + csr_bytes;
+  if (h->h_reduce_bytes < staged) {  // (the stream is idle: every wave ends drained)
+    if (h->h_reduce) SC_HIP(h, hipHostFree(h->h_reduce));
+    h->h_reduce = nullptr;
+    h->h_reduce_bytes = 0;
+    SC_HIP(h, hipHostMalloc(&h->h_reduce, staged));
+    h->h_reduce_bytes = staged;
+  }
+  void* block = nullptr;
+  SC_HIP(h, hipMalloc(&block, staged + own));
+  blocks->blocks.push_back(block);
+  char* dev = static_cast<char*>(block);
+  char* host = static_cast<char*>(h->h_reduce);
+  AhcBatchItem* table_d = reinterpret_cast<AhcBatchItem*>(dev);
+  AhcBatchItem* table_h = reinterpret_cast<AhcBatchItem*>(host);
+  double* Z_d = reinterpret_cast<double*>(dev + table_bytes);
+  double* Z_h = reinterpret_cast<double*>(host + table_bytes);
+  int* bad_d = reinterpret_cast<int*>(Z_d + z_doubles);
+  const int* bad_h = reinterpret_cast<const int*>(Z_h + z_doubles);
+  int* csr_d = reinterpret_cast<int*>(dev + table_bytes + back_bytes);
+  int* csr_h = reinterpret_cast<int*>(host + table_bytes + back_bytes);
+  char* at = dev + staged;
+  auto carve = [&](size_t bytes) {
+    void* p = at;
+    at += align256(bytes);
+    return p;
+  };
+  for (int i = 0; i < count; ++i) {
+    const ReduceMember& m = *wave[i];
+    AhcBatchItem& it = table_h[i];
+    const size_t rows = (size_t)m.n * ldx * sizeof(double);
+    it.n = m.n;
+    it.ld = matrix_ld(m.n);
+    it.ldx = ldx;
+    it.d = d;
+    it.kcap = m.kcap();
+    it.method = m.linkage;
+    it.X = static_cast<double*>(carve(rows));
+    it.Xn = static_cast<double*>(carve(rows));
+    it.D = static_cast<double*>(carve((size_t)m.n * it.ld * sizeof(double)));
+    it.size = static_cast<int*>(carve((size_t)m.n * sizeof(int)));
+    it.chain = static_cast<int*>(carve((size_t)m.n * sizeof(int)));
+    it.Z = Z_d + z_at[i];
+    it.bad = bad_d + i;
+    it.csr = m.centroids() ? csr_d + csr_at[i] : nullptr;
+    it.cent = m.centroids() ? static_cast<double*>(carve((size_t)it.kcap * d * sizeof(double)))
+                            : nullptr;
+  }
+  SC_HIP(h, hipMemcpyAsync(table_d, table_h, (size_t)count * sizeof(AhcBatchItem),
+                           hipMemcpyHostToDevice, s));
+  SC_HIP(h, hipMemsetAsync(bad_d, 0, (size_t)count * sizeof(int), s));
+  bool sync = false;  // (every wave synchronises before it returns)
+  for (int i = 0; i < count; ++i)
+    SC_TRY(ingest_rows_into(h, xs[wave[i]->index], const_cast<double*>(table_h[i].X), ldx, s,
+                            &sync));
+  launch_batch_normalize(s, table_d, count, std::max(chain_rows, lds_rows));
+  // sc_ahc's unit rows and symmetric product (whole K per tile), 16 members per launch
+  for (int base = 0; base < count; base += kGroupMax) {
+    GemmGroupItem items[kGroupMax];
+    const int cnt = std::min(kGroupMax, count - base);
+    for (int z = 0; z < cnt; ++z) {
+      const AhcBatchItem& it = table_h[base + z];
+      items[z].A = it.Xn;
+      items[z].lda = ldx;
+      items[z].C = it.D;
+      items[z].ldc = it.ld;
+      items[z].n = it.n;
+      items[z].K = d;
+    }
+    launch_gemm_nt_group(s, items, cnt, kEpiNone, 0);
+  }
+  if (n_chain > 0) {
+    launch_batch_cosine_distance(s, table_d, 0, n_chain, chain_rows);
+    launch_batch_nn_chain(s, table_d, 0, n_chain);
+  }
+#if SC_POOL_LDS_LINKAGE_MAX > 0
+  if (count > n_chain) launch_batch_linkage_lds(s, table_d, n_chain, count - n_chain, lds_rows);
+#endif
+  SC_TRY(check_last(h, "batched agglomerative clustering launch"));
+  SC_HIP(h, hipMemcpyAsync(Z_h, Z_d, z_doubles * sizeof(double) + (size_t)count * sizeof(int),
+                           hipMemcpyDeviceToHost, s));
+  SC_HIP(h, hipStreamSynchronize(s));
+  int bad_index = -1;  // (the first of the batch, whatever the wave's order)
+  for (int i = 0; i < count; ++i)
+    if (bad_h[i] != 0 && (bad_index < 0 || wave[i]->index < bad_index)) bad_index = wave[i]->index;
+  if (bad_index >= 0) return fail(h, SC_ERR_INVALID, bad_rows_message(bad_index));
+  // sort, relabel, heap cut and the rows of every cluster: independent per member
+  if (!h->gpool) {
+    const unsigned hw = std::thread::hardware_concurrency();
+    h->gpool = new HostPool(hw >= 64 ? kGroupMax - 1 : (hw >= 8 ? 6 : (hw >= 4 ? 2 : 0)));
+  }
+  h->gpool->run(count, [&](int i) {
+    ReduceMember& m = *wave[i];
+    int64_t* lab = labels[m.index];
+    m.k = ahc_tree_cut(Z_h + z_at[i], m.n, m.n_clusters, m.threshold, lab);
+    if (!m.centroids()) return;
+    int* csr = csr_h + csr_at[i];
+    int* offset = csr + 1;  // k + 1 of them
+    int* rows = csr + m.kcap() + 2;
+    csr[0] = m.k;
+    std::fill(offset, offset + m.k + 1, 0);
+    for (int r = 0; r < m.n; ++r) ++offset[lab[r] + 1];
+    for (int c = 0; c < m.k; ++c) offset[c + 1] += offset[c];
+    std::vector<int> next(offset, offset + m.k);
+    for (int r = 0; r < m.n; ++r) rows[next[lab[r]]++] = r;  // ascending inside a cluster
+  });
+  if (max_outputs > 0) {
+    SC_HIP(h, hipMemcpyAsync(csr_d, csr_h, csr_ints * sizeof(int), hipMemcpyHostToDevice, s));
+    launch_batch_centroids(s, table_d, 0, count, max_outputs);
+    SC_TRY(check_last(h, "batched centroid launch"));
+    for (int i = 0; i < count; ++i) {
+      ReduceMember& m = *wave[i];
+      if (!m.centroids()) continue;
+      m.dev_cent = table_h[i].cent;
+      if (m.host_centroids)
+        SC_HIP(h, hipMemcpyAsync(m.host_centroids, m.dev_cent, (size_t)m.k * d * sizeof(double),
+                                 hipMemcpyDeviceToHost, s));
+    }
+    SC_HIP(h, hipStreamSynchronize(s));  // (the staging is the next wave's)
+  }
+  return SC_OK;
+}
+
+// Every member of `members` (checked: n >= 2, n_clusters <= n): labels[m.index], m.k and the
+// centroids.  `retain`: the device blocks -- and so every dev_cent -- live as long as `blocks`;
+// otherwise a wave's block is freed when the wave is done.
+int reduce_members(sc_handle h, const sc_array* xs, int d, std::vector<ReduceMember>* members,
+                   int64_t* const* labels, DeviceBlocks* blocks, bool retain) {
+  std::vector<int> order(members->size());
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(),
+                   [&](int a, int b) { return (*members)[a].n > (*members)[b].n; });
+  size_t at = 0;
+  while (at < order.size()) {
+    size_t budget = h->reduce_wave_bytes;
+    if (budget == 0) {
+      size_t free_bytes = 0, device_bytes = 0;
+      SC_HIP(h, hipMemGetInfo(&free_bytes, &device_bytes));
+      budget = (size_t)(kReduceWaveShare * (double)free_bytes);
+    }
+    ReduceMember* first = &(*members)[order[at]];
+    if (first->n >= kReduceSingleMin || first->wave_bytes(d) + 3 * 256 > budget) {
+      SC_TRY(reduce_single(h, xs[first->index], first, labels[first->index], blocks));
+      if (!retain) blocks->release();
+      ++at;
+      continue;
+    }
+    std::vector<ReduceMember*> wave;
+    size_t bytes = 3 * 256;  // (the slabs' alignment)
+    while (at < order.size()) {
+      ReduceMember* m = &(*members)[order[at]];
+      if (bytes + m->wave_bytes(d) > budget) break;
+      bytes += m->wave_bytes(d);
+      wave.push_back(m);
+      ++at;
+    }
+    // the members of the LDS kernel behind those of the chain kernel (both stay longest first)
+    std::stable_partition(wave.begin(), wave.end(), [](ReduceMember* m) { return !m->lds(); });
+    SC_TRY(reduce_wave(h, xs, d, wave, labels, blocks));
+    if (!retain) blocks->release();
+  }
+  return SC_OK;
+}
+
+int too_few_rows(sc_handle h, int index, int n) {
+  return fail(h, SC_ERR_INVALID,
+              "utterance " + std::to_string(index) + ": Found array with " +
+                  std::to_string(std::max(n, 0)) +
+                  " sample(s) while a minimum of 2 is required by AgglomerativeClustering.");
+}
+
+}  // namespace
+
+extern "C" int sc_set_reduce_wave_bytes(sc_handle h, size_t bytes) {
+  if (!h) return SC_ERR_INVALID;
+  h->reduce_wave_bytes = bytes;
+  return SC_OK;
+}
+
+extern "C" int sc_batch_ahc(sc_handle h, const sc_array* xs, int count, int linkage,
+                            int n_clusters, double distance_threshold, int64_t* const* labels,
+                            double* const* centroids) {
+  if (!h) return SC_ERR_INVALID;
+  if (!xs || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  if (linkage != SC_LINKAGE_COMPLETE && linkage != SC_LINKAGE_AVERAGE)
+    return fail(h, SC_ERR_INVALID, "linkage must be complete or average");
+  SC_HIP(h, hipSetDevice(h->device));
+  bool device_source = false;
+  std::vector<int> ns;
+  int d = 0;
+  SC_TRY(validate_batch_arrays(h, xs, count, &ns, &d, &device_source, labels));
+  std::vector<ReduceMember> members(count);
+  for (int i = 0; i < count; ++i) {
+    if (ns[i] < 2) return too_few_rows(h, i, ns[i]);
+    if (n_clusters < 0 || n_clusters > ns[i])
+      return fail(h, SC_ERR_INVALID, "utterance " + std::to_string(i) +
+                                         ": Cannot extract more clusters than samples");
+    ReduceMember& m = members[i];
+    m.index = i;
+    m.n = ns[i];
+    m.linkage = linkage;
+    m.n_clusters = n_clusters;
+    m.threshold = distance_threshold;
+    m.host_centroids = centroids ? centroids[i] : nullptr;
+  }
+  DeviceBlocks blocks;
+  return reduce_members(h, xs, d, &members, labels, &blocks, false);
+}
+
+extern "C" int sc_predict_batch_reduced(sc_handle h, const sc_array* xs, int count,
+                                        const sc_config* cfg, int max_spectral_size,
+                                        int spectral_min_embeddings,
+                                        double agglomerative_threshold, int64_t* const* labels,
+                                        sc_diag* diags, int group, int32_t* kinds) {
+  if (!h) return SC_ERR_INVALID;
+  if (!xs || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  if (group < 2)
+    return fail(h, SC_ERR_INVALID, "sc_predict_batch_reduced is the grouped form: group >= 2");
+  if (max_spectral_size < 0 || max_spectral_size == 1)
+    return fail(h, SC_ERR_INVALID, "max_spectral_size should be a relatively big number");
+  // (the spectral run of the centroids must not be a fallback member itself)
+  if (max_spectral_size > 0 && max_spectral_size < spectral_min_embeddings)
+    return fail(h, SC_ERR_INVALID,
+                "max_spectral_size must not be below spectral_min_embeddings in a batch");
+  SC_TRY(validate_config(h, cfg));
+  SC_HIP(h, hipSetDevice(h->device));
+  bool device_source = false;
+  std::vector<int> ns;
+  int d = 0;
+  SC_TRY(validate_batch_arrays(h, xs, count, &ns, &d, &device_source, labels));
+  SC_TRY(sc_clear_constraint(h));  // a batch carries none
+  if (count == 0) {
+    h->last_routes.clear();
+    return SC_OK;
+  }
+  std::vector<int32_t> kind(count, 0);
+  std::vector<ReduceMember> members;
+  std::vector<std::vector<int64_t>> pre(count);  // kind 1: the rows' pre-cluster labels
+  std::vector<int64_t*> ahc_labels(count, nullptr);
+  for (int i = 0; i < count; ++i) {
+    ReduceMember m;
+    m.index = i;
+    m.n = ns[i];
+    if (ns[i] < spectral_min_embeddings) {
+      if (ns[i] < 2) return too_few_rows(h, i, ns[i]);
+      kind[i] = 2;
+      m.linkage = SC_LINKAGE_AVERAGE;
+      m.threshold = agglomerative_threshold;
+      ahc_labels[i] = labels[i];
+    } else if (max_spectral_size > 0 && ns[i] > max_spectral_size) {
+      kind[i] = 1;
+      m.linkage = SC_LINKAGE_COMPLETE;
+      m.n_clusters = max_spectral_size;
+      m.keep_centroids = true;
+      pre[i].resize(ns[i]);
+      ahc_labels[i] = pre[i].data();
+    } else {
+      continue;
+    }
+    members.push_back(m);
+  }
+  if (kinds) std::copy(kind.begin(), kind.end(), kinds);
+  DeviceBlocks blocks;  // the centroids live in them until the spectral batch has returned
+  SC_TRY(reduce_members(h, xs, d, &members, ahc_labels.data(), &blocks, true));
+  // ONE grouped batch: the rows of kind 0, the centroids of kind 1
+  std::vector<int> at;  // position in that batch -> utterance
+  std::vector<sc_array> sub;
+  std::vector<int> sub_ns;
+  std::vector<std::vector<int64_t>> main_labels(count);
+  std::vector<int64_t*> sub_labels;
+  for (int i = 0; i < count; ++i)
+    if (kind[i] == 0) {
+      at.push_back(i);
+      sub.push_back(xs[i]);
+      sub_ns.push_back(ns[i]);
+      sub_labels.push_back(labels[i]);
+    }
+  for (const ReduceMember& m : members) {
+    if (kind[m.index] != 1) continue;
+    sc_array c;
+    c.data = m.dev_cent;
+    c.dtype = SC_DTYPE_F64;
+    c.location = SC_MEM_DEVICE;
+    c.rows = m.k;
+    c.cols = d;
+    c.row_stride = d;
+    c.col_stride = 1;
+    main_labels[m.index].resize(m.k);
+    at.push_back(m.index);
+    sub.push_back(c);
+    sub_ns.push_back(m.k);
+    sub_labels.push_back(main_labels[m.index].data());
+  }
+  const int sub_count = (int)at.size();
+  std::vector<sc_diag> sub_diags(diags ? sub_count : 0);
+  std::vector<int32_t> routes(count, SC_BATCH_ROUTE_FALLBACK);
+  if (sub_count > 0) {
+    // the centroids are written, and what the caller ordered before this handle's stream is
+    // done, before the streams of the batch read either
+    SC_HIP(h, hipStreamSynchronize(h->stream));
+    SC_TRY(predict_batch_grouped_impl(h, sub.data(), sub_ns.data(), d, sub_count, cfg,
+                                      sub_labels.data(), diags ? sub_diags.data() : nullptr,
+                                      group));
+    for (int z = 0; z < sub_count; ++z) routes[at[z]] = h->last_routes[z];
+  }
+  h->last_routes = routes;
+  for (int z = 0; z < sub_count; ++z) {
+    const int i = at[z];
+    if (diags) diags[i] = sub_diags[z];
+    if (kind[i] != 1) continue;
+    for (int r = 0; r < ns[i]; ++r) labels[i][r] = main_labels[i][pre[i][r]];
+  }
+  if (diags)
+    for (int i = 0; i < count; ++i)
+      if (kind[i] == 2) memset(&diags[i], 0, sizeof(sc_diag));
+  return SC_OK;
+}

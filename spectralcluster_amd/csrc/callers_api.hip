@@ -22,26 +22,38 @@ extern "C" int sc_ahc(sc_handle h, const double* x, int n, int d, int linkage, i
   if (n_clusters < 0 || n_clusters > n)
     return fail(h, SC_ERR_INVALID, "Cannot extract more clusters than samples");
   SC_HIP(h, hipSetDevice(h->device));
-  // cosine distances: the affinity stage's normalise + symmetric GEMM, then 1 - clip(c)
   SC_TRY(sc_set_embeddings(h, x, n, d));
+  return ahc_resident(h, linkage, n_clusters, distance_threshold, labels, n_clusters_out);
+}
+
+// ... on the n >= 2 rows resident in h->X; the arguments have been checked
+int ahc_resident(sc_handle h, int linkage, int n_clusters, double distance_threshold,
+                 int64_t* labels, int* n_clusters_out) {
+  const int n = h->n, d = h->d;
+  // cosine distances: the affinity stage's normalise + symmetric GEMM, then 1 - clip(c)
   SC_TRY(ensure_tilemap(h, n));
   hipStream_t s = h->stream;
   const int ld = h->ldn;
-  launch_normalize_rows(s, ptr<double>(h->X), h->ldx, n, d, ptr<double>(h->Xn));
+  SC_TRY(grow(h, h->ahc_size, (size_t)n * sizeof(int)));
+  SC_TRY(grow(h, h->ahc_chain, ((size_t)n + 1) * sizeof(int)));
+  SC_TRY(grow(h, h->ahc_Z, (size_t)n * 4 * sizeof(double)));
+  int* bad_d = ptr<int>(h->ahc_chain) + n;  // a zero or non-finite row: D would hold NaNs
+  SC_HIP(h, hipMemsetAsync(bad_d, 0, sizeof(int), s));
+  launch_normalize_rows(s, ptr<double>(h->X), h->ldx, n, d, ptr<double>(h->Xn), bad_d);
   launch_gemm_nt(s, ptr<double>(h->Xn), h->ldx, ptr<double>(h->Xn), h->ldx, ptr<double>(h->B1),
                  ld, n, n, d, kEpiNone, true, ptr<double>(h->splitk), h->tilemap_cur);
   launch_cosine_distance(s, ptr<double>(h->B1), n, ld);
-  SC_TRY(grow(h, h->ahc_size, (size_t)n * sizeof(int)));
-  SC_TRY(grow(h, h->ahc_chain, (size_t)n * sizeof(int)));
-  SC_TRY(grow(h, h->ahc_Z, (size_t)n * 4 * sizeof(double)));
   launch_ahc_nn_chain(s, ptr<double>(h->B1), ld, n, linkage, ptr<int>(h->ahc_size),
-                      ptr<int>(h->ahc_chain), ptr<double>(h->ahc_Z));
+                      ptr<int>(h->ahc_chain), ptr<double>(h->ahc_Z), bad_d);
   SC_TRY(check_last(h, "agglomerative clustering launch"));
   std::vector<double> Z((size_t)(n - 1) * 4);
+  int bad = 0;
   SC_HIP(h, hipMemcpyAsync(Z.data(), h->ahc_Z.p, Z.size() * sizeof(double),
                            hipMemcpyDeviceToHost, s));
+  SC_HIP(h, hipMemcpyAsync(&bad, bad_d, sizeof(int), hipMemcpyDeviceToHost, s));
   SC_HIP(h, hipStreamSynchronize(s));
   h->have_affinity = h->have_cropval = false;
+  if (bad) return fail(h, SC_ERR_INVALID, "embeddings contain a zero or non-finite row");
   // sort, union-find relabelling and the heap cut: ahc_tree.cpp
   const int k = ahc_tree_cut(Z.data(), n, n_clusters, distance_threshold, labels);
   if (n_clusters_out) *n_clusters_out = k;

@@ -85,6 +85,11 @@ struct sc_handle_s {
   // (column-major), residual partials, restart codes, dense Laplacian scratch
   DevBuf crvec, thetai, Vre, Vim, gpart, gsrc, genL, gneg;
   DevBuf ahc_size, ahc_chain, ahc_Z, ahc_lab, ahc_cent;  // size reduction (AHC) scratch
+  // batched size reduction (batch_reduce.hip): bytes a wave may take (0: a share of the free
+  // memory, sc_set_reduce_wave_bytes), the pinned staging of a wave's tables, merge lists and CSR
+  size_t reduce_wave_bytes = 0;
+  void* h_reduce = nullptr;
+  size_t h_reduce_bytes = 0;
   DevBuf fb_part, fb_small, fb_x, fb_cent, fb_int;      // fallback decisions scratch
   // k-means workspace
   DevBuf kXc, kxsq, kclosest, kcand, kenorm, krnd, kcent, klab32, klab64, kinfo, kchain;
@@ -285,6 +290,10 @@ int predict_batch_streams_impl(sc_handle h, const sc_array* xs, const int* ns, i
 int predict_batch_grouped_impl(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
                                const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
                                int group);
+
+// sc_ahc on the embeddings resident in h->X (ingest_embeddings): callers_api.hip
+int ahc_resident(sc_handle h, int linkage, int n_clusters, double distance_threshold,
+                 int64_t* labels, int* n_clusters_out);
 
 int ensure_eig(sc_handle h, int n);
 

@@ -100,6 +100,14 @@ __global__ __launch_bounds__(kRowThreads) void k_normalize_rows(
     int* __restrict__ bad_rows) {
   normalize_rows_body(X, ldx, n, d, Xn, bad_rows);
 }
+// ---- batched size reduction (sc_internal.h AhcBatchItem): blockIdx.y = member of the table,
+//      one wave per row; a zero or non-finite row latches the member's word
+__global__ __launch_bounds__(kRowThreads) void k_batch_normalize_rows(
+    const AhcBatchItem* __restrict__ table, int first) {
+  const AhcBatchItem& a = table[first + blockIdx.y];
+  if ((int)blockIdx.x * 4 >= a.n) return;
+  normalize_rows_body(a.X, a.ldx, a.n, a.d, a.Xn, a.bad);
+}
 // ---- grouped forms of the row kernels (batch_group.hip): blockIdx.y = member of a batch
 //      group, argument blocks by value in the kernel arguments, n = 0 = idle member
 __global__ __launch_bounds__(kRowThreads) void k_normalize_rows_g(const GroupOf<FrontItem> g) {
@@ -1157,6 +1165,12 @@ void launch_normalize_rows(hipStream_t s, const double* X, int ldx, int n, int d
                            double* Xn, int* bad_rows) {
   hipLaunchKernelGGL(k_normalize_rows, dim3((n + 3) / 4), dim3(kRowThreads), 0, s, X, ldx, n,
                      d, Xn, bad_rows);
+}
+void launch_batch_normalize(hipStream_t s, const AhcBatchItem* table, int count, int max_rows) {
+  for (int at = 0; at < count; at += 32768)  // (the member is blockIdx.y)
+    hipLaunchKernelGGL(k_batch_normalize_rows,
+                       dim3((max_rows + 3) / 4, std::min(32768, count - at)), dim3(kRowThreads),
+                       0, s, table, at);
 }
 void launch_pool_append(hipStream_t s, const PoolSlabs& p, const double* stage,
                         const PoolAppendItem* items, int count, int max_rows) {

@@ -688,8 +688,10 @@ void launch_free_colmax(hipStream_t s, const double* W, int n, const int* rows, 
 void launch_cosine_distance(hipStream_t s, double* c, int n, int ld);
 // nearest-neighbour-chain agglomeration on the n x n distance matrix D (destroyed);
 // method 1 complete, 2 average; Z: (n - 1) x 4 (slot x, slot y, height, size), merge order
+// bad (optional): a device word; when it is set (launch_normalize_rows' bad_rows: a zero or
+// non-finite row, so D holds NaNs) the kernel returns before it touches D
 void launch_ahc_nn_chain(hipStream_t s, double* D, int ld, int n, int method, int* size,
-                         int* chain, double* Z);
+                         int* chain, double* Z, const int* bad = nullptr);
 void launch_cluster_centroids(hipStream_t s, const double* X, int ldx, int n, int d,
                               const int* labels, int k, double* out);
 // ---- stream pool (ahc.hip, rowops.hip; host side pool_api.hip) ---------------------------
@@ -744,10 +746,46 @@ constexpr int kPoolLdsLinkageMax = SC_POOL_LDS_LINKAGE_MAX;
 #if SC_POOL_LDS_LINKAGE_MAX > 0
 void launch_pool_linkage_lds(hipStream_t s, const PoolSlabs& p, const int* slots, const int* rows,
                              int first, int count, int max_rows);
+struct AhcBatchItem;  // (below)
+// the same for members [first, first + count) of a batch table (average linkage, 2 <= n <=
+// kPoolLdsLinkageMax, from the GEMM output in D); a member whose word is set is left alone
+void launch_batch_linkage_lds(hipStream_t s, const AhcBatchItem* table, int first, int count,
+                              int max_rows);
 #endif
 // launch_cluster_centroids (k clusters) for every listed session, into the slot's centroids
 void launch_pool_centroids(hipStream_t s, const PoolSlabs& p, const int* slots, const int* rows,
                            int count, int k);
+
+// ---- batched size reduction (ahc.hip, rowops.hip; host side batch_reduce.hip) ---------------
+// One member of a batch of agglomerative clusterings: members of any n share a launch, each
+// with buffers of its own size.  The kernels read a table of these in device memory; position z
+// of a launch works on table[first + z].
+struct AhcBatchItem {
+  const double* X;  // n x ldx rows as ingested
+  double* Xn;       // their unit-norm copies
+  double* D;        // n x ld: Xn Xn^T, then the distances (the chain destroys them)
+  int* size;        // n
+  int* chain;       // n
+  double* Z;        // (n - 1) x 4 merge list
+  int* bad;         // the member's word: set when a row is zero or non-finite
+  // centroids (cent == nullptr: none wanted): csr[0] = k, csr[1 .. k + 1] the offsets of the
+  // clusters into the row list at csr + kcap + 2 (rows ascending inside a cluster)
+  const int* csr;
+  double* cent;     // k x d
+  int n, ld, ldx, d, kcap, method;
+};
+// Xn rows of every member (launch_normalize_rows' bits); a bad row latches the member's word
+void launch_batch_normalize(hipStream_t s, const AhcBatchItem* table, int count, int max_rows);
+// D = 1 - clip(D) of members [first, first + count) (launch_cosine_distance per member)
+void launch_batch_cosine_distance(hipStream_t s, const AhcBatchItem* table, int first, int count,
+                                  int max_rows);
+// launch_ahc_nn_chain for members [first, first + count): one workgroup each; a member whose
+// word is set, or of n < 2, is left alone
+void launch_batch_nn_chain(hipStream_t s, const AhcBatchItem* table, int first, int count);
+// utils.get_cluster_centroids of members [first, first + count) from their CSR; max_outputs:
+// the largest kcap * d among them
+void launch_batch_centroids(hipStream_t s, const AhcBatchItem* table, int first, int count,
+                            int max_outputs);
 
 // ---- fallback decisions (fallback.hip) ---------------------------------------------------
 void launch_naive_cluster(hipStream_t s, const double* X, int n, int d, double threshold,

@@ -85,6 +85,8 @@ class SpectralClusterer:
     self.last_diag: typing.Optional[_lib.ScDiag] = None
     # one route code per utterance of the last predict_batch (None before the first)
     self.last_batch_routes: typing.Optional[typing.List[int]] = None
+    # what each utterance of the last size-reducing predict_batch was (`_lib.BATCH_KIND_*`)
+    self.last_batch_reduced: typing.Optional[typing.List[int]] = None
     # not in the reference: restart cycles block Lanczos may spend before the dense
     # eigensolver takes over (0 = the library default, 40); predict() returns either way
     self.eig_max_cycles = 0
@@ -447,6 +449,27 @@ class SpectralClusterer:
     of their own (route 1), the rest per utterance on the caller's handle (route 0).  Otherwise
     -- a dense ndarray constraint among them -- every utterance runs predict() on a copy of the
     AutoTune object (routes all 0), with the same results.
+
+    `max_spectral_size` and `fallback_options.spectral_min_embeddings` (the multi-stage
+    regime): the batch is ONE `sc_predict_batch_reduced` call when the clusterer is otherwise
+    one the library batch covers (no AutoTune, `min_clusters` not 1, the default affinity and
+    k-means functions), k-means is the cosine one, `group` is not 1, `streams` is not given, no
+    constraint matrices travel, the fallback -- if an utterance needs it -- is the
+    agglomerative one, and `max_spectral_size >= spectral_min_embeddings` when both are set.
+    The utterances of more than `max_spectral_size` rows are pre-clustered together (complete
+    linkage, a workgroup per utterance in one launch per wave), the ones below
+    `spectral_min_embeddings` clustered by the fallback together (average linkage), and one
+    grouped batch then clusters the centroids of the first kind with the utterances that needed
+    neither.  Results are predict()'s -- float64 labels for a size-reduced utterance (the
+    reference's `chain_labels`), int64 otherwise.  `last_batch_reduced` lists what each
+    utterance was (`_lib.BATCH_KIND_*`: 0 spectral, 1 size-reduced, 2 fallback),
+    `last_batch_routes` the route of its spectral run (3, `_lib.BATCH_ROUTE_FALLBACK`, for a
+    fallback utterance), `last_batch_diags` that run's diagnostics (zeroed for a fallback
+    utterance).  Raised before anything is launched: predict()'s ValueError for a
+    `max_spectral_size` that is not above `max_clusters` / `min_clusters`, and for a fallback
+    utterance of one row.  An utterance with a zero or non-finite row raises a ValueError that
+    names its index.  Everything else -- the `Naive` fallback, `min_clusters=1`, constraints,
+    AutoTune, `group=1`, `streams` -- stays the per-utterance loop (routes all 0).
     """
     if autotune_from_entry_state and self.autotune is not None:
       return self._predict_batch_entry_state(utterances, constraint_matrices, streams, group)
@@ -467,6 +490,9 @@ class SpectralClusterer:
           self.last_batch_routes = [_lib.BATCH_ROUTE_SINGLE] * len(utterances)
           return [self.predict(u, c) for u, c in zip(utterances, constraint_matrices)]
         banded = list(constraint_matrices)
+    if (not library_batch and banded is None and
+        self._reduced_batch_covers(utterances, streams, group)):
+      return self._predict_batch_reduced(utterances, 16 if group is None else int(group))
     if group is None:
       group = 16 if streams is None else 0
     if streams is None:
@@ -657,6 +683,98 @@ class SpectralClusterer:
         (self.fallback_options.spectral_min_embeddings > 1 and not min_embeddings_met) or
         self.affinity_function is not utils.compute_affinity_matrix or
         self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans)
+
+  def _batch_kind(self, n: int) -> int:
+    """What predict() does with an utterance of n rows (`_lib.BATCH_KIND_*`): the fallback
+    clusterer, size reduction first, or the spectral path as it is (reference :229-248)."""
+    if n < self.fallback_options.spectral_min_embeddings:
+      return _lib.BATCH_KIND_FALLBACK
+    if self.max_spectral_size is not None and n > self.max_spectral_size:
+      return _lib.BATCH_KIND_REDUCED
+    return _lib.BATCH_KIND_SPECTRAL
+
+  def _reduced_batch_covers(self, utterances: typing.Sequence, streams: typing.Optional[int],
+                            group: typing.Optional[int]) -> bool:
+    """Is this batch ONE `sc_predict_batch_reduced` call?  A clusterer that
+    `_library_batch_covers` but for `max_spectral_size` / `spectral_min_embeddings`, in the
+    grouped form, cosine k-means, no constraints (the caller has looked), an agglomerative
+    fallback for the utterances that need one, and centroids that are not fallback members
+    themselves (predict() recurses on them)."""
+    options = self.fallback_options
+    if self.max_spectral_size is None and options.spectral_min_embeddings <= 1:
+      return False  # (nothing to reduce: the caller's own answer stands)
+    if (self.autotune is not None or self.min_clusters == 1 or
+        self.affinity_function is not utils.compute_affinity_matrix or
+        self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans):
+      return False
+    if streams is not None or (group is not None and int(group) <= 1):
+      return False
+    try:
+      if _lib.kmeans_metric_code(self.custom_dist) != _lib.KMEANS_METRICS["cosine"]:
+        return False
+    except (ValueError, _lib.UnsupportedOnDeviceError):
+      return False
+    if (self.max_spectral_size is not None and
+        self.max_spectral_size < options.spectral_min_embeddings):
+      return False
+    try:
+      kinds = [self._batch_kind(int(np.shape(u)[0])) for u in utterances]
+    except (IndexError, TypeError):
+      return False  # (not (n, d): predict() says what is wrong with it)
+    if (_lib.BATCH_KIND_FALLBACK in kinds and options.fallback_clusterer_type !=
+        fallback_clusterer.FallbackClustererType.Agglomerative):
+      return False
+    return True
+
+  def _predict_batch_reduced(self, utterances: typing.Sequence,
+                             group: int) -> typing.List[np.ndarray]:
+    """ONE `sc_predict_batch_reduced` call; `_reduced_batch_covers` holds."""
+    for u in utterances:
+      if isinstance(u, np.ndarray) and u.ndim != 2:
+        raise ValueError("all utterances must be (n_i, d) with the same d")
+    count = len(utterances)
+    if count == 0:
+      self.last_batch_routes, self.last_batch_reduced, self.last_batch_diags = [], [], []
+      return []
+    sources = []
+    try:
+      with _lib.use_device(self.device):
+        for u in utterances:
+          sources.append(_dlpack.describe(u, self._handle))
+      d = sources[0].shape[1]
+      if any(src.shape[1] != d for src in sources):
+        raise ValueError("all utterances must be (n_i, d) with the same d")
+      # what predict() raises for an utterance, before anything is launched
+      for src in sources:
+        kind = self._batch_kind(src.shape[0])
+        if kind == _lib.BATCH_KIND_FALLBACK and src.shape[0] < 2:
+          raise ValueError("Found array with %d sample(s) while a minimum of 2 is required by "
+                           "AgglomerativeClustering." % src.shape[0])
+        if kind == _lib.BATCH_KIND_REDUCED and (
+            self.max_spectral_size < 2 or
+            (self.max_clusters and self.max_spectral_size <= self.max_clusters) or
+            (self.min_clusters and self.max_spectral_size <= self.min_clusters)):
+          raise ValueError("max_spectral_size should be a relatively big number")
+      labels = [np.empty(src.shape[0], dtype=np.int64) for src in sources]
+      handle = self._handle()
+      lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
+      diags = (_lib.ScDiag * count)()
+      kinds = (ctypes.c_int32 * count)()
+      handle.check(handle.lib.sc_predict_batch_reduced(
+          handle.raw, (_lib.ScArray * count)(*[src.array for src in sources]), count,
+          self.build_config(), int(self.max_spectral_size or 0),
+          int(self.fallback_options.spectral_min_embeddings),
+          float(self.fallback_options.agglomerative_threshold), lp, diags, int(group), kinds),
+          ValueError)
+    finally:
+      for src in sources:
+        src.release()
+    self._batch_report(handle, diags, count)
+    self.last_batch_reduced = [int(k) for k in kinds]
+    # utils.chain_labels fills np.zeros: a size-reduced utterance's labels are float64, as
+    # predict() returns them
+    return [l.astype(np.float64) if k == _lib.BATCH_KIND_REDUCED else l
+            for l, k in zip(labels, self.last_batch_reduced)]
 
   def _batch_arrays_call(self, handle: _lib.Handle, arrays: typing.Sequence[_lib.ScArray],
                          labels: typing.Sequence[np.ndarray], diags, group: int,

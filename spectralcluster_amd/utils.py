@@ -162,3 +162,53 @@ def cosine_agglomerative_clustering(embeddings: np.ndarray,
       int(n_clusters or 0), float(distance_threshold or 0.0), _lib.as_int64_p(labels),
       ctypes.byref(found)))
   return labels
+
+
+def cosine_agglomerative_clustering_batch(embeddings_list: typing.Sequence,
+                                          n_clusters: typing.Optional[int] = None,
+                                          linkage: str = "complete",
+                                          distance_threshold: typing.Optional[float] = None,
+                                          return_centroids: bool = False):
+  """`cosine_agglomerative_clustering` of every entry of `embeddings_list` (each anything
+  predict() takes: NumPy arrays and DLPack objects, float64 / float32 / float16 / bfloat16, host
+  or device memory, mixed freely; all with the same number of columns) in ONE `sc_batch_ahc`
+  call: entries of any size share the launches, a workgroup per entry in the chain.  Returns the
+  list of label arrays; with `return_centroids` also the list of `get_cluster_centroids` of each
+  entry (bit for bit).  An entry with a zero or non-finite row raises a ValueError that names its
+  index."""
+  from spectralcluster_amd import _dlpack  # (it imports this module's siblings)
+  if linkage not in LINKAGE_CODES:
+    raise _lib.UnsupportedOnDeviceError("linkage must be 'complete' or 'average'")
+  if (n_clusters is None) == (distance_threshold is None):
+    raise ValueError("Exactly one of n_clusters and distance_threshold has to be set, "
+                     "and the other needs to be None.")
+  for e in embeddings_list:
+    if isinstance(e, np.ndarray) and e.ndim != 2:
+      raise ValueError("embeddings must be 2-dimensional")
+  count = len(embeddings_list)
+  if count == 0:
+    return ([], []) if return_centroids else []
+  handle = _lib.default_handle()
+  sources = []
+  try:
+    for e in embeddings_list:
+      sources.append(_dlpack.describe(e, lambda: handle))
+    d = sources[0].shape[1]
+    if any(src.shape[1] != d for src in sources):
+      raise ValueError("all utterances must be (n_i, d) with the same d")
+    labels = [np.empty(src.shape[0], dtype=np.int64) for src in sources]
+    lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
+    centroids, cp = None, None
+    if return_centroids:
+      centroids = [np.empty((min(int(n_clusters), src.shape[0]) if n_clusters else src.shape[0], d),
+                            dtype=np.float64) for src in sources]
+      cp = (ctypes.POINTER(ctypes.c_double) * count)(*[_lib.as_double_p(c) for c in centroids])
+    handle.check(handle.lib.sc_batch_ahc(
+        handle.raw, (_lib.ScArray * count)(*[src.array for src in sources]), count,
+        LINKAGE_CODES[linkage], int(n_clusters or 0), float(distance_threshold or 0.0), lp, cp))
+  finally:
+    for src in sources:
+      src.release()
+  if not return_centroids:
+    return labels
+  return labels, [c[:int(l.max()) + 1] for c, l in zip(centroids, labels)]
