@@ -530,6 +530,56 @@ int sc_predict_batch_reduced(sc_handle h, const sc_array* xs, int count, const s
                              sc_diag* diags, int group, int32_t* kinds);
 
 /*
+ * min_clusters = 1: the single-cluster test (fallback_clusterer.py:127-187) inside the batch.
+ * `condition` is one of the four conditions that read the affinity (the values of
+ * SingleClusterCondition); the FallbackClusterer condition reads the embeddings and has no
+ * batched form.  diagonal_offset is read by SC_SINGLE_GMM_BIC alone, threshold by the other three.
+ */
+enum {
+  SC_SINGLE_GMM_BIC = 1,           /* bic1 < bic2 of sc_affinity_gmm_bic */
+  SC_SINGLE_ALL_AFFINITY = 2,      /* affinity.min() > threshold */
+  SC_SINGLE_NEIGHBOR_AFFINITY = 3, /* np.diag(affinity, 1).min() > threshold */
+  SC_SINGLE_AFFINITY_STD = 4       /* np.std(affinity) < threshold */
+};
+typedef struct sc_single_check {
+  int32_t condition;        /* SingleClusterCondition: 1 GmmBic, 2 All, 3 Neighbor, 4 Std */
+  int32_t diagonal_offset;
+  double  threshold;
+} sc_single_check;
+/* sizeof(sc_single_check) and the byte offsets of its 3 fields, in declaration order (a binding
+ * checks its mirror against them) */
+int sc_single_check_layout(int* check_bytes, int* field_offsets);
+/* sc_predict_batch_arrays in its grouped form (group >= 2, else SC_ERR_INVALID) for a clusterer
+ * with min_clusters = 1: every utterance's raw affinity is tested before its eigensolver runs, and
+ * an utterance found to hold one cluster gets labels of zeros, a zeroed diag and single[i] = 1 (0
+ * otherwise; single may be NULL).  The test is group-wide device work on the routes of the batch
+ * (sc_last_batch_routes reports the route the utterance's affinity took): n <= 128, ONE launch
+ * per wave of up to 64 utterances, a workgroup each, the whole decision in the kernel; 128 < n <
+ * 4096, launches over (row blocks x members) for a group of up to 16, parameters updated on the
+ * device, one look at the members' state per 8 launches; n >= 4096 and whatever else takes route
+ * 0, sc_affinity_stats / sc_affinity_gmm_bic's own code on the handle.  The refinement front of
+ * an utterance has been enqueued before its verdict is known; a single-cluster utterance leaves
+ * before the eigensolver.  Arithmetic, start, stop rules and constants are those of
+ * sc_affinity_stats / sc_affinity_gmm_bic; the sums are taken in another (fixed) order, so the
+ * BICs agree to rounding (1e-9 relative), the minima bit for bit.  check == NULL:
+ * sc_predict_batch_arrays.  With SC_SINGLE_GMM_BIC an utterance of diagonal_offset >= rows - 1
+ * (or a negative offset) fails the call with SC_ERR_INVALID before anything is launched:
+ * sc_affinity_gmm_bic's message and "(utterance i)". */
+int sc_predict_batch_single(sc_handle h, const sc_array* xs, int count, const sc_config* cfg,
+                            const sc_single_check* check, int64_t* const* labels,
+                            sc_diag* diags, int group, int32_t* single);
+/* The decision alone, on `count` affinity matrices in host memory (affinities[i]: ns[i] x ns[i]
+ * row-major doubles), through exactly the kernels the batch runs (the short form for n <= 128,
+ * the chain form for 128 < n < 4096; n >= 4096: the single call's): values = count x 8 doubles
+ * {min, neighbour min, mean, std, bic1, bic2, lloyd steps, em steps} -- the last four are 0
+ * unless the condition is SC_SINGLE_GMM_BIC; lloyd steps / em steps: passes of the Lloyd loop /
+ * of the EM loop of the 2-component fit --, single[i] = 1 for one cluster.  A matrix's values do
+ * not depend on what else is in the call.  Every argument is checked before the first launch
+ * (diagonal_offset as above): values and single are untouched then. */
+int sc_batch_single_check(sc_handle h, const double* const* affinities, const int* ns, int count,
+                          const sc_single_check* check, double* values, int32_t* single);
+
+/*
  * Stream pool: up to `capacity` streaming sessions (multi_stage_clusterer.py:128-180) whose
  * caches stay on the device.  A session lives in a slot 0 .. capacity - 1 and holds up to u2
  * rows of d values; its pre-clusterer reduces them to u1 centroids (2 <= u1 < u2).  All device

@@ -166,6 +166,24 @@ class ScFrontOut(ctypes.Structure):
       ("info", ctypes.c_int32 * SC_FRONT_INFO_COUNT)]
 
 
+# sc_single_check.condition (the values of fallback_clusterer.SingleClusterCondition that read
+# the affinity)
+SC_SINGLE_GMM_BIC, SC_SINGLE_ALL_AFFINITY, SC_SINGLE_NEIGHBOR_AFFINITY, SC_SINGLE_AFFINITY_STD = \
+    range(1, 5)
+# sc_batch_single_check: the 8 values per matrix
+SINGLE_CHECK_VALUES = ("min", "neighbor_min", "mean", "std", "bic1", "bic2", "lloyd_steps",
+                       "em_steps")
+
+
+class ScSingleCheck(ctypes.Structure):
+  """Mirror of `sc_single_check`: the single-cluster test a min_clusters = 1 batch carries."""
+  _fields_ = [
+      ("condition", ctypes.c_int32),
+      ("diagonal_offset", ctypes.c_int32),
+      ("threshold", ctypes.c_double),
+  ]
+
+
 # sc_autotune.proxy (the values of autotune.AutoTuneProxy)
 SC_AUTOTUNE_PERCENTILE_OVER_NME, SC_AUTOTUNE_PERCENTILE_SQRT_OVER_NME = 1, 2
 
@@ -302,6 +320,17 @@ PROTOTYPES = {
                                                 ctypes.POINTER(_c_int64_p),
                                                 ctypes.POINTER(ScDiag), ctypes.c_int,
                                                 ctypes.POINTER(ctypes.c_int32)]),
+    "sc_single_check_layout": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int),
+                                              ctypes.POINTER(ctypes.c_int)]),
+    "sc_predict_batch_single": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray), ctypes.c_int,
+                                               ctypes.POINTER(ScConfig),
+                                               ctypes.POINTER(ScSingleCheck),
+                                               ctypes.POINTER(_c_int64_p),
+                                               ctypes.POINTER(ScDiag), ctypes.c_int,
+                                               ctypes.POINTER(ctypes.c_int32)]),
+    "sc_batch_single_check": (ctypes.c_int, [_handle_t, ctypes.POINTER(_c_double_p), _c_int_p,
+                                             ctypes.c_int, ctypes.POINTER(ScSingleCheck),
+                                             _c_double_p, ctypes.POINTER(ctypes.c_int32)]),
     "sc_pool_create": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, ctypes.POINTER(_handle_t)]),
     "sc_pool_destroy": (ctypes.c_int, [_handle_t]),

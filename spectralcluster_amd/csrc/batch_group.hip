@@ -250,11 +250,49 @@ int take_front(sc_handle lead, const int* ns, Member* mb, int count, const EigRe
   return SC_OK;
 }
 
+// min_clusters = 1: the single-cluster test of a group's (`wave`: a short wave's) members on their
+// raw affinities, as group-wide device work on the owner's stream behind the front's hand-over
+// (single_check.hip).  A0 is read only: no front of an unconstrained batch writes it after the
+// affinity product.  The front of the next group or wave is already enqueued on the other bank's
+// stream, so the chip works on it while the host waits for the members' state.  A member found to
+// hold one cluster leaves here -- state 2, labels of zeros, a zeroed diag; its refinement front
+// ran speculatively -- and never enters the eigensolver.
+int decide_single(sc_handle lead, const int* ns, int64_t* const* labels, sc_diag* diags,
+                  Member* mb, int count, int front_bank, bool wave, int route,
+                  const SingleCheck* sc) {
+  if (!sc || count <= 0) return SC_OK;
+  hipStream_t s = lead->stream;
+  if (front_bank >= 0) {
+    SC_HIP(lead, hipStreamWaitEvent(s, lead->gbank_ev[front_bank], 0));
+  } else {
+    for (int z = 0; z < count; ++z) SC_HIP(lead, hipStreamWaitEvent(s, mb[z].h->sync_ev, 0));
+  }
+  std::vector<SingleMember> ms(count);
+  std::vector<int32_t> one(count, 0);
+  for (int z = 0; z < count; ++z)
+    ms[z] = SingleMember{ptr<double>(mb[z].h->A0), mb[z].h->n, mb[z].h->ldn};
+  SC_TRY(wave ? single_check_wave(lead, s, ms.data(), count, sc->opt, nullptr, one.data())
+              : single_check_group(lead, s, ms.data(), count, sc->opt, nullptr, one.data()));
+  for (int z = 0; z < count; ++z) {
+    if (!one[z]) continue;
+    Member& m = mb[z];
+    m.state = 2;
+    std::fill(labels[m.index], labels[m.index] + ns[m.index], (int64_t)0);
+    if (diags) memset(diags + m.index, 0, sizeof(sc_diag));
+    if (sc->single) sc->single[m.index] = 1;
+    if (lead->groutes) lead->groutes[m.index] = route;
+  }
+  return SC_OK;
+}
+
 // Eigensolver and k-means of a group whose stages before are enqueued (enqueue_front), in
 // lockstep on the owner's stream; then the members that left the common path.
 int finish_group(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* const* labels,
-                 sc_diag* diags, Member* mb, int count, const EigRequest& rq, int front_bank) {
+                 sc_diag* diags, Member* mb, int count, const EigRequest& rq, int front_bank,
+                 const SingleCheck* sc = nullptr) {
   const bool trace = sw::group_trace();
+  SC_TRY(decide_single(lead, ns, labels, diags, mb, count, front_bank, false,
+                       SC_BATCH_ROUTE_GROUP_LANCZOS, sc));
   // ---- eigen: lockstep over the symmetric members
   GroupEigMember em[kGroupMax];
   int emz[kGroupMax], ne = 0;
@@ -296,8 +334,10 @@ int finish_group(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* c
 // Eigensolver and k-means of one wave whose fronts are enqueued:
 int finish_short_wave(sc_handle lead, const int* ns, const sc_config* cfg, int64_t* const* labels,
                       sc_diag* diags, Member* mb, int count, const EigRequest& rq,
-                      GroupEigMember* em, int front_bank = -1) {
+                      GroupEigMember* em, int front_bank = -1, const SingleCheck* sc = nullptr) {
   const bool trace = sw::group_trace();
+  SC_TRY(decide_single(lead, ns, labels, diags, mb, count, front_bank, true,
+                       SC_BATCH_ROUTE_GROUP_JACOBI, sc));
   std::vector<int> emz(count);
   int ne = 0;  // (front_bank >= 0: the wave front, one event for the wave)
   SC_TRY(take_front(lead, ns, mb, count, rq, front_bank, em, emz.data(), &ne));
@@ -322,7 +362,8 @@ int finish_short_wave(sc_handle lead, const int* ns, const sc_config* cfg, int64
 // on the caller's handle and host thread.
 int run_short_route(sc_handle h, const sc_array* xs, const int* ns, int d,
                     const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
-                    const std::vector<int>& list, const EigRequest& rq, const Bands* bands) {
+                    const std::vector<int>& list, const EigRequest& rq, const Bands* bands,
+                    const SingleCheck* sc = nullptr) {
   if (list.empty()) return SC_OK;
   SC_HIP(h, hipStreamSynchronize(h->stream));
   SC_TRY(ensure_seed_table(h));
@@ -369,7 +410,7 @@ int run_short_route(sc_handle h, const sc_array* xs, const int* ns, int d,
     }
     if (rc == SC_OK)
       rc = finish_short_wave(h, ns, cfg, labels, diags, mbs[j % banks].data(), wave_count(j), rq,
-                             em.data(), wave ? j % banks : -1);
+                             em.data(), wave ? j % banks : -1, sc);
     if (rc != SC_OK && ahead) {  // the next wave's uploads read the caller's arrays: let them land
       if (wave) (void)hipStreamSynchronize(h->gbank_stream[(j + 1) % banks]);
       for (int z = 0; !wave && z < wave_count(j + 1); ++z)
@@ -454,7 +495,7 @@ int run_group_lane(sc_handle h, const sc_array* xs, const int* ns, int d,
                    const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
                    const std::vector<int>& grouped, const std::vector<int>& gstart, int width,
                    const std::vector<int>& mine, const EigRequest& rq, int group_limit,
-                   const Bands* bands) {
+                   const Bands* bands, const SingleCheck* sc = nullptr) {
   if (mine.empty()) return SC_OK;
   // (the lead's lockstep chains run on its dedicated stream for the duration of the batch)
   struct StreamSwap {
@@ -512,7 +553,7 @@ int run_group_lane(sc_handle h, const sc_array* xs, const int* ns, int d,
     if (j + banks - 1 < ngroups) SC_TRY(front(j + banks - 1));
     if (trace) fprintf(stderr, "[sc] next front enqueued in %.0f us\n", now_us() - t0);
     SC_TRY(finish_group(h, ns, cfg, labels, diags, mbs[j % banks], group_count(j), rq,
-                        front_bank[j % banks]));
+                        front_bank[j % banks], sc));
   }
   return SC_OK;
 }
@@ -530,6 +571,35 @@ int predict_single_banded(sc_handle h, const std::vector<int>& list, const sc_ar
     SC_TRY(sc_run_resident(h, cfg, labels[i], diags ? diags + i : nullptr));
   }
   return sc_clear_constraint(h);
+}
+
+// The members of a min_clusters = 1 batch that run as single calls on the caller's handle: the
+// affinity, the single call's own decision on it (sc_affinity_stats / sc_affinity_gmm_bic's code),
+// and for a member of several clusters the eigensolver and k-means -- predict()'s sequence.
+int predict_single_checked(sc_handle h, const std::vector<int>& list, const sc_array* xs,
+                           const int* ns, const sc_config* cfg, int64_t* const* labels,
+                           sc_diag* diags, const SingleCheck& sc) {
+  for (int i : list) {
+    h->sweep_slot.clear();
+    SC_TRY(ingest_embeddings(h, xs[i], xs[i].location == SC_MEM_HOST));
+    sc_diag local;
+    sc_diag* dg = diags ? diags + i : &local;
+    memset(dg, 0, sizeof(*dg));
+    h->nev = 0;
+    SC_TRY(sc_compute_affinity(h));
+    int32_t one = 0;
+    SC_TRY(single_check_resident(h, sc.opt, nullptr, &one));
+    if (one) {
+      std::fill(labels[i], labels[i] + ns[i], (int64_t)0);
+      if (sc.single) sc.single[i] = 1;
+      continue;
+    }
+    SC_TRY(eig_ncluster_impl(h, cfg, dg, nullptr));
+    int k = dg->n_clusters_raw;
+    if (cfg->min_clusters > 0 && k < cfg->min_clusters) k = cfg->min_clusters;  // :295-296
+    SC_TRY(sc_cluster(h, cfg, k, labels[i], dg));
+  }
+  return SC_OK;
 }
 
 // Do the cp[] work matrices of a constrained batch fit?  Worst case: every position of both
@@ -559,8 +629,9 @@ bool constraint_workspace_fits(sc_handle h, const Bands& bands, int largest, boo
 // the constrained batch (one lane, member-by-member fronts, enqueue_front's band handling)
 int predict_batch_core(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
                        const sc_config* cfg, int64_t* const* labels, sc_diag* diags, int group,
-                       const Bands& band_set) {
+                       const Bands& band_set, const SingleCheck* sc = nullptr) {
   const Bands* bands = band_set.band ? &band_set : nullptr;
+  if (sc && sc->single) std::fill(sc->single, sc->single + count, 0);
   SC_TRY(validate_config(h, cfg));
   SC_HIP(h, hipSetDevice(h->device));
   group = std::max(1, std::min(group, kGroupMax));
@@ -583,7 +654,11 @@ int predict_batch_core(sc_handle h, const sc_array* xs, const int* ns, int d, in
   h->groutes = h->last_routes.data();
   std::vector<int> grouped, shorts, single;
   for (int i = 0; i < count; ++i) {
-    if (cfg_ok && xs[i].data && ns[i] > 0 && sym_group_eligible(ns[i], rq)) grouped.push_back(i);
+    // (the chain form of the single-cluster test covers n < kScChainMaxN, the route's own limit
+    //  unless a switch has moved that)
+    if (cfg_ok && xs[i].data && ns[i] > 0 && sym_group_eligible(ns[i], rq) &&
+        (!sc || ns[i] < kScChainMaxN))
+      grouped.push_back(i);
     else if (cfg_ok && xs[i].data && ns[i] > 0 && ns[i] <= kDenseMax) shorts.push_back(i);
     else single.push_back(i);
   }
@@ -703,7 +778,7 @@ int predict_batch_core(sc_handle h, const sc_array* xs, const int* ns, int d, in
     bool inline_lane[kGroupLanes] = {false};
     auto run_lane = [&](int l) {
       return run_group_lane(leads[l], xs, ns, d, cfg, labels, diags, grouped, gstart, width,
-                            lane_groups[l], rq, group, bands);
+                            lane_groups[l], rq, group, bands, sc);
     };
     for (int l = 1; l < lanes; ++l) {
       auto body = [&, l]() {
@@ -733,11 +808,13 @@ int predict_batch_core(sc_handle h, const sc_array* xs, const int* ns, int d, in
   // kShortWidth members, largest first (a wave's Jacobi launch lasts as long as its largest member)
   if (!shorts.empty()) {
     std::stable_sort(shorts.begin(), shorts.end(), [&](int a, int b) { return ns[a] > ns[b]; });
-    SC_TRY(run_short_route(h, xs, ns, d, cfg, labels, diags, shorts, rq, bands));
+    SC_TRY(run_short_route(h, xs, ns, d, cfg, labels, diags, shorts, rq, bands, sc));
   }
   // (members outside the grouped path's range -- n >= 4096 above all: their uploads ride under
   //  the previous member's pipeline, api.hip predict_sequence)
-  if (!single.empty() && bands)
+  if (!single.empty() && sc)
+    SC_TRY(predict_single_checked(h, single, xs, ns, cfg, labels, diags, *sc));
+  else if (!single.empty() && bands)
     SC_TRY(predict_single_banded(h, single, xs, cfg, labels, diags, *bands));
   else if (!single.empty())
     SC_TRY(predict_sequence(h, single.data(), (int)single.size(), xs, ns, d, cfg, labels, diags));
@@ -1373,6 +1450,36 @@ int predict_batch_constrained_impl(sc_handle h, const sc_array* xs, const double
   cleanup.rc = predict_batch_core(h, xs, ns, d, count, cfg, labels, diags, group,
                                   make_bands(bands, cfg));
   return cleanup.rc;
+}
+
+extern "C" int sc_predict_batch_single(sc_handle h, const sc_array* xs, int count,
+                                       const sc_config* cfg, const sc_single_check* check,
+                                       int64_t* const* labels, sc_diag* diags, int group,
+                                       int32_t* single) {
+  if (!h) return SC_ERR_INVALID;
+  if (!xs || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  if (group < 2)
+    return fail(h, SC_ERR_INVALID, "sc_predict_batch_single is the grouped form: group >= 2");
+  SC_TRY(validate_config(h, cfg));
+  if (check) SC_TRY(validate_single_check(h, check));
+  SC_HIP(h, hipSetDevice(h->device));
+  bool device_source = false;
+  std::vector<int> ns;
+  int d = 0;
+  SC_TRY(validate_batch_arrays(h, xs, count, &ns, &d, &device_source));
+  // (sc_affinity_gmm_bic's check, for every utterance before anything is launched)
+  for (int i = 0; check && i < count; ++i) SC_TRY(check_single_offset(h, check, ns[i], i));
+  if (count == 0) {
+    h->last_routes.clear();
+    return SC_OK;
+  }
+  if (device_source) SC_HIP(h, hipStreamSynchronize(h->stream));  // (as sc_predict_batch_arrays)
+  SingleCheck sc;
+  sc.opt = check;
+  sc.single = single;
+  if (!check && single) std::fill(single, single + count, 0);
+  return predict_batch_core(h, xs, ns.data(), d, count, cfg, labels, diags, group, Bands(),
+                            check ? &sc : nullptr);
 }
 
 extern "C" int sc_predict_batch_grouped(sc_handle h, const double* const* xs, const int* ns,

@@ -23,6 +23,14 @@ struct Bands {
   int ncp = 0;         // cp[] work matrices a member arena holds for the configured operator
 };
 
+// What a min_clusters = 1 batch carries (sc_predict_batch_single): the single-cluster test every
+// utterance's raw affinity takes before its eigensolver, and where the verdicts go (one per
+// utterance, zeroed by predict_batch_core; may be null).
+struct SingleCheck {
+  const sc_single_check* opt = nullptr;
+  int32_t* single = nullptr;
+};
+
 // What sc_eig_ncluster_sweep decides before its rounds: which of the two sequences it groups,
 // whether the level runs as a group at all, and the route of its Diffuse.
 struct SweepPlan {

@@ -2,6 +2,7 @@
 // bookkeeping of the agglomerative clustering, centroids, fallback decisions, naive
 // clusterer; kernels in ahc.hip and fallback.hip.
 #include "ahc_tree.h"
+#include "gmm_common.h"
 #include "handle.h"
 
 // ------------------------------------------------------------------------------
@@ -92,6 +93,10 @@ extern "C" int sc_cluster_centroids(sc_handle h, const double* x, int n, int d,
 extern "C" int sc_affinity_stats(sc_handle h, double* out) {
   if (!h) return SC_ERR_INVALID;
   if (!out) return fail(h, SC_ERR_INVALID, "out is NULL");
+  return affinity_stats_impl(h, out);
+}
+// (also what a batch runs for a member of n >= 4096: single_check.hip)
+int affinity_stats_impl(sc_handle h, double* out) {
   if (!h->have_affinity) return fail(h, SC_ERR_INVALID, "no affinity resident");
   SC_HIP(h, hipSetDevice(h->device));
   const int n = h->n;
@@ -115,6 +120,9 @@ extern "C" int sc_affinity_gmm_bic(sc_handle h, int diagonal_offset, double* bic
                                    double* bic2) {
   if (!h) return SC_ERR_INVALID;
   if (!bic1 || !bic2) return fail(h, SC_ERR_INVALID, "NULL output");
+  return affinity_gmm_bic_impl(h, diagonal_offset, bic1, bic2);
+}
+int affinity_gmm_bic_impl(sc_handle h, int diagonal_offset, double* bic1, double* bic2) {
   if (!h->have_affinity) return fail(h, SC_ERR_INVALID, "no affinity resident");
   const int n = h->n;
   if (diagonal_offset < 0 || diagonal_offset >= n - 1)
@@ -131,7 +139,6 @@ extern "C" int sc_affinity_gmm_bic(sc_handle h, int diagonal_offset, double* bic
   const int ld = h->ldn;
   const double m = (double)(n - diagonal_offset);
   const double count = m * (m + 1.0) / 2.0;
-  const double reg = 1e-6, tiny = 10.0 * 2.220446049250313e-16;
   double sums[8];
   auto pass = [&](int components, int mode, const double* params) -> int {
     SC_HIP(h, hipMemcpyAsync(params_d, params, 6 * sizeof(double), hipMemcpyHostToDevice, s));
@@ -141,19 +148,9 @@ extern "C" int sc_affinity_gmm_bic(sc_handle h, int diagonal_offset, double* bic
     SC_HIP(h, hipStreamSynchronize(s));
     return SC_OK;
   };
-  // M-step of sklearn's _estimate_gaussian_parameters from the pass sums
+  // M-step of sklearn's _estimate_gaussian_parameters from the pass sums (gmm_common.h)
   auto m_step = [&](int components, double* params) {
-    double wsum = 0.0;
-    for (int c = 0; c < components; ++c) {
-      const double nk = sums[3 * c] + tiny;
-      const double mu = sums[3 * c + 1] / nk;
-      const double var = (sums[3 * c + 2] - 2.0 * mu * sums[3 * c + 1] + mu * mu * sums[3 * c]) / nk;
-      params[3 * c] = nk / count;
-      params[3 * c + 1] = mu;
-      params[3 * c + 2] = var + reg;
-      wsum += params[3 * c];
-    }
-    for (int c = 0; c < components; ++c) params[3 * c] /= wsum;
+    gmm_m_step(sums, components, count, params);
   };
   auto fit = [&](int components, double* bic) -> int {
     double params[6] = {1.0, 0.0, 1.0, 0.0, 0.0, 1.0};

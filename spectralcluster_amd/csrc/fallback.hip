@@ -10,6 +10,7 @@
 //     affinity (fallback_clusterer.py:154-173, the AffinityGmmBic condition).
 #include <hip/hip_runtime.h>
 
+#include "gmm_common.h"
 #include "sc_internal.h"
 
 namespace sc {
@@ -97,11 +98,7 @@ __global__ __launch_bounds__(256) void k_affinity_stats_a(const double* __restri
   const int row = blockIdx.x;
   const double inf = __builtin_huge_val();
   double mn = inf, sum = 0.0;
-  for (int j = threadIdx.x; j < n; j += 256) {
-    const double v = a[(size_t)row * ld + j];
-    mn = v < mn ? v : mn;   // NaN never wins: np.min would return NaN; affinities are finite
-    sum += v;
-  }
+  for (int j = threadIdx.x; j < n; j += 256) stats_entry(a[(size_t)row * ld + j], mn, sum);
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
     const double other = __shfl_xor(mn, o);
@@ -126,10 +123,7 @@ __global__ __launch_bounds__(256) void k_affinity_stats_b(const double* __restri
   const int row = blockIdx.x;
   const double mu = *mean;
   double acc = 0.0;
-  for (int j = threadIdx.x; j < n; j += 256) {
-    const double dv = a[(size_t)row * ld + j] - mu;
-    acc += dv * dv;
-  }
+  for (int j = threadIdx.x; j < n; j += 256) stats_dev_entry(a[(size_t)row * ld + j], mu, acc);
   acc = block_sum_256(acc, s_red);
   if (threadIdx.x == 0) partial[(size_t)row * 4 + 3] = acc;
 }
@@ -166,43 +160,10 @@ __global__ __launch_bounds__(256) void k_gmm_pass(const double* __restrict__ a, 
                                                   double* __restrict__ partial) {
   __shared__ double s_red[4];
   const int row = blockIdx.x;
-  const double w0 = params[0], mu0 = params[1], v0 = params[2];
-  const double w1 = params[3], mu1 = params[4], v1 = params[5];
-  const double kLog2Pi = 1.8378770664093453;
-  const double lw0 = log(w0) - 0.5 * (kLog2Pi + log(v0));
-  const double lw1 = components > 1 ? log(w1) - 0.5 * (kLog2Pi + log(v1)) : 0.0;
+  const GmmCoef coef = gmm_coef(params, components);
   double acc[7] = {0, 0, 0, 0, 0, 0, 0};
-  for (int j = row + offset + threadIdx.x; j < n; j += 256) {
-    const double y = a[(size_t)row * ld + j];
-    double r0 = 1.0, r1 = 0.0, extra;
-    if (mode == 0) {
-      const double d0 = (y - mu0) * (y - mu0), d1 = (y - mu1) * (y - mu1);
-      if (d1 < d0) {  // ties go to the first centre (argmin)
-        r0 = 0.0;
-        r1 = 1.0;
-      }
-      extra = d1 < d0 ? d1 : d0;
-    } else {
-      const double l0 = lw0 - 0.5 * (y - mu0) * (y - mu0) / v0;
-      if (components > 1) {
-        const double l1 = lw1 - 0.5 * (y - mu1) * (y - mu1) / v1;
-        const double mx = l0 > l1 ? l0 : l1;
-        const double lse = mx + log(exp(l0 - mx) + exp(l1 - mx));
-        r0 = exp(l0 - lse);
-        r1 = exp(l1 - lse);
-        extra = lse;
-      } else {
-        extra = l0;
-      }
-    }
-    acc[0] += r0;
-    acc[1] += r0 * y;
-    acc[2] += r0 * y * y;
-    acc[3] += r1;
-    acc[4] += r1 * y;
-    acc[5] += r1 * y * y;
-    acc[6] += extra;
-  }
+  for (int j = row + offset + threadIdx.x; j < n; j += 256)
+    gmm_entry(a[(size_t)row * ld + j], components, mode, coef, acc);
 #pragma unroll
   for (int q = 0; q < 7; ++q) {
     const double v = block_sum_256(acc[q], s_red);
@@ -223,11 +184,8 @@ __global__ __launch_bounds__(256) void k_gmm_range(const double* __restrict__ a,
   const int row = blockIdx.x;
   const double inf = __builtin_huge_val();
   double mn = inf, mx = -inf;
-  for (int j = row + offset + threadIdx.x; j < n; j += 256) {
-    const double y = a[(size_t)row * ld + j];
-    mn = y < mn ? y : mn;
-    mx = y > mx ? y : mx;
-  }
+  for (int j = row + offset + threadIdx.x; j < n; j += 256)
+    gmm_range_entry(a[(size_t)row * ld + j], mn, mx);
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
     const double a0 = __shfl_xor(mn, o), a1 = __shfl_xor(mx, o);

@@ -91,6 +91,11 @@ struct sc_handle_s {
   void* h_reduce = nullptr;
   size_t h_reduce_bytes = 0;
   DevBuf fb_part, fb_small, fb_x, fb_cent, fb_int;      // fallback decisions scratch
+  // the single-cluster test of a batch (single_check.hip): slots and row-block partials of the
+  // chain form, records of the short form, the matrices of sc_batch_single_check, and the pinned
+  // twin of the slots / records
+  DevBuf sck_slots, sck_part, sck_rec, sck_mats;
+  void* h_sck = nullptr;
   // k-means workspace
   DevBuf kXc, kxsq, kclosest, kcand, kenorm, krnd, kcent, klab32, klab64, kinfo, kchain;
   DevBuf kbig, kbigw;     // more than kMaxVectors clusters: per-cluster arrays of k_kmeans<true>
@@ -507,5 +512,28 @@ int constraint_propagation_group(sc_handle lead, hipStream_t s, const CpGroupMem
 int predict_batch_constrained_impl(sc_handle h, const sc_array* xs, const double* const* bands,
                                    const int* ns, int d, int count, const sc_config* cfg,
                                    int64_t* const* labels, sc_diag* diags, int group);
+
+// ---- the single-cluster test (callers_api.hip: the single call's; single_check.hip: a batch's)
+// the bodies of sc_affinity_stats / sc_affinity_gmm_bic on the affinity resident in h
+int affinity_stats_impl(sc_handle h, double* out);
+int affinity_gmm_bic_impl(sc_handle h, int diagonal_offset, double* bic1, double* bic2);
+struct SingleMember {
+  const double* a;  // device memory, n x ld
+  int n, ld;
+};
+int validate_single_check(sc_handle h, const sc_single_check* opt);
+// AffinityGmmBic needs diagonal_offset < n - 1: sc_affinity_gmm_bic's message with the index
+int check_single_offset(sc_handle h, const sc_single_check* opt, int n, int index);
+// The decision of `count` members on stream `s` (synchronised on return): values (may be NULL):
+// 8 doubles per member {min, neighbour min, mean, std, bic1, bic2, lloyd steps, em steps}; single:
+// the verdicts.  _wave: members of n <= kDenseMax, kScShortMax per launch; _group: up to kGroupMax
+// members of kDenseMax < n < kScChainMaxN; _resident: the affinity resident in h, any n, through
+// the single call's kernels.
+int single_check_wave(sc_handle lead, hipStream_t s, const SingleMember* ms, int count,
+                      const sc_single_check* opt, double* values, int32_t* single);
+int single_check_group(sc_handle lead, hipStream_t s, const SingleMember* ms, int count,
+                       const sc_single_check* opt, double* values, int32_t* single);
+int single_check_resident(sc_handle h, const sc_single_check* opt, double* values,
+                          int32_t* single);
 
 #endif  // SPECTRALCLUSTER_AMD_HANDLE_H_

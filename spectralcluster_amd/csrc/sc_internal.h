@@ -800,6 +800,35 @@ void launch_gmm_pass(hipStream_t s, const double* a, int n, int ld, int offset, 
 void launch_gmm_range(hipStream_t s, const double* a, int n, int ld, int offset,
                       double* partial, double* out);
 
+// ---- the single-cluster test of a group or wave of a batch (single_check.hip) ---------------
+// One task of one member: the matrix, the diagonal offset of the mixture's entries, and (chain
+// form) which of the member's three tasks the slot runs (gmm_common.h: ScTask).
+struct ScItem {
+  const double* a;
+  int n, ld, offset, task;
+};
+struct ScSlot;  // gmm_common.h
+constexpr int kScShortMax = 64;   // members per launch of the short form (n <= kDenseMax)
+constexpr size_t kScShortLds = (size_t)kDenseMax * (kDenseMax + 1) / 2 * sizeof(double);
+constexpr int kScChainMaxN = 4096;  // chain form: kDenseMax < n < this (256 row blocks at most)
+constexpr int kScRowsPerBlock = 16;
+constexpr int kScChunk = 8;  // launches of the chain form between two looks at the slots
+struct ScShortArgs {
+  ScItem it[kScShortMax];
+  double* rec;  // 10 doubles per member
+  int gmm, condition;
+  double threshold;
+};
+constexpr int kScChainSlots = 3 * 16;  // three tasks of each of up to kGroupMax members
+struct ScChainArgs {
+  ScItem it[kScChainSlots];
+  ScSlot* slots;    // 2 x nslots
+  double* partial;  // 2 x nslots x gmax x 8
+  int gmax, nslots;
+};
+void launch_single_short(hipStream_t s, const ScShortArgs& a, int count, size_t lds_bytes);
+void launch_single_chain(hipStream_t s, const ScChainArgs& a, int t0, int passes);
+
 // ---- k-means -------------------------------------------------------------------
 struct KmeansWorkspace {
   double* Xc = nullptr;       // kMaxVectors x n centred copy (column-major)

@@ -504,8 +504,11 @@ class MultiStageStreamPool:
             fallback_clusterer.FallbackClustererType.Agglomerative)
 
   def _main_is_batchable(self) -> bool:
-    """predict_batch's conditions; spectral_min_embeddings (= L) is met by the U1 centroids."""
-    if not self.main._library_batch_covers(min_embeddings_met=self.L <= self.U1):
+    """predict_batch's conditions; spectral_min_embeddings (= L) is met by the U1 centroids, and
+    a min_clusters = 1 main clusterer is covered when its single-cluster test reads the affinity
+    (predict_device_batch then carries the test inside the grouped call)."""
+    if not self.main._library_batch_covers(min_embeddings_met=self.L <= self.U1,
+                                           single_check_covered=True):
       return False
     try:
       _lib.kmeans_metric_code(self.main.custom_dist)

@@ -85,6 +85,9 @@ class SpectralClusterer:
     self.last_diag: typing.Optional[_lib.ScDiag] = None
     # one route code per utterance of the last predict_batch (None before the first)
     self.last_batch_routes: typing.Optional[typing.List[int]] = None
+    # after a min_clusters = 1 batch that ran as ONE sc_predict_batch_single call: per utterance,
+    # did the single-cluster test find one cluster?  None after any other batch call
+    self.last_batch_single: typing.Optional[typing.List[bool]] = None
     # what each utterance of the last size-reducing predict_batch was (`_lib.BATCH_KIND_*`)
     self.last_batch_reduced: typing.Optional[typing.List[int]] = None
     # not in the reference: restart cycles block Lanczos may spend before the dense
@@ -470,10 +473,44 @@ class SpectralClusterer:
     utterance of one row.  An utterance with a zero or non-finite row raises a ValueError that
     names its index.  Everything else -- the `Naive` fallback, `min_clusters=1`, constraints,
     AutoTune, `group=1`, `streams` -- stays the per-utterance loop (routes all 0).
+
+    `min_clusters=1` (the streaming regime: the clusterer may say "one speaker"): the batch is
+    ONE `sc_predict_batch_single` call when `fallback_options.single_cluster_condition` is one of
+    the four that read the affinity (AffinityGmmBic, AllAffinity, NeighborAffinity, AffinityStd),
+    the clusterer is otherwise one the library batch covers, the batch is the grouped form
+    (`group` not 1, no `streams`), unconstrained, and k-means is the cosine one.  The
+    single-cluster test of every utterance runs on the device inside the call, group by group and
+    wave by wave, before the utterance's eigensolver.  Results are predict()'s:
+    `np.array([0] * n)` for an utterance of one cluster, int64 labels otherwise;
+    `last_batch_single` lists the verdicts (None after a call that did not take this path) and
+    `last_batch_routes` the route each utterance's affinity took (0, 1 or 2).  With
+    AffinityGmmBic an utterance of `single_cluster_affinity_diagonal_offset >= n - 1` raises
+    predict()'s ValueError, with the utterance's index, before anything is launched.  These keep
+    the per-utterance loop (routes all 0) with `min_clusters=1`: the `FallbackClusterer` condition
+    (it clusters the embeddings, not the affinity), constrained batches, AutoTune batches, and
+    batches with `max_spectral_size` / `spectral_min_embeddings`.
     """
+    self.last_batch_single = None
     if autotune_from_entry_state and self.autotune is not None:
       return self._predict_batch_entry_state(utterances, constraint_matrices, streams, group)
     library_batch = self._library_batch_covers()
+    # min_clusters = 1 with a condition that reads the affinity: the test travels inside ONE
+    # sc_predict_batch_single call -- the grouped form, unconstrained, cosine k-means
+    single_check = None
+    if (not library_batch and self.min_clusters == 1 and
+        (constraint_matrices is None or self.constraint_options is None) and
+        streams is None and (group is None or int(group) > 1) and
+        self._library_batch_covers(single_check_covered=True)):
+      try:
+        if _lib.kmeans_metric_code(self.custom_dist) == _lib.KMEANS_METRICS["cosine"]:
+          single_check = self._single_check_struct()
+      except (ValueError, _lib.UnsupportedOnDeviceError):
+        pass  # (predict() raises what it raises today)
+      if single_check is not None:
+        if constraint_matrices is not None and len(constraint_matrices) != len(utterances):
+          raise ValueError("constraint_matrices must be as long as the batch")
+        library_batch = True
+        constraint_matrices = None
     banded = None  # the ConstraintMatrix (or None) of every utterance of a constrained batch
     if constraint_matrices is not None:
       if len(constraint_matrices) != len(utterances):
@@ -537,7 +574,15 @@ class SpectralClusterer:
       handle.check(handle.lib.sc_clear_constraint(handle.raw))  # a batch carries none
       lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
       diags = (_lib.ScDiag * count)()
-      if banded is not None:
+      single = (ctypes.c_int32 * count)()
+      if single_check is not None:
+        # (predict()'s ValueError, before anything is launched; the library checks it as well)
+        self._check_single_offsets(single_check, [src.shape[0] for src in sources])
+        handle.check(handle.lib.sc_predict_batch_single(
+            handle.raw, (_lib.ScArray * count)(*[src.array for src in sources]), count,
+            self.build_config(), ctypes.byref(single_check), lp, diags, int(group), single),
+            TypeError)
+      elif banded is not None:
         arrays = (_lib.ScArray * count)(*[src.array for src in sources])
         bp = (ctypes.POINTER(ctypes.c_double) * count)(
             *[None if b is None else _lib.as_double_p(b) for b in bands])
@@ -564,6 +609,11 @@ class SpectralClusterer:
       for src in sources:
         src.release()
     self._batch_report(handle, diags, count)
+    if single_check is not None:
+      self.last_batch_single = [bool(v) for v in single]
+      # predict()'s result for a single-cluster utterance: np.array([0] * n)
+      labels = [np.array([0] * l.shape[0]) if one else l
+                for l, one in zip(labels, self.last_batch_single)]
     return labels
 
   def _predict_batch_entry_state(self, utterances: typing.Sequence,
@@ -672,14 +722,49 @@ class SpectralClusterer:
     self.last_diag = diags[count - 1]
     return labels
 
-  def _library_batch_covers(self, min_embeddings_met: bool = False) -> bool:
+  def _single_check_struct(self) -> typing.Optional[_lib.ScSingleCheck]:
+    """The `sc_single_check` of this clusterer's single-cluster test, or None when the condition
+    does not read the affinity (FallbackClusterer clusters the embeddings)."""
+    options = self.fallback_options
+    codes = {
+        fallback_clusterer.SingleClusterCondition.AffinityGmmBic: _lib.SC_SINGLE_GMM_BIC,
+        fallback_clusterer.SingleClusterCondition.AllAffinity: _lib.SC_SINGLE_ALL_AFFINITY,
+        fallback_clusterer.SingleClusterCondition.NeighborAffinity:
+            _lib.SC_SINGLE_NEIGHBOR_AFFINITY,
+        fallback_clusterer.SingleClusterCondition.AffinityStd: _lib.SC_SINGLE_AFFINITY_STD,
+    }
+    code = codes.get(options.single_cluster_condition)
+    if code is None:
+      return None
+    return _lib.ScSingleCheck(code, int(options.single_cluster_affinity_diagonal_offset),
+                              float(options.single_cluster_affinity_threshold))
+
+  @staticmethod
+  def _check_single_offsets(single_check: _lib.ScSingleCheck, rows: typing.Sequence[int]) -> None:
+    """AffinityGmmBic needs diagonal_offset < n - 1 for every utterance: the ValueError of
+    `sc_affinity_gmm_bic` (what predict() raises), with the utterance's index."""
+    if single_check.condition != _lib.SC_SINGLE_GMM_BIC:
+      return
+    offset = single_check.diagonal_offset
+    for i, n in enumerate(rows):
+      if offset < 0 or offset >= n - 1:
+        raise ValueError(
+            "single_cluster_affinity_diagonal_offset must be significantly smaller than "
+            "affinity matrix dimension (utterance %d)" % i)
+
+  def _library_batch_covers(self, min_embeddings_met: bool = False,
+                            single_check_covered: bool = False) -> bool:
     """Is this clusterer one whose predict() the library batch calls reproduce?  (What is not:
     AutoTune, size reduction, the fallback decisions, user-supplied functions -- those go
     through predict().)  `min_embeddings_met`: the caller knows every utterance to hold at
-    least `fallback_options.spectral_min_embeddings` rows (the centroids of a stream pool)."""
+    least `fallback_options.spectral_min_embeddings` rows (the centroids of a stream pool).
+    `single_check_covered`: the caller makes the `sc_predict_batch_single` call, which carries
+    the single-cluster test of `min_clusters == 1` -- covered when the condition is one of the
+    four that read the affinity."""
     return not (
         self.autotune is not None or self.max_spectral_size is not None or
-        self.min_clusters == 1 or
+        (self.min_clusters == 1 and
+         not (single_check_covered and self._single_check_struct() is not None)) or
         (self.fallback_options.spectral_min_embeddings > 1 and not min_embeddings_met) or
         self.affinity_function is not utils.compute_affinity_matrix or
         self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans)
@@ -811,6 +896,23 @@ class SpectralClusterer:
     handle = self._handle()
     handle.check(handle.lib.sc_clear_constraint(handle.raw))  # a batch carries none
     diags = (_lib.ScDiag * count)()
-    self._batch_arrays_call(handle, arrays, labels, diags, int(group), 1)
+    self.last_batch_single = None
+    if self.min_clusters == 1:
+      # (the caller's predicate: _library_batch_covers(single_check_covered=True))
+      single_check = self._single_check_struct()
+      if single_check is None:
+        raise ValueError("predict_device_batch: min_clusters=1 needs a single-cluster condition "
+                         "that reads the affinity")
+      self._check_single_offsets(single_check, [int(a.rows) for a in arrays])
+      lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
+      single = (ctypes.c_int32 * count)()
+      handle.check(handle.lib.sc_predict_batch_single(
+          handle.raw, (_lib.ScArray * count)(*arrays), count, self.build_config(),
+          ctypes.byref(single_check), lp, diags, max(2, int(group)), single), TypeError)
+      self.last_batch_single = [bool(v) for v in single]
+      labels = [np.array([0] * l.shape[0]) if one else l
+                for l, one in zip(labels, self.last_batch_single)]
+    else:
+      self._batch_arrays_call(handle, arrays, labels, diags, int(group), 1)
     self._batch_report(handle, diags, count)
     return labels

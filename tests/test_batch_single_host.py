@@ -1,0 +1,194 @@
+"""CPU: the min_clusters=1 batch (sc_predict_batch_single, sc_batch_single_check) is declared,
+prototyped and exported, its struct mirror has the header's layout, the predicates say when it is
+taken, and SpectralClusterer.predict_batch routes to it exactly then -- driven with a stand-in
+handle, no device."""
+
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+import spectralcluster_amd as sca
+from spectralcluster_amd import _lib
+from spectralcluster_amd import fallback_clusterer as fb
+from spectralcluster_amd import multi_stage_clusterer as ms
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ("sc_predict_batch_single", "sc_batch_single_check", "sc_single_check_layout")
+AFFINITY_CONDITIONS = ("AffinityGmmBic", "AllAffinity", "NeighborAffinity", "AffinityStd")
+
+
+def test_new_symbols_are_declared_prototyped_and_exported():
+  header = open(os.path.join(ROOT, "include", "spectralcluster_amd.h")).read()
+  declared = set(re.findall(r"^int\s+(sc_[a-z0-9_]+)\s*\(", header, flags=re.M))
+  lib = _lib.load()
+  for name in NEW_SYMBOLS:
+    assert name in declared, name
+    assert name in _lib.PROTOTYPES, name
+    assert hasattr(lib, name), name
+  assert lib.sc_abi_version() == 10  # functions and a struct were only added
+  cfg, diag = ctypes.c_int(0), ctypes.c_int(0)
+  lib.sc_struct_sizes(ctypes.byref(cfg), ctypes.byref(diag))
+  assert (cfg.value, diag.value) == (ctypes.sizeof(_lib.ScConfig), ctypes.sizeof(_lib.ScDiag))
+  # NULL handle: an error code, no crash
+  assert lib.sc_predict_batch_single(None, None, 0, None, None, None, None, 16,
+                                     None) == _lib.SC_ERR_INVALID
+  assert lib.sc_batch_single_check(None, None, None, 0, None, None, None) == _lib.SC_ERR_INVALID
+
+
+def test_single_check_mirror_has_the_headers_layout():
+  lib = _lib.load()
+  size, offsets = ctypes.c_int(0), (ctypes.c_int * 3)()
+  assert lib.sc_single_check_layout(ctypes.byref(size), offsets) == 0
+  assert size.value == ctypes.sizeof(_lib.ScSingleCheck) == 16
+  fields = [name for name, _ in _lib.ScSingleCheck._fields_]
+  assert fields == ["condition", "diagonal_offset", "threshold"]
+  assert list(offsets) == [getattr(_lib.ScSingleCheck, f).offset for f in fields] == [0, 4, 8]
+  header = open(os.path.join(ROOT, "include", "spectralcluster_amd.h")).read()
+  for name, value in (("GMM_BIC", 1), ("ALL_AFFINITY", 2), ("NEIGHBOR_AFFINITY", 3),
+                      ("AFFINITY_STD", 4)):
+    assert re.search(r"SC_SINGLE_%s\s*=\s*%d\b" % (name, value), header)
+    assert getattr(_lib, "SC_SINGLE_" + name) == value
+  # ... which are the values of SingleClusterCondition
+  for name in AFFINITY_CONDITIONS:
+    options = fb.FallbackOptions(single_cluster_condition=getattr(fb.SingleClusterCondition, name))
+    check = sca.SpectralClusterer(min_clusters=1, fallback_options=options)._single_check_struct()
+    assert check.condition == getattr(fb.SingleClusterCondition, name).value
+
+
+def test_integration_binding_lists_the_entry_points():
+  text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+  for name in NEW_SYMBOLS:
+    assert "`%s`" % name in text, name
+
+
+def clusterer_with(condition, **kwargs):
+  options = fb.FallbackOptions(
+      single_cluster_condition=getattr(fb.SingleClusterCondition, condition),
+      single_cluster_affinity_threshold=0.6, single_cluster_affinity_diagonal_offset=2)
+  return sca.SpectralClusterer(min_clusters=1, max_clusters=6, fallback_options=options, **kwargs)
+
+
+@pytest.mark.parametrize("condition", AFFINITY_CONDITIONS + ("FallbackClusterer",))
+def test_predicates_per_condition(condition):
+  c = clusterer_with(condition)
+  covered = condition != "FallbackClusterer"
+  assert not c._library_batch_covers()   # (what every other batch form asks: unchanged)
+  assert c._library_batch_covers(single_check_covered=True) == covered
+  check = c._single_check_struct()
+  if covered:
+    assert (check.condition, check.diagonal_offset, check.threshold) == (
+        getattr(fb.SingleClusterCondition, condition).value, 2, 0.6)
+  else:
+    assert check is None
+  pool = ms.MultiStageStreamPool.__new__(ms.MultiStageStreamPool)
+  pool.main, pool.L, pool.U1 = c, 1, 4
+  assert pool._main_is_batchable() == covered
+  # min_clusters = 1 does not cover what it did not cover before
+  assert not clusterer_with(condition, max_spectral_size=50)._library_batch_covers(
+      single_check_covered=True)
+  assert not clusterer_with(condition, autotune=sca.AutoTune())._library_batch_covers(
+      single_check_covered=True)
+  # and other clusterers answer as they did
+  assert sca.SpectralClusterer(min_clusters=2)._library_batch_covers(single_check_covered=True)
+  assert sca.SpectralClusterer(min_clusters=2)._library_batch_covers()
+
+
+class FakeLib:
+  """Records the call; says "single" for every utterance of fewer than 10 rows."""
+
+  def __init__(self):
+    self.calls = []
+
+  def sc_clear_constraint(self, raw):
+    return 0
+
+  def sc_predict_batch_single(self, raw, arrays, count, cfg, check, lp, diags, group, single):
+    check = ctypes.cast(check, ctypes.POINTER(_lib.ScSingleCheck)).contents
+    rows = [int(arrays[i].rows) for i in range(count)]
+    for i, n in enumerate(rows):
+      single[i] = 1 if n < 10 else 0
+      for r in range(n):
+        lp[i][r] = 0 if n < 10 else 1 + r % 2
+    self.calls.append(dict(rows=rows, group=group, condition=check.condition,
+                           offset=check.diagonal_offset, threshold=check.threshold,
+                           min_clusters=cfg.min_clusters))
+    return 0
+
+
+class FakeHandle:
+  raw = None
+
+  def __init__(self):
+    self.lib = FakeLib()
+
+  def check(self, rc, invalid_exc=ValueError):
+    assert rc == 0
+
+
+def with_fake_handle(clusterer):
+  handle = FakeHandle()
+  clusterer._handle = lambda: handle
+  clusterer.predict = lambda u, c=None: np.full(np.shape(u)[0], 7)   # (the loop's marker)
+  return handle
+
+
+def test_predict_batch_makes_one_call():
+  clusterer = clusterer_with("AllAffinity")
+  handle = with_fake_handle(clusterer)
+  batch = [np.ones((n, 4)) for n in (5, 12, 9, 200)]
+  got = clusterer.predict_batch(batch)
+  assert handle.lib.calls == [dict(rows=[5, 12, 9, 200], group=16, condition=2, offset=2,
+                                   threshold=0.6, min_clusters=1)]
+  assert clusterer.last_batch_single == [True, False, True, False]
+  for u, labels, one in zip(batch, got, clusterer.last_batch_single):
+    want = np.array([0] * u.shape[0]) if one else 1 + np.arange(u.shape[0]) % 2
+    assert labels.dtype == want.dtype and np.array_equal(labels, want)
+  # a later call that does not take the path clears the report
+  got = clusterer.predict_batch(batch, group=1)
+  assert clusterer.last_batch_single is None and len(handle.lib.calls) == 1
+  assert all((l == 7).all() for l in got) and clusterer.last_batch_routes == [0] * 4
+
+
+@pytest.mark.parametrize("how", ["fallback_condition", "constraints", "autotune", "reduced",
+                                 "streams", "group1", "euclidean"])
+def test_what_keeps_the_loop(how):
+  kwargs, call = {}, {}
+  if how == "constraints":
+    kwargs["constraint_options"] = sca.ConstraintOptions(
+        constraint_name=sca.ConstraintName.AffinityIntegration, apply_before_refinement=False,
+        integration_type=sca.IntegrationType.Max)
+    call["constraint_matrices"] = [None, None]
+  if how == "autotune":
+    kwargs["autotune"] = sca.AutoTune()
+  if how == "reduced":
+    kwargs["max_spectral_size"] = 50
+  if how == "streams":
+    call["streams"] = 2
+  if how == "group1":
+    call["group"] = 1
+  if how == "euclidean":
+    kwargs["custom_dist"] = "euclidean"
+  clusterer = clusterer_with("FallbackClusterer" if how == "fallback_condition" else "AffinityStd",
+                             **kwargs)
+  handle = with_fake_handle(clusterer)
+  got = clusterer.predict_batch([np.ones((5, 4)), np.ones((12, 4))], **call)
+  assert handle.lib.calls == []
+  assert all((l == 7).all() for l in got)
+  assert clusterer.last_batch_routes == [0, 0] and clusterer.last_batch_single is None
+
+
+def test_offset_check_names_the_utterance():
+  clusterer = clusterer_with("AffinityGmmBic")   # diagonal offset 2
+  handle = with_fake_handle(clusterer)
+  with pytest.raises(ValueError, match=r"diagonal_offset must be significantly smaller.*"
+                                       r"\(utterance 1\)"):
+    clusterer.predict_batch([np.ones((5, 4)), np.ones((3, 4)), np.ones((8, 4))])
+  assert handle.lib.calls == []
+  # the three reduction conditions do not read the offset
+  clusterer = clusterer_with("NeighborAffinity")
+  handle = with_fake_handle(clusterer)
+  clusterer.predict_batch([np.ones((5, 4)), np.ones((3, 4))])
+  assert len(handle.lib.calls) == 1
