@@ -481,7 +481,8 @@ enum {
   SC_BATCH_ROUTE_SINGLE = 0,         /* the single-call path, on the member's arena */
   SC_BATCH_ROUTE_GROUP_LANCZOS = 1,  /* lockstep block Lanczos of a group (128 < n < 4096) */
   SC_BATCH_ROUTE_GROUP_JACOBI = 2,   /* short route: one Jacobi workgroup per member (n <= 128) */
-  SC_BATCH_ROUTE_FALLBACK = 3        /* sc_predict_batch_reduced: the agglomerative fallback */
+  SC_BATCH_ROUTE_FALLBACK = 3        /* sc_predict_batch_reduced: the agglomerative fallback;
+                                        sc_predict_batch_single_fallback: found single */
 };
 int sc_last_batch_routes(sc_handle h, int32_t* routes, int count);
 
@@ -532,8 +533,10 @@ int sc_predict_batch_reduced(sc_handle h, const sc_array* xs, int count, const s
 /*
  * min_clusters = 1: the single-cluster test (fallback_clusterer.py:127-187) inside the batch.
  * `condition` is one of the four conditions that read the affinity (the values of
- * SingleClusterCondition); the FallbackClusterer condition reads the embeddings and has no
- * batched form.  diagonal_offset is read by SC_SINGLE_GMM_BIC alone, threshold by the other three.
+ * SingleClusterCondition); the FallbackClusterer condition reads the embeddings, not the
+ * affinity: its batched form is sc_predict_batch_single_fallback below, which takes no
+ * sc_single_check.  diagonal_offset is read by SC_SINGLE_GMM_BIC alone, threshold by the other
+ * three.
  */
 enum {
   SC_SINGLE_GMM_BIC = 1,           /* bic1 < bic2 of sc_affinity_gmm_bic */
@@ -578,6 +581,43 @@ int sc_predict_batch_single(sc_handle h, const sc_array* xs, int count, const sc
  * (diagonal_offset as above): values and single are untouched then. */
 int sc_batch_single_check(sc_handle h, const double* const* affinities, const int* ns, int count,
                           const sc_single_check* check, double* values, int32_t* single);
+
+/*
+ * min_clusters = 1 with the FallbackClusterer condition and the agglomerative fallback type
+ * (fallback_clusterer.py:108-124, 174-176; what MultiStageClusterer's constructor sets): an
+ * utterance holds one cluster when average-linkage cosine AHC, cut at distance_threshold, leaves
+ * one -- when no merge height is >= distance_threshold.
+ *
+ * sc_batch_fallback_check: the decision alone, through exactly the kernels the batch runs.  The
+ * arrays are sc_batch_ahc's (any dtype, host or device memory, the same cols, at least 2 rows
+ * each), taken in its waves (sc_set_reduce_wave_bytes) with its distances (unit rows, the grouped
+ * fp64 product, 1 - clip), then the VERDICT forms of its two linkage kernels: a wavefront per
+ * member of up to 128 rows, a workgroup per longer member; no merge list is written, a wave
+ * downloads one record per member.  single[i] = 1: one cluster, heights[i] the largest merge
+ * height (sc_ahc's, bit for bit).  single[i] = 0: heights[i] is the first merge height found >=
+ * distance_threshold, where the member's work ends.  A member's record does not depend on what
+ * else is in the call.  A member of 4096 rows or more, or one that alone exceeds the wave budget,
+ * runs sc_ahc's own path (heights[i] is then the largest height either way).  Every argument is
+ * checked before the first launch; a member with a zero or non-finite row fails the call with
+ * SC_ERR_INVALID and a message that names its index.  heights and single are written only when
+ * the call succeeds.
+ */
+int sc_batch_fallback_check(sc_handle h, const sc_array* xs, int count,
+                            double distance_threshold, double* heights, int32_t* single);
+/* sc_predict_batch_arrays in its grouped form (group >= 2, else SC_ERR_INVALID) for such a
+ * clusterer.  The verdicts of the WHOLE batch come first, as sc_batch_fallback_check computes
+ * them; then ONE grouped batch clusters the utterances of several clusters.  An utterance found
+ * single never enters the spectral path: labels of zeros, a zeroed diag, single[i] = 1 (0
+ * otherwise; single may be NULL), route SC_BATCH_ROUTE_FALLBACK; the others report the route of
+ * the grouped batch.  An utterance is ingested once: the widened fp64 rows of a wave stay on the
+ * device and the grouped batch reads them there (ingest is exact), while the rows kept add up to
+ * at most half a wave's budget; beyond that the grouped batch ingests the caller's array again.
+ * An utterance of fewer than 2 rows fails the call with SC_ERR_INVALID before anything is
+ * launched (sc_ahc's message and the utterance's index). */
+int sc_predict_batch_single_fallback(sc_handle h, const sc_array* xs, int count,
+                                     const sc_config* cfg, double distance_threshold,
+                                     int64_t* const* labels, sc_diag* diags, int group,
+                                     int32_t* single);
 
 /*
  * Stream pool: up to `capacity` streaming sessions (multi_stage_clusterer.py:128-180) whose

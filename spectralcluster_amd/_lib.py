@@ -331,6 +331,15 @@ PROTOTYPES = {
     "sc_batch_single_check": (ctypes.c_int, [_handle_t, ctypes.POINTER(_c_double_p), _c_int_p,
                                              ctypes.c_int, ctypes.POINTER(ScSingleCheck),
                                              _c_double_p, ctypes.POINTER(ctypes.c_int32)]),
+    "sc_batch_fallback_check": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray), ctypes.c_int,
+                                               ctypes.c_double, _c_double_p,
+                                               ctypes.POINTER(ctypes.c_int32)]),
+    "sc_predict_batch_single_fallback": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),
+                                                        ctypes.c_int, ctypes.POINTER(ScConfig),
+                                                        ctypes.c_double,
+                                                        ctypes.POINTER(_c_int64_p),
+                                                        ctypes.POINTER(ScDiag), ctypes.c_int,
+                                                        ctypes.POINTER(ctypes.c_int32)]),
     "sc_pool_create": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, ctypes.POINTER(_handle_t)]),
     "sc_pool_destroy": (ctypes.c_int, [_handle_t]),

@@ -19,7 +19,11 @@
 //     first two as k_pool_linkage_lds: the distance matrix in LDS, a wavefront per session;
 //   * a batch of utterances of any size (batch_reduce.hip: sc_batch_ahc, sc_predict_batch_reduced)
 //     runs them from a table of per-member descriptors: k_batch_cosine_distance,
-//     k_ahc_nn_chain_batch (a workgroup per member), k_batch_linkage_lds, k_batch_centroids.
+//     k_ahc_nn_chain_batch (a workgroup per member), k_batch_linkage_lds, k_batch_centroids;
+//   * the FallbackClusterer single-cluster test of a batch (sc_batch_fallback_check) asks only
+//     whether a cut at the threshold leaves one cluster: the verdict forms of the two linkage
+//     kernels, k_ahc_nn_chain_verdict and k_batch_linkage_lds_verdict, write a two-double record
+//     per member instead of a merge list.
 #include <hip/hip_runtime.h>
 
 #include "dpp.h"
@@ -71,13 +75,21 @@ __device__ __forceinline__ void block_argmin(double& v, int& idx, double* s_val,
 // method 1: complete linkage (max), 2: average linkage (size-weighted mean).
 // Z[k] = (x, y, height, size) in merge order, x < y slot indices (slot y keeps the cluster).
 // The whole chain of one problem on the calling workgroup (kAhcThreads threads); n >= 2.
+// kVerdict: "does a cut at `threshold` leave one cluster?" -- no merge list; Z is the problem's
+// two-double record {height, verdict}.  One cluster means no merge height >= threshold (the cut
+// counts 1 + #{heights >= threshold}, whatever order the chain emits the merges in): the first
+// such height settles it and ends the chain (record {that height, 0}); a chain that ends without
+// one leaves {the largest height, 1}.  The distances, the scans and the updates are the same
+// expressions, so the heights are the merge list's, bit for bit.
+template <bool kVerdict>
 __device__ __forceinline__ void ahc_nn_chain_body(double* __restrict__ D, int ld, int n,
                                                   int method, int* __restrict__ size,
                                                   int* __restrict__ chain,
                                                   double* __restrict__ Z, double* s_val,
-                                                  int* s_idx) {
+                                                  int* s_idx, double threshold = 0.0) {
   const int tid = threadIdx.x;
   const double inf = __builtin_huge_val();
+  double top = -inf;  // (kVerdict) the largest height so far
   for (int i = tid; i < n; i += kAhcThreads) size[i] = 1;
   __syncthreads();
   int chain_len = 0;
@@ -130,11 +142,23 @@ __device__ __forceinline__ void ahc_nn_chain_body(double* __restrict__ D, int ld
     }
     const int nx = size[x], ny = size[y];
     __syncthreads();  // every thread has read the sizes
+    if constexpr (kVerdict) {
+      if (cur >= threshold) {  // (cur is the same value in every thread: all of them leave)
+        if (tid == 0) {
+          Z[0] = cur;
+          Z[1] = 0.0;
+        }
+        return;
+      }
+      top = cur > top ? cur : top;
+    }
     if (tid == 0) {
-      Z[(size_t)k * 4 + 0] = (double)x;
-      Z[(size_t)k * 4 + 1] = (double)y;
-      Z[(size_t)k * 4 + 2] = cur;
-      Z[(size_t)k * 4 + 3] = (double)(nx + ny);
+      if constexpr (!kVerdict) {
+        Z[(size_t)k * 4 + 0] = (double)x;
+        Z[(size_t)k * 4 + 1] = (double)y;
+        Z[(size_t)k * 4 + 2] = cur;
+        Z[(size_t)k * 4 + 3] = (double)(nx + ny);
+      }
       size[x] = 0;
       size[y] = nx + ny;
     }
@@ -151,6 +175,12 @@ __device__ __forceinline__ void ahc_nn_chain_body(double* __restrict__ D, int ld
     }
     __syncthreads();
   }
+  if constexpr (kVerdict) {
+    if (tid == 0) {
+      Z[0] = top;
+      Z[1] = 1.0;
+    }
+  }
 }
 
 __global__ __launch_bounds__(kAhcThreads) void k_ahc_nn_chain(double* __restrict__ D, int ld,
@@ -164,7 +194,7 @@ __global__ __launch_bounds__(kAhcThreads) void k_ahc_nn_chain(double* __restrict
   // a NaN row of D leaves the last scans without a neighbour (index -1): the body needs finite
   // distances, the host reports the word
   if (bad != nullptr && *bad != 0) return;
-  ahc_nn_chain_body(D, ld, n, method, size, chain, Z, s_val, s_idx);
+  ahc_nn_chain_body<false>(D, ld, n, method, size, chain, Z, s_val, s_idx);
 }
 
 // ---- a batch of problems of any size (sc_batch_ahc): a table of descriptors in device memory,
@@ -191,7 +221,17 @@ __global__ __launch_bounds__(kAhcThreads) void k_ahc_nn_chain_batch(
   __shared__ int s_idx[kAhcThreads / 64];
   const AhcBatchItem& it = table[first + blockIdx.x];
   if (it.n < 2 || *it.bad != 0) return;  // before D is touched
-  ahc_nn_chain_body(it.D, it.ld, it.n, it.method, it.size, it.chain, it.Z, s_val, s_idx);
+  ahc_nn_chain_body<false>(it.D, it.ld, it.n, it.method, it.size, it.chain, it.Z, s_val, s_idx);
+}
+
+// The verdict form (average linkage): it.Z is the member's record {height, verdict}
+__global__ __launch_bounds__(kAhcThreads) void k_ahc_nn_chain_verdict(
+    const AhcBatchItem* __restrict__ table, int first, double threshold) {
+  __shared__ double s_val[kAhcThreads / 64];
+  __shared__ int s_idx[kAhcThreads / 64];
+  const AhcBatchItem& it = table[first + blockIdx.x];
+  if (it.n < 2 || *it.bad != 0) return;  // before D is touched
+  ahc_nn_chain_body<true>(it.D, it.ld, it.n, 2, it.size, it.chain, it.Z, s_val, s_idx, threshold);
 }
 
 // ---- stream pool: the same three steps for every session of a step in one launch each ----
@@ -220,7 +260,7 @@ __global__ __launch_bounds__(kAhcThreads) void k_ahc_nn_chain_pool(const PoolSla
   const int b = blockIdx.x;
   const int n = rows[b];
   if (n < 2) return;
-  ahc_nn_chain_body(p.D + (size_t)slots[b] * p.stride_d, p.ldd, n, method,
+  ahc_nn_chain_body<false>(p.D + (size_t)slots[b] * p.stride_d, p.ldd, n, method,
                     p.size + (size_t)b * p.stride_n, p.chain + (size_t)b * p.stride_n,
                     p.Z + (size_t)b * p.stride_z, s_val, s_idx);
 }
@@ -263,10 +303,15 @@ __device__ __forceinline__ void wave_argmin(double& v, int& idx) {
 // The whole linkage of one problem of 2 <= n <= kPoolLdsLinkageMax rows on the calling wavefront
 // (a 64-thread workgroup): c the GEMM's cosines (pitch ldc), Z the merge list, lds_d the
 // workgroup's dynamic LDS (pool_linkage_lds_bytes(n) at least).  A problem lays its matrix out
-// with its own odd pitch n | 1.
+// with its own odd pitch n | 1.  kVerdict: as ahc_nn_chain_body<true> -- Z is the two-double
+// record {height, verdict}, lane 0 writes it (vector stores), the first height >= threshold
+// ends the work.
+template <bool kVerdict>
 __device__ __forceinline__ void linkage_lds_body(const double* __restrict__ c, int ldc, int n,
-                                                 double* __restrict__ Z, double* lds_d) {
+                                                 double* __restrict__ Z, double* lds_d,
+                                                 double threshold = 0.0) {
   const int lane = threadIdx.x;
+  double top = -__builtin_huge_val();  // (kVerdict) the largest height so far
   const int pitch = n | 1;  // odd: a column walk touches every bank pair once
   double* D = lds_d;                                   // n x pitch
   int* size = reinterpret_cast<int*>(D + n * pitch);   // n
@@ -338,11 +383,23 @@ __device__ __forceinline__ void linkage_lds_body(const double* __restrict__ c, i
     }
     const int nx = size[x], ny = size[y];
     __syncthreads();  // every lane has read the sizes
+    if constexpr (kVerdict) {
+      if (cur >= threshold) {  // (cur is the same value in every lane: the wavefront leaves)
+        if (lane == 0) {
+          Z[0] = cur;
+          Z[1] = 0.0;
+        }
+        return;
+      }
+      top = cur > top ? cur : top;
+    }
     if (lane == 0) {
-      Z[(size_t)k * 4 + 0] = (double)x;
-      Z[(size_t)k * 4 + 1] = (double)y;
-      Z[(size_t)k * 4 + 2] = cur;
-      Z[(size_t)k * 4 + 3] = (double)(nx + ny);
+      if constexpr (!kVerdict) {
+        Z[(size_t)k * 4 + 0] = (double)x;
+        Z[(size_t)k * 4 + 1] = (double)y;
+        Z[(size_t)k * 4 + 2] = cur;
+        Z[(size_t)k * 4 + 3] = (double)(nx + ny);
+      }
       size[x] = 0;
       size[y] = nx + ny;
     }
@@ -360,6 +417,12 @@ __device__ __forceinline__ void linkage_lds_body(const double* __restrict__ c, i
     }
     __syncthreads();
   }
+  if constexpr (kVerdict) {
+    if (lane == 0) {
+      Z[0] = top;
+      Z[1] = 1.0;
+    }
+  }
 }
 
 // Workgroup blockIdx.x works on position first + blockIdx.x of the launch's lists.  The dynamic
@@ -372,7 +435,7 @@ __global__ __launch_bounds__(64) void k_pool_linkage_lds(const PoolSlabs p,
   const int b = first + blockIdx.x;
   const int n = rows[b];
   if (n < 2 || n > kPoolLdsLinkageMax) return;
-  linkage_lds_body(p.D + (size_t)slots[b] * p.stride_d, p.ldd, n, p.Z + (size_t)b * p.stride_z,
+  linkage_lds_body<false>(p.D + (size_t)slots[b] * p.stride_d, p.ldd, n, p.Z + (size_t)b * p.stride_z,
                    lds_d);
 }
 
@@ -383,7 +446,17 @@ __global__ __launch_bounds__(64) void k_batch_linkage_lds(const AhcBatchItem* __
   const AhcBatchItem& it = table[first + blockIdx.x];
   const int n = it.n;
   if (n < 2 || n > kPoolLdsLinkageMax || *it.bad != 0) return;
-  linkage_lds_body(it.D, it.ld, n, it.Z, lds_d);
+  linkage_lds_body<false>(it.D, it.ld, n, it.Z, lds_d);
+}
+
+// ... and its verdict form: it.Z is the member's record {height, verdict}
+__global__ __launch_bounds__(64) void k_batch_linkage_lds_verdict(
+    const AhcBatchItem* __restrict__ table, int first, double threshold) {
+  extern __shared__ __attribute__((aligned(16))) double lds_d[];
+  const AhcBatchItem& it = table[first + blockIdx.x];
+  const int n = it.n;
+  if (n < 2 || n > kPoolLdsLinkageMax || *it.bad != 0) return;
+  linkage_lds_body<true>(it.D, it.ld, n, it.Z, lds_d, threshold);
 }
 #endif  // SC_POOL_LDS_LINKAGE_MAX > 0
 
@@ -466,6 +539,11 @@ void launch_batch_cosine_distance(hipStream_t s, const AhcBatchItem* table, int 
 void launch_batch_nn_chain(hipStream_t s, const AhcBatchItem* table, int first, int count) {
   hipLaunchKernelGGL(k_ahc_nn_chain_batch, dim3(count), dim3(kAhcThreads), 0, s, table, first);
 }
+void launch_batch_nn_chain_verdict(hipStream_t s, const AhcBatchItem* table, int first, int count,
+                                   double threshold) {
+  hipLaunchKernelGGL(k_ahc_nn_chain_verdict, dim3(count), dim3(kAhcThreads), 0, s, table, first,
+                     threshold);
+}
 void launch_batch_centroids(hipStream_t s, const AhcBatchItem* table, int first, int count,
                             int max_outputs) {
   for (int at = 0; at < count; at += kBatchGridY)
@@ -507,6 +585,13 @@ void launch_batch_linkage_lds(hipStream_t s, const AhcBatchItem* table, int firs
   hipLaunchKernelGGL(k_batch_linkage_lds, dim3(count), dim3(64),
                      pool_linkage_lds_bytes(std::min(max_rows, kPoolLdsLinkageMax)), s, table,
                      first);
+}
+void launch_batch_linkage_lds_verdict(hipStream_t s, const AhcBatchItem* table, int first,
+                                      int count, int max_rows, double threshold) {
+  SC_OPT_IN_LDS(k_batch_linkage_lds_verdict, pool_linkage_lds_bytes(kPoolLdsLinkageMax));
+  hipLaunchKernelGGL(k_batch_linkage_lds_verdict, dim3(count), dim3(64),
+                     pool_linkage_lds_bytes(std::min(max_rows, kPoolLdsLinkageMax)), s, table,
+                     first, threshold);
 }
 #endif
 void launch_pool_centroids(hipStream_t s, const PoolSlabs& p, const int* slots, const int* rows,

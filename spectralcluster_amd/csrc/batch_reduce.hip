@@ -15,6 +15,9 @@
 //   centroids   1 copy (all CSRs) + k_batch_centroids
 // whatever the members' sizes are.  A member of n >= kReduceSingleMin rows, or one that alone
 // exceeds the budget, runs sc_ahc's own path (callers_api.hip) inside the call.
+// The FallbackClusterer single-cluster test of a batch (sc_batch_fallback_check,
+// sc_predict_batch_single_fallback) runs the same waves up to the distances, then the verdict
+// forms of the linkage kernels: see VerdictMember below.
 // Kernels: ahc.hip, rowops.hip.
 #include "ahc_tree.h"
 #include "handle.h"
@@ -71,6 +74,17 @@ struct DeviceBlocks {
 
 std::string bad_rows_message(int index) {
   return "utterance " + std::to_string(index) + ": embeddings contain a zero or non-finite row";
+}
+
+// the pinned staging of a wave (the stream is idle: every wave ends drained)
+int ensure_wave_staging(sc_handle h, size_t staged) {
+  if (h->h_reduce_bytes >= staged) return SC_OK;
+  if (h->h_reduce) SC_HIP(h, hipHostFree(h->h_reduce));
+  h->h_reduce = nullptr;
+  h->h_reduce_bytes = 0;
+  SC_HIP(h, hipHostMalloc(&h->h_reduce, staged));
+  h->h_reduce_bytes = staged;
+  return SC_OK;
 }
 
 // one member on sc_ahc's path: the handle's arena, its split-K product, its chain launch
@@ -133,13 +147,7 @@ int reduce_wave(sc_handle h, const sc_array* xs, int d, const std::vector<Reduce
   const size_t back_bytes = align256(z_doubles * sizeof(double) + (size_t)count * sizeof(int));
   const size_t csr_bytes = align256(csr_ints * sizeof(int));
   const size_t staged = table_bytes + back_bytes + csr_bytes;
-  if (h->h_reduce_bytes < staged) {  // (the stream is idle: every wave ends drained)
-    if (h->h_reduce) SC_HIP(h, hipHostFree(h->h_reduce));
-    h->h_reduce = nullptr;
-    h->h_reduce_bytes = 0;
-    SC_HIP(h, hipHostMalloc(&h->h_reduce, staged));
-    h->h_reduce_bytes = staged;
-  }
+  SC_TRY(ensure_wave_staging(h, staged));
   void* block = nullptr;
   SC_HIP(h, hipMalloc(&block, staged + own));
   blocks->blocks.push_back(block);
@@ -303,6 +311,219 @@ int too_few_rows(sc_handle h, int index, int n) {
                   " sample(s) while a minimum of 2 is required by AgglomerativeClustering.");
 }
 
+// ---- the FallbackClusterer single-cluster test of a batch (sc_batch_fallback_check,
+//      sc_predict_batch_single_fallback): "does average-linkage cosine AHC, cut at the threshold,
+//      leave one cluster?" for every member, in waves as above -- ingest, normalise, grouped
+//      GEMM, then the VERDICT forms of the two linkage kernels (ahc.hip): no merge list comes
+//      back and no tree is cut, a wave downloads its records {height, verdict} and `bad` words in
+//      one copy behind one synchronisation.  A wave's widened rows are a block of their own, which
+//      may outlive the wave (the grouped batch of the survivors reads them there).
+struct VerdictMember {
+  int index = 0;  // into the caller's lists
+  int n = 0;
+  // results
+  double height = 0.0;
+  int single = 0;
+  const double* dev_rows = nullptr;  // the widened rows (pitch round_up(d, 16)) where they stayed
+
+  bool lds() const { return kPoolLdsLinkageMax > 0 && n <= kPoolLdsLinkageMax; }
+  size_t rows_bytes(int d) const { return align256((size_t)n * round_up(d, 16) * sizeof(double)); }
+  // Xn, D and (chain kernel) size + chain
+  size_t scratch_bytes(int d) const {
+    return rows_bytes(d) + align256((size_t)n * matrix_ld(n) * sizeof(double)) +
+           (lds() ? 0 : 2 * align256((size_t)n * sizeof(int)));
+  }
+  size_t wave_bytes(int d) const {
+    return rows_bytes(d) + scratch_bytes(d) + sizeof(AhcBatchItem) + 2 * sizeof(double) +
+           sizeof(int);
+  }
+};
+
+// one member on sc_ahc's path (reduce_single's): the verdict from its merge heights
+int verdict_single(sc_handle h, const sc_array& a, VerdictMember* m, double threshold) {
+  h->sweep_slot.clear();
+  SC_TRY(ingest_embeddings(h, a, true));
+  std::vector<int64_t> lab(m->n);
+  const int rc = ahc_resident(h, SC_LINKAGE_AVERAGE, 0, threshold, lab.data(), nullptr, &m->height);
+  if (rc == SC_ERR_INVALID) return fail(h, rc, "utterance " + std::to_string(m->index) + ": " + h->err);
+  SC_TRY(rc);
+  m->single = m->height >= threshold ? 0 : 1;
+  return SC_OK;
+}
+
+// One wave: the members of the chain kernel first, then those of the LDS kernel, each part
+// longest first.  `keep` (may be null): the rows' block joins it and every dev_rows is set;
+// otherwise it is freed with the wave's other buffers.  On return the stream has drained.
+int verdict_wave(sc_handle h, const sc_array* xs, int d, const std::vector<VerdictMember*>& wave,
+                 double threshold, DeviceBlocks* keep) {
+  const int count = (int)wave.size();
+  const int ldx = round_up(d, 16);
+  hipStream_t s = h->stream;
+  size_t rows_total = 0, scratch_total = 0;
+  int n_chain = 0, chain_rows = 0, lds_rows = 0;
+  for (int i = 0; i < count; ++i) {
+    const VerdictMember& m = *wave[i];
+    rows_total += m.rows_bytes(d);
+    scratch_total += m.scratch_bytes(d);
+    if (m.lds()) {
+      lds_rows = std::max(lds_rows, m.n);
+    } else {
+      n_chain = i + 1;
+      chain_rows = std::max(chain_rows, m.n);
+    }
+  }
+  // descriptors | records + bad words
+  const size_t table_bytes = align256((size_t)count * sizeof(AhcBatchItem));
+  const size_t back_doubles = 2 * (size_t)count;
+  const size_t back_bytes = align256(back_doubles * sizeof(double) + (size_t)count * sizeof(int));
+  const size_t staged = table_bytes + back_bytes;
+  SC_TRY(ensure_wave_staging(h, staged));
+  DeviceBlocks scratch;  // freed when the wave returns
+  void* rows_block = nullptr;
+  SC_HIP(h, hipMalloc(&rows_block, rows_total));
+  (keep ? keep : &scratch)->blocks.push_back(rows_block);
+  void* block = nullptr;
+  SC_HIP(h, hipMalloc(&block, staged + scratch_total));
+  scratch.blocks.push_back(block);
+  char* dev = static_cast<char*>(block);
+  char* host = static_cast<char*>(h->h_reduce);
+  AhcBatchItem* table_d = reinterpret_cast<AhcBatchItem*>(dev);
+  AhcBatchItem* table_h = reinterpret_cast<AhcBatchItem*>(host);
+  double* rec_d = reinterpret_cast<double*>(dev + table_bytes);
+  const double* rec_h = reinterpret_cast<const double*>(host + table_bytes);
+  int* bad_d = reinterpret_cast<int*>(rec_d + back_doubles);
+  const int* bad_h = reinterpret_cast<const int*>(rec_h + back_doubles);
+  char* at = dev + staged;
+  char* rows_at = static_cast<char*>(rows_block);
+  auto carve = [](char*& from, size_t bytes) {
+    void* p = from;
+    from += align256(bytes);
+    return p;
+  };
+  for (int i = 0; i < count; ++i) {
+    const VerdictMember& m = *wave[i];
+    AhcBatchItem& it = table_h[i];
+    const size_t rows = (size_t)m.n * ldx * sizeof(double);
+    memset(&it, 0, sizeof(it));
+    it.n = m.n;
+    it.ld = matrix_ld(m.n);
+    it.ldx = ldx;
+    it.d = d;
+    it.kcap = m.n;
+    it.method = SC_LINKAGE_AVERAGE;
+    it.X = static_cast<double*>(carve(rows_at, rows));
+    it.Xn = static_cast<double*>(carve(at, rows));
+    it.D = static_cast<double*>(carve(at, (size_t)m.n * it.ld * sizeof(double)));
+    if (!m.lds()) {  // (the LDS kernel keeps both in LDS)
+      it.size = static_cast<int*>(carve(at, (size_t)m.n * sizeof(int)));
+      it.chain = static_cast<int*>(carve(at, (size_t)m.n * sizeof(int)));
+    }
+    it.Z = rec_d + 2 * (size_t)i;  // the record {height, verdict}
+    it.bad = bad_d + i;
+  }
+  SC_HIP(h, hipMemcpyAsync(table_d, table_h, (size_t)count * sizeof(AhcBatchItem),
+                           hipMemcpyHostToDevice, s));
+  SC_HIP(h, hipMemsetAsync(rec_d, 0, back_doubles * sizeof(double) + (size_t)count * sizeof(int),
+                           s));
+  bool sync = false;  // (the wave synchronises before it returns)
+  for (int i = 0; i < count; ++i)
+    SC_TRY(ingest_rows_into(h, xs[wave[i]->index], const_cast<double*>(table_h[i].X), ldx, s,
+                            &sync));
+  launch_batch_normalize(s, table_d, count, std::max(chain_rows, lds_rows));
+  // sc_batch_ahc's unit rows and symmetric product (whole K per tile), 16 members per launch
+  for (int base = 0; base < count; base += kGroupMax) {
+    GemmGroupItem items[kGroupMax];
+    const int cnt = std::min(kGroupMax, count - base);
+    for (int z = 0; z < cnt; ++z) {
+      const AhcBatchItem& it = table_h[base + z];
+      items[z].A = it.Xn;
+      items[z].lda = ldx;
+      items[z].C = it.D;
+      items[z].ldc = it.ld;
+      items[z].n = it.n;
+      items[z].K = d;
+    }
+    launch_gemm_nt_group(s, items, cnt, kEpiNone, 0);
+  }
+  if (n_chain > 0) {
+    launch_batch_cosine_distance(s, table_d, 0, n_chain, chain_rows);
+    launch_batch_nn_chain_verdict(s, table_d, 0, n_chain, threshold);
+  }
+#if SC_POOL_LDS_LINKAGE_MAX > 0
+  if (count > n_chain)
+    launch_batch_linkage_lds_verdict(s, table_d, n_chain, count - n_chain, lds_rows, threshold);
+#endif
+  SC_TRY(check_last(h, "batched single-cluster verdict launch"));
+  SC_HIP(h, hipMemcpyAsync(const_cast<double*>(rec_h), rec_d,
+                           back_doubles * sizeof(double) + (size_t)count * sizeof(int),
+                           hipMemcpyDeviceToHost, s));
+  SC_HIP(h, hipStreamSynchronize(s));
+  int bad_index = -1;  // (the first of the batch, whatever the wave's order)
+  for (int i = 0; i < count; ++i)
+    if (bad_h[i] != 0 && (bad_index < 0 || wave[i]->index < bad_index)) bad_index = wave[i]->index;
+  if (bad_index >= 0) return fail(h, SC_ERR_INVALID, bad_rows_message(bad_index));
+  for (int i = 0; i < count; ++i) {
+    VerdictMember& m = *wave[i];
+    m.height = rec_h[2 * (size_t)i];
+    m.single = rec_h[2 * (size_t)i + 1] != 0.0;
+    m.dev_rows = keep ? table_h[i].X : nullptr;
+  }
+  return SC_OK;
+}
+
+// Every member of `members` (checked: n >= 2): height and single.  `keep` (may be null): the
+// rows' blocks of the waves stay there, and every dev_rows with them, while they add up to at
+// most half a wave's budget; a member whose rows did not stay has dev_rows == nullptr.
+int fallback_verdicts(sc_handle h, const sc_array* xs, int d, std::vector<VerdictMember>* members,
+                      double threshold, DeviceBlocks* keep) {
+  std::vector<int> order(members->size());
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(),
+                   [&](int a, int b) { return (*members)[a].n > (*members)[b].n; });
+  size_t at = 0, kept = 0;
+  while (at < order.size()) {
+    size_t budget = h->reduce_wave_bytes;
+    if (budget == 0) {
+      size_t free_bytes = 0, device_bytes = 0;
+      SC_HIP(h, hipMemGetInfo(&free_bytes, &device_bytes));
+      budget = (size_t)(kReduceWaveShare * (double)free_bytes);
+    }
+    VerdictMember* first = &(*members)[order[at]];
+    if (first->n >= kReduceSingleMin || first->wave_bytes(d) + 2 * 256 > budget) {
+      SC_TRY(verdict_single(h, xs[first->index], first, threshold));
+      ++at;
+      continue;
+    }
+    std::vector<VerdictMember*> wave;
+    size_t bytes = 2 * 256, rows = 0;  // (the slabs' alignment)
+    while (at < order.size()) {
+      VerdictMember* m = &(*members)[order[at]];
+      if (bytes + m->wave_bytes(d) > budget) break;
+      bytes += m->wave_bytes(d);
+      rows += m->rows_bytes(d);
+      wave.push_back(m);
+      ++at;
+    }
+    // the members of the LDS kernel behind those of the chain kernel (both stay longest first)
+    std::stable_partition(wave.begin(), wave.end(), [](VerdictMember* m) { return !m->lds(); });
+    const bool stay = keep && kept + rows <= budget / 2;
+    SC_TRY(verdict_wave(h, xs, d, wave, threshold, stay ? keep : nullptr));
+    if (stay) kept += rows;
+  }
+  return SC_OK;
+}
+
+// what both entry points check of every utterance before the first launch
+int verdict_members(sc_handle h, const std::vector<int>& ns, std::vector<VerdictMember>* members) {
+  members->resize(ns.size());
+  for (size_t i = 0; i < ns.size(); ++i) {
+    if (ns[i] < 2) return too_few_rows(h, (int)i, ns[i]);
+    (*members)[i].index = (int)i;
+    (*members)[i].n = ns[i];
+  }
+  return SC_OK;
+}
+
 }  // namespace
 
 extern "C" int sc_set_reduce_wave_bytes(sc_handle h, size_t bytes) {
@@ -447,5 +668,96 @@ extern "C" int sc_predict_batch_reduced(sc_handle h, const sc_array* xs, int cou
   if (diags)
     for (int i = 0; i < count; ++i)
       if (kind[i] == 2) memset(&diags[i], 0, sizeof(sc_diag));
+  return SC_OK;
+}
+
+extern "C" int sc_batch_fallback_check(sc_handle h, const sc_array* xs, int count,
+                                       double distance_threshold, double* heights,
+                                       int32_t* single) {
+  if (!h) return SC_ERR_INVALID;
+  if (!xs || !heights || !single || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  SC_HIP(h, hipSetDevice(h->device));
+  bool device_source = false;
+  std::vector<int> ns;
+  int d = 0;
+  SC_TRY(validate_batch_arrays(h, xs, count, &ns, &d, &device_source));
+  std::vector<VerdictMember> members;
+  SC_TRY(verdict_members(h, ns, &members));
+  SC_TRY(fallback_verdicts(h, xs, d, &members, distance_threshold, nullptr));
+  for (const VerdictMember& m : members) {  // (nothing is written unless every wave succeeded)
+    heights[m.index] = m.height;
+    single[m.index] = m.single;
+  }
+  return SC_OK;
+}
+
+extern "C" int sc_predict_batch_single_fallback(sc_handle h, const sc_array* xs, int count,
+                                                const sc_config* cfg, double distance_threshold,
+                                                int64_t* const* labels, sc_diag* diags,
+                                                int group, int32_t* single) {
+  if (!h) return SC_ERR_INVALID;
+  if (!xs || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  if (group < 2)
+    return fail(h, SC_ERR_INVALID,
+                "sc_predict_batch_single_fallback is the grouped form: group >= 2");
+  SC_TRY(validate_config(h, cfg));
+  SC_HIP(h, hipSetDevice(h->device));
+  bool device_source = false;
+  std::vector<int> ns;
+  int d = 0;
+  SC_TRY(validate_batch_arrays(h, xs, count, &ns, &d, &device_source, labels));
+  std::vector<VerdictMember> members;
+  SC_TRY(verdict_members(h, ns, &members));
+  SC_TRY(sc_clear_constraint(h));  // a batch carries none
+  if (count == 0) {
+    h->last_routes.clear();
+    return SC_OK;
+  }
+  // the verdicts of the whole batch first (waves of hundreds of workgroups, not one lockstep
+  // group at a time); the rows of the waves stay on the device for the survivors
+  DeviceBlocks rows;
+  SC_TRY(fallback_verdicts(h, xs, d, &members, distance_threshold, &rows));
+  // ONE grouped batch over the utterances of several clusters
+  std::vector<int> at;  // position in that batch -> utterance
+  std::vector<sc_array> sub;
+  std::vector<int> sub_ns;
+  std::vector<int64_t*> sub_labels;
+  for (const VerdictMember& m : members) {
+    const int i = m.index;
+    if (single) single[i] = m.single;
+    if (m.single) {  // predict(): np.array([0] * n), before the affinity is built
+      std::fill(labels[i], labels[i] + ns[i], (int64_t)0);
+      continue;
+    }
+    sc_array a = xs[i];
+    if (m.dev_rows) {  // the widened rows (exact: the labels are those of the caller's array)
+      a.data = m.dev_rows;
+      a.dtype = SC_DTYPE_F64;
+      a.location = SC_MEM_DEVICE;
+      a.row_stride = round_up(d, 16);
+      a.col_stride = 1;
+    }
+    at.push_back(i);
+    sub.push_back(a);
+    sub_ns.push_back(ns[i]);
+    sub_labels.push_back(labels[i]);
+  }
+  const int sub_count = (int)at.size();
+  std::vector<sc_diag> sub_diags(diags ? sub_count : 0);
+  std::vector<int32_t> routes(count, SC_BATCH_ROUTE_FALLBACK);
+  if (sub_count > 0) {
+    // (every wave ended drained; what the caller ordered before this handle's stream is done
+    //  before the streams of the batch read a device source)
+    SC_HIP(h, hipStreamSynchronize(h->stream));
+    SC_TRY(predict_batch_grouped_impl(h, sub.data(), sub_ns.data(), d, sub_count, cfg,
+                                      sub_labels.data(), diags ? sub_diags.data() : nullptr,
+                                      group));
+    for (int z = 0; z < sub_count; ++z) routes[at[z]] = h->last_routes[z];
+  }
+  h->last_routes = routes;
+  if (diags) {
+    for (int i = 0; i < count; ++i) memset(&diags[i], 0, sizeof(sc_diag));
+    for (int z = 0; z < sub_count; ++z) diags[at[z]] = sub_diags[z];
+  }
   return SC_OK;
 }

@@ -29,7 +29,7 @@ extern "C" int sc_ahc(sc_handle h, const double* x, int n, int d, int linkage, i
 
 // ... on the n >= 2 rows resident in h->X; the arguments have been checked
 int ahc_resident(sc_handle h, int linkage, int n_clusters, double distance_threshold,
-                 int64_t* labels, int* n_clusters_out) {
+                 int64_t* labels, int* n_clusters_out, double* max_height) {
   const int n = h->n, d = h->d;
   // cosine distances: the affinity stage's normalise + symmetric GEMM, then 1 - clip(c)
   SC_TRY(ensure_tilemap(h, n));
@@ -58,6 +58,11 @@ int ahc_resident(sc_handle h, int linkage, int n_clusters, double distance_thres
   // sort, union-find relabelling and the heap cut: ahc_tree.cpp
   const int k = ahc_tree_cut(Z.data(), n, n_clusters, distance_threshold, labels);
   if (n_clusters_out) *n_clusters_out = k;
+  if (max_height) {
+    double top = Z[2];
+    for (int m = 1; m < n - 1; ++m) top = std::max(top, Z[(size_t)m * 4 + 2]);
+    *max_height = top;
+  }
   return SC_OK;
 }
 

@@ -296,9 +296,10 @@ int predict_batch_grouped_impl(sc_handle h, const sc_array* xs, const int* ns, i
                                const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
                                int group);
 
-// sc_ahc on the embeddings resident in h->X (ingest_embeddings): callers_api.hip
+// sc_ahc on the embeddings resident in h->X (ingest_embeddings): callers_api.hip.  max_height
+// (may be null): the largest merge height of the tree.
 int ahc_resident(sc_handle h, int linkage, int n_clusters, double distance_threshold,
-                 int64_t* labels, int* n_clusters_out);
+                 int64_t* labels, int* n_clusters_out, double* max_height = nullptr);
 
 int ensure_eig(sc_handle h, int n);
 

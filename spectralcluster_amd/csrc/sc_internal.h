@@ -782,6 +782,17 @@ void launch_batch_cosine_distance(hipStream_t s, const AhcBatchItem* table, int 
 // launch_ahc_nn_chain for members [first, first + count): one workgroup each; a member whose
 // word is set, or of n < 2, is left alone
 void launch_batch_nn_chain(hipStream_t s, const AhcBatchItem* table, int first, int count);
+// The verdict forms (average linkage; sc_batch_fallback_check): "does a cut at `threshold` leave
+// one cluster?" for members [first, first + count), whose Z points at a two-double record
+// {height, verdict} instead of a merge list.  verdict 1: no merge height >= threshold, height the
+// largest of them; verdict 0: height the first one found >= threshold (the work ends there).
+// The heights are those launch_batch_nn_chain / launch_batch_linkage_lds write, bit for bit.
+void launch_batch_nn_chain_verdict(hipStream_t s, const AhcBatchItem* table, int first, int count,
+                                   double threshold);
+#if SC_POOL_LDS_LINKAGE_MAX > 0
+void launch_batch_linkage_lds_verdict(hipStream_t s, const AhcBatchItem* table, int first,
+                                      int count, int max_rows, double threshold);
+#endif
 // utils.get_cluster_centroids of members [first, first + count) from their CSR; max_outputs:
 // the largest kcap * d among them
 void launch_batch_centroids(hipStream_t s, const AhcBatchItem* table, int first, int count,

@@ -248,6 +248,14 @@ class MultiStageStreamPool:
   cache is kept then and no embedding is downloaded.  Without the flag, or with a main clusterer
   outside the library batch, each such session runs `main.predict` on a host mirror of its
   cache, one after the other.
+
+  `pool_fallback_condition` (keyword only, default False): a `min_clusters=1` main clusterer that
+  carries the single-cluster condition this constructor sets (FallbackClusterer, agglomerative)
+  counts as one the library batch covers.  The step's grouped main call is then ONE
+  `sc_predict_batch_single_fallback` call: the verdicts of all its centroid buffers (and, with
+  `pool_early_stage`, of the caches of L .. U1 rows) on the device, then the grouped batch of
+  those that hold several clusters.  Without the flag such a pool runs `main.predict` per
+  session (routes 0 and 2), as before.
   """
 
   def __init__(self,
@@ -261,7 +269,8 @@ class MultiStageStreamPool:
                device: typing.Optional[int] = None,
                d: typing.Optional[int] = None,
                *,
-               pool_early_stage: bool = False):
+               pool_early_stage: bool = False,
+               pool_fallback_condition: bool = False):
     # (the option changes and the max_spectral_size check of the per-stream class)
     MultiStageClusterer(main_clusterer, fallback_threshold, L, U1, U2, deflicker)
     self.main = main_clusterer
@@ -269,6 +278,7 @@ class MultiStageStreamPool:
     self.L, self.U1, self.U2 = int(L), int(U1), int(U2)
     self.capacity = int(capacity)
     self.pool_early_stage = bool(pool_early_stage)
+    self.pool_fallback_condition = bool(pool_fallback_condition)
     self.device = device if device is not None else main_clusterer.device
     self.d = None
     self._pool = None
@@ -472,7 +482,10 @@ class MultiStageStreamPool:
           arrays.append(_lib.ScArray())
           handle.check(handle.lib.sc_pool_centroids(self._pool, sessions[i],
                                                     ctypes.byref(arrays[-1])))
-        main = self.main.predict_device_batch(arrays)
+        if getattr(self, "pool_fallback_condition", False):
+          main = self.main.predict_device_batch(arrays, batch_fallback_condition=True)
+        else:
+          main = self.main.predict_device_batch(arrays)
         for i, main_labels in zip(early_main, main):
           out[i] = main_labels
           states[i].previous_output = out[i]
@@ -506,7 +519,12 @@ class MultiStageStreamPool:
   def _main_is_batchable(self) -> bool:
     """predict_batch's conditions; spectral_min_embeddings (= L) is met by the U1 centroids, and
     a min_clusters = 1 main clusterer is covered when its single-cluster test reads the affinity
-    (predict_device_batch then carries the test inside the grouped call)."""
+    (predict_device_batch then carries the test inside the grouped call).  With
+    `pool_fallback_condition` the FallbackClusterer condition is covered as well (it checks the
+    metric itself)."""
+    if (getattr(self, "pool_fallback_condition", False) and
+        self.main._fallback_condition_covers(min_embeddings_met=self.L <= self.U1)):
+      return True
     if not self.main._library_batch_covers(min_embeddings_met=self.L <= self.U1,
                                            single_check_covered=True):
       return False

@@ -384,7 +384,8 @@ class SpectralClusterer:
                     streams: typing.Optional[int] = None,
                     group: typing.Optional[int] = None,
                     constraint_matrices: typing.Optional[typing.Sequence] = None,
-                    autotune_from_entry_state: bool = False
+                    autotune_from_entry_state: bool = False,
+                    batch_fallback_condition: bool = False
                     ) -> typing.List[np.ndarray]:
     """Independent predict() calls (the reference has no batch API: a batch is a
     Python loop).
@@ -487,12 +488,33 @@ class SpectralClusterer:
     AffinityGmmBic an utterance of `single_cluster_affinity_diagonal_offset >= n - 1` raises
     predict()'s ValueError, with the utterance's index, before anything is launched.  These keep
     the per-utterance loop (routes all 0) with `min_clusters=1`: the `FallbackClusterer` condition
-    (it clusters the embeddings, not the affinity), constrained batches, AutoTune batches, and
-    batches with `max_spectral_size` / `spectral_min_embeddings`.
+    (it clusters the embeddings, not the affinity; see `batch_fallback_condition`), constrained
+    batches, AutoTune batches, and batches with `max_spectral_size` / `spectral_min_embeddings`.
+
+    `batch_fallback_condition` (default False: the loop above).  With it a `min_clusters=1`
+    batch under the `FallbackClusterer` condition -- what `MultiStageClusterer`'s constructor
+    sets -- is ONE `sc_predict_batch_single_fallback` call when the fallback type is
+    `Agglomerative`, the batch is the grouped form (`group` not 1, no `streams`), unconstrained,
+    there is no AutoTune, no `max_spectral_size`, no `spectral_min_embeddings` above 1, the
+    affinity and k-means functions are the default ones and k-means is the cosine one.  The
+    verdicts of the whole batch are computed first -- "does average-linkage cosine AHC, cut at
+    `agglomerative_threshold`, leave one cluster?", a wavefront or a workgroup per utterance, no
+    merge list downloaded --, then one grouped batch clusters the utterances of several clusters
+    from the rows the verdict waves left on the device.  Results are predict()'s:
+    `np.array([0] * n)` for an utterance of one cluster (route 3, a zeroed diag), int64 labels
+    otherwise (route 0, 1 or 2); `last_batch_single` lists the verdicts.  An utterance of one
+    row raises predict()'s ValueError before anything is launched, one with a zero or non-finite
+    row a ValueError that names its index.  Anything else keeps the loop, flag or no flag.
     """
     self.last_batch_single = None
     if autotune_from_entry_state and self.autotune is not None:
       return self._predict_batch_entry_state(utterances, constraint_matrices, streams, group)
+    if (batch_fallback_condition and streams is None and (group is None or int(group) > 1) and
+        (constraint_matrices is None or self.constraint_options is None) and
+        self._fallback_condition_covers()):
+      if constraint_matrices is not None and len(constraint_matrices) != len(utterances):
+        raise ValueError("constraint_matrices must be as long as the batch")
+      return self._predict_batch_single_fallback(utterances, 16 if group is None else int(group))
     library_batch = self._library_batch_covers()
     # min_clusters = 1 with a condition that reads the affinity: the test travels inside ONE
     # sc_predict_batch_single call -- the grouped form, unconstrained, cosine k-means
@@ -769,6 +791,73 @@ class SpectralClusterer:
         self.affinity_function is not utils.compute_affinity_matrix or
         self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans)
 
+  def _fallback_condition_covers(self, min_embeddings_met: bool = False) -> bool:
+    """Is this clusterer one whose predict() `sc_predict_batch_single_fallback` reproduces?
+    `min_clusters == 1` decided by the FallbackClusterer condition with the agglomerative
+    fallback, and otherwise what `_library_batch_covers` asks, with cosine k-means.
+    `min_embeddings_met` as there."""
+    options = self.fallback_options
+    if not (self.min_clusters == 1 and
+            options.single_cluster_condition ==
+            fallback_clusterer.SingleClusterCondition.FallbackClusterer and
+            options.fallback_clusterer_type ==
+            fallback_clusterer.FallbackClustererType.Agglomerative):
+      return False
+    if (self.autotune is not None or self.max_spectral_size is not None or
+        (options.spectral_min_embeddings > 1 and not min_embeddings_met) or
+        self.affinity_function is not utils.compute_affinity_matrix or
+        self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans):
+      return False
+    try:
+      return _lib.kmeans_metric_code(self.custom_dist) == _lib.KMEANS_METRICS["cosine"]
+    except (ValueError, _lib.UnsupportedOnDeviceError):
+      return False  # (predict() raises what it raises today)
+
+  def _single_fallback_call(self, handle: _lib.Handle, arrays: typing.Sequence[_lib.ScArray],
+                            group: int) -> typing.List[np.ndarray]:
+    """ONE `sc_predict_batch_single_fallback` call on described sources: predict()'s results,
+    `last_batch_single` / `last_batch_routes` / `last_batch_diags` filled."""
+    count = len(arrays)
+    for i, a in enumerate(arrays):
+      if int(a.rows) < 2:  # (predict()'s ValueError, before anything is launched)
+        raise ValueError("Found array with %d sample(s) while a minimum of 2 is required by "
+                         "AgglomerativeClustering." % int(a.rows))
+    labels = [np.empty(int(a.rows), dtype=np.int64) for a in arrays]
+    lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
+    diags = (_lib.ScDiag * count)()
+    single = (ctypes.c_int32 * count)()
+    handle.check(handle.lib.sc_predict_batch_single_fallback(
+        handle.raw, (_lib.ScArray * count)(*arrays), count, self.build_config(),
+        float(self.fallback_options.agglomerative_threshold), lp, diags, int(group), single),
+        ValueError)
+    self._batch_report(handle, diags, count)
+    self.last_batch_single = [bool(v) for v in single]
+    # predict()'s result for a single-cluster utterance: np.array([0] * n)
+    return [np.array([0] * l.shape[0]) if one else l
+            for l, one in zip(labels, self.last_batch_single)]
+
+  def _predict_batch_single_fallback(self, utterances: typing.Sequence,
+                                     group: int) -> typing.List[np.ndarray]:
+    """predict_batch(batch_fallback_condition=True); `_fallback_condition_covers` holds."""
+    for u in utterances:
+      if isinstance(u, np.ndarray) and u.ndim != 2:
+        raise ValueError("all utterances must be (n_i, d) with the same d")
+    if not utterances:
+      self.last_batch_routes, self.last_batch_single, self.last_batch_diags = [], [], []
+      return []
+    sources = []
+    try:
+      with _lib.use_device(self.device):
+        for u in utterances:
+          sources.append(_dlpack.describe(u, self._handle))
+      d = sources[0].shape[1]
+      if any(src.shape[1] != d for src in sources):
+        raise ValueError("all utterances must be (n_i, d) with the same d")
+      return self._single_fallback_call(self._handle(), [src.array for src in sources], group)
+    finally:
+      for src in sources:
+        src.release()
+
   def _batch_kind(self, n: int) -> int:
     """What predict() does with an utterance of n rows (`_lib.BATCH_KIND_*`): the fallback
     clusterer, size reduction first, or the spectral path as it is (reference :229-248)."""
@@ -886,12 +975,20 @@ class SpectralClusterer:
       self.last_batch_routes = [int(r) for r in routes]
 
   def predict_device_batch(self, arrays: typing.Sequence[_lib.ScArray],
-                           group: int = 16) -> typing.List[np.ndarray]:
+                           group: int = 16,
+                           batch_fallback_condition: bool = False) -> typing.List[np.ndarray]:
     """predict_batch for utterances that are already described (`sc_array`s, e.g. the resident
     centroid buffers of a stream pool) on a clusterer `_library_batch_covers`: one grouped
-    library call, `last_batch_routes` / `last_batch_diags` as after predict_batch."""
+    library call, `last_batch_routes` / `last_batch_diags` as after predict_batch.
+    `batch_fallback_condition`: as predict_batch's, for a clusterer
+    `_fallback_condition_covers(min_embeddings_met=True)` (the caller vouches for the rows)."""
     _lib.kmeans_metric_code(self.custom_dist)  # raises for metrics that are not on the device
     count = len(arrays)
+    if batch_fallback_condition and self._fallback_condition_covers(min_embeddings_met=True):
+      handle = self._handle()
+      handle.check(handle.lib.sc_clear_constraint(handle.raw))  # a batch carries none
+      self.last_batch_single = None
+      return self._single_fallback_call(handle, arrays, max(2, int(group)))
     labels = [np.empty(int(a.rows), dtype=np.int64) for a in arrays]
     handle = self._handle()
     handle.check(handle.lib.sc_clear_constraint(handle.raw))  # a batch carries none

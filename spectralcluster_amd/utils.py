@@ -212,3 +212,40 @@ def cosine_agglomerative_clustering_batch(embeddings_list: typing.Sequence,
   if not return_centroids:
     return labels
   return labels, [c[:int(l.max()) + 1] for c, l in zip(centroids, labels)]
+
+
+def cosine_single_cluster_check_batch(embeddings_list: typing.Sequence,
+                                      distance_threshold: float):
+  """Does `cosine_agglomerative_clustering(e, linkage="average", distance_threshold=...)` leave
+  ONE cluster? -- for every entry of `embeddings_list` (what `cosine_agglomerative_clustering_batch`
+  takes) in one `sc_batch_fallback_check` call: the FallbackClusterer single-cluster condition
+  with the agglomerative fallback (`fallback_clusterer.check_single_cluster`), decided on the
+  device without a merge list.  Returns (single, heights): a bool array, and per entry the merge
+  height that decided it -- the largest of the tree for an entry of one cluster, otherwise the
+  first one found at or above the threshold.  An entry with a zero or non-finite row raises a
+  ValueError that names its index; neither output exists then."""
+  from spectralcluster_amd import _dlpack  # (it imports this module's siblings)
+  for e in embeddings_list:
+    if isinstance(e, np.ndarray) and e.ndim != 2:
+      raise ValueError("embeddings must be 2-dimensional")
+  count = len(embeddings_list)
+  heights = np.full(count, np.nan, dtype=np.float64)
+  single = np.full(count, -1, dtype=np.int32)
+  if count == 0:
+    return single.astype(bool), heights
+  handle = _lib.default_handle()
+  sources = []
+  try:
+    for e in embeddings_list:
+      sources.append(_dlpack.describe(e, lambda: handle))
+    d = sources[0].shape[1]
+    if any(src.shape[1] != d for src in sources):
+      raise ValueError("all utterances must be (n_i, d) with the same d")
+    handle.check(handle.lib.sc_batch_fallback_check(
+        handle.raw, (_lib.ScArray * count)(*[src.array for src in sources]), count,
+        float(distance_threshold), _lib.as_double_p(heights),
+        single.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+  finally:
+    for src in sources:
+      src.release()
+  return single.astype(bool), heights
