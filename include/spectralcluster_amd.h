@@ -620,6 +620,62 @@ int sc_predict_batch_single_fallback(sc_handle h, const sc_array* xs, int count,
                                      int32_t* single);
 
 /*
+ * The Naive fallback type (fallback_clusterer.py:114-118, naive_clusterer.py; what a default
+ * FallbackOptions selects) for a whole batch: NaiveClusterer(threshold,
+ * adaptation_threshold).predict from the EMPTY state for every listed array -- the first row
+ * opens centroid 0; after that a cosine to every centroid, the first maximum wins, a new centroid
+ * when best < threshold, a merge when best > adaptation_threshold.
+ *
+ * sc_batch_naive_cluster: the arrays may be of any dtype, in host or device memory, with the same
+ * cols and at least 1 row each.  labels[i] receives rows_i labels, n_clusters[i] the number of
+ * centroids.  centroids and counts may be NULL or hold NULL entries; centroids[i] holds rows_i x
+ * cols doubles and counts[i] rows_i ints, of which the first n_clusters[i] rows / entries are
+ * written.  Labels, counts and centroids are bit for bit those of sc_naive_cluster on the widened
+ * fp64 rows with *n_centroids = 0 (both kernels share their arithmetic), for every input, zero
+ * and NaN rows included.  The members are taken in sc_batch_ahc's waves
+ * (sc_set_reduce_wave_bytes): the longest remaining members whose buffers fit the wave budget
+ * share one allocation, one ingest per member, one table copy, ONE launch (a workgroup of 256
+ * threads per member), one copy back and one synchronisation.  No size sends a member anywhere
+ * else: one that alone exceeds the budget is a wave of its own.  Every argument is checked before
+ * the first launch (SC_ERR_INVALID also for adaptation_threshold < threshold); the outputs are
+ * written only when the call succeeds; a member's result does not depend on what else is in the
+ * call.
+ *
+ * sc_batch_naive_check: "does the walk end with one centroid?" alone, through the VERDICT form of
+ * the same kernel: a member's work ends at the row that would open a second centroid, no labels
+ * or centroids are written, a wave downloads one record per member.  single[i] = 1 and
+ * stopped_at[i] = rows_i when the walk ended with one centroid; otherwise single[i] = 0 and
+ * stopped_at[i] is the index of the row that would open the second one (the first row
+ * sc_batch_naive_cluster labels 1).  Zero and non-finite rows are walked as sc_naive_cluster
+ * walks them; they fail nothing here.
+ */
+int sc_batch_naive_cluster(sc_handle h, const sc_array* xs, int count, double threshold,
+                           double adaptation_threshold, int64_t* const* labels,
+                           int32_t* n_clusters, double* const* centroids,
+                           int32_t* const* counts);
+int sc_batch_naive_check(sc_handle h, const sc_array* xs, int count, double threshold,
+                         double adaptation_threshold, int32_t* single, int32_t* stopped_at);
+/* sc_predict_batch_reduced with the Naive fallback type: the utterances of fewer than
+ * spectral_min_embeddings rows (kind 2) are clustered by sc_batch_naive_cluster's waves inside the
+ * call; one of a single row is fine (label 0).  Kinds 0 and 1, routes and diags are exactly
+ * sc_predict_batch_reduced's (one body runs both calls). */
+int sc_predict_batch_reduced_naive(sc_handle h, const sc_array* xs, int count,
+                                   const sc_config* cfg, int max_spectral_size,
+                                   int spectral_min_embeddings, double naive_threshold,
+                                   double naive_adaptation_threshold, int64_t* const* labels,
+                                   sc_diag* diags, int group, int32_t* kinds);
+/* sc_predict_batch_single_fallback with the Naive fallback type: the verdicts are
+ * sc_batch_naive_check's, and the widened rows of a wave stay on the device for the grouped batch
+ * of the survivors under the same half-budget rule.  An utterance of one row is single (zeros,
+ * route SC_BATCH_ROUTE_FALLBACK).  An utterance with a zero or non-finite row (the rule of the
+ * unit-row kernel) fails the call with SC_ERR_INVALID and a message that names its index, whatever
+ * its verdict, as the agglomerative form does. */
+int sc_predict_batch_single_naive(sc_handle h, const sc_array* xs, int count,
+                                  const sc_config* cfg, double naive_threshold,
+                                  double naive_adaptation_threshold, int64_t* const* labels,
+                                  sc_diag* diags, int group, int32_t* single);
+
+/*
  * Stream pool: up to `capacity` streaming sessions (multi_stage_clusterer.py:128-180) whose
  * caches stay on the device.  A session lives in a slot 0 .. capacity - 1 and holds up to u2
  * rows of d values; its pre-clusterer reduces them to u1 centroids (2 <= u1 < u2).  All device

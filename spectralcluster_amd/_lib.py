@@ -340,6 +340,29 @@ PROTOTYPES = {
                                                         ctypes.POINTER(_c_int64_p),
                                                         ctypes.POINTER(ScDiag), ctypes.c_int,
                                                         ctypes.POINTER(ctypes.c_int32)]),
+    "sc_batch_naive_cluster": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray), ctypes.c_int,
+                                              ctypes.c_double, ctypes.c_double,
+                                              ctypes.POINTER(_c_int64_p),
+                                              ctypes.POINTER(ctypes.c_int32),
+                                              ctypes.POINTER(_c_double_p),
+                                              ctypes.POINTER(ctypes.POINTER(ctypes.c_int32))]),
+    "sc_batch_naive_check": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray), ctypes.c_int,
+                                            ctypes.c_double, ctypes.c_double,
+                                            ctypes.POINTER(ctypes.c_int32),
+                                            ctypes.POINTER(ctypes.c_int32)]),
+    "sc_predict_batch_reduced_naive": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),
+                                                      ctypes.c_int, ctypes.POINTER(ScConfig),
+                                                      ctypes.c_int, ctypes.c_int,
+                                                      ctypes.c_double, ctypes.c_double,
+                                                      ctypes.POINTER(_c_int64_p),
+                                                      ctypes.POINTER(ScDiag), ctypes.c_int,
+                                                      ctypes.POINTER(ctypes.c_int32)]),
+    "sc_predict_batch_single_naive": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),
+                                                     ctypes.c_int, ctypes.POINTER(ScConfig),
+                                                     ctypes.c_double, ctypes.c_double,
+                                                     ctypes.POINTER(_c_int64_p),
+                                                     ctypes.POINTER(ScDiag), ctypes.c_int,
+                                                     ctypes.POINTER(ctypes.c_int32)]),
     "sc_pool_create": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, ctypes.POINTER(_handle_t)]),
     "sc_pool_destroy": (ctypes.c_int, [_handle_t]),

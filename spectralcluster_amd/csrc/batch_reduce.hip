@@ -18,7 +18,10 @@
 // The FallbackClusterer single-cluster test of a batch (sc_batch_fallback_check,
 // sc_predict_batch_single_fallback) runs the same waves up to the distances, then the verdict
 // forms of the linkage kernels: see VerdictMember below.
-// Kernels: ahc.hip, rowops.hip.
+// The Naive fallback type (sc_batch_naive_cluster, sc_batch_naive_check and the _naive forms of
+// the two predict calls) runs the same waves with one launch between ingest and copy back: see
+// NaiveMember below.  The two predict calls and their _naive forms share one body each.
+// Kernels: ahc.hip, rowops.hip, naive_batch.hip.
 #include "ahc_tree.h"
 #include "handle.h"
 #include "host_pool.h"
@@ -524,72 +527,205 @@ int verdict_members(sc_handle h, const std::vector<int>& ns, std::vector<Verdict
   return SC_OK;
 }
 
-}  // namespace
+// ---- the naive fallback clusterer of a batch (sc_batch_naive_cluster, sc_batch_naive_check and
+//      the _naive forms of the two predict calls): NaiveClusterer.predict from the empty state for
+//      every member, in waves as above, with nothing between the ingest and the walk -- one
+//      allocation pair, one ingest per member, one table copy, ONE launch (k_naive_cluster_batch,
+//      a workgroup per member), one copy back, one synchronisation.  There is no single path: a
+//      member that alone exceeds the budget is a wave of its own.
+//      labels form   back: [centroids n x d of the members that want them] [labels n | counts n |
+//                    n_clusters per member]; the other members' centroids are scratch
+//      verdict form  back: {single, stopped_at, bad} per member; scratch: one centroid each.  The
+//                    rows are a block of their own, which may outlive the wave (VerdictMember).
+struct NaiveMember {
+  int index = 0;  // into the caller's lists
+  int n = 0;
+  bool want_centroids = false;  // labels form: the centroids come back
+  // results
+  std::vector<int> ints;     // labels form: labels n | counts n | n_clusters
+  std::vector<double> cent;  // labels form, wanted: n_clusters x d
+  int single = 0, stopped_at = 0;    // verdict form
+  const double* dev_rows = nullptr;  // the widened rows (pitch round_up(d, 16)) where they stayed
 
-extern "C" int sc_set_reduce_wave_bytes(sc_handle h, size_t bytes) {
-  if (!h) return SC_ERR_INVALID;
-  h->reduce_wave_bytes = bytes;
+  int k() const { return ints[2 * (size_t)n]; }
+  size_t rows_bytes(int d) const { return align256((size_t)n * round_up(d, 16) * sizeof(double)); }
+  size_t cent_bytes(int d, bool verdict) const {
+    return align256((size_t)(verdict ? 1 : n) * d * sizeof(double));
+  }
+  size_t back_ints(bool verdict) const { return verdict ? 3 : 2 * (size_t)n + 1; }
+  size_t wave_bytes(int d, bool verdict) const {
+    return rows_bytes(d) + cent_bytes(d, verdict) + back_ints(verdict) * sizeof(int) +
+           sizeof(NaiveBatchItem);
+  }
+};
+
+struct NaiveRun {
+  double threshold = 0.0, adaptation = 0.0;
+  bool verdict = false;
+  bool check_rows = false;  // verdict form: a zero or non-finite row fails the call
+};
+
+// One wave.  `keep` (may be null): the rows' block joins it and every dev_rows is set; otherwise
+// it is freed with the wave's other buffers.  On return the stream has drained.
+int naive_wave(sc_handle h, const sc_array* xs, int d, const std::vector<NaiveMember*>& wave,
+               const NaiveRun& run, DeviceBlocks* keep) {
+  const int count = (int)wave.size();
+  const int ldx = round_up(d, 16);
+  hipStream_t s = h->stream;
+  size_t rows_total = 0, back_cent = 0, back_ints = 0, scratch_total = 0;
+  for (const NaiveMember* m : wave) {
+    rows_total += m->rows_bytes(d);
+    back_ints += m->back_ints(run.verdict);
+    (m->want_centroids ? back_cent : scratch_total) += m->cent_bytes(d, run.verdict);
+  }
+  // descriptors | centroids that travel back + the members' ints
+  const size_t table_bytes = align256((size_t)count * sizeof(NaiveBatchItem));
+  const size_t back_bytes = back_cent + align256(back_ints * sizeof(int));
+  const size_t staged = table_bytes + back_bytes;
+  SC_TRY(ensure_wave_staging(h, staged));
+  DeviceBlocks scratch;  // freed when the wave returns
+  void* rows_block = nullptr;
+  SC_HIP(h, hipMalloc(&rows_block, rows_total));
+  (keep ? keep : &scratch)->blocks.push_back(rows_block);
+  void* block = nullptr;
+  SC_HIP(h, hipMalloc(&block, staged + scratch_total));
+  scratch.blocks.push_back(block);
+  char* dev = static_cast<char*>(block);
+  char* host = static_cast<char*>(h->h_reduce);
+  NaiveBatchItem* table_d = reinterpret_cast<NaiveBatchItem*>(dev);
+  NaiveBatchItem* table_h = reinterpret_cast<NaiveBatchItem*>(host);
+  char* back_d = dev + table_bytes;
+  const char* back_h = host + table_bytes;
+  int* ints_d = reinterpret_cast<int*>(back_d + back_cent);
+  const int* ints_h = reinterpret_cast<const int*>(back_h + back_cent);
+  char* cent_at = back_d;
+  char* scratch_at = dev + staged;
+  char* rows_at = static_cast<char*>(rows_block);
+  auto carve = [](char*& from, size_t bytes) {
+    void* p = from;
+    from += bytes;  // (a multiple of 256)
+    return p;
+  };
+  std::vector<size_t> ints_of(count), cent_of(count);  // offsets into the back slab
+  size_t ints_used = 0;
+  for (int i = 0; i < count; ++i) {
+    const NaiveMember& m = *wave[i];
+    NaiveBatchItem& it = table_h[i];
+    memset(&it, 0, sizeof(it));
+    it.n = m.n;
+    it.ldx = ldx;
+    it.d = d;
+    it.X = static_cast<double*>(carve(rows_at, m.rows_bytes(d)));
+    cent_of[i] = (size_t)(cent_at - back_d);
+    it.cent = static_cast<double*>(
+        carve(m.want_centroids ? cent_at : scratch_at, m.cent_bytes(d, run.verdict)));
+    ints_of[i] = ints_used;
+    int* mine = ints_d + ints_used;
+    ints_used += m.back_ints(run.verdict);
+    if (run.verdict) {
+      it.out = mine;
+      it.bad = run.check_rows ? mine + 2 : nullptr;
+    } else {
+      it.labels = mine;
+      it.counts = mine + m.n;
+      it.out = mine + 2 * (size_t)m.n;
+    }
+  }
+  SC_HIP(h, hipMemcpyAsync(table_d, table_h, (size_t)count * sizeof(NaiveBatchItem),
+                           hipMemcpyHostToDevice, s));
+  if (run.verdict) SC_HIP(h, hipMemsetAsync(ints_d, 0, back_ints * sizeof(int), s));
+  bool sync = false;  // (the wave synchronises before it returns)
+  for (int i = 0; i < count; ++i)
+    SC_TRY(ingest_rows_into(h, xs[wave[i]->index], const_cast<double*>(table_h[i].X), ldx, s,
+                            &sync));
+  launch_naive_cluster_batch(s, table_d, count, run.threshold, run.adaptation, run.verdict);
+  SC_TRY(check_last(h, "batched naive clusterer launch"));
+  SC_HIP(h, hipMemcpyAsync(const_cast<char*>(back_h), back_d,
+                           back_cent + back_ints * sizeof(int), hipMemcpyDeviceToHost, s));
+  SC_HIP(h, hipStreamSynchronize(s));
+  if (run.verdict) {
+    int bad_index = -1;  // (the first of the batch, whatever the wave's order)
+    for (int i = 0; i < count; ++i)
+      if (ints_h[ints_of[i] + 2] != 0 && (bad_index < 0 || wave[i]->index < bad_index))
+        bad_index = wave[i]->index;
+    if (bad_index >= 0) return fail(h, SC_ERR_INVALID, bad_rows_message(bad_index));
+  }
+  for (int i = 0; i < count; ++i) {
+    NaiveMember& m = *wave[i];
+    const int* mine = ints_h + ints_of[i];
+    m.dev_rows = keep ? table_h[i].X : nullptr;
+    if (run.verdict) {
+      m.single = mine[0];
+      m.stopped_at = mine[1];
+      continue;
+    }
+    m.ints.assign(mine, mine + m.back_ints(false));
+    if (m.want_centroids) {
+      const double* c = reinterpret_cast<const double*>(back_h + cent_of[i]);
+      m.cent.assign(c, c + (size_t)m.k() * d);
+    }
+  }
   return SC_OK;
 }
 
-extern "C" int sc_batch_ahc(sc_handle h, const sc_array* xs, int count, int linkage,
-                            int n_clusters, double distance_threshold, int64_t* const* labels,
-                            double* const* centroids) {
-  if (!h) return SC_ERR_INVALID;
-  if (!xs || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
-  if (linkage != SC_LINKAGE_COMPLETE && linkage != SC_LINKAGE_AVERAGE)
-    return fail(h, SC_ERR_INVALID, "linkage must be complete or average");
-  SC_HIP(h, hipSetDevice(h->device));
-  bool device_source = false;
-  std::vector<int> ns;
-  int d = 0;
-  SC_TRY(validate_batch_arrays(h, xs, count, &ns, &d, &device_source, labels));
-  std::vector<ReduceMember> members(count);
-  for (int i = 0; i < count; ++i) {
-    if (ns[i] < 2) return too_few_rows(h, i, ns[i]);
-    if (n_clusters < 0 || n_clusters > ns[i])
-      return fail(h, SC_ERR_INVALID, "utterance " + std::to_string(i) +
-                                         ": Cannot extract more clusters than samples");
-    ReduceMember& m = members[i];
-    m.index = i;
-    m.n = ns[i];
-    m.linkage = linkage;
-    m.n_clusters = n_clusters;
-    m.threshold = distance_threshold;
-    m.host_centroids = centroids ? centroids[i] : nullptr;
+// Every member of `members` (checked: n >= 1).  `keep` (may be null): as fallback_verdicts', the
+// rows' blocks of the waves stay there while they add up to at most half a wave's budget.
+int naive_members(sc_handle h, const sc_array* xs, int d, std::vector<NaiveMember>* members,
+                  const NaiveRun& run, DeviceBlocks* keep) {
+  std::vector<int> order(members->size());
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(),
+                   [&](int a, int b) { return (*members)[a].n > (*members)[b].n; });
+  size_t at = 0, kept = 0;
+  while (at < order.size()) {
+    size_t budget = h->reduce_wave_bytes;
+    if (budget == 0) {
+      size_t free_bytes = 0, device_bytes = 0;
+      SC_HIP(h, hipMemGetInfo(&free_bytes, &device_bytes));
+      budget = (size_t)(kReduceWaveShare * (double)free_bytes);
+    }
+    std::vector<NaiveMember*> wave;
+    size_t bytes = 2 * 256, rows = 0;  // (the slabs' alignment)
+    while (at < order.size()) {
+      NaiveMember* m = &(*members)[order[at]];
+      // (the longest remaining member always goes: alone when it exceeds the budget)
+      if (!wave.empty() && bytes + m->wave_bytes(d, run.verdict) > budget) break;
+      bytes += m->wave_bytes(d, run.verdict);
+      rows += m->rows_bytes(d);
+      wave.push_back(m);
+      ++at;
+    }
+    const bool stay = keep && kept + rows <= budget / 2;
+    SC_TRY(naive_wave(h, xs, d, wave, run, stay ? keep : nullptr));
+    if (stay) kept += rows;
   }
-  DeviceBlocks blocks;
-  return reduce_members(h, xs, d, &members, labels, &blocks, false);
+  return SC_OK;
 }
 
-extern "C" int sc_predict_batch_reduced(sc_handle h, const sc_array* xs, int count,
-                                        const sc_config* cfg, int max_spectral_size,
-                                        int spectral_min_embeddings,
-                                        double agglomerative_threshold, int64_t* const* labels,
-                                        sc_diag* diags, int group, int32_t* kinds) {
-  if (!h) return SC_ERR_INVALID;
-  if (!xs || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
-  if (group < 2)
-    return fail(h, SC_ERR_INVALID, "sc_predict_batch_reduced is the grouped form: group >= 2");
-  if (max_spectral_size < 0 || max_spectral_size == 1)
-    return fail(h, SC_ERR_INVALID, "max_spectral_size should be a relatively big number");
-  // (the spectral run of the centroids must not be a fallback member itself)
-  if (max_spectral_size > 0 && max_spectral_size < spectral_min_embeddings)
-    return fail(h, SC_ERR_INVALID,
-                "max_spectral_size must not be below spectral_min_embeddings in a batch");
-  SC_TRY(validate_config(h, cfg));
-  SC_HIP(h, hipSetDevice(h->device));
-  bool device_source = false;
-  std::vector<int> ns;
-  int d = 0;
-  SC_TRY(validate_batch_arrays(h, xs, count, &ns, &d, &device_source, labels));
-  SC_TRY(sc_clear_constraint(h));  // a batch carries none
-  if (count == 0) {
-    h->last_routes.clear();
-    return SC_OK;
-  }
+// NaiveClusterer.__init__'s check (naive_clusterer.py:36-37)
+int validate_naive_thresholds(sc_handle h, double threshold, double adaptation) {
+  if (adaptation < threshold)
+    return fail(h, SC_ERR_INVALID, "adaptation_threshold cannot be smaller than threshold");
+  return SC_OK;
+}
+
+// what clusters the fallback utterances (kind 2) of sc_predict_batch_reduced[_naive]
+struct FallbackSpec {
+  bool naive = false;
+  double threshold = 0.0;   // agglomerative: the distance threshold; naive: the similarity one
+  double adaptation = 0.0;  // naive only
+};
+
+// The body of sc_predict_batch_reduced and sc_predict_batch_reduced_naive (their arguments are
+// checked by predict_batch_reduced_entry below).
+int predict_batch_reduced_body(sc_handle h, const sc_array* xs, int count, const sc_config* cfg,
+                               int max_spectral_size, int spectral_min_embeddings,
+                               const FallbackSpec& fallback, int64_t* const* labels,
+                               sc_diag* diags, int group, int32_t* kinds,
+                               const std::vector<int>& ns, int d) {
   std::vector<int32_t> kind(count, 0);
   std::vector<ReduceMember> members;
+  std::vector<NaiveMember> naive;
   std::vector<std::vector<int64_t>> pre(count);  // kind 1: the rows' pre-cluster labels
   std::vector<int64_t*> ahc_labels(count, nullptr);
   for (int i = 0; i < count; ++i) {
@@ -597,10 +733,17 @@ extern "C" int sc_predict_batch_reduced(sc_handle h, const sc_array* xs, int cou
     m.index = i;
     m.n = ns[i];
     if (ns[i] < spectral_min_embeddings) {
-      if (ns[i] < 2) return too_few_rows(h, i, ns[i]);
       kind[i] = 2;
+      if (fallback.naive) {  // (a single row is fine: label 0)
+        NaiveMember nm;
+        nm.index = i;
+        nm.n = ns[i];
+        naive.push_back(nm);
+        continue;
+      }
+      if (ns[i] < 2) return too_few_rows(h, i, ns[i]);
       m.linkage = SC_LINKAGE_AVERAGE;
-      m.threshold = agglomerative_threshold;
+      m.threshold = fallback.threshold;
       ahc_labels[i] = labels[i];
     } else if (max_spectral_size > 0 && ns[i] > max_spectral_size) {
       kind[i] = 1;
@@ -617,6 +760,14 @@ extern "C" int sc_predict_batch_reduced(sc_handle h, const sc_array* xs, int cou
   if (kinds) std::copy(kind.begin(), kind.end(), kinds);
   DeviceBlocks blocks;  // the centroids live in them until the spectral batch has returned
   SC_TRY(reduce_members(h, xs, d, &members, ahc_labels.data(), &blocks, true));
+  if (!naive.empty()) {
+    NaiveRun run;
+    run.threshold = fallback.threshold;
+    run.adaptation = fallback.adaptation;
+    SC_TRY(naive_members(h, xs, d, &naive, run, nullptr));
+    for (const NaiveMember& m : naive)
+      std::copy(m.ints.begin(), m.ints.begin() + m.n, labels[m.index]);
+  }
   // ONE grouped batch: the rows of kind 0, the centroids of kind 1
   std::vector<int> at;  // position in that batch -> utterance
   std::vector<sc_array> sub;
@@ -671,6 +822,220 @@ extern "C" int sc_predict_batch_reduced(sc_handle h, const sc_array* xs, int cou
   return SC_OK;
 }
 
+// the checks of both forms, then the body
+int predict_batch_reduced_entry(sc_handle h, const char* name, const sc_array* xs, int count,
+                                const sc_config* cfg, int max_spectral_size,
+                                int spectral_min_embeddings, const FallbackSpec& fallback,
+                                int64_t* const* labels, sc_diag* diags, int group,
+                                int32_t* kinds) {
+  if (!xs || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  if (group < 2)
+    return fail(h, SC_ERR_INVALID, std::string(name) + " is the grouped form: group >= 2");
+  if (max_spectral_size < 0 || max_spectral_size == 1)
+    return fail(h, SC_ERR_INVALID, "max_spectral_size should be a relatively big number");
+  // (the spectral run of the centroids must not be a fallback member itself)
+  if (max_spectral_size > 0 && max_spectral_size < spectral_min_embeddings)
+    return fail(h, SC_ERR_INVALID,
+                "max_spectral_size must not be below spectral_min_embeddings in a batch");
+  if (fallback.naive) SC_TRY(validate_naive_thresholds(h, fallback.threshold, fallback.adaptation));
+  SC_TRY(validate_config(h, cfg));
+  SC_HIP(h, hipSetDevice(h->device));
+  bool device_source = false;
+  std::vector<int> ns;
+  int d = 0;
+  SC_TRY(validate_batch_arrays(h, xs, count, &ns, &d, &device_source, labels));
+  SC_TRY(sc_clear_constraint(h));  // a batch carries none
+  if (count == 0) {
+    h->last_routes.clear();
+    return SC_OK;
+  }
+  return predict_batch_reduced_body(h, xs, count, cfg, max_spectral_size, spectral_min_embeddings,
+                                    fallback, labels, diags, group, kinds, ns, d);
+}
+
+// One verdict of the FallbackClusterer condition per utterance, whichever clusterer gave it
+struct SingleVerdict {
+  int single = 0;
+  const double* dev_rows = nullptr;  // the widened rows where a wave left them, or nullptr
+};
+
+// The second half of sc_predict_batch_single_fallback and sc_predict_batch_single_naive: zeros
+// for the single utterances, ONE grouped batch over the others.
+int predict_batch_single_rest(sc_handle h, const sc_array* xs, int count, const sc_config* cfg,
+                              const std::vector<SingleVerdict>& verdicts,
+                              const std::vector<int>& ns, int d, int64_t* const* labels,
+                              sc_diag* diags, int group, int32_t* single) {
+  std::vector<int> at;  // position in that batch -> utterance
+  std::vector<sc_array> sub;
+  std::vector<int> sub_ns;
+  std::vector<int64_t*> sub_labels;
+  for (int i = 0; i < count; ++i) {
+    const SingleVerdict& v = verdicts[i];
+    if (single) single[i] = v.single;
+    if (v.single) {  // predict(): np.array([0] * n), before the affinity is built
+      std::fill(labels[i], labels[i] + ns[i], (int64_t)0);
+      continue;
+    }
+    sc_array a = xs[i];
+    if (v.dev_rows) {  // the widened rows (exact: the labels are those of the caller's array)
+      a.data = v.dev_rows;
+      a.dtype = SC_DTYPE_F64;
+      a.location = SC_MEM_DEVICE;
+      a.row_stride = round_up(d, 16);
+      a.col_stride = 1;
+    }
+    at.push_back(i);
+    sub.push_back(a);
+    sub_ns.push_back(ns[i]);
+    sub_labels.push_back(labels[i]);
+  }
+  const int sub_count = (int)at.size();
+  std::vector<sc_diag> sub_diags(diags ? sub_count : 0);
+  std::vector<int32_t> routes(count, SC_BATCH_ROUTE_FALLBACK);
+  if (sub_count > 0) {
+    // (every wave ended drained; what the caller ordered before this handle's stream is done
+    //  before the streams of the batch read a device source)
+    SC_HIP(h, hipStreamSynchronize(h->stream));
+    SC_TRY(predict_batch_grouped_impl(h, sub.data(), sub_ns.data(), d, sub_count, cfg,
+                                      sub_labels.data(), diags ? sub_diags.data() : nullptr,
+                                      group));
+    for (int z = 0; z < sub_count; ++z) routes[at[z]] = h->last_routes[z];
+  }
+  h->last_routes = routes;
+  if (diags) {
+    for (int i = 0; i < count; ++i) memset(&diags[i], 0, sizeof(sc_diag));
+    for (int z = 0; z < sub_count; ++z) diags[at[z]] = sub_diags[z];
+  }
+  return SC_OK;
+}
+
+}  // namespace
+
+extern "C" int sc_set_reduce_wave_bytes(sc_handle h, size_t bytes) {
+  if (!h) return SC_ERR_INVALID;
+  h->reduce_wave_bytes = bytes;
+  return SC_OK;
+}
+
+extern "C" int sc_batch_ahc(sc_handle h, const sc_array* xs, int count, int linkage,
+                            int n_clusters, double distance_threshold, int64_t* const* labels,
+                            double* const* centroids) {
+  if (!h) return SC_ERR_INVALID;
+  if (!xs || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  if (linkage != SC_LINKAGE_COMPLETE && linkage != SC_LINKAGE_AVERAGE)
+    return fail(h, SC_ERR_INVALID, "linkage must be complete or average");
+  SC_HIP(h, hipSetDevice(h->device));
+  bool device_source = false;
+  std::vector<int> ns;
+  int d = 0;
+  SC_TRY(validate_batch_arrays(h, xs, count, &ns, &d, &device_source, labels));
+  std::vector<ReduceMember> members(count);
+  for (int i = 0; i < count; ++i) {
+    if (ns[i] < 2) return too_few_rows(h, i, ns[i]);
+    if (n_clusters < 0 || n_clusters > ns[i])
+      return fail(h, SC_ERR_INVALID, "utterance " + std::to_string(i) +
+                                         ": Cannot extract more clusters than samples");
+    ReduceMember& m = members[i];
+    m.index = i;
+    m.n = ns[i];
+    m.linkage = linkage;
+    m.n_clusters = n_clusters;
+    m.threshold = distance_threshold;
+    m.host_centroids = centroids ? centroids[i] : nullptr;
+  }
+  DeviceBlocks blocks;
+  return reduce_members(h, xs, d, &members, labels, &blocks, false);
+}
+
+extern "C" int sc_predict_batch_reduced(sc_handle h, const sc_array* xs, int count,
+                                        const sc_config* cfg, int max_spectral_size,
+                                        int spectral_min_embeddings,
+                                        double agglomerative_threshold, int64_t* const* labels,
+                                        sc_diag* diags, int group, int32_t* kinds) {
+  if (!h) return SC_ERR_INVALID;
+  FallbackSpec fallback;
+  fallback.threshold = agglomerative_threshold;
+  return predict_batch_reduced_entry(h, "sc_predict_batch_reduced", xs, count, cfg,
+                                     max_spectral_size, spectral_min_embeddings, fallback, labels,
+                                     diags, group, kinds);
+}
+
+extern "C" int sc_predict_batch_reduced_naive(sc_handle h, const sc_array* xs, int count,
+                                              const sc_config* cfg, int max_spectral_size,
+                                              int spectral_min_embeddings, double naive_threshold,
+                                              double naive_adaptation_threshold,
+                                              int64_t* const* labels, sc_diag* diags, int group,
+                                              int32_t* kinds) {
+  if (!h) return SC_ERR_INVALID;
+  FallbackSpec fallback;
+  fallback.naive = true;
+  fallback.threshold = naive_threshold;
+  fallback.adaptation = naive_adaptation_threshold;
+  return predict_batch_reduced_entry(h, "sc_predict_batch_reduced_naive", xs, count, cfg,
+                                     max_spectral_size, spectral_min_embeddings, fallback, labels,
+                                     diags, group, kinds);
+}
+
+extern "C" int sc_batch_naive_cluster(sc_handle h, const sc_array* xs, int count, double threshold,
+                                      double adaptation_threshold, int64_t* const* labels,
+                                      int32_t* n_clusters, double* const* centroids,
+                                      int32_t* const* counts) {
+  if (!h) return SC_ERR_INVALID;
+  if (!xs || !labels || !n_clusters || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  SC_TRY(validate_naive_thresholds(h, threshold, adaptation_threshold));
+  SC_HIP(h, hipSetDevice(h->device));
+  bool device_source = false;
+  std::vector<int> ns;
+  int d = 0;
+  SC_TRY(validate_batch_arrays(h, xs, count, &ns, &d, &device_source, labels));
+  std::vector<NaiveMember> members(count);
+  for (int i = 0; i < count; ++i) {
+    members[i].index = i;
+    members[i].n = ns[i];
+    members[i].want_centroids = centroids && centroids[i];
+  }
+  NaiveRun run;
+  run.threshold = threshold;
+  run.adaptation = adaptation_threshold;
+  SC_TRY(naive_members(h, xs, d, &members, run, nullptr));
+  for (const NaiveMember& m : members) {  // (nothing is written unless every wave succeeded)
+    const int i = m.index, k = m.k();
+    std::copy(m.ints.begin(), m.ints.begin() + m.n, labels[i]);
+    n_clusters[i] = k;
+    if (counts && counts[i]) std::copy(m.ints.begin() + m.n, m.ints.begin() + m.n + k, counts[i]);
+    if (m.want_centroids) std::copy(m.cent.begin(), m.cent.end(), centroids[i]);
+  }
+  return SC_OK;
+}
+
+extern "C" int sc_batch_naive_check(sc_handle h, const sc_array* xs, int count, double threshold,
+                                    double adaptation_threshold, int32_t* single,
+                                    int32_t* stopped_at) {
+  if (!h) return SC_ERR_INVALID;
+  if (!xs || !single || !stopped_at || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  SC_TRY(validate_naive_thresholds(h, threshold, adaptation_threshold));
+  SC_HIP(h, hipSetDevice(h->device));
+  bool device_source = false;
+  std::vector<int> ns;
+  int d = 0;
+  SC_TRY(validate_batch_arrays(h, xs, count, &ns, &d, &device_source));
+  std::vector<NaiveMember> members(count);
+  for (int i = 0; i < count; ++i) {
+    members[i].index = i;
+    members[i].n = ns[i];
+  }
+  NaiveRun run;
+  run.threshold = threshold;
+  run.adaptation = adaptation_threshold;
+  run.verdict = true;
+  SC_TRY(naive_members(h, xs, d, &members, run, nullptr));
+  for (const NaiveMember& m : members) {  // (nothing is written unless every wave succeeded)
+    single[m.index] = m.single;
+    stopped_at[m.index] = m.stopped_at;
+  }
+  return SC_OK;
+}
+
 extern "C" int sc_batch_fallback_check(sc_handle h, const sc_array* xs, int count,
                                        double distance_threshold, double* heights,
                                        int32_t* single) {
@@ -717,47 +1082,53 @@ extern "C" int sc_predict_batch_single_fallback(sc_handle h, const sc_array* xs,
   // group at a time); the rows of the waves stay on the device for the survivors
   DeviceBlocks rows;
   SC_TRY(fallback_verdicts(h, xs, d, &members, distance_threshold, &rows));
-  // ONE grouped batch over the utterances of several clusters
-  std::vector<int> at;  // position in that batch -> utterance
-  std::vector<sc_array> sub;
-  std::vector<int> sub_ns;
-  std::vector<int64_t*> sub_labels;
+  std::vector<SingleVerdict> verdicts(count);
   for (const VerdictMember& m : members) {
-    const int i = m.index;
-    if (single) single[i] = m.single;
-    if (m.single) {  // predict(): np.array([0] * n), before the affinity is built
-      std::fill(labels[i], labels[i] + ns[i], (int64_t)0);
-      continue;
-    }
-    sc_array a = xs[i];
-    if (m.dev_rows) {  // the widened rows (exact: the labels are those of the caller's array)
-      a.data = m.dev_rows;
-      a.dtype = SC_DTYPE_F64;
-      a.location = SC_MEM_DEVICE;
-      a.row_stride = round_up(d, 16);
-      a.col_stride = 1;
-    }
-    at.push_back(i);
-    sub.push_back(a);
-    sub_ns.push_back(ns[i]);
-    sub_labels.push_back(labels[i]);
+    verdicts[m.index].single = m.single;
+    verdicts[m.index].dev_rows = m.dev_rows;
   }
-  const int sub_count = (int)at.size();
-  std::vector<sc_diag> sub_diags(diags ? sub_count : 0);
-  std::vector<int32_t> routes(count, SC_BATCH_ROUTE_FALLBACK);
-  if (sub_count > 0) {
-    // (every wave ended drained; what the caller ordered before this handle's stream is done
-    //  before the streams of the batch read a device source)
-    SC_HIP(h, hipStreamSynchronize(h->stream));
-    SC_TRY(predict_batch_grouped_impl(h, sub.data(), sub_ns.data(), d, sub_count, cfg,
-                                      sub_labels.data(), diags ? sub_diags.data() : nullptr,
-                                      group));
-    for (int z = 0; z < sub_count; ++z) routes[at[z]] = h->last_routes[z];
+  return predict_batch_single_rest(h, xs, count, cfg, verdicts, ns, d, labels, diags, group,
+                                   single);
+}
+
+extern "C" int sc_predict_batch_single_naive(sc_handle h, const sc_array* xs, int count,
+                                             const sc_config* cfg, double naive_threshold,
+                                             double naive_adaptation_threshold,
+                                             int64_t* const* labels, sc_diag* diags, int group,
+                                             int32_t* single) {
+  if (!h) return SC_ERR_INVALID;
+  if (!xs || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  if (group < 2)
+    return fail(h, SC_ERR_INVALID, "sc_predict_batch_single_naive is the grouped form: group >= 2");
+  SC_TRY(validate_naive_thresholds(h, naive_threshold, naive_adaptation_threshold));
+  SC_TRY(validate_config(h, cfg));
+  SC_HIP(h, hipSetDevice(h->device));
+  bool device_source = false;
+  std::vector<int> ns;
+  int d = 0;
+  SC_TRY(validate_batch_arrays(h, xs, count, &ns, &d, &device_source, labels));
+  SC_TRY(sc_clear_constraint(h));  // a batch carries none
+  if (count == 0) {
+    h->last_routes.clear();
+    return SC_OK;
   }
-  h->last_routes = routes;
-  if (diags) {
-    for (int i = 0; i < count; ++i) memset(&diags[i], 0, sizeof(sc_diag));
-    for (int z = 0; z < sub_count; ++z) diags[at[z]] = sub_diags[z];
+  std::vector<NaiveMember> members(count);
+  for (int i = 0; i < count; ++i) {  // (an utterance of one row is single)
+    members[i].index = i;
+    members[i].n = ns[i];
   }
-  return SC_OK;
+  NaiveRun run;
+  run.threshold = naive_threshold;
+  run.adaptation = naive_adaptation_threshold;
+  run.verdict = true;
+  run.check_rows = true;  // predict() builds the affinity of such an utterance and raises
+  DeviceBlocks rows;  // the rows of the waves stay on the device for the survivors
+  SC_TRY(naive_members(h, xs, d, &members, run, &rows));
+  std::vector<SingleVerdict> verdicts(count);
+  for (const NaiveMember& m : members) {
+    verdicts[m.index].single = m.single;
+    verdicts[m.index].dev_rows = m.dev_rows;
+  }
+  return predict_batch_single_rest(h, xs, count, cfg, verdicts, ns, d, labels, diags, group,
+                                   single);
 }

@@ -11,19 +11,10 @@
 #include <hip/hip_runtime.h>
 
 #include "gmm_common.h"
+#include "naive_common.h"
 #include "sc_internal.h"
 
 namespace sc {
-
-__device__ __forceinline__ double block_sum_256(double v, double* s_red) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[wave] = v;
-  __syncthreads();
-  return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-}
 
 // state: centroids (row-major, capacity >= k0 + n), counts, *n_centroids (in/out)
 __global__ __launch_bounds__(256) void k_naive_cluster(const double* __restrict__ X, int n, int d,
@@ -47,21 +38,11 @@ __global__ __launch_bounds__(256) void k_naive_cluster(const double* __restrict_
       __syncthreads();
       continue;
     }
-    double ee = 0.0;
-    for (int f = tid; f < d; f += 256) ee += e[f] * e[f];
-    const double enorm = sqrt(block_sum_256(ee, s_red));
+    const double enorm = naive_norm(e, d, s_red);
     double best = -__builtin_huge_val();
     int label = 0;
     for (int c = 0; c < k; ++c) {
-      const double* cv = centroids + (size_t)c * d;
-      double dot = 0.0, cc = 0.0;
-      for (int f = tid; f < d; f += 256) {
-        dot += cv[f] * e[f];
-        cc += cv[f] * cv[f];
-      }
-      dot = block_sum_256(dot, s_red);
-      cc = block_sum_256(cc, s_red);
-      const double sim = dot / (sqrt(cc) * enorm);  // :19-22
+      const double sim = naive_cosine(centroids + (size_t)c * d, e, d, enorm, s_red);  // :19-22
       if (sim > best) {  // np.argmax: first maximum
         best = sim;
         label = c;
@@ -77,8 +58,7 @@ __global__ __launch_bounds__(256) void k_naive_cluster(const double* __restrict_
     } else {
       if (best > adapt_threshold) {  // merge, :13-17
         const double cnt = (double)counts[label];
-        double* cv = centroids + (size_t)label * d;
-        for (int f = tid; f < d; f += 256) cv[f] = (cv[f] * cnt + e[f]) / (cnt + 1.0);
+        naive_merge(centroids + (size_t)label * d, e, d, cnt);
         __syncthreads();
         if (tid == 0) counts[label] += 1;
       }

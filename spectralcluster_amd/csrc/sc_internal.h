@@ -802,6 +802,24 @@ void launch_batch_centroids(hipStream_t s, const AhcBatchItem* table, int first,
 void launch_naive_cluster(hipStream_t s, const double* X, int n, int d, double threshold,
                           double adapt_threshold, double* centroids, int* counts,
                           int* n_centroids, int* labels);
+// One member of a wave of naive clusterings from the empty state (naive_batch.hip; host side
+// batch_reduce.hip): workgroup z of the launch works on table[z], a table in device memory.
+struct NaiveBatchItem {
+  const double* X;  // n x ldx rows as ingested
+  double* cent;     // labels form: n x d (pitch d), the first n_clusters rows written;
+                    // verdict form: d doubles of scratch
+  int* counts;      // labels form: n, the first n_clusters written
+  int* labels;      // labels form: n
+  int* out;         // labels form: {n_clusters}; verdict form: {single, stopped_at}
+  int* bad;         // verdict form: the member's word, set when a row is zero or non-finite by the
+                    // rule of launch_normalize_rows (nullptr: not looked for)
+  int n, ldx, d, pad;
+};
+// NaiveClusterer(threshold, adapt_threshold).predict of every member, bit for bit what
+// launch_naive_cluster gives from *n_centroids = 0; `verdict`: the walk ends at the row that would
+// open a second centroid (stopped_at: its index, or n with single = 1)
+void launch_naive_cluster_batch(hipStream_t s, const NaiveBatchItem* table, int count,
+                                double threshold, double adapt_threshold, bool verdict);
 // out = {min, min of the first superdiagonal, mean, population std}; partial: n x 8 doubles
 void launch_affinity_stats(hipStream_t s, const double* a, int n, int ld, double* partial,
                            double* out);

@@ -92,6 +92,81 @@ class NaiveClusterer:
     self._counts = counts[:found.value].copy()
     return labels
 
+  def _batch_call(self, utterances: typing.Sequence, call):
+    """`call(handle, arrays, count, rows)` on the described utterances (anything
+    SpectralClusterer.predict_batch takes), released afterwards."""
+    from spectralcluster_amd import _dlpack  # (it imports this module's siblings)
+    for u in utterances:
+      if isinstance(u, np.ndarray) and u.ndim != 2:
+        raise ValueError("embeddings must be 2-dimensional")
+    handle = _lib.default_handle()
+    sources = []
+    try:
+      for u in utterances:
+        sources.append(_dlpack.describe(u, lambda: handle))
+      d = sources[0].shape[1]
+      if any(src.shape[1] != d for src in sources):
+        raise ValueError("all utterances must be (n_i, d) with the same d")
+      count = len(sources)
+      arrays = (_lib.ScArray * count)(*[src.array for src in sources])
+      return call(handle, arrays, count, [src.shape[0] for src in sources])
+    finally:
+      for src in sources:
+        src.release()
+
+  def predict_batch(self, utterances: typing.Sequence,
+                    return_state: bool = False):
+    """A fresh `NaiveClusterer(threshold, adaptation_threshold).predict(u)` for every
+    utterance -- NumPy arrays and DLPack objects, float64 / float32 / float16 / bfloat16, host or
+    device memory, strided, mixed freely, the same number of columns -- in ONE
+    `sc_batch_naive_cluster` call: a workgroup per utterance, one launch per wave.  Returns the
+    list of int64 label arrays, bit for bit predict()'s decisions; with `return_state` also the
+    lists of centroid arrays (k_i x d) and count arrays.  Every utterance starts from the empty
+    state and this object's own online state is left untouched."""
+    if not utterances:
+      return ([], [], []) if return_state else []
+
+    def call(handle, arrays, count, rows):
+      d = int(arrays[0].cols)
+      labels = [np.empty(n, dtype=np.int64) for n in rows]
+      lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
+      found = (ctypes.c_int32 * count)()
+      cp, kp, centroids, counts = None, None, None, None
+      if return_state:
+        centroids = [np.empty((n, d), dtype=np.float64) for n in rows]
+        counts = [np.empty(n, dtype=np.int32) for n in rows]
+        cp = (ctypes.POINTER(ctypes.c_double) * count)(*[_lib.as_double_p(c) for c in centroids])
+        kp = (ctypes.POINTER(ctypes.c_int32) * count)(
+            *[c.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) for c in counts])
+      handle.check(handle.lib.sc_batch_naive_cluster(
+          handle.raw, arrays, count, float(self.threshold), float(self.adaptation_threshold),
+          lp, found, cp, kp), ValueError)
+      if not return_state:
+        return labels
+      return (labels, [c[:k].copy() for c, k in zip(centroids, found)],
+              [c[:k].copy() for c, k in zip(counts, found)])
+
+    return self._batch_call(utterances, call)
+
+  def check_single_batch(self, utterances: typing.Sequence):
+    """Does a fresh predict(u) end with ONE centroid? -- for every utterance (what predict_batch
+    takes) in one `sc_batch_naive_check` call, each walk ending at the row that would open a
+    second centroid.  Returns (single, stopped_at): a bool array, and that row's index per
+    utterance (its number of rows when it is single)."""
+    if not utterances:
+      return np.zeros(0, dtype=bool), np.zeros(0, dtype=np.int32)
+
+    def call(handle, arrays, count, rows):
+      single = np.zeros(count, dtype=np.int32)
+      stopped = np.zeros(count, dtype=np.int32)
+      as_p = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+      handle.check(handle.lib.sc_batch_naive_check(
+          handle.raw, arrays, count, float(self.threshold), float(self.adaptation_threshold),
+          as_p(single), as_p(stopped)), ValueError)
+      return single.astype(bool), stopped
+
+    return self._batch_call(utterances, call)
+
   def predict_next(self, embedding: np.ndarray) -> int:
     return int(self.predict(np.asarray(embedding, dtype=np.float64)[None, :])[0])
 

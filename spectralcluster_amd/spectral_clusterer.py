@@ -30,6 +30,7 @@ from spectralcluster_amd import constraint as constraint_lib
 from spectralcluster_amd import custom_distance_kmeans
 from spectralcluster_amd import fallback_clusterer
 from spectralcluster_amd import laplacian
+from spectralcluster_amd import naive_clusterer
 from spectralcluster_amd import refinement
 from spectralcluster_amd import utils
 
@@ -385,7 +386,8 @@ class SpectralClusterer:
                     group: typing.Optional[int] = None,
                     constraint_matrices: typing.Optional[typing.Sequence] = None,
                     autotune_from_entry_state: bool = False,
-                    batch_fallback_condition: bool = False
+                    batch_fallback_condition: bool = False,
+                    batch_naive_fallback: bool = False
                     ) -> typing.List[np.ndarray]:
     """Independent predict() calls (the reference has no batch API: a batch is a
     Python loop).
@@ -472,7 +474,8 @@ class SpectralClusterer:
     utterance).  Raised before anything is launched: predict()'s ValueError for a
     `max_spectral_size` that is not above `max_clusters` / `min_clusters`, and for a fallback
     utterance of one row.  An utterance with a zero or non-finite row raises a ValueError that
-    names its index.  Everything else -- the `Naive` fallback, `min_clusters=1`, constraints,
+    names its index.  Everything else -- the `Naive` fallback (but see
+    `batch_naive_fallback`), `min_clusters=1`, constraints,
     AutoTune, `group=1`, `streams` -- stays the per-utterance loop (routes all 0).
 
     `min_clusters=1` (the streaming regime: the clusterer may say "one speaker"): the batch is
@@ -505,13 +508,31 @@ class SpectralClusterer:
     otherwise (route 0, 1 or 2); `last_batch_single` lists the verdicts.  An utterance of one
     row raises predict()'s ValueError before anything is launched, one with a zero or non-finite
     row a ValueError that names its index.  Anything else keeps the loop, flag or no flag.
+
+    `batch_naive_fallback` (default False: the `Naive` fallback type -- what a default
+    `FallbackOptions` selects -- keeps the loop in both regimes above).  With it
+      * a batch that is the `sc_predict_batch_reduced` call but for a fallback utterance meeting
+        the `Naive` type is ONE `sc_predict_batch_reduced_naive` call: the fallback utterances
+        are walked by the naive clusterer from the empty state, a workgroup each in one launch
+        per wave, with `naive_threshold` / `naive_adaptation_threshold` (None: the threshold).
+        `last_batch_reduced`, `last_batch_routes` (3 for a fallback utterance), `last_batch_diags`
+        and the result dtypes are as above; a fallback utterance of one row is fine (label 0);
+      * together with `batch_fallback_condition`, a `min_clusters=1` batch under the
+        `FallbackClusterer` condition with the `Naive` type is ONE `sc_predict_batch_single_naive`
+        call under every other clause of that flag: the verdict of an utterance is "the naive walk
+        ends with one centroid", and its work ends at the row that would open a second one.  An
+        utterance of one row is single; one with a zero or non-finite row raises a ValueError that
+        names its index.
+    Labels equal predict()'s: the batch kernel shares its arithmetic with the one predict() runs.
+    A threshold pair that `NaiveClusterer` rejects raises its ValueError before anything is
+    launched.  With the `Agglomerative` type the flag does nothing.
     """
     self.last_batch_single = None
     if autotune_from_entry_state and self.autotune is not None:
       return self._predict_batch_entry_state(utterances, constraint_matrices, streams, group)
     if (batch_fallback_condition and streams is None and (group is None or int(group) > 1) and
         (constraint_matrices is None or self.constraint_options is None) and
-        self._fallback_condition_covers()):
+        self._fallback_condition_covers(naive=batch_naive_fallback)):
       if constraint_matrices is not None and len(constraint_matrices) != len(utterances):
         raise ValueError("constraint_matrices must be as long as the batch")
       return self._predict_batch_single_fallback(utterances, 16 if group is None else int(group))
@@ -550,7 +571,7 @@ class SpectralClusterer:
           return [self.predict(u, c) for u, c in zip(utterances, constraint_matrices)]
         banded = list(constraint_matrices)
     if (not library_batch and banded is None and
-        self._reduced_batch_covers(utterances, streams, group)):
+        self._reduced_batch_covers(utterances, streams, group, naive=batch_naive_fallback)):
       return self._predict_batch_reduced(utterances, 16 if group is None else int(group))
     if group is None:
       group = 16 if streams is None else 0
@@ -791,17 +812,32 @@ class SpectralClusterer:
         self.affinity_function is not utils.compute_affinity_matrix or
         self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans)
 
-  def _fallback_condition_covers(self, min_embeddings_met: bool = False) -> bool:
+  def _naive_fallback(self) -> bool:
+    return (self.fallback_options.fallback_clusterer_type ==
+            fallback_clusterer.FallbackClustererType.Naive)
+
+  def _naive_thresholds(self) -> typing.Tuple[float, float]:
+    """(threshold, adaptation_threshold) as `NaiveClusterer` holds them -- None adaptation is
+    the threshold -- or its ValueError."""
+    c = naive_clusterer.NaiveClusterer(
+        threshold=self.fallback_options.naive_threshold,
+        adaptation_threshold=self.fallback_options.naive_adaptation_threshold)
+    return float(c.threshold), float(c.adaptation_threshold)
+
+  def _fallback_condition_covers(self, min_embeddings_met: bool = False,
+                                 naive: bool = False) -> bool:
     """Is this clusterer one whose predict() `sc_predict_batch_single_fallback` reproduces?
     `min_clusters == 1` decided by the FallbackClusterer condition with the agglomerative
     fallback, and otherwise what `_library_batch_covers` asks, with cosine k-means.
-    `min_embeddings_met` as there."""
+    `min_embeddings_met` as there.  `naive`: the Naive fallback type is covered as well (the
+    caller then makes the `sc_predict_batch_single_naive` call)."""
     options = self.fallback_options
     if not (self.min_clusters == 1 and
             options.single_cluster_condition ==
             fallback_clusterer.SingleClusterCondition.FallbackClusterer and
-            options.fallback_clusterer_type ==
-            fallback_clusterer.FallbackClustererType.Agglomerative):
+            (options.fallback_clusterer_type ==
+             fallback_clusterer.FallbackClustererType.Agglomerative or
+             (naive and self._naive_fallback()))):
       return False
     if (self.autotune is not None or self.max_spectral_size is not None or
         (options.spectral_min_embeddings > 1 and not min_embeddings_met) or
@@ -814,22 +850,30 @@ class SpectralClusterer:
       return False  # (predict() raises what it raises today)
 
   def _single_fallback_call(self, handle: _lib.Handle, arrays: typing.Sequence[_lib.ScArray],
-                            group: int) -> typing.List[np.ndarray]:
-    """ONE `sc_predict_batch_single_fallback` call on described sources: predict()'s results,
-    `last_batch_single` / `last_batch_routes` / `last_batch_diags` filled."""
+                            group: int, naive: bool = False) -> typing.List[np.ndarray]:
+    """ONE `sc_predict_batch_single_fallback` call (`naive`: `sc_predict_batch_single_naive`) on
+    described sources: predict()'s results, `last_batch_single` / `last_batch_routes` /
+    `last_batch_diags` filled."""
     count = len(arrays)
+    if naive:
+      thresholds = self._naive_thresholds()  # (NaiveClusterer's ValueError, before any launch)
     for i, a in enumerate(arrays):
-      if int(a.rows) < 2:  # (predict()'s ValueError, before anything is launched)
+      if int(a.rows) < 2 and not naive:  # (predict()'s ValueError, before anything is launched)
         raise ValueError("Found array with %d sample(s) while a minimum of 2 is required by "
                          "AgglomerativeClustering." % int(a.rows))
     labels = [np.empty(int(a.rows), dtype=np.int64) for a in arrays]
     lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
     diags = (_lib.ScDiag * count)()
     single = (ctypes.c_int32 * count)()
-    handle.check(handle.lib.sc_predict_batch_single_fallback(
-        handle.raw, (_lib.ScArray * count)(*arrays), count, self.build_config(),
-        float(self.fallback_options.agglomerative_threshold), lp, diags, int(group), single),
-        ValueError)
+    if naive:
+      handle.check(handle.lib.sc_predict_batch_single_naive(
+          handle.raw, (_lib.ScArray * count)(*arrays), count, self.build_config(),
+          thresholds[0], thresholds[1], lp, diags, int(group), single), ValueError)
+    else:
+      handle.check(handle.lib.sc_predict_batch_single_fallback(
+          handle.raw, (_lib.ScArray * count)(*arrays), count, self.build_config(),
+          float(self.fallback_options.agglomerative_threshold), lp, diags, int(group), single),
+          ValueError)
     self._batch_report(handle, diags, count)
     self.last_batch_single = [bool(v) for v in single]
     # predict()'s result for a single-cluster utterance: np.array([0] * n)
@@ -853,7 +897,8 @@ class SpectralClusterer:
       d = sources[0].shape[1]
       if any(src.shape[1] != d for src in sources):
         raise ValueError("all utterances must be (n_i, d) with the same d")
-      return self._single_fallback_call(self._handle(), [src.array for src in sources], group)
+      return self._single_fallback_call(self._handle(), [src.array for src in sources], group,
+                                        naive=self._naive_fallback())
     finally:
       for src in sources:
         src.release()
@@ -868,12 +913,13 @@ class SpectralClusterer:
     return _lib.BATCH_KIND_SPECTRAL
 
   def _reduced_batch_covers(self, utterances: typing.Sequence, streams: typing.Optional[int],
-                            group: typing.Optional[int]) -> bool:
+                            group: typing.Optional[int], naive: bool = False) -> bool:
     """Is this batch ONE `sc_predict_batch_reduced` call?  A clusterer that
     `_library_batch_covers` but for `max_spectral_size` / `spectral_min_embeddings`, in the
     grouped form, cosine k-means, no constraints (the caller has looked), an agglomerative
     fallback for the utterances that need one, and centroids that are not fallback members
-    themselves (predict() recurses on them)."""
+    themselves (predict() recurses on them).  `naive`: fallback utterances may meet the Naive
+    type as well (the caller then makes the `sc_predict_batch_reduced_naive` call)."""
     options = self.fallback_options
     if self.max_spectral_size is None and options.spectral_min_embeddings <= 1:
       return False  # (nothing to reduce: the caller's own answer stands)
@@ -896,13 +942,14 @@ class SpectralClusterer:
     except (IndexError, TypeError):
       return False  # (not (n, d): predict() says what is wrong with it)
     if (_lib.BATCH_KIND_FALLBACK in kinds and options.fallback_clusterer_type !=
-        fallback_clusterer.FallbackClustererType.Agglomerative):
+        fallback_clusterer.FallbackClustererType.Agglomerative and
+        not (naive and self._naive_fallback())):
       return False
     return True
 
   def _predict_batch_reduced(self, utterances: typing.Sequence,
                              group: int) -> typing.List[np.ndarray]:
-    """ONE `sc_predict_batch_reduced` call; `_reduced_batch_covers` holds."""
+    """ONE `sc_predict_batch_reduced` (or `_naive`) call; `_reduced_batch_covers` holds."""
     for u in utterances:
       if isinstance(u, np.ndarray) and u.ndim != 2:
         raise ValueError("all utterances must be (n_i, d) with the same d")
@@ -918,10 +965,16 @@ class SpectralClusterer:
       d = sources[0].shape[1]
       if any(src.shape[1] != d for src in sources):
         raise ValueError("all utterances must be (n_i, d) with the same d")
+      # the fallback utterances meet the Naive type (`_reduced_batch_covers(naive=True)` let
+      # them through): the _naive form of the call
+      naive = self._naive_fallback() and any(
+          self._batch_kind(src.shape[0]) == _lib.BATCH_KIND_FALLBACK for src in sources)
+      if naive:
+        thresholds = self._naive_thresholds()  # (NaiveClusterer's ValueError)
       # what predict() raises for an utterance, before anything is launched
       for src in sources:
         kind = self._batch_kind(src.shape[0])
-        if kind == _lib.BATCH_KIND_FALLBACK and src.shape[0] < 2:
+        if kind == _lib.BATCH_KIND_FALLBACK and src.shape[0] < 2 and not naive:
           raise ValueError("Found array with %d sample(s) while a minimum of 2 is required by "
                            "AgglomerativeClustering." % src.shape[0])
         if kind == _lib.BATCH_KIND_REDUCED and (
@@ -934,12 +987,18 @@ class SpectralClusterer:
       lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
       diags = (_lib.ScDiag * count)()
       kinds = (ctypes.c_int32 * count)()
-      handle.check(handle.lib.sc_predict_batch_reduced(
-          handle.raw, (_lib.ScArray * count)(*[src.array for src in sources]), count,
-          self.build_config(), int(self.max_spectral_size or 0),
-          int(self.fallback_options.spectral_min_embeddings),
-          float(self.fallback_options.agglomerative_threshold), lp, diags, int(group), kinds),
-          ValueError)
+      arrays = (_lib.ScArray * count)(*[src.array for src in sources])
+      if naive:
+        handle.check(handle.lib.sc_predict_batch_reduced_naive(
+            handle.raw, arrays, count, self.build_config(), int(self.max_spectral_size or 0),
+            int(self.fallback_options.spectral_min_embeddings), thresholds[0], thresholds[1],
+            lp, diags, int(group), kinds), ValueError)
+      else:
+        handle.check(handle.lib.sc_predict_batch_reduced(
+            handle.raw, arrays, count, self.build_config(), int(self.max_spectral_size or 0),
+            int(self.fallback_options.spectral_min_embeddings),
+            float(self.fallback_options.agglomerative_threshold), lp, diags, int(group), kinds),
+            ValueError)
     finally:
       for src in sources:
         src.release()
