@@ -383,10 +383,33 @@ int sc_cluster(sc_handle h, const sc_config* cfg, int n_clusters,
  * none) -- and the current device sizes in bytes of the band buffer and of the (n, ld) dense
  * buffer (buffers are kept across calls; one that was never needed stays 0).  Any out pointer
  * may be NULL.
+ *
+ * The entry-list form: a handful of must-link / cannot-link pairs, what E2CP is about.
+ * sc_set_constraint_pairs takes Q as its `count` non-zero entries Q[rows[e], cols[e]] = vals[e]
+ * (host memory; a symmetric pair is two entries).  count * 16 bytes are uploaded, nothing else;
+ * count = 0 is valid (Q = 0).  SC_ERR_INVALID: an index outside [0, n), a non-finite value, a
+ * position listed twice.  Whether the list is symmetric -- every (r, c, v) with r != c has its
+ * twin (c, r, v) -- is decided on the host while validating; an asymmetric list behaves as the
+ * asymmetric dense matrix it stands for.  It replaces a dense or banded constraint and is
+ * replaced by them, sc_clear_constraint clears it, sc_constraint_info reports kind 3, and
+ * sc_constraint_pairs_info the entry count (0 when another form or none is resident) and the
+ * current device size in bytes of the entry buffer.
+ * AffinityIntegration: one pass over A with Q = 0, then the `count` entries are patched from the
+ * originals gathered before it.  ConstraintPropagation, count <= n: T Q T = sum_e vals[e]
+ * T[:, rows[e]] T[cols[e], :] = U V^T with two (n, round_up(count, 16)) panels held in idle work
+ * matrices; one kernel forms U V^T tile by tile (fp64 MFMA, entry order, no atomics) and adjusts
+ * A with it in registers -- instead of two n^3 GEMMs and three more passes.  count > n: the
+ * entries are scattered into the zero-filled dense buffer on the device and the dense stage
+ * runs (still no (n, n) upload).  When A and the list are symmetric the result is exactly
+ * symmetric.
  */
 int sc_set_constraint(sc_handle h, const double* constraint_matrix, int n);
 /* constraint.py:167-207 (ConstraintMatrix) + sc_set_constraint, without the matrix */
 int sc_set_constraint_band(sc_handle h, const double* band, int n);
+/* sc_set_constraint with the matrix given as its non-zero entries */
+int sc_set_constraint_pairs(sc_handle h, const int32_t* rows, const int32_t* cols,
+                            const double* vals, int count, int n);
+int sc_constraint_pairs_info(sc_handle h, int* count, size_t* pair_bytes);
 int sc_clear_constraint(sc_handle h);
 int sc_apply_constraint(sc_handle h, const sc_config* cfg);
 int sc_constraint_info(sc_handle h, int* kind, int* n, size_t* band_bytes,
@@ -471,6 +494,33 @@ int sc_predict_batch_arrays(sc_handle h, const sc_array* xs, int count, const sc
  * when the call returns, whatever it returns.  Every descriptor is validated before the first
  * launch.  A band of the wrong length cannot be detected here. */
 int sc_predict_batch_constrained(sc_handle h, const sc_array* xs, const double* const* bands,
+                                 int count, const sc_config* cfg, int64_t* const* labels,
+                                 sc_diag* diags, int group);
+/* The constraint of one utterance of sc_predict_batch_constraints; every pointer is host memory,
+ * valid for the duration of the call.  kind: sc_constraint_info's codes -- 0 none, 2 band (`band`:
+ * rows - 1 values), 3 pairs (`count` directed entries rows / cols / vals as
+ * sc_set_constraint_pairs takes them); the fields of the other kinds are not read. */
+typedef struct sc_constraint_desc {
+  int32_t kind;
+  int32_t count;
+  const double* band;
+  const int32_t* rows;
+  const int32_t* cols;
+  const double* vals;
+} sc_constraint_desc;
+/* sizeof(sc_constraint_desc) and the offsets of its 6 fields in declaration order (either may be
+ * NULL): lets a binding check its mirror of the struct, as sc_array_layout does */
+int sc_constraint_desc_layout(int* bytes, int* field_offsets);
+/* sc_predict_batch_constrained with one sc_constraint_desc per utterance (cons == NULL: none has a
+ * constraint); that function is this one with every kind 0 or 2.  An entry list becomes the
+ * resident constraint (kind 3) of its member arena, behind the affinity, in buffers reserved with
+ * the arena for the batch's largest list.  In ConstraintPropagation before refinement the Neumann
+ * chain is shared by all members of a group; its last stage runs the band members' three launches
+ * with the pair members idle, then the pair members' two (k_cp_pair_panels_g,
+ * k_cp_pairs_adjust_g) with the band members idle; a launch without live members is skipped.  A
+ * member with more entries than rows takes the dense stage and runs as a single call (route 0).
+ * Every list is validated before the first launch (SC_ERR_INVALID as sc_set_constraint_pairs). */
+int sc_predict_batch_constraints(sc_handle h, const sc_array* xs, const sc_constraint_desc* cons,
                                  int count, const sc_config* cfg, int64_t* const* labels,
                                  sc_diag* diags, int group);
 /* What ran: one code per utterance of the last sc_predict_batch* call on this handle (a
@@ -768,6 +818,21 @@ int sc_stage_constraint_band(sc_handle h, const sc_config* cfg, const double* af
 int sc_stage_constraint_band_group(sc_handle h, const sc_config* cfg, int count, const int32_t* ns,
                                    const double* const* affinities, const double* const* bands,
                                    double* const* outs);
+/* sc_stage_constraint with the constraint matrix given as `count` directed entries
+ * (sc_set_constraint_pairs) */
+int sc_stage_constraint_pairs(sc_handle h, const sc_config* cfg, const double* affinity,
+                              const int32_t* rows, const int32_t* cols, const double* vals,
+                              int count, int n, double* out);
+/* Test entry: sc_stage_constraint_band_group with member z's constraint given as counts[z] <=
+ * ns[z] entries (rows[z], cols[z], vals[z]) instead of a band; the entry buffers are NaN-filled
+ * before the upload like everything else.  ns[z] = 0 marks an idle member; counts[z] = 0 is a
+ * live member with Q = 0 (outs[z] receives the affinity unchanged).  A member's result is, bit
+ * for bit, what the last stage of sc_stage_constraint_pairs makes of the same T. */
+int sc_stage_constraint_pairs_group(sc_handle h, const sc_config* cfg, int count,
+                                    const int32_t* ns, const double* const* affinities,
+                                    const int32_t* const* rows, const int32_t* const* cols,
+                                    const double* const* vals, const int32_t* counts,
+                                    double* const* outs);
 /* rowmax / rowsum of Diffuse(a) = a a^T (refinement.py:232-234) for a SYMMETRIC (n, n) input --
  * what RowWiseNormalize (refinement.py:240-245) and the Laplacian degree (laplacian.py:41) read
  * of it -- by either route: mode 1 the explicit fp64 product, mode 2 the matrix-free search

@@ -11,7 +11,8 @@ import importlib as _importlib
 _PUBLIC = {
     "autotune": ("AutoTune", "AutoTuneProxy"),
     "configs": ("ICASSP2018_REFINEMENT_SEQUENCE", "TURNTODIARIZE_REFINEMENT_SEQUENCE"),
-    "constraint": ("ConstraintOptions", "ConstraintName", "ConstraintMatrix", "IntegrationType"),
+    "constraint": ("ConstraintOptions", "ConstraintName", "ConstraintMatrix", "IntegrationType",
+                   "PairwiseConstraints"),
     "custom_distance_kmeans": (),
     "fallback_clusterer": ("FallbackOptions", "SingleClusterCondition",
                            "FallbackClustererType"),

@@ -184,6 +184,19 @@ class ScSingleCheck(ctypes.Structure):
   ]
 
 
+class ScConstraintDesc(ctypes.Structure):
+  """Mirror of `sc_constraint_desc`: the constraint of one utterance of
+  `sc_predict_batch_constraints` (kind 0 none / 2 band / 3 pairs; host pointers)."""
+  _fields_ = [
+      ("kind", ctypes.c_int32),
+      ("count", ctypes.c_int32),
+      ("band", ctypes.POINTER(ctypes.c_double)),
+      ("rows", ctypes.POINTER(ctypes.c_int32)),
+      ("cols", ctypes.POINTER(ctypes.c_int32)),
+      ("vals", ctypes.POINTER(ctypes.c_double)),
+  ]
+
+
 # sc_autotune.proxy (the values of autotune.AutoTuneProxy)
 SC_AUTOTUNE_PERCENTILE_OVER_NME, SC_AUTOTUNE_PERCENTILE_SQRT_OVER_NME = 1, 2
 
@@ -275,6 +288,13 @@ PROTOTYPES = {
                                                     ctypes.POINTER(ScConfig),
                                                     ctypes.POINTER(_c_int64_p),
                                                     ctypes.POINTER(ScDiag), ctypes.c_int]),
+    "sc_constraint_desc_layout": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int),
+                                                 ctypes.POINTER(ctypes.c_int)]),
+    "sc_predict_batch_constraints": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),
+                                                    ctypes.POINTER(ScConstraintDesc), ctypes.c_int,
+                                                    ctypes.POINTER(ScConfig),
+                                                    ctypes.POINTER(_c_int64_p),
+                                                    ctypes.POINTER(ScDiag), ctypes.c_int]),
     "sc_stage_ingest": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray), _c_double_p]),
     "sc_compute_affinity": (ctypes.c_int, [_handle_t]),
     "sc_set_affinity": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int]),
@@ -305,6 +325,26 @@ PROTOTYPES = {
                                                       ctypes.POINTER(_c_double_p),
                                                       ctypes.POINTER(_c_double_p),
                                                       ctypes.POINTER(_c_double_p)]),
+    "sc_set_constraint_pairs": (ctypes.c_int, [_handle_t, ctypes.POINTER(ctypes.c_int32),
+                                               ctypes.POINTER(ctypes.c_int32), _c_double_p,
+                                               ctypes.c_int, ctypes.c_int]),
+    "sc_constraint_pairs_info": (ctypes.c_int, [_handle_t, _c_int_p,
+                                                ctypes.POINTER(ctypes.c_size_t)]),
+    "sc_stage_constraint_pairs": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScConfig),
+                                                 _c_double_p, ctypes.POINTER(ctypes.c_int32),
+                                                 ctypes.POINTER(ctypes.c_int32), _c_double_p,
+                                                 ctypes.c_int, ctypes.c_int, _c_double_p]),
+    "sc_stage_constraint_pairs_group": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScConfig),
+                                                       ctypes.c_int,
+                                                       ctypes.POINTER(ctypes.c_int32),
+                                                       ctypes.POINTER(_c_double_p),
+                                                       ctypes.POINTER(
+                                                           ctypes.POINTER(ctypes.c_int32)),
+                                                       ctypes.POINTER(
+                                                           ctypes.POINTER(ctypes.c_int32)),
+                                                       ctypes.POINTER(_c_double_p),
+                                                       ctypes.POINTER(ctypes.c_int32),
+                                                       ctypes.POINTER(_c_double_p)]),
     "sc_ahc": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                               ctypes.c_int, ctypes.c_double, _c_int64_p,
                               ctypes.POINTER(ctypes.c_int)]),
@@ -595,6 +635,10 @@ def sync_blur_weights(handle, cfg) -> None:
 
 def as_int64_p(a: np.ndarray):
   return a.ctypes.data_as(_c_int64_p)
+
+
+def as_int32_p(a: np.ndarray):
+  return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
 
 
 class Handle:

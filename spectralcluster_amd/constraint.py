@@ -5,8 +5,10 @@
 resident and the same kernels run in the pipeline (`sc_set_constraint`).  Wherever a
 constraint matrix is accepted, a `ConstraintMatrix` instance is accepted too: its n - 1 band
 values travel instead of the (n, n) array of `compute_diagonals()`
-(`sc_set_constraint_band` / `sc_stage_constraint_band`).  An ndarray always takes the dense
-route, whatever it holds.  The E2CP
+(`sc_set_constraint_band` / `sc_stage_constraint_band`).  A `PairwiseConstraints` instance -- a
+list of must-link / cannot-link pairs -- is accepted as well: its K directed entries travel
+(`sc_set_constraint_pairs` / `sc_stage_constraint_pairs`), 16 bytes each, and no (n, n) array is
+built on either side.  An ndarray always takes the dense route, whatever it holds.  The E2CP
 inverse `(I - alpha * A_norm)^-1` is evaluated as a Neumann product of fp64 MFMA GEMMs
 (see `csrc/constraint_api.hip: constraint_propagation`), which needs |alpha| < 1 and a
 non-negative affinity; anything else raises `UnsupportedOnDeviceError`.
@@ -43,8 +45,10 @@ def _device_adjust(affinity: np.ndarray, constraint_matrix, name: ConstraintName
                    alpha: float) -> np.ndarray:
   src = np.ascontiguousarray(affinity, dtype=np.float64)
   banded = isinstance(constraint_matrix, ConstraintMatrix)
-  con = constraint_matrix.band() if banded else np.ascontiguousarray(
-      constraint_matrix, dtype=np.float64)
+  paired = isinstance(constraint_matrix, PairwiseConstraints)
+  if not paired:
+    con = constraint_matrix.band() if banded else np.ascontiguousarray(
+        constraint_matrix, dtype=np.float64)
   cfg = _lib.ScConfig()
   _lib.load().sc_config_default(cfg)
   cfg.constraint_name = name.value
@@ -53,6 +57,12 @@ def _device_adjust(affinity: np.ndarray, constraint_matrix, name: ConstraintName
   cfg.constraint_alpha = float(alpha)
   out = np.empty_like(src)
   handle = _lib.default_handle()
+  if paired:
+    rows, cols, vals = constraint_matrix.entries()
+    handle.check(handle.lib.sc_stage_constraint_pairs(
+        handle.raw, cfg, _lib.as_double_p(src), _lib.as_int32_p(rows), _lib.as_int32_p(cols),
+        _lib.as_double_p(vals), len(vals), src.shape[0], _lib.as_double_p(out)))
+    return out
   stage = handle.lib.sc_stage_constraint_band if banded else handle.lib.sc_stage_constraint
   handle.check(stage(
       handle.raw, cfg, _lib.as_double_p(src), _lib.as_double_p(con), src.shape[0],
@@ -65,9 +75,11 @@ class ConstraintOperation(metaclass=abc.ABCMeta):
 
   def check_input(self, affinity: np.ndarray, constraint_matrix):
     """Same checks and messages as reference constraint.py:54-76.  A `ConstraintMatrix`
-    stands for the (n, n) matrix of its `compute_diagonals()`, n = its number of scores."""
-    if isinstance(constraint_matrix, ConstraintMatrix):
-      n = len(constraint_matrix.speaker_turn_scores)
+    stands for the (n, n) matrix of its `compute_diagonals()`, n = its number of scores; a
+    `PairwiseConstraints` for the (n, n) matrix of its `to_dense()`."""
+    if isinstance(constraint_matrix, (ConstraintMatrix, PairwiseConstraints)):
+      n = (constraint_matrix.n if isinstance(constraint_matrix, PairwiseConstraints)
+           else len(constraint_matrix.speaker_turn_scores))
       constraint_matrix = np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0))
     for what, m in (("affinity", affinity), ("constraint matrix", constraint_matrix)):
       if len(m.shape) != 2:
@@ -174,3 +186,74 @@ class ConstraintMatrix:
     out[idx, idx + 1] = band
     out[idx + 1, idx] = band
     return out
+
+
+class PairwiseConstraints:
+  """Constraint matrix given as a list of pairs: Q[i, j] = Q[j, i] = v for every listed pair
+  {i, j}, 0 elsewhere (the input E2CP is about: a handful of must-link / cannot-link pairs).
+
+  `must_link` / `cannot_link`: sequences of (i, j), values +1 / -1 (the convention of
+  `ConstraintMatrix.compute_diagonals`).  `pairs` (m, 2) with `values` (m,): arbitrary finite
+  weights.  i == j is allowed and gives one entry on the diagonal.  Pass the object wherever a
+  constraint matrix is accepted and only its entries travel to the device."""
+
+  def __init__(self, n: int, must_link: typing.Sequence = (), cannot_link: typing.Sequence = (),
+               pairs=None, values=None):
+    self.n = int(n)
+    if self.n < 0:
+      raise ValueError("n must not be negative")
+    if (pairs is None) != (values is None):
+      raise ValueError("pairs and values must be given together")
+    ij = [np.asarray(must_link, dtype=np.int64).reshape(-1, 2),
+          np.asarray(cannot_link, dtype=np.int64).reshape(-1, 2)]
+    v = [np.ones(len(ij[0])), -np.ones(len(ij[1]))]
+    if pairs is not None:
+      pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+      values = np.asarray(values, dtype=np.float64).reshape(-1)
+      if len(pairs) != len(values):
+        raise ValueError("pairs and values must have the same length")
+      ij.append(pairs)
+      v.append(values)
+    self._pairs = np.concatenate(ij)
+    self._values = np.concatenate(v).astype(np.float64)
+    if np.any(self._pairs < 0) or np.any(self._pairs >= self.n):
+      raise ValueError("pair index outside [0, n)")
+    if not np.all(np.isfinite(self._values)):
+      raise ValueError("constraint values must be finite")
+    key = self._pairs.min(axis=1) * max(self.n, 1) + self._pairs.max(axis=1)
+    if len(np.unique(key)) != len(key):
+      raise ValueError("a pair is listed twice")
+
+  @classmethod
+  def from_dense(cls, q) -> "PairwiseConstraints":
+    """The non-zeros of a symmetric (n, n) matrix."""
+    q = np.asarray(q, dtype=np.float64)
+    if q.ndim != 2 or q.shape[0] != q.shape[1]:
+      raise ValueError("constraint matrix must be a square matrix")
+    if not np.array_equal(q, q.T):
+      raise ValueError("constraint matrix must be symmetric")
+    i, j = np.nonzero(np.triu(q))
+    return cls(q.shape[0], pairs=np.stack([i, j], axis=1), values=q[i, j])
+
+  def to_dense(self) -> np.ndarray:
+    """The (n, n) float64 matrix the pairs stand for."""
+    out = np.zeros((self.n, self.n))
+    out[self._pairs[:, 0], self._pairs[:, 1]] = self._values
+    out[self._pairs[:, 1], self._pairs[:, 0]] = self._values
+    return out
+
+  def entries(self) -> typing.Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(rows int32, cols int32, vals float64): the directed entries Q[rows[e], cols[e]] =
+    vals[e], in the order the pairs were given -- (i, j) then (j, i), adjacent; a diagonal pair
+    gives one entry.  What `sc_set_constraint_pairs` takes."""
+    i, j = self._pairs[:, 0], self._pairs[:, 1]
+    rows = np.stack([i, j], axis=1).reshape(-1)
+    cols = np.stack([j, i], axis=1).reshape(-1)
+    keep = np.stack([np.ones(len(i), dtype=bool), i != j], axis=1).reshape(-1)
+    return (np.ascontiguousarray(rows[keep], dtype=np.int32),
+            np.ascontiguousarray(cols[keep], dtype=np.int32),
+            np.ascontiguousarray(np.repeat(self._values, 2)[keep], dtype=np.float64))
+
+  def __array__(self, dtype=None, copy=None):
+    out = self.to_dense()
+    return out if dtype is None else out.astype(dtype, copy=False)

@@ -44,10 +44,14 @@ double now_us() {
 }
 
 // The Bands of a constrained batch under `cfg` ...
-Bands make_bands(const double* const* band, const sc_config* cfg) {
+Bands make_bands(const sc_constraint_desc* cons, const std::vector<double>* packed,
+                 const char* pairs_symmetric, int kmax, const sc_config* cfg) {
   Bands b;
   if (cfg->constraint_name == SC_CONSTRAINT_NONE) return b;  // (nothing would read them)
-  b.band = band;
+  b.cons = cons;
+  b.packed = packed;
+  b.pairs_symmetric = pairs_symmetric;
+  b.kmax = kmax;
   if (cfg->constraint_name == SC_CONSTRAINT_PROPAGATION) {
     b.chain = cfg->constraint_before_refinement != 0;
     // the grouped chain works in B1 / B2 (idle until refinement starts) + two more matrices; after
@@ -58,8 +62,12 @@ Bands make_bands(const double* const* band, const sc_config* cfg) {
 }
 // ... and what a member arena holds for it, reserved with the arena (never inside a front)
 int reserve_constraint(sc_handle hz, const Bands* bands, int n_max) {
-  if (!bands || !bands->band) return SC_OK;
+  if (!bands || !bands->cons) return SC_OK;
   SC_TRY(grow(hz, hz->Cband, (size_t)std::max(n_max - 1, 1) * sizeof(double)));
+  if (bands->kmax > 0) {  // entries (16 bytes each) and AffinityIntegration's gathered originals
+    SC_TRY(grow(hz, hz->Cpairs, (size_t)bands->kmax * 2 * sizeof(double)));
+    SC_TRY(grow(hz, hz->Cporig, (size_t)bands->kmax * sizeof(double)));
+  }
   const size_t nn = (size_t)n_max * matrix_ld(n_max) * sizeof(double);
   for (int i = 0; i < bands->ncp; ++i) SC_TRY(grow(hz, hz->cp[i], nn));
   return SC_OK;
@@ -132,10 +140,31 @@ int enqueue_front(sc_handle lead, const sc_array* xs, const int* ns, int d,
     h->nev = 0;
     if (diags) memset(diags + m.index, 0, sizeof(sc_diag));
     if (rc == SC_OK) rc = sc_compute_affinity(h);
-    // the arena's resident constraint is this member's band, or none
-    h->have_constraint = h->constraint_banded = false;
+    // the arena's resident constraint is this member's band or entry list, or none
+    h->have_constraint = h->constraint_banded = h->constraint_pairs = false;
     h->qn = 0;
-    const double* band = bands && bands->band ? bands->band[m.index] : nullptr;
+    const double* band = bands ? bands->band(m.index) : nullptr;
+    const bool pairs = bands && bands->pairs(m.index);
+    if (rc == SC_OK && pairs) {
+      // (buffers reserved with the arena for the batch's largest list: reserve_constraint)
+      const int k = bands->cons[m.index].count;
+      const size_t bytes = (size_t)k * 2 * sizeof(double);
+      if (h->Cpairs.bytes < bytes || h->Cporig.bytes < (size_t)k * sizeof(double))
+        rc = fail(h, SC_ERR_INVALID, "member arena without the entry buffers");
+      if (rc == SC_OK && bytes > 0 &&
+          hipMemcpyAsync(h->Cpairs.p, bands->packed[m.index].data(), bytes, hipMemcpyHostToDevice,
+                         h->stream) != hipSuccess)
+        rc = fail(h, SC_ERR_HIP, "could not upload a constraint entry list");
+      h->have_constraint = h->constraint_pairs = true;
+      h->constraint_symmetric = bands->pairs_symmetric[m.index] != 0;
+      h->pairs_count = k;
+      h->qn = h->n;
+    }
+    if (rc == SC_OK && pairs && bands->chain) {
+      chained.push_back(z);
+      SC_HIP(lead, hipEventRecord(h->sync_ev, h->stream));  // "affinity and entries are there"
+      continue;
+    }
     if (rc == SC_OK && band) {
       const size_t bytes = (size_t)(h->n - 1) * sizeof(double);
       rc = grow(h, h->Cband, std::max<size_t>(bytes, sizeof(double)));
@@ -178,6 +207,14 @@ int enqueue_front(sc_handle lead, const sc_array* xs, const int* ns, int d,
       cm[q].rowmax = ptr<double>(h->cut);
       cm[q].band = ptr<double>(h->Cband);
       cm[q].tilemap = h->tilemap_cur;
+      if (h->constraint_pairs) {
+        cm[q].pairs = true;
+        cm[q].psym = h->constraint_symmetric;
+        cm[q].pk = h->pairs_count;
+        cm[q].pvals = ptr<double>(h->Cpairs);
+        cm[q].prows = reinterpret_cast<const int32_t*>(cm[q].pvals + cm[q].pk);
+        cm[q].pcols = cm[q].prows + cm[q].pk;
+      }
     }
     SC_TRY(constraint_propagation_group(lead, chain_stream, cm, cnt, cfg->constraint_alpha));
   }
@@ -186,6 +223,7 @@ int enqueue_front(sc_handle lead, const sc_array* xs, const int* ns, int d,
     sc_handle h = mb[z].h;
     SC_HIP(lead, hipStreamWaitEvent(h->stream, chain_ev, 0));
     h->have_cropval = false;  // (what sc_apply_constraint leaves: the epilogue's crop values are stale)
+    h->affinity_symmetric = h->affinity_symmetric && h->constraint_symmetric;  // (a band is)
     h->constraint_applied = true;
     h->n_vec = 0;
     SC_TRY(refine(z));
@@ -383,7 +421,7 @@ int run_short_route(sc_handle h, const sc_array* xs, const int* ns, int d,
       hz->have_constraint = false;
     }
   ShortWaveOps wave_ops;
-  const bool wave = !sw::short_front_memberwise() && !(bands && bands->band) &&
+  const bool wave = !sw::short_front_memberwise() && !(bands && bands->cons) &&
                     d <= kShortWaveMaxD && short_wave_covers(cfg, &wave_ops);
   if (wave || (bands && bands->chain))  // (the grouped chain of a wave: a stream of the wave's bank)
     for (int b = 0; b < banks; ++b) SC_TRY(ensure_bank_stream(h, b));
@@ -559,12 +597,17 @@ int run_group_lane(sc_handle h, const sc_array* xs, const int* ns, int d,
 }
 
 // The members of a constrained batch that run as single calls on the caller's handle: each with
-// its own band resident for the call (sc_predict with sc_set_constraint_band in front).
+// its own band or entry list resident for the call (sc_predict with sc_set_constraint_band /
+// sc_set_constraint_pairs in front).
 int predict_single_banded(sc_handle h, const std::vector<int>& list, const sc_array* xs,
                           const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
                           const Bands& bands) {
   for (int i : list) {
-    if (bands.band[i]) SC_TRY(sc_set_constraint_band(h, bands.band[i], (int)xs[i].rows));
+    const int n = (int)xs[i].rows;
+    if (bands.pairs(i))
+      SC_TRY(sc_set_constraint_pairs(h, bands.cons[i].rows, bands.cons[i].cols, bands.cons[i].vals,
+                                     bands.cons[i].count, n));
+    else if (bands.band(i)) SC_TRY(sc_set_constraint_band(h, bands.band(i), n));
     else SC_TRY(sc_clear_constraint(h));
     h->sweep_slot.clear();
     SC_TRY(ingest_embeddings(h, xs[i], xs[i].location == SC_MEM_HOST));
@@ -625,12 +668,12 @@ bool constraint_workspace_fits(sc_handle h, const Bands& bands, int largest, boo
   return (double)bytes <= 0.85 * (double)free_b;
 }
 
-// partition, groups, lanes, banks and short waves of a grouped batch; `band_set.band` non-null:
+// partition, groups, lanes, banks and short waves of a grouped batch; `band_set.cons` non-null:
 // the constrained batch (one lane, member-by-member fronts, enqueue_front's band handling)
 int predict_batch_core(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
                        const sc_config* cfg, int64_t* const* labels, sc_diag* diags, int group,
                        const Bands& band_set, const SingleCheck* sc = nullptr) {
-  const Bands* bands = band_set.band ? &band_set : nullptr;
+  const Bands* bands = band_set.cons ? &band_set : nullptr;
   if (sc && sc->single) std::fill(sc->single, sc->single + count, 0);
   SC_TRY(validate_config(h, cfg));
   SC_HIP(h, hipSetDevice(h->device));
@@ -656,8 +699,11 @@ int predict_batch_core(sc_handle h, const sc_array* xs, const int* ns, int d, in
   for (int i = 0; i < count; ++i) {
     // (the chain form of the single-cluster test covers n < kScChainMaxN, the route's own limit
     //  unless a switch has moved that)
-    if (cfg_ok && xs[i].data && ns[i] > 0 && sym_group_eligible(ns[i], rq) &&
-        (!sc || ns[i] < kScChainMaxN))
+    // (an entry list longer than n takes the dense stage: the single call's)
+    if (bands && bands->pairs(i) && bands->cons[i].count > ns[i])
+      single.push_back(i);
+    else if (cfg_ok && xs[i].data && ns[i] > 0 && sym_group_eligible(ns[i], rq) &&
+             (!sc || ns[i] < kScChainMaxN))
       grouped.push_back(i);
     else if (cfg_ok && xs[i].data && ns[i] > 0 && ns[i] <= kDenseMax) shorts.push_back(i);
     else single.push_back(i);
@@ -668,11 +714,11 @@ int predict_batch_core(sc_handle h, const sc_array* xs, const int* ns, int d, in
     int largest = 0;
     bool any_short = false;
     for (int i : grouped) largest = std::max(largest, ns[i]);
-    for (int i : shorts) any_short = any_short || bands->band[i];
+    for (int i : shorts) any_short = any_short || bands->has(i);
     if (!constraint_workspace_fits(h, *bands, largest, any_short)) {
       auto hand_over = [&](std::vector<int>& list) {
         std::vector<int> keep;
-        for (int i : list) (bands->band[i] ? single : keep).push_back(i);
+        for (int i : list) (bands->has(i) ? single : keep).push_back(i);
         list.swap(keep);
       };
       hand_over(grouped);
@@ -1155,7 +1201,8 @@ int enqueue_front_short_wave(sc_handle lead, const sc_array* xs, const int* ns, 
     if (n > kDenseMax) return fail(lead, SC_ERR_INVALID, "short wave: a member above 128 rows");
     SC_TRY(member_problem(lead, h, xs[m.index], n, d, s));
     h->have_cropval = ops.crop != 0;  // (the front kernel writes the vector only then)
-    h->have_constraint = h->constraint_banded = false;  // (a constrained wave's arena: its band)
+    h->have_constraint = h->constraint_banded = h->constraint_pairs = false;  // (a constrained
+    // wave's arena: its band or entry list)
     h->qn = 0;
     if (diags) memset(diags + m.index, 0, sizeof(sc_diag));
     fi[z] = front_item(h, kFrontRows);  // (the rest is the wave kernel's, which reads the table)
@@ -1402,14 +1449,27 @@ bool release_large_arenas(sc_handle* leads, int lanes, bool always) {
   return true;
 }
 
-extern "C" int sc_predict_batch_constrained(sc_handle h, const sc_array* xs,
-                                            const double* const* bands, int count,
+extern "C" int sc_constraint_desc_layout(int* bytes, int* field_offsets) {
+  if (bytes) *bytes = (int)sizeof(sc_constraint_desc);
+  if (field_offsets) {
+    field_offsets[0] = (int)offsetof(sc_constraint_desc, kind);
+    field_offsets[1] = (int)offsetof(sc_constraint_desc, count);
+    field_offsets[2] = (int)offsetof(sc_constraint_desc, band);
+    field_offsets[3] = (int)offsetof(sc_constraint_desc, rows);
+    field_offsets[4] = (int)offsetof(sc_constraint_desc, cols);
+    field_offsets[5] = (int)offsetof(sc_constraint_desc, vals);
+  }
+  return SC_OK;
+}
+
+extern "C" int sc_predict_batch_constraints(sc_handle h, const sc_array* xs,
+                                            const sc_constraint_desc* cons, int count,
                                             const sc_config* cfg, int64_t* const* labels,
                                             sc_diag* diags, int group) {
   if (!h) return SC_ERR_INVALID;
   if (!xs || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
   if (group < 2)
-    return fail(h, SC_ERR_INVALID, "sc_predict_batch_constrained is the grouped form: group >= 2");
+    return fail(h, SC_ERR_INVALID, "a constrained batch is the grouped form: group >= 2");
   SC_TRY(validate_config(h, cfg));
   SC_HIP(h, hipSetDevice(h->device));
   bool device_source = false;
@@ -1422,15 +1482,55 @@ extern "C" int sc_predict_batch_constrained(sc_handle h, const sc_array* xs,
     return SC_OK;
   }
   if (device_source) SC_HIP(h, hipStreamSynchronize(h->stream));  // (as sc_predict_batch_arrays)
-  return predict_batch_constrained_impl(h, xs, bands, ns.data(), d, count, cfg, labels, diags,
+  return predict_batch_constrained_impl(h, xs, cons, ns.data(), d, count, cfg, labels, diags,
                                         group);
 }
 
-int predict_batch_constrained_impl(sc_handle h, const sc_array* xs, const double* const* bands,
+// (sc_predict_batch_constraints with every kind 0 or 2)
+extern "C" int sc_predict_batch_constrained(sc_handle h, const sc_array* xs,
+                                            const double* const* bands, int count,
+                                            const sc_config* cfg, int64_t* const* labels,
+                                            sc_diag* diags, int group) {
+  if (!h) return SC_ERR_INVALID;
+  if (!xs || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  if (group < 2)
+    return fail(h, SC_ERR_INVALID, "sc_predict_batch_constrained is the grouped form: group >= 2");
+  std::vector<sc_constraint_desc> cons;
+  if (bands && count > 0) {
+    cons.assign((size_t)count, sc_constraint_desc());
+    for (int i = 0; i < count; ++i) {
+      cons[i].kind = bands[i] ? 2 : 0;
+      cons[i].band = bands[i];
+    }
+  }
+  return sc_predict_batch_constraints(h, xs, cons.empty() ? nullptr : cons.data(), count, cfg,
+                                      labels, diags, group);
+}
+
+int predict_batch_constrained_impl(sc_handle h, const sc_array* xs, const sc_constraint_desc* cons,
                                    const int* ns, int d, int count, const sc_config* cfg,
                                    int64_t* const* labels, sc_diag* diags, int group) {
-  // no band stays resident in a member arena, and none of them is still on its way up from the
-  // caller's memory, however the batch ends
+  // every entry list is checked, and packed for its upload, before anything is launched
+  std::vector<std::vector<double>> packed((size_t)count);
+  std::vector<char> pairs_symmetric((size_t)count, 1);
+  int kmax = 0;
+  const bool read = cons && cfg->constraint_name != SC_CONSTRAINT_NONE;
+  for (int i = 0; read && i < count; ++i) {
+    const sc_constraint_desc& c = cons[i];
+    if (c.kind != 0 && c.kind != 2 && c.kind != 3)
+      return fail(h, SC_ERR_INVALID, "constraint kind must be 0 (none), 2 (band) or 3 (pairs)");
+    if (c.kind == 2 && !c.band)
+      return fail(h, SC_ERR_INVALID, "a band constraint without its values");
+    if (c.kind != 3) continue;
+    bool symmetric = true;
+    SC_TRY(validate_constraint_pairs(h, c.rows, c.cols, c.vals, c.count, ns[i], &symmetric));
+    pairs_symmetric[i] = symmetric ? 1 : 0;
+    if (c.count > ns[i]) continue;  // (the dense stage: a single call, sc_set_constraint_pairs)
+    packed[i] = pack_constraint_pairs(c.rows, c.cols, c.vals, c.count);
+    kmax = std::max(kmax, std::max(c.count, 1));  // (an empty list still reserves its buffers)
+  }
+  // no constraint stays resident in a member arena, and none of them is still on its way up from
+  // the caller's memory, however the batch ends
   struct Cleanup {
     sc_handle h;
     int rc = SC_OK;
@@ -1448,7 +1548,8 @@ int predict_batch_constrained_impl(sc_handle h, const sc_array* xs, const double
     }
   } cleanup{h};
   cleanup.rc = predict_batch_core(h, xs, ns, d, count, cfg, labels, diags, group,
-                                  make_bands(bands, cfg));
+                                  make_bands(cons, packed.data(), pairs_symmetric.data(), kmax,
+                                             cfg));
   return cleanup.rc;
 }
 

@@ -15,12 +15,21 @@ struct Member {
   const GroupEigMember* eig = nullptr;  // what the group's eigensolver left for it
 };
 
-// What a constrained batch carries (sc_predict_batch_constrained): per utterance the band of its
-// ConstraintMatrix (host memory, n_i - 1 values; nullptr: that utterance has no constraint).
+// What a constrained batch carries (sc_predict_batch_constraints): per utterance one constraint
+// that is the band of its ConstraintMatrix (kind 2: n_i - 1 values), a list of directed entries
+// (kind 3) or nothing (kind 0); host memory, validated before the batch starts.
 struct Bands {
-  const double* const* band = nullptr;
+  const sc_constraint_desc* cons = nullptr;  // nullptr: the batch carries no constraints
+  // per utterance of kind 3: vals | rows | cols as Cpairs holds them (the upload's source, alive
+  // for the whole call) and whether the list is symmetric
+  const std::vector<double>* packed = nullptr;
+  const char* pairs_symmetric = nullptr;
+  int kmax = 0;        // the largest entry list: what a member arena reserves
   bool chain = false;  // ConstraintPropagation before refinement: the grouped Neumann chain
   int ncp = 0;         // cp[] work matrices a member arena holds for the configured operator
+  bool has(int i) const { return cons && cons[i].kind != 0; }
+  const double* band(int i) const { return cons && cons[i].kind == 2 ? cons[i].band : nullptr; }
+  bool pairs(int i) const { return cons && cons[i].kind == 3; }
 };
 
 // What a min_clusters = 1 batch carries (sc_predict_batch_single): the single-cluster test every

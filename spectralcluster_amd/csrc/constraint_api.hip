@@ -1,7 +1,12 @@
 // Host side of the constraint operators (reference constraint.py:95-164): the resident
-// constraint (a dense matrix, or the band of ConstraintMatrix, constraint.py:167-207) and the
-// GEMM chain of ConstraintPropagation; kernels in constraint.hip and gemm_f64.hip.
+// constraint (a dense matrix, the band of ConstraintMatrix, constraint.py:167-207, or a list of
+// directed entries) and the GEMM chain of ConstraintPropagation; kernels in constraint.hip and
+// gemm_f64.hip.
+#include <algorithm>
+#include <cmath>
 #include <limits>
+#include <utility>
+#include <vector>
 
 #include "handle.h"
 
@@ -52,14 +57,41 @@ static int neumann_steps(sc_handle h, double alpha, int* out) {
   return SC_OK;
 }
 
+// A resident entry list on the device (sc_set_constraint_pairs): Q[rows[e], cols[e]] = vals[e]
+struct DevPairs {
+  const int32_t* rows = nullptr;
+  const int32_t* cols = nullptr;
+  const double* vals = nullptr;
+  int k = 0;
+};
+static DevPairs resident_pairs(sc_handle h) {
+  DevPairs p;
+  p.k = h->pairs_count;
+  p.vals = ptr<double>(h->Cpairs);
+  p.rows = reinterpret_cast<const int32_t*>(p.vals + p.k);
+  p.cols = p.rows + p.k;
+  return p;
+}
+
+// `pairs` (k <= n entries, or nullptr): Q is that list; neither q nor band is read, and the last
+// stage -- T^T Q^T, T X^T and the adjustment -- is the panels U, V and one kernel that forms
+// U V^T tile by tile and adjusts A with it (constraint.hip).  The panels take two work matrices
+// the chain has left idle; a symmetric A then needs four cp[] matrices instead of five.
 static int constraint_propagation(sc_handle h, const double* a, bool sym_a, const double* q,
-                                  bool sym_q, const double* band, bool banded, double alpha,
-                                  double* out, int n, int ld) {
+                                  bool sym_q, const double* band, bool banded,
+                                  const DevPairs* pairs, double alpha, double* out, int n,
+                                  int ld) {
   hipStream_t s = h->stream;
   int steps = 0;
   SC_TRY(neumann_steps(h, alpha, &steps));
+  if (pairs && pairs->k == 0) {  // Q = 0: F = 0 and the adjustment is the identity
+    if (out != a)
+      SC_HIP(h, hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), a, (size_t)ld * sizeof(double),
+                                 (size_t)n * sizeof(double), n, hipMemcpyDeviceToDevice, s));
+    return SC_OK;
+  }
   const size_t bytes = (size_t)n * ld * sizeof(double);
-  for (int i = 0; i < 5; ++i) SC_TRY(grow(h, h->cp[i], bytes));
+  for (int i = 0; i < (pairs && sym_a ? 4 : 5); ++i) SC_TRY(grow(h, h->cp[i], bytes));
   SC_TRY(ensure_tilemap(h, n));
   double* P = ptr<double>(h->cp[0]);
   double* T = ptr<double>(h->cp[1]);
@@ -93,6 +125,27 @@ static int constraint_propagation(sc_handle h, const double* a, bool sym_a, cons
   if (!sym_a) {
     launch_transpose(s, T, Tn, n, ld);
     Tt = Tn;
+  }
+  if (pairs) {
+    // idle now: Pn, and Tn (symmetric A) or X (general A, whose Tn holds T^T)
+    CpPairItem m;
+    m.tu = Tt;
+    m.tv = T;
+    m.rows = pairs->rows;
+    m.cols = pairs->cols;
+    m.vals = pairs->vals;
+    m.U = Pn;
+    m.V = sym_a ? Tn : X;
+    m.a = a;
+    m.out = out;
+    m.n = n;
+    m.ld = ld;
+    m.k = pairs->k;
+    m.kp = cp_pair_panel_width(pairs->k);
+    m.sym = sym_a && sym_q;
+    launch_cp_pair_panels(s, m);
+    launch_cp_pairs_adjust(s, m, (1.0 - alpha) * (1.0 - alpha));
+    return check_last(h, "constraint propagation launch");
   }
   if (banded)
     launch_cp_band_product(s, Tt, band, X, n, ld);
@@ -161,27 +214,79 @@ int constraint_propagation_group(sc_handle lead, hipStream_t s, const CpGroupMem
     launch_gemm_nt_pair_group(s, gm, count, kEpiAdd);
     for (int z = 0; z < count; ++z) std::swap(T[z], Tn[z]);
   }
+  // The last stage, twice: the band members with the pair members idle, then the reverse (a
+  // launch without live members is skipped).
   // X = T Q^T into the idle partner of T,  T Q T = T X^T into the idle partner of P
-  for (int z = 0; z < count; ++z)
-    if (mem[z].n > 0) it[z] = CpItem{T[z], mem[z].band, Tn[z], nullptr, mem[z].n, mem[z].ld};
-  launch_cp_band_product_group(s, it, count);
-  for (int z = 0; z < count; ++z) product(z, T[z], Tn[z], Pn[z], nullptr);
-  launch_gemm_nt_pair_group(s, gm, count, kEpiNone);
-  for (int z = 0; z < count; ++z)
-    if (mem[z].n > 0) it[z] = CpItem{Pn[z], mem[z].A, mem[z].A, nullptr, mem[z].n, mem[z].ld};
-  launch_cp_adjust_group(s, it, count, (1.0 - alpha) * (1.0 - alpha));
+  bool any_band = false, any_pairs = false;
+  for (int z = 0; z < count; ++z) {
+    it[z].n = 0;
+    if (mem[z].n <= 0) continue;
+    if (mem[z].pairs) {
+      any_pairs = any_pairs || mem[z].pk > 0;  // (no entries: Q = 0, A stays as it is)
+      continue;
+    }
+    any_band = true;
+    it[z] = CpItem{T[z], mem[z].band, Tn[z], nullptr, mem[z].n, mem[z].ld};
+  }
+  if (any_band) {
+    launch_cp_band_product_group(s, it, count);
+    for (int z = 0; z < count; ++z) {
+      product(z, T[z], Tn[z], Pn[z], nullptr);
+      if (mem[z].pairs) gm[z] = GemmPairItem();
+    }
+    launch_gemm_nt_pair_group(s, gm, count, kEpiNone);
+    for (int z = 0; z < count; ++z)
+      if (it[z].n > 0) it[z] = CpItem{Pn[z], mem[z].A, mem[z].A, nullptr, mem[z].n, mem[z].ld};
+    launch_cp_adjust_group(s, it, count, (1.0 - alpha) * (1.0 - alpha));
+  }
+  if (any_pairs) {
+    // the panels into the idle partners of P and T (T is symmetric: it is its own transpose)
+    CpPairItem pm[kGroupMax];
+    memset(pm, 0, sizeof(pm));
+    for (int z = 0; z < count; ++z) {
+      const CpGroupMember& m = mem[z];
+      if (m.n <= 0 || !m.pairs || m.pk <= 0) continue;
+      if (m.pk > m.n)
+        return fail(lead, SC_ERR_INVALID, "a grouped entry list holds at most n entries");
+      CpPairItem& p = pm[z];
+      p.tu = p.tv = T[z];
+      p.rows = m.prows;
+      p.cols = m.pcols;
+      p.vals = m.pvals;
+      p.U = Pn[z];
+      p.V = Tn[z];
+      p.a = p.out = m.A;
+      p.n = m.n;
+      p.ld = m.ld;
+      p.k = m.pk;
+      p.kp = cp_pair_panel_width(m.pk);
+      p.sym = m.psym ? 1 : 0;
+    }
+    launch_cp_pair_panels_group(s, pm, count);
+    launch_cp_pairs_adjust_group(s, pm, count, (1.0 - alpha) * (1.0 - alpha));
+  }
   return check_last(lead, "grouped constraint propagation launch");
 }
 
-// cfg's constraint operator on `a` with the resident constraint (dense or banded); out may
-// alias a
+// cfg's constraint operator on `a` with the resident constraint (dense, banded or an entry
+// list); out may alias a.
+// The route of an entry list of K directed entries (derived, not tuned): AffinityIntegration
+// always takes the list.  ConstraintPropagation takes it while K <= n: the pair stage then does
+// at most n^3 of the dense stage's 3 n^3 flops and needs no n x n temporary beyond T.  For K > n
+// the entries are scattered into the zero-filled Cq on the device and the dense stage runs.
 int adjust_affinity(sc_handle h, const sc_config* cfg, const double* a, bool sym_a,
                            double* out, int n, int ld) {
   if (cfg->constraint_name == SC_CONSTRAINT_AFFINITY_INTEGRATION) {
     if (cfg->integration_type != SC_INTEGRATION_MAX &&
         cfg->integration_type != SC_INTEGRATION_AVERAGE)
       return fail(h, SC_ERR_INVALID, "Unsupported integration type");
-    if (h->constraint_banded)
+    if (h->constraint_pairs) {
+      const DevPairs p = resident_pairs(h);
+      SC_TRY(grow(h, h->Cporig, (size_t)std::max(p.k, 1) * sizeof(double)));
+      launch_affinity_integration_pairs(h->stream, a, p.rows, p.cols, p.vals, p.k,
+                                        ptr<double>(h->Cporig), out, n, ld,
+                                        cfg->integration_type);
+    } else if (h->constraint_banded)
       launch_affinity_integration_band(h->stream, a, ptr<double>(h->Cband), out, n, ld,
                                        cfg->integration_type);
     else
@@ -189,11 +294,69 @@ int adjust_affinity(sc_handle h, const sc_config* cfg, const double* a, bool sym
                                   cfg->integration_type);
     return check_last(h, "affinity integration launch");
   }
-  if (cfg->constraint_name == SC_CONSTRAINT_PROPAGATION)
+  if (cfg->constraint_name == SC_CONSTRAINT_PROPAGATION) {
+    if (h->constraint_pairs) {
+      const DevPairs p = resident_pairs(h);
+      if (p.k <= n)
+        return constraint_propagation(h, a, sym_a, nullptr, h->constraint_symmetric, nullptr,
+                                      false, &p, cfg->constraint_alpha, out, n, ld);
+      int steps = 0;
+      SC_TRY(neumann_steps(h, cfg->constraint_alpha, &steps));  // (before Cq is allocated)
+      const size_t bytes = (size_t)n * ld * sizeof(double);
+      SC_TRY(grow(h, h->Cq, bytes));
+      SC_HIP(h, hipMemsetAsync(h->Cq.p, 0, bytes, h->stream));
+      launch_pairs_to_dense(h->stream, p.rows, p.cols, p.vals, p.k, ld, ptr<double>(h->Cq));
+      return constraint_propagation(h, a, sym_a, ptr<double>(h->Cq), h->constraint_symmetric,
+                                    nullptr, false, nullptr, cfg->constraint_alpha, out, n, ld);
+    }
     return constraint_propagation(h, a, sym_a, ptr<double>(h->Cq), h->constraint_symmetric,
-                                  ptr<double>(h->Cband), h->constraint_banded,
+                                  ptr<double>(h->Cband), h->constraint_banded, nullptr,
                                   cfg->constraint_alpha, out, n, ld);
+  }
   return fail(h, SC_ERR_INVALID, "constraint_name must be a ConstraintName");
+}
+
+// An entry list as the caller gives it (host memory): every index inside [0, n), every value
+// finite, no position twice -- and whether it is symmetric (every (r, c, v) with r != c has its
+// twin (c, r, v)), all on the host, O(K log K)
+int validate_constraint_pairs(sc_handle h, const int32_t* rows, const int32_t* cols,
+                              const double* vals, int count, int n, bool* symmetric) {
+  if (count < 0 || (count > 0 && (!rows || !cols || !vals)))
+    return fail(h, SC_ERR_INVALID, "a constraint entry list holds rows, cols and vals");
+  std::vector<std::pair<int64_t, double>> at((size_t)count);
+  for (int e = 0; e < count; ++e) {
+    if (rows[e] < 0 || rows[e] >= n || cols[e] < 0 || cols[e] >= n)
+      return fail(h, SC_ERR_INVALID, "constraint entry index outside [0, n)");
+    if (!std::isfinite(vals[e]))
+      return fail(h, SC_ERR_INVALID, "constraint entry values must be finite");
+    at[e] = {(int64_t)rows[e] * n + cols[e], vals[e]};
+  }
+  std::sort(at.begin(), at.end());
+  for (int e = 1; e < count; ++e)
+    if (at[e].first == at[e - 1].first)
+      return fail(h, SC_ERR_INVALID, "a constraint entry position is listed twice");
+  bool sym = true;
+  for (int e = 0; e < count && sym; ++e) {
+    const int64_t r = at[e].first / n, c = at[e].first % n;
+    if (r == c) continue;
+    const auto twin = std::lower_bound(at.begin(), at.end(),
+                                       std::make_pair(c * n + r, -HUGE_VAL));
+    sym = twin != at.end() && twin->first == c * n + r && twin->second == at[e].second;
+  }
+  *symmetric = sym;
+  return SC_OK;
+}
+// vals | rows | cols as Cpairs holds them: 16 bytes per entry
+std::vector<double> pack_constraint_pairs(const int32_t* rows, const int32_t* cols,
+                                          const double* vals, int count) {
+  std::vector<double> packed((size_t)2 * count);
+  if (count > 0) {
+    memcpy(packed.data(), vals, (size_t)count * sizeof(double));
+    int32_t* index = reinterpret_cast<int32_t*>(packed.data() + count);
+    memcpy(index, rows, (size_t)count * sizeof(int32_t));
+    memcpy(index + count, cols, (size_t)count * sizeof(int32_t));
+  }
+  return packed;
 }
 
 extern "C" int sc_set_constraint(sc_handle h, const double* q, int n) {
@@ -205,7 +368,7 @@ extern "C" int sc_set_constraint(sc_handle h, const double* q, int n) {
   SC_TRY(h2d_matrix(h, q, n, n, ptr<double>(h->Cq), ld));
   SC_TRY(device_is_symmetric(h, ptr<double>(h->Cq), n, ld, &h->constraint_symmetric));
   h->have_constraint = true;
-  h->constraint_banded = false;
+  h->constraint_banded = h->constraint_pairs = false;
   h->qn = n;
   return SC_OK;
 }
@@ -226,15 +389,49 @@ extern "C" int sc_set_constraint_band(sc_handle h, const double* band, int n) {
   }
   h->have_constraint = true;
   h->constraint_banded = true;
+  h->constraint_pairs = false;
   h->constraint_symmetric = true;
   h->qn = n;
+  return SC_OK;
+}
+
+// A constraint matrix given as its `count` non-zero entries: count x (4 + 4 + 8) bytes up,
+// nothing else; symmetry is decided on the host while validating
+extern "C" int sc_set_constraint_pairs(sc_handle h, const int32_t* rows, const int32_t* cols,
+                                       const double* vals, int count, int n) {
+  if (!h) return SC_ERR_INVALID;
+  if (n <= 0) return fail(h, SC_ERR_INVALID, "constraint matrix must be (n, n)");
+  bool symmetric = true;
+  SC_TRY(validate_constraint_pairs(h, rows, cols, vals, count, n, &symmetric));
+  SC_HIP(h, hipSetDevice(h->device));
+  const size_t bytes = (size_t)count * 2 * sizeof(double);
+  SC_TRY(grow(h, h->Cpairs, bytes));
+  if (bytes > 0) {
+    const std::vector<double> packed = pack_constraint_pairs(rows, cols, vals, count);
+    SC_HIP(h, hipMemcpyAsync(h->Cpairs.p, packed.data(), bytes, hipMemcpyHostToDevice,
+                             h->stream));
+    SC_HIP(h, hipStreamSynchronize(h->stream));  // (pageable source)
+  }
+  h->have_constraint = true;
+  h->constraint_banded = false;
+  h->constraint_pairs = true;
+  h->constraint_symmetric = symmetric;
+  h->pairs_count = count;
+  h->qn = n;
+  return SC_OK;
+}
+
+extern "C" int sc_constraint_pairs_info(sc_handle h, int* count, size_t* pair_bytes) {
+  if (!h) return SC_ERR_INVALID;
+  if (count) *count = h->have_constraint && h->constraint_pairs ? h->pairs_count : 0;
+  if (pair_bytes) *pair_bytes = h->Cpairs.bytes;
   return SC_OK;
 }
 
 extern "C" int sc_clear_constraint(sc_handle h) {
   if (!h) return SC_ERR_INVALID;
   h->have_constraint = false;
-  h->constraint_banded = false;
+  h->constraint_banded = h->constraint_pairs = false;
   h->qn = 0;
   return SC_OK;
 }
@@ -242,7 +439,8 @@ extern "C" int sc_clear_constraint(sc_handle h) {
 extern "C" int sc_constraint_info(sc_handle h, int* kind, int* n, size_t* band_bytes,
                                   size_t* dense_bytes) {
   if (!h) return SC_ERR_INVALID;
-  if (kind) *kind = !h->have_constraint ? 0 : (h->constraint_banded ? 2 : 1);
+  if (kind)
+    *kind = !h->have_constraint ? 0 : (h->constraint_pairs ? 3 : (h->constraint_banded ? 2 : 1));
   if (n) *n = h->have_constraint ? h->qn : 0;
   if (band_bytes) *band_bytes = h->Cband.bytes;
   if (dense_bytes) *dense_bytes = h->Cq.bytes;
@@ -306,25 +504,53 @@ extern "C" int sc_stage_constraint_band(sc_handle h, const sc_config* cfg,
   return d2h_matrix(h, ptr<double>(h->A0), h->ldn, n, n, out);
 }
 
+extern "C" int sc_stage_constraint_pairs(sc_handle h, const sc_config* cfg,
+                                         const double* affinity, const int32_t* rows,
+                                         const int32_t* cols, const double* vals, int count, int n,
+                                         double* out) {
+  if (!h) return SC_ERR_INVALID;
+  SC_TRY(validate_config(h, cfg));
+  if (!affinity || !out || n <= 0)
+    return fail(h, SC_ERR_INVALID, "affinity must be (n, n)");
+  SC_TRY(sc_set_affinity(h, affinity, n));
+  SC_TRY(sc_set_constraint_pairs(h, rows, cols, vals, count, n));
+  const int rc = sc_apply_constraint(h, cfg);
+  sc_clear_constraint(h);
+  SC_TRY(rc);
+  return d2h_matrix(h, ptr<double>(h->A0), h->ldn, n, n, out);
+}
+
 // ConstraintPropagation of `count` affinities with banded constraints as ONE grouped chain,
 // through the launchers a constrained batch uses (tests).  Owns its device memory: per member the
 // affinity and the four work matrices at the arena's row pitch, all of it -- padding columns and
 // workspaces -- quiet NaNs before the inputs go in, so a read outside a matrix shows in the result.
-extern "C" int sc_stage_constraint_band_group(sc_handle h, const sc_config* cfg, int count,
-                                              const int32_t* ns, const double* const* affinities,
-                                              const double* const* bands, double* const* outs) {
-  if (!h) return SC_ERR_INVALID;
+// bands == nullptr: the members' constraints are entry lists (rows[z], cols[z], vals[z], counts[z]
+// <= ns[z] entries) instead, in NaN-filled buffers of their own.
+static int stage_constraint_group(sc_handle h, const sc_config* cfg, int count, const int32_t* ns,
+                                  const double* const* affinities, const double* const* bands,
+                                  const int32_t* const* rows, const int32_t* const* cols,
+                                  const double* const* vals, const int32_t* counts,
+                                  double* const* outs) {
   SC_TRY(validate_config(h, cfg));
-  if (count < 1 || count > kGroupMax || !ns || !affinities || !bands || !outs)
+  if (count < 1 || count > kGroupMax || !ns || !affinities || !outs ||
+      (!bands && (!rows || !cols || !vals || !counts)))
     return fail(h, SC_ERR_INVALID, "a constraint group holds 1 .. 16 members");
+  bool list_symmetric[kGroupMax] = {};
   for (int z = 0; z < count; ++z) {
     if (ns[z] < 0) return fail(h, SC_ERR_INVALID, "n must not be negative (0: idle member)");
     // (larger tile grids get their order uploaded per size: one per handle at a time)
     if (gemm_tile_dim(ns[z]) > kTilemapTableMax)
       return fail(h, SC_ERR_UNSUPPORTED, "a member of the constraint group is larger than 8192");
-    const bool idle = ns[z] == 0 || (!bands[z] && ns[z] > 1);
+    const bool idle = ns[z] == 0 || (bands && !bands[z] && ns[z] > 1);
     if (!idle && (!affinities[z] || !outs[z]))
       return fail(h, SC_ERR_INVALID, "affinity must be (n, n) and the band hold n - 1 values");
+    if (!idle && !bands) {
+      if (counts[z] > ns[z])
+        return fail(h, SC_ERR_UNSUPPORTED,
+                    "an entry list of more than n entries takes the dense route: not grouped");
+      SC_TRY(validate_constraint_pairs(h, rows[z], cols[z], vals[z], counts[z], ns[z],
+                                       &list_symmetric[z]));
+    }
   }
   int steps = 0;
   SC_TRY(neumann_steps(h, cfg->constraint_alpha, &steps));  // (before anything is allocated)
@@ -350,12 +576,29 @@ extern "C" int sc_stage_constraint_band_group(sc_handle h, const sc_config* cfg,
     return SC_OK;
   };
   CpGroupMember mem[kGroupMax];
+  std::vector<double> packed[kGroupMax];  // (pageable sources of the entry uploads)
   for (int z = 0; z < count; ++z) {
     const int n = ns[z];
-    if (n == 0 || (!bands[z] && n > 1)) continue;  // idle
+    if (n == 0 || (bands && !bands[z] && n > 1)) continue;  // idle
     const int ld = matrix_ld(n);
     CpGroupMember& m = mem[z];
     double* band = nullptr;
+    if (!bands) {
+      double* packed_dev = nullptr;
+      const int k = counts[z];
+      SC_TRY(device_nan((size_t)2 * k, &packed_dev));
+      if (k > 0) {
+        packed[z] = pack_constraint_pairs(rows[z], cols[z], vals[z], k);
+        SC_HIP(h, hipMemcpyAsync(packed_dev, packed[z].data(), (size_t)2 * k * sizeof(double),
+                                 hipMemcpyHostToDevice, s));
+      }
+      m.pairs = true;
+      m.psym = list_symmetric[z];
+      m.pk = k;
+      m.pvals = packed_dev;
+      m.prows = reinterpret_cast<const int32_t*>(packed_dev + k);
+      m.pcols = m.prows + k;
+    }
     SC_TRY(device_nan((size_t)n * ld, &m.A));
     SC_TRY(device_nan((size_t)n * ld, &m.P));
     SC_TRY(device_nan((size_t)n * ld, &m.T));
@@ -365,7 +608,7 @@ extern "C" int sc_stage_constraint_band_group(sc_handle h, const sc_config* cfg,
     SC_TRY(device_nan(round_up(n, 16), &m.rowmax));
     SC_TRY(device_nan(n - 1, &band));
     SC_TRY(h2d_matrix(h, affinities[z], n, n, m.A, ld));  // (same stream: after the fill)
-    if (n > 1)
+    if (bands && n > 1)
       SC_HIP(h, hipMemcpyAsync(band, bands[z], (size_t)(n - 1) * sizeof(double),
                                hipMemcpyHostToDevice, s));
     SC_TRY(ensure_tilemap(h, n));
@@ -380,4 +623,28 @@ extern "C" int sc_stage_constraint_band_group(sc_handle h, const sc_config* cfg,
     if (mem[z].n > 0) SC_TRY(d2h_matrix(h, mem[z].A, mem[z].ld, mem[z].n, mem[z].n, outs[z]));
   SC_HIP(h, hipStreamSynchronize(s));
   return SC_OK;
+}
+
+extern "C" int sc_stage_constraint_band_group(sc_handle h, const sc_config* cfg, int count,
+                                              const int32_t* ns, const double* const* affinities,
+                                              const double* const* bands, double* const* outs) {
+  if (!h) return SC_ERR_INVALID;
+  if (!bands) return fail(h, SC_ERR_INVALID, "a constraint group holds 1 .. 16 members");
+  return stage_constraint_group(h, cfg, count, ns, affinities, bands, nullptr, nullptr, nullptr,
+                                nullptr, outs);
+}
+
+// the same with each member's constraint as an entry list (sc_set_constraint_pairs)
+extern "C" int sc_stage_constraint_pairs_group(sc_handle h, const sc_config* cfg, int count,
+                                               const int32_t* ns,
+                                               const double* const* affinities,
+                                               const int32_t* const* rows,
+                                               const int32_t* const* cols,
+                                               const double* const* vals, const int32_t* counts,
+                                               double* const* outs) {
+  if (!h) return SC_ERR_INVALID;
+  if (!rows || !cols || !vals || !counts)
+    return fail(h, SC_ERR_INVALID, "a constraint group holds 1 .. 16 members");
+  return stage_constraint_group(h, cfg, count, ns, affinities, nullptr, rows, cols, vals, counts,
+                                outs);
 }

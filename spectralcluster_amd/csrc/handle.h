@@ -62,6 +62,11 @@ struct sc_handle_s {
   DevBuf Cband;
   bool have_constraint = false, constraint_symmetric = false, constraint_applied = false;
   bool constraint_banded = false;  // the resident constraint is Cband, not Cq
+  // ... or a list of directed entries (sc_set_constraint_pairs): Cpairs holds vals (pairs_count
+  // doubles), then rows, then cols (int32 each); Cporig: pairs_count doubles of scratch
+  DevBuf Cpairs, Cporig;
+  bool constraint_pairs = false;  // the resident constraint is Cpairs (never with _banded)
+  int pairs_count = 0;
   bool affinity_symmetric = true;
   bool affinity_from_embeddings = false;  // symflag[1] then says whether a row was NaN
   int qn = 0;
@@ -506,11 +511,23 @@ struct CpGroupMember {
   double *deg = nullptr, *rowmax = nullptr;
   const double* band = nullptr;
   const int2* tilemap = nullptr;
+  // pairs: the constraint is not the band but pk <= n directed entries Q[prows[e], pcols[e]] =
+  // pvals[e] on the device (psym: the list is symmetric); pk = 0 leaves A as it is
+  bool pairs = false, psym = false;
+  int pk = 0;
+  const int32_t *prows = nullptr, *pcols = nullptr;
+  const double* pvals = nullptr;
 };
 int constraint_propagation_group(sc_handle lead, hipStream_t s, const CpGroupMember* mem,
                                  int count, double alpha);
-// the body of sc_predict_batch_constrained (batch_group.hip)
-int predict_batch_constrained_impl(sc_handle h, const sc_array* xs, const double* const* bands,
+// sc_set_constraint_pairs' checks of a host entry list, and whether it is symmetric
+int validate_constraint_pairs(sc_handle h, const int32_t* rows, const int32_t* cols,
+                              const double* vals, int count, int n, bool* symmetric);
+// vals | rows | cols as Cpairs holds them: 16 bytes per entry
+std::vector<double> pack_constraint_pairs(const int32_t* rows, const int32_t* cols,
+                                          const double* vals, int count);
+// the body of sc_predict_batch_constraints (batch_group.hip); cons == nullptr: no constraints
+int predict_batch_constrained_impl(sc_handle h, const sc_array* xs, const sc_constraint_desc* cons,
                                    const int* ns, int d, int count, const sc_config* cfg,
                                    int64_t* const* labels, sc_diag* diags, int group);
 

@@ -386,6 +386,37 @@ void launch_cp_prepare_group(hipStream_t s, const CpItem* items, int count, doub
 void launch_cp_band_product_group(hipStream_t s, const CpItem* items, int count);
 // launch_cp_adjust per member: src = T Q T, vec = A (n x ld), dst = out (may be A)
 void launch_cp_adjust_group(hipStream_t s, const CpItem* items, int count, double scale);
+// ConstraintPropagation's last stage against a constraint of k <= n directed entries
+// Q[rows[e], cols[e]] = vals[e] (constraint.hip), one matrix or one member of a group (n = 0:
+// idle); everything on the device.
+struct CpPairItem {
+  const double* tu;     // n x ld: T^T (T itself when T is symmetric) -- the source of U
+  const double* tv;     // n x ld: T -- the source of V
+  const int32_t* rows;  // k entries
+  const int32_t* cols;
+  const double* vals;
+  double* U;            // n x kp panels, U V^T = T Q T; neither may alias tu / tv
+  double* V;
+  const double* a;      // n x ld affinity
+  double* out;          // n x ld adjusted affinity, may be a
+  int n, ld;
+  int k, kp;            // kp = cp_pair_panel_width(k)
+  int sym;              // a and the entry list are symmetric: out is written exactly symmetric
+};
+int cp_pair_panel_width(int k);  // round_up(max(k, 1), 16)
+void launch_cp_pair_panels(hipStream_t s, const CpPairItem& m);                // fills U, V
+void launch_cp_pairs_adjust(hipStream_t s, const CpPairItem& m, double scale);  // U, V, a -> out
+void launch_cp_pair_panels_group(hipStream_t s, const CpPairItem* items, int count);
+void launch_cp_pairs_adjust_group(hipStream_t s, const CpPairItem* items, int count,
+                                  double scale);
+// AffinityIntegration against such a list (any k, no two entries at one position); orig: k
+// doubles of scratch; out may alias a
+void launch_affinity_integration_pairs(hipStream_t s, const double* a, const int32_t* rows,
+                                       const int32_t* cols, const double* vals, int k,
+                                       double* orig, double* out, int n, int ld, int type);
+// q[rows[e], cols[e]] = vals[e] into an (n, ld) matrix the caller has zero-filled
+void launch_pairs_to_dense(hipStream_t s, const int32_t* rows, const int32_t* cols,
+                           const double* vals, int k, int ld, double* q);
 void launch_cut_percentile_group(hipStream_t s, const FrontItem* items, int count, int zero_diag);
 void launch_row_stats_group(hipStream_t s, const FrontItem* items, int count);
 bool blur_group_supported(int n_min, int radius);

@@ -143,10 +143,20 @@ class SpectralClusterer:
     """Make `constraint_matrix` resident (or clear a stale one).  Like the reference
     (spectral_clusterer.py:137-142, 259-264) it is used only when both
     `constraint_options` and the matrix are given.  A `ConstraintMatrix` goes up as its band
-    of n - 1 values (`sc_set_constraint_band`), anything else as a dense (n, n) array."""
+    of n - 1 values (`sc_set_constraint_band`), a `PairwiseConstraints` as its directed entries
+    (`sc_set_constraint_pairs`), anything else as a dense (n, n) array."""
     if self.constraint_options is None or constraint_matrix is None:
       handle.check(handle.lib.sc_clear_constraint(handle.raw))
       return False
+    if isinstance(constraint_matrix, constraint_lib.PairwiseConstraints):
+      self.constraint_options.constraint_operator.check_input(
+          np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)),
+          constraint_matrix)
+      rows, cols, vals = constraint_matrix.entries()
+      handle.check(handle.lib.sc_set_constraint_pairs(
+          handle.raw, _lib.as_int32_p(rows), _lib.as_int32_p(cols), _lib.as_double_p(vals),
+          len(vals), n))
+      return True
     if isinstance(constraint_matrix, constraint_lib.ConstraintMatrix):
       self.constraint_options.constraint_operator.check_input(
           np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)),
@@ -435,7 +445,13 @@ class SpectralClusterer:
     the after-refinement operators run per utterance inside the group's front; an utterance
     whose entry is None is clustered as in a batch without constraints.  A `ConstraintMatrix`
     whose length is not its utterance's raises the ValueError of predict() before anything is
-    launched.  Anything else -- a dense ndarray among the entries, AutoTune (the Turn-to-Diarize
+    launched.  `PairwiseConstraints` entries are taken in the same way, in any mix with the
+    other two: with one among them the call is `sc_predict_batch_constraints`, each list (K
+    directed entries, 16 bytes each) resident in its member arena, the last stage of the chain
+    run once for the band members and once for the pair members of a group; a list of more
+    entries than its utterance has rows runs that utterance as a single call (route 0), and one
+    whose n is not its utterance's raises predict()'s ValueError before anything is launched.
+    Anything else -- a dense ndarray among the entries, AutoTune (the Turn-to-Diarize
     preset), group=1, `streams` -- runs as per-utterance `predict(u, c)` calls (routes all 0).
 
     `autotune_from_entry_state` (a clusterer without AutoTune ignores it).  `AutoTune.tune`
@@ -565,7 +581,8 @@ class SpectralClusterer:
           cosine = False
         if not (library_batch and cosine and streams is None and
                 (group is None or int(group) > 1) and
-                all(c is None or isinstance(c, constraint_lib.ConstraintMatrix)
+                all(c is None or isinstance(c, (constraint_lib.ConstraintMatrix,
+                                                constraint_lib.PairwiseConstraints))
                     for c in constraint_matrices)):
           self.last_batch_routes = [_lib.BATCH_ROUTE_SINGLE] * len(utterances)
           return [self.predict(u, c) for u, c in zip(utterances, constraint_matrices)]
@@ -609,6 +626,9 @@ class SpectralClusterer:
           # (predict()'s check and message: _set_constraint)
           self.constraint_options.constraint_operator.check_input(
               np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)), cm)
+          if isinstance(cm, constraint_lib.PairwiseConstraints):
+            bands.append(cm.entries())  # (rows, cols, vals)
+            continue
           band = np.zeros(max(n - 1, 1), dtype=np.float64)  # (n = 1: no values, a valid pointer)
           band[:n - 1] = cm.band()
           bands.append(band)
@@ -625,6 +645,19 @@ class SpectralClusterer:
             handle.raw, (_lib.ScArray * count)(*[src.array for src in sources]), count,
             self.build_config(), ctypes.byref(single_check), lp, diags, int(group), single),
             TypeError)
+      elif banded is not None and any(isinstance(b, tuple) for b in bands):
+        # entry lists among the constraints: one descriptor per utterance
+        arrays = (_lib.ScArray * count)(*[src.array for src in sources])
+        cons = (_lib.ScConstraintDesc * count)()
+        for desc, b in zip(cons, bands):
+          if isinstance(b, tuple):
+            desc.kind, desc.count = 3, len(b[2])
+            desc.rows, desc.cols = _lib.as_int32_p(b[0]), _lib.as_int32_p(b[1])
+            desc.vals = _lib.as_double_p(b[2])
+          elif b is not None:
+            desc.kind, desc.band = 2, _lib.as_double_p(b)
+        handle.check(handle.lib.sc_predict_batch_constraints(
+            handle.raw, arrays, cons, count, self.build_config(), lp, diags, int(group)), TypeError)
       elif banded is not None:
         arrays = (_lib.ScArray * count)(*[src.array for src in sources])
         bp = (ctypes.POINTER(ctypes.c_double) * count)(
