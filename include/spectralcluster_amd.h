@@ -334,6 +334,22 @@ int sc_compute_affinity(sc_handle h);
 /* H2D of a caller-supplied (n, n) affinity (custom affinity_function /
  * _compute_eigenvectors_ncluster(affinity), spectral_clusterer.py:108). */
 int sc_set_affinity(sc_handle h, const double* affinity, int n);
+/* ... of a described (n, n) source, read where it is: device or host memory, fp64 / fp32 / fp16 /
+ * bf16, any non-negative element strides (a transposed view, a [::2, ::2] slice).  It is widened
+ * exactly on the device, so the resident affinity is bit for bit the source converted to double
+ * on the host; the padding columns n .. ld of the resident rows are zero.  A device source and a
+ * narrow host source are widened by one kernel that decides the exact symmetry of the matrix in
+ * the same pass; a host fp64 source goes up by a 2-D copy as in sc_set_affinity.  The handle's
+ * state afterwards is that of sc_set_affinity.  SC_ERR_INVALID before any launch for what
+ * sc_predict_array rejects and for rows != cols.  Returns with the handle's stream synchronised:
+ * the source may be overwritten or freed at once. */
+int sc_set_affinity_array(sc_handle h, const sc_array* affinity);
+/* predict() from an affinity the caller holds: sc_set_affinity_array, the before-refinement
+ * constraint if one is resident, sc_eig_ncluster, sc_cluster -- sc_predict_array without the
+ * embeddings and the affinity GEMM.  diag->stage_ms[SC_STAGE_AFFINITY] is the constraint's time
+ * (the ingest is host-synchronous: time it on the host). */
+int sc_predict_affinity_array(sc_handle h, const sc_array* affinity, const sc_config* cfg,
+                              int64_t* labels, sc_diag* diag);
 /*
  * SpectralClusterer._compute_eigenvectors_ncluster (spectral_clusterer.py:
  * 108-168) on the resident affinity, which is left untouched (AutoTune calls
@@ -523,6 +539,19 @@ int sc_constraint_desc_layout(int* bytes, int* field_offsets);
 int sc_predict_batch_constraints(sc_handle h, const sc_array* xs, const sc_constraint_desc* cons,
                                  int count, const sc_config* cfg, int64_t* const* labels,
                                  sc_diag* diags, int group);
+/* [predict_affinity(a_i, c_i)]: sc_predict_batch_constraints for (n_i, n_i) affinities the caller
+ * holds (sc_set_affinity_array's sources, any mix of dtypes, layouts and locations) instead of
+ * embeddings; cons may be NULL.  The same routes (sc_last_batch_routes): n <= 128 in Jacobi waves
+ * of up to 64, 128 < n < 4096 as lockstep groups of up to `group`, the rest and members that leave
+ * their route as single calls inside the call.  A group or wave is ingested by ONE
+ * k_ingest_affinity_group launch, and the host reads its members' symmetry flags in one wait;
+ * the members then take the member-by-member front (the fused fronts read CropDiagonal's value
+ * and a cosine bound from the affinity GEMM's epilogue).  A member that is not symmetric and
+ * whose sequence does not symmetrise it leaves its route for the general solver.  With a device
+ * source the handle's stream is synchronised once at entry; sources stay valid until return. */
+int sc_predict_batch_affinities(sc_handle h, const sc_array* affinities,
+                                const sc_constraint_desc* cons, int count, const sc_config* cfg,
+                                int64_t* const* labels, sc_diag* diags, int group);
 /* What ran: one code per utterance of the last sc_predict_batch* call on this handle (a
  * member of a grouped batch that was handed back to the single-call path reports
  * SC_BATCH_ROUTE_SINGLE; after sc_predict_batch / sc_predict_batch_streams every code is).
@@ -794,6 +823,14 @@ int sc_naive_cluster(sc_handle h, const double* x, int n, int d, double threshol
  *      per-op Python classes use these) ------------------------------------- */
 /* the ingest alone: out receives the (rows, cols) fp64 values the pipeline sees for `x` */
 int sc_stage_ingest(sc_handle h, const sc_array* x, double* out);
+/* the affinity ingest alone, on destination memory filled with NaNs: out receives the n rows of
+ * matrix_ld(n) doubles as sc_set_affinity_array left them (matrix_ld(n): n rounded up to 16, plus
+ * 16 where that is a multiple of 512), padding included, *symmetric the flag of the same pass */
+int sc_stage_affinity_ingest(sc_handle h, const sc_array* affinity, double* out, int* symmetric);
+/* ... of `count` (<= 64) matrices by ONE grouped launch (host sources staged at their own width
+ * first): outs[i] receives member i's rows, symmetric[i] its flag */
+int sc_stage_affinity_ingest_group(sc_handle h, const sc_array* affinities, int count,
+                                   double* const* outs, int* symmetric);
 /* utils.compute_affinity_matrix (utils.py:20-41) */
 int sc_stage_affinity(sc_handle h, const double* x, int n, int d, double* out);
 /* AffinityRefinementOperation.refine (refinement.py:136-245); op = sc_op,

@@ -117,10 +117,16 @@ class Source:
       pass
 
 
-def _from_numpy(a: np.ndarray) -> Source:
+def _from_numpy(a: np.ndarray, strided: bool = False) -> Source:
   if a.ndim != 2:
     raise ValueError("embeddings must be 2-dimensional")
   dtype = _NUMPY_DTYPES.get(a.dtype)
+  if (strided and dtype is not None and
+      all(s >= 0 and s % a.itemsize == 0 for s in a.strides)):
+    # a view (a .T, a [::2, ::2] slice) is described as it lies: no host copy of n x n values
+    arr = _lib.ScArray(a.ctypes.data, dtype, _lib.SC_MEM_HOST, a.shape[0], a.shape[1],
+                       a.strides[0] // a.itemsize, a.strides[1] // a.itemsize)
+    return Source(arr, a, numpy=a)
   if dtype is None:  # ints, bools, longdouble, other byte orders: promoted on the host
     x = np.ascontiguousarray(a, dtype=np.float64)
     dtype = _lib.SC_DTYPE_F64
@@ -159,12 +165,15 @@ def _from_capsule(capsule, location: int) -> Source:
   return src
 
 
-def describe(embeddings, get_handle: typing.Callable[[], "_lib.Handle"]) -> Source:
+def describe(embeddings, get_handle: typing.Callable[[], "_lib.Handle"],
+             strided: bool = False) -> Source:
   """`embeddings` -> Source.  TypeError / ValueError for what cannot be taken, before any
   device call (`get_handle` is only called for an object that says it lives on a GPU: its
-  device must be the handle's, and the handle's stream goes to `__dlpack__`)."""
+  device must be the handle's, and the handle's stream goes to `__dlpack__`).  `strided`: a
+  NumPy view keeps its strides (the affinity entry points take them); otherwise it is made
+  contiguous on the host, as the embeddings paths expect."""
   if isinstance(embeddings, np.ndarray):
-    return _from_numpy(embeddings)
+    return _from_numpy(embeddings, strided)
   if not (hasattr(embeddings, "__dlpack__") and hasattr(embeddings, "__dlpack_device__")):
     raise TypeError("embeddings must be a numpy array")
   device_type, device_id = embeddings.__dlpack_device__()

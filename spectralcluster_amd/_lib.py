@@ -295,7 +295,21 @@ PROTOTYPES = {
                                                     ctypes.POINTER(ScConfig),
                                                     ctypes.POINTER(_c_int64_p),
                                                     ctypes.POINTER(ScDiag), ctypes.c_int]),
+    "sc_predict_batch_affinities": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),
+                                                   ctypes.POINTER(ScConstraintDesc), ctypes.c_int,
+                                                   ctypes.POINTER(ScConfig),
+                                                   ctypes.POINTER(_c_int64_p),
+                                                   ctypes.POINTER(ScDiag), ctypes.c_int]),
     "sc_stage_ingest": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray), _c_double_p]),
+    "sc_set_affinity_array": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray)]),
+    "sc_predict_affinity_array": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),
+                                                 ctypes.POINTER(ScConfig), _c_int64_p,
+                                                 ctypes.POINTER(ScDiag)]),
+    "sc_stage_affinity_ingest": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray), _c_double_p,
+                                                _c_int_p]),
+    "sc_stage_affinity_ingest_group": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),
+                                                      ctypes.c_int, ctypes.POINTER(_c_double_p),
+                                                      _c_int_p]),
     "sc_compute_affinity": (ctypes.c_int, [_handle_t]),
     "sc_set_affinity": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int]),
     "sc_eig_ncluster": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScConfig),

@@ -1043,10 +1043,17 @@ extern "C" int sc_get_eigenvectors(sc_handle h, double* out, int n, int ncols) {
 // ------------------------------------------------------------------------------
 extern "C" int sc_run_resident(sc_handle h, const sc_config* cfg, int64_t* labels,
                                sc_diag* diag) {
+  return run_resident(h, cfg, labels, diag, true);
+}
+
+int run_resident(sc_handle h, const sc_config* cfg, int64_t* labels, sc_diag* diag,
+                 bool from_embeddings) {
   if (!h) return SC_ERR_INVALID;
   SC_TRY(validate_config(h, cfg));
   if (!labels) return fail(h, SC_ERR_INVALID, "labels is NULL");
-  if (!h->have_x) return fail(h, SC_ERR_INVALID, "no embeddings resident");
+  if (from_embeddings && !h->have_x) return fail(h, SC_ERR_INVALID, "no embeddings resident");
+  if (!from_embeddings && (!h->have_affinity || h->affinity_from_embeddings))
+    return fail(h, SC_ERR_INVALID, "no caller-supplied affinity resident");
   SC_HIP(h, hipSetDevice(h->device));
   sc_diag local;
   sc_diag* dg = diag ? diag : &local;
@@ -1054,7 +1061,7 @@ extern "C" int sc_run_resident(sc_handle h, const sc_config* cfg, int64_t* label
   h->nev = 0;
   int e0, e1, e2;
   ev_rec(h, &e0);
-  SC_TRY(sc_compute_affinity(h));
+  if (from_embeddings) SC_TRY(sc_compute_affinity(h));
   if (constraint_active(h, cfg, true)) SC_TRY(sc_apply_constraint(h, cfg));  // :259-264
   ev_rec(h, &e1);
   // (no wait between the eigensolver and k-means: its launches queue behind the Ritz vectors)
@@ -1071,7 +1078,7 @@ extern "C" int sc_run_resident(sc_handle h, const sc_config* cfg, int64_t* label
   resolve_stage_times(h, dg);
   dg->stage_ms[SC_STAGE_AFFINITY] = ev_ms(h, e0, e1);
   dg->stage_ms[SC_STAGE_TOTAL] = ev_ms(h, e0, e2);
-  if (h->profile_level >= 1)
+  if (h->profile_level >= 1 && from_embeddings)
     dg->stage_ms[SC_STAGE_AFFINITY_GEMM] = ev_ms(h, h->aff_ev[0], h->aff_ev[1]);
   return SC_OK;
 }

@@ -98,6 +98,54 @@ int member_problem(sc_handle lead, sc_handle h, const sc_array& x, int n, int d,
   return SC_OK;
 }
 
+// The members of a front whose arrays are the callers' affinities (Bands::affinities): ONE grouped
+// ingest launch on `s` widens every member's matrix into its arena's A0 and leaves the members'
+// symmetry flags in one device array, which the host reads once -- the front's only wait; the
+// arenas then are in the state sc_set_affinity_array leaves.  Descriptor table, flags and the
+// staging rows of host members live in the first arena's staging buffer (the group owns it).
+int ingest_member_affinities(sc_handle lead, const sc_array* xs, const int* idx, int count,
+                             int slot0, std::vector<sc_handle_s*>* arenas, hipStream_t s) {
+  std::vector<sc_array> as(count);
+  std::vector<double*> dsts(count);
+  std::vector<sc_handle> hs(count);
+  std::vector<int> flags(count, 0);
+  for (int z = 0; z < count; ++z) {
+    SC_TRY(group_slot(lead, slot0 + z, &hs[z], arenas));
+    sc_handle h = hs[z];
+    h->err.clear();
+    as[z] = xs[idx[z]];
+    const int n = (int)as[z].rows;
+    int rc = ensure_matrices(h, n, 0);
+    if (rc == SC_OK) rc = ensure_tilemap(h, n);
+    if (rc == SC_OK) rc = grow(h, h->symflag, 16);
+    if (rc != SC_OK) return fail(lead, rc, h->err);
+    dsts[z] = ptr<double>(h->A0);
+  }
+  auto align256 = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t table_at = align256(count * sizeof(int));
+  const size_t stage_at = table_at + align256(count * affinity_group_table_bytes());
+  sc_handle h0 = hs[0];
+  if (grow(h0, h0->Xstage, stage_at + affinity_group_stage_bytes(as.data(), count)) != SC_OK)
+    return fail(lead, SC_ERR_OOM, h0->err);
+  unsigned char* base = static_cast<unsigned char*>(h0->Xstage.p);
+  SC_TRY(ingest_affinity_group(lead, as.data(), count, dsts.data(), reinterpret_cast<int*>(base),
+                               base + stage_at, base + table_at, s, flags.data()));
+  for (int z = 0; z < count; ++z) {
+    sc_handle h = hs[z];
+    h->n = (int)as[z].rows;
+    h->d = 0;
+    h->ldn = matrix_ld(h->n);
+    h->ldx = 0;
+    h->n_vec = 0;
+    h->have_x = h->have_cropval = false;
+    h->have_affinity = true;
+    h->affinity_symmetric = flags[z] != 0;
+    h->affinity_from_embeddings = false;
+    h->constraint_applied = false;
+  }
+  return SC_OK;
+}
+
 // Stages before the eigensolver of one group, member after member, each on its member's
 // stream: no synchronisation.  `slot0`: first member arena of the bank the group uses.
 // `arenas`: the member arenas to use (default: the lead's gslots).
@@ -128,6 +176,9 @@ int enqueue_front(sc_handle lead, const sc_array* xs, const int* ns, int d,
     return SC_OK;
   };
   std::vector<int> chained;  // members whose affinity the grouped chain adjusts
+  const bool affinities = bands && bands->affinities;
+  if (affinities)
+    SC_TRY(ingest_member_affinities(lead, xs, idx, count, slot0, arenas, chain_stream));
   for (int z = 0; z < count; ++z) {
     Member& m = mb[z];
     m = Member();
@@ -136,10 +187,10 @@ int enqueue_front(sc_handle lead, const sc_array* xs, const int* ns, int d,
     sc_handle h = m.h;
     h->err.clear();
     // (no wait: the caller's arrays stay valid for the whole batch call)
-    int rc = ingest_embeddings(h, xs[m.index], false);
+    int rc = affinities ? SC_OK : ingest_embeddings(h, xs[m.index], false);
     h->nev = 0;
     if (diags) memset(diags + m.index, 0, sizeof(sc_diag));
-    if (rc == SC_OK) rc = sc_compute_affinity(h);
+    if (rc == SC_OK && !affinities) rc = sc_compute_affinity(h);
     // the arena's resident constraint is this member's band or entry list, or none
     h->have_constraint = h->constraint_banded = h->constraint_pairs = false;
     h->qn = 0;
@@ -160,7 +211,10 @@ int enqueue_front(sc_handle lead, const sc_array* xs, const int* ns, int d,
       h->pairs_count = k;
       h->qn = h->n;
     }
-    if (rc == SC_OK && pairs && bands->chain) {
+    // (the grouped chain works on symmetric affinities: a caller's matrix that is not symmetric
+    //  takes the member's own operator below)
+    const bool chain = bands && bands->chain && h->affinity_symmetric;
+    if (rc == SC_OK && pairs && chain) {
       chained.push_back(z);
       SC_HIP(lead, hipEventRecord(h->sync_ev, h->stream));  // "affinity and entries are there"
       continue;
@@ -174,7 +228,7 @@ int enqueue_front(sc_handle lead, const sc_array* xs, const int* ns, int d,
       h->have_constraint = h->constraint_banded = h->constraint_symmetric = true;
       h->qn = h->n;
     }
-    if (rc == SC_OK && band && bands->chain) {
+    if (rc == SC_OK && band && chain) {
       chained.push_back(z);
       SC_HIP(lead, hipEventRecord(h->sync_ev, h->stream));  // "affinity and band are there"
       continue;
@@ -421,9 +475,10 @@ int run_short_route(sc_handle h, const sc_array* xs, const int* ns, int d,
       hz->have_constraint = false;
     }
   ShortWaveOps wave_ops;
-  const bool wave = !sw::short_front_memberwise() && !(bands && bands->cons) &&
+  const bool wave = !sw::short_front_memberwise() && !bands &&
                     d <= kShortWaveMaxD && short_wave_covers(cfg, &wave_ops);
-  if (wave || (bands && bands->chain))  // (the grouped chain of a wave: a stream of the wave's bank)
+  // (the grouped chain of a wave, the grouped ingest of callers' affinities: a stream of the wave's bank)
+  if (wave || (bands && (bands->chain || bands->affinities)))
     for (int b = 0; b < banks; ++b) SC_TRY(ensure_bank_stream(h, b));
   if (wave && wave_ops.blur_radius > 0) SC_TRY(upload_group_blur_weights(h, cfg));
   std::vector<Member> mbs[kGroupBanks];
@@ -610,6 +665,11 @@ int predict_single_banded(sc_handle h, const std::vector<int>& list, const sc_ar
     else if (bands.band(i)) SC_TRY(sc_set_constraint_band(h, bands.band(i), n));
     else SC_TRY(sc_clear_constraint(h));
     h->sweep_slot.clear();
+    if (bands.affinities) {  // (sc_predict_affinity_array behind the constraint)
+      SC_TRY(sc_set_affinity_array(h, xs + i));
+      SC_TRY(run_resident(h, cfg, labels[i], diags ? diags + i : nullptr, false));
+      continue;
+    }
     SC_TRY(ingest_embeddings(h, xs[i], xs[i].location == SC_MEM_HOST));
     SC_TRY(sc_run_resident(h, cfg, labels[i], diags ? diags + i : nullptr));
   }
@@ -673,7 +733,7 @@ bool constraint_workspace_fits(sc_handle h, const Bands& bands, int largest, boo
 int predict_batch_core(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
                        const sc_config* cfg, int64_t* const* labels, sc_diag* diags, int group,
                        const Bands& band_set, const SingleCheck* sc = nullptr) {
-  const Bands* bands = band_set.cons ? &band_set : nullptr;
+  const Bands* bands = band_set.cons || band_set.affinities ? &band_set : nullptr;
   if (sc && sc->single) std::fill(sc->single, sc->single + count, 0);
   SC_TRY(validate_config(h, cfg));
   SC_HIP(h, hipSetDevice(h->device));
@@ -1509,7 +1569,8 @@ extern "C" int sc_predict_batch_constrained(sc_handle h, const sc_array* xs,
 
 int predict_batch_constrained_impl(sc_handle h, const sc_array* xs, const sc_constraint_desc* cons,
                                    const int* ns, int d, int count, const sc_config* cfg,
-                                   int64_t* const* labels, sc_diag* diags, int group) {
+                                   int64_t* const* labels, sc_diag* diags, int group,
+                                   bool affinities) {
   // every entry list is checked, and packed for its upload, before anything is launched
   std::vector<std::vector<double>> packed((size_t)count);
   std::vector<char> pairs_symmetric((size_t)count, 1);
@@ -1547,10 +1608,40 @@ int predict_batch_constrained_impl(sc_handle h, const sc_array* xs, const sc_con
       (void)sc_clear_constraint(h);
     }
   } cleanup{h};
-  cleanup.rc = predict_batch_core(h, xs, ns, d, count, cfg, labels, diags, group,
-                                  make_bands(cons, packed.data(), pairs_symmetric.data(), kmax,
-                                             cfg));
+  Bands bands = make_bands(cons, packed.data(), pairs_symmetric.data(), kmax, cfg);
+  bands.affinities = affinities;
+  cleanup.rc = predict_batch_core(h, xs, ns, d, count, cfg, labels, diags, group, bands);
   return cleanup.rc;
+}
+
+extern "C" int sc_predict_batch_affinities(sc_handle h, const sc_array* as,
+                                           const sc_constraint_desc* cons, int count,
+                                           const sc_config* cfg, int64_t* const* labels,
+                                           sc_diag* diags, int group) {
+  if (!h) return SC_ERR_INVALID;
+  if (!as || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  if (group < 2)
+    return fail(h, SC_ERR_INVALID, "sc_predict_batch_affinities is the grouped form: group >= 2");
+  SC_TRY(validate_config(h, cfg));
+  SC_HIP(h, hipSetDevice(h->device));
+  bool device_source = false;
+  std::vector<int> ns(count, 0);
+  for (int i = 0; i < count; ++i) {  // every descriptor before the first launch
+    SC_TRY(validate_affinity_array(h, as + i));
+    if (!labels[i]) return fail(h, SC_ERR_INVALID, "NULL labels");
+    ns[i] = (int)as[i].rows;
+    device_source |= as[i].location == SC_MEM_DEVICE;
+  }
+  if (count == 0) {
+    h->last_routes.clear();
+    return SC_OK;
+  }
+  // (as sc_predict_batch_arrays: what the producers ordered before this stream is done before
+  //  the streams of the batch read a device source)
+  if (device_source) SC_HIP(h, hipStreamSynchronize(h->stream));
+  SC_TRY(sc_clear_constraint(h));  // the handle's own resident constraint takes no part
+  return predict_batch_constrained_impl(h, as, cons, ns.data(), 0, count, cfg, labels, diags, group,
+                                        true);
 }
 
 extern "C" int sc_predict_batch_single(sc_handle h, const sc_array* xs, int count,

@@ -27,6 +27,9 @@ struct Bands {
   int kmax = 0;        // the largest entry list: what a member arena reserves
   bool chain = false;  // ConstraintPropagation before refinement: the grouped Neumann chain
   int ncp = 0;         // cp[] work matrices a member arena holds for the configured operator
+  // sc_predict_batch_affinities: the batch's arrays are (n, n) affinities the callers hold, not
+  // embeddings -- the grouped ingest of a front replaces the rows' upload and the affinity GEMM
+  bool affinities = false;
   bool has(int i) const { return cons && cons[i].kind != 0; }
   const double* band(int i) const { return cons && cons[i].kind == 2 ? cons[i].band : nullptr; }
   bool pairs(int i) const { return cons && cons[i].kind == 3; }

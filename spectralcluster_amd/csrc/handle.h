@@ -293,6 +293,25 @@ int ingest_embeddings(sc_handle h, const sc_array& a, bool sync, hipStream_t str
 // staging rows): *sync is set when the caller must wait for s before the source may go
 int ingest_rows_into(sc_handle h, const sc_array& a, double* X, int ldx, hipStream_t s,
                      bool* sync);
+// ---- a caller's affinity as a described source (ingest.hip, affinity_api.hip) -------------
+// validate_array and rows == cols
+int validate_affinity_array(sc_handle h, const sc_array* a);
+// the (n, n) values, widened, into dst (row pitch ld, padding columns zeroed) on stream s, and the
+// exact-symmetry flag into *flag (device memory); *sync as in ingest_rows_into
+int ingest_affinity_into(sc_handle h, const sc_array& a, double* dst, int ld, int* flag,
+                         hipStream_t s, bool* sync);
+// up to 64 sources by one launch (member z: dsts[z] of pitch matrix_ld(n_z), flags[z]); `stage`
+// (affinity_group_stage_bytes) takes the host members at their own width, `table`
+// (count * affinity_group_table_bytes()) the descriptors; `host_flags` (may be null) receives the
+// flags in the same wait; returns with s synchronised
+size_t affinity_group_table_bytes();
+size_t affinity_group_stage_bytes(const sc_array* as, int count);
+int ingest_affinity_group(sc_handle h, const sc_array* as, int count, double* const* dsts,
+                          int* flags, void* stage, void* table, hipStream_t s,
+                          int* host_flags = nullptr);
+// sc_run_resident; `from_embeddings` false: the resident affinity is the caller's (no GEMM)
+int run_resident(sc_handle h, const sc_config* cfg, int64_t* labels, sc_diag* diag,
+                 bool from_embeddings);
 // the bodies of sc_predict_batch_streams / sc_predict_batch_grouped on described sources
 int predict_batch_streams_impl(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
                                const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
@@ -529,7 +548,8 @@ std::vector<double> pack_constraint_pairs(const int32_t* rows, const int32_t* co
 // the body of sc_predict_batch_constraints (batch_group.hip); cons == nullptr: no constraints
 int predict_batch_constrained_impl(sc_handle h, const sc_array* xs, const sc_constraint_desc* cons,
                                    const int* ns, int d, int count, const sc_config* cfg,
-                                   int64_t* const* labels, sc_diag* diags, int group);
+                                   int64_t* const* labels, sc_diag* diags, int group,
+                                   bool affinities = false);  // (xs are the callers' affinities)
 
 // ---- the single-cluster test (callers_api.hip: the single call's; single_check.hip: a batch's)
 // the bodies of sc_affinity_stats / sc_affinity_gmm_bic on the affinity resident in h

@@ -112,6 +112,189 @@ size_t dtype_bytes(int dtype) {
   return dtype == SC_DTYPE_F64 ? 8 : dtype == SC_DTYPE_F32 ? 4 : 2;
 }
 
+// ---- an (n, n) affinity where it is -> fp64 rows of pitch ld, and its symmetry flag ----------
+// A workgroup takes the 64 x 64 tile (I, J), I <= J, together with its mirror (J, I): both are
+// widened into LDS, stored from there in rows (16-byte stores), and compared element against
+// transposed element -- every source byte is read once, the flag costs no second pass.
+//   kAffVec   col_stride 1, base and row pitch multiples of 16 bytes: 16-byte loads (the item that
+//             straddles column n reads its elements one by one, never past the row)
+//   kAffRows  scalar loads, adjacent lanes on adjacent columns (col_stride <= row_stride)
+//   kAffCols  scalar loads, adjacent lanes on adjacent ROWS: a transposed view is walked along
+//             its memory, LDS does the transposition
+//   kAffVecCols  kAffVec for a transposed view: row_stride 1, base and column pitch multiples of
+//             16 bytes -- 16-byte loads down the columns
+// LDS rows are not padded (two fp64 tiles are the whole 64 KB): the pair index of a row is
+// XOR-ed with the row number instead, which keeps 16-byte pairs together and spreads a column
+// over all banks.
+constexpr int kAffTile = 64;
+enum { kAffVec = 0, kAffRows = 1, kAffCols = 2, kAffVecCols = 3 };
+
+__device__ __forceinline__ int aff_at(int r, int c) {
+  return r * kAffTile + (c ^ ((r & 31) << 1));
+}
+
+template <typename T, int E, bool COLWALK>
+__device__ __forceinline__ void aff_load_tile(const T* __restrict__ src, long long rs,
+                                              long long cs, int n, int r0, int c0,
+                                              double* __restrict__ lds) {
+  // an item is E elements along the walked direction: of a row, or (COLWALK) of a column
+  constexpr int kPerLine = kAffTile / E;
+#pragma unroll
+  for (int it = 0; it < kAffTile * kAffTile / E / 256; ++it) {
+    const int item = it * 256 + (int)threadIdx.x;
+    const int line = item / kPerLine, at = (item % kPerLine) * E;
+    const int r = COLWALK ? at : line, c = COLWALK ? line : at;
+    const int gr = r0 + r, gc = c0 + c;
+    if constexpr (E > 1) {
+      // (the walked stride is 1: kAffVec walks rows, kAffVecCols columns)
+      const long long base = COLWALK ? (long long)gc * cs + gr : (long long)gr * rs + gc;
+      const int gline = COLWALK ? gc : gr, gat = COLWALK ? gr : gc;
+      double w[E];
+      if (gline < n && gat + E <= n) {
+        const Chunk<T> ch = *reinterpret_cast<const Chunk<T>*>(src + base);
+#pragma unroll
+        for (int e = 0; e < E; ++e) w[e] = widen(ch.v[e]);
+      } else {
+#pragma unroll
+        for (int e = 0; e < E; ++e) w[e] = gline < n && gat + e < n ? widen(src[base + e]) : 0.0;
+      }
+      if constexpr (COLWALK) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) lds[aff_at(r + e, c)] = w[e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < E; e += 2)
+          *reinterpret_cast<double2*>(lds + aff_at(r, c + e)) = make_double2(w[e], w[e + 1]);
+      }
+    } else {
+      lds[aff_at(r, c)] =
+          gr < n && gc < n ? widen(src[(long long)gr * rs + (long long)gc * cs]) : 0.0;
+    }
+  }
+}
+
+// rows of one tile from LDS to dst (only elements inside the matrix)
+__device__ __forceinline__ void aff_store_pair(double* __restrict__ dst, int ld, int n, int gr,
+                                               int gc, double2 v) {
+  if (gr >= n || gc >= n) return;
+  double* out = dst + (size_t)gr * ld + gc;
+  if (gc + 1 < n) *reinterpret_cast<double2*>(out) = v;
+  else *out = v.x;
+}
+
+struct AffIngestItem {
+  const void* src;
+  long long row_stride, col_stride;  // elements
+  double* dst;
+  int* flag;  // set to 1 before the launch; cleared when an (i, j) differs from (j, i)
+  int n, ld, dtype, mode;
+};
+
+template <typename T, int E, bool COLWALK>
+__device__ __forceinline__ void aff_ingest_tiles(const AffIngestItem& m, int ti, int tj,
+                                                 double* __restrict__ sp,
+                                                 double* __restrict__ sq) {
+  const T* src = static_cast<const T*>(m.src);
+  const int n = m.n, ld = m.ld, r0 = ti * kAffTile, c0 = tj * kAffTile;
+  const bool diag = ti == tj;
+  aff_load_tile<T, E, COLWALK>(src, m.row_stride, m.col_stride, n, r0, c0, sp);
+  if (!diag) aff_load_tile<T, E, COLWALK>(src, m.row_stride, m.col_stride, n, c0, r0, sq);
+  __syncthreads();
+  const double* mir = diag ? sp : sq;
+  bool differs = false;
+#pragma unroll
+  for (int it = 0; it < kAffTile * kAffTile / 2 / 256; ++it) {
+    const int item = it * 256 + (int)threadIdx.x;
+    const int r = item / (kAffTile / 2), c = (item % (kAffTile / 2)) * 2;
+    const double2 p = *reinterpret_cast<const double2*>(sp + aff_at(r, c));
+    // k_symmetry_flag's test, on the pairs above the diagonal (elements outside the matrix are
+    // zeros on both sides)
+    if (!diag || c > r) differs |= !(p.x == mir[aff_at(c, r)]);
+    if (!diag || c + 1 > r) differs |= !(p.y == mir[aff_at(c + 1, r)]);
+    aff_store_pair(m.dst, ld, n, r0 + r, c0 + c, p);
+    if (!diag)
+      aff_store_pair(m.dst, ld, n, c0 + r, r0 + c,
+                     *reinterpret_cast<const double2*>(sq + aff_at(r, c)));
+  }
+  if (differs) *m.flag = 0;
+  if (diag) {  // the padding columns of these 64 rows
+    const int gr = r0 + ((int)threadIdx.x >> 2);
+    if (gr < n)
+      for (int c = n + ((int)threadIdx.x & 3); c < ld; c += 4) m.dst[(size_t)gr * ld + c] = 0.0;
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ void aff_ingest_modes(const AffIngestItem& m, int ti, int tj,
+                                                 double* sp, double* sq) {
+  if (m.mode == kAffVec) aff_ingest_tiles<T, 16 / (int)sizeof(T), false>(m, ti, tj, sp, sq);
+  else if (m.mode == kAffRows) aff_ingest_tiles<T, 1, false>(m, ti, tj, sp, sq);
+  else if (m.mode == kAffCols) aff_ingest_tiles<T, 1, true>(m, ti, tj, sp, sq);
+  else aff_ingest_tiles<T, 16 / (int)sizeof(T), true>(m, ti, tj, sp, sq);
+}
+
+// block p of a member: the p-th tile pair of the upper triangle, row by row
+__device__ __forceinline__ void aff_ingest_block(const AffIngestItem& m, int p, double* sp,
+                                                 double* sq) {
+  const int nt = (m.n + kAffTile - 1) / kAffTile;
+  if (p >= nt * (nt + 1) / 2) return;  // (a smaller member of a group)
+  int ti = 0;
+  while (p >= nt - ti) {
+    p -= nt - ti;
+    ++ti;
+  }
+  const int tj = ti + p;
+  switch (m.dtype) {
+    case SC_DTYPE_F64: aff_ingest_modes<double>(m, ti, tj, sp, sq); break;
+    case SC_DTYPE_F32: aff_ingest_modes<float>(m, ti, tj, sp, sq); break;
+    case SC_DTYPE_F16: aff_ingest_modes<F16Bits>(m, ti, tj, sp, sq); break;
+    default: aff_ingest_modes<BF16Bits>(m, ti, tj, sp, sq); break;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_ingest_affinity(AffIngestItem m) {
+  __shared__ alignas(16) double sp[kAffTile * kAffTile];
+  __shared__ alignas(16) double sq[kAffTile * kAffTile];
+  aff_ingest_block(m, (int)blockIdx.x, sp, sq);
+}
+
+// blockIdx.y: the member; its descriptor comes from a table in device memory
+__global__ __launch_bounds__(256) void k_ingest_affinity_group(
+    const AffIngestItem* __restrict__ members) {
+  __shared__ alignas(16) double sp[kAffTile * kAffTile];
+  __shared__ alignas(16) double sq[kAffTile * kAffTile];
+  const AffIngestItem m = members[blockIdx.y];
+  aff_ingest_block(m, (int)blockIdx.x, sp, sq);
+}
+
+unsigned aff_blocks(int n) {
+  const unsigned nt = (unsigned)((n + kAffTile - 1) / kAffTile);
+  return nt * (nt + 1) / 2;
+}
+
+AffIngestItem aff_item(int dtype, const void* src, long long row_stride, long long col_stride,
+                       int n, double* dst, int ld, int* flag) {
+  const long long eb = (long long)dtype_bytes(dtype);
+  AffIngestItem m;
+  m.src = src;
+  m.row_stride = row_stride;
+  m.col_stride = col_stride;
+  m.dst = dst;
+  m.flag = flag;
+  m.n = n;
+  m.ld = ld;
+  m.dtype = dtype;
+  if (col_stride == 1 && (reinterpret_cast<uintptr_t>(src) & 15u) == 0 &&
+      (n == 1 || (row_stride * eb) % 16 == 0))
+    m.mode = kAffVec;
+  else if (row_stride == 1 && col_stride != 1 && (reinterpret_cast<uintptr_t>(src) & 15u) == 0 &&
+           (col_stride * eb) % 16 == 0)
+    m.mode = kAffVecCols;
+  else
+    m.mode = col_stride > row_stride ? kAffCols : kAffRows;
+  return m;
+}
+
 // Host rows that hipMemcpy2D cannot describe (a column stride, rows that overlap): gathered
 // into `tmp` at the source's width.
 void pack_host_rows(const sc_array& a, std::vector<unsigned char>* tmp) {
@@ -122,6 +305,27 @@ void pack_host_rows(const sc_array& a, std::vector<unsigned char>* tmp) {
   for (int64_t r = 0; r < a.rows; ++r)
     for (int64_t c = 0; c < a.cols; ++c, out += eb)
       memcpy(out, base + (size_t)(r * a.row_stride + c * a.col_stride) * eb, eb);
+}
+
+
+// Host rows at their own width into staging memory of a 16-byte pitch (device pointer `stage`),
+// gathered first where hipMemcpy2D cannot describe them.  *sync: `packed` is a local.
+int stage_host_affinity(sc_handle h, const sc_array& a, void* stage, size_t pitch, hipStream_t s,
+                        std::vector<unsigned char>* packed, bool* sync) {
+  const int n = (int)a.rows;
+  const size_t eb = dtype_bytes(a.dtype);
+  const void* src = a.data;
+  size_t spitch = (size_t)a.row_stride * eb;
+  if (a.col_stride != 1 || (a.row_stride < a.cols && n > 1)) {
+    pack_host_rows(a, packed);
+    src = packed->data();
+    spitch = (size_t)n * eb;
+    *sync = true;
+  }
+  if (n == 1) spitch = eb;
+  SC_HIP(h, hipMemcpy2DAsync(stage, pitch, src, spitch, (size_t)n * eb, n, hipMemcpyHostToDevice,
+                             s));
+  return SC_OK;
 }
 
 }  // namespace
@@ -253,6 +457,106 @@ int ingest_rows_into(sc_handle h, const sc_array& a, double* X, int ldx, hipStre
     }
   }
   if (sync) *sync_out = true;
+  return SC_OK;
+}
+
+// ------------------------------------------------------------------------------
+// the one place a caller's affinity enters
+// ------------------------------------------------------------------------------
+int validate_affinity_array(sc_handle h, const sc_array* a) {
+  SC_TRY(validate_array(h, a));
+  if (a->rows != a->cols) return fail(h, SC_ERR_INVALID, "affinity must be (n, n)");
+  return SC_OK;
+}
+
+// The (n, n) values of a validated source, widened, into dst (row pitch ld doubles, padding
+// columns zeroed) on stream s, and *flag (device memory) = is it exactly symmetric.  *sync as in
+// ingest_rows_into.  A host fp64 source takes sc_set_affinity's copy and the separate symmetry
+// pass (staging it would cost a second n x n fp64 buffer); everything else is one kernel.
+int ingest_affinity_into(sc_handle h, const sc_array& a, double* dst, int ld, int* flag,
+                         hipStream_t s, bool* sync_out) {
+  static const int kOne = 1;
+  const int n = (int)a.rows;
+  const size_t eb = dtype_bytes(a.dtype);
+  bool sync = false;
+  SC_HIP(h, hipMemcpyAsync(flag, &kOne, sizeof(int), hipMemcpyHostToDevice, s));
+  if (a.location == SC_MEM_DEVICE) {
+    hipLaunchKernelGGL(k_ingest_affinity, dim3(aff_blocks(n)), dim3(256), 0, s,
+                       aff_item(a.dtype, a.data, a.row_stride, a.col_stride, n, dst, ld, flag));
+    SC_TRY(check_last(h, "affinity ingest launch"));
+  } else if (a.dtype == SC_DTYPE_F64) {
+    std::vector<unsigned char> packed;
+    SC_TRY(stage_host_affinity(h, a, dst, (size_t)ld * sizeof(double), s, &packed, &sync));
+    if (ld > n)
+      SC_HIP(h, hipMemset2DAsync(dst + n, (size_t)ld * sizeof(double), 0,
+                                 (size_t)(ld - n) * sizeof(double), n, s));
+    launch_symmetry_flag(s, dst, n, ld, flag);
+    SC_TRY(check_last(h, "symmetry flag launch"));
+    if (sync) SC_HIP(h, hipStreamSynchronize(s));  // (`packed` is a local)
+  } else {
+    const size_t pitch = ((size_t)n * eb + 15) / 16 * 16;
+    if (h->Xstage.bytes < (size_t)n * pitch) {
+      if (h->Xstage.p && s != h->stream) SC_HIP(h, hipStreamSynchronize(s));
+      SC_TRY(grow(h, h->Xstage, (size_t)n * pitch));
+    }
+    std::vector<unsigned char> packed;
+    SC_TRY(stage_host_affinity(h, a, h->Xstage.p, pitch, s, &packed, &sync));
+    hipLaunchKernelGGL(k_ingest_affinity, dim3(aff_blocks(n)), dim3(256), 0, s,
+                       aff_item(a.dtype, h->Xstage.p, (long long)(pitch / eb), 1, n, dst, ld, flag));
+    SC_TRY(check_last(h, "affinity ingest launch"));
+    if (sync) SC_HIP(h, hipStreamSynchronize(s));  // (`packed` is a local)
+  }
+  if (sync) *sync_out = true;
+  return SC_OK;
+}
+
+// `count` (<= 64) sources by ONE launch: member z into dsts[z] (pitch matrix_ld(n_z)), its flag
+// into flags[z] (device memory).  Host members are copied at their own width into `stage` (device
+// memory of affinity_group_stage_bytes bytes) first; `table` holds the descriptors (device memory,
+// count * affinity_group_table_bytes()).  The host side of the copies is waited for before return.
+size_t affinity_group_table_bytes() { return sizeof(AffIngestItem); }
+size_t affinity_group_stage_bytes(const sc_array* as, int count) {
+  size_t total = 0;
+  for (int z = 0; z < count; ++z)
+    if (as[z].location == SC_MEM_HOST)
+      total += (size_t)as[z].rows * (((size_t)as[z].rows * dtype_bytes(as[z].dtype) + 15) / 16 * 16);
+  return total;
+}
+int ingest_affinity_group(sc_handle h, const sc_array* as, int count, double* const* dsts,
+                          int* flags, void* stage, void* table, hipStream_t s, int* host_flags) {
+  if (count <= 0) return SC_OK;
+  if (count > 64) return fail(h, SC_ERR_INVALID, "at most 64 affinities per grouped ingest");
+  std::vector<AffIngestItem> items(count);
+  std::vector<int> ones(count, 1);
+  std::vector<std::vector<unsigned char>> packed(count);
+  unsigned char* at = static_cast<unsigned char*>(stage);
+  unsigned blocks = 0;
+  bool sync = false;
+  for (int z = 0; z < count; ++z) {
+    const sc_array& a = as[z];
+    const int n = (int)a.rows;
+    const size_t eb = dtype_bytes(a.dtype);
+    if (a.location == SC_MEM_HOST) {
+      const size_t pitch = ((size_t)n * eb + 15) / 16 * 16;
+      SC_TRY(stage_host_affinity(h, a, at, pitch, s, &packed[z], &sync));
+      items[z] = aff_item(a.dtype, at, (long long)(pitch / eb), 1, n, dsts[z], matrix_ld(n),
+                          flags + z);
+      at += (size_t)n * pitch;
+    } else {
+      items[z] = aff_item(a.dtype, a.data, a.row_stride, a.col_stride, n, dsts[z], matrix_ld(n),
+                          flags + z);
+    }
+    blocks = std::max(blocks, aff_blocks(n));
+  }
+  SC_HIP(h, hipMemcpyAsync(flags, ones.data(), count * sizeof(int), hipMemcpyHostToDevice, s));
+  SC_HIP(h, hipMemcpyAsync(table, items.data(), count * sizeof(AffIngestItem),
+                           hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_ingest_affinity_group, dim3(blocks, count), dim3(256), 0, s,
+                     static_cast<const AffIngestItem*>(table));
+  SC_TRY(check_last(h, "grouped affinity ingest launch"));
+  if (host_flags)
+    SC_HIP(h, hipMemcpyAsync(host_flags, flags, count * sizeof(int), hipMemcpyDeviceToHost, s));
+  SC_HIP(h, hipStreamSynchronize(s));  // (`items`, `ones`, `packed` are locals)
   return SC_OK;
 }
 

@@ -186,10 +186,16 @@ class SpectralClusterer:
       handle.check(handle.lib.sc_set_embeddings_array(handle.raw, ctypes.byref(source.array)))
       handle.check(handle.lib.sc_compute_affinity(handle.raw))
     else:
-      a = np.ascontiguousarray(self.affinity_function(source.host_f64(handle)),
-                               dtype=np.float64)
-      handle.check(handle.lib.sc_set_affinity(handle.raw, _lib.as_double_p(a),
-                                              a.shape[0]))
+      # what the user's function returns is read where it is (sc_set_affinity_array): a float64
+      # host array as before, but also float32 / float16 / bfloat16 or a tensor on the GPU
+      a = self.affinity_function(source.host_f64(handle))
+      if not isinstance(a, np.ndarray) and not hasattr(a, "__dlpack__"):
+        a = np.asarray(a, dtype=np.float64)
+      affinity = _dlpack.describe(a, lambda: handle, strided=True)
+      try:
+        handle.check(handle.lib.sc_set_affinity_array(handle.raw, ctypes.byref(affinity.array)))
+      finally:
+        affinity.release()
 
   def _eig_resident(self, handle: _lib.Handle, p_percentile=None) -> _lib.ScDiag:
     diag = _lib.ScDiag()
@@ -339,7 +345,14 @@ class SpectralClusterer:
       return labels
 
     self._upload(handle, source)
-    if single_check and not by_fallback:
+    return self._predict_resident(handle, n, constrained, single_check and not by_fallback,
+                                  default_tail)
+
+  def _predict_resident(self, handle: _lib.Handle, n: int, constrained: bool,
+                        affinity_single_check: bool, default_tail: bool) -> np.ndarray:
+    """predict() from the resident affinity on (the embeddings' GEMM or a caller's matrix put it
+    there): single-cluster test, constraint, AutoTune or one evaluation, the clustering tail."""
+    if affinity_single_check:
       # single-vs-multi cluster(s) decision on the resident affinity (reference :253-256; the
       # affinity conditions do not read the embeddings)
       if fallback_clusterer.check_single_cluster(self.fallback_options, None, None,
@@ -389,6 +402,180 @@ class SpectralClusterer:
     return self.post_eigen_cluster_function(
         spectral_embeddings=spectral, n_clusters=n_clusters,
         custom_dist=self.custom_dist, max_iter=self.max_iter)
+
+  # ------------------------------------------------- an affinity the caller holds
+  def _check_affinity_input(self, affinity, what: str = "affinity") -> int:
+    """The ValueErrors of predict_affinity that need no device: a matrix that is not 2-D or not
+    square, and the options that read embeddings.  Returns n."""
+    shape = np.shape(affinity) if isinstance(affinity, np.ndarray) else getattr(
+        affinity, "shape", None)
+    if shape is None:
+      raise TypeError("%s must be a numpy array or support __dlpack__" % what)
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 2:
+      raise ValueError("%s must be 2-dimensional, got shape %s" % (what, shape))
+    if shape[0] != shape[1]:
+      raise ValueError("%s must be a square matrix, got shape %s" % (what, shape))
+    n = shape[0]
+    if n < self.fallback_options.spectral_min_embeddings:
+      raise ValueError(
+          "fallback_options.spectral_min_embeddings = %d is above n = %d: the fallback clusterer "
+          "reads embeddings, which predict_affinity does not have"
+          % (self.fallback_options.spectral_min_embeddings, n))
+    if self.max_spectral_size is not None and n > self.max_spectral_size:
+      raise ValueError(
+          "max_spectral_size = %d is below n = %d: the size reduction clusters embeddings, which "
+          "predict_affinity does not have" % (self.max_spectral_size, n))
+    if (self.min_clusters == 1 and self.fallback_options.single_cluster_condition ==
+        fallback_clusterer.SingleClusterCondition.FallbackClusterer):
+      raise ValueError(
+          "single_cluster_condition = FallbackClusterer with min_clusters = 1 clusters the "
+          "embeddings, which predict_affinity does not have: use one of the conditions that "
+          "read the affinity")
+    return n
+
+  def predict_affinity(self, affinity, constraint_matrix=None) -> np.ndarray:
+    """Cluster from an (n, n) affinity the caller already holds -- PLDA or other learned scores,
+    raw cosine in [-1, 1], a Gaussian kernel, what a model has just written on the GPU.
+
+    The result is that of `predict(x, constraint_matrix)` on a copy of this clusterer whose
+    `affinity_function` is `lambda _: A64`, A64 being `affinity` widened to float64, for any `x`
+    of n rows.  `affinity` is whatever predict() takes, but square: a NumPy array or an object
+    with `__dlpack__`, in host memory or on the clusterer's GPU, float64 / float32 / float16 /
+    bfloat16, contiguous or a strided view (a `.T`, a `[::2, ::2]` slice).  It is read where it
+    is and widened exactly on the device; the same kernel pass decides whether it is symmetric.
+    A device tensor needs no synchronisation by the caller and may be overwritten or freed when
+    the call has returned.  Every Laplacian and eigengap rule, AutoTune, the three constraint
+    forms, `min_clusters=1` under the four conditions that read the affinity and a user
+    `post_eigen_cluster_function` work as in predict(); without AutoTune, a single-cluster test
+    or a user tail it is ONE `sc_predict_affinity_array` call.
+
+    ValueError, before any device is touched: a matrix that is not 2-D or not square, and the
+    options that read embeddings -- n below `fallback_options.spectral_min_embeddings`,
+    `max_spectral_size` below n, `min_clusters == 1` under the `FallbackClusterer` condition."""
+    n = self._check_affinity_input(affinity)
+    with _lib.use_device(self.device):
+      source = _dlpack.describe(affinity, self._handle, strided=True)
+      try:
+        handle = self._handle()
+        default_tail = (self.post_eigen_cluster_function is custom_distance_kmeans.run_kmeans)
+        if default_tail:
+          _lib.kmeans_metric_code(self.custom_dist)  # raises for metrics not on the device
+        constrained = self._set_constraint(handle, n, constraint_matrix)
+        single_check = self.min_clusters == 1
+        if self.autotune is None and default_tail and not single_check:
+          labels = np.empty(n, dtype=np.int64)
+          diag = _lib.ScDiag()
+          handle.check(handle.lib.sc_predict_affinity_array(
+              handle.raw, ctypes.byref(source.array), self.build_config(),
+              _lib.as_int64_p(labels), diag), TypeError)
+          self.last_diag = diag
+          return labels
+        handle.check(handle.lib.sc_set_affinity_array(handle.raw, ctypes.byref(source.array)))
+        return self._predict_resident(handle, n, constrained, single_check, default_tail)
+      finally:
+        source.release()
+
+  def predict_affinity_batch(self, affinities: typing.Sequence,
+                             constraint_matrices: typing.Optional[typing.Sequence] = None,
+                             group: typing.Optional[int] = None) -> typing.List[np.ndarray]:
+    """`[predict_affinity(a, c) for a, c in zip(affinities, constraint_matrices)]`; host and
+    device matrices of any of the four dtypes may be mixed.
+
+    Every check of predict_affinity, the length of `constraint_matrices` and the size of each
+    `ConstraintMatrix` / `PairwiseConstraints` are made for the whole list before anything is
+    launched.  The batch is ONE `sc_predict_batch_affinities` call when the clusterer is one
+    `_library_batch_covers()` accepts but for its `affinity_function` (no AutoTune, `min_clusters`
+    not 1, the default k-means function), the metric is on the device (cosine when constraints
+    travel), `group` is not 1 and every constraint is a `ConstraintMatrix`, a
+    `PairwiseConstraints` or None.  It takes `predict_batch`'s routes -- n <= 128 in Jacobi waves
+    (route 2), 128 < n < 4096 in lockstep groups of up to `group` (route 1), n >= 4096 and members
+    that leave their route as single calls inside the call (route 0) -- with one grouped ingest
+    launch per group or wave and the member-by-member refinement front; results agree with
+    predict_affinity as predict_batch's do with predict() (labels equal unless an eigengap
+    decision is a near tie, eigenvalues within 1e-10 relative on route 2 and 1e-6 on route 1),
+    and the same list gives the same results.  With a device tensor in the list the library
+    synchronises its stream once at entry; the tensors may be overwritten or freed when the call
+    has returned.  Otherwise -- AutoTune, `min_clusters=1`, a user k-means function, a dense
+    ndarray constraint, `group=1` -- the matrices run one after the other through
+    predict_affinity (routes all 0).  `last_batch_routes` / `last_batch_diags` are filled as in
+    predict_batch."""
+    count = len(affinities)
+    if constraint_matrices is None:
+      constraint_matrices = [None] * count
+    elif len(constraint_matrices) != count:
+      raise ValueError("constraint_matrices must be as long as the batch")
+    if group is not None and int(group) < 1:
+      raise ValueError("group must be at least 1")
+    for i, (a, cm) in enumerate(zip(affinities, constraint_matrices)):
+      n = self._check_affinity_input(a, "affinity %d" % i)
+      if self.constraint_options is not None and isinstance(
+          cm, (constraint_lib.ConstraintMatrix, constraint_lib.PairwiseConstraints)):
+        # (predict()'s check and message: _set_constraint)
+        self.constraint_options.constraint_operator.check_input(
+            np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)), cm)
+    self.last_batch_single = None
+    constrained = self.constraint_options is not None and any(
+        c is not None for c in constraint_matrices)
+    try:  # (a metric that is not on the device raises in predict_affinity, as in predict())
+      metric = _lib.kmeans_metric_code(self.custom_dist)
+      metric_ok = not constrained or metric == _lib.KMEANS_METRICS["cosine"]
+    except (ValueError, _lib.UnsupportedOnDeviceError):
+      metric_ok = False
+    if (count and metric_ok and self._library_batch_covers(affinity_input=True) and
+        (group is None or int(group) > 1) and
+        all(c is None or isinstance(c, (constraint_lib.ConstraintMatrix,
+                                        constraint_lib.PairwiseConstraints))
+            for c in constraint_matrices)):
+      return self._affinity_library_batch(affinities, constraint_matrices if constrained else None,
+                                          16 if group is None else int(group))
+    labels, diags = [], []
+    for a, cm in zip(affinities, constraint_matrices):
+      labels.append(self.predict_affinity(a, cm))
+      diags.append(self.last_diag)
+    self.last_batch_routes = [_lib.BATCH_ROUTE_SINGLE] * count
+    self.last_batch_diags = diags
+    return labels
+
+  def _affinity_library_batch(self, affinities: typing.Sequence,
+                              constraint_matrices: typing.Optional[typing.Sequence],
+                              group: int) -> typing.List[np.ndarray]:
+    """ONE `sc_predict_batch_affinities` call; the checks of predict_affinity_batch passed."""
+    count = len(affinities)
+    sources = []
+    try:
+      with _lib.use_device(self.device):
+        for a in affinities:
+          sources.append(_dlpack.describe(a, self._handle, strided=True))
+      handle = self._handle()
+      handle.check(handle.lib.sc_clear_constraint(handle.raw))
+      cons, keep = None, []
+      if constraint_matrices is not None:
+        cons = (_lib.ScConstraintDesc * count)()
+        for desc, src, cm in zip(cons, sources, constraint_matrices):
+          if isinstance(cm, constraint_lib.PairwiseConstraints):
+            rows, cols, vals = cm.entries()
+            keep.append((rows, cols, vals))
+            desc.kind, desc.count = 3, len(vals)
+            desc.rows, desc.cols = _lib.as_int32_p(rows), _lib.as_int32_p(cols)
+            desc.vals = _lib.as_double_p(vals)
+          elif cm is not None:
+            n = src.shape[0]
+            band = np.zeros(max(n - 1, 1), dtype=np.float64)  # (n = 1: a valid pointer)
+            band[:n - 1] = cm.band()
+            keep.append(band)
+            desc.kind, desc.band = 2, _lib.as_double_p(band)
+      labels = [np.empty(src.shape[0], dtype=np.int64) for src in sources]
+      lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
+      diags = (_lib.ScDiag * count)()
+      handle.check(handle.lib.sc_predict_batch_affinities(
+          handle.raw, (_lib.ScArray * count)(*[src.array for src in sources]), cons, count,
+          self.build_config(), lp, diags, int(group)), TypeError)
+    finally:
+      for src in sources:
+        src.release()
+    self._batch_report(handle, diags, count)
+    return labels
 
   # -------------------------------------------------------------- batch (new)
   def predict_batch(self, utterances: typing.Sequence,
@@ -829,20 +1016,25 @@ class SpectralClusterer:
             "affinity matrix dimension (utterance %d)" % i)
 
   def _library_batch_covers(self, min_embeddings_met: bool = False,
-                            single_check_covered: bool = False) -> bool:
+                            single_check_covered: bool = False,
+                            affinity_input: bool = False) -> bool:
     """Is this clusterer one whose predict() the library batch calls reproduce?  (What is not:
     AutoTune, size reduction, the fallback decisions, user-supplied functions -- those go
     through predict().)  `min_embeddings_met`: the caller knows every utterance to hold at
     least `fallback_options.spectral_min_embeddings` rows (the centroids of a stream pool).
     `single_check_covered`: the caller makes the `sc_predict_batch_single` call, which carries
     the single-cluster test of `min_clusters == 1` -- covered when the condition is one of the
-    four that read the affinity."""
+    four that read the affinity.  `affinity_input`: the caller makes the
+    `sc_predict_batch_affinities` call -- the `affinity_function` takes no part, and
+    predict_affinity's checks have dealt with the options that read embeddings."""
     return not (
-        self.autotune is not None or self.max_spectral_size is not None or
+        self.autotune is not None or
+        (self.max_spectral_size is not None and not affinity_input) or
         (self.min_clusters == 1 and
          not (single_check_covered and self._single_check_struct() is not None)) or
-        (self.fallback_options.spectral_min_embeddings > 1 and not min_embeddings_met) or
-        self.affinity_function is not utils.compute_affinity_matrix or
+        (self.fallback_options.spectral_min_embeddings > 1 and not min_embeddings_met and
+         not affinity_input) or
+        (self.affinity_function is not utils.compute_affinity_matrix and not affinity_input) or
         self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans)
 
   def _naive_fallback(self) -> bool:
