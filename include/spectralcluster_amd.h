@@ -426,6 +426,14 @@ int sc_set_constraint_band(sc_handle h, const double* band, int n);
 int sc_set_constraint_pairs(sc_handle h, const int32_t* rows, const int32_t* cols,
                             const double* vals, int count, int n);
 int sc_constraint_pairs_info(sc_handle h, int* count, size_t* pair_bytes);
+/* sc_set_constraint for a described (n, n) source, read where it is: device or host memory, fp64 /
+ * fp32 / fp16 / bf16, any non-negative element strides (sc_set_affinity_array's rules and errors).
+ * A device source is read in place, a narrow host source crosses the link at its own width; the
+ * kernel that widens it (exactly) into the resident matrix decides its symmetry in the same pass
+ * (a host fp64 source takes sc_set_constraint's copy and separate pass).  The source may be
+ * reused when the call has returned.  State afterwards is sc_set_constraint's: sc_constraint_info
+ * kind 1.  The dense arithmetic runs whatever the matrix holds: no structure is detected. */
+int sc_set_constraint_array(sc_handle h, const sc_array* constraint_matrix);
 int sc_clear_constraint(sc_handle h);
 int sc_apply_constraint(sc_handle h, const sc_config* cfg);
 int sc_constraint_info(sc_handle h, int* kind, int* n, size_t* band_bytes,
@@ -552,6 +560,27 @@ int sc_predict_batch_constraints(sc_handle h, const sc_array* xs, const sc_const
 int sc_predict_batch_affinities(sc_handle h, const sc_array* affinities,
                                 const sc_constraint_desc* cons, int count, const sc_config* cfg,
                                 int64_t* const* labels, sc_diag* diags, int group);
+/* sc_predict_batch_constraints (affinities = 0: xs are embeddings) or sc_predict_batch_affinities
+ * (affinities != 0: xs are (n_i, n_i) affinities) plus a parallel list `dense` of dense constraint
+ * matrices as described sources (sc_set_constraint_array's: device or host, four dtypes, strides).
+ * dense[i].data != NULL: utterance i carries the (n_i, n_i) matrix dense[i], and cons[i].kind must
+ * be 0; otherwise cons[i] applies as in those calls.  cons or dense may be NULL; with dense == NULL
+ * the call is exactly the existing one.  Dense members travel the same routes.  The dense sources of
+ * a group or wave are widened into their member arenas' constraint buffers by k_ingest_affinity_group
+ * launches (one per <= 64 sources) and the host reads their symmetry flags in one wait (the wait of
+ * the affinities' ingest, where there is one).  In ConstraintPropagation before refinement a member
+ * with a symmetric affinity and a symmetric dense constraint joins the group's Neumann chain, whose
+ * last stage runs the dense members' three launches (T Q^T by the full-output grouped product,
+ * T (T Q^T)^T by the symmetric one, the adjustment) with the band and pair members idle; any other
+ * dense member runs its own operator on its arena (sc_apply_constraint).  The member arenas reserve
+ * one more n x ld matrix each; when that does not fit, the constrained members run as single calls
+ * (route 0), a dense one with sc_set_constraint_array in front -- as every dense member of
+ * n >= 4096 does.  Every source and every entry list is validated before the first launch.  With a
+ * device source the handle's stream is synchronised once at entry; sources stay valid until return. */
+int sc_predict_batch_constraint_arrays(sc_handle h, const sc_array* xs,
+                                       const sc_constraint_desc* cons, const sc_array* dense,
+                                       int count, const sc_config* cfg, int64_t* const* labels,
+                                       sc_diag* diags, int group, int affinities);
 /* What ran: one code per utterance of the last sc_predict_batch* call on this handle (a
  * member of a grouped batch that was handed back to the single-call path reports
  * SC_BATCH_ROUTE_SINGLE; after sc_predict_batch / sc_predict_batch_streams every code is).
@@ -870,6 +899,29 @@ int sc_stage_constraint_pairs_group(sc_handle h, const sc_config* cfg, int count
                                     const int32_t* const* rows, const int32_t* const* cols,
                                     const double* const* vals, const int32_t* counts,
                                     double* const* outs);
+/* sc_stage_constraint with the constraint matrix as a described source (sc_set_constraint_array) */
+int sc_stage_constraint_array(sc_handle h, const sc_config* cfg, const double* affinity,
+                              const sc_array* constraint_matrix, int n, double* out);
+/* Test entry: sc_stage_constraint_band_group with member z's constraint given as a dense SYMMETRIC
+ * (ns[z], ns[z]) row-major host matrix constraints[z] (SC_ERR_INVALID for one that is not), in a
+ * NaN-filled matrix of the arena's row pitch.  ns[z] = 0 or constraints[z] = NULL marks an idle
+ * member.  The last stage is the dense one of a constrained batch's chain: T Q^T by the
+ * full-output grouped product, T (T Q^T)^T by the symmetric one, the adjustment. */
+int sc_stage_constraint_dense_group(sc_handle h, const sc_config* cfg, int count,
+                                    const int32_t* ns, const double* const* affinities,
+                                    const double* const* constraints, double* const* outs);
+/* Test entry: ONE launch of the grouped two-operand fp64 product on host operands.  Member z:
+ * outs[z] = As[z] Bs[z]^T (+ addends[z] when epilogue = 2; epilogue = 0: none) for (ns[z], ns[z])
+ * row-major matrices, Bs[z] = NULL (or Bs = NULL): B = A; ns[z] = 0: idle, outs[z] not written.
+ * Operands and result live in device matrices of the arena's row pitch ld = ns[z] rounded up to 16
+ * (+ 16 when that is a multiple of 512), NaN-filled before the operands go in; outs[z] receives
+ * all ns[z] x ld elements of the result buffer, padding columns as the launch left them.
+ * full = 0: the symmetric form (upper-triangle tiles, mirror tiles written transposed: commuting
+ * symmetric operands); full != 0: every tile (ti, tj) from its own operands.  1 <= count <= 16,
+ * ns[z] <= 8192. */
+int sc_stage_gemm_pair_group(sc_handle h, int count, const int32_t* ns, const double* const* As,
+                             const double* const* Bs, const double* const* addends,
+                             double* const* outs, int epilogue, int full);
 /* rowmax / rowsum of Diffuse(a) = a a^T (refinement.py:232-234) for a SYMMETRIC (n, n) input --
  * what RowWiseNormalize (refinement.py:240-245) and the Laplacian degree (laplacian.py:41) read
  * of it -- by either route: mode 1 the explicit fp64 product, mode 2 the matrix-free search

@@ -12,7 +12,7 @@ _PUBLIC = {
     "autotune": ("AutoTune", "AutoTuneProxy"),
     "configs": ("ICASSP2018_REFINEMENT_SEQUENCE", "TURNTODIARIZE_REFINEMENT_SEQUENCE"),
     "constraint": ("ConstraintOptions", "ConstraintName", "ConstraintMatrix", "IntegrationType",
-                   "PairwiseConstraints"),
+                   "PairwiseConstraints", "DenseConstraints"),
     "custom_distance_kmeans": (),
     "fallback_clusterer": ("FallbackOptions", "SingleClusterCondition",
                            "FallbackClustererType"),

@@ -66,6 +66,16 @@ _set_name.restype = ctypes.c_int
 _set_name.argtypes = [ctypes.py_object, ctypes.c_char_p]
 
 
+def dtype_message(what: str, detail: str) -> str:
+  """The TypeError text for a source of a dtype that is none of the four."""
+  return "%s must be float64, float32, float16 or bfloat16 (%s)" % (what, detail)
+
+
+def negative_strides_message(what: str) -> str:
+  """The ValueError text for a source with a negative stride."""
+  return "%s with negative strides are not supported" % what
+
+
 class Source:
   """An `sc_array` and what keeps its memory alive until `release()`.
 
@@ -148,13 +158,12 @@ def _from_capsule(capsule, location: int) -> Source:
       raise ValueError("embeddings must be 2-dimensional")
     dtype = _DLPACK_DTYPES.get((t.dtype.code, t.dtype.bits)) if t.dtype.lanes == 1 else None
     if dtype is None:
-      raise TypeError("embeddings must be float64, float32, float16 or bfloat16 "
-                      "(DLPack type code %d, %d bits, %d lanes)"
-                      % (t.dtype.code, t.dtype.bits, t.dtype.lanes))
+      raise TypeError(dtype_message("embeddings", "DLPack type code %d, %d bits, %d lanes"
+                                    % (t.dtype.code, t.dtype.bits, t.dtype.lanes)))
     rows, cols = int(t.shape[0]), int(t.shape[1])
     row_stride, col_stride = (int(t.strides[0]), int(t.strides[1])) if t.strides else (cols, 1)
     if row_stride < 0 or col_stride < 0:
-      raise ValueError("embeddings with negative strides are not supported")
+      raise ValueError(negative_strides_message("embeddings"))
     itemsize = t.dtype.bits // 8
     assert int(t.byte_offset) % itemsize == 0
     src.array = _lib.ScArray((t.data or 0) + int(t.byte_offset), dtype, location, rows, cols,

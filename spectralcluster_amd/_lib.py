@@ -300,6 +300,30 @@ PROTOTYPES = {
                                                    ctypes.POINTER(ScConfig),
                                                    ctypes.POINTER(_c_int64_p),
                                                    ctypes.POINTER(ScDiag), ctypes.c_int]),
+    "sc_predict_batch_constraint_arrays": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),
+                                                          ctypes.POINTER(ScConstraintDesc),
+                                                          ctypes.POINTER(ScArray), ctypes.c_int,
+                                                          ctypes.POINTER(ScConfig),
+                                                          ctypes.POINTER(_c_int64_p),
+                                                          ctypes.POINTER(ScDiag), ctypes.c_int,
+                                                          ctypes.c_int]),
+    "sc_set_constraint_array": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray)]),
+    "sc_stage_constraint_array": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScConfig),
+                                                 _c_double_p, ctypes.POINTER(ScArray),
+                                                 ctypes.c_int, _c_double_p]),
+    "sc_stage_constraint_dense_group": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScConfig),
+                                                       ctypes.c_int,
+                                                       ctypes.POINTER(ctypes.c_int32),
+                                                       ctypes.POINTER(_c_double_p),
+                                                       ctypes.POINTER(_c_double_p),
+                                                       ctypes.POINTER(_c_double_p)]),
+    "sc_stage_gemm_pair_group": (ctypes.c_int, [_handle_t, ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_int32),
+                                                ctypes.POINTER(_c_double_p),
+                                                ctypes.POINTER(_c_double_p),
+                                                ctypes.POINTER(_c_double_p),
+                                                ctypes.POINTER(_c_double_p), ctypes.c_int,
+                                                ctypes.c_int]),
     "sc_stage_ingest": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray), _c_double_p]),
     "sc_set_affinity_array": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray)]),
     "sc_predict_affinity_array": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),

@@ -8,7 +8,12 @@ values travel instead of the (n, n) array of `compute_diagonals()`
 (`sc_set_constraint_band` / `sc_stage_constraint_band`).  A `PairwiseConstraints` instance -- a
 list of must-link / cannot-link pairs -- is accepted as well: its K directed entries travel
 (`sc_set_constraint_pairs` / `sc_stage_constraint_pairs`), 16 bytes each, and no (n, n) array is
-built on either side.  An ndarray always takes the dense route, whatever it holds.  The E2CP
+built on either side.  A `DenseConstraints` instance wraps a dense (n, n) matrix that is read where
+it is -- host or device memory, float64 / float32 / float16 / bfloat16, any strides -- and widened
+exactly on the device (`sc_set_constraint_array` / `sc_stage_constraint_array`); in a batch it
+travels inside the library call.  An ndarray always takes the dense route through the host
+(widened to float64 there, `sc_set_constraint`), and a `DenseConstraints` the dense arithmetic,
+whatever either holds: no band or sparse structure is looked for.  The E2CP
 inverse `(I - alpha * A_norm)^-1` is evaluated as a Neumann product of fp64 MFMA GEMMs
 (see `csrc/constraint_api.hip: constraint_propagation`), which needs |alpha| < 1 and a
 non-negative affinity; anything else raises `UnsupportedOnDeviceError`.
@@ -17,12 +22,14 @@ non-negative affinity; anything else raises `UnsupportedOnDeviceError`.
 from __future__ import annotations
 
 import abc
+import ctypes
 import dataclasses
 import enum
 import typing
 
 import numpy as np
 
+from spectralcluster_amd import _dlpack
 from spectralcluster_amd import _lib
 
 EPS = 1e-10
@@ -46,7 +53,8 @@ def _device_adjust(affinity: np.ndarray, constraint_matrix, name: ConstraintName
   src = np.ascontiguousarray(affinity, dtype=np.float64)
   banded = isinstance(constraint_matrix, ConstraintMatrix)
   paired = isinstance(constraint_matrix, PairwiseConstraints)
-  if not paired:
+  dense = isinstance(constraint_matrix, DenseConstraints)
+  if not paired and not dense:
     con = constraint_matrix.band() if banded else np.ascontiguousarray(
         constraint_matrix, dtype=np.float64)
   cfg = _lib.ScConfig()
@@ -57,6 +65,16 @@ def _device_adjust(affinity: np.ndarray, constraint_matrix, name: ConstraintName
   cfg.constraint_alpha = float(alpha)
   out = np.empty_like(src)
   handle = _lib.default_handle()
+  if dense:
+    with _lib.use_device(handle.device):
+      source = constraint_matrix.describe(lambda: handle)
+      try:
+        handle.check(handle.lib.sc_stage_constraint_array(
+            handle.raw, cfg, _lib.as_double_p(src), ctypes.byref(source.array), src.shape[0],
+            _lib.as_double_p(out)), TypeError)
+      finally:
+        source.release()
+    return out
   if paired:
     rows, cols, vals = constraint_matrix.entries()
     handle.check(handle.lib.sc_stage_constraint_pairs(
@@ -76,10 +94,11 @@ class ConstraintOperation(metaclass=abc.ABCMeta):
   def check_input(self, affinity: np.ndarray, constraint_matrix):
     """Same checks and messages as reference constraint.py:54-76.  A `ConstraintMatrix`
     stands for the (n, n) matrix of its `compute_diagonals()`, n = its number of scores; a
-    `PairwiseConstraints` for the (n, n) matrix of its `to_dense()`."""
-    if isinstance(constraint_matrix, (ConstraintMatrix, PairwiseConstraints)):
-      n = (constraint_matrix.n if isinstance(constraint_matrix, PairwiseConstraints)
-           else len(constraint_matrix.speaker_turn_scores))
+    `PairwiseConstraints` for the (n, n) matrix of its `to_dense()`; a `DenseConstraints` is
+    the (n, n) matrix it holds."""
+    if isinstance(constraint_matrix, (ConstraintMatrix, PairwiseConstraints, DenseConstraints)):
+      n = (len(constraint_matrix.speaker_turn_scores)
+           if isinstance(constraint_matrix, ConstraintMatrix) else constraint_matrix.n)
       constraint_matrix = np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0))
     for what, m in (("affinity", affinity), ("constraint matrix", constraint_matrix)):
       if len(m.shape) != 2:
@@ -257,3 +276,74 @@ class PairwiseConstraints:
   def __array__(self, dtype=None, copy=None):
     out = self.to_dense()
     return out if dtype is None else out.astype(dtype, copy=False)
+
+
+def check_square_input(matrix, what: str) -> int:
+  """The TypeError / ValueError for an object that is no (n, n) matrix -- no `shape`, not 2-D,
+  not square -- before any device is touched.  Returns n."""
+  shape = np.shape(matrix) if isinstance(matrix, np.ndarray) else getattr(matrix, "shape", None)
+  if shape is None:
+    raise TypeError("%s must be a numpy array or support __dlpack__" % what)
+  shape = tuple(int(s) for s in shape)
+  if len(shape) != 2:
+    raise ValueError("%s must be 2-dimensional, got shape %s" % (what, shape))
+  if shape[0] != shape[1]:
+    raise ValueError("%s must be a square matrix, got shape %s" % (what, shape))
+  return shape[0]
+
+
+class DenseConstraints:
+  """A dense (n, n) constraint matrix taken where it is: a model's pairwise same-speaker /
+  different-speaker scores, learned must-link weights -- a NumPy array or an object with
+  `__dlpack__` (a PyTorch tensor on the clusterer's GPU), float64 / float32 / float16 / bfloat16,
+  contiguous or a strided view (a `.T`, every other column of a wider array).
+
+  The object is stored as it is: nothing is copied or converted here, and the device widens the
+  values exactly when a call reads them, deciding in the same kernel pass whether the matrix is
+  symmetric.  A device tensor needs no synchronisation by the caller and may be overwritten or
+  freed when the call that read it has returned.  Pass the wrapper wherever a constraint matrix is
+  accepted; inside `predict_batch` / `predict_affinity_batch` it travels in the library call,
+  where a raw ndarray sends the batch through per-utterance calls.
+
+  No structure is detected: a `DenseConstraints` always takes the dense arithmetic (two n^3
+  products in ConstraintPropagation), also when the matrix it holds is a band or a handful of
+  pairs -- `ConstraintMatrix` and `PairwiseConstraints` are the forms for those.
+
+  TypeError / ValueError as `predict_affinity` raises them for its matrix, here at construction:
+  an object without a shape, not 2-D, not square; a dtype that is none of the four (nothing is
+  promoted here); a negative stride.  An ndarray is checked in full.  A DLPack object is checked
+  through its `dtype` attribute and its `stride()` / `strides`, which PyTorch, CuPy and JAX arrays
+  have, without asking for a capsule; one that has neither is checked when a call describes it,
+  with the same errors."""
+
+  _DTYPE_NAMES = ("float64", "float32", "float16", "bfloat16")
+
+  def __init__(self, matrix):
+    what = "constraint matrix"
+    self.n = check_square_input(matrix, what)
+    if isinstance(matrix, np.ndarray):
+      if matrix.dtype not in (np.dtype(np.float64), np.dtype(np.float32), np.dtype(np.float16)):
+        raise TypeError(_dlpack.dtype_message(what, "got %s" % matrix.dtype))
+      strides = matrix.strides
+    elif not (hasattr(matrix, "__dlpack__") and hasattr(matrix, "__dlpack_device__")):
+      raise TypeError("%s must be a numpy array or support __dlpack__" % what)
+    else:
+      dtype = getattr(matrix, "dtype", None)
+      # ("torch.float32", "float32", dtype('float32'), "<class 'jax.numpy.float32'>")
+      if dtype is not None and not any(
+          str(getattr(dtype, "name", dtype)).split(".")[-1].rstrip("'>") == name
+          for name in self._DTYPE_NAMES):
+        raise TypeError(_dlpack.dtype_message(what, "got %s" % dtype))
+      strides = getattr(matrix, "stride", None)
+      strides = strides() if callable(strides) else getattr(matrix, "strides", None)
+    if strides is not None and any(int(s) < 0 for s in strides):
+      raise ValueError(_dlpack.negative_strides_message("constraint matrices"))
+    self.matrix = matrix
+
+  @property
+  def shape(self) -> typing.Tuple[int, int]:
+    return (self.n, self.n)
+
+  def describe(self, get_handle):
+    """The `_dlpack.Source` of the matrix as it lies (release() it after the library call)."""
+    return _dlpack.describe(self.matrix, get_handle, strided=True)

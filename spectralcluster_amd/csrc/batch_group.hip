@@ -28,7 +28,10 @@
 // A batch may carry one speaker-turn band per utterance (sc_predict_batch_constrained): the same
 // routes on one lane with member-by-member fronts, each member's band resident in its arena, and
 // ConstraintPropagation before refinement as one chain of grouped launches per group
-// (enqueue_front; constraint_api.hip: constraint_propagation_group).
+// (enqueue_front; constraint_api.hip: constraint_propagation_group).  A member's constraint may
+// also be an entry list or a dense matrix given as a described source
+// (sc_predict_batch_constraint_arrays): the dense sources of a front are widened into the member
+// arenas' Cq by the grouped ingest, together with the affinities where the batch's arrays are those.
 #include <ctime>
 #include <thread>
 #include <utility>
@@ -45,10 +48,12 @@ double now_us() {
 
 // The Bands of a constrained batch under `cfg` ...
 Bands make_bands(const sc_constraint_desc* cons, const std::vector<double>* packed,
-                 const char* pairs_symmetric, int kmax, const sc_config* cfg) {
+                 const char* pairs_symmetric, int kmax, const sc_config* cfg,
+                 const sc_array* dense) {
   Bands b;
   if (cfg->constraint_name == SC_CONSTRAINT_NONE) return b;  // (nothing would read them)
   b.cons = cons;
+  b.dense = dense;
   b.packed = packed;
   b.pairs_symmetric = pairs_symmetric;
   b.kmax = kmax;
@@ -60,9 +65,15 @@ Bands make_bands(const sc_constraint_desc* cons, const std::vector<double>* pack
   }
   return b;
 }
-// ... and what a member arena holds for it, reserved with the arena (never inside a front)
+// ... and what a member arena holds for it, reserved with the arena (never inside a front).  The
+// one exception is the staging of a front's HOST dense sources (and host affinities), which lies
+// in the first arena's Xstage at the sources' own width and grows in the first front that needs
+// more (ingest_member_sources); constraint_workspace_fits counts its worst case.
 int reserve_constraint(sc_handle hz, const Bands* bands, int n_max) {
-  if (!bands || !bands->cons) return SC_OK;
+  if (!bands || (!bands->cons && !bands->dense)) return SC_OK;
+  // (a dense member's matrix: the ingest kernel widens its source into Cq)
+  if (bands->dense)
+    SC_TRY(grow(hz, hz->Cq, (size_t)n_max * matrix_ld(n_max) * sizeof(double)));
   SC_TRY(grow(hz, hz->Cband, (size_t)std::max(n_max - 1, 1) * sizeof(double)));
   if (bands->kmax > 0) {  // entries (16 bytes each) and AffinityIntegration's gathered originals
     SC_TRY(grow(hz, hz->Cpairs, (size_t)bands->kmax * 2 * sizeof(double)));
@@ -98,41 +109,67 @@ int member_problem(sc_handle lead, sc_handle h, const sc_array& x, int n, int d,
   return SC_OK;
 }
 
-// The members of a front whose arrays are the callers' affinities (Bands::affinities): ONE grouped
-// ingest launch on `s` widens every member's matrix into its arena's A0 and leaves the members'
-// symmetry flags in one device array, which the host reads once -- the front's only wait; the
-// arenas then are in the state sc_set_affinity_array leaves.  Descriptor table, flags and the
-// staging rows of host members live in the first arena's staging buffer (the group owns it).
-int ingest_member_affinities(sc_handle lead, const sc_array* xs, const int* idx, int count,
-                             int slot0, std::vector<sc_handle_s*>* arenas, hipStream_t s) {
-  std::vector<sc_array> as(count);
-  std::vector<double*> dsts(count);
+// The members of a front whose arrays are the callers' affinities (Bands::affinities) and the dense
+// constraints its members carry (Bands::dense): grouped ingest launches on `s`, one per 64
+// sources, widen every affinity into its arena's A0 and every dense constraint into its arena's Cq
+// and leave the sources' symmetry flags in one device array, which the host reads once -- the
+// front's only wait; the arenas of ingested affinities then are in the state sc_set_affinity_array
+// leaves, and dense_symmetric[z] says what member z's constraint is (enqueue_front makes it the
+// arena's resident constraint).  Descriptor table, flags and the staging rows of host members live
+// in the first arena's staging buffer (the group owns it).
+int ingest_member_sources(sc_handle lead, const sc_array* xs, const int* idx, int count,
+                          int slot0, std::vector<sc_handle_s*>* arenas, hipStream_t s,
+                          const Bands& bands, std::vector<char>* dense_symmetric) {
+  std::vector<sc_array> as;
+  std::vector<double*> dsts;
   std::vector<sc_handle> hs(count);
-  std::vector<int> flags(count, 0);
+  std::vector<int> dense_at(count, -1);
+  dense_symmetric->assign(count, 0);
   for (int z = 0; z < count; ++z) {
     SC_TRY(group_slot(lead, slot0 + z, &hs[z], arenas));
     sc_handle h = hs[z];
     h->err.clear();
-    as[z] = xs[idx[z]];
-    const int n = (int)as[z].rows;
-    int rc = ensure_matrices(h, n, 0);
-    if (rc == SC_OK) rc = ensure_tilemap(h, n);
-    if (rc == SC_OK) rc = grow(h, h->symflag, 16);
+    const int n = (int)xs[idx[z]].rows;
+    int rc = SC_OK;
+    if (bands.affinities) {
+      rc = ensure_matrices(h, n, 0);
+      if (rc == SC_OK) rc = ensure_tilemap(h, n);
+      if (rc == SC_OK) rc = grow(h, h->symflag, 16);
+    }
     if (rc != SC_OK) return fail(lead, rc, h->err);
-    dsts[z] = ptr<double>(h->A0);
+    if (bands.affinities) {
+      as.push_back(xs[idx[z]]);
+      dsts.push_back(ptr<double>(h->A0));
+    }
   }
+  for (int z = 0; z < count; ++z) {  // (behind the affinities: flags[z] stays member z's affinity)
+    if (!bands.is_dense(idx[z])) continue;
+    sc_handle h = hs[z];
+    const int n = (int)bands.dense[idx[z]].rows;
+    // (reserved with the arena: reserve_constraint)
+    if (grow(h, h->Cq, (size_t)n * matrix_ld(n) * sizeof(double)) != SC_OK)
+      return fail(lead, SC_ERR_OOM, h->err);
+    dense_at[z] = (int)as.size();
+    as.push_back(bands.dense[idx[z]]);
+    dsts.push_back(ptr<double>(h->Cq));
+  }
+  const int total = (int)as.size();
+  if (total == 0) return SC_OK;
+  std::vector<int> flags(total, 0);
   auto align256 = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t table_at = align256(count * sizeof(int));
-  const size_t stage_at = table_at + align256(count * affinity_group_table_bytes());
+  const size_t table_at = align256(total * sizeof(int));
+  const size_t stage_at = table_at + align256(total * affinity_group_table_bytes());
   sc_handle h0 = hs[0];
-  if (grow(h0, h0->Xstage, stage_at + affinity_group_stage_bytes(as.data(), count)) != SC_OK)
+  if (grow(h0, h0->Xstage, stage_at + affinity_group_stage_bytes(as.data(), total)) != SC_OK)
     return fail(lead, SC_ERR_OOM, h0->err);
   unsigned char* base = static_cast<unsigned char*>(h0->Xstage.p);
-  SC_TRY(ingest_affinity_group(lead, as.data(), count, dsts.data(), reinterpret_cast<int*>(base),
+  SC_TRY(ingest_affinity_group(lead, as.data(), total, dsts.data(), reinterpret_cast<int*>(base),
                                base + stage_at, base + table_at, s, flags.data()));
   for (int z = 0; z < count; ++z) {
+    if (dense_at[z] >= 0) (*dense_symmetric)[z] = flags[dense_at[z]] != 0 ? 1 : 0;
+    if (!bands.affinities) continue;
     sc_handle h = hs[z];
-    h->n = (int)as[z].rows;
+    h->n = (int)xs[idx[z]].rows;
     h->d = 0;
     h->ldn = matrix_ld(h->n);
     h->ldx = 0;
@@ -177,8 +214,10 @@ int enqueue_front(sc_handle lead, const sc_array* xs, const int* ns, int d,
   };
   std::vector<int> chained;  // members whose affinity the grouped chain adjusts
   const bool affinities = bands && bands->affinities;
-  if (affinities)
-    SC_TRY(ingest_member_affinities(lead, xs, idx, count, slot0, arenas, chain_stream));
+  std::vector<char> dense_symmetric;  // of the members that carry a dense constraint
+  if (affinities || (bands && bands->dense))
+    SC_TRY(ingest_member_sources(lead, xs, idx, count, slot0, arenas, chain_stream, *bands,
+                                 &dense_symmetric));
   for (int z = 0; z < count; ++z) {
     Member& m = mb[z];
     m = Member();
@@ -214,6 +253,18 @@ int enqueue_front(sc_handle lead, const sc_array* xs, const int* ns, int d,
     // (the grouped chain works on symmetric affinities: a caller's matrix that is not symmetric
     //  takes the member's own operator below)
     const bool chain = bands && bands->chain && h->affinity_symmetric;
+    if (rc == SC_OK && bands && bands->is_dense(m.index)) {
+      // (its matrix is in Cq already: ingest_member_sources)
+      h->have_constraint = true;
+      h->constraint_symmetric = dense_symmetric[z] != 0;
+      h->qn = h->n;
+      // (the chain's dense stage is the symmetric one; any other Q takes the member's own operator)
+      if (chain && h->constraint_symmetric) {
+        chained.push_back(z);
+        SC_HIP(lead, hipEventRecord(h->sync_ev, h->stream));  // "the affinity is there"
+        continue;
+      }
+    }
     if (rc == SC_OK && pairs && chain) {
       chained.push_back(z);
       SC_HIP(lead, hipEventRecord(h->sync_ev, h->stream));  // "affinity and entries are there"
@@ -268,6 +319,10 @@ int enqueue_front(sc_handle lead, const sc_array* xs, const int* ns, int d,
         cm[q].pvals = ptr<double>(h->Cpairs);
         cm[q].prows = reinterpret_cast<const int32_t*>(cm[q].pvals + cm[q].pk);
         cm[q].pcols = cm[q].prows + cm[q].pk;
+      } else if (!h->constraint_banded) {  // a dense symmetric matrix
+        if (h->Cq.bytes < nn)
+          return fail(lead, SC_ERR_INVALID, "member arena without the dense constraint matrix");
+        cm[q].q = ptr<double>(h->Cq);
       }
     }
     SC_TRY(constraint_propagation_group(lead, chain_stream, cm, cnt, cfg->constraint_alpha));
@@ -478,7 +533,7 @@ int run_short_route(sc_handle h, const sc_array* xs, const int* ns, int d,
   const bool wave = !sw::short_front_memberwise() && !bands &&
                     d <= kShortWaveMaxD && short_wave_covers(cfg, &wave_ops);
   // (the grouped chain of a wave, the grouped ingest of callers' affinities: a stream of the wave's bank)
-  if (wave || (bands && (bands->chain || bands->affinities)))
+  if (wave || (bands && (bands->chain || bands->affinities || bands->dense)))
     for (int b = 0; b < banks; ++b) SC_TRY(ensure_bank_stream(h, b));
   if (wave && wave_ops.blur_radius > 0) SC_TRY(upload_group_blur_weights(h, cfg));
   std::vector<Member> mbs[kGroupBanks];
@@ -652,14 +707,15 @@ int run_group_lane(sc_handle h, const sc_array* xs, const int* ns, int d,
 }
 
 // The members of a constrained batch that run as single calls on the caller's handle: each with
-// its own band or entry list resident for the call (sc_predict with sc_set_constraint_band /
-// sc_set_constraint_pairs in front).
+// its own band, entry list or dense matrix resident for the call (sc_predict with
+// sc_set_constraint_band / sc_set_constraint_pairs / sc_set_constraint_array in front).
 int predict_single_banded(sc_handle h, const std::vector<int>& list, const sc_array* xs,
                           const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
                           const Bands& bands) {
   for (int i : list) {
     const int n = (int)xs[i].rows;
-    if (bands.pairs(i))
+    if (bands.is_dense(i)) SC_TRY(sc_set_constraint_array(h, bands.dense + i));
+    else if (bands.pairs(i))
       SC_TRY(sc_set_constraint_pairs(h, bands.cons[i].rows, bands.cons[i].cols, bands.cons[i].vals,
                                      bands.cons[i].count, n));
     else if (bands.band(i)) SC_TRY(sc_set_constraint_band(h, bands.band(i), n));
@@ -708,21 +764,28 @@ int predict_single_checked(sc_handle h, const std::vector<int>& list, const sc_a
 // Do the cp[] work matrices of a constrained batch fit?  Worst case: every position of both
 // banks of the Lanczos route at the largest grouped member, every position of both wave banks of
 // the short route at kDenseMax (what the arenas below reserve); what the arenas already hold counts.
-bool constraint_workspace_fits(sc_handle h, const Bands& bands, int largest, bool any_short) {
-  if (bands.ncp == 0) return true;
+// `stage_bytes`: the staging of the host dense sources of one front, worst case (the first arena
+// of each bank holds it).
+bool constraint_workspace_fits(sc_handle h, const Bands& bands, int largest, bool any_short,
+                               size_t stage_bytes) {
+  if (bands.ncp == 0 && !bands.dense) return true;
   auto need = [&](const std::vector<sc_handle_s*>& slots, int positions, int n) {
     const size_t nn = (size_t)n * matrix_ld(n) * sizeof(double);
     size_t bytes = 0;
-    for (int z = 0; z < positions; ++z)
+    for (int z = 0; z < positions; ++z) {
       for (int i = 0; i < bands.ncp; ++i) {
         const size_t have = z < (int)slots.size() ? slots[z]->cp[i].bytes : 0;
         if (have < nn) bytes += nn;
       }
+      // (a batch with a dense member: one more matrix per position, the arena's Cq)
+      if (bands.dense && (z < (int)slots.size() ? slots[z]->Cq.bytes : 0) < nn) bytes += nn;
+    }
     return bytes;
   };
   size_t bytes = 0;
   if (largest > 0) bytes += need(h->gslots, kGroupBanks * kGroupMax, largest);
   if (any_short) bytes += need(h->gshort, kGroupBanks * kShortWidth, kDenseMax);
+  bytes += kGroupBanks * stage_bytes;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
   return (double)bytes <= 0.85 * (double)free_b;
@@ -733,7 +796,8 @@ bool constraint_workspace_fits(sc_handle h, const Bands& bands, int largest, boo
 int predict_batch_core(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
                        const sc_config* cfg, int64_t* const* labels, sc_diag* diags, int group,
                        const Bands& band_set, const SingleCheck* sc = nullptr) {
-  const Bands* bands = band_set.cons || band_set.affinities ? &band_set : nullptr;
+  const Bands* bands =
+      band_set.cons || band_set.affinities || band_set.dense ? &band_set : nullptr;
   if (sc && sc->single) std::fill(sc->single, sc->single + count, 0);
   SC_TRY(validate_config(h, cfg));
   SC_HIP(h, hipSetDevice(h->device));
@@ -775,7 +839,17 @@ int predict_batch_core(sc_handle h, const sc_array* xs, const int* ns, int d, in
     bool any_short = false;
     for (int i : grouped) largest = std::max(largest, ns[i]);
     for (int i : shorts) any_short = any_short || bands->has(i);
-    if (!constraint_workspace_fits(h, *bands, largest, any_short)) {
+    // a front's host dense sources are staged at their own width: at most `group` members of a
+    // lockstep group, each no larger than the largest one, or a wave's kShortWidth of n <= kDenseMax
+    size_t stage_one = 0, stage_short = 0;
+    auto staged = [&](int i) {
+      return bands->is_dense(i) && bands->dense[i].location == SC_MEM_HOST
+                 ? affinity_group_stage_bytes(bands->dense + i, 1) : (size_t)0;
+    };
+    for (int i : grouped) stage_one = std::max(stage_one, staged(i));
+    for (int i : shorts) stage_short = std::max(stage_short, staged(i));
+    const size_t stage_bytes = std::max((size_t)group * stage_one, (size_t)kShortWidth * stage_short);
+    if (!constraint_workspace_fits(h, *bands, largest, any_short, stage_bytes)) {
       auto hand_over = [&](std::vector<int>& list) {
         std::vector<int> keep;
         for (int i : list) (bands->has(i) ? single : keep).push_back(i);
@@ -1497,7 +1571,8 @@ bool release_large_arenas(sc_handle* leads, int lanes, bool always) {
     for (int l = 0; l < lanes; ++l)
       for (sc_handle sub : leads[l]->gslots) {
         held += sub->A0.bytes + sub->B1.bytes + sub->B2.bytes;
-        for (const DevBuf& w : sub->cp) held += w.bytes;  // (a constrained batch's work matrices)
+        for (const DevBuf& w : sub->cp) held += w.bytes;  // (a constrained batch's work matrices,
+        held += sub->Cq.bytes + sub->Xstage.bytes;        //  dense constraints and their staging)
       }
     if (held <= total_b / 4) return false;
   }
@@ -1570,7 +1645,7 @@ extern "C" int sc_predict_batch_constrained(sc_handle h, const sc_array* xs,
 int predict_batch_constrained_impl(sc_handle h, const sc_array* xs, const sc_constraint_desc* cons,
                                    const int* ns, int d, int count, const sc_config* cfg,
                                    int64_t* const* labels, sc_diag* diags, int group,
-                                   bool affinities) {
+                                   bool affinities, const sc_array* dense) {
   // every entry list is checked, and packed for its upload, before anything is launched
   std::vector<std::vector<double>> packed((size_t)count);
   std::vector<char> pairs_symmetric((size_t)count, 1);
@@ -1608,7 +1683,7 @@ int predict_batch_constrained_impl(sc_handle h, const sc_array* xs, const sc_con
       (void)sc_clear_constraint(h);
     }
   } cleanup{h};
-  Bands bands = make_bands(cons, packed.data(), pairs_symmetric.data(), kmax, cfg);
+  Bands bands = make_bands(cons, packed.data(), pairs_symmetric.data(), kmax, cfg, dense);
   bands.affinities = affinities;
   cleanup.rc = predict_batch_core(h, xs, ns, d, count, cfg, labels, diags, group, bands);
   return cleanup.rc;
@@ -1642,6 +1717,55 @@ extern "C" int sc_predict_batch_affinities(sc_handle h, const sc_array* as,
   SC_TRY(sc_clear_constraint(h));  // the handle's own resident constraint takes no part
   return predict_batch_constrained_impl(h, as, cons, ns.data(), 0, count, cfg, labels, diags, group,
                                         true);
+}
+
+extern "C" int sc_predict_batch_constraint_arrays(sc_handle h, const sc_array* xs,
+                                                  const sc_constraint_desc* cons,
+                                                  const sc_array* dense, int count,
+                                                  const sc_config* cfg, int64_t* const* labels,
+                                                  sc_diag* diags, int group, int affinities) {
+  if (!h) return SC_ERR_INVALID;
+  if (!dense)  // exactly the existing calls
+    return affinities ? sc_predict_batch_affinities(h, xs, cons, count, cfg, labels, diags, group)
+                      : sc_predict_batch_constraints(h, xs, cons, count, cfg, labels, diags, group);
+  if (!xs || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
+  if (group < 2)
+    return fail(h, SC_ERR_INVALID,
+                "sc_predict_batch_constraint_arrays is the grouped form: group >= 2");
+  SC_TRY(validate_config(h, cfg));
+  SC_HIP(h, hipSetDevice(h->device));
+  bool device_source = false;
+  std::vector<int> ns(count, 0);
+  int d = 0;
+  if (affinities) {
+    for (int i = 0; i < count; ++i) {  // every descriptor before the first launch
+      SC_TRY(validate_affinity_array(h, xs + i));
+      ns[i] = (int)xs[i].rows;
+      device_source |= xs[i].location == SC_MEM_DEVICE;
+    }
+  } else {
+    SC_TRY(validate_batch_arrays(h, xs, count, &ns, &d, &device_source));
+  }
+  bool any_dense = false;
+  for (int i = 0; i < count; ++i) {
+    if (!labels[i]) return fail(h, SC_ERR_INVALID, "NULL labels");
+    if (!dense[i].data) continue;
+    if (cons && cons[i].kind != 0)
+      return fail(h, SC_ERR_INVALID, "an utterance with a dense constraint has constraint kind 0");
+    SC_TRY(validate_constraint_array(h, dense + i));
+    if (dense[i].rows != ns[i])
+      return fail(h, SC_ERR_INVALID, "affinity and constraint matrix must have the same shape");
+    any_dense = true;
+    device_source |= dense[i].location == SC_MEM_DEVICE;
+  }
+  SC_TRY(sc_clear_constraint(h));  // the handle's own resident constraint takes no part
+  if (count == 0) {
+    h->last_routes.clear();
+    return SC_OK;
+  }
+  if (device_source) SC_HIP(h, hipStreamSynchronize(h->stream));  // (as sc_predict_batch_arrays)
+  return predict_batch_constrained_impl(h, xs, cons, ns.data(), d, count, cfg, labels, diags,
+                                        group, affinities != 0, any_dense ? dense : nullptr);
 }
 
 extern "C" int sc_predict_batch_single(sc_handle h, const sc_array* xs, int count,

@@ -30,7 +30,11 @@ struct Bands {
   // sc_predict_batch_affinities: the batch's arrays are (n, n) affinities the callers hold, not
   // embeddings -- the grouped ingest of a front replaces the rows' upload and the affinity GEMM
   bool affinities = false;
-  bool has(int i) const { return cons && cons[i].kind != 0; }
+  // sc_predict_batch_constraint_arrays: dense[i].data != nullptr -- utterance i carries a dense
+  // (n_i, n_i) constraint as a described source (its cons[i].kind is 0); nullptr: no member does
+  const sc_array* dense = nullptr;
+  bool is_dense(int i) const { return dense && dense[i].data; }
+  bool has(int i) const { return (cons && cons[i].kind != 0) || is_dense(i); }
   const double* band(int i) const { return cons && cons[i].kind == 2 ? cons[i].band : nullptr; }
   bool pairs(int i) const { return cons && cons[i].kind == 3; }
 };

@@ -163,7 +163,9 @@ static int constraint_propagation(sc_handle h, const double* a, bool sym_a, cons
 // the whole group where the members one by one take 13 each (and split their few tiles over K).
 // `steps` depends on alpha alone.  Per member the elementwise arithmetic is the single route's;
 // the products sum every tile's K whole.  The adjusted affinity replaces mem[z].A.  No
-// allocation, no synchronisation.
+// allocation, no synchronisation.  A member's constraint may instead be an entry list (two
+// launches for the pair members) or a dense symmetric matrix (mem[z].q: T Q^T by the full-output
+// grouped product, T X^T, adjust).
 int constraint_propagation_group(sc_handle lead, hipStream_t s, const CpGroupMember* mem,
                                  int count, double alpha) {
   int steps = 0;
@@ -214,13 +216,17 @@ int constraint_propagation_group(sc_handle lead, hipStream_t s, const CpGroupMem
     launch_gemm_nt_pair_group(s, gm, count, kEpiAdd);
     for (int z = 0; z < count; ++z) std::swap(T[z], Tn[z]);
   }
-  // The last stage, twice: the band members with the pair members idle, then the reverse (a
-  // launch without live members is skipped).
+  // The last stage, three times: the band members with the others idle, then the dense members,
+  // then the pair members (a launch without live members is skipped).
   // X = T Q^T into the idle partner of T,  T Q T = T X^T into the idle partner of P
-  bool any_band = false, any_pairs = false;
+  bool any_band = false, any_pairs = false, any_dense = false;
   for (int z = 0; z < count; ++z) {
     it[z].n = 0;
     if (mem[z].n <= 0) continue;
+    if (mem[z].q) {
+      any_dense = true;
+      continue;
+    }
     if (mem[z].pairs) {
       any_pairs = any_pairs || mem[z].pk > 0;  // (no entries: Q = 0, A stays as it is)
       continue;
@@ -232,11 +238,31 @@ int constraint_propagation_group(sc_handle lead, hipStream_t s, const CpGroupMem
     launch_cp_band_product_group(s, it, count);
     for (int z = 0; z < count; ++z) {
       product(z, T[z], Tn[z], Pn[z], nullptr);
-      if (mem[z].pairs) gm[z] = GemmPairItem();
+      if (mem[z].pairs || mem[z].q) gm[z] = GemmPairItem();
     }
     launch_gemm_nt_pair_group(s, gm, count, kEpiNone);
     for (int z = 0; z < count; ++z)
       if (it[z].n > 0) it[z] = CpItem{Pn[z], mem[z].A, mem[z].A, nullptr, mem[z].n, mem[z].ld};
+    launch_cp_adjust_group(s, it, count, (1.0 - alpha) * (1.0 - alpha));
+  }
+  if (any_dense) {
+    // X = T Q^T is not symmetric: every tile from its own operands (the full-output product);
+    // T X^T = T Q T is, for a symmetric Q
+    for (int z = 0; z < count; ++z) {
+      product(z, T[z], mem[z].q, Tn[z], nullptr);
+      if (!mem[z].q) gm[z] = GemmPairItem();
+    }
+    launch_gemm_nt_pair_group(s, gm, count, kEpiNone, true);
+    for (int z = 0; z < count; ++z) {
+      product(z, T[z], Tn[z], Pn[z], nullptr);
+      if (!mem[z].q) gm[z] = GemmPairItem();
+    }
+    launch_gemm_nt_pair_group(s, gm, count, kEpiNone);
+    for (int z = 0; z < count; ++z) {
+      it[z].n = 0;
+      if (mem[z].n > 0 && mem[z].q)
+        it[z] = CpItem{Pn[z], mem[z].A, mem[z].A, nullptr, mem[z].n, mem[z].ld};
+    }
     launch_cp_adjust_group(s, it, count, (1.0 - alpha) * (1.0 - alpha));
   }
   if (any_pairs) {
@@ -373,6 +399,39 @@ extern "C" int sc_set_constraint(sc_handle h, const double* q, int n) {
   return SC_OK;
 }
 
+// validate_affinity_array's rules for a dense constraint source
+int validate_constraint_array(sc_handle h, const sc_array* q) {
+  SC_TRY(validate_array(h, q));
+  if (q->rows != q->cols) return fail(h, SC_ERR_INVALID, "constraint matrix must be (n, n)");
+  return SC_OK;
+}
+
+// sc_set_constraint for a described source: read where it is (a device source in place, a narrow
+// host source crossing the link at its own width), widened exactly into Cq by the ingest kernel,
+// whose own flag is the symmetry -- one pass.  (Host fp64 keeps sc_set_constraint's copy and the
+// separate pass: ingest_affinity_into.)
+extern "C" int sc_set_constraint_array(sc_handle h, const sc_array* q) {
+  if (!h) return SC_ERR_INVALID;
+  SC_TRY(validate_constraint_array(h, q));
+  SC_HIP(h, hipSetDevice(h->device));
+  const int n = (int)q->rows, ld = matrix_ld(n);
+  SC_TRY(grow(h, h->Cq, (size_t)n * ld * sizeof(double)));
+  SC_TRY(grow(h, h->symflag, 16));
+  h->have_constraint = false;
+  // (symflag[0] is the affinity ingest's word and [1] the embedding rows': this one is [2])
+  int* flag = ptr<int>(h->symflag) + 2;
+  bool packed = false;  // (not read: the wait below comes whether or not the source was packed)
+  SC_TRY(ingest_affinity_into(h, *q, ptr<double>(h->Cq), ld, flag, h->stream, &packed));
+  int symmetric = 0;
+  SC_HIP(h, hipMemcpyAsync(&symmetric, flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  SC_HIP(h, hipStreamSynchronize(h->stream));  // (and the source may be reused)
+  h->constraint_symmetric = symmetric != 0;
+  h->have_constraint = true;
+  h->constraint_banded = h->constraint_pairs = false;
+  h->qn = n;
+  return SC_OK;
+}
+
 // ConstraintMatrix.compute_diagonals (constraint.py:188-201) without the matrix: n - 1 doubles
 // up, nothing else (a band is symmetric by construction)
 extern "C" int sc_set_constraint_band(sc_handle h, const double* band, int n) {
@@ -489,6 +548,24 @@ extern "C" int sc_stage_constraint(sc_handle h, const sc_config* cfg, const doub
   return d2h_matrix(h, ptr<double>(h->A0), h->ldn, n, n, out);
 }
 
+// the same with the constraint matrix as a described source (sc_set_constraint_array)
+extern "C" int sc_stage_constraint_array(sc_handle h, const sc_config* cfg, const double* affinity,
+                                         const sc_array* q, int n, double* out) {
+  if (!h) return SC_ERR_INVALID;
+  SC_TRY(validate_config(h, cfg));
+  if (!affinity || !out || n <= 0)
+    return fail(h, SC_ERR_INVALID, "affinity and constraint matrix must be (n, n)");
+  SC_TRY(validate_constraint_array(h, q));
+  if (q->rows != n)
+    return fail(h, SC_ERR_INVALID, "affinity and constraint matrix must have the same shape");
+  SC_TRY(sc_set_affinity(h, affinity, n));
+  SC_TRY(sc_set_constraint_array(h, q));
+  const int rc = sc_apply_constraint(h, cfg);
+  sc_clear_constraint(h);
+  SC_TRY(rc);
+  return d2h_matrix(h, ptr<double>(h->A0), h->ldn, n, n, out);
+}
+
 extern "C" int sc_stage_constraint_band(sc_handle h, const sc_config* cfg,
                                         const double* affinity, const double* band, int n,
                                         double* out) {
@@ -525,26 +602,38 @@ extern "C" int sc_stage_constraint_pairs(sc_handle h, const sc_config* cfg,
 // affinity and the four work matrices at the arena's row pitch, all of it -- padding columns and
 // workspaces -- quiet NaNs before the inputs go in, so a read outside a matrix shows in the result.
 // bands == nullptr: the members' constraints are entry lists (rows[z], cols[z], vals[z], counts[z]
-// <= ns[z] entries) instead, in NaN-filled buffers of their own.
+// <= ns[z] entries) instead, in NaN-filled buffers of their own.  denses != nullptr: they are dense
+// symmetric (ns[z], ns[z]) host matrices, each in a NaN-filled matrix of the arena's pitch
+// (denses[z] == nullptr: idle member).
 static int stage_constraint_group(sc_handle h, const sc_config* cfg, int count, const int32_t* ns,
                                   const double* const* affinities, const double* const* bands,
                                   const int32_t* const* rows, const int32_t* const* cols,
                                   const double* const* vals, const int32_t* counts,
-                                  double* const* outs) {
+                                  double* const* outs, const double* const* denses = nullptr) {
   SC_TRY(validate_config(h, cfg));
   if (count < 1 || count > kGroupMax || !ns || !affinities || !outs ||
-      (!bands && (!rows || !cols || !vals || !counts)))
+      (!bands && !denses && (!rows || !cols || !vals || !counts)))
     return fail(h, SC_ERR_INVALID, "a constraint group holds 1 .. 16 members");
+  auto is_idle = [&](int z) {
+    return ns[z] == 0 || (bands && !bands[z] && ns[z] > 1) || (denses && !denses[z]);
+  };
   bool list_symmetric[kGroupMax] = {};
   for (int z = 0; z < count; ++z) {
     if (ns[z] < 0) return fail(h, SC_ERR_INVALID, "n must not be negative (0: idle member)");
     // (larger tile grids get their order uploaded per size: one per handle at a time)
     if (gemm_tile_dim(ns[z]) > kTilemapTableMax)
       return fail(h, SC_ERR_UNSUPPORTED, "a member of the constraint group is larger than 8192");
-    const bool idle = ns[z] == 0 || (bands && !bands[z] && ns[z] > 1);
+    const bool idle = is_idle(z);
     if (!idle && (!affinities[z] || !outs[z]))
       return fail(h, SC_ERR_INVALID, "affinity must be (n, n) and the band hold n - 1 values");
-    if (!idle && !bands) {
+    if (!idle && denses) {  // (the grouped chain's dense stage is the symmetric one)
+      const int n = ns[z];
+      for (int i = 0; i < n; ++i)
+        for (int j = i + 1; j < n; ++j)
+          if (!(denses[z][(size_t)i * n + j] == denses[z][(size_t)j * n + i]))
+            return fail(h, SC_ERR_INVALID, "a grouped dense constraint must be symmetric");
+    }
+    if (!idle && !bands && !denses) {
       if (counts[z] > ns[z])
         return fail(h, SC_ERR_UNSUPPORTED,
                     "an entry list of more than n entries takes the dense route: not grouped");
@@ -579,11 +668,16 @@ static int stage_constraint_group(sc_handle h, const sc_config* cfg, int count, 
   std::vector<double> packed[kGroupMax];  // (pageable sources of the entry uploads)
   for (int z = 0; z < count; ++z) {
     const int n = ns[z];
-    if (n == 0 || (bands && !bands[z] && n > 1)) continue;  // idle
+    if (is_idle(z)) continue;
     const int ld = matrix_ld(n);
     CpGroupMember& m = mem[z];
     double* band = nullptr;
-    if (!bands) {
+    if (denses) {
+      double* q_dev = nullptr;
+      SC_TRY(device_nan((size_t)n * ld, &q_dev));
+      SC_TRY(h2d_matrix(h, denses[z], n, n, q_dev, ld));  // (same stream: after the fill)
+      m.q = q_dev;
+    } else if (!bands) {
       double* packed_dev = nullptr;
       const int k = counts[z];
       SC_TRY(device_nan((size_t)2 * k, &packed_dev));
@@ -647,4 +741,89 @@ extern "C" int sc_stage_constraint_pairs_group(sc_handle h, const sc_config* cfg
     return fail(h, SC_ERR_INVALID, "a constraint group holds 1 .. 16 members");
   return stage_constraint_group(h, cfg, count, ns, affinities, nullptr, rows, cols, vals, counts,
                                 outs);
+}
+
+// the same with each member's constraint as a dense symmetric (ns[z], ns[z]) host matrix
+extern "C" int sc_stage_constraint_dense_group(sc_handle h, const sc_config* cfg, int count,
+                                               const int32_t* ns,
+                                               const double* const* affinities,
+                                               const double* const* constraints,
+                                               double* const* outs) {
+  if (!h) return SC_ERR_INVALID;
+  if (!constraints) return fail(h, SC_ERR_INVALID, "a constraint group holds 1 .. 16 members");
+  return stage_constraint_group(h, cfg, count, ns, affinities, nullptr, nullptr, nullptr, nullptr,
+                                nullptr, outs, constraints);
+}
+
+// ONE launch_gemm_nt_pair_group launch on host operands (tests): member z computes outs[z] =
+// As[z] Bs[z]^T (+ addends[z]) for (ns[z], ns[z]) row-major matrices; Bs[z] == NULL: B = A.  The
+// operands and the result live in matrices of the arena's row pitch whose every other element is a
+// quiet NaN, and outs[z] receives all ns[z] x matrix_ld(ns[z]) elements of the result's buffer,
+// padding columns included.  full = 0: the symmetric form (upper-triangle tiles and the mirror,
+// for commuting symmetric operands); full != 0: every tile from its own operands.
+extern "C" int sc_stage_gemm_pair_group(sc_handle h, int count, const int32_t* ns,
+                                        const double* const* As, const double* const* Bs,
+                                        const double* const* addends, double* const* outs,
+                                        int epilogue, int full) {
+  if (!h) return SC_ERR_INVALID;
+  if (count < 1 || count > kGroupMax || !ns || !As || !outs)
+    return fail(h, SC_ERR_INVALID, "a product group holds 1 .. 16 members");
+  if (epilogue != kEpiNone && epilogue != kEpiAdd)
+    return fail(h, SC_ERR_INVALID, "epilogue must be 0 (none) or the add epilogue");
+  if (epilogue == kEpiAdd && !addends) return fail(h, SC_ERR_INVALID, "addends is NULL");
+  for (int z = 0; z < count; ++z) {
+    if (ns[z] < 0) return fail(h, SC_ERR_INVALID, "n must not be negative (0: idle member)");
+    if (gemm_tile_dim(ns[z]) > kTilemapTableMax)
+      return fail(h, SC_ERR_UNSUPPORTED, "a member of the product group is larger than 8192");
+    if (ns[z] > 0 && (!As[z] || !outs[z] || (epilogue == kEpiAdd && !addends[z])))
+      return fail(h, SC_ERR_INVALID, "NULL operand of a live member");
+  }
+  SC_HIP(h, hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  struct Owned {  // freed however the function returns
+    std::vector<void*> p;
+    ~Owned() {
+      for (void* q : p) (void)hipFree(q);
+    }
+  } owned;
+  size_t largest = 16;
+  for (int z = 0; z < count; ++z) largest = std::max(largest, (size_t)ns[z] * matrix_ld(ns[z]));
+  const std::vector<double> nans(largest, std::numeric_limits<double>::quiet_NaN());
+  auto device_matrix = [&](const double* src, int n, int ld, double** out) -> int {
+    void* d = nullptr;
+    SC_HIP(h, hipMalloc(&d, (size_t)n * ld * sizeof(double)));
+    owned.p.push_back(d);
+    SC_HIP(h, hipMemcpyAsync(d, nans.data(), (size_t)n * ld * sizeof(double),
+                             hipMemcpyHostToDevice, s));
+    *out = reinterpret_cast<double*>(d);
+    if (src) SC_TRY(h2d_matrix(h, src, n, n, *out, ld));  // (same stream: after the fill)
+    return SC_OK;
+  };
+  GemmPairItem gm[kGroupMax];
+  for (int z = 0; z < count; ++z) {
+    const int n = ns[z];
+    if (n == 0) continue;
+    const int ld = matrix_ld(n);
+    double *a = nullptr, *b = nullptr, *add = nullptr, *c = nullptr;
+    SC_TRY(device_matrix(As[z], n, ld, &a));
+    if (Bs && Bs[z]) SC_TRY(device_matrix(Bs[z], n, ld, &b));
+    if (epilogue == kEpiAdd) SC_TRY(device_matrix(addends[z], n, ld, &add));
+    SC_TRY(device_matrix(nullptr, n, ld, &c));
+    SC_TRY(ensure_tilemap(h, n));
+    gm[z].A = a;
+    gm[z].B = b;
+    gm[z].lda = gm[z].ldb = gm[z].ldc = ld;
+    gm[z].C = c;
+    gm[z].n = n;
+    gm[z].tilemap = h->tilemap_cur;
+    gm[z].addend = add;
+  }
+  SC_HIP(h, hipStreamSynchronize(s));  // (`nans` is pageable)
+  launch_gemm_nt_pair_group(s, gm, count, epilogue, full != 0);
+  SC_TRY(check_last(h, "grouped product launch"));
+  for (int z = 0; z < count; ++z)
+    if (ns[z] > 0)
+      SC_TRY(d2h_matrix(h, gm[z].C, gm[z].ldc, ns[z], gm[z].ldc, outs[z]));
+  SC_HIP(h, hipStreamSynchronize(s));
+  return SC_OK;
 }

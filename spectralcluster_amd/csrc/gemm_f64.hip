@@ -879,6 +879,15 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_pg(const GemmPairGroup grp, 
                                                0x7fffffff, 1, nullptr, nullptr, nullptr,
                                                xcd_chunk, stats, nullptr, 0, 0, &grp);
 }
+// ... and for operands that are not symmetric (T Q^T of a dense constraint): first[] counts all
+// nt x nt tiles of a member, each computed from its own operands; no tilemap, no mirror write
+template <int EPI>
+__global__ __launch_bounds__(256, 2) void k_gemm_nt_pgf(const GemmPairGroup grp, int xcd_chunk) {
+  GemmStats stats{nullptr, nullptr, 0, nullptr};
+  gemm_nt_body<EPI, false, true, GemmPairGroup>(nullptr, 0, nullptr, 0, nullptr, 0, 0, 0, 0, 0, 0,
+                                                0x7fffffff, 1, nullptr, nullptr, nullptr,
+                                                xcd_chunk, stats, nullptr, 0, 0, &grp);
+}
 
 // rowmax / rowsum of every member from its per-tile partials (k_gemm_stats_reduce, grouped)
 struct StatsReduceItem {
@@ -1219,7 +1228,10 @@ void launch_gemm_nt_group(hipStream_t s, const GemmGroupItem* items, int count, 
 // the upper-triangle tiles of all members, each with its whole K = n, the mirror tile written
 // transposed -- what launch_gemm_nt(symmetric) computes for one member, without the split over K
 // a single short product takes.  items[z].n = 0: idle member.
-void launch_gemm_nt_pair_group(hipStream_t s, const GemmPairItem* items, int count, int epilogue) {
+// `full`: operands of any kind -- all nt x nt tiles of every member, what
+// launch_gemm_nt(symmetric = false) computes for one member (again with whole K per tile).
+void launch_gemm_nt_pair_group(hipStream_t s, const GemmPairItem* items, int count, int epilogue,
+                               bool full) {
   GemmPairGroup grp;
   memset(&grp, 0, sizeof(grp));
   int total = 0;
@@ -1229,14 +1241,22 @@ void launch_gemm_nt_pair_group(hipStream_t s, const GemmPairItem* items, int cou
     const GemmPairItem& it = items[z];
     const int nt = (it.n + BM - 1) / BM;
     const bool self = it.B == nullptr;
-    grp.m[z] = GemmPairMember{it.A, self ? it.A : it.B, it.addend, it.C, it.tilemap,
+    grp.m[z] = GemmPairMember{it.A, self ? it.A : it.B, it.addend, it.C,
+                              full ? nullptr : it.tilemap,
                               it.lda, self ? it.lda : it.ldb, it.ldc, it.n, nt};
-    total += nt * (nt + 1) / 2;
+    total += full ? nt * nt : nt * (nt + 1) / 2;
   }
   grp.first[kGroupMax] = total;
   if (total == 0) return;
   const int xcd_chunk = (total + 7) / 8;
   const int grid = 8 * xcd_chunk;
+  if (full) {
+    if (epilogue == kEpiAdd)
+      hipLaunchKernelGGL((k_gemm_nt_pgf<kEpiAdd>), dim3(grid), dim3(256), 0, s, grp, xcd_chunk);
+    else
+      hipLaunchKernelGGL((k_gemm_nt_pgf<kEpiNone>), dim3(grid), dim3(256), 0, s, grp, xcd_chunk);
+    return;
+  }
   if (epilogue == kEpiAdd)
     hipLaunchKernelGGL((k_gemm_nt_pg<kEpiAdd>), dim3(grid), dim3(256), 0, s, grp, xcd_chunk);
   else

@@ -300,7 +300,7 @@ int validate_affinity_array(sc_handle h, const sc_array* a);
 // exact-symmetry flag into *flag (device memory); *sync as in ingest_rows_into
 int ingest_affinity_into(sc_handle h, const sc_array& a, double* dst, int ld, int* flag,
                          hipStream_t s, bool* sync);
-// up to 64 sources by one launch (member z: dsts[z] of pitch matrix_ld(n_z), flags[z]); `stage`
+// 64 sources per launch (member z: dsts[z] of pitch matrix_ld(n_z), flags[z]); `stage`
 // (affinity_group_stage_bytes) takes the host members at their own width, `table`
 // (count * affinity_group_table_bytes()) the descriptors; `host_flags` (may be null) receives the
 // flags in the same wait; returns with s synchronised
@@ -536,9 +536,14 @@ struct CpGroupMember {
   int pk = 0;
   const int32_t *prows = nullptr, *pcols = nullptr;
   const double* pvals = nullptr;
+  // q: the constraint is neither but a dense SYMMETRIC matrix on the device (n x ld, the arena's
+  // Cq); band and the entry fields are not read
+  const double* q = nullptr;
 };
 int constraint_propagation_group(sc_handle lead, hipStream_t s, const CpGroupMember* mem,
                                  int count, double alpha);
+// validate_affinity_array's rules for a dense constraint source (sc_set_constraint_array)
+int validate_constraint_array(sc_handle h, const sc_array* q);
 // sc_set_constraint_pairs' checks of a host entry list, and whether it is symmetric
 int validate_constraint_pairs(sc_handle h, const int32_t* rows, const int32_t* cols,
                               const double* vals, int count, int n, bool* symmetric);
@@ -549,7 +554,9 @@ std::vector<double> pack_constraint_pairs(const int32_t* rows, const int32_t* co
 int predict_batch_constrained_impl(sc_handle h, const sc_array* xs, const sc_constraint_desc* cons,
                                    const int* ns, int d, int count, const sc_config* cfg,
                                    int64_t* const* labels, sc_diag* diags, int group,
-                                   bool affinities = false);  // (xs are the callers' affinities)
+                                   bool affinities = false,  // (xs are the callers' affinities)
+                                   // per utterance, data != nullptr: its dense constraint source
+                                   const sc_array* dense = nullptr);
 
 // ---- the single-cluster test (callers_api.hip: the single call's; single_check.hip: a batch's)
 // the bodies of sc_affinity_stats / sc_affinity_gmm_bic on the affinity resident in h

@@ -510,7 +510,7 @@ int ingest_affinity_into(sc_handle h, const sc_array& a, double* dst, int ld, in
   return SC_OK;
 }
 
-// `count` (<= 64) sources by ONE launch: member z into dsts[z] (pitch matrix_ld(n_z)), its flag
+// `count` sources by ONE launch per 64 of them: member z into dsts[z] (pitch matrix_ld(n_z)), its flag
 // into flags[z] (device memory).  Host members are copied at their own width into `stage` (device
 // memory of affinity_group_stage_bytes bytes) first; `table` holds the descriptors (device memory,
 // count * affinity_group_table_bytes()).  The host side of the copies is waited for before return.
@@ -525,12 +525,10 @@ size_t affinity_group_stage_bytes(const sc_array* as, int count) {
 int ingest_affinity_group(sc_handle h, const sc_array* as, int count, double* const* dsts,
                           int* flags, void* stage, void* table, hipStream_t s, int* host_flags) {
   if (count <= 0) return SC_OK;
-  if (count > 64) return fail(h, SC_ERR_INVALID, "at most 64 affinities per grouped ingest");
   std::vector<AffIngestItem> items(count);
   std::vector<int> ones(count, 1);
   std::vector<std::vector<unsigned char>> packed(count);
   unsigned char* at = static_cast<unsigned char*>(stage);
-  unsigned blocks = 0;
   bool sync = false;
   for (int z = 0; z < count; ++z) {
     const sc_array& a = as[z];
@@ -546,13 +544,17 @@ int ingest_affinity_group(sc_handle h, const sc_array* as, int count, double* co
       items[z] = aff_item(a.dtype, a.data, a.row_stride, a.col_stride, n, dsts[z], matrix_ld(n),
                           flags + z);
     }
-    blocks = std::max(blocks, aff_blocks(n));
   }
   SC_HIP(h, hipMemcpyAsync(flags, ones.data(), count * sizeof(int), hipMemcpyHostToDevice, s));
   SC_HIP(h, hipMemcpyAsync(table, items.data(), count * sizeof(AffIngestItem),
                            hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_ingest_affinity_group, dim3(blocks, count), dim3(256), 0, s,
-                     static_cast<const AffIngestItem*>(table));
+  for (int z0 = 0; z0 < count; z0 += 64) {  // one launch per <= 64 sources, one wait for all
+    const int cnt = std::min(64, count - z0);
+    unsigned blocks = 0;
+    for (int z = z0; z < z0 + cnt; ++z) blocks = std::max(blocks, aff_blocks(items[z].n));
+    hipLaunchKernelGGL(k_ingest_affinity_group, dim3(blocks, cnt), dim3(256), 0, s,
+                       static_cast<const AffIngestItem*>(table) + z0);
+  }
   SC_TRY(check_last(h, "grouped affinity ingest launch"));
   if (host_flags)
     SC_HIP(h, hipMemcpyAsync(host_flags, flags, count * sizeof(int), hipMemcpyDeviceToHost, s));

@@ -120,7 +120,10 @@ struct GemmPairItem {
 };
 // epilogue: kEpiNone or kEpiAdd.  Upper-triangle tiles of all members in one launch, whole K per
 // tile, the mirror tile written transposed.
-void launch_gemm_nt_pair_group(hipStream_t s, const GemmPairItem* items, int count, int epilogue);
+// `full`: any A and B -- every tile (ti, tj) of every member from its own operands, row by row of
+// the tile grid, no mirror write; `tilemap` is not read.
+void launch_gemm_nt_pair_group(hipStream_t s, const GemmPairItem* items, int count, int epilogue,
+                               bool full = false);
 // patch-ordered (ti, tj) list of the upper triangle, for `tilemap` (symmetric launches)
 void gemm_build_sym_tilemap(int nt, std::vector<int2>* out);
 int gemm_tile_dim(int n);

@@ -42,6 +42,11 @@ RefinementOptions = refinement.RefinementOptions
 EigenGapType = utils.EigenGapType
 
 
+# the constraint forms that travel inside a library batch call
+_BATCH_CONSTRAINTS = (constraint_lib.ConstraintMatrix, constraint_lib.PairwiseConstraints,
+                      constraint_lib.DenseConstraints)
+
+
 class SpectralClusterer:
   """Spectral clustering of speaker embeddings on the GPU.
 
@@ -144,7 +149,8 @@ class SpectralClusterer:
     (spectral_clusterer.py:137-142, 259-264) it is used only when both
     `constraint_options` and the matrix are given.  A `ConstraintMatrix` goes up as its band
     of n - 1 values (`sc_set_constraint_band`), a `PairwiseConstraints` as its directed entries
-    (`sc_set_constraint_pairs`), anything else as a dense (n, n) array."""
+    (`sc_set_constraint_pairs`), a `DenseConstraints` is read where it is
+    (`sc_set_constraint_array`), anything else goes up as a dense (n, n) float64 host array."""
     if self.constraint_options is None or constraint_matrix is None:
       handle.check(handle.lib.sc_clear_constraint(handle.raw))
       return False
@@ -156,6 +162,18 @@ class SpectralClusterer:
       handle.check(handle.lib.sc_set_constraint_pairs(
           handle.raw, _lib.as_int32_p(rows), _lib.as_int32_p(cols), _lib.as_double_p(vals),
           len(vals), n))
+      return True
+    if isinstance(constraint_matrix, constraint_lib.DenseConstraints):
+      self.constraint_options.constraint_operator.check_input(
+          np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)),
+          constraint_matrix)
+      with _lib.use_device(self.device):
+        source = constraint_matrix.describe(self._handle)
+        try:
+          handle.check(handle.lib.sc_set_constraint_array(
+              handle.raw, ctypes.byref(source.array)), TypeError)
+        finally:
+          source.release()
       return True
     if isinstance(constraint_matrix, constraint_lib.ConstraintMatrix):
       self.constraint_options.constraint_operator.check_input(
@@ -407,16 +425,7 @@ class SpectralClusterer:
   def _check_affinity_input(self, affinity, what: str = "affinity") -> int:
     """The ValueErrors of predict_affinity that need no device: a matrix that is not 2-D or not
     square, and the options that read embeddings.  Returns n."""
-    shape = np.shape(affinity) if isinstance(affinity, np.ndarray) else getattr(
-        affinity, "shape", None)
-    if shape is None:
-      raise TypeError("%s must be a numpy array or support __dlpack__" % what)
-    shape = tuple(int(s) for s in shape)
-    if len(shape) != 2:
-      raise ValueError("%s must be 2-dimensional, got shape %s" % (what, shape))
-    if shape[0] != shape[1]:
-      raise ValueError("%s must be a square matrix, got shape %s" % (what, shape))
-    n = shape[0]
+    n = constraint_lib.check_square_input(affinity, what)
     if n < self.fallback_options.spectral_min_embeddings:
       raise ValueError(
           "fallback_options.spectral_min_embeddings = %d is above n = %d: the fallback clusterer "
@@ -488,7 +497,8 @@ class SpectralClusterer:
     `_library_batch_covers()` accepts but for its `affinity_function` (no AutoTune, `min_clusters`
     not 1, the default k-means function), the metric is on the device (cosine when constraints
     travel), `group` is not 1 and every constraint is a `ConstraintMatrix`, a
-    `PairwiseConstraints` or None.  It takes `predict_batch`'s routes -- n <= 128 in Jacobi waves
+    `PairwiseConstraints`, a `DenseConstraints` (then `sc_predict_batch_constraint_arrays`) or
+    None.  It takes `predict_batch`'s routes -- n <= 128 in Jacobi waves
     (route 2), 128 < n < 4096 in lockstep groups of up to `group` (route 1), n >= 4096 and members
     that leave their route as single calls inside the call (route 0) -- with one grouped ingest
     launch per group or wave and the member-by-member refinement front; results agree with
@@ -496,7 +506,7 @@ class SpectralClusterer:
     decision is a near tie, eigenvalues within 1e-10 relative on route 2 and 1e-6 on route 1),
     and the same list gives the same results.  With a device tensor in the list the library
     synchronises its stream once at entry; the tensors may be overwritten or freed when the call
-    has returned.  Otherwise -- AutoTune, `min_clusters=1`, a user k-means function, a dense
+    has returned.  Otherwise -- AutoTune, `min_clusters=1`, a user k-means function, a raw dense
     ndarray constraint, `group=1` -- the matrices run one after the other through
     predict_affinity (routes all 0).  `last_batch_routes` / `last_batch_diags` are filled as in
     predict_batch."""
@@ -510,7 +520,7 @@ class SpectralClusterer:
     for i, (a, cm) in enumerate(zip(affinities, constraint_matrices)):
       n = self._check_affinity_input(a, "affinity %d" % i)
       if self.constraint_options is not None and isinstance(
-          cm, (constraint_lib.ConstraintMatrix, constraint_lib.PairwiseConstraints)):
+          cm, _BATCH_CONSTRAINTS):
         # (predict()'s check and message: _set_constraint)
         self.constraint_options.constraint_operator.check_input(
             np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)), cm)
@@ -524,9 +534,7 @@ class SpectralClusterer:
       metric_ok = False
     if (count and metric_ok and self._library_batch_covers(affinity_input=True) and
         (group is None or int(group) > 1) and
-        all(c is None or isinstance(c, (constraint_lib.ConstraintMatrix,
-                                        constraint_lib.PairwiseConstraints))
-            for c in constraint_matrices)):
+        all(c is None or isinstance(c, _BATCH_CONSTRAINTS) for c in constraint_matrices)):
       return self._affinity_library_batch(affinities, constraint_matrices if constrained else None,
                                           16 if group is None else int(group))
     labels, diags = [], []
@@ -537,22 +545,42 @@ class SpectralClusterer:
     self.last_batch_diags = diags
     return labels
 
+  def _describe_dense(self, constraint_matrices: typing.Sequence,
+                      sources: typing.List[_dlpack.Source]):
+    """The `dense` list of `sc_predict_batch_constraint_arrays` -- one `sc_array` per utterance,
+    `data` NULL where its constraint is no `DenseConstraints` -- or None when the batch holds
+    none.  The described matrices are appended to `sources`, a list of the caller's that holds
+    nothing else: it releases them when the library call has returned."""
+    if not any(isinstance(c, constraint_lib.DenseConstraints) for c in constraint_matrices):
+      return None
+    dense = (_lib.ScArray * len(constraint_matrices))()
+    with _lib.use_device(self.device):
+      for i, cm in enumerate(constraint_matrices):
+        if isinstance(cm, constraint_lib.DenseConstraints):
+          src = cm.describe(self._handle)
+          sources.append(src)
+          dense[i] = src.array
+    return dense
+
   def _affinity_library_batch(self, affinities: typing.Sequence,
                               constraint_matrices: typing.Optional[typing.Sequence],
                               group: int) -> typing.List[np.ndarray]:
     """ONE `sc_predict_batch_affinities` call; the checks of predict_affinity_batch passed."""
     count = len(affinities)
-    sources = []
+    sources, dense_sources = [], []
     try:
       with _lib.use_device(self.device):
         for a in affinities:
           sources.append(_dlpack.describe(a, self._handle, strided=True))
       handle = self._handle()
       handle.check(handle.lib.sc_clear_constraint(handle.raw))
-      cons, keep = None, []
+      cons, keep, dense = None, [], None
       if constraint_matrices is not None:
         cons = (_lib.ScConstraintDesc * count)()
+        dense = self._describe_dense(constraint_matrices, dense_sources)
         for desc, src, cm in zip(cons, sources, constraint_matrices):
+          if isinstance(cm, constraint_lib.DenseConstraints):
+            continue  # (kind 0: its matrix travels in `dense`)
           if isinstance(cm, constraint_lib.PairwiseConstraints):
             rows, cols, vals = cm.entries()
             keep.append((rows, cols, vals))
@@ -568,11 +596,16 @@ class SpectralClusterer:
       labels = [np.empty(src.shape[0], dtype=np.int64) for src in sources]
       lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
       diags = (_lib.ScDiag * count)()
-      handle.check(handle.lib.sc_predict_batch_affinities(
-          handle.raw, (_lib.ScArray * count)(*[src.array for src in sources]), cons, count,
-          self.build_config(), lp, diags, int(group)), TypeError)
+      if dense is not None:
+        handle.check(handle.lib.sc_predict_batch_constraint_arrays(
+            handle.raw, (_lib.ScArray * count)(*[src.array for src in sources]), cons, dense,
+            count, self.build_config(), lp, diags, int(group), 1), TypeError)
+      else:
+        handle.check(handle.lib.sc_predict_batch_affinities(
+            handle.raw, (_lib.ScArray * count)(*[src.array for src in sources]), cons, count,
+            self.build_config(), lp, diags, int(group)), TypeError)
     finally:
-      for src in sources:
+      for src in sources + dense_sources:
         src.release()
     self._batch_report(handle, diags, count)
     return labels
@@ -638,7 +671,12 @@ class SpectralClusterer:
     run once for the band members and once for the pair members of a group; a list of more
     entries than its utterance has rows runs that utterance as a single call (route 0), and one
     whose n is not its utterance's raises predict()'s ValueError before anything is launched.
-    Anything else -- a dense ndarray among the entries, AutoTune (the Turn-to-Diarize
+    `DenseConstraints` entries travel too (`sc_predict_batch_constraint_arrays`): their matrices
+    are read where they are, widened into the member arenas by one grouped launch per 64 of a
+    group or wave, and take the dense arithmetic -- inside the group's chain for a symmetric
+    matrix on a symmetric affinity, the member's own operator otherwise; one whose n is not its
+    utterance's raises the same ValueError before anything is launched.
+    Anything else -- a raw dense ndarray among the entries, AutoTune (the Turn-to-Diarize
     preset), group=1, `streams` -- runs as per-utterance `predict(u, c)` calls (routes all 0).
 
     `autotune_from_entry_state` (a clusterer without AutoTune ignores it).  `AutoTune.tune`
@@ -768,8 +806,7 @@ class SpectralClusterer:
           cosine = False
         if not (library_batch and cosine and streams is None and
                 (group is None or int(group) > 1) and
-                all(c is None or isinstance(c, (constraint_lib.ConstraintMatrix,
-                                                constraint_lib.PairwiseConstraints))
+                all(c is None or isinstance(c, _BATCH_CONSTRAINTS)
                     for c in constraint_matrices)):
           self.last_batch_routes = [_lib.BATCH_ROUTE_SINGLE] * len(utterances)
           return [self.predict(u, c) for u, c in zip(utterances, constraint_matrices)]
@@ -794,7 +831,7 @@ class SpectralClusterer:
     for u in utterances:
       if isinstance(u, np.ndarray) and u.ndim != 2:
         raise ValueError("all utterances must be (n_i, d) with the same d")
-    sources = []
+    sources, dense_sources = [], []
     try:
       with _lib.use_device(self.device):
         for u in utterances:
@@ -813,12 +850,18 @@ class SpectralClusterer:
           # (predict()'s check and message: _set_constraint)
           self.constraint_options.constraint_operator.check_input(
               np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)), cm)
+          if isinstance(cm, constraint_lib.DenseConstraints):
+            bands.append(None)  # (its matrix travels in `dense`)
+            continue
           if isinstance(cm, constraint_lib.PairwiseConstraints):
             bands.append(cm.entries())  # (rows, cols, vals)
             continue
           band = np.zeros(max(n - 1, 1), dtype=np.float64)  # (n = 1: no values, a valid pointer)
           band[:n - 1] = cm.band()
           bands.append(band)
+      dense = None  # the sc_array of every DenseConstraints of the batch, when there is one
+      if banded is not None:
+        dense = self._describe_dense(banded, dense_sources)
       labels = [np.empty(src.shape[0], dtype=np.int64) for src in sources]
       handle = self._handle()
       handle.check(handle.lib.sc_clear_constraint(handle.raw))  # a batch carries none
@@ -832,8 +875,8 @@ class SpectralClusterer:
             handle.raw, (_lib.ScArray * count)(*[src.array for src in sources]), count,
             self.build_config(), ctypes.byref(single_check), lp, diags, int(group), single),
             TypeError)
-      elif banded is not None and any(isinstance(b, tuple) for b in bands):
-        # entry lists among the constraints: one descriptor per utterance
+      elif banded is not None and (dense is not None or any(isinstance(b, tuple) for b in bands)):
+        # entry lists or dense matrices among the constraints: one descriptor per utterance
         arrays = (_lib.ScArray * count)(*[src.array for src in sources])
         cons = (_lib.ScConstraintDesc * count)()
         for desc, b in zip(cons, bands):
@@ -843,8 +886,14 @@ class SpectralClusterer:
             desc.vals = _lib.as_double_p(b[2])
           elif b is not None:
             desc.kind, desc.band = 2, _lib.as_double_p(b)
-        handle.check(handle.lib.sc_predict_batch_constraints(
-            handle.raw, arrays, cons, count, self.build_config(), lp, diags, int(group)), TypeError)
+        if dense is not None:
+          handle.check(handle.lib.sc_predict_batch_constraint_arrays(
+              handle.raw, arrays, cons, dense, count, self.build_config(), lp, diags, int(group),
+              0), TypeError)
+        else:
+          handle.check(handle.lib.sc_predict_batch_constraints(
+              handle.raw, arrays, cons, count, self.build_config(), lp, diags, int(group)),
+              TypeError)
       elif banded is not None:
         arrays = (_lib.ScArray * count)(*[src.array for src in sources])
         bp = (ctypes.POINTER(ctypes.c_double) * count)(
@@ -869,7 +918,7 @@ class SpectralClusterer:
         self._batch_arrays_call(handle, [src.array for src in sources], labels, diags,
                                 int(group), max(1, int(streams)))
     finally:
-      for src in sources:
+      for src in sources + dense_sources:
         src.release()
     self._batch_report(handle, diags, count)
     if single_check is not None:
@@ -900,7 +949,7 @@ class SpectralClusterer:
           "contains RowWiseThreshold")
     if self.constraint_options is not None:
       for u, cm in zip(utterances, constraint_matrices):
-        if isinstance(cm, constraint_lib.ConstraintMatrix):
+        if isinstance(cm, (constraint_lib.ConstraintMatrix, constraint_lib.DenseConstraints)):
           n = int(np.shape(u)[0])
           # (predict()'s check and message: _set_constraint)
           self.constraint_options.constraint_operator.check_input(
