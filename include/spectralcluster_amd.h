@@ -1226,6 +1226,39 @@ int sc_stage_kmeans(sc_handle h, const double* e, int n, int k, int max_iter,
 int sc_stage_kmeans_metric(sc_handle h, const double* e, int n, int k, int max_iter,
                            int metric, int64_t* labels, double* centroids_out,
                            int* iterations);
+/* sc_stage_kmeans (cosine) with what its kernels compute on the way, for tests.  form: which
+ * kernels run -- SC_KMEANS_FORM_AUTO as sc_stage_kmeans chooses, _CHAIN the chain of short
+ * kernels (SC_ERR_UNSUPPORTED when it does not take this (n, k): k > 32 or too many rows),
+ * _SINGLE the single-workgroup kernel (its large-k form above 64 clusters); the argument
+ * decides, not the process-wide switch.  *form_run: 1 chain, 2 single-workgroup, 3 its large-k
+ * form.  Every output but labels may be NULL.  All forms: seeds [k] (the k-means++ rows),
+ * *iterations, centroids [k * k], labels [n].  The chain alone (left untouched otherwise):
+ * col_means [k]; last_candidates / last_potentials [8]: the candidate rows of the last k-means++
+ * round and their potentials (the first 2 + int(log k) of each; k = 1: none);
+ * lloyd_centroids [k * k] after the sklearn Lloyd step; first_labels [n], the assignment of
+ * pass 0; mean_dist[p], p < min(*iterations, mean_dist_cap), the mean distance of pass p.  The
+ * chain is enqueued as pass 0, passes 1-3, then four passes at a time. */
+#define SC_KMEANS_FORM_AUTO 0
+#define SC_KMEANS_FORM_CHAIN 1
+#define SC_KMEANS_FORM_SINGLE 2
+int sc_stage_kmeans_trace(sc_handle h, const double* e, int n, int k, int max_iter, int form,
+                          int* form_run, double* col_means, int* seeds, int* last_candidates,
+                          double* last_potentials, double* lloyd_centroids,
+                          int64_t* first_labels, double* mean_dist, int mean_dist_cap,
+                          int* iterations, double* centroids, int64_t* labels);
+/* The grouped chain (one launch per phase for up to 16 independent problems, as the grouped
+ * batch runs it) with the same outputs per member.  es: the members' (ns[z], ks[z]) row-major
+ * inputs one after the other; ns[z] = 0 is an idle position.  Outputs are packed by position z:
+ * col_means and seeds at z * 32, last_candidates and last_potentials at z * 8, lloyd_centroids
+ * and centroids at z * 1024, mean_dist at z * mean_dist_cap, iterations at z; first_labels and
+ * labels hold the members' rows one after the other.  A member that met its stop rule goes idle
+ * for the later enqueues.  SC_ERR_UNSUPPORTED when the chain does not take a member. */
+int sc_stage_kmeans_trace_group(sc_handle h, const double* es, const int* ns, const int* ks,
+                                int count, int max_iter, double* col_means, int* seeds,
+                                int* last_candidates, double* last_potentials,
+                                double* lloyd_centroids, int64_t* first_labels,
+                                double* mean_dist, int mean_dist_cap, int* iterations,
+                                double* centroids, int64_t* labels);
 /* custom_distance_kmeans.run_kmeans (:13-52) / CustomKMeans.predict (:85-141) on an (n, dim)
  * input, dim independent of k.  init_centroids (k, dim) row-major, or NULL = sklearn k-means++
  * seeds + one Lloyd step.  centroids_out (k, dim) may be NULL: the centroids of the last

@@ -540,6 +540,16 @@ PROTOTYPES = {
     "sc_stage_kmeans_metric": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               _c_int64_p, _c_double_p, _c_int_p]),
+    "sc_stage_kmeans_trace": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_int, _c_int_p, _c_double_p,
+                                             _c_int_p, _c_int_p, _c_double_p, _c_double_p,
+                                             _c_int64_p, _c_double_p, ctypes.c_int, _c_int_p,
+                                             _c_double_p, _c_int64_p]),
+    "sc_stage_kmeans_trace_group": (ctypes.c_int, [_handle_t, _c_double_p, _c_int_p, _c_int_p,
+                                                   ctypes.c_int, ctypes.c_int, _c_double_p,
+                                                   _c_int_p, _c_int_p, _c_double_p, _c_double_p,
+                                                   _c_int64_p, _c_double_p, ctypes.c_int,
+                                                   _c_int_p, _c_double_p, _c_int64_p]),
     "sc_stage_kmeans_general": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_double, _c_double_p,

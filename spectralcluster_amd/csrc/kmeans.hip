@@ -125,7 +125,7 @@ __global__ __launch_bounds__(KT) void k_kmeans(
     double* __restrict__ enorm, const double* __restrict__ rnd,
     double* __restrict__ cent_out, int* __restrict__ labels32,
     long long* __restrict__ labels64, int* __restrict__ info, int metric,
-    double* __restrict__ gws, int* __restrict__ gwi) {
+    double* __restrict__ gws, int* __restrict__ gwi, int* __restrict__ seeds_out) {
   constexpr int KL = BIG ? 1 : kMaxVectors;  // LDS footprint of the per-cluster arrays
   __shared__ double sm[KW];
   __shared__ double s_mean[KL];
@@ -411,6 +411,8 @@ __global__ __launch_bounds__(KT) void k_kmeans(
   }
   for (int r = tid; r < n; r += KT) labels64[r] = labels32[r];
   for (int e = tid; e < k * k; e += KT) cent_out[e] = cent[e];
+  if (seeds_out)  // (the trace entry; production passes null)
+    for (int t = tid; t < k; t += KT) seeds_out[t] = seeds[t];
   if (tid == 0) {
     info[0] = it + 1;
     info[4] = (int)(wall_clock64() - t_start);
@@ -431,18 +433,19 @@ void launch_to_colmajor(hipStream_t s, const double* src, int n, int k, double* 
 
 void launch_kmeans(hipStream_t s, const double* ET, int lde, int n, int k,
                    int max_iter, int first_center, int trials,
-                   const KmeansWorkspace& ws, int metric) {
-  if (k > kMaxVectors) {
+                   const KmeansWorkspace& ws, int metric, int* seeds_out) {
+  if (k > kMaxVectors) {  // (this form's seeds are in ws.big_words already)
     hipLaunchKernelGGL(k_kmeans<true>, dim3(1), dim3(KT), 0, s, ET, lde, n, k, max_iter,
                        first_center, trials, ws.Xc, ws.xsq, ws.closest, ws.cand, ws.enorm, ws.rnd,
                        ws.centroids, ws.labels32, ws.labels64, ws.info, metric, ws.big,
-                       ws.big_words);
+                       ws.big_words, static_cast<int*>(nullptr));
     return;
   }
   hipLaunchKernelGGL(k_kmeans<false>, dim3(1), dim3(KT), 0, s, ET, lde, n, k, max_iter,
                      first_center, trials, ws.Xc, ws.xsq, ws.closest, ws.cand,
                      ws.enorm, ws.rnd, ws.centroids, ws.labels32, ws.labels64,
-                     ws.info, metric, static_cast<double*>(nullptr), static_cast<int*>(nullptr));
+                     ws.info, metric, static_cast<double*>(nullptr), static_cast<int*>(nullptr),
+                     seeds_out);
 }
 
 }  // namespace sc

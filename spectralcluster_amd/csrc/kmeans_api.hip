@@ -130,13 +130,9 @@ static int check_kmeans_request(sc_handle h, int n, int k, int max_iter, int met
 // ------------------------------------------------------------------------------
 // the (n, k) spectral embedding
 // ------------------------------------------------------------------------------
-static int kmeans_on_device(sc_handle h, const double* E, int lde, int n, int k, int max_iter,
-                            int64_t* labels, double* centroids_out, int* iterations,
-                            int metric = kKmeansCosine) {
-  // 8 trial slots up to kMaxVectors centres, 16 in the large-k form
-  SC_TRY(check_kmeans_request(h, n, k, max_iter, metric, k > kMaxVectors ? 16 : 8));
-  SC_TRY(ensure_kmeans(h, n, k));
-  // the RandomState(0) constants are functions of n and k: what the last call left is reused
+// the RandomState(0) constants are functions of n and k: what the last call left is reused
+// (h->kfirst, h->krnd_trials, and the doubles in h->krnd)
+static int kmeans_seed_state(sc_handle h, int n, int k) {
   if (h->kfirst_n != n || h->krnd_k != k) {
     double u_first;
     int trials;
@@ -155,6 +151,16 @@ static int kmeans_on_device(sc_handle h, const double* E, int lde, int n, int k,
       h->krnd_trials = trials;
     }
   }
+  return SC_OK;
+}
+
+static int kmeans_on_device(sc_handle h, const double* E, int lde, int n, int k, int max_iter,
+                            int64_t* labels, double* centroids_out, int* iterations,
+                            int metric = kKmeansCosine) {
+  // 8 trial slots up to kMaxVectors centres, 16 in the large-k form
+  SC_TRY(check_kmeans_request(h, n, k, max_iter, metric, k > kMaxVectors ? 16 : 8));
+  SC_TRY(ensure_kmeans(h, n, k));
+  SC_TRY(kmeans_seed_state(h, n, k));
   const int first = h->kfirst, trials = h->krnd_trials;
   const KmeansWorkspace ws = kmeans_workspace(h);
   int info[16] = {0};
@@ -321,4 +327,255 @@ extern "C" int sc_stage_kmeans_general(sc_handle h, const double* x, int n, int 
   SC_HIP(h, hipStreamSynchronize(s));
   if (iterations) *iterations = w[kKgenIters];
   return SC_OK;
+}
+
+// ------------------------------------------------------------------------------
+// stage/test entries that expose what the k-means kernels compute on the way
+// ------------------------------------------------------------------------------
+namespace {
+
+struct KmTraceOut {  // any pointer may be null
+  double* col_means = nullptr;      // [k]
+  int* seeds = nullptr;             // [k]
+  int* last_candidates = nullptr;   // [8], the first `trials` of the last k-means++ round
+  double* last_potentials = nullptr;  // [8]
+  double* lloyd_centroids = nullptr;  // [k * k]
+  int64_t* first_labels = nullptr;  // [n]
+  double* mean_dist = nullptr;      // [cap]
+  int cap = 0;
+  int* iterations = nullptr;
+  double* centroids = nullptr;      // [k * k]
+  int64_t* labels = nullptr;        // [n]
+};
+
+// synchronous device -> host copy of `count` T's (the stream has been drained)
+template <typename T>
+hipError_t fetch(T* dst, const void* src, size_t count) {
+  if (!dst || count == 0) return hipSuccess;
+  return hipMemcpy(dst, src, count * sizeof(T), hipMemcpyDeviceToHost);
+}
+
+// The chain on km[0..count) (n = 0: idle), enqueued by `launch(it_begin, it_count)`: pass 0
+// alone, so that the seeds, the Lloyd-step centroids and the first assignment can be read
+// before pass 1 overwrites them, then passes 1-3 and four at a time as production does.  A
+// member that met its stop rule is read out and goes idle (km[q].n = 0), as in the grouped batch.
+template <typename Launch>
+int drive_chain_trace(sc_handle h, hipStream_t s, KmGroupItem* km, int count, const KmTraceOut* outs,
+                      int max_iter, Launch launch) {
+  int running = 0;
+  for (int q = 0; q < count; ++q) running += km[q].n > 0;
+  std::vector<double> ring(kKmMeand);
+  for (int b = 0, c = 1; running > 0;) {
+    launch(b, c);
+    SC_TRY(check_last(h, "kmeans trace launch"));
+    SC_HIP(h, hipStreamSynchronize(s));
+    for (int q = 0; q < count; ++q) {
+      const int n = km[q].n, k = km[q].k;
+      if (n <= 0) continue;
+      const KmTraceOut& o = outs[q];
+      const KmChainView v = kmeans_chain_view(n, km[q].ws);
+      if (b == 0) {
+        SC_HIP(h, fetch(o.col_means, v.meang, k));
+        SC_HIP(h, fetch(o.seeds, v.seeds, k));
+        SC_HIP(h, fetch(o.lloyd_centroids, v.cent0, (size_t)k * k));
+        SC_HIP(h, fetch(o.first_labels, km[q].ws.labels64, n));
+        if (k > 1) {
+          SC_HIP(h, fetch(o.last_candidates, v.cand[(k - 1) & 1], 8));
+          if (o.last_potentials) {  // the partial sums in workgroup order, as km_best_trial adds
+            std::vector<double> pT((size_t)v.G * 8);
+            SC_HIP(h, fetch(pT.data(), v.pT, pT.size()));
+            for (int t = 0; t < 8; ++t) {
+              double acc = 0.0;
+              for (int g = 0; g < v.G; ++g) acc += pT[(size_t)g * 8 + t];
+              o.last_potentials[t] = t < km[q].trials ? acc : 0.0;
+            }
+          }
+        }
+      }
+      if (o.mean_dist) {  // passes whose stop rule this enqueue tested: b - 1 .. b + c - 2
+        SC_HIP(h, fetch(ring.data(), v.meand, kKmMeand));
+        for (int p = std::max(b, 1) - 1; p < b + c - 1; ++p)
+          if (p < o.cap) o.mean_dist[p] = ring[p & (kKmMeand - 1)];
+      }
+      int info[9] = {0};
+      SC_HIP(h, fetch(info, km[q].ws.info, 9));
+      if (info[8] == 0) continue;
+      if (o.iterations) *o.iterations = info[0];
+      SC_HIP(h, fetch(o.centroids, km[q].ws.centroids, (size_t)k * k));
+      SC_HIP(h, fetch(o.labels, km[q].ws.labels64, n));
+      km[q].n = 0;  // idle from here on
+      --running;
+    }
+    if (running > 0 && b > max_iter + 4)
+      return fail(h, SC_ERR_HIP, "k-means chain did not reach its stop rule");
+    if (b == 0) {
+      b = 1;
+      c = 3;
+    } else {
+      b += c;
+      c = 4;
+    }
+  }
+  return SC_OK;
+}
+
+struct DeviceSlabs {  // device allocations of one call, freed when it returns
+  std::vector<void*> p;
+  ~DeviceSlabs() {
+    for (void* q : p) hipFree(q);
+  }
+};
+
+}  // namespace
+
+extern "C" int sc_stage_kmeans_trace(sc_handle h, const double* e, int n, int k, int max_iter,
+                                     int form, int* form_run, double* col_means, int* seeds,
+                                     int* last_candidates, double* last_potentials,
+                                     double* lloyd_centroids, int64_t* first_labels,
+                                     double* mean_dist, int mean_dist_cap, int* iterations,
+                                     double* centroids, int64_t* labels) {
+  if (!h) return SC_ERR_INVALID;
+  if (!e || !labels || n <= 0 || k <= 0) return fail(h, SC_ERR_INVALID, "bad k-means input");
+  if (form < SC_KMEANS_FORM_AUTO || form > SC_KMEANS_FORM_SINGLE)
+    return fail(h, SC_ERR_INVALID, "k-means form: auto, chain or single");
+  SC_TRY(check_kmeans_request(h, n, k, max_iter, kKmeansCosine, k > kMaxVectors ? 16 : 8));
+  SC_HIP(h, hipSetDevice(h->device));
+  SC_TRY(ensure_kmeans(h, n, k));
+  SC_TRY(kmeans_seed_state(h, n, k));
+  const int first = h->kfirst, trials = h->krnd_trials, lde = round_up(n, 16);
+  const bool chain_ok = kmeans_chain_supported(n, k, trials);
+  if (form == SC_KMEANS_FORM_CHAIN && !chain_ok)
+    return fail(h, SC_ERR_UNSUPPORTED, "the k-means chain does not take this (n, k)");
+  const bool chain = form == SC_KMEANS_FORM_CHAIN ||
+                     (form == SC_KMEANS_FORM_AUTO && chain_ok && !sw::kmeans_single());
+  hipStream_t s = h->stream;
+  SC_HIP(h, hipMemcpyAsync(h->Eio.p, e, (size_t)n * k * sizeof(double), hipMemcpyHostToDevice, s));
+  const double* E = ptr<double>(h->Ek);
+  launch_to_colmajor(s, ptr<double>(h->Eio), n, k, ptr<double>(h->Ek), lde);
+  const KmeansWorkspace ws = kmeans_workspace(h);
+  if (chain) {
+    if (form_run) *form_run = 1;
+    KmGroupItem km;
+    km.ET = E;
+    km.lde = lde;
+    km.n = n;
+    km.k = k;
+    km.max_iter = max_iter;
+    km.first_center = first;
+    km.trials = trials;
+    km.ws = ws;
+    KmTraceOut o;
+    o.col_means = col_means;
+    o.seeds = seeds;
+    o.last_candidates = last_candidates;
+    o.last_potentials = last_potentials;
+    o.lloyd_centroids = lloyd_centroids;
+    o.first_labels = first_labels;
+    o.mean_dist = mean_dist;
+    o.cap = mean_dist_cap;
+    o.iterations = iterations;
+    o.centroids = centroids;
+    o.labels = labels;
+    return drive_chain_trace(h, s, &km, 1, &o, max_iter, [&](int b, int c) {
+      launch_kmeans_chain(s, E, lde, n, k, max_iter, first, trials, ws, b, c);
+    });
+  }
+  // the single-workgroup kernel: the small form writes its seeds through the optional pointer,
+  // the large-k form keeps them in its global workspace
+  const bool big = k > kMaxVectors;
+  if (form_run) *form_run = big ? 3 : 2;
+  if (!big) SC_TRY(grow(h, h->kbigw, (size_t)3 * kMaxVectors * sizeof(int)));
+  SC_HIP(h, hipMemsetAsync(h->kinfo.p, 0, 8 * sizeof(int), s));
+  launch_kmeans(s, E, lde, n, k, max_iter, first, trials, ws, kKmeansCosine,
+                big ? nullptr : ptr<int>(h->kbigw));
+  SC_TRY(check_last(h, "kmeans launch"));
+  SC_HIP(h, hipStreamSynchronize(s));
+  int info[6] = {0};
+  SC_HIP(h, fetch(info, h->kinfo.p, 6));
+  SC_HIP(h, fetch(seeds, h->kbigw.p, k));
+  SC_HIP(h, fetch(centroids, h->kcent.p, (size_t)k * k));
+  SC_HIP(h, fetch(labels, h->klab64.p, n));
+  if (iterations) *iterations = info[0];
+  return SC_OK;
+}
+
+extern "C" int sc_stage_kmeans_trace_group(sc_handle h, const double* es, const int* ns,
+                                           const int* ks, int count, int max_iter,
+                                           double* col_means, int* seeds, int* last_candidates,
+                                           double* last_potentials, double* lloyd_centroids,
+                                           int64_t* first_labels, double* mean_dist,
+                                           int mean_dist_cap, int* iterations, double* centroids,
+                                           int64_t* labels) {
+  if (!h) return SC_ERR_INVALID;
+  if (!es || !ns || !ks || !labels || count < 1 || count > kGroupMax)
+    return fail(h, SC_ERR_INVALID, "bad grouped k-means input");
+  SC_HIP(h, hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  KmGroupItem km[kGroupMax];
+  KmTraceOut outs[kGroupMax];
+  DeviceSlabs slabs;
+  std::vector<std::vector<double>> staged(count);  // alive until the first synchronisation
+  size_t e_off = 0, row_off = 0;
+  for (int z = 0; z < count; ++z) {
+    const int n = ns[z], k = ks[z];
+    if (n < 0 || (n > 0 && k < 1)) return fail(h, SC_ERR_INVALID, "bad grouped k-means input");
+    if (n == 0) continue;  // an idle position
+    SC_TRY(check_kmeans_request(h, n, k, max_iter, kKmeansCosine, 8));
+    double u_first;
+    int trials;
+    std::vector<double> rnd;
+    kmeans_seed_constants(k, &u_first, &trials, &rnd);
+    if (!kmeans_chain_supported(n, k, trials))
+      return fail(h, SC_ERR_UNSUPPORTED, "the k-means chain does not take this (n, k)");
+    // one slab per member: ET | rnd | closest | xsq | labels64 | centroids | chain | info
+    const size_t lde = round_up(n, 16), chain = kmeans_chain_workspace_doubles(n);
+    const size_t total = lde * k + rnd.size() + 3 * (size_t)n + 32 * 32 + chain + 8;
+    void* slab = nullptr;
+    SC_HIP(h, hipMalloc(&slab, total * sizeof(double)));
+    slabs.p.push_back(slab);
+    SC_HIP(h, hipMemsetAsync(slab, 0, total * sizeof(double), s));
+    std::vector<double>& st = staged[z];
+    st.assign(lde * k + rnd.size(), 0.0);
+    for (int r = 0; r < n; ++r)
+      for (int j = 0; j < k; ++j) st[(size_t)j * lde + r] = es[e_off + (size_t)r * k + j];
+    std::copy(rnd.begin(), rnd.end(), st.begin() + lde * k);
+    SC_HIP(h, hipMemcpyAsync(slab, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice,
+                             s));
+    double* p = static_cast<double*>(slab);
+    KmGroupItem& it = km[z];
+    it.ET = p;                 p += lde * k;
+    it.ws.rnd = p;             p += rnd.size();
+    it.ws.closest = p;         p += n;
+    it.ws.xsq = p;             p += n;
+    it.ws.labels64 = reinterpret_cast<long long*>(p);  p += n;
+    it.ws.centroids = p;       p += 32 * 32;
+    it.ws.chain = p;           p += chain;
+    it.ws.info = reinterpret_cast<int*>(p);
+    it.lde = (int)lde;
+    it.n = n;
+    it.k = k;
+    it.max_iter = max_iter;
+    it.first_center = sc_uniform_choice(n, u_first);
+    it.trials = trials;
+    KmTraceOut& o = outs[z];
+    if (col_means) o.col_means = col_means + (size_t)z * 32;
+    if (seeds) o.seeds = seeds + (size_t)z * 32;
+    if (last_candidates) o.last_candidates = last_candidates + (size_t)z * 8;
+    if (last_potentials) o.last_potentials = last_potentials + (size_t)z * 8;
+    if (lloyd_centroids) o.lloyd_centroids = lloyd_centroids + (size_t)z * 32 * 32;
+    if (first_labels) o.first_labels = first_labels + row_off;
+    if (mean_dist) o.mean_dist = mean_dist + (size_t)z * mean_dist_cap;
+    o.cap = mean_dist_cap;
+    if (iterations) o.iterations = iterations + z;
+    if (centroids) o.centroids = centroids + (size_t)z * 32 * 32;
+    o.labels = labels + row_off;
+    e_off += (size_t)n * k;
+    row_off += (size_t)n;
+  }
+  SC_HIP(h, hipStreamSynchronize(s));
+  const int rc = drive_chain_trace(h, s, km, count, outs, max_iter, [&](int b, int c) {
+    launch_kmeans_chain_group(s, km, count, b, c);
+  });
+  hipStreamSynchronize(s);  // nothing of the slabs is in use when they are freed
+  return rc;
 }

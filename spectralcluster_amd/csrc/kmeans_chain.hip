@@ -55,7 +55,7 @@ struct KmChain {
   double* pT;     // [G][8]
   double* pS[2];  // [G][k*k + 2k]
   double* pD[2];  // [G]
-  double* meand;  // [512]
+  double* meand;  // [kKmMeand]: ring of the passes' mean distances, pass p in slot p % kKmMeand
   double* cent[2];
   int* seeds;     // [64]
   int* cand[2];   // [8]
@@ -468,11 +468,11 @@ __device__ __forceinline__ void km_cosine_body(const KmChain& a, int it) {
   if (it > 0) {
     if (tid == 0) {
       const double mean_d = km_ordered_sum(a.pD[it & 1], 1, a.G) / (double)a.n;
-      const double prev = it >= 2 ? a.meand[it - 2] : 0.0;
+      const double prev = it >= 2 ? a.meand[(it - 2) & (kKmMeand - 1)] : 0.0;
       s_done = ((mean_d <= prev && mean_d >= (1.0 - 0.001) * prev) || it - 1 == a.max_iter)
                    ? 1 : 0;
       if (blockIdx.x == 0) {
-        a.meand[it - 1] = mean_d;
+        a.meand[(it - 1) & (kKmMeand - 1)] = mean_d;  // (max_iter may exceed the ring)
         if (s_done) {
           a.info[0] = it;  // iterations run = (it - 1) + 1
           a.info[8] = 1;
@@ -560,7 +560,7 @@ __global__ __launch_bounds__(kKmT) void km_cosine_g(const GroupOf<KmChain> g, in
 size_t kmeans_chain_workspace_doubles(int n) {
   const size_t G = (size_t)(n + kKmT - 1) / kKmT;
   // pm, ppot, pT, 2 x pS (k <= 32), 2 x pD, meand, 2 x cent, ints (seeds, cand, as doubles)
-  return G * 64 + 64 + G + G * 8 + 2 * G * (32 * 32 + 64) + 2 * G + 512 + 2 * 32 * 32 + 256;
+  return G * 64 + 64 + G + G * 8 + 2 * G * (32 * 32 + 64) + 2 * G + kKmMeand + 2 * 32 * 32 + 256;
 }
 
 bool kmeans_chain_supported(int n, int k, int trials) {
@@ -596,7 +596,7 @@ static KmChain km_args(const double* ET, int lde, int n, int k, int max_iter, in
   a.pS[1] = p;       p += G * (32 * 32 + 64);
   a.pD[0] = p;       p += G;
   a.pD[1] = p;       p += G;
-  a.meand = p;       p += 512;
+  a.meand = p;       p += kKmMeand;
   a.cent[0] = p;     p += 32 * 32;
   a.cent[1] = p;     p += 32 * 32;
   int* ip = reinterpret_cast<int*>(p);
@@ -605,6 +605,21 @@ static KmChain km_args(const double* ET, int lde, int n, int k, int max_iter, in
   a.cand[1] = ip + 72;
   a.info = ws.info;
   return a;
+}
+
+// where the chain keeps what the stage/test entries read back (sc_stage_kmeans_trace)
+KmChainView kmeans_chain_view(int n, const KmeansWorkspace& ws) {
+  const KmChain a = km_args(nullptr, 0, n, 1, 0, 0, 0, ws);
+  KmChainView v;
+  v.G = a.G;
+  v.meang = a.meang;
+  v.pT = a.pT;
+  v.meand = a.meand;
+  v.cent0 = a.cent[0];
+  v.seeds = a.seeds;
+  v.cand[0] = a.cand[0];
+  v.cand[1] = a.cand[1];
+  return v;
 }
 
 template <int KC>

@@ -912,6 +912,19 @@ size_t kmeans_big_workspace_doubles(int k);
 // k-means as a chain of short multi-workgroup kernels (kmeans_chain.hip), cosine metric
 size_t kmeans_chain_workspace_doubles(int n);
 bool kmeans_chain_supported(int n, int k, int trials);
+// slots of the chain's ring of per-pass mean distances (a power of two): pass p lives in slot
+// p % kKmMeand, the stop rule reads only the pass before
+constexpr int kKmMeand = 512;
+struct KmChainView {  // parts of ws.chain the trace entries read after a synchronisation
+  int G = 0;                 // workgroups = partial sums per quantity
+  const double* meang = nullptr;  // [k] column means
+  const double* pT = nullptr;     // [G][8] trial potentials of the last k-means++ round
+  const double* meand = nullptr;  // [kKmMeand] ring of mean distances
+  const double* cent0 = nullptr;  // [k * k] centroids of the even passes (pass 0: the Lloyd step)
+  const int* seeds = nullptr;     // [k]
+  const int* cand[2] = {nullptr, nullptr};  // [8] candidate rows of round c in cand[c & 1]
+};
+KmChainView kmeans_chain_view(int n, const KmeansWorkspace& ws);
 struct KmGroupItem {  // one member of a grouped chain launch; n = 0: idle
   const double* ET = nullptr;
   int lde = 0, n = 0, k = 0, max_iter = 0, first_center = 0, trials = 0;
@@ -938,7 +951,8 @@ enum {
 };
 void launch_kmeans(hipStream_t s, const double* ET, int lde, int n, int k,
                    int max_iter, int first_center, int trials,
-                   const KmeansWorkspace& ws, int metric = kKmeansCosine);
+                   const KmeansWorkspace& ws, int metric = kKmeansCosine,
+                   int* seeds_out = nullptr);  // k <= kMaxVectors: k ints, the k-means++ rows
 
 
 // k-means on an (n, dim) input of any width as grids of short kernels (kmeans_general.hip).
