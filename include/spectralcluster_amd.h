@@ -1267,6 +1267,51 @@ int sc_stage_kmeans_trace_group(sc_handle h, const double* es, const int* ns, co
 int sc_stage_kmeans_general(sc_handle h, const double* x, int n, int dim, int k, int max_iter,
                             int metric, double tol, const double* init_centroids,
                             int64_t* labels, double* centroids_out, int* iterations);
+/* Every form of the nearest-neighbour-chain linkage (sc_ahc, sc_batch_ahc, the stream pool,
+ * sc_batch_fallback_check) on the caller's COSINE matrices, for tests: each form runs its own
+ * 1 - clip(c) step and its linkage kernel through the launches production uses, on a descriptor
+ * table / pool slabs laid out by hand.  form:
+ *   _SINGLE         sc_ahc's distance kernel + chain kernel, one member after the other
+ *   _BATCH          sc_batch_ahc's distance kernel + chain kernel (a workgroup per member)
+ *   _BATCH_LDS      sc_batch_ahc's LDS kernel (a wavefront per member)
+ *   _POOL           the stream pool's distance kernel + chain kernel (position i of the launch
+ *                   works in slot count - 1 - i)
+ *   _POOL_LDS       the stream pool's LDS kernel
+ *   _CHAIN_VERDICT  sc_batch_fallback_check's distance kernel + chain kernel in its verdict form
+ *   _LDS_VERDICT    ... its LDS kernel in its verdict form
+ * method: SC_LINKAGE_*; the LDS forms take members of at most 128 rows, they and the verdict forms
+ * average linkage only.  ns [count]: rows of each member (a member of fewer than 2 rows is left
+ * alone); cosines: the members' (n_i, n_i) row-major matrices one after the other.  On the device
+ * every matrix has a pitch above n_i, and its padding columns and rows hold what a scan would take
+ * for the smallest distance -- cosine 1 (distance 0) for the LDS forms, which turn cosines into
+ * distances while they load them, and -1 for the others, whose distance kernel works on the
+ * n_i x n_i part alone and whose chain kernel would read the padding as it is: a kernel that
+ * looked beyond column n_i would pick one.  first: the table offset of the batch and LDS
+ * launches -- members before it are not worked on (forms _SINGLE and _POOL: 0).  bad (may be NULL; not for
+ * the pool forms): the members' `bad` words, nonzero = left alone.  threshold: of the verdict
+ * forms.  Outputs hold what the caller put there wherever a member was left alone.  Z (forms
+ * without a verdict): the members' raw merge lists one after the other, max(n_i - 1, 0) rows of
+ * (slot x < slot y, height, size) in chain order.  records (verdict forms): {height, verdict} per
+ * member.  labels (may be NULL; forms without a verdict): n_i labels per member, ahc_tree_cut of
+ * its Z for n_clusters > 0 or, n_clusters == 0, distance_threshold -- sc_ahc's host half.
+ * SC_ERR_HIP when a kernel wrote behind a member's cluster sizes or behind its chain (where
+ * sc_ahc keeps the `bad` word).  Every argument is checked before the first launch. */
+#define SC_LINKAGE_FORM_SINGLE 0
+#define SC_LINKAGE_FORM_BATCH 1
+#define SC_LINKAGE_FORM_BATCH_LDS 2
+#define SC_LINKAGE_FORM_POOL 3
+#define SC_LINKAGE_FORM_POOL_LDS 4
+#define SC_LINKAGE_FORM_CHAIN_VERDICT 5
+#define SC_LINKAGE_FORM_LDS_VERDICT 6
+int sc_stage_linkage(sc_handle h, int form, int method, int count, const int32_t* ns,
+                     const double* cosines, int first, double threshold, const int32_t* bad,
+                     double* Z, double* records, int64_t* labels, int n_clusters,
+                     double distance_threshold);
+/* The (n, n) cosine distances sc_ahc (route 0: row normalisation, the symmetric single-call
+ * product, 1 - clip) and sc_batch_ahc (route 1: the batched normalisation, the grouped product,
+ * the batched 1 - clip, on a wave of this one member) hand to their linkage kernels, for tests.
+ * x: (n, d), n >= 2. */
+int sc_stage_cosine_distances(sc_handle h, int route, const double* x, int n, int d, double* out);
 
 /* ---- multi-GPU: replicas of the path over the GPUs of one node ------------------------
  * The reference has no distributed layer (a batch is a Python `for` over predict(),

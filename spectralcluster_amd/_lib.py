@@ -554,6 +554,12 @@ PROTOTYPES = {
                                                ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_double, _c_double_p,
                                                _c_int64_p, _c_double_p, _c_int_p]),
+    "sc_stage_linkage": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        _c_int_p, _c_double_p, ctypes.c_int, ctypes.c_double,
+                                        _c_int_p, _c_double_p, _c_double_p, _c_int64_p,
+                                        ctypes.c_int, ctypes.c_double]),
+    "sc_stage_cosine_distances": (ctypes.c_int, [_handle_t, ctypes.c_int, _c_double_p,
+                                                 ctypes.c_int, ctypes.c_int, _c_double_p]),
     "sc_comm_available": (ctypes.c_int, []),
     "sc_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "sc_comm_init_rank": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.c_int,

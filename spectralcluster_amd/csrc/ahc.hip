@@ -7,7 +7,9 @@
 // neighbour-chain algorithm, a stable sort of the merges by height and a union-find
 // relabelling; sklearn then cuts the tree with a heap of node ids (_hc_cut).  Here:
 //   * distances: the fp64 MFMA GEMM of the affinity stage on the row-normalised embeddings,
-//     d_ij = 1 - clip(cos_ij) (k_cosine_distance);
+//     d_ij = 1 - clip(cos_ij) (k_cosine_distance); every tile of that product takes the whole K
+//     (no split-K tail), so equal rows give bit-equal distance columns, as scipy's pdist does --
+//     the tie rules below decide sklearn's label numbering on such inputs;
 //   * nearest-neighbour chain: ONE persistent workgroup (k_ahc_nn_chain).  The chain is
 //     inherently sequential (about 3 n steps); each step is a coalesced scan of one row of
 //     the n x n distance matrix (first index of the minimum, the previous chain element wins
@@ -31,14 +33,21 @@
 
 namespace sc {
 
+// d = 1 - clip(c): scipy clips the cosine to [-1, 1].  A row's distance to itself is 0, as in
+// scipy's squareform(pdist(.)): the product of a unit row with itself misses 1 by a few ulp
+// (2 at d = 24, 6.5 at d = 256 were measured), and although no scan or update reads the diagonal
+// (they skip i == x), D is the distance matrix only with the zero there.
+__device__ __forceinline__ double cosine_distance_value(double v, bool diagonal) {
+  v = v > 1.0 ? 1.0 : (v < -1.0 ? -1.0 : v);
+  return diagonal ? 0.0 : 1.0 - v;
+}
+
 __global__ __launch_bounds__(256) void k_cosine_distance(double* __restrict__ c, int n,
                                                          int ld) {
   const int row = blockIdx.y;
   const int col = blockIdx.x * 256 + threadIdx.x;
   if (col >= n) return;
-  double v = c[(size_t)row * ld + col];
-  v = v > 1.0 ? 1.0 : (v < -1.0 ? -1.0 : v);  // scipy clips the cosine to [-1, 1]
-  c[(size_t)row * ld + col] = 1.0 - v;
+  c[(size_t)row * ld + col] = cosine_distance_value(c[(size_t)row * ld + col], row == col);
 }
 
 constexpr int kAhcThreads = 1024;
@@ -207,9 +216,7 @@ __global__ __launch_bounds__(256) void k_batch_cosine_distance(
   double* __restrict__ c = it.D;
   for (int row = blockIdx.x; row < n; row += gridDim.x)
     for (int col = threadIdx.x; col < n; col += 256) {
-      double v = c[(size_t)row * ld + col];
-      v = v > 1.0 ? 1.0 : (v < -1.0 ? -1.0 : v);  // k_cosine_distance's expression
-      c[(size_t)row * ld + col] = 1.0 - v;
+      c[(size_t)row * ld + col] = cosine_distance_value(c[(size_t)row * ld + col], row == col);
     }
 }
 
@@ -244,9 +251,7 @@ __global__ __launch_bounds__(256) void k_pool_cosine_distance(const PoolSlabs p,
   const int col = blockIdx.x * 256 + threadIdx.x;
   if (row >= n || col >= n) return;
   double* c = p.D + (size_t)slots[blockIdx.z] * p.stride_d;
-  double v = c[(size_t)row * p.ldd + col];
-  v = v > 1.0 ? 1.0 : (v < -1.0 ? -1.0 : v);
-  c[(size_t)row * p.ldd + col] = 1.0 - v;
+  c[(size_t)row * p.ldd + col] = cosine_distance_value(c[(size_t)row * p.ldd + col], row == col);
 }
 
 // One persistent workgroup per session: sessions of different sizes share the launch, each
@@ -320,9 +325,7 @@ __device__ __forceinline__ void linkage_lds_body(const double* __restrict__ c, i
   {  // the GEMM's cosines -> distances (k_pool_cosine_distance's expression)
     for (int e = lane; e < n * n; e += 64) {
       const int i = e / n, j = e - i * n;
-      double v = c[(size_t)i * ldc + j];
-      v = v > 1.0 ? 1.0 : (v < -1.0 ? -1.0 : v);
-      D[i * pitch + j] = 1.0 - v;
+      D[i * pitch + j] = cosine_distance_value(c[(size_t)i * ldc + j], i == j);
     }
   }
   const int i0 = lane, i1 = lane + 64;  // the two columns of this lane

@@ -56,7 +56,8 @@ enum { kEpiNone = 0, kEpiAffinity = 1, kEpiAdd = 2 };
 // is written transposed, so C is exactly symmetric.  kEpiAdd adds `addend` (ld = ldc,
 // symmetric when `symmetric`; must not alias C).
 // `splitk_ws`: gemm_splitk_workspace_bytes() of scratch owned by the caller (per handle): the
-// split-K partials and the persistent plan's queue counters.
+// split-K partials and the persistent plan's queue counters.  nullptr: every tile takes the whole
+// K, so an entry's bits do not depend on which tile it falls into (sc_ahc's distances).
 // `rs` (optional): row statistics of C fused into the epilogue -- mode 1: rowmax / rowsum,
 // mode 2: max over j != i clamped at 0 (CropDiagonal's fill value) in rowmax.  The partial
 // arrays hold M x gemm_tile_dim(N) doubles each.
