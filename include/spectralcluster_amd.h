@@ -1267,6 +1267,29 @@ int sc_stage_kmeans_trace_group(sc_handle h, const double* es, const int* ns, co
 int sc_stage_kmeans_general(sc_handle h, const double* x, int n, int dim, int k, int max_iter,
                             int metric, double tol, const double* init_centroids,
                             int64_t* labels, double* centroids_out, int* iterations);
+/* sc_stage_kmeans_general on a described source: x is (n, dim) in host or device memory, fp64 /
+ * fp32 / fp16 / bf16, any non-negative element strides.  It is widened exactly on the device
+ * into the kernels' column-major layout (a device source is read in place on the handle's
+ * stream, a host source is copied at its own width first), so the results are bit for bit those
+ * of the same values passed as double*.  Compact host fp64 rows take sc_stage_kmeans_general's
+ * own copy.  init_centroids and the outputs are host fp64 as there.  SC_ERR_INVALID before any
+ * copy or launch for: an unknown dtype or location, a negative stride, NULL data, a device
+ * pointer that is not memory of the handle's device, rows * cols > 2^31 - 1.  The source is not
+ * modified and may be reused when the call returns. */
+int sc_stage_kmeans_general_array(sc_handle h, const sc_array* x, int k, int max_iter, int metric,
+                                  double tol, const double* init_centroids, int64_t* labels,
+                                  double* centroids_out, int* iterations);
+/* sc_stage_kmeans_metric on a described source: e is the (n, k) spectral embedding, k = e->cols;
+ * sources, checks and results as sc_stage_kmeans_general_array. */
+int sc_stage_kmeans_metric_array(sc_handle h, const sc_array* e, int max_iter, int metric,
+                                 int64_t* labels, double* centroids_out, int* iterations);
+/* the k-means ingest alone (a test entry, the twin of sc_stage_ingest): out receives the
+ * round_up(rows, 16) x cols doubles the k-means kernels are handed for x, column-major
+ * (out[j * ld + r], ld = round_up(rows, 16)), written over memory filled with NaNs: rows
+ * 0 .. rows - 1 of every column are the widened values, the rest of the column is zero.
+ * (Compact host fp64 rows go through the same kernels here; the k-means entries keep their
+ * copy + transposition for them, which leaves the rest of a column unwritten.) */
+int sc_stage_ingest_columns(sc_handle h, const sc_array* x, double* out);
 /* Every form of the nearest-neighbour-chain linkage (sc_ahc, sc_batch_ahc, the stream pool,
  * sc_batch_fallback_check) on the caller's COSINE matrices, for tests: each form runs its own
  * 1 - clip(c) step and its linkage kernel through the launches production uses, on a descriptor

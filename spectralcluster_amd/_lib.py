@@ -554,6 +554,14 @@ PROTOTYPES = {
                                                ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_double, _c_double_p,
                                                _c_int64_p, _c_double_p, _c_int_p]),
+    "sc_stage_kmeans_general_array": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),
+                                                     ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.c_double, _c_double_p, _c_int64_p,
+                                                     _c_double_p, _c_int_p]),
+    "sc_stage_kmeans_metric_array": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),
+                                                    ctypes.c_int, ctypes.c_int, _c_int64_p,
+                                                    _c_double_p, _c_int_p]),
+    "sc_stage_ingest_columns": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray), _c_double_p]),
     "sc_stage_linkage": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         _c_int_p, _c_double_p, ctypes.c_int, ctypes.c_double,
                                         _c_int_p, _c_double_p, _c_double_p, _c_int64_p,

@@ -293,6 +293,14 @@ int ingest_embeddings(sc_handle h, const sc_array& a, bool sync, hipStream_t str
 // staging rows): *sync is set when the caller must wait for s before the source may go
 int ingest_rows_into(sc_handle h, const sc_array& a, double* X, int ldx, hipStream_t s,
                      bool* sync);
+// ---- a k-means input as a described source (ingest.hip, kmeans_api.hip) -------------------
+// validate_array and rows * cols <= 2^31 - 1
+int validate_kmeans_array(sc_handle h, const sc_array* a);
+// compact host fp64 rows: what the double* k-means entries take (one copy + k_to_colmajor)
+bool array_is_compact_host_f64(const sc_array& a);
+// the (n, dim) values, widened, into X[j * ld + r], ld = round_up(n, 16) (rows n .. ld - 1 of
+// every column zeroed) on stream s; the caller waits for s before the source may go
+int ingest_columns_into(sc_handle h, const sc_array& a, double* X, int ld, hipStream_t s);
 // ---- a caller's affinity as a described source (ingest.hip, affinity_api.hip) -------------
 // validate_array and rows == cols
 int validate_affinity_array(sc_handle h, const sc_array* a);

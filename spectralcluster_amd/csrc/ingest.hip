@@ -6,6 +6,9 @@
 //                        or a quarter of the fp64 bytes over the link), then the same kernel.
 // All arithmetic after this stays fp64, and widening is exact for every bit pattern, so results
 // are bit for bit those of the values converted to double on the host.
+// An (n, n) affinity or constraint matrix (k_ingest_affinity) and the (n, dim) input of the
+// k-means entries (k_ingest_columns: the column-major layout of the k-means kernels) come in the
+// same way, through the same widening and the same LDS tile.
 #include <climits>
 #include <cstddef>
 
@@ -133,12 +136,15 @@ __device__ __forceinline__ int aff_at(int r, int c) {
   return r * kAffTile + (c ^ ((r & 31) << 1));
 }
 
+// (the source has nr rows and nc columns: an affinity passes n twice, the k-means ingest the
+// transposed view of an (n, dim) input)
 template <typename T, int E, bool COLWALK>
 __device__ __forceinline__ void aff_load_tile(const T* __restrict__ src, long long rs,
-                                              long long cs, int n, int r0, int c0,
+                                              long long cs, int nr, int nc, int r0, int c0,
                                               double* __restrict__ lds) {
   // an item is E elements along the walked direction: of a row, or (COLWALK) of a column
   constexpr int kPerLine = kAffTile / E;
+  const int nline = COLWALK ? nc : nr, nat = COLWALK ? nr : nc;
 #pragma unroll
   for (int it = 0; it < kAffTile * kAffTile / E / 256; ++it) {
     const int item = it * 256 + (int)threadIdx.x;
@@ -150,13 +156,13 @@ __device__ __forceinline__ void aff_load_tile(const T* __restrict__ src, long lo
       const long long base = COLWALK ? (long long)gc * cs + gr : (long long)gr * rs + gc;
       const int gline = COLWALK ? gc : gr, gat = COLWALK ? gr : gc;
       double w[E];
-      if (gline < n && gat + E <= n) {
+      if (gline < nline && gat + E <= nat) {
         const Chunk<T> ch = *reinterpret_cast<const Chunk<T>*>(src + base);
 #pragma unroll
         for (int e = 0; e < E; ++e) w[e] = widen(ch.v[e]);
       } else {
 #pragma unroll
-        for (int e = 0; e < E; ++e) w[e] = gline < n && gat + e < n ? widen(src[base + e]) : 0.0;
+        for (int e = 0; e < E; ++e) w[e] = gline < nline && gat + e < nat ? widen(src[base + e]) : 0.0;
       }
       if constexpr (COLWALK) {
 #pragma unroll
@@ -168,7 +174,7 @@ __device__ __forceinline__ void aff_load_tile(const T* __restrict__ src, long lo
       }
     } else {
       lds[aff_at(r, c)] =
-          gr < n && gc < n ? widen(src[(long long)gr * rs + (long long)gc * cs]) : 0.0;
+          gr < nr && gc < nc ? widen(src[(long long)gr * rs + (long long)gc * cs]) : 0.0;
     }
   }
 }
@@ -197,8 +203,8 @@ __device__ __forceinline__ void aff_ingest_tiles(const AffIngestItem& m, int ti,
   const T* src = static_cast<const T*>(m.src);
   const int n = m.n, ld = m.ld, r0 = ti * kAffTile, c0 = tj * kAffTile;
   const bool diag = ti == tj;
-  aff_load_tile<T, E, COLWALK>(src, m.row_stride, m.col_stride, n, r0, c0, sp);
-  if (!diag) aff_load_tile<T, E, COLWALK>(src, m.row_stride, m.col_stride, n, c0, r0, sq);
+  aff_load_tile<T, E, COLWALK>(src, m.row_stride, m.col_stride, n, n, r0, c0, sp);
+  if (!diag) aff_load_tile<T, E, COLWALK>(src, m.row_stride, m.col_stride, n, n, c0, r0, sq);
   __syncthreads();
   const double* mir = diag ? sp : sq;
   bool differs = false;
@@ -310,22 +316,102 @@ void pack_host_rows(const sc_array& a, std::vector<unsigned char>* tmp) {
 
 // Host rows at their own width into staging memory of a 16-byte pitch (device pointer `stage`),
 // gathered first where hipMemcpy2D cannot describe them.  *sync: `packed` is a local.
-int stage_host_affinity(sc_handle h, const sc_array& a, void* stage, size_t pitch, hipStream_t s,
-                        std::vector<unsigned char>* packed, bool* sync) {
+int stage_host_rows(sc_handle h, const sc_array& a, void* stage, size_t pitch, hipStream_t s,
+                    std::vector<unsigned char>* packed, bool* sync) {
   const int n = (int)a.rows;
-  const size_t eb = dtype_bytes(a.dtype);
+  const size_t eb = dtype_bytes(a.dtype), width = (size_t)a.cols * eb;
   const void* src = a.data;
   size_t spitch = (size_t)a.row_stride * eb;
   if (a.col_stride != 1 || (a.row_stride < a.cols && n > 1)) {
     pack_host_rows(a, packed);
     src = packed->data();
-    spitch = (size_t)n * eb;
+    spitch = width;
     *sync = true;
   }
-  if (n == 1) spitch = eb;
-  SC_HIP(h, hipMemcpy2DAsync(stage, pitch, src, spitch, (size_t)n * eb, n, hipMemcpyHostToDevice,
-                             s));
+  if (n == 1) spitch = width;
+  SC_HIP(h, hipMemcpy2DAsync(stage, pitch, src, spitch, width, n, hipMemcpyHostToDevice, s));
   return SC_OK;
+}
+
+// ---- an (n, dim) input where it is -> the k-means layout X[j * ld + r], fp64 -----------------
+// X has the shape of the source's transposed view ((dim, n), the two strides swapped) in rows of
+// pitch ld = round_up(n, 16).  Which way the source's memory runs decides the kernel:
+//   along its rows (col_stride 1, or the smaller stride)  k_ingest_columns: a workgroup takes a
+//     64 x 64 tile, loads it along the memory with the affinity ingest's column walk of the
+//     transposed view (E > 1: 16-byte loads -- col_stride 1, base and row pitch multiples of 16
+//     bytes; E = 1: scalar loads, adjacent lanes on adjacent columns), LDS does the transposition
+//     (aff_at's swizzle), and the stores run down the columns of X, 16 bytes each;
+//   along its columns (row_stride 1: it is column-major already; or the smaller stride)
+//     nothing is to be transposed: k_ingest_rows on the transposed view.
+// Either way every source byte is read once and every element of X is written once, rows
+// n .. ld - 1 of each column as zeros (no k-means kernel reads them; they are defined all the
+// same, as the embedding ingest defines its padding columns).
+template <typename T, int E>
+__global__ __launch_bounds__(256) void k_ingest_columns(const T* __restrict__ src,
+                                                        long long row_stride, long long col_stride,
+                                                        int n, int dim, double* __restrict__ X,
+                                                        int ld) {
+  __shared__ alignas(16) double tile[kAffTile * kAffTile];
+  const int tiles_r = (n + kAffTile - 1) / kAffTile;
+  const int r0 = (int)(blockIdx.x % tiles_r) * kAffTile, j0 = (int)(blockIdx.x / tiles_r) * kAffTile;
+  // tile[aff_at(j, r)] = source(r0 + r, j0 + j), zero outside the source
+  aff_load_tile<T, E, true>(src, col_stride, row_stride, dim, n, j0, r0, tile);
+  __syncthreads();
+#pragma unroll
+  for (int it = 0; it < kAffTile * kAffTile / 2 / 256; ++it) {
+    const int item = it * 256 + (int)threadIdx.x;
+    const int j = item / (kAffTile / 2), r = (item % (kAffTile / 2)) * 2;
+    // (r0 + r and ld are even: a pair lies inside the column or outside it)
+    if (j0 + j < dim && r0 + r < ld)
+      *reinterpret_cast<double2*>(X + (size_t)(j0 + j) * ld + r0 + r) =
+          *reinterpret_cast<const double2*>(tile + aff_at(j, r));
+  }
+}
+
+template <typename T>
+void launch_ingest_columns_typed(hipStream_t s, const void* src, long long row_stride,
+                                 long long col_stride, int n, int dim, double* X, int ld) {
+  const unsigned tiles = (unsigned)((n + kAffTile - 1) / kAffTile) *
+                         (unsigned)((dim + kAffTile - 1) / kAffTile);
+  const bool vec = col_stride == 1 && (reinterpret_cast<uintptr_t>(src) & 15u) == 0 &&
+                   (n == 1 || (row_stride * (long long)sizeof(T)) % 16 == 0);
+  const T* p = static_cast<const T*>(src);
+  if (vec)
+    hipLaunchKernelGGL((k_ingest_columns<T, 16 / (int)sizeof(T)>), dim3(tiles), dim3(256), 0, s, p,
+                       row_stride, col_stride, n, dim, X, ld);
+  else
+    hipLaunchKernelGGL((k_ingest_columns<T, 1>), dim3(tiles), dim3(256), 0, s, p, row_stride,
+                       col_stride, n, dim, X, ld);
+}
+
+// the direction of the memory: the smaller stride (a zero stride repeats one element, it walks
+// nothing)
+long long walked(long long stride) { return stride == 0 ? LLONG_MAX : stride; }
+bool runs_along_columns(long long row_stride, long long col_stride, int dim) {
+  const long long r = walked(row_stride), c = walked(col_stride);
+  return r < c || (r == c && dim == 1);
+}
+
+void launch_ingest_columns(hipStream_t s, int dtype, const void* src, long long row_stride,
+                           long long col_stride, int n, int dim, double* X, int ld) {
+  if (runs_along_columns(row_stride, col_stride, dim)) {
+    launch_ingest_rows(s, dtype, src, col_stride, row_stride, dim, n, X, ld);
+    return;
+  }
+  switch (dtype) {
+    case SC_DTYPE_F64:
+      launch_ingest_columns_typed<double>(s, src, row_stride, col_stride, n, dim, X, ld);
+      break;
+    case SC_DTYPE_F32:
+      launch_ingest_columns_typed<float>(s, src, row_stride, col_stride, n, dim, X, ld);
+      break;
+    case SC_DTYPE_F16:
+      launch_ingest_columns_typed<F16Bits>(s, src, row_stride, col_stride, n, dim, X, ld);
+      break;
+    default:
+      launch_ingest_columns_typed<BF16Bits>(s, src, row_stride, col_stride, n, dim, X, ld);
+      break;
+  }
 }
 
 }  // namespace
@@ -461,6 +547,56 @@ int ingest_rows_into(sc_handle h, const sc_array& a, double* X, int ldx, hipStre
 }
 
 // ------------------------------------------------------------------------------
+// the one place a described k-means input enters
+// ------------------------------------------------------------------------------
+int validate_kmeans_array(sc_handle h, const sc_array* a) {
+  SC_TRY(validate_array(h, a));
+  if (a->rows * a->cols > 0x7fffffffLL)
+    return fail(h, SC_ERR_INVALID, "k-means input larger than 2^31 elements");
+  return SC_OK;
+}
+
+bool array_is_compact_host_f64(const sc_array& a) {
+  return a.location == SC_MEM_HOST && a.dtype == SC_DTYPE_F64 &&
+         (a.col_stride == 1 || a.cols == 1) && (a.row_stride == a.cols || a.rows == 1);
+}
+
+// The (n, dim) values of a validated source, widened, into X[j * ld + r] (ld = round_up(n, 16),
+// rows n .. ld - 1 zeroed) on stream s.  A device source is read in place; a host source is
+// copied at its own width into the handle's staging buffer, in the direction its memory runs (a
+// transposed view is staged as the rows it is made of), and read from there.  The caller waits
+// for s before it hands the source back (every k-means entry does, for its labels).
+int ingest_columns_into(sc_handle h, const sc_array& a, double* X, int ld, hipStream_t s) {
+  const int n = (int)a.rows, dim = (int)a.cols;
+  if (a.location == SC_MEM_DEVICE) {
+    launch_ingest_columns(s, a.dtype, a.data, a.row_stride, a.col_stride, n, dim, X, ld);
+    return check_last(h, "k-means ingest launch");
+  }
+  const size_t eb = dtype_bytes(a.dtype);
+  const bool flip = runs_along_columns(a.row_stride, a.col_stride, dim);
+  sc_array v = a;  // the view whose rows run along the memory
+  if (flip) {
+    v.rows = a.cols;
+    v.cols = a.rows;
+    v.row_stride = a.col_stride;
+    v.col_stride = a.row_stride;
+  }
+  const size_t pitch = ((size_t)v.cols * eb + 15) / 16 * 16;
+  if (h->Xstage.bytes < (size_t)v.rows * pitch) {
+    if (h->Xstage.p && s != h->stream) SC_HIP(h, hipStreamSynchronize(s));
+    SC_TRY(grow(h, h->Xstage, (size_t)v.rows * pitch));
+  }
+  std::vector<unsigned char> packed;
+  bool sync = false;
+  SC_TRY(stage_host_rows(h, v, h->Xstage.p, pitch, s, &packed, &sync));
+  const long long step = (long long)(pitch / eb);
+  launch_ingest_columns(s, a.dtype, h->Xstage.p, flip ? 1 : step, flip ? step : 1, n, dim, X, ld);
+  SC_TRY(check_last(h, "k-means ingest launch"));
+  if (sync) SC_HIP(h, hipStreamSynchronize(s));  // (`packed` is a local)
+  return SC_OK;
+}
+
+// ------------------------------------------------------------------------------
 // the one place a caller's affinity enters
 // ------------------------------------------------------------------------------
 int validate_affinity_array(sc_handle h, const sc_array* a) {
@@ -486,7 +622,7 @@ int ingest_affinity_into(sc_handle h, const sc_array& a, double* dst, int ld, in
     SC_TRY(check_last(h, "affinity ingest launch"));
   } else if (a.dtype == SC_DTYPE_F64) {
     std::vector<unsigned char> packed;
-    SC_TRY(stage_host_affinity(h, a, dst, (size_t)ld * sizeof(double), s, &packed, &sync));
+    SC_TRY(stage_host_rows(h, a, dst, (size_t)ld * sizeof(double), s, &packed, &sync));
     if (ld > n)
       SC_HIP(h, hipMemset2DAsync(dst + n, (size_t)ld * sizeof(double), 0,
                                  (size_t)(ld - n) * sizeof(double), n, s));
@@ -500,7 +636,7 @@ int ingest_affinity_into(sc_handle h, const sc_array& a, double* dst, int ld, in
       SC_TRY(grow(h, h->Xstage, (size_t)n * pitch));
     }
     std::vector<unsigned char> packed;
-    SC_TRY(stage_host_affinity(h, a, h->Xstage.p, pitch, s, &packed, &sync));
+    SC_TRY(stage_host_rows(h, a, h->Xstage.p, pitch, s, &packed, &sync));
     hipLaunchKernelGGL(k_ingest_affinity, dim3(aff_blocks(n)), dim3(256), 0, s,
                        aff_item(a.dtype, h->Xstage.p, (long long)(pitch / eb), 1, n, dst, ld, flag));
     SC_TRY(check_last(h, "affinity ingest launch"));
@@ -536,7 +672,7 @@ int ingest_affinity_group(sc_handle h, const sc_array* as, int count, double* co
     const size_t eb = dtype_bytes(a.dtype);
     if (a.location == SC_MEM_HOST) {
       const size_t pitch = ((size_t)n * eb + 15) / 16 * 16;
-      SC_TRY(stage_host_affinity(h, a, at, pitch, s, &packed[z], &sync));
+      SC_TRY(stage_host_rows(h, a, at, pitch, s, &packed[z], &sync));
       items[z] = aff_item(a.dtype, at, (long long)(pitch / eb), 1, n, dsts[z], matrix_ld(n),
                           flags + z);
       at += (size_t)n * pitch;

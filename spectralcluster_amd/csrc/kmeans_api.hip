@@ -58,12 +58,13 @@ KmeansWorkspace kmeans_workspace(sc_handle h) {
 enum { kgX, kgIo, kgRow, kgVec, kgCd, kgPart, kgRnd, kgLab32, kgLab64, kgInt, kgCount };
 static_assert(kgCount <= kKgenBufs, "handle.h kgen buffers");
 
+// (`row_major_io`: the (n, dim) fp64 copy of a compact host input, which k_to_colmajor reads)
 static int ensure_kmeans_general(sc_handle h, int n, int dim, int k, int trials,
-                                 KmeansGeneralWorkspace* ws) {
+                                 bool row_major_io, KmeansGeneralWorkspace* ws) {
   constexpr int TS = kKgenTrialSlots;
   const size_t ld = round_up(n, 16);
   SC_TRY(grow(h, h->kgen[kgX], ld * dim * sizeof(double)));
-  SC_TRY(grow(h, h->kgen[kgIo], (size_t)n * dim * sizeof(double)));
+  if (row_major_io) SC_TRY(grow(h, h->kgen[kgIo], (size_t)n * dim * sizeof(double)));
   SC_TRY(grow(h, h->kgen[kgRow], 4 * ld * sizeof(double)));
   // mean (dim) | centroids (k dim) | cval (k) | cmx (k) | trial rows (TS dim) | csq (TS) | scalars
   SC_TRY(grow(h, h->kgen[kgVec],
@@ -247,19 +248,41 @@ extern "C" int sc_cluster(sc_handle h, const sc_config* cfg, int n_clusters, int
   return SC_OK;
 }
 
+// the (n, k) embedding `e` (validated) into h->Ek, column-major: compact host fp64 rows by the
+// copy and the transposition they have always had, every other source by the widening ingest
+static int kmeans_metric_on(sc_handle h, const sc_array& e, int max_iter, int metric,
+                            int64_t* labels, double* centroids_out, int* iterations) {
+  const int n = (int)e.rows, k = (int)e.cols, lde = round_up(n, 16);
+  SC_TRY(check_kmeans_request(h, n, k, max_iter, metric, k > kMaxVectors ? 16 : 8));
+  SC_HIP(h, hipSetDevice(h->device));
+  SC_TRY(ensure_kmeans(h, n, k));
+  if (array_is_compact_host_f64(e)) {
+    SC_HIP(h, hipMemcpyAsync(h->Eio.p, e.data, (size_t)n * k * sizeof(double),
+                             hipMemcpyHostToDevice, h->stream));
+    launch_to_colmajor(h->stream, ptr<double>(h->Eio), n, k, ptr<double>(h->Ek), lde);
+  } else {
+    SC_TRY(ingest_columns_into(h, e, ptr<double>(h->Ek), lde, h->stream));
+  }
+  return kmeans_on_device(h, ptr<double>(h->Ek), lde, n, k, max_iter, labels, centroids_out,
+                          iterations, metric);
+}
+
 extern "C" int sc_stage_kmeans_metric(sc_handle h, const double* e, int n, int k, int max_iter,
                                       int metric, int64_t* labels, double* centroids_out,
                                       int* iterations) {
   if (!h) return SC_ERR_INVALID;
   if (!e || !labels || n <= 0 || k <= 0) return fail(h, SC_ERR_INVALID, "bad k-means input");
-  SC_HIP(h, hipSetDevice(h->device));
-  SC_TRY(ensure_kmeans(h, n, k));
-  SC_HIP(h, hipMemcpyAsync(h->Eio.p, e, (size_t)n * k * sizeof(double), hipMemcpyHostToDevice,
-                           h->stream));
-  launch_to_colmajor(h->stream, ptr<double>(h->Eio), n, k, ptr<double>(h->Ek),
-                     round_up(n, 16));
-  return kmeans_on_device(h, ptr<double>(h->Ek), round_up(n, 16), n, k, max_iter, labels,
-                          centroids_out, iterations, metric);
+  return kmeans_metric_on(h, host_f64_array(e, n, k), max_iter, metric, labels, centroids_out,
+                          iterations);
+}
+
+extern "C" int sc_stage_kmeans_metric_array(sc_handle h, const sc_array* e, int max_iter,
+                                            int metric, int64_t* labels, double* centroids_out,
+                                            int* iterations) {
+  if (!h) return SC_ERR_INVALID;
+  SC_TRY(validate_kmeans_array(h, e));
+  if (!labels) return fail(h, SC_ERR_INVALID, "labels is NULL");
+  return kmeans_metric_on(h, *e, max_iter, metric, labels, centroids_out, iterations);
 }
 
 extern "C" int sc_stage_kmeans(sc_handle h, const double* e, int n, int k, int max_iter,
@@ -271,16 +294,13 @@ extern "C" int sc_stage_kmeans(sc_handle h, const double* e, int n, int k, int m
 // ------------------------------------------------------------------------------
 // an (n, dim) input of any width: run_kmeans with dim != k, CustomKMeans
 // ------------------------------------------------------------------------------
-extern "C" int sc_stage_kmeans_general(sc_handle h, const double* x, int n, int dim, int k,
-                                       int max_iter, int metric, double tol,
-                                       const double* init_centroids, int64_t* labels,
-                                       double* centroids_out, int* iterations) {
+// `x`: a validated source of at most 2^31 - 1 elements
+static int kmeans_general_on(sc_handle h, const sc_array& x, int k, int max_iter, int metric,
+                             double tol, const double* init_centroids, int64_t* labels,
+                             double* centroids_out, int* iterations) {
   constexpr int kItersPerSync = 4;  // loop iterations enqueued per host synchronisation
-  if (!h) return SC_ERR_INVALID;
-  if (!x || !labels || n <= 0 || dim <= 0 || k <= 0)
-    return fail(h, SC_ERR_INVALID, "bad k-means input");
-  if ((long long)n * dim > 0x7fffffffLL)
-    return fail(h, SC_ERR_INVALID, "k-means input larger than 2^31 elements");
+  const int n = (int)x.rows, dim = (int)x.cols;
+  const bool compact = array_is_compact_host_f64(x);
   SC_TRY(check_kmeans_request(h, n, k, max_iter, metric, kKgenTrialSlots));
   double u_first;
   int trials;
@@ -288,12 +308,16 @@ extern "C" int sc_stage_kmeans_general(sc_handle h, const double* x, int n, int 
   kmeans_seed_constants(k, &u_first, &trials, &rnd);
   SC_HIP(h, hipSetDevice(h->device));
   KmeansGeneralWorkspace ws;
-  SC_TRY(ensure_kmeans_general(h, n, dim, k, trials, &ws));
+  SC_TRY(ensure_kmeans_general(h, n, dim, k, trials, compact, &ws));
   hipStream_t s = h->stream;
 
-  SC_HIP(h, hipMemcpyAsync(h->kgen[kgIo].p, x, (size_t)n * dim * sizeof(double),
-                           hipMemcpyHostToDevice, s));
-  launch_to_colmajor(s, ptr<double>(h->kgen[kgIo]), n, dim, ws.X, ws.ld);
+  if (compact) {
+    SC_HIP(h, hipMemcpyAsync(h->kgen[kgIo].p, x.data, (size_t)n * dim * sizeof(double),
+                             hipMemcpyHostToDevice, s));
+    launch_to_colmajor(s, ptr<double>(h->kgen[kgIo]), n, dim, ws.X, ws.ld);
+  } else {
+    SC_TRY(ingest_columns_into(h, x, ws.X, ws.ld, s));
+  }
   SC_HIP(h, hipMemsetAsync(ws.words, 0, kKgenWords * sizeof(int), s));
   SC_HIP(h, hipMemsetAsync(ws.scal, 0, kKgenScalars * sizeof(double), s));
   launch_kmeans_general_stats(s, ws, n, dim, metric);
@@ -326,6 +350,44 @@ extern "C" int sc_stage_kmeans_general(sc_handle h, const double* x, int n, int 
                              hipMemcpyDeviceToHost, s));
   SC_HIP(h, hipStreamSynchronize(s));
   if (iterations) *iterations = w[kKgenIters];
+  return SC_OK;
+}
+
+extern "C" int sc_stage_kmeans_general(sc_handle h, const double* x, int n, int dim, int k,
+                                       int max_iter, int metric, double tol,
+                                       const double* init_centroids, int64_t* labels,
+                                       double* centroids_out, int* iterations) {
+  if (!h) return SC_ERR_INVALID;
+  if (!x || !labels || n <= 0 || dim <= 0 || k <= 0)
+    return fail(h, SC_ERR_INVALID, "bad k-means input");
+  if ((long long)n * dim > 0x7fffffffLL)
+    return fail(h, SC_ERR_INVALID, "k-means input larger than 2^31 elements");
+  return kmeans_general_on(h, host_f64_array(x, n, dim), k, max_iter, metric, tol, init_centroids,
+                           labels, centroids_out, iterations);
+}
+
+extern "C" int sc_stage_kmeans_general_array(sc_handle h, const sc_array* x, int k, int max_iter,
+                                             int metric, double tol,
+                                             const double* init_centroids, int64_t* labels,
+                                             double* centroids_out, int* iterations) {
+  if (!h) return SC_ERR_INVALID;
+  SC_TRY(validate_kmeans_array(h, x));
+  if (!labels || k <= 0) return fail(h, SC_ERR_INVALID, "bad k-means input");
+  return kmeans_general_on(h, *x, k, max_iter, metric, tol, init_centroids, labels,
+                           centroids_out, iterations);
+}
+
+extern "C" int sc_stage_ingest_columns(sc_handle h, const sc_array* x, double* out) {
+  if (!h) return SC_ERR_INVALID;
+  SC_TRY(validate_kmeans_array(h, x));
+  if (!out) return fail(h, SC_ERR_INVALID, "out is NULL");
+  SC_HIP(h, hipSetDevice(h->device));
+  const size_t ld = round_up((int)x->rows, 16), bytes = ld * (size_t)x->cols * sizeof(double);
+  SC_TRY(grow(h, h->kgen[kgX], bytes));
+  SC_HIP(h, hipMemsetAsync(h->kgen[kgX].p, 0xff, bytes, h->stream));  // NaNs
+  SC_TRY(ingest_columns_into(h, *x, ptr<double>(h->kgen[kgX]), (int)ld, h->stream));
+  SC_HIP(h, hipMemcpyAsync(out, h->kgen[kgX].p, bytes, hipMemcpyDeviceToHost, h->stream));
+  SC_HIP(h, hipStreamSynchronize(h->stream));
   return SC_OK;
 }
 
