@@ -784,7 +784,59 @@ int sc_predict_batch_single_naive(sc_handle h, const sc_array* xs, int count,
                                   sc_diag* diags, int group, int32_t* single);
 
 /*
- * Stream pool: up to `capacity` streaming sessions (multi_stage_clusterer.py:128-180) whose
+ * The multi-stage regime with min_clusters = 1 as one call: fallback_options.spectral_min_embeddings,
+ * max_spectral_size and the single-cluster test together (spectral_clusterer.py:229-256, 170-199).
+ * The three interact per utterance, so the calls above cannot be combined by partitioning a batch.
+ */
+/* SingleClusterCondition.FallbackClusterer: a value of sc_multi_stage.single_condition only (an
+ * sc_single_check takes the four conditions that read the affinity) */
+enum { SC_SINGLE_BY_FALLBACK = 5 };
+typedef struct sc_multi_stage {
+  int32_t max_spectral_size;         /* 0 = None */
+  int32_t spectral_min_embeddings;
+  int32_t fallback_type;             /* FallbackClustererType: 1 Agglomerative, 2 Naive */
+  double  agglomerative_threshold;   /* read by the Agglomerative type */
+  double  naive_threshold;           /* read by the Naive type ... */
+  double  naive_adaptation_threshold; /* ... a None arrives as naive_threshold */
+  int32_t single_condition;          /* 0: no single-cluster test; 1-4: the values of
+                                        sc_single_check.condition; 5: FallbackClusterer */
+  double  single_threshold;          /* conditions 2-4 */
+  int32_t diagonal_offset;           /* condition 1 */
+} sc_multi_stage;
+/* sizeof(sc_multi_stage) and the byte offsets of its 9 fields, in declaration order (a binding
+ * checks its mirror against them) */
+int sc_multi_stage_layout(int* bytes, int* field_offsets);
+/* sc_predict_batch_reduced[_naive] generalised (one body runs all three): utterance i is of kind
+ *   2  rows < spectral_min_embeddings: the labels are the fallback clusterer's (fallback_type);
+ *      no single-cluster test runs; single[i] = -1, route SC_BATCH_ROUTE_FALLBACK, a zeroed diag,
+ *   1  max_spectral_size > 0 and rows > max_spectral_size: complete-linkage AHC down to
+ *      max_spectral_size clusters; the centroids stay on the device and are clustered as an
+ *      utterance of max_spectral_size rows, INCLUDING the single-cluster test (on their rows under
+ *      condition 5, on their affinity under conditions 1-4); labels[i][r] = label of row r's
+ *      cluster -- zeros when the centroids are found single,
+ *   0  everything else: the single-cluster test on the utterance, then the spectral path.
+ * Stage A runs kinds 1 and 2 in sc_batch_ahc's / sc_batch_naive_cluster's waves.  The handle's
+ * stream is then synchronised -- the centroids are written before anything reads them -- and the
+ * sub-batch (the rows of kind 0, the centroid descriptors of kind 1) takes one road:
+ * single_condition 0, sc_predict_batch_arrays' grouped form; 1-4, sc_predict_batch_single's body;
+ * 5, the verdict waves of sc_predict_batch_single_fallback (fallback_type 1) or
+ * sc_predict_batch_single_naive (fallback_type 2) and one grouped batch of the survivors.  Routes,
+ * diags and single[i] = 1 / 0 keep each road's convention (conditions 1-4: the route the affinity
+ * took and a zeroed diag for a single utterance; condition 5: SC_BATCH_ROUTE_FALLBACK).  The
+ * centroids live until the last stage has returned.  Stage A and the verdict waves honour
+ * sc_set_reduce_wave_bytes; a member of 4096 rows or more, or one that alone exceeds the budget,
+ * keeps sc_ahc's own path.  kinds and single may be NULL.
+ * SC_ERR_INVALID before the first launch: group < 2; max_spectral_size == 1 or
+ * < spectral_min_embeddings; an unknown fallback_type or single_condition; a Naive threshold
+ * pair NaiveClusterer rejects; under condition 1 a member of diagonal_offset >= rows - 1 (kind 1:
+ * rows = max_spectral_size); an agglomerative member of one row (kind 2, or kind 0 under condition
+ * 5).  The per-member messages carry the utterance's index. */
+int sc_predict_batch_multi_stage(sc_handle h, const sc_array* xs, int count, const sc_config* cfg,
+                                 const sc_multi_stage* stage, int64_t* const* labels,
+                                 sc_diag* diags, int group, int32_t* kinds, int32_t* single);
+
+/*
+ * Stream pool:up to `capacity` streaming sessions (multi_stage_clusterer.py:128-180) whose
  * caches stay on the device.  A session lives in a slot 0 .. capacity - 1 and holds up to u2
  * rows of d values; its pre-clusterer reduces them to u1 centroids (2 <= u1 < u2).  All device
  * memory is taken by sc_pool_create, as slabs indexed by slot; SC_ERR_OOM when they do not fit

@@ -170,6 +170,9 @@ class ScFrontOut(ctypes.Structure):
 # the affinity)
 SC_SINGLE_GMM_BIC, SC_SINGLE_ALL_AFFINITY, SC_SINGLE_NEIGHBOR_AFFINITY, SC_SINGLE_AFFINITY_STD = \
     range(1, 5)
+# sc_multi_stage.single_condition takes those four and the FallbackClusterer condition, which
+# reads the embeddings (0: no single-cluster test)
+SC_SINGLE_BY_FALLBACK = 5
 # sc_batch_single_check: the 8 values per matrix
 SINGLE_CHECK_VALUES = ("min", "neighbor_min", "mean", "std", "bic1", "bic2", "lloyd_steps",
                        "em_steps")
@@ -181,6 +184,23 @@ class ScSingleCheck(ctypes.Structure):
       ("condition", ctypes.c_int32),
       ("diagonal_offset", ctypes.c_int32),
       ("threshold", ctypes.c_double),
+  ]
+
+
+class ScMultiStage(ctypes.Structure):
+  """Mirror of `sc_multi_stage`: the multi-stage regime of `sc_predict_batch_multi_stage` --
+  size reduction, the short-clip fallback and the single-cluster test of min_clusters = 1
+  (`single_condition`: 0 none, 1-4 `SC_SINGLE_*`, 5 the FallbackClusterer condition)."""
+  _fields_ = [
+      ("max_spectral_size", ctypes.c_int32),
+      ("spectral_min_embeddings", ctypes.c_int32),
+      ("fallback_type", ctypes.c_int32),
+      ("agglomerative_threshold", ctypes.c_double),
+      ("naive_threshold", ctypes.c_double),
+      ("naive_adaptation_threshold", ctypes.c_double),
+      ("single_condition", ctypes.c_int32),
+      ("single_threshold", ctypes.c_double),
+      ("diagonal_offset", ctypes.c_int32),
   ]
 
 
@@ -441,6 +461,15 @@ PROTOTYPES = {
                                                      ctypes.POINTER(_c_int64_p),
                                                      ctypes.POINTER(ScDiag), ctypes.c_int,
                                                      ctypes.POINTER(ctypes.c_int32)]),
+    "sc_multi_stage_layout": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int),
+                                             ctypes.POINTER(ctypes.c_int)]),
+    "sc_predict_batch_multi_stage": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),
+                                                    ctypes.c_int, ctypes.POINTER(ScConfig),
+                                                    ctypes.POINTER(ScMultiStage),
+                                                    ctypes.POINTER(_c_int64_p),
+                                                    ctypes.POINTER(ScDiag), ctypes.c_int,
+                                                    ctypes.POINTER(ctypes.c_int32),
+                                                    ctypes.POINTER(ctypes.c_int32)]),
     "sc_pool_create": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, ctypes.POINTER(_handle_t)]),
     "sc_pool_destroy": (ctypes.c_int, [_handle_t]),

@@ -1790,11 +1790,19 @@ extern "C" int sc_predict_batch_single(sc_handle h, const sc_array* xs, int coun
     return SC_OK;
   }
   if (device_source) SC_HIP(h, hipStreamSynchronize(h->stream));  // (as sc_predict_batch_arrays)
+  return predict_batch_single_impl(h, xs, ns.data(), d, count, cfg, check, labels, diags, group,
+                                   single);
+}
+
+int predict_batch_single_impl(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
+                              const sc_config* cfg, const sc_single_check* check,
+                              int64_t* const* labels, sc_diag* diags, int group,
+                              int32_t* single) {
   SingleCheck sc;
   sc.opt = check;
   sc.single = single;
   if (!check && single) std::fill(single, single + count, 0);
-  return predict_batch_core(h, xs, ns.data(), d, count, cfg, labels, diags, group, Bands(),
+  return predict_batch_core(h, xs, ns, d, count, cfg, labels, diags, group, Bands(),
                             check ? &sc : nullptr);
 }
 

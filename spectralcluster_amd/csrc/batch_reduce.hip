@@ -21,6 +21,9 @@
 // The Naive fallback type (sc_batch_naive_cluster, sc_batch_naive_check and the _naive forms of
 // the two predict calls) runs the same waves with one launch between ingest and copy back: see
 // NaiveMember below.  The two predict calls and their _naive forms share one body each.
+// sc_predict_batch_multi_stage (size reduction, fallback and the single-cluster test of
+// min_clusters = 1 together) is the first of those bodies with the test in front of its sub-batch:
+// see SingleSpec below.
 // Kernels: ahc.hip, rowops.hip, naive_batch.hip.
 #include "ahc_tree.h"
 #include "handle.h"
@@ -323,12 +326,14 @@ int too_few_rows(sc_handle h, int index, int n) {
 //      may outlive the wave (the grouped batch of the survivors reads them there).
 struct VerdictMember {
   int index = 0;  // into the caller's lists
+  int name = -1;  // the utterance a message names, when the lists are a sub-batch (< 0: index)
   int n = 0;
   // results
   double height = 0.0;
   int single = 0;
   const double* dev_rows = nullptr;  // the widened rows (pitch round_up(d, 16)) where they stayed
 
+  int named() const { return name < 0 ? index : name; }
   bool lds() const { return kPoolLdsLinkageMax > 0 && n <= kPoolLdsLinkageMax; }
   size_t rows_bytes(int d) const { return align256((size_t)n * round_up(d, 16) * sizeof(double)); }
   // Xn, D and (chain kernel) size + chain
@@ -348,7 +353,8 @@ int verdict_single(sc_handle h, const sc_array& a, VerdictMember* m, double thre
   SC_TRY(ingest_embeddings(h, a, true));
   std::vector<int64_t> lab(m->n);
   const int rc = ahc_resident(h, SC_LINKAGE_AVERAGE, 0, threshold, lab.data(), nullptr, &m->height);
-  if (rc == SC_ERR_INVALID) return fail(h, rc, "utterance " + std::to_string(m->index) + ": " + h->err);
+  if (rc == SC_ERR_INVALID)
+    return fail(h, rc, "utterance " + std::to_string(m->named()) + ": " + h->err);
   SC_TRY(rc);
   m->single = m->height >= threshold ? 0 : 1;
   return SC_OK;
@@ -463,7 +469,8 @@ int verdict_wave(sc_handle h, const sc_array* xs, int d, const std::vector<Verdi
   SC_HIP(h, hipStreamSynchronize(s));
   int bad_index = -1;  // (the first of the batch, whatever the wave's order)
   for (int i = 0; i < count; ++i)
-    if (bad_h[i] != 0 && (bad_index < 0 || wave[i]->index < bad_index)) bad_index = wave[i]->index;
+    if (bad_h[i] != 0 && (bad_index < 0 || wave[i]->named() < bad_index))
+      bad_index = wave[i]->named();
   if (bad_index >= 0) return fail(h, SC_ERR_INVALID, bad_rows_message(bad_index));
   for (int i = 0; i < count; ++i) {
     VerdictMember& m = *wave[i];
@@ -539,6 +546,7 @@ int verdict_members(sc_handle h, const std::vector<int>& ns, std::vector<Verdict
 //                    rows are a block of their own, which may outlive the wave (VerdictMember).
 struct NaiveMember {
   int index = 0;  // into the caller's lists
+  int name = -1;  // the utterance a message names, when the lists are a sub-batch (< 0: index)
   int n = 0;
   bool want_centroids = false;  // labels form: the centroids come back
   // results
@@ -547,6 +555,7 @@ struct NaiveMember {
   int single = 0, stopped_at = 0;    // verdict form
   const double* dev_rows = nullptr;  // the widened rows (pitch round_up(d, 16)) where they stayed
 
+  int named() const { return name < 0 ? index : name; }
   int k() const { return ints[2 * (size_t)n]; }
   size_t rows_bytes(int d) const { return align256((size_t)n * round_up(d, 16) * sizeof(double)); }
   size_t cent_bytes(int d, bool verdict) const {
@@ -646,8 +655,8 @@ int naive_wave(sc_handle h, const sc_array* xs, int d, const std::vector<NaiveMe
   if (run.verdict) {
     int bad_index = -1;  // (the first of the batch, whatever the wave's order)
     for (int i = 0; i < count; ++i)
-      if (ints_h[ints_of[i] + 2] != 0 && (bad_index < 0 || wave[i]->index < bad_index))
-        bad_index = wave[i]->index;
+      if (ints_h[ints_of[i] + 2] != 0 && (bad_index < 0 || wave[i]->named() < bad_index))
+        bad_index = wave[i]->named();
     if (bad_index >= 0) return fail(h, SC_ERR_INVALID, bad_rows_message(bad_index));
   }
   for (int i = 0; i < count; ++i) {
@@ -716,13 +725,32 @@ struct FallbackSpec {
   double adaptation = 0.0;  // naive only
 };
 
-// The body of sc_predict_batch_reduced and sc_predict_batch_reduced_naive (their arguments are
-// checked by predict_batch_reduced_entry below).
+// The single-cluster test of min_clusters = 1 that sc_predict_batch_multi_stage puts in front of
+// the spectral run of the sub-batch (the rows of kind 0, the centroids of kind 1)
+struct SingleSpec {
+  int condition = 0;         // 0 none; 1-4 `check` (the affinity); 5 the fallback clusterer's verdict
+  sc_single_check check{};
+  int32_t* single = nullptr;  // per utterance 1 / 0, -1 for kind 2 (not tested); may be null
+};
+
+// The verdicts of the FallbackClusterer condition for a whole batch, then ONE grouped batch of the
+// survivors (defined below, with the two entry points that are nothing else).  `names` (may be
+// null): the utterance a message names for xs[z], when xs is a sub-batch.
+int predict_batch_fallback_condition(sc_handle h, const sc_array* xs, int count,
+                                     const sc_config* cfg, const FallbackSpec& fallback,
+                                     const std::vector<int>& ns, int d, int64_t* const* labels,
+                                     sc_diag* diags, int group, int32_t* single,
+                                     const int* names);
+
+// The body of sc_predict_batch_reduced, sc_predict_batch_reduced_naive (test == nullptr) and
+// sc_predict_batch_multi_stage (their arguments are checked by predict_batch_reduced_entry below;
+// what is checked per member is checked here, before the first launch).
 int predict_batch_reduced_body(sc_handle h, const sc_array* xs, int count, const sc_config* cfg,
                                int max_spectral_size, int spectral_min_embeddings,
-                               const FallbackSpec& fallback, int64_t* const* labels,
-                               sc_diag* diags, int group, int32_t* kinds,
+                               const FallbackSpec& fallback, const SingleSpec* test,
+                               int64_t* const* labels, sc_diag* diags, int group, int32_t* kinds,
                                const std::vector<int>& ns, int d) {
+  const int condition = test ? test->condition : 0;
   std::vector<int32_t> kind(count, 0);
   std::vector<ReduceMember> members;
   std::vector<NaiveMember> naive;
@@ -732,6 +760,15 @@ int predict_batch_reduced_body(sc_handle h, const sc_array* xs, int count, const
     ReduceMember m;
     m.index = i;
     m.n = ns[i];
+    if (ns[i] >= spectral_min_embeddings && condition != 0) {
+      // what is tested: the utterance, or the max_spectral_size centroids of kind 1
+      const int rows = max_spectral_size > 0 && ns[i] > max_spectral_size ? max_spectral_size
+                                                                           : ns[i];
+      if (condition <= SC_SINGLE_AFFINITY_STD)
+        SC_TRY(check_single_offset(h, &test->check, rows, i));
+      else if (!fallback.naive && rows < 2)
+        return too_few_rows(h, i, rows);
+    }
     if (ns[i] < spectral_min_embeddings) {
       kind[i] = 2;
       if (fallback.naive) {  // (a single row is fine: label 0)
@@ -800,16 +837,30 @@ int predict_batch_reduced_body(sc_handle h, const sc_array* xs, int count, const
   const int sub_count = (int)at.size();
   std::vector<sc_diag> sub_diags(diags ? sub_count : 0);
   std::vector<int32_t> routes(count, SC_BATCH_ROUTE_FALLBACK);
+  std::vector<int32_t> sub_single(sub_count, 0);
   if (sub_count > 0) {
     // the centroids are written, and what the caller ordered before this handle's stream is
-    // done, before the streams of the batch read either
+    // done, before a verdict wave or the streams of the batch read either
     SC_HIP(h, hipStreamSynchronize(h->stream));
-    SC_TRY(predict_batch_grouped_impl(h, sub.data(), sub_ns.data(), d, sub_count, cfg,
-                                      sub_labels.data(), diags ? sub_diags.data() : nullptr,
-                                      group));
+    sc_diag* sub_dg = diags ? sub_diags.data() : nullptr;
+    if (condition == 0)
+      SC_TRY(predict_batch_grouped_impl(h, sub.data(), sub_ns.data(), d, sub_count, cfg,
+                                        sub_labels.data(), sub_dg, group));
+    else if (condition <= SC_SINGLE_AFFINITY_STD)
+      SC_TRY(predict_batch_single_impl(h, sub.data(), sub_ns.data(), d, sub_count, cfg,
+                                       &test->check, sub_labels.data(), sub_dg, group,
+                                       sub_single.data()));
+    else
+      SC_TRY(predict_batch_fallback_condition(h, sub.data(), sub_count, cfg, fallback, sub_ns, d,
+                                              sub_labels.data(), sub_dg, group,
+                                              sub_single.data(), at.data()));
     for (int z = 0; z < sub_count; ++z) routes[at[z]] = h->last_routes[z];
   }
   h->last_routes = routes;
+  if (test && test->single) {
+    std::fill(test->single, test->single + count, -1);  // kind 2: not tested
+    for (int z = 0; z < sub_count; ++z) test->single[at[z]] = sub_single[z];
+  }
   for (int z = 0; z < sub_count; ++z) {
     const int i = at[z];
     if (diags) diags[i] = sub_diags[z];
@@ -827,7 +878,7 @@ int predict_batch_reduced_entry(sc_handle h, const char* name, const sc_array* x
                                 const sc_config* cfg, int max_spectral_size,
                                 int spectral_min_embeddings, const FallbackSpec& fallback,
                                 int64_t* const* labels, sc_diag* diags, int group,
-                                int32_t* kinds) {
+                                int32_t* kinds, const SingleSpec* test = nullptr) {
   if (!xs || !labels || count < 0) return fail(h, SC_ERR_INVALID, "NULL argument");
   if (group < 2)
     return fail(h, SC_ERR_INVALID, std::string(name) + " is the grouped form: group >= 2");
@@ -838,6 +889,8 @@ int predict_batch_reduced_entry(sc_handle h, const char* name, const sc_array* x
     return fail(h, SC_ERR_INVALID,
                 "max_spectral_size must not be below spectral_min_embeddings in a batch");
   if (fallback.naive) SC_TRY(validate_naive_thresholds(h, fallback.threshold, fallback.adaptation));
+  if (test && test->condition >= SC_SINGLE_GMM_BIC && test->condition <= SC_SINGLE_AFFINITY_STD)
+    SC_TRY(validate_single_check(h, &test->check));
   SC_TRY(validate_config(h, cfg));
   SC_HIP(h, hipSetDevice(h->device));
   bool device_source = false;
@@ -850,7 +903,7 @@ int predict_batch_reduced_entry(sc_handle h, const char* name, const sc_array* x
     return SC_OK;
   }
   return predict_batch_reduced_body(h, xs, count, cfg, max_spectral_size, spectral_min_embeddings,
-                                    fallback, labels, diags, group, kinds, ns, d);
+                                    fallback, test, labels, diags, group, kinds, ns, d);
 }
 
 // One verdict of the FallbackClusterer condition per utterance, whichever clusterer gave it
@@ -907,6 +960,46 @@ int predict_batch_single_rest(sc_handle h, const sc_array* xs, int count, const 
     for (int z = 0; z < sub_count; ++z) diags[at[z]] = sub_diags[z];
   }
   return SC_OK;
+}
+
+int predict_batch_fallback_condition(sc_handle h, const sc_array* xs, int count,
+                                     const sc_config* cfg, const FallbackSpec& fallback,
+                                     const std::vector<int>& ns, int d, int64_t* const* labels,
+                                     sc_diag* diags, int group, int32_t* single,
+                                     const int* names) {
+  // the verdicts of the whole batch first (waves of hundreds of workgroups, not one lockstep
+  // group at a time); the rows of the waves stay on the device for the survivors
+  DeviceBlocks rows;
+  std::vector<SingleVerdict> verdicts(count);
+  if (fallback.naive) {
+    std::vector<NaiveMember> members(count);
+    for (int i = 0; i < count; ++i) {  // (an utterance of one row is single)
+      members[i].index = i;
+      members[i].name = names ? names[i] : -1;
+      members[i].n = ns[i];
+    }
+    NaiveRun run;
+    run.threshold = fallback.threshold;
+    run.adaptation = fallback.adaptation;
+    run.verdict = true;
+    run.check_rows = true;  // predict() builds the affinity of such an utterance and raises
+    SC_TRY(naive_members(h, xs, d, &members, run, &rows));
+    for (const NaiveMember& m : members) {
+      verdicts[m.index].single = m.single;
+      verdicts[m.index].dev_rows = m.dev_rows;
+    }
+  } else {
+    std::vector<VerdictMember> members;
+    SC_TRY(verdict_members(h, ns, &members));  // (the callers have checked n >= 2)
+    for (int i = 0; names && i < count; ++i) members[i].name = names[i];
+    SC_TRY(fallback_verdicts(h, xs, d, &members, fallback.threshold, &rows));
+    for (const VerdictMember& m : members) {
+      verdicts[m.index].single = m.single;
+      verdicts[m.index].dev_rows = m.dev_rows;
+    }
+  }
+  return predict_batch_single_rest(h, xs, count, cfg, verdicts, ns, d, labels, diags, group,
+                                   single);
 }
 
 }  // namespace
@@ -974,6 +1067,48 @@ extern "C" int sc_predict_batch_reduced_naive(sc_handle h, const sc_array* xs, i
   return predict_batch_reduced_entry(h, "sc_predict_batch_reduced_naive", xs, count, cfg,
                                      max_spectral_size, spectral_min_embeddings, fallback, labels,
                                      diags, group, kinds);
+}
+
+extern "C" int sc_multi_stage_layout(int* bytes, int* field_offsets) {
+  if (bytes) *bytes = (int)sizeof(sc_multi_stage);
+  if (field_offsets) {
+    field_offsets[0] = (int)offsetof(sc_multi_stage, max_spectral_size);
+    field_offsets[1] = (int)offsetof(sc_multi_stage, spectral_min_embeddings);
+    field_offsets[2] = (int)offsetof(sc_multi_stage, fallback_type);
+    field_offsets[3] = (int)offsetof(sc_multi_stage, agglomerative_threshold);
+    field_offsets[4] = (int)offsetof(sc_multi_stage, naive_threshold);
+    field_offsets[5] = (int)offsetof(sc_multi_stage, naive_adaptation_threshold);
+    field_offsets[6] = (int)offsetof(sc_multi_stage, single_condition);
+    field_offsets[7] = (int)offsetof(sc_multi_stage, single_threshold);
+    field_offsets[8] = (int)offsetof(sc_multi_stage, diagonal_offset);
+  }
+  return SC_OK;
+}
+
+extern "C" int sc_predict_batch_multi_stage(sc_handle h, const sc_array* xs, int count,
+                                            const sc_config* cfg, const sc_multi_stage* stage,
+                                            int64_t* const* labels, sc_diag* diags, int group,
+                                            int32_t* kinds, int32_t* single) {
+  if (!h) return SC_ERR_INVALID;
+  if (!stage) return fail(h, SC_ERR_INVALID, "NULL argument");
+  constexpr int kAgglomerative = 1, kNaive = 2;  // FallbackClustererType's values
+  if (stage->fallback_type != kAgglomerative && stage->fallback_type != kNaive)
+    return fail(h, SC_ERR_INVALID, "fallback_type must be 1 (Agglomerative) or 2 (Naive)");
+  if (stage->single_condition < 0 || stage->single_condition > SC_SINGLE_BY_FALLBACK)
+    return fail(h, SC_ERR_INVALID, "single_condition must be 0 (no test) or 1 .. 5");
+  FallbackSpec fallback;
+  fallback.naive = stage->fallback_type == kNaive;
+  fallback.threshold = fallback.naive ? stage->naive_threshold : stage->agglomerative_threshold;
+  fallback.adaptation = stage->naive_adaptation_threshold;
+  SingleSpec test;
+  test.condition = stage->single_condition;
+  test.check.condition = stage->single_condition;
+  test.check.diagonal_offset = stage->diagonal_offset;
+  test.check.threshold = stage->single_threshold;
+  test.single = single;
+  return predict_batch_reduced_entry(h, "sc_predict_batch_multi_stage", xs, count, cfg,
+                                     stage->max_spectral_size, stage->spectral_min_embeddings,
+                                     fallback, labels, diags, group, kinds, &test);
 }
 
 extern "C" int sc_batch_naive_cluster(sc_handle h, const sc_array* xs, int count, double threshold,
@@ -1078,17 +1213,10 @@ extern "C" int sc_predict_batch_single_fallback(sc_handle h, const sc_array* xs,
     h->last_routes.clear();
     return SC_OK;
   }
-  // the verdicts of the whole batch first (waves of hundreds of workgroups, not one lockstep
-  // group at a time); the rows of the waves stay on the device for the survivors
-  DeviceBlocks rows;
-  SC_TRY(fallback_verdicts(h, xs, d, &members, distance_threshold, &rows));
-  std::vector<SingleVerdict> verdicts(count);
-  for (const VerdictMember& m : members) {
-    verdicts[m.index].single = m.single;
-    verdicts[m.index].dev_rows = m.dev_rows;
-  }
-  return predict_batch_single_rest(h, xs, count, cfg, verdicts, ns, d, labels, diags, group,
-                                   single);
+  FallbackSpec fallback;
+  fallback.threshold = distance_threshold;
+  return predict_batch_fallback_condition(h, xs, count, cfg, fallback, ns, d, labels, diags, group,
+                                          single, nullptr);
 }
 
 extern "C" int sc_predict_batch_single_naive(sc_handle h, const sc_array* xs, int count,
@@ -1112,23 +1240,10 @@ extern "C" int sc_predict_batch_single_naive(sc_handle h, const sc_array* xs, in
     h->last_routes.clear();
     return SC_OK;
   }
-  std::vector<NaiveMember> members(count);
-  for (int i = 0; i < count; ++i) {  // (an utterance of one row is single)
-    members[i].index = i;
-    members[i].n = ns[i];
-  }
-  NaiveRun run;
-  run.threshold = naive_threshold;
-  run.adaptation = naive_adaptation_threshold;
-  run.verdict = true;
-  run.check_rows = true;  // predict() builds the affinity of such an utterance and raises
-  DeviceBlocks rows;  // the rows of the waves stay on the device for the survivors
-  SC_TRY(naive_members(h, xs, d, &members, run, &rows));
-  std::vector<SingleVerdict> verdicts(count);
-  for (const NaiveMember& m : members) {
-    verdicts[m.index].single = m.single;
-    verdicts[m.index].dev_rows = m.dev_rows;
-  }
-  return predict_batch_single_rest(h, xs, count, cfg, verdicts, ns, d, labels, diags, group,
-                                   single);
+  FallbackSpec fallback;
+  fallback.naive = true;
+  fallback.threshold = naive_threshold;
+  fallback.adaptation = naive_adaptation_threshold;
+  return predict_batch_fallback_condition(h, xs, count, cfg, fallback, ns, d, labels, diags, group,
+                                          single, nullptr);
 }

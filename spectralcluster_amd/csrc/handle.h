@@ -327,6 +327,12 @@ int predict_batch_streams_impl(sc_handle h, const sc_array* xs, const int* ns, i
 int predict_batch_grouped_impl(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
                                const sc_config* cfg, int64_t* const* labels, sc_diag* diags,
                                int group);
+// the body of sc_predict_batch_single behind its checks (check may be null: the grouped batch;
+// single may be null); the caller has synchronised h->stream when a source is on the device
+int predict_batch_single_impl(sc_handle h, const sc_array* xs, const int* ns, int d, int count,
+                              const sc_config* cfg, const sc_single_check* check,
+                              int64_t* const* labels, sc_diag* diags, int group,
+                              int32_t* single);
 
 // sc_ahc on the embeddings resident in h->X (ingest_embeddings): callers_api.hip.  max_height
 // (may be null): the largest merge height of the tree.

@@ -311,7 +311,12 @@ class SpectralClusterer:
     float64 on the device (exactly: labels and eigenvalues are those of
     `predict(x.astype(np.float64))`).  A device tensor needs no synchronisation by the caller:
     its producer orders its pending writes before the library's stream, and the tensor may be
-    overwritten or freed when predict() has returned."""
+    overwritten or freed when predict() has returned.
+
+    With `fallback_options.spectral_min_embeddings`, `max_spectral_size` or `min_clusters=1`
+    under the `FallbackClusterer` condition, predict() brings a device tensor to the host (up to
+    three times when they meet).  `predict_batch([x], batch_multi_stage=True)` runs that regime
+    on a single tensor without a host round trip, with the same labels."""
     with _lib.use_device(self.device):  # helpers without a device argument follow self.device
       source = _dlpack.describe(embeddings, self._handle)
       try:
@@ -617,7 +622,9 @@ class SpectralClusterer:
                     constraint_matrices: typing.Optional[typing.Sequence] = None,
                     autotune_from_entry_state: bool = False,
                     batch_fallback_condition: bool = False,
-                    batch_naive_fallback: bool = False
+                    batch_naive_fallback: bool = False,
+                    *,
+                    batch_multi_stage: bool = False
                     ) -> typing.List[np.ndarray]:
     """Independent predict() calls (the reference has no batch API: a batch is a
     Python loop).
@@ -716,7 +723,7 @@ class SpectralClusterer:
     `max_spectral_size` that is not above `max_clusters` / `min_clusters`, and for a fallback
     utterance of one row.  An utterance with a zero or non-finite row raises a ValueError that
     names its index.  Everything else -- the `Naive` fallback (but see
-    `batch_naive_fallback`), `min_clusters=1`, constraints,
+    `batch_naive_fallback`), `min_clusters=1` (but see `batch_multi_stage`), constraints,
     AutoTune, `group=1`, `streams` -- stays the per-utterance loop (routes all 0).
 
     `min_clusters=1` (the streaming regime: the clusterer may say "one speaker"): the batch is
@@ -733,7 +740,8 @@ class SpectralClusterer:
     predict()'s ValueError, with the utterance's index, before anything is launched.  These keep
     the per-utterance loop (routes all 0) with `min_clusters=1`: the `FallbackClusterer` condition
     (it clusters the embeddings, not the affinity; see `batch_fallback_condition`), constrained
-    batches, AutoTune batches, and batches with `max_spectral_size` / `spectral_min_embeddings`.
+    batches, AutoTune batches, and batches with `max_spectral_size` / `spectral_min_embeddings`
+    (but see `batch_multi_stage`).
 
     `batch_fallback_condition` (default False: the loop above).  With it a `min_clusters=1`
     batch under the `FallbackClusterer` condition -- what `MultiStageClusterer`'s constructor
@@ -767,10 +775,37 @@ class SpectralClusterer:
     Labels equal predict()'s: the batch kernel shares its arithmetic with the one predict() runs.
     A threshold pair that `NaiveClusterer` rejects raises its ValueError before anything is
     launched.  With the `Agglomerative` type the flag does nothing.
+
+    `batch_multi_stage` (keyword only; default False: the loop, as the paragraphs above say).
+    The three options of a robust offline diarizer together -- `max_spectral_size` and / or
+    `fallback_options.spectral_min_embeddings` above 1, with `min_clusters=1` -- are ONE
+    `sc_predict_batch_multi_stage` call when the batch is the grouped form (`group` not 1, no
+    `streams`), no `constraint_matrices` are given, there is no AutoTune, the affinity and k-means functions are the
+    default ones, k-means is the cosine one, and `max_spectral_size >= spectral_min_embeddings`
+    when both are set.  Any of the five single-cluster conditions and either fallback type is
+    taken; `batch_fallback_condition` / `batch_naive_fallback` are not needed as well.  Per
+    utterance, in predict()'s order: fewer than `spectral_min_embeddings` rows, the fallback
+    clusterer's labels and no single-cluster test; more than `max_spectral_size` rows,
+    complete-linkage pre-clustering, then what predict() does with the centroids -- which stay on
+    the device --, their single-cluster test included; otherwise the single-cluster test and the
+    spectral path.  Results have predict()'s dtypes: float64 for a size-reduced utterance (zeros
+    when its centroids hold one cluster), `np.array([0] * n)` for an utterance of one cluster,
+    int64 otherwise.  Afterwards `last_batch_reduced` holds the kinds, `last_batch_single` True /
+    False / None (None: a fallback utterance, not tested), `last_batch_routes` the route of the
+    spectral run (under the `FallbackClusterer` condition 3 for an utterance found single; 3 for a
+    fallback utterance) and `last_batch_diags` its diagnostics (zeroed for single and fallback
+    utterances).  predict()'s ValueErrors -- `max_spectral_size` not above `max_clusters` /
+    `min_clusters`, an agglomerative utterance of one row, an AffinityGmmBic diagonal offset that
+    is not below the tested rows - 1, a threshold pair `NaiveClusterer` rejects -- are raised,
+    with the utterance's index, before anything is launched.  A batch of one utterance is
+    covered.  Without the flag, and for every other clusterer, nothing changes.
     """
     self.last_batch_single = None
     if autotune_from_entry_state and self.autotune is not None:
       return self._predict_batch_entry_state(utterances, constraint_matrices, streams, group)
+    if (batch_multi_stage and streams is None and (group is None or int(group) > 1) and
+        constraint_matrices is None and self._multi_stage_batch_covers()):
+      return self._predict_batch_multi_stage(utterances, 16 if group is None else int(group))
     if (batch_fallback_condition and streams is None and (group is None or int(group) > 1) and
         (constraint_matrices is None or self.constraint_options is None) and
         self._fallback_condition_covers(naive=batch_naive_fallback)):
@@ -1282,6 +1317,124 @@ class SpectralClusterer:
     # predict() returns them
     return [l.astype(np.float64) if k == _lib.BATCH_KIND_REDUCED else l
             for l, k in zip(labels, self.last_batch_reduced)]
+
+  def _multi_stage_batch_covers(self) -> bool:
+    """Is this clusterer one whose predict() `sc_predict_batch_multi_stage` reproduces?
+    `min_clusters == 1` with `max_spectral_size` and / or `spectral_min_embeddings` above 1, no
+    AutoTune, the default affinity and k-means functions, cosine k-means, and centroids that are
+    not fallback members themselves.  (The caller has looked at the form of the batch.)"""
+    options = self.fallback_options
+    if self.min_clusters != 1:
+      return False
+    if self.max_spectral_size is None and options.spectral_min_embeddings <= 1:
+      return False
+    if (self.autotune is not None or
+        self.affinity_function is not utils.compute_affinity_matrix or
+        self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans):
+      return False
+    if (self.max_spectral_size is not None and
+        self.max_spectral_size < options.spectral_min_embeddings):
+      return False
+    if not isinstance(options.single_cluster_condition, fallback_clusterer.SingleClusterCondition):
+      return False  # (predict() says what is wrong with it)
+    if not isinstance(options.fallback_clusterer_type, fallback_clusterer.FallbackClustererType):
+      return False
+    try:
+      return _lib.kmeans_metric_code(self.custom_dist) == _lib.KMEANS_METRICS["cosine"]
+    except (ValueError, _lib.UnsupportedOnDeviceError):
+      return False  # (predict() raises what it raises today)
+
+  def _multi_stage_struct(self) -> _lib.ScMultiStage:
+    """The `sc_multi_stage` of this clusterer (`_multi_stage_batch_covers` holds); the
+    ValueError of `NaiveClusterer` for a threshold pair it rejects."""
+    options = self.fallback_options
+    stage = _lib.ScMultiStage()
+    stage.max_spectral_size = int(self.max_spectral_size or 0)
+    stage.spectral_min_embeddings = int(options.spectral_min_embeddings)
+    stage.fallback_type = options.fallback_clusterer_type.value
+    stage.agglomerative_threshold = float(options.agglomerative_threshold)
+    if self._naive_fallback():
+      stage.naive_threshold, stage.naive_adaptation_threshold = self._naive_thresholds()
+    stage.single_condition = options.single_cluster_condition.value
+    stage.single_threshold = float(options.single_cluster_affinity_threshold)
+    stage.diagonal_offset = int(options.single_cluster_affinity_diagonal_offset)
+    return stage
+
+  def _check_multi_stage_rows(self, stage: _lib.ScMultiStage,
+                              rows: typing.Sequence[int]) -> None:
+    """What predict() raises for an utterance of the multi-stage regime, with the utterance's
+    index, before anything is launched (the library checks the same)."""
+    agglomerative = not self._naive_fallback()
+    few = ("Found array with %d sample(s) while a minimum of 2 is required by "
+           "AgglomerativeClustering. (utterance %d)")
+    for i, n in enumerate(rows):
+      kind = self._batch_kind(n)
+      if kind == _lib.BATCH_KIND_FALLBACK:
+        if n < 2 and agglomerative:
+          raise ValueError(few % (n, i))
+        continue
+      if kind == _lib.BATCH_KIND_REDUCED:
+        if (self.max_spectral_size < 2 or
+            (self.max_clusters and self.max_spectral_size <= self.max_clusters) or
+            self.max_spectral_size <= self.min_clusters):
+          raise ValueError("max_spectral_size should be a relatively big number "
+                           "(utterance %d)" % i)
+        n = self.max_spectral_size  # what is tested: the centroids
+      if stage.single_condition == _lib.SC_SINGLE_GMM_BIC:
+        if stage.diagonal_offset < 0 or stage.diagonal_offset >= n - 1:
+          raise ValueError(
+              "single_cluster_affinity_diagonal_offset must be significantly smaller than "
+              "affinity matrix dimension (utterance %d)" % i)
+      elif stage.single_condition == _lib.SC_SINGLE_BY_FALLBACK and agglomerative and n < 2:
+        raise ValueError(few % (n, i))
+
+  def _predict_batch_multi_stage(self, utterances: typing.Sequence,
+                                 group: int) -> typing.List[np.ndarray]:
+    """predict_batch(batch_multi_stage=True): ONE `sc_predict_batch_multi_stage` call;
+    `_multi_stage_batch_covers` holds."""
+    for u in utterances:
+      if isinstance(u, np.ndarray) and u.ndim != 2:
+        raise ValueError("all utterances must be (n_i, d) with the same d")
+    count = len(utterances)
+    if count == 0:
+      self.last_batch_routes, self.last_batch_reduced, self.last_batch_diags = [], [], []
+      self.last_batch_single = []
+      return []
+    sources = []
+    try:
+      with _lib.use_device(self.device):
+        for u in utterances:
+          sources.append(_dlpack.describe(u, self._handle))
+      d = sources[0].shape[1]
+      if any(src.shape[1] != d for src in sources):
+        raise ValueError("all utterances must be (n_i, d) with the same d")
+      stage = self._multi_stage_struct()
+      self._check_multi_stage_rows(stage, [src.shape[0] for src in sources])
+      labels = [np.empty(src.shape[0], dtype=np.int64) for src in sources]
+      handle = self._handle()
+      lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
+      diags = (_lib.ScDiag * count)()
+      kinds = (ctypes.c_int32 * count)()
+      single = (ctypes.c_int32 * count)()
+      arrays = (_lib.ScArray * count)(*[src.array for src in sources])
+      handle.check(handle.lib.sc_predict_batch_multi_stage(
+          handle.raw, arrays, count, self.build_config(), ctypes.byref(stage), lp, diags,
+          int(group), kinds, single), ValueError)
+    finally:
+      for src in sources:
+        src.release()
+    self._batch_report(handle, diags, count)
+    self.last_batch_reduced = [int(k) for k in kinds]
+    self.last_batch_single = [None if v < 0 else bool(v) for v in single]
+    out = []
+    for l, k, one in zip(labels, self.last_batch_reduced, self.last_batch_single):
+      if k == _lib.BATCH_KIND_REDUCED:
+        out.append(l.astype(np.float64))  # utils.chain_labels fills np.zeros: float64
+      elif one:
+        out.append(np.array([0] * l.shape[0]))  # predict()'s result for one cluster
+      else:
+        out.append(l)
+    return out
 
   def _batch_arrays_call(self, handle: _lib.Handle, arrays: typing.Sequence[_lib.ScArray],
                          labels: typing.Sequence[np.ndarray], diags, group: int,
