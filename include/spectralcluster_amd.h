@@ -593,6 +593,17 @@ enum {
                                         sc_predict_batch_single_fallback: found single */
 };
 int sc_last_batch_routes(sc_handle h, int32_t* routes, int count);
+/* A per-handle permission (default off).  Off: the grouped and short routes of every batch call
+ * take cfg->kmeans_metric == SC_KMEANS_COSINE alone, and an utterance under any other metric runs
+ * as a single call inside the batch call (route 0), whose k-means is the single-workgroup kernel.
+ * On: every SC_KMEANS_* metric takes the routes cosine takes, in every batch call that ends in
+ * the grouped batch (plain, constrained, affinities, single, single_fallback / _naive, reduced /
+ * _naive, multi_stage); its k-means is the lockstep chain with the metric's distance in the
+ * assignment.  Labels then equal the single call's unless an assignment or the stop rule is a
+ * near tie (the two kernels add in different orders).  sc_predict_batch_autotune and the stream
+ * pool do not read it.  The caller sets it before a batch call and clears it afterwards; it
+ * changes nothing else.  SC_ERR_INVALID for a NULL handle. */
+int sc_set_batch_any_metric(sc_handle h, int on);
 
 /*
  * Size reduction before the spectral path (spectral_clusterer.py:170-199,
@@ -1298,6 +1309,17 @@ int sc_stage_kmeans_trace(sc_handle h, const double* e, int n, int k, int max_it
                           double* last_potentials, double* lloyd_centroids,
                           int64_t* first_labels, double* mean_dist, int mean_dist_cap,
                           int* iterations, double* centroids, int64_t* labels);
+/* sc_stage_kmeans_trace with custom_dist = SC_KMEANS_* (sc_stage_kmeans_trace is this call with
+ * SC_KMEANS_COSINE): _CHAIN runs the chain with the metric's distance in its assignment (what a
+ * grouped batch under sc_set_batch_any_metric runs), _SINGLE the single-workgroup kernel with it
+ * (what sc_stage_kmeans_metric runs for a metric other than cosine), _AUTO what
+ * sc_stage_kmeans_metric chooses.  Outputs as there. */
+int sc_stage_kmeans_trace_metric(sc_handle h, const double* e, int n, int k, int max_iter,
+                                 int form, int metric, int* form_run, double* col_means,
+                                 int* seeds, int* last_candidates, double* last_potentials,
+                                 double* lloyd_centroids, int64_t* first_labels,
+                                 double* mean_dist, int mean_dist_cap, int* iterations,
+                                 double* centroids, int64_t* labels);
 /* The grouped chain (one launch per phase for up to 16 independent problems, as the grouped
  * batch runs it) with the same outputs per member.  es: the members' (ns[z], ks[z]) row-major
  * inputs one after the other; ns[z] = 0 is an idle position.  Outputs are packed by position z:
@@ -1311,6 +1333,15 @@ int sc_stage_kmeans_trace_group(sc_handle h, const double* es, const int* ns, co
                                 double* lloyd_centroids, int64_t* first_labels,
                                 double* mean_dist, int mean_dist_cap, int* iterations,
                                 double* centroids, int64_t* labels);
+/* ... with custom_dist = SC_KMEANS_*, one metric for all members (a batch has one sc_config);
+ * outputs and packing as sc_stage_kmeans_trace_group, which is this call with SC_KMEANS_COSINE */
+int sc_stage_kmeans_trace_group_metric(sc_handle h, const double* es, const int* ns,
+                                       const int* ks, int count, int max_iter, int metric,
+                                       double* col_means, int* seeds, int* last_candidates,
+                                       double* last_potentials, double* lloyd_centroids,
+                                       int64_t* first_labels, double* mean_dist,
+                                       int mean_dist_cap, int* iterations, double* centroids,
+                                       int64_t* labels);
 /* custom_distance_kmeans.run_kmeans (:13-52) / CustomKMeans.predict (:85-141) on an (n, dim)
  * input, dim independent of k.  init_centroids (k, dim) row-major, or NULL = sklearn k-means++
  * seeds + one Lloyd step.  centroids_out (k, dim) may be NULL: the centroids of the last

@@ -579,6 +579,19 @@ PROTOTYPES = {
                                                    _c_int_p, _c_int_p, _c_double_p, _c_double_p,
                                                    _c_int64_p, _c_double_p, ctypes.c_int,
                                                    _c_int_p, _c_double_p, _c_int64_p]),
+    "sc_stage_kmeans_trace_metric": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int,
+                                                    ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_int, _c_int_p, _c_double_p, _c_int_p,
+                                                    _c_int_p, _c_double_p, _c_double_p,
+                                                    _c_int64_p, _c_double_p, ctypes.c_int,
+                                                    _c_int_p, _c_double_p, _c_int64_p]),
+    "sc_stage_kmeans_trace_group_metric": (ctypes.c_int, [_handle_t, _c_double_p, _c_int_p,
+                                                          _c_int_p, ctypes.c_int, ctypes.c_int,
+                                                          ctypes.c_int, _c_double_p, _c_int_p,
+                                                          _c_int_p, _c_double_p, _c_double_p,
+                                                          _c_int64_p, _c_double_p, ctypes.c_int,
+                                                          _c_int_p, _c_double_p, _c_int64_p]),
+    "sc_set_batch_any_metric": (ctypes.c_int, [_handle_t, ctypes.c_int]),
     "sc_stage_kmeans_general": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_double, _c_double_p,

@@ -806,7 +806,14 @@ int predict_batch_core(sc_handle h, const sc_array* xs, const int* ns, int d, in
   h->sweep_slot.clear();
   for (sc_handle lane : h->glanes) lane->sweep_slot.clear();
   const EigRequest rq = make_eig_request(cfg);
-  const bool cfg_ok = group > 1 && cfg->kmeans_metric == kKmeansCosine &&
+  // the chain's iteration kernel takes every device metric: cosine without being asked, the
+  // others with the handle's permission (sc_set_batch_any_metric); a code that names no metric
+  // goes to the single call, which says so
+  const bool metric_ok =
+      cfg->kmeans_metric == kKmeansCosine ||
+      (h->batch_any_metric && cfg->kmeans_metric > kKmeansCosine &&
+       cfg->kmeans_metric <= kKmeansCanberra);
+  const bool cfg_ok = group > 1 && metric_ok &&
                       !constraint_active(h, cfg, true) && !constraint_active(h, cfg, false);
   const bool covered = grouped_front_covers(cfg) && !bands;
   // what ran (sc_last_batch_routes): the routes below report into it while the call runs
@@ -1475,6 +1482,7 @@ int cluster_members(sc_handle lead, const int* ns, const sc_config* cfg, int64_t
     it.n = n;
     it.k = k;
     it.max_iter = cfg->max_iter;
+    it.metric = cfg->kmeans_metric;
     it.first_center = sc_uniform_choice(n, u);
     it.trials = trials;
     it.ws = kmeans_workspace(h);

@@ -152,6 +152,9 @@ struct sc_handle_s {
   // a lead of the running batch reports (the caller handle's last_routes)
   std::vector<int32_t> last_routes;
   int32_t* groutes = nullptr;
+  // sc_set_batch_any_metric: the grouped and short routes of a batch take every device metric
+  // (off: cosine alone, every other metric's utterances run as single calls)
+  bool batch_any_metric = false;
   std::vector<sc_handle_s*> glanes;  // the leads of lanes 1.. (batch_group.hip: ensure_lanes)
   class HostPool* gpool = nullptr;  // host workers of the group checks (host_pool.h)
   // grouped front: the stages before the eigensolver of a whole group as grouped launches on

@@ -490,17 +490,24 @@ struct DeviceSlabs {  // device allocations of one call, freed when it returns
 
 }  // namespace
 
-extern "C" int sc_stage_kmeans_trace(sc_handle h, const double* e, int n, int k, int max_iter,
-                                     int form, int* form_run, double* col_means, int* seeds,
-                                     int* last_candidates, double* last_potentials,
-                                     double* lloyd_centroids, int64_t* first_labels,
-                                     double* mean_dist, int mean_dist_cap, int* iterations,
-                                     double* centroids, int64_t* labels) {
+extern "C" int sc_set_batch_any_metric(sc_handle h, int on) {
+  if (!h) return SC_ERR_INVALID;
+  h->batch_any_metric = on != 0;
+  return SC_OK;
+}
+
+extern "C" int sc_stage_kmeans_trace_metric(sc_handle h, const double* e, int n, int k,
+                                            int max_iter, int form, int metric, int* form_run,
+                                            double* col_means, int* seeds, int* last_candidates,
+                                            double* last_potentials, double* lloyd_centroids,
+                                            int64_t* first_labels, double* mean_dist,
+                                            int mean_dist_cap, int* iterations, double* centroids,
+                                            int64_t* labels) {
   if (!h) return SC_ERR_INVALID;
   if (!e || !labels || n <= 0 || k <= 0) return fail(h, SC_ERR_INVALID, "bad k-means input");
   if (form < SC_KMEANS_FORM_AUTO || form > SC_KMEANS_FORM_SINGLE)
     return fail(h, SC_ERR_INVALID, "k-means form: auto, chain or single");
-  SC_TRY(check_kmeans_request(h, n, k, max_iter, kKmeansCosine, k > kMaxVectors ? 16 : 8));
+  SC_TRY(check_kmeans_request(h, n, k, max_iter, metric, k > kMaxVectors ? 16 : 8));
   SC_HIP(h, hipSetDevice(h->device));
   SC_TRY(ensure_kmeans(h, n, k));
   SC_TRY(kmeans_seed_state(h, n, k));
@@ -508,8 +515,10 @@ extern "C" int sc_stage_kmeans_trace(sc_handle h, const double* e, int n, int k,
   const bool chain_ok = kmeans_chain_supported(n, k, trials);
   if (form == SC_KMEANS_FORM_CHAIN && !chain_ok)
     return fail(h, SC_ERR_UNSUPPORTED, "the k-means chain does not take this (n, k)");
+  // (auto: what kmeans_on_device chooses -- the chain for cosine alone)
   const bool chain = form == SC_KMEANS_FORM_CHAIN ||
-                     (form == SC_KMEANS_FORM_AUTO && chain_ok && !sw::kmeans_single());
+                     (form == SC_KMEANS_FORM_AUTO && metric == kKmeansCosine && chain_ok &&
+                      !sw::kmeans_single());
   hipStream_t s = h->stream;
   SC_HIP(h, hipMemcpyAsync(h->Eio.p, e, (size_t)n * k * sizeof(double), hipMemcpyHostToDevice, s));
   const double* E = ptr<double>(h->Ek);
@@ -525,6 +534,7 @@ extern "C" int sc_stage_kmeans_trace(sc_handle h, const double* e, int n, int k,
     km.max_iter = max_iter;
     km.first_center = first;
     km.trials = trials;
+    km.metric = metric;
     km.ws = ws;
     KmTraceOut o;
     o.col_means = col_means;
@@ -539,7 +549,7 @@ extern "C" int sc_stage_kmeans_trace(sc_handle h, const double* e, int n, int k,
     o.centroids = centroids;
     o.labels = labels;
     return drive_chain_trace(h, s, &km, 1, &o, max_iter, [&](int b, int c) {
-      launch_kmeans_chain(s, E, lde, n, k, max_iter, first, trials, ws, b, c);
+      launch_kmeans_chain(s, E, lde, n, k, max_iter, first, trials, ws, b, c, metric);
     });
   }
   // the single-workgroup kernel: the small form writes its seeds through the optional pointer,
@@ -548,7 +558,7 @@ extern "C" int sc_stage_kmeans_trace(sc_handle h, const double* e, int n, int k,
   if (form_run) *form_run = big ? 3 : 2;
   if (!big) SC_TRY(grow(h, h->kbigw, (size_t)3 * kMaxVectors * sizeof(int)));
   SC_HIP(h, hipMemsetAsync(h->kinfo.p, 0, 8 * sizeof(int), s));
-  launch_kmeans(s, E, lde, n, k, max_iter, first, trials, ws, kKmeansCosine,
+  launch_kmeans(s, E, lde, n, k, max_iter, first, trials, ws, metric,
                 big ? nullptr : ptr<int>(h->kbigw));
   SC_TRY(check_last(h, "kmeans launch"));
   SC_HIP(h, hipStreamSynchronize(s));
@@ -561,13 +571,23 @@ extern "C" int sc_stage_kmeans_trace(sc_handle h, const double* e, int n, int k,
   return SC_OK;
 }
 
-extern "C" int sc_stage_kmeans_trace_group(sc_handle h, const double* es, const int* ns,
-                                           const int* ks, int count, int max_iter,
-                                           double* col_means, int* seeds, int* last_candidates,
-                                           double* last_potentials, double* lloyd_centroids,
-                                           int64_t* first_labels, double* mean_dist,
-                                           int mean_dist_cap, int* iterations, double* centroids,
-                                           int64_t* labels) {
+extern "C" int sc_stage_kmeans_trace(sc_handle h, const double* e, int n, int k, int max_iter,
+                                     int form, int* form_run, double* col_means, int* seeds,
+                                     int* last_candidates, double* last_potentials,
+                                     double* lloyd_centroids, int64_t* first_labels,
+                                     double* mean_dist, int mean_dist_cap, int* iterations,
+                                     double* centroids, int64_t* labels) {
+  return sc_stage_kmeans_trace_metric(h, e, n, k, max_iter, form, SC_KMEANS_COSINE, form_run,
+                                      col_means, seeds, last_candidates, last_potentials,
+                                      lloyd_centroids, first_labels, mean_dist, mean_dist_cap,
+                                      iterations, centroids, labels);
+}
+
+extern "C" int sc_stage_kmeans_trace_group_metric(
+    sc_handle h, const double* es, const int* ns, const int* ks, int count, int max_iter,
+    int metric, double* col_means, int* seeds, int* last_candidates, double* last_potentials,
+    double* lloyd_centroids, int64_t* first_labels, double* mean_dist, int mean_dist_cap,
+    int* iterations, double* centroids, int64_t* labels) {
   if (!h) return SC_ERR_INVALID;
   if (!es || !ns || !ks || !labels || count < 1 || count > kGroupMax)
     return fail(h, SC_ERR_INVALID, "bad grouped k-means input");
@@ -582,7 +602,7 @@ extern "C" int sc_stage_kmeans_trace_group(sc_handle h, const double* es, const 
     const int n = ns[z], k = ks[z];
     if (n < 0 || (n > 0 && k < 1)) return fail(h, SC_ERR_INVALID, "bad grouped k-means input");
     if (n == 0) continue;  // an idle position
-    SC_TRY(check_kmeans_request(h, n, k, max_iter, kKmeansCosine, 8));
+    SC_TRY(check_kmeans_request(h, n, k, max_iter, metric, 8));
     double u_first;
     int trials;
     std::vector<double> rnd;
@@ -619,6 +639,7 @@ extern "C" int sc_stage_kmeans_trace_group(sc_handle h, const double* es, const 
     it.max_iter = max_iter;
     it.first_center = sc_uniform_choice(n, u_first);
     it.trials = trials;
+    it.metric = metric;
     KmTraceOut& o = outs[z];
     if (col_means) o.col_means = col_means + (size_t)z * 32;
     if (seeds) o.seeds = seeds + (size_t)z * 32;
@@ -640,4 +661,17 @@ extern "C" int sc_stage_kmeans_trace_group(sc_handle h, const double* es, const 
   });
   hipStreamSynchronize(s);  // nothing of the slabs is in use when they are freed
   return rc;
+}
+
+extern "C" int sc_stage_kmeans_trace_group(sc_handle h, const double* es, const int* ns,
+                                           const int* ks, int count, int max_iter,
+                                           double* col_means, int* seeds, int* last_candidates,
+                                           double* last_potentials, double* lloyd_centroids,
+                                           int64_t* first_labels, double* mean_dist,
+                                           int mean_dist_cap, int* iterations, double* centroids,
+                                           int64_t* labels) {
+  return sc_stage_kmeans_trace_group_metric(h, es, ns, ks, count, max_iter, SC_KMEANS_COSINE,
+                                            col_means, seeds, last_candidates, last_potentials,
+                                            lloyd_centroids, first_labels, mean_dist,
+                                            mean_dist_cap, iterations, centroids, labels);
 }

@@ -19,11 +19,12 @@
 //                        km_trials  (potential of every candidate)
 //   km_lloyd             last winner; one Euclidean Lloyd assignment on the centred data +
 //                        per-cluster partial sums
-//   km_cosine(it)        test of iteration it - 1 (mean-distance stop rule, :131-133), centroid
+//   km_iter<M>(it)       test of iteration it - 1 (mean-distance stop rule, :131-133), centroid
 //                        update (Lloyd rule for it = 0, the `.any()`-on-indices rule after,
-//                        :136-140), cosine assignment it, labels, partial sums.  Iterations are
-//                        enqueued four at a time; a `done` word, read with the labels, says
-//                        whether more are needed.
+//                        :136-140), assignment it under metric M (kmeans_common.h; cosine is what
+//                        predict() runs, the others serve the grouped batch), labels, partial
+//                        sums.  Iterations are enqueued four at a time; a `done` word, read with
+//                        the labels, says whether more are needed.
 #include <algorithm>
 #include <cstring>
 #include <mutex>
@@ -448,13 +449,25 @@ __global__ __launch_bounds__(kKmT) void km_lloyd_g(const GroupOf<KmChain> g) {
   km_lloyd_body<KC>(a);
 }
 
-// Cosine iteration `it` of CustomKMeans.predict (:118-141); see the header.
-template <int KC>
-__device__ __forceinline__ void km_cosine_body(const KmChain& a, int it) {
+// pw_mean of m <= 128 elements is its leaf: stated here without the explicit stack of the
+// longer runs, which would cost every thread scratch memory (k <= 32 in this file)
+template <typename At>
+__device__ __forceinline__ double km_leaf_mean(At at, int m) {
+  return pw_leaf(at, 0, m) / (double)m;
+}
+
+// Iteration `it` of CustomKMeans.predict (:118-141) under the scipy metric M; see the header.
+// Only the assignment reads M: the stop rule, the centroid update and the partial sums are the
+// same statements for every metric.
+template <int KC, int M>
+__device__ __forceinline__ void km_iter_body(const KmChain& a, int it) {
+  constexpr bool kCorr = M == kKmeansCorrelation;
+  constexpr bool kNorms = M == kKmeansCosine || kCorr;  // the metrics that read |e| and |c|
   extern __shared__ __attribute__((aligned(16))) double dyn[];
   double* vals = dyn;
   int* labs = reinterpret_cast<int*>(vals + kKmT * KC);
   __shared__ double mean[KC], cent[KC * KC], cnorm[KC], tot[KC * KC + 2 * KC], sm[kKmW];
+  __shared__ double cmean[kCorr ? KC : 1];  // correlation: the centroids' own means
   __shared__ double zero[KC];
   __shared__ int seeds[KC];
   __shared__ int s_done;
@@ -512,28 +525,52 @@ __device__ __forceinline__ void km_cosine_body(const KmChain& a, int it) {
   __syncthreads();
   if (blockIdx.x == 0)
     for (int e = tid; e < k * k; e += kKmT) a.cent[it & 1][e] = cent[e];
-  if (tid < k) {
+  // ---- what the metric wants of a centroid and of a row before the pairs: cosine their norms,
+  // correlation the row means (numpy's order: pw_leaf) and the norms of the centred vectors, the
+  // others nothing (kmeans.hip states the same for its single workgroup)
+  if (kNorms && tid < k) {
     double s2 = 0.0;
-    for (int j = 0; j < k; ++j) s2 += cent[tid * k + j] * cent[tid * k + j];
+    if (kCorr) {
+      const double mc = km_leaf_mean([&](int j) { return cent[tid * k + j]; }, k);
+      for (int j = 0; j < k; ++j) s2 += (cent[tid * k + j] - mc) * (cent[tid * k + j] - mc);
+      cmean[tid] = mc;
+    } else {
+      for (int j = 0; j < k; ++j) s2 += cent[tid * k + j] * cent[tid * k + j];
+    }
     cnorm[tid] = sqrt(s2);
   }
-  __syncthreads();
-  // ---- cosine assignment: 1 - clip(e.c / (|e| |c|)); argmin takes the first minimum
-  double en = 0.0;
+  double en = 0.0, mx = 0.0;
+  if (kCorr) {
+    // (pw_leaf indexes its operand with a run-time j: the row goes through this thread's slot
+    //  of `vals`, which km_cluster_partials fills again below, and the registers stay registers)
 #pragma unroll
-  for (int j = 0; j < KC; ++j)
-    if (j < k) en += v[j] * v[j];
-  en = sqrt(en);
+    for (int j = 0; j < KC; ++j)
+      if (j < k) vals[tid * KC + j] = v[j];
+    mx = km_leaf_mean([&](int j) { return vals[tid * KC + j]; }, k);
+  }
+  if (kNorms) {
+#pragma unroll
+    for (int j = 0; j < KC; ++j)
+      if (j < k) {
+        const double x = kCorr ? v[j] - mx : v[j];
+        en += x * x;
+      }
+    en = sqrt(en);
+  }
+  __syncthreads();
+  // ---- assignment: argmin takes the first minimum, and a NaN distance never wins
   int best = 0;
   double bd = INFINITY;
   for (int c2 = 0; c2 < k; ++c2) {
-    double dot = 0.0;
+    double acc = 0.0, aux = 0.0;
+    const double cm = kCorr ? cmean[c2] : 0.0;
 #pragma unroll
     for (int j = 0; j < KC; ++j)
-      if (j < k) dot += v[j] * cent[c2 * k + j];
-    double cosine = dot / (en * cnorm[c2]);
-    if (fabs(cosine) > 1.0) cosine = copysign(1.0, cosine);
-    const double d = 1.0 - cosine;
+      if (j < k) {
+        const double x = kCorr ? v[j] - mx : v[j];
+        metric_accumulate(M, x, cent[c2 * k + j], cm, acc, aux);
+      }
+    const double d = metric_finish(M, acc, aux, en, kNorms ? cnorm[c2] : 0.0);
     if (d < bd) {
       bd = d;
       best = c2;
@@ -545,15 +582,16 @@ __device__ __forceinline__ void km_cosine_body(const KmChain& a, int it) {
   km_cluster_partials<KC>(a, v, zero, best, r, vals, labs,
                           a.pS[(it + 1) & 1] + (size_t)blockIdx.x * nsum);
 }
-template <int KC>
-__global__ __launch_bounds__(kKmT) void km_cosine(const KmChain a, int it) {
-  km_cosine_body<KC>(a, it);
+template <int KC, int M>
+__global__ __launch_bounds__(kKmT) void km_iter(const KmChain a, int it) {
+  km_iter_body<KC, M>(a, it);
 }
-template <int KC>
-__global__ __launch_bounds__(kKmT) void km_cosine_g(const GroupOf<KmChain> g, int it) {
+// (all active members of a grouped launch share the metric: a batch has one sc_config)
+template <int KC, int M>
+__global__ __launch_bounds__(kKmT) void km_iter_g(const GroupOf<KmChain> g, int it) {
   const KmChain& a = g.s[blockIdx.y];
   if ((int)blockIdx.x >= a.G) return;
-  km_cosine_body<KC>(a, it);
+  km_iter_body<KC, M>(a, it);
 }
 
 // ---------------------------------------------------------------- host side
@@ -622,19 +660,40 @@ KmChainView kmeans_chain_view(int n, const KmeansWorkspace& ws) {
   return v;
 }
 
+// iterations [it_begin, it_begin + it_count) under metric M, single and grouped form
+template <int KC, int M>
+static void km_enqueue_iters(hipStream_t s, const KmChain& a, int it_begin, int it_count) {
+  const size_t dyn = sizeof(double) * kKmT * KC + sizeof(int) * kKmT;
+  SC_OPT_IN_LDS((km_iter<KC, M>), 96 * 1024);
+  for (int it = it_begin; it < it_begin + it_count; ++it)
+    hipLaunchKernelGGL((km_iter<KC, M>), dim3(a.G), dim3(kKmT), dyn, s, a, it);
+}
+template <int KC, int M>
+static void km_enqueue_group_iters(hipStream_t s, const GroupOf<KmChain>& g, int count, int gmax,
+                                   int it_begin, int it_count) {
+  const size_t dyn = sizeof(double) * kKmT * KC + sizeof(int) * kKmT;
+  SC_OPT_IN_LDS((km_iter_g<KC, M>), 96 * 1024);
+  for (int it = it_begin; it < it_begin + it_count; ++it)
+    hipLaunchKernelGGL((km_iter_g<KC, M>), dim3(gmax, count), dim3(kKmT), dyn, s, g, it);
+}
+// the run-time metric (validated by the caller: check_kmeans_request) picks the instantiation
+#define SC_KM_BY_METRIC(metric, CALL)                                   \
+  switch (metric) {                                                     \
+    case kKmeansEuclidean: CALL(kKmeansEuclidean); break;               \
+    case kKmeansSqeuclidean: CALL(kKmeansSqeuclidean); break;           \
+    case kKmeansCityblock: CALL(kKmeansCityblock); break;               \
+    case kKmeansChebyshev: CALL(kKmeansChebyshev); break;               \
+    case kKmeansCorrelation: CALL(kKmeansCorrelation); break;           \
+    case kKmeansBraycurtis: CALL(kKmeansBraycurtis); break;             \
+    case kKmeansCanberra: CALL(kKmeansCanberra); break;                 \
+    default: CALL(kKmeansCosine); break;                                \
+  }
+
 template <int KC>
-static void km_enqueue(hipStream_t s, const KmChain& a, int it_begin, int it_count) {
+static void km_enqueue(hipStream_t s, const KmChain& a, int metric, int it_begin, int it_count) {
   const dim3 grid(a.G), block(kKmT);
   const size_t dyn = sizeof(double) * kKmT * KC + sizeof(int) * kKmT;
-  static std::once_flag once[16];
-  int dev = 0;
-  hipGetDevice(&dev);
-  std::call_once(once[dev & 15], [] {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(km_lloyd<KC>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(km_cosine<KC>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-  });
+  SC_OPT_IN_LDS(km_lloyd<KC>, 96 * 1024);
   if (it_begin == 0) {
     hipLaunchKernelGGL(km_colsum<KC>, grid, block, 0, s, a);
     hipLaunchKernelGGL(km_meanreduce, dim3(1), dim3(64), 0, s, a);
@@ -645,17 +704,17 @@ static void km_enqueue(hipStream_t s, const KmChain& a, int it_begin, int it_cou
     }
     hipLaunchKernelGGL(km_lloyd<KC>, grid, block, dyn, s, a);
   }
-  for (int it = it_begin; it < it_begin + it_count; ++it)
-    hipLaunchKernelGGL(km_cosine<KC>, grid, block, dyn, s, a, it);
+#define SC_KM_CALL(M) km_enqueue_iters<KC, M>(s, a, it_begin, it_count)
+  SC_KM_BY_METRIC(metric, SC_KM_CALL)
+#undef SC_KM_CALL
 }
 
 template <int KC>
 static void km_enqueue_group(hipStream_t s, const GroupOf<KmChain>& g, int count, int gmax,
-                             int kmax, int it_begin, int it_count) {
+                             int kmax, int metric, int it_begin, int it_count) {
   const dim3 grid(gmax, count), block(kKmT);
   const size_t dyn = sizeof(double) * kKmT * KC + sizeof(int) * kKmT;
   SC_OPT_IN_LDS(km_lloyd_g<KC>, 96 * 1024);
-  SC_OPT_IN_LDS(km_cosine_g<KC>, 96 * 1024);
   if (it_begin == 0) {
     hipLaunchKernelGGL(km_colsum_g<KC>, grid, block, 0, s, g);
     hipLaunchKernelGGL(km_meanreduce_g, dim3(1, count), dim3(64), 0, s, g);
@@ -666,43 +725,45 @@ static void km_enqueue_group(hipStream_t s, const GroupOf<KmChain>& g, int count
     }
     hipLaunchKernelGGL(km_lloyd_g<KC>, grid, block, dyn, s, g);
   }
-  for (int it = it_begin; it < it_begin + it_count; ++it)
-    hipLaunchKernelGGL(km_cosine_g<KC>, grid, block, dyn, s, g, it);
+#define SC_KM_CALL(M) km_enqueue_group_iters<KC, M>(s, g, count, gmax, it_begin, it_count)
+  SC_KM_BY_METRIC(metric, SC_KM_CALL)
+#undef SC_KM_CALL
 }
 
 // The same chain for up to kGroupMax independent problems per launch (items[z].n = 0: idle
 // member).  Every member runs exactly the arithmetic of launch_kmeans_chain: the register
 // tile width KC (taken from the largest k of the group) only sizes arrays, the sums run over
-// j < k in the same order.
+// j < k in the same order.  The metric is that of the first active member.
 void launch_kmeans_chain_group(hipStream_t s, const KmGroupItem* items, int count, int it_begin,
                                int it_count) {
   GroupOf<KmChain> g;
   memset(&g, 0, sizeof(g));
-  int gmax = 0, kmax = 0;
+  int gmax = 0, kmax = 0, metric = -1;
   for (int z = 0; z < count; ++z) {
     const KmGroupItem& it = items[z];
     if (it.n <= 0) continue;
     g.s[z] = km_args(it.ET, it.lde, it.n, it.k, it.max_iter, it.first_center, it.trials, it.ws);
     gmax = std::max(gmax, g.s[z].G);
     kmax = std::max(kmax, it.k);
+    if (metric < 0) metric = it.metric;
   }
   if (gmax == 0) return;
-  if (kmax <= 8) km_enqueue_group<8>(s, g, count, gmax, kmax, it_begin, it_count);
-  else if (kmax <= 16) km_enqueue_group<16>(s, g, count, gmax, kmax, it_begin, it_count);
-  else km_enqueue_group<32>(s, g, count, gmax, kmax, it_begin, it_count);
+  if (kmax <= 8) km_enqueue_group<8>(s, g, count, gmax, kmax, metric, it_begin, it_count);
+  else if (kmax <= 16) km_enqueue_group<16>(s, g, count, gmax, kmax, metric, it_begin, it_count);
+  else km_enqueue_group<32>(s, g, count, gmax, kmax, metric, it_begin, it_count);
 }
 
-// Enqueue the chain: seeding + Lloyd step (when it_begin == 0) and cosine iterations
-// [it_begin, it_begin + it_count).  The caller reads ws.info[8] (done) after a sync and calls
-// again with the next iteration range while it is 0.  (Iteration it tests the stop rule of
-// it - 1, so max_iter + 2 launches always suffice.)
+// Enqueue the chain: seeding + Lloyd step (when it_begin == 0) and the iterations
+// [it_begin, it_begin + it_count) under `metric`.  The caller reads ws.info[8] (done) after a
+// sync and calls again with the next iteration range while it is 0.  (Iteration it tests the
+// stop rule of it - 1, so max_iter + 2 launches always suffice.)
 void launch_kmeans_chain(hipStream_t s, const double* ET, int lde, int n, int k, int max_iter,
                          int first_center, int trials, const KmeansWorkspace& ws, int it_begin,
-                         int it_count) {
+                         int it_count, int metric) {
   const KmChain a = km_args(ET, lde, n, k, max_iter, first_center, trials, ws);
-  if (k <= 8) km_enqueue<8>(s, a, it_begin, it_count);
-  else if (k <= 16) km_enqueue<16>(s, a, it_begin, it_count);
-  else km_enqueue<32>(s, a, it_begin, it_count);
+  if (k <= 8) km_enqueue<8>(s, a, metric, it_begin, it_count);
+  else if (k <= 16) km_enqueue<16>(s, a, metric, it_begin, it_count);
+  else km_enqueue<32>(s, a, metric, it_begin, it_count);
 }
 
 }  // namespace sc

@@ -910,7 +910,19 @@ struct KmeansWorkspace {
   int* big_words = nullptr;   // ... and 3 k ints
 };
 size_t kmeans_big_workspace_doubles(int k);
-// k-means as a chain of short multi-workgroup kernels (kmeans_chain.hip), cosine metric
+// metric of the custom-distance loop (scipy cdist names)
+enum {
+  kKmeansCosine = 0,
+  kKmeansEuclidean = 1,
+  kKmeansSqeuclidean = 2,
+  kKmeansCityblock = 3,
+  kKmeansChebyshev = 4,
+  kKmeansCorrelation = 5,
+  kKmeansBraycurtis = 6,
+  kKmeansCanberra = 7
+};
+// k-means as a chain of short multi-workgroup kernels (kmeans_chain.hip); the iterations take
+// any of the metrics above
 size_t kmeans_chain_workspace_doubles(int n);
 bool kmeans_chain_supported(int n, int k, int trials);
 // slots of the chain's ring of per-pass mean distances (a power of two): pass p lives in slot
@@ -929,27 +941,17 @@ KmChainView kmeans_chain_view(int n, const KmeansWorkspace& ws);
 struct KmGroupItem {  // one member of a grouped chain launch; n = 0: idle
   const double* ET = nullptr;
   int lde = 0, n = 0, k = 0, max_iter = 0, first_center = 0, trials = 0;
+  int metric = kKmeansCosine;  // one per launch: the active members of a group share it
   KmeansWorkspace ws;
 };
 void launch_kmeans_chain_group(hipStream_t s, const KmGroupItem* items, int count, int it_begin,
                                int it_count);
 void launch_kmeans_chain(hipStream_t s, const double* ET, int lde, int n, int k, int max_iter,
                          int first_center, int trials, const KmeansWorkspace& ws, int it_begin,
-                         int it_count);
+                         int it_count, int metric = kKmeansCosine);
 void launch_row_renorm(hipStream_t s, double* ET, int lde, int n, int k);
 void launch_to_colmajor(hipStream_t s, const double* src, int n, int k, double* dst,
                         int ldt);
-// metric of the custom-distance loop (scipy cdist names)
-enum {
-  kKmeansCosine = 0,
-  kKmeansEuclidean = 1,
-  kKmeansSqeuclidean = 2,
-  kKmeansCityblock = 3,
-  kKmeansChebyshev = 4,
-  kKmeansCorrelation = 5,
-  kKmeansBraycurtis = 6,
-  kKmeansCanberra = 7
-};
 void launch_kmeans(hipStream_t s, const double* ET, int lde, int n, int k,
                    int max_iter, int first_center, int trials,
                    const KmeansWorkspace& ws, int metric = kKmeansCosine,

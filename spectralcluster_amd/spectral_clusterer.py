@@ -17,6 +17,7 @@ than the two vectors and callables are out of the device scope.  Those raise
 
 from __future__ import annotations
 
+import contextlib
 import copy
 import ctypes
 import typing
@@ -492,7 +493,9 @@ class SpectralClusterer:
 
   def predict_affinity_batch(self, affinities: typing.Sequence,
                              constraint_matrices: typing.Optional[typing.Sequence] = None,
-                             group: typing.Optional[int] = None) -> typing.List[np.ndarray]:
+                             group: typing.Optional[int] = None,
+                             *,
+                             batch_any_metric: bool = False) -> typing.List[np.ndarray]:
     """`[predict_affinity(a, c) for a, c in zip(affinities, constraint_matrices)]`; host and
     device matrices of any of the four dtypes may be mixed.
 
@@ -514,7 +517,11 @@ class SpectralClusterer:
     has returned.  Otherwise -- AutoTune, `min_clusters=1`, a user k-means function, a raw dense
     ndarray constraint, `group=1` -- the matrices run one after the other through
     predict_affinity (routes all 0).  `last_batch_routes` / `last_batch_diags` are filled as in
-    predict_batch."""
+    predict_batch.
+
+    `batch_any_metric` (keyword only, default False): predict_batch's flag.  With it a
+    `custom_dist` other than cosine that is on the device takes routes 1 and 2 as cosine does,
+    constrained or not; see there for how the labels then compare with predict_affinity's."""
     count = len(affinities)
     if constraint_matrices is None:
       constraint_matrices = [None] * count
@@ -532,9 +539,13 @@ class SpectralClusterer:
     self.last_batch_single = None
     constrained = self.constraint_options is not None and any(
         c is not None for c in constraint_matrices)
+    if (batch_any_metric and (group is None or int(group) > 1) and
+        self._metric_needs_permission()):
+      with self._any_metric_permission():
+        return self.predict_affinity_batch(affinities, constraint_matrices, group)
     try:  # (a metric that is not on the device raises in predict_affinity, as in predict())
-      metric = _lib.kmeans_metric_code(self.custom_dist)
-      metric_ok = not constrained or metric == _lib.KMEANS_METRICS["cosine"]
+      _lib.kmeans_metric_code(self.custom_dist)
+      metric_ok = not constrained or self._batch_kmeans_ok()
     except (ValueError, _lib.UnsupportedOnDeviceError):
       metric_ok = False
     if (count and metric_ok and self._library_batch_covers(affinity_input=True) and
@@ -624,7 +635,8 @@ class SpectralClusterer:
                     batch_fallback_condition: bool = False,
                     batch_naive_fallback: bool = False,
                     *,
-                    batch_multi_stage: bool = False
+                    batch_multi_stage: bool = False,
+                    batch_any_metric: bool = False
                     ) -> typing.List[np.ndarray]:
     """Independent predict() calls (the reference has no batch API: a batch is a
     Python loop).
@@ -799,10 +811,36 @@ class SpectralClusterer:
     is not below the tested rows - 1, a threshold pair `NaiveClusterer` rejects -- are raised,
     with the utterance's index, before anything is launched.  A batch of one utterance is
     covered.  Without the flag, and for every other clusterer, nothing changes.
+
+    `batch_any_metric` (keyword only; default False).  Wherever the paragraphs above say
+    "k-means is the cosine one", a `custom_dist` other than cosine keeps the batch out of the
+    grouped and short routes: a plain batch is still one library call, but every utterance runs
+    as a single call inside it (routes all 0), and the constrained, `min_clusters=1`, reduced,
+    fallback-condition, naive and multi-stage batches are the per-utterance loop.  With the
+    flag that clause reads "k-means is on the device" -- any `custom_dist` predict() runs there:
+    euclidean (minkowski), sqeuclidean, cityblock, chebyshev, correlation, braycurtis, canberra
+    -- in every one-call form above but the AutoTune one (`autotune_from_entry_state`), which
+    ignores the flag: `last_batch_routes` reports 1 and 2 as for cosine, and the k-means of a
+    group is the lockstep chain with the metric's distance in its assignment.  The call gives
+    the handle the permission (`sc_set_batch_any_metric`) before the library call and takes it
+    back afterwards, also when the call raises.  Results agree with predict() to the statement
+    made for the cosine grouped batch at the top.  In addition, for a metric other than cosine
+    predict()'s own k-means is another kernel (one workgroup) than the batch's chain, which adds
+    the mean distance and the centroid sums in another order: labels are equal unless an
+    assignment or the stop rule is a near tie, and that holds on the short route (n <= 128) as
+    well, whose eigenvectors are otherwise predict()'s own.  Without the flag, with "cosine",
+    or with `group=1` / `streams`, nothing changes; a metric that is not on the device raises
+    what predict() raises.
     """
     self.last_batch_single = None
     if autotune_from_entry_state and self.autotune is not None:
       return self._predict_batch_entry_state(utterances, constraint_matrices, streams, group)
+    if (batch_any_metric and streams is None and (group is None or int(group) > 1) and
+        self._metric_needs_permission()):
+      with self._any_metric_permission():
+        return self.predict_batch(
+            utterances, streams, group, constraint_matrices, autotune_from_entry_state,
+            batch_fallback_condition, batch_naive_fallback, batch_multi_stage=batch_multi_stage)
     if (batch_multi_stage and streams is None and (group is None or int(group) > 1) and
         constraint_matrices is None and self._multi_stage_batch_covers()):
       return self._predict_batch_multi_stage(utterances, 16 if group is None else int(group))
@@ -821,7 +859,7 @@ class SpectralClusterer:
         streams is None and (group is None or int(group) > 1) and
         self._library_batch_covers(single_check_covered=True)):
       try:
-        if _lib.kmeans_metric_code(self.custom_dist) == _lib.KMEANS_METRICS["cosine"]:
+        if self._batch_kmeans_ok():
           single_check = self._single_check_struct()
       except (ValueError, _lib.UnsupportedOnDeviceError):
         pass  # (predict() raises what it raises today)
@@ -835,10 +873,8 @@ class SpectralClusterer:
       if len(constraint_matrices) != len(utterances):
         raise ValueError("constraint_matrices must be as long as the batch")
       if self.constraint_options is not None:
-        try:  # (a metric that is not on the device raises in predict(), as it does today)
-          cosine = _lib.kmeans_metric_code(self.custom_dist) == _lib.KMEANS_METRICS["cosine"]
-        except (ValueError, _lib.UnsupportedOnDeviceError):
-          cosine = False
+        # (a metric that is not on the device raises in predict(), as it does today)
+        cosine = self._batch_kmeans_ok()
         if not (library_batch and cosine and streams is None and
                 (group is None or int(group) > 1) and
                 all(c is None or isinstance(c, _BATCH_CONSTRAINTS)
@@ -1099,6 +1135,41 @@ class SpectralClusterer:
             "single_cluster_affinity_diagonal_offset must be significantly smaller than "
             "affinity matrix dimension (utterance %d)" % i)
 
+  # predict_batch(..., batch_any_metric=True) while its library call runs
+  _batch_any_metric = False
+
+  def _batch_kmeans_ok(self) -> bool:
+    """Is this clusterer's k-means one the grouped batch runs?  The cosine one; under
+    `batch_any_metric` every metric that is on the device.  False for a metric that is not
+    (predict() raises what it raises today)."""
+    try:
+      metric = _lib.kmeans_metric_code(self.custom_dist)
+    except (ValueError, _lib.UnsupportedOnDeviceError):
+      return False
+    return metric == _lib.KMEANS_METRICS["cosine"] or self._batch_any_metric
+
+  def _metric_needs_permission(self) -> bool:
+    """A device metric other than cosine, outside a call that already holds the permission."""
+    if self._batch_any_metric:
+      return False
+    try:
+      return _lib.kmeans_metric_code(self.custom_dist) != _lib.KMEANS_METRICS["cosine"]
+    except (ValueError, _lib.UnsupportedOnDeviceError):
+      return False  # (predict() raises what it raises today)
+
+  @contextlib.contextmanager
+  def _any_metric_permission(self):
+    """The handle's `sc_set_batch_any_metric` permission for the body: set before, cleared
+    after, also when the body raises."""
+    handle = self._handle()
+    handle.check(handle.lib.sc_set_batch_any_metric(handle.raw, 1))
+    self._batch_any_metric = True
+    try:
+      yield
+    finally:
+      self._batch_any_metric = False
+      handle.lib.sc_set_batch_any_metric(handle.raw, 0)
+
   def _library_batch_covers(self, min_embeddings_met: bool = False,
                             single_check_covered: bool = False,
                             affinity_input: bool = False) -> bool:
@@ -1153,10 +1224,7 @@ class SpectralClusterer:
         self.affinity_function is not utils.compute_affinity_matrix or
         self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans):
       return False
-    try:
-      return _lib.kmeans_metric_code(self.custom_dist) == _lib.KMEANS_METRICS["cosine"]
-    except (ValueError, _lib.UnsupportedOnDeviceError):
-      return False  # (predict() raises what it raises today)
+    return self._batch_kmeans_ok()  # (a metric not on the device: predict() raises as today)
 
   def _single_fallback_call(self, handle: _lib.Handle, arrays: typing.Sequence[_lib.ScArray],
                             group: int, naive: bool = False) -> typing.List[np.ndarray]:
@@ -1238,10 +1306,7 @@ class SpectralClusterer:
       return False
     if streams is not None or (group is not None and int(group) <= 1):
       return False
-    try:
-      if _lib.kmeans_metric_code(self.custom_dist) != _lib.KMEANS_METRICS["cosine"]:
-        return False
-    except (ValueError, _lib.UnsupportedOnDeviceError):
+    if not self._batch_kmeans_ok():
       return False
     if (self.max_spectral_size is not None and
         self.max_spectral_size < options.spectral_min_embeddings):
@@ -1339,10 +1404,7 @@ class SpectralClusterer:
       return False  # (predict() says what is wrong with it)
     if not isinstance(options.fallback_clusterer_type, fallback_clusterer.FallbackClustererType):
       return False
-    try:
-      return _lib.kmeans_metric_code(self.custom_dist) == _lib.KMEANS_METRICS["cosine"]
-    except (ValueError, _lib.UnsupportedOnDeviceError):
-      return False  # (predict() raises what it raises today)
+    return self._batch_kmeans_ok()  # (a metric not on the device: predict() raises as today)
 
   def _multi_stage_struct(self) -> _lib.ScMultiStage:
     """The `sc_multi_stage` of this clusterer (`_multi_stage_batch_covers` holds); the
