@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 10
+#define SC_ABI_VERSION 11
 #define SC_MAX_OPS 16
 #define SC_MAX_BLUR_RADIUS 32
 #define SC_MAX_EIG 128 /* max eigenvalues reported in sc_diag */
@@ -1141,6 +1141,41 @@ int sc_stage_tridiag_values(sc_handle h, const double* d, const double* e, int n
                             double* values_desc);
 int sc_stage_td_backtransform(sc_handle h, const double* reflectors, const double* tau, int n,
                               double* z, int cols, int flags);
+/* Test entries of the general (non-symmetric) path (additions of ABI 11; no reference equivalent
+ * -- the reference calls np.linalg.eig): the device Hessenberg reduction alone, the Rayleigh-Ritz
+ * kernels on given data, and what a block Arnoldi solve left in the arena.  The first two own
+ * their device memory like the entries above: arena shapes (row pitch, the basis pitch of 136
+ * doubles for Q, Op Q and the coefficient vectors, vectors padded to a multiple of 16), quiet
+ * NaNs everywhere before the inputs are copied in.
+ *
+ * sc_stage_hessenberg: m (n, n) row-major, n >= 1, through the step the dense general route runs
+ *   between "matrix in scratch" and "packed matrix and tau on the host": the read-back of
+ *   max|a|, the power-of-two scaling of a matrix beyond 2^+-400, the reduction.  Outputs (each
+ *   may be NULL): packed (n, n) in LAPACK dgehd2 storage (H on and above the subdiagonal,
+ *   v_k[k+2 ..] below it in column k, v_k[k+1] = 1 implied), tau (n), scale (1 double): the
+ *   factor the eigenvalues of H get back, 1.0 when nothing was scaled.
+ * sc_stage_general_ritz: q, opq (n, m) row-major, yre, yim (m, cols), theta_re, theta_im (cols),
+ *   1 <= cols <= m <= 128.  q = NULL is the identity form of the dense solver (m = n <= 64).
+ *   Outputs (each may be NULL): vre, vim (n, cols) = Q Y after k_gen_ritz; resid (cols) =
+ *   ||Op Q y - theta Q y||_2, 32 pairs per launch as the solver runs them (needs q, opq, theta);
+ *   pre, pim (n, cols) the vectors after k_gen_phase and e (n, cols) the real-part copy it
+ *   writes.  codes (8 ints: -1 noise, else 2 * column + part, part 1 = imaginary) with w (n, 8):
+ *   the restart block k_gen_gather builds from the phased vectors with `seed`; both or neither.
+ * sc_stage_arnoldi_state: read-only, like sc_stage_krylov_state.  After a solve that ended in
+ *   SC_EIG_PATH_BLOCK_ARNOLDI: info (8 ints) = [0] m, [1] n, [2] 1 for the wide form, [3] restart
+ *   cycles, [4] block passes, [5] 1 when the operator had its sign turned; q, opq (n, m)
+ *   row-major, hm (m, m) the projected matrix of the final check, cl, cr, p (n each) the scalings
+ *   of Op x = p .* x + cl .* (M (cr .* x)) as the solve used them.  Any of them but info may be
+ *   NULL.  SC_ERR_INVALID after any other kind of solve. */
+int sc_stage_hessenberg(sc_handle h, const double* m, int n, double* packed, double* tau,
+                        double* scale);
+int sc_stage_general_ritz(sc_handle h, const double* q, const double* opq, int n, int m,
+                          const double* yre, const double* yim, const double* theta_re,
+                          const double* theta_im, int cols, double* vre, double* vim,
+                          double* resid, double* pre, double* pim, double* e,
+                          const int32_t* codes, uint64_t seed, double* w);
+int sc_stage_arnoldi_state(sc_handle h, int32_t* info, double* q, double* opq, double* hm,
+                           double* cl, double* cr, double* p);
 /* laplacian.compute_laplacian (laplacian.py:24-60) */
 int sc_stage_laplacian(sc_handle h, int laplacian_type, const double* in, int n,
                        double* out);

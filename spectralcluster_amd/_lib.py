@@ -53,7 +53,7 @@ class EigenSolverNotConverged(RuntimeError):
   """The block-Lanczos eigensolver did not reach its tolerance."""
 
 
-SC_ABI_VERSION = 10
+SC_ABI_VERSION = 11
 
 
 class ScConfig(ctypes.Structure):
@@ -285,6 +285,17 @@ PROTOTYPES = {
     "sc_stage_td_backtransform": (ctypes.c_int, [_handle_t, _c_double_p, _c_double_p,
                                                  ctypes.c_int, _c_double_p, ctypes.c_int,
                                                  ctypes.c_int]),
+    "sc_stage_hessenberg": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int, _c_double_p,
+                                           _c_double_p, _c_double_p]),
+    "sc_stage_general_ritz": (ctypes.c_int, [_handle_t, _c_double_p, _c_double_p, ctypes.c_int,
+                                             ctypes.c_int, _c_double_p, _c_double_p, _c_double_p,
+                                             _c_double_p, ctypes.c_int, _c_double_p, _c_double_p,
+                                             _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                             ctypes.POINTER(ctypes.c_int32), ctypes.c_uint64,
+                                             _c_double_p]),
+    "sc_stage_arnoldi_state": (ctypes.c_int, [_handle_t, ctypes.POINTER(ctypes.c_int32),
+                                              _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                              _c_double_p, _c_double_p]),
     "sc_config_default": (ctypes.c_int, [ctypes.POINTER(ScConfig)]),
     "sc_gaussian_weights": (ctypes.c_int, [ctypes.c_double,
                                            ctypes.POINTER(ctypes.c_int32),

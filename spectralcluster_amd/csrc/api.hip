@@ -25,6 +25,7 @@
 // ------------------------------------------------------------------------------
 int ensure_matrices(sc_handle h, int n, int d, bool affinity_copy) {
   h->krylov_m = 0;  // a new problem: the last solve's state is no longer reported
+  h->arnoldi_m = 0;
   const size_t ldn = matrix_ld(n);
   const size_t nn = (size_t)n * ldn * sizeof(double);
   if (affinity_copy) SC_TRY(grow(h, h->A0, nn));
@@ -88,7 +89,7 @@ int ensure_tilemap(sc_handle h, int n) {
 
 int ensure_eig(sc_handle h, int n) {
   const size_t nq = (size_t)n * kLdq * sizeof(double);
-  if (h->Q.bytes < nq) h->krylov_m = 0;  // (the basis is about to be reallocated)
+  if (h->Q.bytes < nq) h->krylov_m = h->arnoldi_m = 0;  // (the basis is about to be reallocated)
   SC_TRY(grow(h, h->Q, nq));
   SC_TRY(grow(h, h->Q2, nq));
   SC_TRY(grow(h, h->Vs, (size_t)n * kEigBlock * sizeof(double)));

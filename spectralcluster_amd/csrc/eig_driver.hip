@@ -485,6 +485,7 @@ int sym_topk(sc_handle h, const FrontResult& op_in, int n, const EigRequest& rq_
              sc_diag* diag, EigDecision* out_dc, std::vector<double>* out_w) {
   hipStream_t s = h->stream;
   h->krylov_m = 0;  // (sc_stage_krylov_state: nothing to report until this solve leaves it)
+  h->arnoldi_m = 0;  // (sc_stage_arnoldi_state: this solve reuses Q / Q2 / T)
   SC_TRY(ensure_eig(h, n));
   FrontResult op = op_in;  // (free_materialize turns it into the explicit operator)
   const int ld = op.ld;
@@ -1488,6 +1489,34 @@ int dense_topk_group(sc_handle lead, GroupEigMember* mem, int count) {
 //   host    QR iteration for the n eigenvalues, inverse iteration + back-transform for the
 //           leading max(n_clusters, min_clusters) eigenvectors (host_eig.cpp)
 //   device  dgeev's norm / phase convention and the real parts (k_gen_phase)
+// The device half of that route, from "the matrix is in B" to "packed matrix and tau ready to
+// copy out" (gen_dense_large below and the test entry sc_stage_hessenberg, stage_dense.hip).
+// A badly scaled matrix (max|a| beyond 2^+-400) is brought to [1, 2) by a power of two first:
+// the reflectors square their columns (hessenberg.hip); *eig_scale is the factor the eigenvalues
+// get back (1 when nothing was scaled).  B (n x n, ld) is reduced in place to dgehd2 storage;
+// absmax: 1 double of device scratch, tau: n doubles, vwork: 2 n doubles.  Synchronises once.
+int hessenberg_reduce_scaled(sc_handle h, double* B, int ld, int n, double* absmax, double* tau,
+                             double* vwork, double* eig_scale) {
+  hipStream_t s = h->stream;
+  *eig_scale = 1.0;
+  SC_HIP(h, hipMemsetAsync(absmax, 0, sizeof(double), s));
+  launch_free_absmax(s, B, n, ld, absmax);
+  double amax = 0.0;
+  SC_HIP(h, hipMemcpyAsync(&amax, absmax, sizeof(double), hipMemcpyDeviceToHost, s));
+  SC_HIP(h, hipStreamSynchronize(s));
+  int e = 0;
+  if (amax > 0.0 && std::isfinite(amax)) {
+    std::frexp(amax, &e);  // amax = f * 2^e, f in [0.5, 1)
+    if (e > 400 || e < -400) {
+      *eig_scale = std::ldexp(1.0, e - 1);  // amax / eig_scale in [1, 2)
+      launch_scale_matrix(s, B, ld, n, std::ldexp(1.0, 1 - e));
+    }
+  }
+  SC_HIP(h, hipMemsetAsync(tau, 0, (size_t)n * sizeof(double), s));
+  launch_hessenberg(s, B, ld, n, tau, vwork);
+  return check_last(h, "Hessenberg reduction launch");
+}
+
 constexpr int kGenDenseLimit = 16384;  // (the host QR iteration is ~10 n^3 flops: minutes beyond)
 static int gen_dense_large(sc_handle h, const double* M, int ld, int n, int laplacian_type,
                            const EigRequest& rq, sc_diag* diag, EigDecision* out_dc,
@@ -1495,6 +1524,7 @@ static int gen_dense_large(sc_handle h, const double* M, int ld, int n, int lapl
   hipStream_t s = h->stream;
   if (scratch == nullptr || scratch == M)
     return fail(h, SC_ERR_UNSUPPORTED, "no scratch matrix for the dense general eigen path");
+  h->arnoldi_m = 0;  // (a far-end solve may have come first: the state reported is the main solve's)
   if (n > kGenDenseLimit)
     return fail(h, SC_ERR_UNSUPPORTED,
                 "the dense general eigen path (every eigenvalue of a matrix that is not "
@@ -1510,28 +1540,10 @@ static int gen_dense_large(sc_handle h, const double* M, int ld, int n, int lapl
     SC_HIP(h, hipMemcpyAsync(scratch, M, (size_t)n * ld * sizeof(double), hipMemcpyDeviceToDevice, s));
   }
   const double t_begin = sw::eig_trace() ? now_us() : 0.0;
-  // a badly scaled matrix (max|a| beyond 2^+-400) is brought to [1, 2) by a power of two first:
-  // the reflectors square their columns (hessenberg.hip); the eigenvalues get the factor back
   double eig_scale = 1.0;
-  {
-    SC_TRY(grow(h, h->fscal, 4 * sizeof(double)));
-    SC_HIP(h, hipMemsetAsync(h->fscal.p, 0, sizeof(double), s));
-    launch_free_absmax(s, scratch, n, ld, ptr<double>(h->fscal));
-    double amax = 0.0;
-    SC_HIP(h, hipMemcpyAsync(&amax, h->fscal.p, sizeof(double), hipMemcpyDeviceToHost, s));
-    SC_HIP(h, hipStreamSynchronize(s));
-    int e = 0;
-    if (amax > 0.0 && std::isfinite(amax)) {
-      std::frexp(amax, &e);  // amax = f * 2^e, f in [0.5, 1)
-      if (e > 400 || e < -400) {
-        eig_scale = std::ldexp(1.0, e - 1);  // amax / eig_scale in [1, 2)
-        launch_scale_matrix(s, scratch, ld, n, std::ldexp(1.0, 1 - e));
-      }
-    }
-  }
-  SC_HIP(h, hipMemsetAsync(h->td_tau.p, 0, (size_t)n * sizeof(double), s));
-  launch_hessenberg(s, scratch, ld, n, ptr<double>(h->td_tau), ptr<double>(h->td_work));
-  SC_TRY(check_last(h, "Hessenberg reduction launch"));
+  SC_TRY(grow(h, h->fscal, 4 * sizeof(double)));
+  SC_TRY(hessenberg_reduce_scaled(h, scratch, ld, n, ptr<double>(h->fscal), ptr<double>(h->td_tau),
+                                  ptr<double>(h->td_work), &eig_scale));
   std::vector<double> packed((size_t)n * ld), tau(n);
   SC_HIP(h, hipMemcpyAsync(packed.data(), scratch, packed.size() * sizeof(double),
                            hipMemcpyDeviceToHost, s));
@@ -1610,10 +1622,22 @@ static int gen_dense_large(sc_handle h, const double* M, int ld, int n, int lapl
   return SC_OK;
 }
 
+// Explicit residuals of the Ritz pairs [0, count) of a basis of m vectors (Q, OpQ, Yre, Yim at
+// pitch kLdq): the residual kernel takes 32 pairs per launch (gen_topk below and the test entry
+// sc_stage_general_ritz, stage_dense.hip).  partial: gen_residual_blocks(n) * 32 doubles.
+void gen_residuals(hipStream_t s, const double* Q, const double* OpQ, int m, int n,
+                   const double* Yre, const double* Yim, const double* theta_re,
+                   const double* theta_im, int count, double* partial, double* resid) {
+  for (int c0 = 0; c0 < count; c0 += 32)
+    launch_gen_residual(s, Q, OpQ, kLdq, m, n, Yre + c0, Yim + c0, kLdq, theta_re + c0,
+                        theta_im + c0, std::min(32, count - c0), partial, resid + c0);
+}
+
 int gen_topk(sc_handle h, const double* M, int ld, int n, int laplacian_type,
                     const EigRequest& rq_in, sc_diag* diag, EigDecision* out_dc,
                     std::vector<double>* out_w, double* scratch) {
   h->krylov_m = 0;  // (sc_stage_krylov_state: the Arnoldi chain reuses Q / Q2)
+  h->arnoldi_m = 0;  // (sc_stage_arnoldi_state: nothing to report until this solve leaves it)
   EigRequest rq = rq_in;
   hipStream_t s = h->stream;
   SC_TRY(ensure_eig(h, n));
@@ -1711,6 +1735,7 @@ int gen_topk(sc_handle h, const double* M, int ld, int n, int laplacian_type,
       sc_diag fdiag;
       memset(&fdiag, 0, sizeof(fdiag));
       const int rc_far = gen_topk(h, M, ld, n, laplacian_type, fr, &fdiag, &fdc, &fw, scratch);
+      h->arnoldi_m = 0;  // (the state reported is the main solve's)
       if (rc_far == SC_OK && !fw.empty()) {
         rq.have_far = 1;
         rq.far_value = fw[0];
@@ -1835,10 +1860,8 @@ int gen_topk(sc_handle h, const double* M, int ld, int n, int laplacian_type,
         SC_HIP(h, hipMemsetAsync(info_d, 0, 2 * sizeof(int), s));
         SC_HIP(h, hipStreamSynchronize(s));  // (th / thi / hy are reused below)
         const int c1 = std::min(m, kMaxCheck);
-        for (int c0 = 0; c0 < c1; c0 += 32)  // (the residual kernel takes 32 pairs per launch)
-          launch_gen_residual(s, Q, OpQ, kLdq, m, n, Yre + c0, Yim + c0, kLdq, theta_d + c0,
-                              thetai_d + c0, std::min(32, c1 - c0), ptr<double>(h->gpart),
-                              resid_d + c0);
+        gen_residuals(s, Q, OpQ, m, n, Yre, Yim, theta_d, thetai_d, c1, ptr<double>(h->gpart),
+                      resid_d);
         if (far_end && m - 1 >= c1)
           launch_gen_residual(s, Q, OpQ, kLdq, m, n, Yre + (m - 1), Yim + (m - 1), kLdq,
                               theta_d + (m - 1), thetai_d + (m - 1), 1, ptr<double>(h->gpart),
@@ -1930,7 +1953,20 @@ int gen_topk(sc_handle h, const double* M, int ld, int n, int laplacian_type,
           codes.push_back(2 * i);
           codes.push_back(2 * i + 1);
         }
-        if ((int)codes.size() > max_cols) codes.resize(max_cols);
+        if ((int)codes.size() > max_cols) {
+          // Keep whole pairs.  A cut between the real and the imaginary part of a complex Ritz
+          // vector leaves a column whose image under Op is not in the new basis, exactly like a
+          // random pad: the cut moves down by whole blocks until it splits no pair (a block
+          // boundary that does not exist only when every one of them splits a pair: then the
+          // real part goes too and the pad below fills the block).
+          auto splits = [&](int len) {
+            return codes[len - 1] >= 0 && (codes[len - 1] & 1) == 0 &&
+                   codes[len] == codes[len - 1] + 1;
+          };
+          int keep = max_cols;
+          while (keep > 0 && splits(keep)) keep -= kEigBlock;
+          codes.resize(keep > 0 ? keep : max_cols - 1);
+        }
         while (codes.size() % kEigBlock) codes.push_back(-1);  // last resort (tiny bases)
         for (int j = 0; j < kEigBlock; ++j) codes.push_back(2 * (kStash + j));
         start_blocks.clear();
@@ -1947,6 +1983,14 @@ int gen_topk(sc_handle h, const double* M, int ld, int n, int laplacian_type,
     SC_TRY(check_last(h, "ritz vector launch"));
     h->n_vec = cols;
     if (diag) diag->eig_path = SC_EIG_PATH_BLOCK_ARNOLDI;
+    // what sc_stage_arnoldi_state reports: values this function already has (Q, Q2 and T are as
+    // the final check read them: the Ritz vector kernels above write Vre / Vim / E only)
+    h->arnoldi_m = m;
+    h->arnoldi_n = n;
+    h->arnoldi_cycles = cycles;
+    h->arnoldi_passes = passes;
+    h->arnoldi_wide = wide;
+    h->arnoldi_negate = rq.negate != 0;
   }
   if (out_w) {
     out_w->resize(dc.kw);

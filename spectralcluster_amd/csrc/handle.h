@@ -193,6 +193,11 @@ struct sc_handle_s {
   // n, restart cycles, block steps enqueued beyond the basis (run-ahead), two-product operator
   int krylov_m = 0, krylov_n = 0, krylov_cycles = 0, krylov_ahead = 0;
   bool krylov_free = false;
+  // The same for the last block Arnoldi solve of gen_topk (Q, Q2 = Op Q, T = H, the scaling
+  // vectors), for sc_stage_arnoldi_state: basis size at exit (0: no such solve), its n, restart
+  // cycles and block passes of that solve alone, the wide form, the operator with its sign turned
+  int arnoldi_m = 0, arnoldi_n = 0, arnoldi_cycles = 0, arnoldi_passes = 0;
+  bool arnoldi_wide = false, arnoldi_negate = false;
   // What the last front on this handle launched, for sc_stage_front: the blur kernel (and the
   // rows per wave of the streaming one)
   BlurLaunch last_blur;
@@ -488,6 +493,14 @@ int sym_topk(sc_handle h, const FrontResult& op, int n, const EigRequest& rq, sc
 int gen_topk(sc_handle h, const double* M, int ld, int n, int laplacian_type,
              const EigRequest& rq, sc_diag* diag, EigDecision* out_dc,
              std::vector<double>* out_w, double* scratch);
+// two steps of the general path that its test entries (stage_dense.hip) run as the solver does:
+// power-of-two scaling + Hessenberg reduction of B in place, and the explicit residuals of the
+// first `count` Ritz pairs, 32 per launch (eig_driver.hip)
+int hessenberg_reduce_scaled(sc_handle h, double* B, int ld, int n, double* absmax, double* tau,
+                             double* vwork, double* eig_scale);
+void gen_residuals(hipStream_t s, const double* Q, const double* OpQ, int m, int n,
+                   const double* Yre, const double* Yim, const double* theta_re,
+                   const double* theta_im, int count, double* partial, double* resid);
 
 // matrix-free Diffuse (free_api.hip)
 // does this call take the matrix-free route for a Diffuse whose output only feeds

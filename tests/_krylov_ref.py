@@ -1,5 +1,8 @@
 """The block Lanczos chain of csrc/eig.hip restated in NumPy fp64, the a-priori bounds its
-kernels are held to, and `longdouble` evaluators of the quantities the bounds are about.
+kernels are held to, and `longdouble` evaluators of the quantities the bounds are about; and the
+same for the block Arnoldi chain of the general path (ArnoldiChain, ArnoldiInvariants: separate
+left and right scalings, a full non-symmetric H, the same CGS-2 + CholQR-2 steps and start block
+generator; used by test_gpu_general_kernels.py).
 
 Shared by tests/test_krylov_reference_host.py (CPU: the restated chain itself stays within
 every bound with a factor 8 to spare, so the bounds are honest) and by the GPU tests
@@ -253,6 +256,147 @@ class Invariants:
   def figures(self):
     return {"orth": self.orth, "proj": float(np.max(self.proj_err)),
             "krylov": float(np.max(self.krylov_err))}
+
+
+# ------------------------------------------------------------------------------ block Arnoldi
+# The general path's chain (eig_driver.hip, gen_topk), a non-symmetric variant of the one above:
+# the operator has separate left and right scalings, Op x = p .* x + cl .* (M (cr .* x))
+# (Operator(m, c=cl, p=p, s=cr)); a block is orthogonalised by the host-driven links
+# (orthonormalize: CGS twice, CholQR twice) and NOT recorded in T; the products Op Q are kept
+# (Q2) and the projected matrix is formed explicitly and in full, H = Q^T (Op Q), at a check.
+#   start block   W = hash_uniform(ARNOLDI_SEED) | CholQR | CholQR -> Q[:, 0:8]
+#   block step    W = Op Q[:, m-8:m] (kept as OpQ[:, m-8:m]) | CGS | CGS | CholQR | CholQR
+ARNOLDI_SEED = 0x9E3779B97F4A7C15
+GEN_MAX = 64             # kGenMax: basis cap of the narrow form
+
+
+def arnoldi_cap(n, wide=False):
+  return min(BASIS_CAP if wide else GEN_MAX, ((n - B) // B) * B)
+
+
+class ArnoldiChain:
+  """State of the restated chain without restarts: q, opq (n, m), m a multiple of 8."""
+
+  def __init__(self, op, seed=ARNOLDI_SEED):
+    self.op = op
+    self.n = op.n
+    self.q = np.zeros((self.n, BASIS_CAP + B))
+    self.opq = np.zeros((self.n, BASIS_CAP + B))
+    self.m = 0
+    self.seed = seed
+
+  def step(self):
+    m = self.m
+    w = start_block(self.n, self.seed) if m == 0 else self.opq[:, m - B:m].copy()
+    q = self.q[:, :m]
+    if m > 0:
+      for _ in range(2):
+        w = w - q @ _rows_product(q, w)
+    w = w @ _chol_inverse(_rows_product(w, w))
+    w = w @ _chol_inverse(_rows_product(w, w))
+    self.q[:, m:m + B] = w
+    self.opq[:, m:m + B] = self.op.apply(w)
+    self.m = m + B
+
+  def run(self, m_final):
+    while self.m < m_final:
+      self.step()
+    return self
+
+  def state(self):
+    """q, opq (n, m) and H = Q^T (Op Q), column block after column block."""
+    m = self.m
+    q, opq = self.q[:, :m].copy(), self.opq[:, :m].copy()
+    return q, opq, _rows_product(q, opq)
+
+
+class ArnoldiInvariants:
+  """The measured quantities (longdouble) and their derived bounds for a basis Q (n, m), the
+  stored products OpQ (n, m) and the projected matrix H (m, m) of the operator `op`:
+    orthonormality   max |Q^T Q - I| <= 4 gamma_{n+m}                         (the Lanczos bar)
+    operator         |OpQ - Op Q| <= gamma_{n+4} (|p||Q| + |cl| (|M| (|cr||Q|)))
+    projection       |H - Q^T OpQ| <= 2 gamma_{n+m+8} |Q|^T |OpQ| + m orth max|H|
+    Arnoldi property |(I - Q Q^T) Op Q[:, 0:m-8]| <= operator bound + m orth max|H|
+                     (+ 16 x the reference chain's figure, + 1e-12 m max|H| after a restart:
+                     arnoldi_ratio)"""
+
+  def __init__(self, op, q, opq, h):
+    n, m = q.shape
+    self.n, self.m = n, m
+    ql = q.astype(LD)
+    self.orth = float(np.max(np.abs(ql.T @ ql - np.eye(m, dtype=LD))))
+    self.orth_bound = 4.0 * gamma(n + m)
+    exact = op.apply_ld(q)
+    self.op_err = np.abs(opq.astype(LD) - exact).astype(np.float64)
+    self.op_bound = op.bound(q)
+    self.hmax = float(np.max(np.abs(h)))
+    self.slack = m * self.orth * self.hmax
+    self.proj_err = np.abs(h.astype(LD) - ql.T @ opq.astype(LD)).astype(np.float64)
+    self.proj_bound = 2.0 * gamma(n + m + 8) * (np.abs(q).T @ np.abs(opq)) + self.slack
+    k = m - B
+    proj = ql.T @ exact
+    self.arnoldi_err = np.abs(exact[:, :k] - ql @ proj[:, :k]).astype(np.float64)
+    self.arnoldi_bound = self.op_bound[:, :k] + self.slack
+
+  def op_ratio(self):
+    return float(np.max(self.op_err / self.op_bound))
+
+  def proj_ratio(self):
+    return float(np.max(self.proj_err / self.proj_bound))
+
+  def arnoldi_figure(self):
+    return float(np.max(self.arnoldi_err)) if self.arnoldi_err.size else 0.0
+
+  def arnoldi_ratio(self, ref_figure=0.0, restarted=False):
+    if not self.arnoldi_err.size:
+      return 0.0
+    bound = self.arnoldi_bound + 16.0 * ref_figure
+    if restarted:  # the kept Ritz vectors Q Y: Y from the host solver, held to 1e-12 m ||H||
+      bound = bound + 1e-12 * self.m * self.hmax
+    return float(np.max(self.arnoldi_err / bound))
+
+
+def general_scaling_vectors(deg, laplacian_type):
+  """k_scaling_general (eig_general.hip): cl, cr, p of Op = M (None / Affinity), -(D - M)
+  (Unnormalized), -D'^-1 (D - M) (RandomWalk), -D'^-1/2 (D - M) D'^-1/2 (GraphCut)."""
+  one, zero = np.ones_like(deg), np.zeros_like(deg)
+  if laplacian_type in (0, 1):
+    return one, one, zero
+  if laplacian_type == 2:
+    return one, one, -deg
+  if laplacian_type == 3:
+    g = 1.0 / (deg + 1e-10)
+    return g, one, -(g * deg)
+  if laplacian_type == 4:
+    h = 1.0 / (np.sqrt(deg) + 1e-10)
+    return h, h, -((h * deg) * h)
+  raise ValueError("laplacian_type")
+
+
+def separated_matrix(n):
+  """Three eigenvalues near 5, 4, 3 over a non-symmetric bulk of radius 0.03: a block Krylov
+  space of a few blocks holds them to 1e-10 -- a solve without a restart."""
+  rng = np.random.default_rng(6000 + n)
+  m = 0.03 * rng.standard_normal((n, n)) / np.sqrt(n)
+  m[np.arange(3), np.arange(3)] += np.array([5.0, 4.0, 3.0])
+  return m
+
+
+def nonnormal_cluster(n, seed=0):
+  """A non-normal matrix with a tight leading cluster: eigenvalues 2 - 1e-2 k (k < 12) over a
+  bulk in the unit disc (2 x 2 rotation blocks: complex pairs), in a basis of condition ~30."""
+  rng = np.random.default_rng(7000 + n + seed)
+  d = np.zeros((n, n))
+  k = 12
+  d[np.arange(k), np.arange(k)] = 2.0 - 1e-2 * np.arange(k)
+  for i in range(k, n - 1, 2):
+    r, phi = rng.uniform(0.2, 0.95), rng.uniform(0.1, np.pi - 0.1)
+    d[i:i + 2, i:i + 2] = r * np.array([[np.cos(phi), -np.sin(phi)], [np.sin(phi), np.cos(phi)]])
+  if (n - k) % 2:
+    d[n - 1, n - 1] = -0.5
+  x, _ = np.linalg.qr(rng.standard_normal((n, n)))
+  s = x * np.logspace(0, 1.5, n)[rng.permutation(n)]
+  return np.ascontiguousarray(s @ d @ np.linalg.inv(s))
 
 
 # ------------------------------------------------------------------------------ scaling vectors

@@ -128,7 +128,7 @@ def test_new_symbols_are_declared_prototyped_exported_and_listed():
     assert hasattr(lib, name), name
     assert "`%s`" % name in integration, name
   assert declared == set(_lib.PROTOTYPES), declared ^ set(_lib.PROTOTYPES)
-  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 10  # functions were only added
+  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 11  # functions were only added
 
 
 def test_entry_points_reject_a_null_handle():

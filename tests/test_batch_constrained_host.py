@@ -29,10 +29,10 @@ def test_new_symbols_are_declared_mirrored_and_exported():
 
 
 def test_abi_version_is_9():
-  assert _lib.SC_ABI_VERSION == 10
-  assert _lib.load().sc_abi_version() == 10
+  assert _lib.SC_ABI_VERSION == 11
+  assert _lib.load().sc_abi_version() == 11
   text = open(HEADER).read()
-  assert re.search(r"#define\s+SC_ABI_VERSION\s+10\b", text)
+  assert re.search(r"#define\s+SC_ABI_VERSION\s+11\b", text)
 
 
 def test_null_handle_is_invalid():

@@ -28,7 +28,7 @@ def test_new_symbols_are_declared_prototyped_exported_and_listed():
     assert name in _lib.PROTOTYPES, name
     assert hasattr(lib, name), name
     assert "`%s`" % name in integration, name
-  assert lib.sc_abi_version() == 10  # functions were only added
+  assert lib.sc_abi_version() == 11  # functions were only added
   assert "no batched form" not in header
   # NULL handle: an error code, no crash
   assert lib.sc_batch_fallback_check(None, None, 0, 0.5, None, None) == _lib.SC_ERR_INVALID

@@ -30,7 +30,7 @@ def test_new_symbols_are_declared_prototyped_exported_and_listed():
     assert name in _lib.PROTOTYPES, name
     assert hasattr(lib, name), name
     assert "`%s`" % name in integration, name
-  assert lib.sc_abi_version() == 10  # functions were only added; sc_config is as it was
+  assert lib.sc_abi_version() == 11  # functions were only added; sc_config is as it was
   assert lib.sc_set_batch_any_metric(None, 1) == _lib.SC_ERR_INVALID  # NULL handle: no crash
 
 

@@ -34,7 +34,7 @@ def test_new_symbols_are_declared_prototyped_exported_and_listed():
     assert name in _lib.PROTOTYPES, name
     assert hasattr(lib, name), name
     assert "`%s`" % name in integration, name
-  assert lib.sc_abi_version() == 10  # functions and a struct were only added
+  assert lib.sc_abi_version() == 11  # functions and a struct were only added
   assert re.search(r"SC_SINGLE_BY_FALLBACK\s*=\s*5\b", header)
   assert _lib.SC_SINGLE_BY_FALLBACK == fb.SingleClusterCondition.FallbackClusterer.value == 5
   # NULL handle: an error code, no crash

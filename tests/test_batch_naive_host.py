@@ -30,7 +30,7 @@ def test_new_symbols_are_declared_prototyped_and_exported():
     assert name in declared, name
     assert name in _lib.PROTOTYPES, name
     assert hasattr(lib, name), name
-  assert lib.sc_abi_version() == 10 and _lib.SC_ABI_VERSION == 10  # functions were only added
+  assert lib.sc_abi_version() == 11 and _lib.SC_ABI_VERSION == 11  # functions were only added
   # NULL handle: an error code, no crash
   assert lib.sc_batch_naive_cluster(None, None, 0, 0.5, 0.5, None, None, None,
                                     None) == _lib.SC_ERR_INVALID

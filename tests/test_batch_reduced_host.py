@@ -26,7 +26,7 @@ def test_new_symbols_are_declared_prototyped_and_exported():
     assert hasattr(lib, name), name
   assert re.search(r"SC_BATCH_ROUTE_FALLBACK\s*=\s*3\b", header)
   assert _lib.BATCH_ROUTE_FALLBACK == 3
-  assert lib.sc_abi_version() == 10  # functions were only added
+  assert lib.sc_abi_version() == 11  # functions were only added
   # NULL handle: an error code, no crash
   assert lib.sc_set_reduce_wave_bytes(None, 0) == _lib.SC_ERR_INVALID
   assert lib.sc_batch_ahc(None, None, 0, 1, 2, 0.0, None, None) == _lib.SC_ERR_INVALID

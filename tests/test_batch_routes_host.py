@@ -24,7 +24,7 @@ def test_library_exports_the_batch_route_report():
     assert re.search(r"SC_BATCH_ROUTE_%s\s*=\s*%d\b" % (name, value), header), name
     assert getattr(_lib, "BATCH_ROUTE_" + name) == value
   # an addition only: the structs are the parent's (ABI 9: the test entry of the refinement front)
-  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 10
+  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 11
 
 
 def test_null_handle_is_invalid():

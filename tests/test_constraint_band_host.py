@@ -71,7 +71,7 @@ def test_library_exports_the_band_entry_points():
     assert hasattr(lib, name), name
   assert declared == set(_lib.PROTOTYPES), declared ^ set(_lib.PROTOTYPES)
   # additions only: the structs are the parent's (ABI 9: the test entry of the refinement front)
-  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 10
+  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 11
 
 
 def test_check_input_reads_a_constraint_matrix_as_its_n_by_n_shape():

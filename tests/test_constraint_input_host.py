@@ -146,9 +146,9 @@ def test_new_symbols_are_declared_prototyped_exported_and_listed():
 
 def test_abi_version_is_still_10_everywhere():
   header = open(os.path.join(ROOT, "include", "spectralcluster_amd.h")).read()
-  assert re.search(r"^#define SC_ABI_VERSION 10$", header, flags=re.M)
-  assert _lib.SC_ABI_VERSION == 10
-  assert _lib.load().sc_abi_version() == 10  # functions were only added
+  assert re.search(r"^#define SC_ABI_VERSION 11$", header, flags=re.M)
+  assert _lib.SC_ABI_VERSION == 11
+  assert _lib.load().sc_abi_version() == 11  # functions were only added
 
 
 def test_the_batch_descriptor_did_not_move():

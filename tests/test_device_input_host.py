@@ -194,7 +194,7 @@ def test_header_binding_and_library_agree_on_the_additions():
   assert re.search(r"^void\*\s+sc_stream\s*\(", header, flags=re.M)
   assert "sc_stream" in _lib.POINTER_PROTOTYPES and hasattr(lib, "sc_stream")
   assert declared == set(_lib.PROTOTYPES)
-  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 10
+  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 11
   for i, name in enumerate(("F64", "F32", "F16", "BF16")):
     assert re.search(r"SC_DTYPE_%s\s*=\s*%d\b" % (name, i), header)
     assert getattr(_lib, "SC_DTYPE_" + name) == i

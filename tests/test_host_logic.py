@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import spectral_oracle as so
+from _hessenberg_ref import gehd2 as _gehd2
 import spectralcluster_amd as sca
 from spectralcluster_amd import _lib, multigpu
 
@@ -26,7 +27,7 @@ def test_library_exports_every_declared_symbol():
   for name in sorted(declared):
     assert hasattr(lib, name), name
   assert declared == set(_lib.PROTOTYPES), declared ^ set(_lib.PROTOTYPES)
-  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 10
+  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 11
 
 
 def test_graft_entry_build_runs():
@@ -563,29 +564,6 @@ def test_host_general_eig_vs_numpy(entry):
       v = vr + 1j * vi
       assert np.abs(a @ v - v * w[None, :nvec]).max() < 1e-12 * scale * m, (m, kind)
       assert np.abs(np.linalg.norm(v, axis=0) - 1.0).max() < 1e-13 * m
-
-
-def _gehd2(a):
-  """LAPACK dgehd2 in NumPy, in the storage the device reduction (hessenberg.hip) leaves: the
-  Hessenberg matrix on and above the subdiagonal, reflector k (v[k + 1] = 1 implied) below the
-  subdiagonal of column k, tau."""
-  a = a.copy()
-  n = a.shape[0]
-  tau = np.zeros(max(n - 2, 1))
-  for k in range(n - 2):
-    x = a[k + 1:, k].copy()
-    alpha, xnorm = x[0], np.linalg.norm(x[1:])
-    if xnorm == 0.0:
-      continue
-    beta = -np.copysign(np.hypot(alpha, xnorm), alpha)
-    tau[k] = (beta - alpha) / beta
-    v = x / (alpha - beta)
-    v[0] = 1.0
-    a[:, k + 1:] -= tau[k] * np.outer(a[:, k + 1:] @ v, v)
-    a[k + 1:, k + 1:] -= tau[k] * np.outer(v, v @ a[k + 1:, k + 1:])
-    a[k + 1, k] = beta
-    a[k + 2:, k] = v[1:]
-  return np.ascontiguousarray(a), tau
 
 
 def _host_hessenberg_eig(a, pick):

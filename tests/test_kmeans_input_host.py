@@ -33,8 +33,8 @@ def test_header_binding_and_library_agree_on_the_additions():
     assert len(args.split(",")) == len(_lib.PROTOTYPES[name][1]), name
     assert _lib.PROTOTYPES[name][1][1] == ctypes.POINTER(_lib.ScArray)
   # additions only: the version every host test pins
-  assert re.search(r"#define\s+SC_ABI_VERSION\s+10\b", header)
-  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 10
+  assert re.search(r"#define\s+SC_ABI_VERSION\s+11\b", header)
+  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 11
 
 
 class Recorder:

@@ -90,3 +90,47 @@ def test_reference_chain_within_bounds(name):
     scale = float(np.max(np.abs(t)))
     assert float(inv.proj_err.max()) <= 64 * kr.gamma(inv.n + inv.m) * scale
     assert float(inv.krylov_err.max()) <= 64 * kr.gamma(inv.n + inv.m) * scale
+
+
+# ------------------------------------------------------------------------------ block Arnoldi
+def _arnoldi_operator(name):
+  """The operators of the GPU cases (test_gpu_general_kernels.py, section C), scalings in fp64
+  from the row sums as k_scaling_general forms them."""
+  import _hessenberg_ref as hr
+  n, lap = {"cap56": (65, 0), "pitch129": (129, 0), "affinity_none": (300, 0),
+            "random_walk": (520, 3), "graph_cut": (520, 4), "unnormalized": (520, 2),
+            "restart": (300, 0)}[name]
+  m = (kr.nonnormal_cluster(n) if name == "restart" else
+       kr.separated_matrix(n) if name in ("cap56", "pitch129") else hr.thresholded_affinity(n))
+  cl, cr, p = kr.general_scaling_vectors(m.sum(axis=1), lap)
+  return kr.Operator(m, c=cl, p=p, s=cr), lap
+
+
+@pytest.mark.parametrize("name", ["cap56", "pitch129", "affinity_none", "random_walk", "graph_cut",
+                                  "unnormalized", "restart"])
+def test_reference_arnoldi_chain_within_bounds(name):
+  import spectral_oracle as so
+  op, lap = _arnoldi_operator(name)
+  n = op.n
+  if lap:  # the scalings are those of the oracle's Laplacian
+    dense = np.diag(op.p) + op.c[:, None] * op.m * op.s[None, :]
+    want = -so.laplacian(op.m, lap)
+    assert np.abs(dense - want).max() <= 4 * kr.gamma(n) * max(1.0, np.abs(want).max())
+    assert (lap == 3) == (not np.array_equal(op.c, op.s))
+  for m in (24, kr.arnoldi_cap(n)):
+    q, opq, h = kr.ArnoldiChain(op).run(m).state()
+    inv = kr.ArnoldiInvariants(op, q, opq, h)
+    print("%s n=%d m=%d: orth %.2e (bound %.2e)  operator %.3f  projection %.3f  Arnoldi %.2e "
+          "(ratio %.3f)" % (name, n, m, inv.orth, inv.orth_bound, inv.op_ratio(), inv.proj_ratio(),
+                            inv.arnoldi_figure(), inv.arnoldi_ratio()))
+    assert not np.array_equal(h, h.T)          # a full, non-symmetric H
+    assert inv.orth * SPARE <= inv.orth_bound
+    assert inv.op_ratio() * SPARE <= 1.0
+    assert inv.proj_ratio() * SPARE <= 1.0
+    assert inv.arnoldi_ratio() * SPARE <= 1.0
+  # the wide form's basis
+  if name == "affinity_none":
+    assert kr.arnoldi_cap(n, wide=True) == 128 and kr.arnoldi_cap(65) == 56
+    q, opq, h = kr.ArnoldiChain(op).run(128).state()
+    inv = kr.ArnoldiInvariants(op, q, opq, h)
+    assert inv.orth * SPARE <= inv.orth_bound and inv.arnoldi_ratio() * SPARE <= 1.0

@@ -146,7 +146,7 @@ def test_library_exports_the_pair_entry_points():
     assert hasattr(lib, name), name
   assert declared == set(_lib.PROTOTYPES), declared ^ set(_lib.PROTOTYPES)
   # additions only: no struct or signature of the parent changes
-  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 10
+  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 11
   assert "PairwiseConstraints" in sca.__all__
   assert sca.PairwiseConstraints is sca.constraint.PairwiseConstraints
 

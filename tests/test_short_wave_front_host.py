@@ -40,8 +40,8 @@ def test_enumerators_match_the_python_mirror():
 
 def test_abi_version_is_unchanged():
   header = read("include", "spectralcluster_amd.h")
-  assert re.search(r"#define\s+SC_ABI_VERSION\s+10\b", header)
-  assert _lib.SC_ABI_VERSION == 10
+  assert re.search(r"#define\s+SC_ABI_VERSION\s+11\b", header)
+  assert _lib.SC_ABI_VERSION == 11
 
 
 def test_switch_is_listed_with_the_other_route_switches():

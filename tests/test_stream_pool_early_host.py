@@ -25,7 +25,7 @@ def test_library_exports_the_early_stage_entries():
     assert hasattr(lib, name), name
   assert declared == set(_lib.PROTOTYPES), declared ^ set(_lib.PROTOTYPES)
   # additions only: no struct changed
-  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 10
+  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 11
 
 
 def test_null_pool_is_invalid():

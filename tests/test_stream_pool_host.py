@@ -92,9 +92,9 @@ def test_multi_stage_clusterer_goes_through_the_helper(monkeypatch):
 
 def test_abi_version_is_still_9():
   header = open(os.path.join(ROOT, "include", "spectralcluster_amd.h")).read()
-  assert re.search(r"^#define SC_ABI_VERSION (\d+)$", header, flags=re.M).group(1) == "10"
-  assert _lib.SC_ABI_VERSION == 10
-  assert _lib.load().sc_abi_version() == 10
+  assert re.search(r"^#define SC_ABI_VERSION (\d+)$", header, flags=re.M).group(1) == "11"
+  assert _lib.SC_ABI_VERSION == 11
+  assert _lib.load().sc_abi_version() == 11
   for name in ("sc_pool_create", "sc_pool_destroy", "sc_pool_reset", "sc_pool_rows",
                "sc_pool_append", "sc_pool_precluster", "sc_pool_centroids", "sc_pool_get",
                "sc_pool_compress"):
