@@ -18,12 +18,12 @@ than the two vectors and callables are out of the device scope.  Those raise
 from __future__ import annotations
 
 import contextlib
-import copy
 import ctypes
 import typing
 
 import numpy as np
 
+from spectralcluster_amd import _batch
 from spectralcluster_amd import _dlpack
 from spectralcluster_amd import _lib
 from spectralcluster_amd import autotune as autotune_lib
@@ -41,11 +41,6 @@ LaplacianType = laplacian.LaplacianType
 RefinementName = refinement.RefinementName
 RefinementOptions = refinement.RefinementOptions
 EigenGapType = utils.EigenGapType
-
-
-# the constraint forms that travel inside a library batch call
-_BATCH_CONSTRAINTS = (constraint_lib.ConstraintMatrix, constraint_lib.PairwiseConstraints,
-                      constraint_lib.DenseConstraints)
 
 
 class SpectralClusterer:
@@ -156,18 +151,14 @@ class SpectralClusterer:
       handle.check(handle.lib.sc_clear_constraint(handle.raw))
       return False
     if isinstance(constraint_matrix, constraint_lib.PairwiseConstraints):
-      self.constraint_options.constraint_operator.check_input(
-          np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)),
-          constraint_matrix)
+      _batch.check_constraint(self, n, constraint_matrix)
       rows, cols, vals = constraint_matrix.entries()
       handle.check(handle.lib.sc_set_constraint_pairs(
           handle.raw, _lib.as_int32_p(rows), _lib.as_int32_p(cols), _lib.as_double_p(vals),
           len(vals), n))
       return True
     if isinstance(constraint_matrix, constraint_lib.DenseConstraints):
-      self.constraint_options.constraint_operator.check_input(
-          np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)),
-          constraint_matrix)
+      _batch.check_constraint(self, n, constraint_matrix)
       with _lib.use_device(self.device):
         source = constraint_matrix.describe(self._handle)
         try:
@@ -177,16 +168,12 @@ class SpectralClusterer:
           source.release()
       return True
     if isinstance(constraint_matrix, constraint_lib.ConstraintMatrix):
-      self.constraint_options.constraint_operator.check_input(
-          np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)),
-          constraint_matrix)
+      _batch.check_constraint(self, n, constraint_matrix)
       band = np.ascontiguousarray(constraint_matrix.band(), dtype=np.float64)
       handle.check(handle.lib.sc_set_constraint_band(handle.raw, _lib.as_double_p(band), n))
       return True
     con = np.asarray(constraint_matrix)
-    # ConstraintOperation.check_input against the (n, n) affinity: only its shape is read
-    self.constraint_options.constraint_operator.check_input(
-        np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)), con)
+    _batch.check_constraint(self, n, con)
     con = np.ascontiguousarray(con, dtype=np.float64)
     handle.check(handle.lib.sc_set_constraint(handle.raw, _lib.as_double_p(con), n))
     return True
@@ -336,10 +323,8 @@ class SpectralClusterer:
       if constraint_matrix is not None:
         raise RuntimeError(
             "Cannot handle constraint_matrix when max_spectral_size is set")
-      if (self.max_spectral_size < 2 or
-          (self.max_clusters and self.max_spectral_size <= self.max_clusters) or
-          (self.min_clusters and self.max_spectral_size <= self.min_clusters)):
-        raise ValueError("max_spectral_size should be a relatively big number")
+      if _batch.spectral_size_too_small(self):
+        raise _batch.small_spectral_size()
       return self._reduce_size_and_predict(source.host_f64(self._handle()))
     handle = self._handle()
     default_tail = (self.post_eigen_cluster_function is custom_distance_kmeans.run_kmeans)
@@ -386,11 +371,7 @@ class SpectralClusterer:
       # reference :259-264 -- once, before the AutoTune sweep re-reads the affinity
       handle.check(handle.lib.sc_apply_constraint(handle.raw, self.build_config()))
     if self.autotune:
-      sequence = self.refinement_options.refinement_sequence or []
-      if RefinementName.RowWiseThreshold not in sequence:
-        raise ValueError(
-            "AutoTune is only effective when the refinement sequence"
-            "contains RowWiseThreshold")
+      _batch.check_autotune_sequence(self)
       evaluated = []
 
       def evaluate_level(ps):
@@ -501,130 +482,43 @@ class SpectralClusterer:
 
     Every check of predict_affinity, the length of `constraint_matrices` and the size of each
     `ConstraintMatrix` / `PairwiseConstraints` are made for the whole list before anything is
-    launched.  The batch is ONE `sc_predict_batch_affinities` call when the clusterer is one
-    `_library_batch_covers()` accepts but for its `affinity_function` (no AutoTune, `min_clusters`
-    not 1, the default k-means function), the metric is on the device (cosine when constraints
-    travel), `group` is not 1 and every constraint is a `ConstraintMatrix`, a
-    `PairwiseConstraints`, a `DenseConstraints` (then `sc_predict_batch_constraint_arrays`) or
-    None.  It takes `predict_batch`'s routes -- n <= 128 in Jacobi waves
-    (route 2), 128 < n < 4096 in lockstep groups of up to `group` (route 1), n >= 4096 and members
-    that leave their route as single calls inside the call (route 0) -- with one grouped ingest
-    launch per group or wave and the member-by-member refinement front; results agree with
-    predict_affinity as predict_batch's do with predict() (labels equal unless an eigengap
-    decision is a near tie, eigenvalues within 1e-10 relative on route 2 and 1e-6 on route 1),
-    and the same list gives the same results.  With a device tensor in the list the library
-    synchronises its stream once at entry; the tensors may be overwritten or freed when the call
-    has returned.  Otherwise -- AutoTune, `min_clusters=1`, a user k-means function, a raw dense
-    ndarray constraint, `group=1` -- the matrices run one after the other through
-    predict_affinity (routes all 0).  `last_batch_routes` / `last_batch_diags` are filled as in
-    predict_batch.
+    launched.  The batch is the `predict_affinity_batch` row of predict_batch's table: ONE
+    `sc_predict_batch_affinities` call when the clusterer is one `_library_batch_covers()`
+    accepts but for its `affinity_function` (no AutoTune, `min_clusters` not 1, the default
+    k-means function), the metric is on the device (cosine when constraints travel), `group` is
+    not 1 and every constraint is a `ConstraintMatrix`, a `PairwiseConstraints`, a
+    `DenseConstraints` (then `sc_predict_batch_constraint_arrays`) or None.  It takes
+    `predict_batch`'s routes -- n <= 128 in Jacobi waves (route 2), 128 < n < 4096 in lockstep
+    groups of up to `group` (route 1), n >= 4096 and members that leave their route as single
+    calls inside the call (route 0) -- with one grouped ingest launch per group or wave and the
+    member-by-member refinement front; results agree with predict_affinity as predict_batch's do
+    with predict() (labels equal unless an eigengap decision is a near tie, eigenvalues within
+    1e-10 relative on route 2 and 1e-6 on route 1), and the same list gives the same results.
+    With a device tensor in the list the library synchronises its stream once at entry; the
+    tensors may be overwritten or freed when the call has returned.  Otherwise -- AutoTune,
+    `min_clusters=1`, a user k-means function, a raw dense ndarray constraint, `group=1` -- the
+    matrices run one after the other through predict_affinity (routes all 0).
+    `last_batch_routes` / `last_batch_diags` are filled as in predict_batch.
 
     `batch_any_metric` (keyword only, default False): predict_batch's flag.  With it a
     `custom_dist` other than cosine that is on the device takes routes 1 and 2 as cosine does,
     constrained or not; see there for how the labels then compare with predict_affinity's."""
     count = len(affinities)
+    _batch.check_length(constraint_matrices, count)
     if constraint_matrices is None:
       constraint_matrices = [None] * count
-    elif len(constraint_matrices) != count:
-      raise ValueError("constraint_matrices must be as long as the batch")
     if group is not None and int(group) < 1:
       raise ValueError("group must be at least 1")
     for i, (a, cm) in enumerate(zip(affinities, constraint_matrices)):
       n = self._check_affinity_input(a, "affinity %d" % i)
-      if self.constraint_options is not None and isinstance(
-          cm, _BATCH_CONSTRAINTS):
-        # (predict()'s check and message: _set_constraint)
-        self.constraint_options.constraint_operator.check_input(
-            np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)), cm)
+      if self.constraint_options is not None and isinstance(cm, _batch.BATCH_CONSTRAINTS):
+        _batch.check_constraint(self, n, cm)
     self.last_batch_single = None
-    constrained = self.constraint_options is not None and any(
-        c is not None for c in constraint_matrices)
-    if (batch_any_metric and (group is None or int(group) > 1) and
-        self._metric_needs_permission()):
-      with self._any_metric_permission():
-        return self.predict_affinity_batch(affinities, constraint_matrices, group)
-    try:  # (a metric that is not on the device raises in predict_affinity, as in predict())
-      _lib.kmeans_metric_code(self.custom_dist)
-      metric_ok = not constrained or self._batch_kmeans_ok()
-    except (ValueError, _lib.UnsupportedOnDeviceError):
-      metric_ok = False
-    if (count and metric_ok and self._library_batch_covers(affinity_input=True) and
-        (group is None or int(group) > 1) and
-        all(c is None or isinstance(c, _BATCH_CONSTRAINTS) for c in constraint_matrices)):
-      return self._affinity_library_batch(affinities, constraint_matrices if constrained else None,
-                                          16 if group is None else int(group))
-    labels, diags = [], []
-    for a, cm in zip(affinities, constraint_matrices):
-      labels.append(self.predict_affinity(a, cm))
-      diags.append(self.last_diag)
-    self.last_batch_routes = [_lib.BATCH_ROUTE_SINGLE] * count
-    self.last_batch_diags = diags
-    return labels
-
-  def _describe_dense(self, constraint_matrices: typing.Sequence,
-                      sources: typing.List[_dlpack.Source]):
-    """The `dense` list of `sc_predict_batch_constraint_arrays` -- one `sc_array` per utterance,
-    `data` NULL where its constraint is no `DenseConstraints` -- or None when the batch holds
-    none.  The described matrices are appended to `sources`, a list of the caller's that holds
-    nothing else: it releases them when the library call has returned."""
-    if not any(isinstance(c, constraint_lib.DenseConstraints) for c in constraint_matrices):
-      return None
-    dense = (_lib.ScArray * len(constraint_matrices))()
-    with _lib.use_device(self.device):
-      for i, cm in enumerate(constraint_matrices):
-        if isinstance(cm, constraint_lib.DenseConstraints):
-          src = cm.describe(self._handle)
-          sources.append(src)
-          dense[i] = src.array
-    return dense
-
-  def _affinity_library_batch(self, affinities: typing.Sequence,
-                              constraint_matrices: typing.Optional[typing.Sequence],
-                              group: int) -> typing.List[np.ndarray]:
-    """ONE `sc_predict_batch_affinities` call; the checks of predict_affinity_batch passed."""
-    count = len(affinities)
-    sources, dense_sources = [], []
-    try:
-      with _lib.use_device(self.device):
-        for a in affinities:
-          sources.append(_dlpack.describe(a, self._handle, strided=True))
-      handle = self._handle()
-      handle.check(handle.lib.sc_clear_constraint(handle.raw))
-      cons, keep, dense = None, [], None
-      if constraint_matrices is not None:
-        cons = (_lib.ScConstraintDesc * count)()
-        dense = self._describe_dense(constraint_matrices, dense_sources)
-        for desc, src, cm in zip(cons, sources, constraint_matrices):
-          if isinstance(cm, constraint_lib.DenseConstraints):
-            continue  # (kind 0: its matrix travels in `dense`)
-          if isinstance(cm, constraint_lib.PairwiseConstraints):
-            rows, cols, vals = cm.entries()
-            keep.append((rows, cols, vals))
-            desc.kind, desc.count = 3, len(vals)
-            desc.rows, desc.cols = _lib.as_int32_p(rows), _lib.as_int32_p(cols)
-            desc.vals = _lib.as_double_p(vals)
-          elif cm is not None:
-            n = src.shape[0]
-            band = np.zeros(max(n - 1, 1), dtype=np.float64)  # (n = 1: a valid pointer)
-            band[:n - 1] = cm.band()
-            keep.append(band)
-            desc.kind, desc.band = 2, _lib.as_double_p(band)
-      labels = [np.empty(src.shape[0], dtype=np.int64) for src in sources]
-      lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
-      diags = (_lib.ScDiag * count)()
-      if dense is not None:
-        handle.check(handle.lib.sc_predict_batch_constraint_arrays(
-            handle.raw, (_lib.ScArray * count)(*[src.array for src in sources]), cons, dense,
-            count, self.build_config(), lp, diags, int(group), 1), TypeError)
-      else:
-        handle.check(handle.lib.sc_predict_batch_affinities(
-            handle.raw, (_lib.ScArray * count)(*[src.array for src in sources]), cons, count,
-            self.build_config(), lp, diags, int(group)), TypeError)
-    finally:
-      for src in sources + dense_sources:
-        src.release()
-    self._batch_report(handle, diags, count)
-    return labels
+    form = _batch.Form.make(group, None)
+    flags = _batch.Flags(any_metric=batch_any_metric)
+    with self._permission_if(_batch.wants_permission(self, form, flags)):
+      plan = _batch.plan_affinity(self, form, constraint_matrices, count)
+      return _batch.execute(self, plan, form, affinities)
 
   # -------------------------------------------------------------- batch (new)
   def predict_batch(self, utterances: typing.Sequence,
@@ -674,10 +568,144 @@ class SpectralClusterer:
     before it -- and the streams of the batch read the tensors from then on; they may be
     overwritten or freed when the call has returned.
 
+    How a batch chooses its call (`_batch.plan`; `tests/golden/batch_dispatch.json` records it
+    case by case).  THE LIBRARY-BATCH FORM, which every one-call regime below needs: `streams`
+    is not given and `group` is not 1 (the grouped form); there is no AutoTune (but for the first
+    row); the affinity and k-means functions are the default ones; k-means is the cosine one
+    (with `batch_any_metric`: any metric on the device).  The first row that applies is taken:
+
+      call (sc_predict_batch_...)   regime                              flag it needs               what keeps the loop
+      ----------------------------  ----------------------------------  --------------------------  ---------------------------------
+      _autotune                     a clusterer with AutoTune           autotune_from_entry_state   a metric other than cosine, a
+                                                                                                    constraint that is no
+                                                                                                    ConstraintMatrix (on copies of
+                                                                                                    the AutoTune object); without
+                                                                                                    the flag: the order-dependent loop
+      _multi_stage                  min_clusters=1 with                 batch_multi_stage           constraint_matrices given,
+                                    max_spectral_size and / or                                      max_spectral_size below
+                                    spectral_min_embeddings > 1                                     spectral_min_embeddings
+      _single_fallback              min_clusters=1, the                 batch_fallback_condition    the Naive type, constraints,
+                                    FallbackClusterer condition,                                    max_spectral_size,
+                                    Agglomerative type                                              spectral_min_embeddings > 1
+      _single_naive                 the same, Naive type                batch_fallback_condition    as above
+                                                                        and batch_naive_fallback
+      _single                       min_clusters=1, a condition         --                          constraints, the two size
+                                    that reads the affinity                                         options
+      _constrained, _constraints,   constraint_options and              --                          a raw ndarray among the
+      _constraint_arrays            constraint_matrices                                             entries, min_clusters=1, the
+                                                                                                    two size options
+      _reduced                      max_spectral_size and / or          --                          the Naive type for a fallback
+                                    spectral_min_embeddings > 1,                                    utterance, min_clusters=1,
+                                    min_clusters not 1                                              max_spectral_size below
+                                                                                                    spectral_min_embeddings
+      _reduced_naive                the same, a fallback utterance      batch_naive_fallback        as above
+                                    meeting the Naive type
+      _grouped, _streams, _arrays   every other clusterer the library   --                          (user functions, AutoTune, the
+                                    batch covers; any form                                          fallback decisions: the loop)
+      _affinities,                  predict_affinity_batch              --                          see there
+      _constraint_arrays
+
+    The loop is per-utterance `predict(u, c)` calls (routes all 0); `group=1` and `streams` keep
+    it for every row but the plain one, and so does a metric other than cosine without
+    `batch_any_metric`.  The rows, in that order:
+
+    `autotune_from_entry_state` (a clusterer without AutoTune ignores it).  `AutoTune.tune`
+    leaves the object's range and step narrowed, so the default loop searches utterance i + 1 on
+    the grid utterance i left behind: results depend on the order of the batch.  With the flag
+    every utterance is searched from the state the `AutoTune` object has when the call is
+    entered -- what a fresh clusterer per utterance gives -- and the object is left as it was
+    found.  The missing-RowWiseThreshold ValueError and the ValueError of a `ConstraintMatrix`
+    of the wrong length are raised before anything is launched.  Afterwards `last_batch_best_p`
+    holds the winning p_percentile per utterance, `last_batch_diags` the winner's diagnostics,
+    and `refinement_options.p_percentile` the last value evaluated for the last utterance.  It
+    is ONE `sc_predict_batch_autotune` call in the library-batch form when the metric is cosine
+    (this row ignores `batch_any_metric`) and every constraint is a `ConstraintMatrix` or None:
+    utterances of n <= 128 in waves whose (utterance, p) pairs
+    share one front launch and one Jacobi launch per 64 pairs and level (route 2), 128 < n < 4096
+    dealt to three lanes that each run the per-utterance search on a handle, stream and thread
+    of their own (route 1), the rest per utterance on the caller's handle (route 0).  Otherwise
+    -- a dense ndarray constraint among them -- every utterance runs predict() on a copy of the
+    AutoTune object (routes all 0), with the same results.
+
+    `batch_multi_stage` (keyword only; default False: the loop).
+    The three options of a robust offline diarizer together -- `max_spectral_size` and / or
+    `fallback_options.spectral_min_embeddings` above 1, with `min_clusters=1` -- are ONE
+    `sc_predict_batch_multi_stage` call in the library-batch form when no `constraint_matrices`
+    are given and `max_spectral_size >= spectral_min_embeddings` when both are set.
+    Any of the five single-cluster conditions and either fallback type is
+    taken; `batch_fallback_condition` / `batch_naive_fallback` are not needed as well.  Per
+    utterance, in predict()'s order: fewer than `spectral_min_embeddings` rows, the fallback
+    clusterer's labels and no single-cluster test; more than `max_spectral_size` rows,
+    complete-linkage pre-clustering, then what predict() does with the centroids -- which stay on
+    the device --, their single-cluster test included; otherwise the single-cluster test and the
+    spectral path.  Results have predict()'s dtypes: float64 for a size-reduced utterance (zeros
+    when its centroids hold one cluster), `np.array([0] * n)` for an utterance of one cluster,
+    int64 otherwise.  Afterwards `last_batch_reduced` holds the kinds, `last_batch_single` True /
+    False / None (None: a fallback utterance, not tested), `last_batch_routes` the route of the
+    spectral run (under the `FallbackClusterer` condition 3 for an utterance found single; 3 for a
+    fallback utterance) and `last_batch_diags` its diagnostics (zeroed for single and fallback
+    utterances).  predict()'s ValueErrors -- `max_spectral_size` not above `max_clusters` /
+    `min_clusters`, an agglomerative utterance of one row, an AffinityGmmBic diagonal offset that
+    is not below the tested rows - 1, a threshold pair `NaiveClusterer` rejects -- are raised,
+    with the utterance's index, before anything is launched.  A batch of one utterance is
+    covered.  Without the flag, and for every other clusterer, nothing changes.
+
+    `batch_fallback_condition` (default False: the loop).  With it a `min_clusters=1`
+    batch under the `FallbackClusterer` condition -- what `MultiStageClusterer`'s constructor
+    sets -- is ONE `sc_predict_batch_single_fallback` call in the library-batch form when the
+    fallback type is `Agglomerative`, the batch is unconstrained, and there is no
+    `max_spectral_size` and no `spectral_min_embeddings` above 1.  The
+    verdicts of the whole batch are computed first -- "does average-linkage cosine AHC, cut at
+    `agglomerative_threshold`, leave one cluster?", a wavefront or a workgroup per utterance, no
+    merge list downloaded --, then one grouped batch clusters the utterances of several clusters
+    from the rows the verdict waves left on the device.  Results are predict()'s:
+    `np.array([0] * n)` for an utterance of one cluster (route 3, a zeroed diag), int64 labels
+    otherwise (route 0, 1 or 2); `last_batch_single` lists the verdicts.  An utterance of one
+    row raises predict()'s ValueError before anything is launched, one with a zero or non-finite
+    row a ValueError that names its index.  Anything else keeps the loop, flag or no flag.
+
+    `batch_naive_fallback` (default False: the `Naive` fallback type -- what a default
+    `FallbackOptions` selects -- keeps the loop in the fallback-condition and the reduced
+    regimes).  With it
+      * a batch that is the `sc_predict_batch_reduced` call but for a fallback utterance meeting
+        the `Naive` type is ONE `sc_predict_batch_reduced_naive` call: the fallback utterances
+        are walked by the naive clusterer from the empty state, a workgroup each in one launch
+        per wave, with `naive_threshold` / `naive_adaptation_threshold` (None: the threshold).
+        `last_batch_reduced`, `last_batch_routes` (3 for a fallback utterance), `last_batch_diags`
+        and the result dtypes are as in the reduced regime; a fallback utterance of one row is
+        fine (label 0);
+      * together with `batch_fallback_condition`, a `min_clusters=1` batch under the
+        `FallbackClusterer` condition with the `Naive` type is ONE `sc_predict_batch_single_naive`
+        call under every other clause of that flag: the verdict of an utterance is "the naive walk
+        ends with one centroid", and its work ends at the row that would open a second one.  An
+        utterance of one row is single; one with a zero or non-finite row raises a ValueError that
+        names its index.
+    Labels equal predict()'s: the batch kernel shares its arithmetic with the one predict() runs.
+    A threshold pair that `NaiveClusterer` rejects raises its ValueError before anything is
+    launched.  With the `Agglomerative` type the flag does nothing.
+
+    `min_clusters=1` (the streaming regime: the clusterer may say "one speaker"): the batch is
+    ONE `sc_predict_batch_single` call in the library-batch form when
+    `fallback_options.single_cluster_condition` is one of the four that read the affinity
+    (AffinityGmmBic, AllAffinity, NeighborAffinity, AffinityStd) and the batch is
+    unconstrained.  The
+    single-cluster test of every utterance runs on the device inside the call, group by group and
+    wave by wave, before the utterance's eigensolver.  Results are predict()'s:
+    `np.array([0] * n)` for an utterance of one cluster, int64 labels otherwise;
+    `last_batch_single` lists the verdicts (None after a call that did not take this path) and
+    `last_batch_routes` the route each utterance's affinity took (0, 1 or 2).  With
+    AffinityGmmBic an utterance of `single_cluster_affinity_diagonal_offset >= n - 1` raises
+    predict()'s ValueError, with the utterance's index, before anything is launched.  These keep
+    the per-utterance loop (routes all 0) with `min_clusters=1`: the `FallbackClusterer` condition
+    (it clusters the embeddings, not the affinity; see `batch_fallback_condition`), constrained
+    batches, AutoTune batches, and batches with `max_spectral_size` / `spectral_min_embeddings`
+    (but see `batch_multi_stage`).
+
     `constraint_matrices`: one `ConstraintMatrix` / ndarray / None per utterance, used when
-    `constraint_options` is set (without it a batch carries no constraints).  When every entry
-    is a `ConstraintMatrix` or None, the batch is the grouped form (`group` > 1, no `streams`),
-    k-means is the cosine one and nothing above sends it through predict(), it is ONE `sc_predict_batch_constrained` call:
+    `constraint_options` is set (without it a batch carries no constraints); a list that is not
+    as long as the batch raises a ValueError.  When every entry
+    is a `ConstraintMatrix` or None and the batch is in the library-batch form, it is ONE
+    `sc_predict_batch_constrained` call:
     the same routes as an unconstrained batch, each utterance's band (`ConstraintMatrix.band()`,
     n - 1 values) resident in its member arena.  ConstraintPropagation before refinement then runs
     as one chain of grouped launches per group of up to 16 utterances; AffinityIntegration and
@@ -698,29 +726,10 @@ class SpectralClusterer:
     Anything else -- a raw dense ndarray among the entries, AutoTune (the Turn-to-Diarize
     preset), group=1, `streams` -- runs as per-utterance `predict(u, c)` calls (routes all 0).
 
-    `autotune_from_entry_state` (a clusterer without AutoTune ignores it).  `AutoTune.tune`
-    leaves the object's range and step narrowed, so the default loop searches utterance i + 1 on
-    the grid utterance i left behind: results depend on the order of the batch.  With the flag
-    every utterance is searched from the state the `AutoTune` object has when the call is
-    entered -- what a fresh clusterer per utterance gives -- and the object is left as it was
-    found.  The missing-RowWiseThreshold ValueError and the ValueError of a `ConstraintMatrix`
-    of the wrong length are raised before anything is launched.  Afterwards `last_batch_best_p`
-    holds the winning p_percentile per utterance, `last_batch_diags` the winner's diagnostics,
-    and `refinement_options.p_percentile` the last value evaluated for the last utterance.  It
-    is ONE `sc_predict_batch_autotune` call when the clusterer is otherwise one the library batch
-    covers, the metric is cosine, `group` is not 1, `streams` is not given and every constraint
-    is a `ConstraintMatrix` or None: utterances of n <= 128 in waves whose (utterance, p) pairs
-    share one front launch and one Jacobi launch per 64 pairs and level (route 2), 128 < n < 4096
-    dealt to three lanes that each run the per-utterance search on a handle, stream and thread
-    of their own (route 1), the rest per utterance on the caller's handle (route 0).  Otherwise
-    -- a dense ndarray constraint among them -- every utterance runs predict() on a copy of the
-    AutoTune object (routes all 0), with the same results.
-
     `max_spectral_size` and `fallback_options.spectral_min_embeddings` (the multi-stage
-    regime): the batch is ONE `sc_predict_batch_reduced` call when the clusterer is otherwise
-    one the library batch covers (no AutoTune, `min_clusters` not 1, the default affinity and
-    k-means functions), k-means is the cosine one, `group` is not 1, `streams` is not given, no
-    constraint matrices travel, the fallback -- if an utterance needs it -- is the
+    regime): the batch is ONE `sc_predict_batch_reduced` call in the library-batch form when
+    `min_clusters` is not 1, no constraint matrices travel, the fallback -- if an utterance
+    needs it -- is the
     agglomerative one, and `max_spectral_size >= spectral_min_embeddings` when both are set.
     The utterances of more than `max_spectral_size` rows are pre-clustered together (complete
     linkage, a workgroup per utterance in one launch per wave), the ones below
@@ -738,81 +747,7 @@ class SpectralClusterer:
     `batch_naive_fallback`), `min_clusters=1` (but see `batch_multi_stage`), constraints,
     AutoTune, `group=1`, `streams` -- stays the per-utterance loop (routes all 0).
 
-    `min_clusters=1` (the streaming regime: the clusterer may say "one speaker"): the batch is
-    ONE `sc_predict_batch_single` call when `fallback_options.single_cluster_condition` is one of
-    the four that read the affinity (AffinityGmmBic, AllAffinity, NeighborAffinity, AffinityStd),
-    the clusterer is otherwise one the library batch covers, the batch is the grouped form
-    (`group` not 1, no `streams`), unconstrained, and k-means is the cosine one.  The
-    single-cluster test of every utterance runs on the device inside the call, group by group and
-    wave by wave, before the utterance's eigensolver.  Results are predict()'s:
-    `np.array([0] * n)` for an utterance of one cluster, int64 labels otherwise;
-    `last_batch_single` lists the verdicts (None after a call that did not take this path) and
-    `last_batch_routes` the route each utterance's affinity took (0, 1 or 2).  With
-    AffinityGmmBic an utterance of `single_cluster_affinity_diagonal_offset >= n - 1` raises
-    predict()'s ValueError, with the utterance's index, before anything is launched.  These keep
-    the per-utterance loop (routes all 0) with `min_clusters=1`: the `FallbackClusterer` condition
-    (it clusters the embeddings, not the affinity; see `batch_fallback_condition`), constrained
-    batches, AutoTune batches, and batches with `max_spectral_size` / `spectral_min_embeddings`
-    (but see `batch_multi_stage`).
-
-    `batch_fallback_condition` (default False: the loop above).  With it a `min_clusters=1`
-    batch under the `FallbackClusterer` condition -- what `MultiStageClusterer`'s constructor
-    sets -- is ONE `sc_predict_batch_single_fallback` call when the fallback type is
-    `Agglomerative`, the batch is the grouped form (`group` not 1, no `streams`), unconstrained,
-    there is no AutoTune, no `max_spectral_size`, no `spectral_min_embeddings` above 1, the
-    affinity and k-means functions are the default ones and k-means is the cosine one.  The
-    verdicts of the whole batch are computed first -- "does average-linkage cosine AHC, cut at
-    `agglomerative_threshold`, leave one cluster?", a wavefront or a workgroup per utterance, no
-    merge list downloaded --, then one grouped batch clusters the utterances of several clusters
-    from the rows the verdict waves left on the device.  Results are predict()'s:
-    `np.array([0] * n)` for an utterance of one cluster (route 3, a zeroed diag), int64 labels
-    otherwise (route 0, 1 or 2); `last_batch_single` lists the verdicts.  An utterance of one
-    row raises predict()'s ValueError before anything is launched, one with a zero or non-finite
-    row a ValueError that names its index.  Anything else keeps the loop, flag or no flag.
-
-    `batch_naive_fallback` (default False: the `Naive` fallback type -- what a default
-    `FallbackOptions` selects -- keeps the loop in both regimes above).  With it
-      * a batch that is the `sc_predict_batch_reduced` call but for a fallback utterance meeting
-        the `Naive` type is ONE `sc_predict_batch_reduced_naive` call: the fallback utterances
-        are walked by the naive clusterer from the empty state, a workgroup each in one launch
-        per wave, with `naive_threshold` / `naive_adaptation_threshold` (None: the threshold).
-        `last_batch_reduced`, `last_batch_routes` (3 for a fallback utterance), `last_batch_diags`
-        and the result dtypes are as above; a fallback utterance of one row is fine (label 0);
-      * together with `batch_fallback_condition`, a `min_clusters=1` batch under the
-        `FallbackClusterer` condition with the `Naive` type is ONE `sc_predict_batch_single_naive`
-        call under every other clause of that flag: the verdict of an utterance is "the naive walk
-        ends with one centroid", and its work ends at the row that would open a second one.  An
-        utterance of one row is single; one with a zero or non-finite row raises a ValueError that
-        names its index.
-    Labels equal predict()'s: the batch kernel shares its arithmetic with the one predict() runs.
-    A threshold pair that `NaiveClusterer` rejects raises its ValueError before anything is
-    launched.  With the `Agglomerative` type the flag does nothing.
-
-    `batch_multi_stage` (keyword only; default False: the loop, as the paragraphs above say).
-    The three options of a robust offline diarizer together -- `max_spectral_size` and / or
-    `fallback_options.spectral_min_embeddings` above 1, with `min_clusters=1` -- are ONE
-    `sc_predict_batch_multi_stage` call when the batch is the grouped form (`group` not 1, no
-    `streams`), no `constraint_matrices` are given, there is no AutoTune, the affinity and k-means functions are the
-    default ones, k-means is the cosine one, and `max_spectral_size >= spectral_min_embeddings`
-    when both are set.  Any of the five single-cluster conditions and either fallback type is
-    taken; `batch_fallback_condition` / `batch_naive_fallback` are not needed as well.  Per
-    utterance, in predict()'s order: fewer than `spectral_min_embeddings` rows, the fallback
-    clusterer's labels and no single-cluster test; more than `max_spectral_size` rows,
-    complete-linkage pre-clustering, then what predict() does with the centroids -- which stay on
-    the device --, their single-cluster test included; otherwise the single-cluster test and the
-    spectral path.  Results have predict()'s dtypes: float64 for a size-reduced utterance (zeros
-    when its centroids hold one cluster), `np.array([0] * n)` for an utterance of one cluster,
-    int64 otherwise.  Afterwards `last_batch_reduced` holds the kinds, `last_batch_single` True /
-    False / None (None: a fallback utterance, not tested), `last_batch_routes` the route of the
-    spectral run (under the `FallbackClusterer` condition 3 for an utterance found single; 3 for a
-    fallback utterance) and `last_batch_diags` its diagnostics (zeroed for single and fallback
-    utterances).  predict()'s ValueErrors -- `max_spectral_size` not above `max_clusters` /
-    `min_clusters`, an agglomerative utterance of one row, an AffinityGmmBic diagonal offset that
-    is not below the tested rows - 1, a threshold pair `NaiveClusterer` rejects -- are raised,
-    with the utterance's index, before anything is launched.  A batch of one utterance is
-    covered.  Without the flag, and for every other clusterer, nothing changes.
-
-    `batch_any_metric` (keyword only; default False).  Wherever the paragraphs above say
+    `batch_any_metric` (keyword only; default False).  Wherever the library-batch form says
     "k-means is the cosine one", a `custom_dist` other than cosine keeps the batch out of the
     grouped and short routes: a plain batch is still one library call, but every utterance runs
     as a single call inside it (routes all 0), and the constrained, `min_clusters=1`, reduced,
@@ -833,278 +768,33 @@ class SpectralClusterer:
     what predict() raises.
     """
     self.last_batch_single = None
-    if autotune_from_entry_state and self.autotune is not None:
-      return self._predict_batch_entry_state(utterances, constraint_matrices, streams, group)
-    if (batch_any_metric and streams is None and (group is None or int(group) > 1) and
-        self._metric_needs_permission()):
-      with self._any_metric_permission():
-        return self.predict_batch(
-            utterances, streams, group, constraint_matrices, autotune_from_entry_state,
-            batch_fallback_condition, batch_naive_fallback, batch_multi_stage=batch_multi_stage)
-    if (batch_multi_stage and streams is None and (group is None or int(group) > 1) and
-        constraint_matrices is None and self._multi_stage_batch_covers()):
-      return self._predict_batch_multi_stage(utterances, 16 if group is None else int(group))
-    if (batch_fallback_condition and streams is None and (group is None or int(group) > 1) and
-        (constraint_matrices is None or self.constraint_options is None) and
-        self._fallback_condition_covers(naive=batch_naive_fallback)):
-      if constraint_matrices is not None and len(constraint_matrices) != len(utterances):
-        raise ValueError("constraint_matrices must be as long as the batch")
-      return self._predict_batch_single_fallback(utterances, 16 if group is None else int(group))
-    library_batch = self._library_batch_covers()
-    # min_clusters = 1 with a condition that reads the affinity: the test travels inside ONE
-    # sc_predict_batch_single call -- the grouped form, unconstrained, cosine k-means
-    single_check = None
-    if (not library_batch and self.min_clusters == 1 and
-        (constraint_matrices is None or self.constraint_options is None) and
-        streams is None and (group is None or int(group) > 1) and
-        self._library_batch_covers(single_check_covered=True)):
-      try:
-        if self._batch_kmeans_ok():
-          single_check = self._single_check_struct()
-      except (ValueError, _lib.UnsupportedOnDeviceError):
-        pass  # (predict() raises what it raises today)
-      if single_check is not None:
-        if constraint_matrices is not None and len(constraint_matrices) != len(utterances):
-          raise ValueError("constraint_matrices must be as long as the batch")
-        library_batch = True
-        constraint_matrices = None
-    banded = None  # the ConstraintMatrix (or None) of every utterance of a constrained batch
-    if constraint_matrices is not None:
-      if len(constraint_matrices) != len(utterances):
-        raise ValueError("constraint_matrices must be as long as the batch")
-      if self.constraint_options is not None:
-        # (a metric that is not on the device raises in predict(), as it does today)
-        cosine = self._batch_kmeans_ok()
-        if not (library_batch and cosine and streams is None and
-                (group is None or int(group) > 1) and
-                all(c is None or isinstance(c, _BATCH_CONSTRAINTS)
-                    for c in constraint_matrices)):
-          self.last_batch_routes = [_lib.BATCH_ROUTE_SINGLE] * len(utterances)
-          return [self.predict(u, c) for u, c in zip(utterances, constraint_matrices)]
-        banded = list(constraint_matrices)
-    if (not library_batch and banded is None and
-        self._reduced_batch_covers(utterances, streams, group, naive=batch_naive_fallback)):
-      return self._predict_batch_reduced(utterances, 16 if group is None else int(group))
-    if group is None:
-      group = 16 if streams is None else 0
-    if streams is None:
-      streams = 1
-    if not library_batch:
-      # anything sc_predict_batch does not cover (user-supplied affinity / clustering
-      # functions, AutoTune, size reduction, fallback decisions) goes through predict().
-      # A batch never carries a constraint matrix -- same as predict(u) without one.
-      self.last_batch_routes = [_lib.BATCH_ROUTE_SINGLE] * len(utterances)
-      return [self.predict(u) for u in utterances]
-    _lib.kmeans_metric_code(self.custom_dist)  # raises for metrics that are not on the device
-    if not utterances:
-      self.last_batch_routes = []
-      return []
-    for u in utterances:
-      if isinstance(u, np.ndarray) and u.ndim != 2:
-        raise ValueError("all utterances must be (n_i, d) with the same d")
-    sources, dense_sources = [], []
-    try:
-      with _lib.use_device(self.device):
-        for u in utterances:
-          sources.append(_dlpack.describe(u, self._handle))
-      d = sources[0].shape[1]
-      if any(src.shape[1] != d for src in sources):
-        raise ValueError("all utterances must be (n_i, d) with the same d")
-      count = len(sources)
-      bands = []
-      if banded is not None:
-        for src, cm in zip(sources, banded):
-          if cm is None:
-            bands.append(None)
-            continue
-          n = src.shape[0]
-          # (predict()'s check and message: _set_constraint)
-          self.constraint_options.constraint_operator.check_input(
-              np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)), cm)
-          if isinstance(cm, constraint_lib.DenseConstraints):
-            bands.append(None)  # (its matrix travels in `dense`)
-            continue
-          if isinstance(cm, constraint_lib.PairwiseConstraints):
-            bands.append(cm.entries())  # (rows, cols, vals)
-            continue
-          band = np.zeros(max(n - 1, 1), dtype=np.float64)  # (n = 1: no values, a valid pointer)
-          band[:n - 1] = cm.band()
-          bands.append(band)
-      dense = None  # the sc_array of every DenseConstraints of the batch, when there is one
-      if banded is not None:
-        dense = self._describe_dense(banded, dense_sources)
-      labels = [np.empty(src.shape[0], dtype=np.int64) for src in sources]
-      handle = self._handle()
-      handle.check(handle.lib.sc_clear_constraint(handle.raw))  # a batch carries none
-      lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
-      diags = (_lib.ScDiag * count)()
-      single = (ctypes.c_int32 * count)()
-      if single_check is not None:
-        # (predict()'s ValueError, before anything is launched; the library checks it as well)
-        self._check_single_offsets(single_check, [src.shape[0] for src in sources])
-        handle.check(handle.lib.sc_predict_batch_single(
-            handle.raw, (_lib.ScArray * count)(*[src.array for src in sources]), count,
-            self.build_config(), ctypes.byref(single_check), lp, diags, int(group), single),
-            TypeError)
-      elif banded is not None and (dense is not None or any(isinstance(b, tuple) for b in bands)):
-        # entry lists or dense matrices among the constraints: one descriptor per utterance
-        arrays = (_lib.ScArray * count)(*[src.array for src in sources])
-        cons = (_lib.ScConstraintDesc * count)()
-        for desc, b in zip(cons, bands):
-          if isinstance(b, tuple):
-            desc.kind, desc.count = 3, len(b[2])
-            desc.rows, desc.cols = _lib.as_int32_p(b[0]), _lib.as_int32_p(b[1])
-            desc.vals = _lib.as_double_p(b[2])
-          elif b is not None:
-            desc.kind, desc.band = 2, _lib.as_double_p(b)
-        if dense is not None:
-          handle.check(handle.lib.sc_predict_batch_constraint_arrays(
-              handle.raw, arrays, cons, dense, count, self.build_config(), lp, diags, int(group),
-              0), TypeError)
-        else:
-          handle.check(handle.lib.sc_predict_batch_constraints(
-              handle.raw, arrays, cons, count, self.build_config(), lp, diags, int(group)),
-              TypeError)
-      elif banded is not None:
-        arrays = (_lib.ScArray * count)(*[src.array for src in sources])
-        bp = (ctypes.POINTER(ctypes.c_double) * count)(
-            *[None if b is None else _lib.as_double_p(b) for b in bands])
-        handle.check(handle.lib.sc_predict_batch_constrained(
-            handle.raw, arrays, bp, count, self.build_config(), lp, diags, int(group)), TypeError)
-      elif all(src.is_host_f64 for src in sources):
-        # compact float64 host rows: the `double*` forms (sc_predict_batch_arrays runs the same
-        # code on the descriptors of exactly these arrays)
-        xp = (ctypes.POINTER(ctypes.c_double) * count)(
-            *[_lib.as_double_p(src.keep) for src in sources])
-        ns = (ctypes.c_int * count)(*[src.shape[0] for src in sources])
-        if int(group) > 1:
-          handle.check(handle.lib.sc_predict_batch_grouped(
-              handle.raw, xp, ns, d, count, self.build_config(), lp, diags, int(group)),
-              TypeError)
-        else:
-          handle.check(handle.lib.sc_predict_batch_streams(
-              handle.raw, xp, ns, d, count, self.build_config(), lp, diags,
-              max(1, int(streams))), TypeError)
-      else:
-        self._batch_arrays_call(handle, [src.array for src in sources], labels, diags,
-                                int(group), max(1, int(streams)))
-    finally:
-      for src in sources + dense_sources:
-        src.release()
-    self._batch_report(handle, diags, count)
-    if single_check is not None:
-      self.last_batch_single = [bool(v) for v in single]
-      # predict()'s result for a single-cluster utterance: np.array([0] * n)
-      labels = [np.array([0] * l.shape[0]) if one else l
-                for l, one in zip(labels, self.last_batch_single)]
-    return labels
+    form = _batch.Form.make(group, streams)
+    flags = _batch.Flags(autotune_from_entry_state, batch_fallback_condition,
+                         batch_naive_fallback, batch_multi_stage, batch_any_metric)
+    with self._permission_if(_batch.wants_permission(self, form, flags)):
+      plan = _batch.plan(self, form, flags, constraint_matrices, utterances)
+      return _batch.execute(self, plan, form, utterances)
 
-  def _predict_batch_entry_state(self, utterances: typing.Sequence,
-                                 constraint_matrices: typing.Optional[typing.Sequence],
-                                 streams: typing.Optional[int] = None,
-                                 group: typing.Optional[int] = None
-                                 ) -> typing.List[np.ndarray]:
-    """predict_batch(autotune_from_entry_state=True) on a clusterer with AutoTune: every
-    utterance searched from the state the AutoTune object has now -- ONE
-    `sc_predict_batch_autotune` call where the library batch covers the clusterer, else
-    predict() per utterance on a copy of the object."""
-    count = len(utterances)
-    if constraint_matrices is None:
-      constraint_matrices = [None] * count
-    elif len(constraint_matrices) != count:
-      raise ValueError("constraint_matrices must be as long as the batch")
-    sequence = self.refinement_options.refinement_sequence or []
-    if RefinementName.RowWiseThreshold not in sequence:
-      raise ValueError(
-          "AutoTune is only effective when the refinement sequence"
-          "contains RowWiseThreshold")
-    if self.constraint_options is not None:
-      for u, cm in zip(utterances, constraint_matrices):
-        if isinstance(cm, (constraint_lib.ConstraintMatrix, constraint_lib.DenseConstraints)):
-          n = int(np.shape(u)[0])
-          # (predict()'s check and message: _set_constraint)
-          self.constraint_options.constraint_operator.check_input(
-              np.lib.stride_tricks.as_strided(np.zeros(1, dtype=bool), (n, n), (0, 0)), cm)
-    entry = self.autotune
-    try:  # (a metric that is not on the device raises in predict(), as it does today)
-      cosine = _lib.kmeans_metric_code(self.custom_dist) == _lib.KMEANS_METRICS["cosine"]
-    except (ValueError, _lib.UnsupportedOnDeviceError):
-      cosine = False
-    self.autotune = None
-    try:
-      covered = self._library_batch_covers()
-    finally:
-      self.autotune = entry
-    if (covered and cosine and streams is None and (group is None or int(group) > 1) and count and
-        all(c is None or isinstance(c, constraint_lib.ConstraintMatrix)
-            for c in constraint_matrices)):
-      return self._autotune_library_batch(utterances, constraint_matrices,
-                                          16 if group is None else int(group))
-    labels, best_p, diags = [], [], []
-    try:
-      for u, cm in zip(utterances, constraint_matrices):
-        self.autotune = copy.deepcopy(entry)
-        self.last_best_p = None
-        labels.append(self.predict(u, cm))
-        # (None: the utterance left predict() before the search -- fallback, size reduction)
-        best_p.append(self.last_best_p)
-        diags.append(self.last_diag)
-    finally:
-      self.autotune = entry
-    self.last_batch_best_p = best_p
-    self.last_batch_diags = diags
-    self.last_batch_routes = [_lib.BATCH_ROUTE_SINGLE] * count
-    return labels
+  def predict_device_batch(self, arrays: typing.Sequence[_lib.ScArray],
+                           group: int = 16,
+                           batch_fallback_condition: bool = False) -> typing.List[np.ndarray]:
+    """predict_batch for utterances that are already described (`sc_array`s, e.g. the resident
+    centroid buffers of a stream pool) on a clusterer `_library_batch_covers`: one grouped
+    library call, `last_batch_routes` / `last_batch_diags` as after predict_batch.
+    `batch_fallback_condition`: as predict_batch's, for a clusterer
+    `_fallback_condition_covers(min_embeddings_met=True)` (the caller vouches for the rows)."""
+    _lib.kmeans_metric_code(self.custom_dist)  # raises for metrics that are not on the device
+    self.last_batch_single = None
+    plan = _batch.plan_device(self, batch_fallback_condition)
+    return _batch.execute_device(self, plan, _batch.Form(True, int(group), 1), arrays)
 
   def _autotune_library_batch(self, utterances: typing.Sequence,
                               constraint_matrices: typing.Sequence,
                               group: int) -> typing.List[np.ndarray]:
-    """ONE `sc_predict_batch_autotune` call; the checks of _predict_batch_entry_state passed."""
-    for u in utterances:
-      if isinstance(u, np.ndarray) and u.ndim != 2:
-        raise ValueError("all utterances must be (n_i, d) with the same d")
-    count = len(utterances)
-    sources = []
-    try:
-      with _lib.use_device(self.device):
-        for u in utterances:
-          sources.append(_dlpack.describe(u, self._handle))
-      d = sources[0].shape[1]
-      if any(src.shape[1] != d for src in sources):
-        raise ValueError("all utterances must be (n_i, d) with the same d")
-      bands = []
-      for src, cm in zip(sources, constraint_matrices):
-        if cm is None or self.constraint_options is None:
-          bands.append(None)
-          continue
-        n = src.shape[0]
-        band = np.zeros(max(n - 1, 1), dtype=np.float64)  # (n = 1: no values, a valid pointer)
-        band[:n - 1] = cm.band()
-        bands.append(band)
-      labels = [np.empty(src.shape[0], dtype=np.int64) for src in sources]
-      handle = self._handle()
-      lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
-      diags = (_lib.ScDiag * count)()
-      arrays = (_lib.ScArray * count)(*[src.array for src in sources])
-      bp = (ctypes.POINTER(ctypes.c_double) * count)(
-          *[None if b is None else _lib.as_double_p(b) for b in bands])
-      best_p = np.zeros(count, dtype=np.float64)
-      last_p = np.zeros(count, dtype=np.float64)
-      state = self.autotune.to_struct()
-      handle.check(handle.lib.sc_predict_batch_autotune(
-          handle.raw, arrays, bp, count, self.build_config(), ctypes.byref(state), lp, diags,
-          _lib.as_double_p(best_p), int(group), _lib.as_double_p(last_p)), TypeError)
-    finally:
-      for src in sources:
-        src.release()
-    self._batch_report(handle, diags, count)
-    self.last_batch_best_p = [float(p) for p in best_p]
-    # reference closure: p_percentile stays at the last value evaluated (spectral_clusterer.py:277)
-    self.refinement_options.p_percentile = float(last_p[-1])
-    self.last_best_p = float(best_p[-1])
-    self.last_diag = diags[count - 1]
-    return labels
+    """ONE `sc_predict_batch_autotune` call; the checks of `_batch.plan` passed."""
+    return _batch.autotune_call(self, utterances, constraint_matrices, group)
 
+  # ------------------------------------------- what the plan reads of the clusterer
   def _single_check_struct(self) -> typing.Optional[_lib.ScSingleCheck]:
     """The `sc_single_check` of this clusterer's single-cluster test, or None when the condition
     does not read the affinity (FallbackClusterer clusters the embeddings)."""
@@ -1122,31 +812,12 @@ class SpectralClusterer:
     return _lib.ScSingleCheck(code, int(options.single_cluster_affinity_diagonal_offset),
                               float(options.single_cluster_affinity_threshold))
 
-  @staticmethod
-  def _check_single_offsets(single_check: _lib.ScSingleCheck, rows: typing.Sequence[int]) -> None:
-    """AffinityGmmBic needs diagonal_offset < n - 1 for every utterance: the ValueError of
-    `sc_affinity_gmm_bic` (what predict() raises), with the utterance's index."""
-    if single_check.condition != _lib.SC_SINGLE_GMM_BIC:
-      return
-    offset = single_check.diagonal_offset
-    for i, n in enumerate(rows):
-      if offset < 0 or offset >= n - 1:
-        raise ValueError(
-            "single_cluster_affinity_diagonal_offset must be significantly smaller than "
-            "affinity matrix dimension (utterance %d)" % i)
-
   # predict_batch(..., batch_any_metric=True) while its library call runs
   _batch_any_metric = False
 
   def _batch_kmeans_ok(self) -> bool:
-    """Is this clusterer's k-means one the grouped batch runs?  The cosine one; under
-    `batch_any_metric` every metric that is on the device.  False for a metric that is not
-    (predict() raises what it raises today)."""
-    try:
-      metric = _lib.kmeans_metric_code(self.custom_dist)
-    except (ValueError, _lib.UnsupportedOnDeviceError):
-      return False
-    return metric == _lib.KMEANS_METRICS["cosine"] or self._batch_any_metric
+    """Is this clusterer's k-means one the grouped batch runs?  (`_batch.kmeans_ok`)"""
+    return _batch.kmeans_ok(self)
 
   def _metric_needs_permission(self) -> bool:
     """A device metric other than cosine, outside a call that already holds the permission."""
@@ -1170,6 +841,9 @@ class SpectralClusterer:
       self._batch_any_metric = False
       handle.lib.sc_set_batch_any_metric(handle.raw, 0)
 
+  def _permission_if(self, wanted: bool):
+    return self._any_metric_permission() if wanted else contextlib.nullcontext()
+
   def _library_batch_covers(self, min_embeddings_met: bool = False,
                             single_check_covered: bool = False,
                             affinity_input: bool = False) -> bool:
@@ -1182,15 +856,7 @@ class SpectralClusterer:
     four that read the affinity.  `affinity_input`: the caller makes the
     `sc_predict_batch_affinities` call -- the `affinity_function` takes no part, and
     predict_affinity's checks have dealt with the options that read embeddings."""
-    return not (
-        self.autotune is not None or
-        (self.max_spectral_size is not None and not affinity_input) or
-        (self.min_clusters == 1 and
-         not (single_check_covered and self._single_check_struct() is not None)) or
-        (self.fallback_options.spectral_min_embeddings > 1 and not min_embeddings_met and
-         not affinity_input) or
-        (self.affinity_function is not utils.compute_affinity_matrix and not affinity_input) or
-        self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans)
+    return _batch.library_covers(self, min_embeddings_met, single_check_covered, affinity_input)
 
   def _naive_fallback(self) -> bool:
     return (self.fallback_options.fallback_clusterer_type ==
@@ -1211,74 +877,7 @@ class SpectralClusterer:
     fallback, and otherwise what `_library_batch_covers` asks, with cosine k-means.
     `min_embeddings_met` as there.  `naive`: the Naive fallback type is covered as well (the
     caller then makes the `sc_predict_batch_single_naive` call)."""
-    options = self.fallback_options
-    if not (self.min_clusters == 1 and
-            options.single_cluster_condition ==
-            fallback_clusterer.SingleClusterCondition.FallbackClusterer and
-            (options.fallback_clusterer_type ==
-             fallback_clusterer.FallbackClustererType.Agglomerative or
-             (naive and self._naive_fallback()))):
-      return False
-    if (self.autotune is not None or self.max_spectral_size is not None or
-        (options.spectral_min_embeddings > 1 and not min_embeddings_met) or
-        self.affinity_function is not utils.compute_affinity_matrix or
-        self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans):
-      return False
-    return self._batch_kmeans_ok()  # (a metric not on the device: predict() raises as today)
-
-  def _single_fallback_call(self, handle: _lib.Handle, arrays: typing.Sequence[_lib.ScArray],
-                            group: int, naive: bool = False) -> typing.List[np.ndarray]:
-    """ONE `sc_predict_batch_single_fallback` call (`naive`: `sc_predict_batch_single_naive`) on
-    described sources: predict()'s results, `last_batch_single` / `last_batch_routes` /
-    `last_batch_diags` filled."""
-    count = len(arrays)
-    if naive:
-      thresholds = self._naive_thresholds()  # (NaiveClusterer's ValueError, before any launch)
-    for i, a in enumerate(arrays):
-      if int(a.rows) < 2 and not naive:  # (predict()'s ValueError, before anything is launched)
-        raise ValueError("Found array with %d sample(s) while a minimum of 2 is required by "
-                         "AgglomerativeClustering." % int(a.rows))
-    labels = [np.empty(int(a.rows), dtype=np.int64) for a in arrays]
-    lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
-    diags = (_lib.ScDiag * count)()
-    single = (ctypes.c_int32 * count)()
-    if naive:
-      handle.check(handle.lib.sc_predict_batch_single_naive(
-          handle.raw, (_lib.ScArray * count)(*arrays), count, self.build_config(),
-          thresholds[0], thresholds[1], lp, diags, int(group), single), ValueError)
-    else:
-      handle.check(handle.lib.sc_predict_batch_single_fallback(
-          handle.raw, (_lib.ScArray * count)(*arrays), count, self.build_config(),
-          float(self.fallback_options.agglomerative_threshold), lp, diags, int(group), single),
-          ValueError)
-    self._batch_report(handle, diags, count)
-    self.last_batch_single = [bool(v) for v in single]
-    # predict()'s result for a single-cluster utterance: np.array([0] * n)
-    return [np.array([0] * l.shape[0]) if one else l
-            for l, one in zip(labels, self.last_batch_single)]
-
-  def _predict_batch_single_fallback(self, utterances: typing.Sequence,
-                                     group: int) -> typing.List[np.ndarray]:
-    """predict_batch(batch_fallback_condition=True); `_fallback_condition_covers` holds."""
-    for u in utterances:
-      if isinstance(u, np.ndarray) and u.ndim != 2:
-        raise ValueError("all utterances must be (n_i, d) with the same d")
-    if not utterances:
-      self.last_batch_routes, self.last_batch_single, self.last_batch_diags = [], [], []
-      return []
-    sources = []
-    try:
-      with _lib.use_device(self.device):
-        for u in utterances:
-          sources.append(_dlpack.describe(u, self._handle))
-      d = sources[0].shape[1]
-      if any(src.shape[1] != d for src in sources):
-        raise ValueError("all utterances must be (n_i, d) with the same d")
-      return self._single_fallback_call(self._handle(), [src.array for src in sources], group,
-                                        naive=self._naive_fallback())
-    finally:
-      for src in sources:
-        src.release()
+    return _batch.fallback_condition_covers(self, min_embeddings_met, naive)
 
   def _batch_kind(self, n: int) -> int:
     """What predict() does with an utterance of n rows (`_lib.BATCH_KIND_*`): the fallback
@@ -1297,114 +896,16 @@ class SpectralClusterer:
     fallback for the utterances that need one, and centroids that are not fallback members
     themselves (predict() recurses on them).  `naive`: fallback utterances may meet the Naive
     type as well (the caller then makes the `sc_predict_batch_reduced_naive` call)."""
-    options = self.fallback_options
-    if self.max_spectral_size is None and options.spectral_min_embeddings <= 1:
-      return False  # (nothing to reduce: the caller's own answer stands)
-    if (self.autotune is not None or self.min_clusters == 1 or
-        self.affinity_function is not utils.compute_affinity_matrix or
-        self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans):
-      return False
-    if streams is not None or (group is not None and int(group) <= 1):
-      return False
-    if not self._batch_kmeans_ok():
-      return False
-    if (self.max_spectral_size is not None and
-        self.max_spectral_size < options.spectral_min_embeddings):
-      return False
-    try:
-      kinds = [self._batch_kind(int(np.shape(u)[0])) for u in utterances]
-    except (IndexError, TypeError):
-      return False  # (not (n, d): predict() says what is wrong with it)
-    if (_lib.BATCH_KIND_FALLBACK in kinds and options.fallback_clusterer_type !=
-        fallback_clusterer.FallbackClustererType.Agglomerative and
-        not (naive and self._naive_fallback())):
-      return False
-    return True
-
-  def _predict_batch_reduced(self, utterances: typing.Sequence,
-                             group: int) -> typing.List[np.ndarray]:
-    """ONE `sc_predict_batch_reduced` (or `_naive`) call; `_reduced_batch_covers` holds."""
-    for u in utterances:
-      if isinstance(u, np.ndarray) and u.ndim != 2:
-        raise ValueError("all utterances must be (n_i, d) with the same d")
-    count = len(utterances)
-    if count == 0:
-      self.last_batch_routes, self.last_batch_reduced, self.last_batch_diags = [], [], []
-      return []
-    sources = []
-    try:
-      with _lib.use_device(self.device):
-        for u in utterances:
-          sources.append(_dlpack.describe(u, self._handle))
-      d = sources[0].shape[1]
-      if any(src.shape[1] != d for src in sources):
-        raise ValueError("all utterances must be (n_i, d) with the same d")
-      # the fallback utterances meet the Naive type (`_reduced_batch_covers(naive=True)` let
-      # them through): the _naive form of the call
-      naive = self._naive_fallback() and any(
-          self._batch_kind(src.shape[0]) == _lib.BATCH_KIND_FALLBACK for src in sources)
-      if naive:
-        thresholds = self._naive_thresholds()  # (NaiveClusterer's ValueError)
-      # what predict() raises for an utterance, before anything is launched
-      for src in sources:
-        kind = self._batch_kind(src.shape[0])
-        if kind == _lib.BATCH_KIND_FALLBACK and src.shape[0] < 2 and not naive:
-          raise ValueError("Found array with %d sample(s) while a minimum of 2 is required by "
-                           "AgglomerativeClustering." % src.shape[0])
-        if kind == _lib.BATCH_KIND_REDUCED and (
-            self.max_spectral_size < 2 or
-            (self.max_clusters and self.max_spectral_size <= self.max_clusters) or
-            (self.min_clusters and self.max_spectral_size <= self.min_clusters)):
-          raise ValueError("max_spectral_size should be a relatively big number")
-      labels = [np.empty(src.shape[0], dtype=np.int64) for src in sources]
-      handle = self._handle()
-      lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
-      diags = (_lib.ScDiag * count)()
-      kinds = (ctypes.c_int32 * count)()
-      arrays = (_lib.ScArray * count)(*[src.array for src in sources])
-      if naive:
-        handle.check(handle.lib.sc_predict_batch_reduced_naive(
-            handle.raw, arrays, count, self.build_config(), int(self.max_spectral_size or 0),
-            int(self.fallback_options.spectral_min_embeddings), thresholds[0], thresholds[1],
-            lp, diags, int(group), kinds), ValueError)
-      else:
-        handle.check(handle.lib.sc_predict_batch_reduced(
-            handle.raw, arrays, count, self.build_config(), int(self.max_spectral_size or 0),
-            int(self.fallback_options.spectral_min_embeddings),
-            float(self.fallback_options.agglomerative_threshold), lp, diags, int(group), kinds),
-            ValueError)
-    finally:
-      for src in sources:
-        src.release()
-    self._batch_report(handle, diags, count)
-    self.last_batch_reduced = [int(k) for k in kinds]
-    # utils.chain_labels fills np.zeros: a size-reduced utterance's labels are float64, as
-    # predict() returns them
-    return [l.astype(np.float64) if k == _lib.BATCH_KIND_REDUCED else l
-            for l, k in zip(labels, self.last_batch_reduced)]
+    # (nothing to reduce: False, the caller's own answer stands)
+    return _batch.reduced_covers(self, utterances, _batch.Form.make(group, streams).grouped,
+                                 naive)
 
   def _multi_stage_batch_covers(self) -> bool:
     """Is this clusterer one whose predict() `sc_predict_batch_multi_stage` reproduces?
     `min_clusters == 1` with `max_spectral_size` and / or `spectral_min_embeddings` above 1, no
     AutoTune, the default affinity and k-means functions, cosine k-means, and centroids that are
     not fallback members themselves.  (The caller has looked at the form of the batch.)"""
-    options = self.fallback_options
-    if self.min_clusters != 1:
-      return False
-    if self.max_spectral_size is None and options.spectral_min_embeddings <= 1:
-      return False
-    if (self.autotune is not None or
-        self.affinity_function is not utils.compute_affinity_matrix or
-        self.post_eigen_cluster_function is not custom_distance_kmeans.run_kmeans):
-      return False
-    if (self.max_spectral_size is not None and
-        self.max_spectral_size < options.spectral_min_embeddings):
-      return False
-    if not isinstance(options.single_cluster_condition, fallback_clusterer.SingleClusterCondition):
-      return False  # (predict() says what is wrong with it)
-    if not isinstance(options.fallback_clusterer_type, fallback_clusterer.FallbackClustererType):
-      return False
-    return self._batch_kmeans_ok()  # (a metric not on the device: predict() raises as today)
+    return _batch.multi_stage_covers(self)
 
   def _multi_stage_struct(self) -> _lib.ScMultiStage:
     """The `sc_multi_stage` of this clusterer (`_multi_stage_batch_covers` holds); the
@@ -1422,93 +923,6 @@ class SpectralClusterer:
     stage.diagonal_offset = int(options.single_cluster_affinity_diagonal_offset)
     return stage
 
-  def _check_multi_stage_rows(self, stage: _lib.ScMultiStage,
-                              rows: typing.Sequence[int]) -> None:
-    """What predict() raises for an utterance of the multi-stage regime, with the utterance's
-    index, before anything is launched (the library checks the same)."""
-    agglomerative = not self._naive_fallback()
-    few = ("Found array with %d sample(s) while a minimum of 2 is required by "
-           "AgglomerativeClustering. (utterance %d)")
-    for i, n in enumerate(rows):
-      kind = self._batch_kind(n)
-      if kind == _lib.BATCH_KIND_FALLBACK:
-        if n < 2 and agglomerative:
-          raise ValueError(few % (n, i))
-        continue
-      if kind == _lib.BATCH_KIND_REDUCED:
-        if (self.max_spectral_size < 2 or
-            (self.max_clusters and self.max_spectral_size <= self.max_clusters) or
-            self.max_spectral_size <= self.min_clusters):
-          raise ValueError("max_spectral_size should be a relatively big number "
-                           "(utterance %d)" % i)
-        n = self.max_spectral_size  # what is tested: the centroids
-      if stage.single_condition == _lib.SC_SINGLE_GMM_BIC:
-        if stage.diagonal_offset < 0 or stage.diagonal_offset >= n - 1:
-          raise ValueError(
-              "single_cluster_affinity_diagonal_offset must be significantly smaller than "
-              "affinity matrix dimension (utterance %d)" % i)
-      elif stage.single_condition == _lib.SC_SINGLE_BY_FALLBACK and agglomerative and n < 2:
-        raise ValueError(few % (n, i))
-
-  def _predict_batch_multi_stage(self, utterances: typing.Sequence,
-                                 group: int) -> typing.List[np.ndarray]:
-    """predict_batch(batch_multi_stage=True): ONE `sc_predict_batch_multi_stage` call;
-    `_multi_stage_batch_covers` holds."""
-    for u in utterances:
-      if isinstance(u, np.ndarray) and u.ndim != 2:
-        raise ValueError("all utterances must be (n_i, d) with the same d")
-    count = len(utterances)
-    if count == 0:
-      self.last_batch_routes, self.last_batch_reduced, self.last_batch_diags = [], [], []
-      self.last_batch_single = []
-      return []
-    sources = []
-    try:
-      with _lib.use_device(self.device):
-        for u in utterances:
-          sources.append(_dlpack.describe(u, self._handle))
-      d = sources[0].shape[1]
-      if any(src.shape[1] != d for src in sources):
-        raise ValueError("all utterances must be (n_i, d) with the same d")
-      stage = self._multi_stage_struct()
-      self._check_multi_stage_rows(stage, [src.shape[0] for src in sources])
-      labels = [np.empty(src.shape[0], dtype=np.int64) for src in sources]
-      handle = self._handle()
-      lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
-      diags = (_lib.ScDiag * count)()
-      kinds = (ctypes.c_int32 * count)()
-      single = (ctypes.c_int32 * count)()
-      arrays = (_lib.ScArray * count)(*[src.array for src in sources])
-      handle.check(handle.lib.sc_predict_batch_multi_stage(
-          handle.raw, arrays, count, self.build_config(), ctypes.byref(stage), lp, diags,
-          int(group), kinds, single), ValueError)
-    finally:
-      for src in sources:
-        src.release()
-    self._batch_report(handle, diags, count)
-    self.last_batch_reduced = [int(k) for k in kinds]
-    self.last_batch_single = [None if v < 0 else bool(v) for v in single]
-    out = []
-    for l, k, one in zip(labels, self.last_batch_reduced, self.last_batch_single):
-      if k == _lib.BATCH_KIND_REDUCED:
-        out.append(l.astype(np.float64))  # utils.chain_labels fills np.zeros: float64
-      elif one:
-        out.append(np.array([0] * l.shape[0]))  # predict()'s result for one cluster
-      else:
-        out.append(l)
-    return out
-
-  def _batch_arrays_call(self, handle: _lib.Handle, arrays: typing.Sequence[_lib.ScArray],
-                         labels: typing.Sequence[np.ndarray], diags, group: int,
-                         streams: int) -> None:
-    """One `sc_predict_batch_arrays` call on described sources (host or device memory) into
-    the given int64 label arrays and `sc_diag` array."""
-    count = len(arrays)
-    lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
-    handle.check(handle.lib.sc_predict_batch_arrays(
-        handle.raw, (_lib.ScArray * count)(*arrays), count, self.build_config(), lp, diags,
-        group, streams), TypeError)
-
   def _batch_report(self, handle: _lib.Handle, diags, count: int) -> None:
     """`last_batch_diags` / `last_batch_routes` after a library batch call."""
     self.last_batch_diags = list(diags)
@@ -1521,43 +935,3 @@ class SpectralClusterer:
       routes = (ctypes.c_int32 * count)()
       handle.check(report(handle.raw, routes, count))
       self.last_batch_routes = [int(r) for r in routes]
-
-  def predict_device_batch(self, arrays: typing.Sequence[_lib.ScArray],
-                           group: int = 16,
-                           batch_fallback_condition: bool = False) -> typing.List[np.ndarray]:
-    """predict_batch for utterances that are already described (`sc_array`s, e.g. the resident
-    centroid buffers of a stream pool) on a clusterer `_library_batch_covers`: one grouped
-    library call, `last_batch_routes` / `last_batch_diags` as after predict_batch.
-    `batch_fallback_condition`: as predict_batch's, for a clusterer
-    `_fallback_condition_covers(min_embeddings_met=True)` (the caller vouches for the rows)."""
-    _lib.kmeans_metric_code(self.custom_dist)  # raises for metrics that are not on the device
-    count = len(arrays)
-    if batch_fallback_condition and self._fallback_condition_covers(min_embeddings_met=True):
-      handle = self._handle()
-      handle.check(handle.lib.sc_clear_constraint(handle.raw))  # a batch carries none
-      self.last_batch_single = None
-      return self._single_fallback_call(handle, arrays, max(2, int(group)))
-    labels = [np.empty(int(a.rows), dtype=np.int64) for a in arrays]
-    handle = self._handle()
-    handle.check(handle.lib.sc_clear_constraint(handle.raw))  # a batch carries none
-    diags = (_lib.ScDiag * count)()
-    self.last_batch_single = None
-    if self.min_clusters == 1:
-      # (the caller's predicate: _library_batch_covers(single_check_covered=True))
-      single_check = self._single_check_struct()
-      if single_check is None:
-        raise ValueError("predict_device_batch: min_clusters=1 needs a single-cluster condition "
-                         "that reads the affinity")
-      self._check_single_offsets(single_check, [int(a.rows) for a in arrays])
-      lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
-      single = (ctypes.c_int32 * count)()
-      handle.check(handle.lib.sc_predict_batch_single(
-          handle.raw, (_lib.ScArray * count)(*arrays), count, self.build_config(),
-          ctypes.byref(single_check), lp, diags, max(2, int(group)), single), TypeError)
-      self.last_batch_single = [bool(v) for v in single]
-      labels = [np.array([0] * l.shape[0]) if one else l
-                for l, one in zip(labels, self.last_batch_single)]
-    else:
-      self._batch_arrays_call(handle, arrays, labels, diags, int(group), 1)
-    self._batch_report(handle, diags, count)
-    return labels

@@ -10,6 +10,7 @@ import re
 import numpy as np
 import pytest
 
+import _batch_fake
 import spectralcluster_amd as sca
 from spectralcluster_amd import _lib
 from spectralcluster_amd import fallback_clusterer as fb
@@ -82,28 +83,9 @@ class FakeLib:
     return 0
 
 
-class FakeHandle:
-  raw = None
-
-  def __init__(self):
-    self.lib = FakeLib()
-
-  def check(self, rc, *a):
-    assert rc == 0
-
-
 def wire(monkeypatch, c):
   """`c` on a stand-in handle; predict() replaced by a recorder that returns int64 sevens."""
-  handle = FakeHandle()
-  looped = []
-  monkeypatch.setattr(c, "_handle", lambda: handle)
-  monkeypatch.setattr(c, "build_config", lambda: None)
-
-  def fake_predict(u, constraint_matrix=None):
-    looped.append(np.shape(u)[0])
-    return np.full(np.shape(u)[0], 7, dtype=np.int64)
-
-  monkeypatch.setattr(c, "predict", fake_predict)
+  handle, looped = _batch_fake.wire(monkeypatch, c, FakeLib())
   return handle.lib.calls, looped
 
 

@@ -12,6 +12,7 @@ import pytest
 import spectral_oracle as so
 from conftest import golden
 
+import _batch_fake
 import _naive_ref
 import spectralcluster_amd as sca
 from spectralcluster_amd import _lib
@@ -107,28 +108,9 @@ class FakeLib:
                         adaptation=adaptation, group=group)
 
 
-class FakeHandle:
-  raw = None
-
-  def __init__(self):
-    self.lib = FakeLib()
-
-  def check(self, rc, *a):
-    assert rc == 0
-
-
 def wire(monkeypatch, c):
   """`c` on a stand-in handle; predict() replaced by a recorder that returns int64 zeros."""
-  handle = FakeHandle()
-  single = []
-  monkeypatch.setattr(c, "_handle", lambda: handle)
-  monkeypatch.setattr(c, "build_config", lambda: None)
-
-  def fake_predict(u, constraint_matrix=None):
-    single.append(np.shape(u)[0])
-    return np.zeros(np.shape(u)[0], dtype=np.int64)
-
-  monkeypatch.setattr(c, "predict", fake_predict)
+  handle, single = _batch_fake.wire(monkeypatch, c, FakeLib(), marker=0)
   return handle.lib.calls, single
 
 

@@ -10,6 +10,7 @@ import re
 import numpy as np
 import pytest
 
+import _batch_fake
 import spectralcluster_amd as sca
 from spectralcluster_amd import _lib
 from spectralcluster_amd import fallback_clusterer as fb
@@ -118,21 +119,9 @@ class FakeLib:
     return 0
 
 
-class FakeHandle:
-  raw = None
-
-  def __init__(self):
-    self.lib = FakeLib()
-
-  def check(self, rc, invalid_exc=ValueError):
-    assert rc == 0
-
-
 def with_fake_handle(clusterer):
-  handle = FakeHandle()
-  clusterer._handle = lambda: handle
-  clusterer.predict = lambda u, c=None: np.full(np.shape(u)[0], 7)   # (the loop's marker)
-  return handle
+  # (the loop's marker is 7; build_config stays the clusterer's own)
+  return _batch_fake.wire(None, clusterer, FakeLib(), keep_config=True)[0]
 
 
 def test_predict_batch_makes_one_call():
