@@ -1198,6 +1198,45 @@ int sc_stage_sym_eig(sc_handle h, const double* m, int n, int count, int descend
  */
 int sc_stage_eig(sc_handle h, const double* m, int n, int count, int descend,
                  double* values, double* vectors, sc_diag* diag);
+/*
+ * The building blocks on described arrays: each is the ingest of its input (sc_set_embeddings_array's
+ * / sc_set_affinity_array's sources and errors), the launches of the double* entry above, and the
+ * egress of the result into `out` -- an sc_array in host or device memory, fp64 / fp32 / fp16 /
+ * bf16, of exactly the result's shape, with non-negative element strides that map no two indices
+ * to one address: over the dimensions of more than one element, ordered by stride, the small
+ * stride is >= 1 and the big one >= small stride x extent of the small one (SC_ERR_INVALID
+ * otherwise, before anything is launched).  Narrowing is fp64 -> fp32 round to nearest even, then
+ * fp32 -> fp16 / bf16 round to nearest even (PyTorch's tensor.to(dtype)): overflow to +-inf, signed
+ * zeros and subnormals of every width kept, NaN stays NaN.  The results are, bit for bit, the
+ * double* entry's on the widened values, narrowed.  Only elements of the view are written.  The
+ * input is completely inside the handle's buffers before the first byte of `out` is written: `out`
+ * may be the input, any view of it, or overlap it.  All return with the stream drained.
+ */
+/* utils.compute_affinity_matrix: x (n, d) -> out (n, n) */
+int sc_stage_affinity_array(sc_handle h, const sc_array* x, const sc_array* out);
+/* AffinityRefinementOperation.refine: in (n, n) -> out (n, n); op and cfg as sc_stage_refine */
+int sc_stage_refine_array(sc_handle h, int op, const sc_config* cfg, const sc_array* in,
+                          const sc_array* out);
+/* laplacian.compute_laplacian: in (n, n) -> out (n, n) */
+int sc_stage_laplacian_array(sc_handle h, int laplacian_type, const sc_array* in,
+                             const sc_array* out);
+/* utils.compute_sorted_eigenvectors: in (n, n) -> values (1, count), vectors (n, count).  The
+ * symmetric / general decision -- np.allclose(m, m.T, rtol=0, atol=1e-12 * max(max|m|, 1e-300)) on
+ * the widened fp64 values, a matrix with a NaN is not symmetric -- is made on the device from one
+ * pass that leaves max|m|, max|m_ij - m_ji| and a flag; sc_stage_sym_eig or sc_stage_eig runs
+ * accordingly, *symmetric (may be NULL) says which.  count = -1 asks for the default count, which
+ * follows the decision (symmetric: n up to 128, else 64; general: n up to 64, else 32): values and
+ * vectors then have the symmetric default's columns, the leading columns of the count taken are
+ * written, and *symmetric (required) tells the caller which it was -- one pass over the input.
+ * count = 0 (values and vectors are not read, *symmetric required) makes the decision alone. */
+int sc_stage_eig_array(sc_handle h, const sc_array* in, int count, int descend,
+                       const sc_array* values, const sc_array* vectors, int* symmetric);
+/* the egress alone (a test entry, the twin of sc_stage_ingest): host_src, (rows, cols) doubles in
+ * rows, is uploaded into a buffer at the library's own pitch filled with NaNs first -- rows of
+ * matrix_ld(cols) doubles, or with column_major the eigenvector layout E[c * round_up(rows, 16) + r]
+ * -- and leaves through the egress into `out` (rows, cols). */
+int sc_stage_egress(sc_handle h, const double* host_src, int rows, int cols, int column_major,
+                    const sc_array* out);
 /* numpy.random.RandomState(seed).random_sample(count): the MT19937 stream that
  * sklearn's KMeans(random_state=0) (custom_distance_kmeans.py:39-43) consumes.
  * Host-only; exported so the stream can be pinned without a GPU. */

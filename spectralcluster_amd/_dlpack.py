@@ -147,23 +147,28 @@ def _from_numpy(a: np.ndarray, strided: bool = False) -> Source:
   return Source(arr, x, numpy=a)
 
 
-def _from_capsule(capsule, location: int) -> Source:
+def _from_capsule(capsule, location: int, what: str = "embeddings", ndim: int = 2) -> Source:
+  """`ndim` 1 (an output vector): described as one row, (1, count)."""
   address = _get_pointer(capsule, _NAME)  # raises ValueError for a capsule of another name
   managed = ctypes.cast(address, ctypes.POINTER(DLManagedTensor))
   _set_name(capsule, _USED_NAME)  # consumed: the deleter is ours to call now
   src = Source(_lib.ScArray(), None, capsule=capsule, managed=managed)
   try:
     t = managed.contents.dl_tensor
-    if t.ndim != 2:
-      raise ValueError("embeddings must be 2-dimensional")
+    if t.ndim != ndim:
+      raise ValueError("%s must be %d-dimensional" % (what, ndim))
     dtype = _DLPACK_DTYPES.get((t.dtype.code, t.dtype.bits)) if t.dtype.lanes == 1 else None
     if dtype is None:
-      raise TypeError(dtype_message("embeddings", "DLPack type code %d, %d bits, %d lanes"
+      raise TypeError(dtype_message(what, "DLPack type code %d, %d bits, %d lanes"
                                     % (t.dtype.code, t.dtype.bits, t.dtype.lanes)))
-    rows, cols = int(t.shape[0]), int(t.shape[1])
-    row_stride, col_stride = (int(t.strides[0]), int(t.strides[1])) if t.strides else (cols, 1)
+    if ndim == 1:
+      rows, cols = 1, int(t.shape[0])
+      row_stride, col_stride = 0, (int(t.strides[0]) if t.strides else 1)
+    else:
+      rows, cols = int(t.shape[0]), int(t.shape[1])
+      row_stride, col_stride = (int(t.strides[0]), int(t.strides[1])) if t.strides else (cols, 1)
     if row_stride < 0 or col_stride < 0:
-      raise ValueError(negative_strides_message("embeddings"))
+      raise ValueError(negative_strides_message(what))
     itemsize = t.dtype.bits // 8
     assert int(t.byte_offset) % itemsize == 0
     src.array = _lib.ScArray((t.data or 0) + int(t.byte_offset), dtype, location, rows, cols,
@@ -198,3 +203,93 @@ def describe(embeddings, get_handle: typing.Callable[[], "_lib.Handle"],
                      % (int(device_id), handle.device))
   # the producer makes the library's stream wait for whatever still writes the tensor
   return _from_capsule(embeddings.__dlpack__(stream=handle.stream()), _lib.SC_MEM_DEVICE)
+
+
+# ---- results where the caller wants them -------------------------------------------------------
+
+def is_described(obj) -> bool:
+  """Not an ndarray, but something that can say where it is: it is read through DLPack."""
+  return (not isinstance(obj, np.ndarray) and hasattr(obj, "__dlpack__") and
+          hasattr(obj, "__dlpack_device__"))
+
+
+def describe_input(obj, get_handle: typing.Callable[[], "_lib.Handle"]) -> Source:
+  """`describe(..., strided=True)` for the building blocks: whatever is neither an ndarray nor a
+  DLPack object (a list, say) becomes an ndarray first, as `np.ascontiguousarray` made it one."""
+  if not isinstance(obj, np.ndarray) and not is_described(obj):
+    obj = np.asarray(obj)
+  return describe(obj, get_handle, strided=True)
+
+
+def view_is_injective(shape: typing.Sequence[int], strides: typing.Sequence[int]) -> bool:
+  """No two indices of the view share an address -- the rule `out=` is held to: over the
+  dimensions of more than one element, ordered by stride, the small stride is >= 1 and the big
+  one >= small stride * extent of the small one (element strides; the library checks the same)."""
+  dims = sorted((int(s), int(e)) for e, s in zip(shape, strides) if int(e) > 1)
+  if not dims:
+    return True
+  if dims[0][0] < 1:
+    return False
+  return len(dims) == 1 or dims[1][0] >= dims[0][0] * dims[0][1]
+
+
+def describe_out(out, get_handle: typing.Callable[[], "_lib.Handle"],
+                 shape: typing.Tuple[int, ...], what: str = "out") -> Source:
+  """`out` -> the Source the library writes into.  A writeable ndarray (float64 / float32 /
+  float16) or a DLPack object (those and bfloat16) in host memory or on the handle's device, of
+  exactly `shape` (1-D or 2-D), with non-negative strides under which no two indices share an
+  address.  TypeError / ValueError naming `what` for anything else, before any launch."""
+  shape = tuple(int(e) for e in shape)
+  if isinstance(out, np.ndarray):
+    if not out.flags.writeable:
+      raise ValueError("%s is not writeable" % what)
+    dtype = _NUMPY_DTYPES.get(out.dtype)
+    if dtype is None:
+      raise TypeError(dtype_message(what, "numpy %s" % out.dtype))
+    if out.shape != shape:
+      raise ValueError("%s must have shape %s, not %s" % (what, shape, out.shape))
+    if any(s < 0 for s in out.strides):
+      raise ValueError(negative_strides_message(what))
+    if any(s % out.itemsize for s in out.strides):
+      raise ValueError("%s: strides must be multiples of the item size" % what)
+    strides = [s // out.itemsize for s in out.strides]
+    if not view_is_injective(shape, strides):
+      raise ValueError("%s maps two indices to one address (strides %s of shape %s)"
+                       % (what, tuple(strides), shape))
+    if len(shape) == 1:
+      shape, strides = (1,) + shape, [0] + strides
+    arr = _lib.ScArray(out.ctypes.data, dtype, _lib.SC_MEM_HOST, shape[0], shape[1],
+                       strides[0], strides[1])
+    return Source(arr, out, numpy=out)
+  if not (hasattr(out, "__dlpack__") and hasattr(out, "__dlpack_device__")):
+    raise TypeError("%s must be a numpy array or an object with __dlpack__" % what)
+  device_type, device_id = out.__dlpack_device__()
+  device_type = int(device_type)
+  try:
+    if device_type in HOST_DEVICE_TYPES:
+      src = _from_capsule(out.__dlpack__(), _lib.SC_MEM_HOST, what, len(shape))
+    elif device_type in DEVICE_DEVICE_TYPES:
+      handle = get_handle()
+      if int(device_id) != handle.device:
+        raise ValueError("%s is on device %d, the library runs on device %d"
+                         % (what, int(device_id), handle.device))
+      # the producer makes the library's stream wait for whatever still uses the tensor
+      src = _from_capsule(out.__dlpack__(stream=handle.stream()), _lib.SC_MEM_DEVICE, what,
+                          len(shape))
+    else:
+      raise TypeError("%s lives on DLPack device type %d: host memory and ROCm device memory "
+                      "are supported" % (what, device_type))
+  except BufferError as e:  # what a producer answers for memory it will not hand out writeable
+    raise ValueError("%s cannot be exported as writeable memory: %s" % (what, e)) from e
+  a = src.array
+  got = (int(a.cols),) if len(shape) == 1 else (int(a.rows), int(a.cols))
+  try:
+    if got != shape:
+      raise ValueError("%s must have shape %s, not %s" % (what, shape, got))
+    if not view_is_injective((a.rows, a.cols), (a.row_stride, a.col_stride)):
+      raise ValueError("%s maps two indices to one address (strides %s of shape %s)"
+                       % (what, (int(a.row_stride), int(a.col_stride)), got))
+  except Exception:
+    src.release()
+    raise
+  return src

@@ -541,6 +541,17 @@ PROTOTYPES = {
     "sc_stage_eig": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_int, _c_double_p,
                                         _c_double_p, ctypes.POINTER(ScDiag)]),
+    "sc_stage_affinity_array": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),
+                                               ctypes.POINTER(ScArray)]),
+    "sc_stage_refine_array": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.POINTER(ScConfig),
+                                             ctypes.POINTER(ScArray), ctypes.POINTER(ScArray)]),
+    "sc_stage_laplacian_array": (ctypes.c_int, [_handle_t, ctypes.c_int, ctypes.POINTER(ScArray),
+                                                ctypes.POINTER(ScArray)]),
+    "sc_stage_eig_array": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray), ctypes.c_int,
+                                          ctypes.c_int, ctypes.POINTER(ScArray),
+                                          ctypes.POINTER(ScArray), ctypes.POINTER(ctypes.c_int)]),
+    "sc_stage_egress": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.POINTER(ScArray)]),
     "sc_random_state_doubles": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_int,
                                                _c_double_p]),
     "sc_uniform_choice": (ctypes.c_int, [ctypes.c_int, ctypes.c_double]),

@@ -1361,19 +1361,12 @@ __global__ void k_fill(double* p, int n, double v) {
   if (i < n) p[i] = v;
 }
 
-extern "C" int sc_stage_sym_eig(sc_handle h, const double* m, int n, int count, int descend,
-                                double* values, double* vectors, sc_diag* diag) {
-  if (!h) return SC_ERR_INVALID;
-  if (!m || n <= 0 || count <= 0 || count > n || !values)
-    return fail(h, SC_ERR_INVALID, "bad eigen request");
-  SC_HIP(h, hipSetDevice(h->device));
-  SC_TRY(ensure_matrices(h, n, 0));
+// sc_stage_sym_eig behind its upload: the matrix is in B1 (row pitch matrix_ld(n)).  Leaves the
+// `count` values in `values` and, with `vectors`, the eigenvectors in E (column-major, pitch
+// round_up(n, 16)); returns with the stream drained.
+int stage_sym_eig_resident(sc_handle h, int n, int count, int descend, double* values,
+                           bool vectors, sc_diag* diag) {
   const int ld = matrix_ld(n);
-  h->n = n;
-  h->ldn = ld;
-  h->have_affinity = h->have_cropval = false;
-  h->have_x = false;
-  SC_TRY(h2d_matrix(h, m, n, n, ptr<double>(h->B1), ld));
   if (n > kDenseMax && count > kMaxVectors && !vectors) {
     // values only, more than a Krylov basis holds: the dense full-spectrum path
     // (Householder tridiagonalisation + Sturm bisection, eig_dense.hip)
@@ -1442,6 +1435,23 @@ extern "C" int sc_stage_sym_eig(sc_handle h, const double* m, int n, int count, 
   SC_TRY(sym_topk(h, op, n, rq, dg, &dc, &w));
   SC_HIP(h, hipStreamSynchronize(h->stream));
   for (int i = 0; i < count; ++i) values[i] = w[i];
+  return SC_OK;
+}
+
+extern "C" int sc_stage_sym_eig(sc_handle h, const double* m, int n, int count, int descend,
+                                double* values, double* vectors, sc_diag* diag) {
+  if (!h) return SC_ERR_INVALID;
+  if (!m || n <= 0 || count <= 0 || count > n || !values)
+    return fail(h, SC_ERR_INVALID, "bad eigen request");
+  SC_HIP(h, hipSetDevice(h->device));
+  SC_TRY(ensure_matrices(h, n, 0));
+  const int ld = matrix_ld(n);
+  h->n = n;
+  h->ldn = ld;
+  h->have_affinity = h->have_cropval = false;
+  h->have_x = false;
+  SC_TRY(h2d_matrix(h, m, n, n, ptr<double>(h->B1), ld));
+  SC_TRY(stage_sym_eig_resident(h, n, count, descend, values, vectors != nullptr, diag));
   if (vectors) {
     launch_colmajor_to_rowmajor(h->stream, ptr<double>(h->E), round_up(n, 16), n, count,
                                 ptr<double>(h->Eio), count);
@@ -1450,20 +1460,10 @@ extern "C" int sc_stage_sym_eig(sc_handle h, const double* m, int n, int count, 
   return SC_OK;
 }
 
-extern "C" int sc_stage_eig(sc_handle h, const double* m, int n, int count, int descend,
-                            double* values, double* vectors, sc_diag* diag) {
-  if (!h) return SC_ERR_INVALID;
-  if (!m || n <= 0 || count <= 0 || count > n || !values)
-    return fail(h, SC_ERR_INVALID, "bad eigen request");
-  SC_HIP(h, hipSetDevice(h->device));
-  SC_TRY(ensure_matrices(h, n, 0));
-  SC_TRY(ensure_gen(h, n));
+// sc_stage_eig behind its upload, as stage_sym_eig_resident (ensure_gen has run)
+int stage_eig_resident(sc_handle h, int n, int count, int descend, double* values,
+                       sc_diag* diag) {
   const int ld = matrix_ld(n);
-  h->n = n;
-  h->ldn = ld;
-  h->have_affinity = h->have_cropval = false;
-  h->have_x = false;
-  SC_TRY(h2d_matrix(h, m, n, n, ptr<double>(h->B1), ld));
   const int nb = (n + 255) / 256;
   hipLaunchKernelGGL(k_fill, dim3(nb), dim3(256), 0, h->stream, ptr<double>(h->cvec), n, 1.0);
   hipLaunchKernelGGL(k_fill, dim3(nb), dim3(256), 0, h->stream, ptr<double>(h->crvec), n, 1.0);
@@ -1497,6 +1497,24 @@ extern "C" int sc_stage_eig(sc_handle h, const double* m, int n, int count, int 
                   S == ptr<double>(h->B1) ? ptr<double>(h->B2) : ptr<double>(h->B1)));
   SC_HIP(h, hipStreamSynchronize(h->stream));
   for (int i = 0; i < count; ++i) values[i] = w[i];
+  return SC_OK;
+}
+
+extern "C" int sc_stage_eig(sc_handle h, const double* m, int n, int count, int descend,
+                            double* values, double* vectors, sc_diag* diag) {
+  if (!h) return SC_ERR_INVALID;
+  if (!m || n <= 0 || count <= 0 || count > n || !values)
+    return fail(h, SC_ERR_INVALID, "bad eigen request");
+  SC_HIP(h, hipSetDevice(h->device));
+  SC_TRY(ensure_matrices(h, n, 0));
+  SC_TRY(ensure_gen(h, n));
+  const int ld = matrix_ld(n);
+  h->n = n;
+  h->ldn = ld;
+  h->have_affinity = h->have_cropval = false;
+  h->have_x = false;
+  SC_TRY(h2d_matrix(h, m, n, n, ptr<double>(h->B1), ld));
+  SC_TRY(stage_eig_resident(h, n, count, descend, values, diag));
   if (vectors) {
     launch_colmajor_to_rowmajor(h->stream, ptr<double>(h->E), round_up(n, 16), n, count,
                                 ptr<double>(h->Eio), count);

@@ -325,6 +325,20 @@ size_t affinity_group_stage_bytes(const sc_array* as, int count);
 int ingest_affinity_group(sc_handle h, const sc_array* as, int count, double* const* dsts,
                           int* flags, void* stage, void* table, hipStream_t s,
                           int* host_flags = nullptr);
+// ---- results where the caller wants them (egress.hip) -----------------------------------
+// every check of an output descriptor `what`, before any launch or copy: validate_array's, the
+// exact shape, and that no two indices of the view share an address
+int validate_out_array(sc_handle h, const sc_array* a, const char* what, int rows, int cols);
+// The (rows, cols) fp64 values at src -- element (r, c) at src[r * ld + c], or with
+// `column_major` at src[c * ld + r] -- narrowed into the validated `out` on the handle's stream.
+// Returns with the stream drained (a host destination is complete, a device one as well).
+int egress_matrix(sc_handle h, const double* src, int ld, int rows, int cols, bool column_major,
+                  const sc_array& out);
+// sc_stage_sym_eig / sc_stage_eig behind their upload (api.hip): the matrix is in B1, the values
+// land in `values` and the eigenvectors in E (column-major, pitch round_up(n, 16))
+int stage_sym_eig_resident(sc_handle h, int n, int count, int descend, double* values,
+                           bool vectors, sc_diag* diag);
+int stage_eig_resident(sc_handle h, int n, int count, int descend, double* values, sc_diag* diag);
 // sc_run_resident; `from_embeddings` false: the resident affinity is the caller's (no GEMM)
 int run_resident(sc_handle h, const sc_config* cfg, int64_t* labels, sc_diag* diag,
                  bool from_embeddings);

@@ -12,14 +12,12 @@
 #include <climits>
 #include <cstddef>
 
+#include "array_layout.h"
 #include "handle.h"
 
 namespace {
 
 // ---- exact widening ---------------------------------------------------------------------
-struct F16Bits { unsigned short v; };
-struct BF16Bits { unsigned short v; };
-
 __device__ __forceinline__ double widen(double v) { return v; }
 __device__ __forceinline__ double widen(float v) { return (double)v; }
 // bf16 is the upper half of an fp32: place the bits, widen the fp32
@@ -43,12 +41,6 @@ __device__ __forceinline__ double widen(F16Bits b) {
   }
   return __longlong_as_double((long long)bits);
 }
-
-// 16 bytes of source as one load
-template <typename T>
-struct alignas(16) Chunk {
-  T v[16 / sizeof(T)];
-};
 
 // One work item = 16 bytes of a source row = E elements = E doubles of X (E / 2 stores of 16
 // bytes).  A row of X has ldx = round_up(d, 16) doubles and E divides 16, so the items of a row
@@ -111,10 +103,6 @@ void launch_ingest_rows(hipStream_t s, int dtype, const void* src, long long row
   }
 }
 
-size_t dtype_bytes(int dtype) {
-  return dtype == SC_DTYPE_F64 ? 8 : dtype == SC_DTYPE_F32 ? 4 : 2;
-}
-
 // ---- an (n, n) affinity where it is -> fp64 rows of pitch ld, and its symmetry flag ----------
 // A workgroup takes the 64 x 64 tile (I, J), I <= J, together with its mirror (J, I): both are
 // widened into LDS, stored from there in rows (16-byte stores), and compared element against
@@ -129,12 +117,7 @@ size_t dtype_bytes(int dtype) {
 // LDS rows are not padded (two fp64 tiles are the whole 64 KB): the pair index of a row is
 // XOR-ed with the row number instead, which keeps 16-byte pairs together and spreads a column
 // over all banks.
-constexpr int kAffTile = 64;
 enum { kAffVec = 0, kAffRows = 1, kAffCols = 2, kAffVecCols = 3 };
-
-__device__ __forceinline__ int aff_at(int r, int c) {
-  return r * kAffTile + (c ^ ((r & 31) << 1));
-}
 
 // (the source has nr rows and nc columns: an affinity passes n twice, the k-means ingest the
 // transposed view of an (n, dim) input)
@@ -382,14 +365,6 @@ void launch_ingest_columns_typed(hipStream_t s, const void* src, long long row_s
   else
     hipLaunchKernelGGL((k_ingest_columns<T, 1>), dim3(tiles), dim3(256), 0, s, p, row_stride,
                        col_stride, n, dim, X, ld);
-}
-
-// the direction of the memory: the smaller stride (a zero stride repeats one element, it walks
-// nothing)
-long long walked(long long stride) { return stride == 0 ? LLONG_MAX : stride; }
-bool runs_along_columns(long long row_stride, long long col_stride, int dim) {
-  const long long r = walked(row_stride), c = walked(col_stride);
-  return r < c || (r == c && dim == 1);
 }
 
 void launch_ingest_columns(hipStream_t s, int dtype, const void* src, long long row_stride,

@@ -10,6 +10,7 @@ not call these one by one but hands the whole sequence to the device pipeline.
 from __future__ import annotations
 
 import abc
+import ctypes
 import dataclasses
 import enum
 import typing
@@ -104,8 +105,29 @@ class AffinityRefinementOperation(metaclass=abc.ABCMeta):
 
   _OP: typing.ClassVar[RefinementName]
 
-  def refine(self, affinity: np.ndarray) -> np.ndarray:
-    """Run this operator's kernel on the device; returns a new (n, n) array."""
+  def refine(self, affinity, out=None):
+    """Run this operator's kernel on the device; returns a new (n, n) host float64 array, or
+    `out`.
+
+    `affinity` and `out` are what `utils.compute_affinity_matrix` takes and writes: NumPy arrays
+    or DLPack objects, host or device memory, float64 / float32 / float16 / bfloat16, strided
+    views; a device tensor is read in place and the result, rounded to `out`'s dtype, is written
+    where `out` is.  `out` may be `affinity` itself, a view of it (`affinity.T` included) or
+    overlap it in any way: the input is completely inside the library's buffers before the first
+    byte of `out` is written."""
+    from spectralcluster_amd import _dlpack, utils  # (they import this module's siblings)
+    if out is not None or _dlpack.is_described(affinity):
+      if not hasattr(affinity, "shape"):
+        affinity = np.asarray(affinity)
+      self.check_input(affinity)
+
+      def call(handle, sources, outs):
+        cfg = self._config()
+        _lib.sync_blur_weights(handle, cfg)
+        handle.check(handle.lib.sc_stage_refine_array(
+            handle.raw, self._OP.value, cfg, ctypes.byref(sources[0].array),
+            ctypes.byref(outs[0].array)))
+      return utils._stage_on_arrays([affinity], [(out, lambda s: s[0].shape, "out")], call)[0]
     self.check_input(affinity)
     src = np.ascontiguousarray(affinity, dtype=np.float64)
     out = np.empty_like(src)

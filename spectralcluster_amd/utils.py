@@ -20,8 +20,50 @@ class EigenGapType(enum.Enum):
   NormalizedDiff = 2
 
 
-def compute_affinity_matrix(embeddings: np.ndarray) -> np.ndarray:
-  """(cos(x_i, x_j) + 1) / 2 on the fp64 MFMA GEMM (reference utils.py:20-41)."""
+def _stage_on_arrays(inputs, out_specs, call):
+  """A building block on described arrays: `inputs` are read where they are (`_dlpack.describe`'s
+  sources), every `(out, shape, what)` of `out_specs` is written where it is -- or, for an `out`
+  of None, into a new host float64 array -- and `call(handle, sources, outs)` makes the library
+  call.  Returns the list of results (each `out` object itself, or the new array)."""
+  from spectralcluster_amd import _dlpack  # (it imports this module's siblings)
+  handle = _lib.default_handle()
+  held = []
+  try:
+    sources = [_dlpack.describe_input(x, lambda: handle) for x in inputs]
+    held += sources
+    results, outs = [], []
+    for out, shape, what in out_specs:
+      shape = shape(sources) if callable(shape) else shape
+      if out is None:
+        out = np.empty(shape, dtype=np.float64)
+      results.append(out)
+      outs.append(_dlpack.describe_out(out, lambda: handle, shape, what))
+      held.append(outs[-1])
+    call(handle, sources, outs)
+  finally:
+    for src in held:
+      src.release()
+  return results
+
+
+def compute_affinity_matrix(embeddings, out=None):
+  """(cos(x_i, x_j) + 1) / 2 on the fp64 MFMA GEMM (reference utils.py:20-41).
+
+  `embeddings` is whatever predict() takes: a NumPy array, or an object with `__dlpack__` in host
+  memory or on the GPU, float64 / float32 / float16 / bfloat16, any non-negative strides; a device
+  tensor is read in place.  `out`, when given, receives the (n, n) result and is returned: a
+  writeable ndarray (float64 / float32 / float16) or a DLPack object (also bfloat16), host or
+  device, of exactly that shape, with non-negative strides under which no two indices share an
+  address.  The result is the float64 one rounded to nearest even into float32 and from there
+  into float16 / bfloat16.  `out` may be `embeddings`, a view of it or overlap it: the input is
+  completely inside the library's buffers before the first byte of `out` is written.  Without
+  `out` the result is a new host float64 array."""
+  from spectralcluster_amd import _dlpack  # (it imports this module's siblings)
+  if out is not None or _dlpack.is_described(embeddings):
+    def call(handle, sources, outs):
+      handle.check(handle.lib.sc_stage_affinity_array(
+          handle.raw, ctypes.byref(sources[0].array), ctypes.byref(outs[0].array)))
+    return _stage_on_arrays([embeddings], [(out, lambda s: (s[0].shape[0],) * 2, "out")], call)[0]
   x = np.ascontiguousarray(embeddings, dtype=np.float64)
   if x.ndim != 2:
     raise ValueError("embeddings must be 2-dimensional")
@@ -34,8 +76,8 @@ def compute_affinity_matrix(embeddings: np.ndarray) -> np.ndarray:
 
 
 def compute_sorted_eigenvectors(
-    input_matrix: np.ndarray, descend: bool = True,
-    count: typing.Optional[int] = None) -> typing.Tuple[np.ndarray, np.ndarray]:
+    input_matrix, descend: bool = True,
+    count: typing.Optional[int] = None, out=None) -> typing.Tuple:
   """Sorted eigenpairs (reference utils.py:44-71): `np.linalg.eig`, real parts,
   argsort by eigenvalue.
 
@@ -46,7 +88,17 @@ def compute_sorted_eigenvectors(
   extreme ones, default 32; more than 64 -- up to all n -- take the dense Hessenberg route:
   reduction on the device, QR iteration + inverse iteration on the host); eigenvectors of
   complex pairs carry LAPACK's normalisation before `.real`.
+
+  `input_matrix` and `out` are what `compute_affinity_matrix` takes; `out` is a pair (values,
+  vectors) of shapes (count,) and (n, count), and the pair is returned.  With `out` given and
+  `count` None, `count = out[0].shape[0]`; given both, they must agree.  For an input that is read
+  where it is (a DLPack object, or any input when `out` is given) the symmetric / general decision
+  is made on the device, by the rule above on the widened float64 values -- a matrix with a NaN is
+  not symmetric -- from three numbers: the matrix is not downloaded.  `out` may overlap the input.
   """
+  from spectralcluster_amd import _dlpack  # (it imports this module's siblings)
+  if out is not None or _dlpack.is_described(input_matrix):
+    return _sorted_eigenvectors_on_arrays(input_matrix, descend, count, out)
   m = np.ascontiguousarray(input_matrix, dtype=np.float64)
   if m.ndim != 2 or m.shape[0] != m.shape[1]:
     raise ValueError("input_matrix must be square")
@@ -65,6 +117,45 @@ def compute_sorted_eigenvectors(
   handle.check(entry(
       handle.raw, _lib.as_double_p(m), n, count, int(bool(descend)),
       _lib.as_double_p(values), _lib.as_double_p(vectors), None))
+  return values, vectors
+
+
+def _sorted_eigenvectors_on_arrays(input_matrix, descend, count, out):
+  """compute_sorted_eigenvectors through `sc_stage_eig_array`."""
+  from spectralcluster_amd import _dlpack  # (it imports this module's siblings)
+  if out is not None:
+    if not isinstance(out, (tuple, list)) or len(out) != 2:
+      raise TypeError("out must be a pair (values, vectors)")
+    shape = getattr(out[0], "shape", None)
+    if shape is None or len(shape) != 1:
+      raise ValueError("out values must be 1-dimensional, (count,)")
+    if count is None:
+      count = int(shape[0])
+    elif int(count) != int(shape[0]):
+      raise ValueError("out values hold %d entries, count is %d" % (int(shape[0]), int(count)))
+  if not hasattr(input_matrix, "shape"):
+    input_matrix = np.asarray(input_matrix)
+  shape = input_matrix.shape
+  if len(shape) != 2 or shape[0] != shape[1]:
+    raise ValueError("input_matrix must be square")
+  n = int(shape[0])
+  symmetric = ctypes.c_int(0)
+  # count None (only without `out`): the default count follows the decision, which the library
+  # makes -- it is given room for the larger default and says which one it took
+  room = (n if n <= 128 else 64) if count is None else int(count)
+  request = -1 if count is None else room
+  values, vectors = out if out is not None else (None, None)
+
+  def call(handle, sources, outs):
+    handle.check(handle.lib.sc_stage_eig_array(
+        handle.raw, ctypes.byref(sources[0].array), request, int(bool(descend)),
+        ctypes.byref(outs[0].array), ctypes.byref(outs[1].array), ctypes.byref(symmetric)))
+  values, vectors = _stage_on_arrays(
+      [input_matrix], [(values, (room,), "out values"), (vectors, (n, room), "out vectors")],
+      call)
+  if count is None and not symmetric.value:
+    count = n if n <= 64 else 32
+    values, vectors = values[:count].copy(), np.ascontiguousarray(vectors[:, :count])
   return values, vectors
 
 

@@ -1,0 +1,301 @@
+"""The building blocks on described arrays, the part that needs no GPU: the C ABI grew by five
+functions and nothing else, every function and method has its `out` parameter, an `out` is
+described as it lies or refused before anything is launched, and a call that takes today's route
+(an ndarray or a list in, `out=None`) makes exactly today's library call."""
+
+import ctypes
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import spectralcluster_amd as sca
+from spectralcluster_amd import _dlpack
+from spectralcluster_amd import _lib
+from spectralcluster_amd import laplacian
+from spectralcluster_amd import refinement
+from spectralcluster_amd import utils
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ("sc_stage_affinity_array", "sc_stage_refine_array", "sc_stage_laplacian_array",
+               "sc_stage_eig_array", "sc_stage_egress")
+OPERATORS = (refinement.CropDiagonal, refinement.GaussianBlur, refinement.RowWiseThreshold,
+             refinement.Symmetrize, refinement.Diffuse, refinement.RowWiseNormalize)
+
+
+def test_header_binding_library_and_integration_agree_on_the_additions():
+  header = open(os.path.join(ROOT, "include", "spectralcluster_amd.h")).read()
+  integration = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+  declared = set(re.findall(r"^(?:int|const char\*)\s+(sc_[a-z0-9_]+)\s*\(", header, flags=re.M))
+  lib = _lib.load()
+  for name in NEW_SYMBOLS:
+    assert name in declared and name in _lib.PROTOTYPES and hasattr(lib, name), name
+    assert "`%s`" % name in integration, name
+    args = re.search(r"^int\s+%s\s*\(([^;]*)\);" % name, header, flags=re.M | re.S).group(1)
+    assert len(args.split(",")) == len(_lib.PROTOTYPES[name][1]), name
+    assert _lib.PROTOTYPES[name][1][-1] in (ctypes.POINTER(_lib.ScArray),
+                                            ctypes.POINTER(ctypes.c_int))
+  assert declared == set(_lib.PROTOTYPES)
+  # additions only: the version every host test pins
+  assert re.search(r"#define\s+SC_ABI_VERSION\s+11\b", header)
+  assert lib.sc_abi_version() == _lib.SC_ABI_VERSION == 11
+  # a NULL handle is answered, not dereferenced
+  assert lib.sc_stage_egress(None, None, 1, 1, 0, None) == _lib.SC_ERR_INVALID
+  assert lib.sc_stage_eig_array(None, None, 1, 1, None, None, None) == _lib.SC_ERR_INVALID
+
+
+def test_each_of_the_ten_functions_and_methods_has_an_out_parameter():
+  functions = [utils.compute_affinity_matrix, utils.compute_sorted_eigenvectors,
+               laplacian.compute_laplacian, refinement.AffinityRefinementOperation.refine]
+  functions += [op.refine for op in OPERATORS]
+  assert len(functions) == 10
+  for f in functions:
+    p = inspect.signature(f).parameters.get("out")
+    assert p is not None and p.default is None, f.__qualname__
+    assert "out" in (f.__doc__ or ""), f.__qualname__
+  # positional order of the existing parameters is as it was
+  assert list(inspect.signature(utils.compute_sorted_eigenvectors).parameters) == [
+      "input_matrix", "descend", "count", "out"]
+  assert list(inspect.signature(laplacian.compute_laplacian).parameters) == [
+      "affinity", "laplacian_type", "eps", "out"]
+
+
+def no_handle():
+  raise AssertionError("a host array must not ask for the handle")
+
+
+def described(src):
+  a = src.array
+  return (a.data, a.dtype, a.location, a.rows, a.cols, a.row_stride, a.col_stride)
+
+
+BASE = np.zeros((12, 16), dtype=np.float32)
+AT = BASE.ctypes.data
+
+
+@pytest.mark.parametrize("name,view,want", [
+    ("contiguous", lambda b: b[:, :], (AT, 12, 16, 16, 1)),
+    ("row-strided interior view", lambda b: b[2:8, 3:9], (AT + 4 * (2 * 16 + 3), 6, 6, 16, 1)),
+    ("transposed", lambda b: b[:8, :8].T, (AT, 8, 8, 1, 16)),
+    ("step 2 in the columns", lambda b: b[:6, ::2][:, :6], (AT, 6, 6, 16, 2)),
+    ("step 2 in the rows", lambda b: b[::2, :6], (AT, 6, 6, 32, 1)),
+    ("step 2 in both", lambda b: b[::2, ::2][:6, :6], (AT, 6, 6, 32, 2)),
+    ("transposed step 2", lambda b: b[::2, ::2][:6, :6].T, (AT, 6, 6, 2, 32)),
+    ("one row", lambda b: b[3:4, :1], (AT + 4 * 48, 1, 1, 16, 1)),
+])
+def test_an_ndarray_view_is_described_as_it_lies(name, view, want):
+  out = view(BASE)
+  src = _dlpack.describe_out(out, no_handle, out.shape)
+  data, rows, cols, rs, cs = want
+  assert described(src) == (data, _lib.SC_DTYPE_F32, _lib.SC_MEM_HOST, rows, cols, rs, cs), name
+  assert src.numpy is out
+  src.release()
+
+
+def test_a_vector_is_described_as_one_row():
+  v = np.zeros(10, dtype=np.float64)
+  src = _dlpack.describe_out(v[::2], no_handle, (5,), "out values")
+  assert described(src) == (v.ctypes.data, _lib.SC_DTYPE_F64, _lib.SC_MEM_HOST, 1, 5, 0, 2)
+  t = torch.zeros(7, dtype=torch.bfloat16)
+  src = _dlpack.describe_out(t, no_handle, (7,), "out values")
+  assert described(src) == (t.data_ptr(), _lib.SC_DTYPE_BF16, _lib.SC_MEM_HOST, 1, 7, 0, 1)
+  src.release()
+
+
+def test_a_host_dlpack_object_is_described_as_it_lies():
+  t = torch.zeros(12, 16, dtype=torch.float16)
+  for view, want in ((t, (12, 16, 16, 1)), (t[:8, :8].t(), (8, 8, 1, 16)),
+                     (t[1:7:2, 2:8:2], (3, 3, 32, 2))):
+    src = _dlpack.describe_out(view, no_handle, tuple(view.shape))
+    assert described(src) == (view.data_ptr(), _lib.SC_DTYPE_F16, _lib.SC_MEM_HOST) + want
+    src.release()
+
+
+def read_only():
+  a = np.zeros((4, 4))
+  a.flags.writeable = False
+  return a
+
+
+@pytest.mark.parametrize("name,make,shape,exc,match", [
+    ("zero stride", lambda: np.lib.stride_tricks.as_strided(np.zeros(4), (4, 4), (0, 8)), (4, 4),
+     ValueError, "out maps two indices to one address"),
+    ("broadcast view", lambda: np.broadcast_to(np.zeros((1, 4)), (4, 4)), (4, 4), ValueError, "out"),
+    ("writeable broadcast view", lambda: np.lib.stride_tricks.as_strided(
+        np.zeros((1, 4)), (4, 4), (0, 8), writeable=True), (4, 4), ValueError,
+     "out maps two indices to one address"),
+    ("overlapping rows", lambda: np.lib.stride_tricks.as_strided(np.zeros(16), (4, 4), (16, 8)),
+     (4, 4), ValueError, "out maps two indices to one address"),
+    ("overlapping columns", lambda: np.lib.stride_tricks.as_strided(np.zeros(16), (4, 4), (8, 24)),
+     (4, 4), ValueError, "out maps two indices to one address"),
+    ("negative row stride", lambda: np.zeros((4, 4))[::-1], (4, 4), ValueError,
+     "out with negative strides"),
+    ("negative column stride", lambda: np.zeros((4, 4))[:, ::-1], (4, 4), ValueError,
+     "out with negative strides"),
+    ("read-only", read_only, (4, 4), ValueError, "out is not writeable"),
+    ("wrong shape", lambda: np.zeros((4, 5)), (4, 4), ValueError, r"out must have shape \(4, 4\)"),
+    ("wrong number of dimensions", lambda: np.zeros(16), (4, 4), ValueError, "out must have shape"),
+    ("integer dtype", lambda: np.zeros((4, 4), dtype=np.int32), (4, 4), TypeError,
+     "out must be float64, float32, float16 or bfloat16"),
+    ("longdouble", lambda: np.zeros((4, 4), dtype=np.longdouble), (4, 4), TypeError, "out must be"),
+    ("a list", lambda: [[0.0] * 4] * 4, (4, 4), TypeError, "out must be a numpy array or"),
+    ("integer tensor", lambda: torch.zeros(4, 4, dtype=torch.int64), (4, 4), TypeError,
+     "out must be float64"),
+    ("tensor of the wrong shape", lambda: torch.zeros(4, 3), (4, 4), ValueError,
+     "out must have shape"),
+    ("expanded tensor", lambda: torch.zeros(1, 4).expand(4, 4), (4, 4), ValueError,
+     "out maps two indices to one address"),
+    ("tensor that needs grad", lambda: torch.zeros(4, 4, requires_grad=True), (4, 4), ValueError,
+     "out cannot be exported as writeable memory"),
+    ("1-D tensor for a matrix", lambda: torch.zeros(16), (4, 4), ValueError,
+     "out must be 2-dimensional"),
+])
+def test_what_cannot_be_written_is_refused_by_name(name, make, shape, exc, match):
+  with pytest.raises(exc, match=match):
+    _dlpack.describe_out(make(), no_handle, shape)
+
+
+def test_the_overlap_rule():
+  ok = _dlpack.view_is_injective
+  assert ok((4, 4), (4, 1)) and ok((4, 4), (1, 4)) and ok((4, 4), (8, 2)) and ok((4, 4), (2, 8))
+  assert ok((4, 4), (5, 1)) and not ok((4, 4), (3, 1)) and not ok((4, 4), (1, 3))
+  assert not ok((4, 4), (7, 2)) and ok((4, 4), (2, 8)) and not ok((4, 4), (0, 1))
+  assert not ok((4, 4), (4, 0)) and not ok((4, 4), (1, 1))
+  # dimensions of one element address nothing, whatever their stride
+  assert ok((1, 4), (0, 1)) and ok((4, 1), (1, 0)) and ok((1, 1), (0, 0)) and ok((4, 1), (1, 1))
+  assert not ok((1, 4), (0, 0)) and not ok((5,), (0,)) and ok((5,), (3,)) and ok((1,), (0,))
+
+
+class Recorder:
+  """Stands in for the handle: records every library call, answers SC_OK and writes nothing."""
+  device, raw = 0, "raw"
+
+  def __init__(self):
+    self.calls = []
+    self.lib = self
+
+  def __getattr__(self, name):
+    if not name.startswith("sc_"):
+      raise AttributeError(name)
+
+    def call(*args):
+      self.calls.append((name,) + args)
+      return _lib.SC_OK
+    return call
+
+  def check(self, rc, invalid_exc=ValueError):
+    assert rc == _lib.SC_OK
+
+  def stream(self):
+    raise AssertionError("a host input must not ask for the stream")
+
+
+@pytest.fixture
+def recorder(monkeypatch):
+  rec = Recorder()
+  monkeypatch.setattr(_lib, "default_handle", lambda device=None: rec)
+  monkeypatch.setattr(_lib, "sync_blur_weights", lambda handle, cfg: None)
+  return rec
+
+
+def test_todays_route_makes_todays_calls(recorder):
+  for a in (np.eye(6), np.eye(6, dtype=np.float32), np.eye(6, dtype=np.int64), np.eye(6).tolist(),
+            np.eye(6)[:, ::-1]):
+    del recorder.calls[:]
+    got = utils.compute_affinity_matrix(a)
+    assert [c[0] for c in recorder.calls] == ["sc_stage_affinity"]
+    assert isinstance(got, np.ndarray) and got.dtype == np.float64 and got.shape == (6, 6)
+    for op in OPERATORS:
+      del recorder.calls[:]
+      got = op().refine(np.asarray(a))
+      assert [c[0] for c in recorder.calls] == ["sc_stage_refine"]
+      assert got.dtype == np.float64 and got.shape == (6, 6)
+    del recorder.calls[:]
+    laplacian.compute_laplacian(a)
+    assert [c[0] for c in recorder.calls] == ["sc_stage_laplacian"]
+    del recorder.calls[:]
+    values, vectors = utils.compute_sorted_eigenvectors(a)
+    want = "sc_stage_sym_eig" if np.allclose(np.asarray(a), np.asarray(a).T) else "sc_stage_eig"
+    assert [c[0] for c in recorder.calls] == [want]
+    assert values.shape == (6,) and vectors.shape == (6, 6)
+
+
+def test_an_out_or_a_dlpack_input_takes_the_array_entries(recorder):
+  a = np.zeros((6, 6), dtype=np.float32)
+  o = np.zeros((8, 8), dtype=np.float16)[1:7, 1:7]
+  assert utils.compute_affinity_matrix(a[:, :4], out=o) is o
+  (name, raw, x, out), = recorder.calls
+  assert name == "sc_stage_affinity_array"
+  assert (x._obj.rows, x._obj.cols, x._obj.dtype) == (6, 4, _lib.SC_DTYPE_F32)
+  assert (out._obj.data, out._obj.rows, out._obj.cols, out._obj.row_stride, out._obj.col_stride,
+          out._obj.dtype) == (o.ctypes.data, 6, 6, 8, 1, _lib.SC_DTYPE_F16)
+
+  del recorder.calls[:]
+  t = torch.zeros(6, 6, dtype=torch.bfloat16)
+  got = refinement.Symmetrize().refine(t)  # no `out`: a new host float64 array
+  (name, raw, op, cfg, src, out), = recorder.calls
+  assert (name, op) == ("sc_stage_refine_array", refinement.RefinementName.Symmetrize.value)
+  assert src._obj.data == t.data_ptr() and src._obj.dtype == _lib.SC_DTYPE_BF16
+  assert isinstance(got, np.ndarray) and got.dtype == np.float64 and got.shape == (6, 6)
+  assert out._obj.data == got.ctypes.data
+
+  del recorder.calls[:]
+  assert refinement.CropDiagonal().refine(t, out=t.t()) is not None  # aliasing is allowed
+  assert laplacian.compute_laplacian(a, laplacian.LaplacianType.Unnormalized, out=a) is a
+  assert [c[0] for c in recorder.calls] == ["sc_stage_refine_array", "sc_stage_laplacian_array"]
+  assert recorder.calls[1][2] == laplacian.LaplacianType.Unnormalized.value
+
+  del recorder.calls[:]
+  values, vectors = np.zeros(3, dtype=np.float32), torch.zeros(6, 3, dtype=torch.float16)
+  got = utils.compute_sorted_eigenvectors(a, descend=False, out=(values, vectors))
+  assert got[0] is values and got[1] is vectors
+  (name, raw, src, count, descend, pv, pe, sym), = recorder.calls
+  assert (name, count, descend) == ("sc_stage_eig_array", 3, 0)
+  assert (pv._obj.rows, pv._obj.cols, pe._obj.rows, pe._obj.cols) == (1, 3, 6, 3)
+  # count and out must agree
+  with pytest.raises(ValueError, match="count is 4"):
+    utils.compute_sorted_eigenvectors(a, count=4, out=(values, vectors))
+  with pytest.raises(ValueError, match=r"out vectors must have shape \(6, 3\)"):
+    utils.compute_sorted_eigenvectors(a, out=(values, torch.zeros(6, 4)))
+  with pytest.raises(TypeError, match="pair"):
+    utils.compute_sorted_eigenvectors(a, out=values)
+
+  # without count and out ONE call asks for the default count (-1) with room for the larger default
+  del recorder.calls[:]
+  values, vectors = utils.compute_sorted_eigenvectors(t)
+  (name, raw, src, count, descend, pv, pe, sym), = recorder.calls
+  assert (name, count) == ("sc_stage_eig_array", -1)
+  assert (pv._obj.cols, pe._obj.rows, pe._obj.cols) == (6, 6, 6)
+  assert values.shape == (6,) and vectors.shape == (6, 6) and vectors.dtype == np.float64
+  # ... and what comes back is cut to the count the library took (general: 32 of the 64 columns)
+  values, vectors = utils.compute_sorted_eigenvectors(torch.zeros(130, 130))
+  assert recorder.calls[-1][5]._obj.cols == 64
+  assert values.shape == (32,) and vectors.shape == (130, 32) and vectors.flags.c_contiguous
+
+
+def test_the_argument_checks_are_todays_whatever_the_route(recorder):
+  o = np.zeros((6, 6))
+  for bad in (np.zeros((6, 5)), torch.zeros(6, 5)):
+    with pytest.raises(ValueError, match="affinity must be a square matrix"):
+      refinement.CropDiagonal().refine(bad, out=o)
+    with pytest.raises(ValueError, match="affinity must be a square matrix"):
+      laplacian.compute_laplacian(bad, out=o)
+    with pytest.raises(ValueError, match="input_matrix must be square"):
+      utils.compute_sorted_eigenvectors(bad, out=(np.zeros(2), np.zeros((6, 2))))
+  for bad in (np.zeros(6), torch.zeros(6)):
+    with pytest.raises(ValueError, match="affinity must be 2-dimensional"):
+      refinement.Diffuse().refine(bad, out=o)
+    with pytest.raises(ValueError, match="embeddings must be 2-dimensional"):
+      utils.compute_affinity_matrix(bad, out=o)
+  with pytest.raises(TypeError, match="laplacian_type must be a LaplacianType"):
+    laplacian.compute_laplacian(torch.zeros(6, 6), 4)
+  with pytest.raises(sca.UnsupportedOnDeviceError):
+    laplacian.compute_laplacian(torch.zeros(6, 6), eps=1e-9, out=o)
+  with pytest.raises(TypeError, match="float64, float32, float16 or bfloat16"):
+    refinement.CropDiagonal().refine(torch.zeros(6, 6, dtype=torch.int32))
+  with pytest.raises(ValueError, match=r"out must have shape \(6, 6\)"):
+    utils.compute_affinity_matrix(np.zeros((6, 3)), out=np.zeros((6, 3)))
+  assert recorder.calls == []
