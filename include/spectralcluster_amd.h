@@ -242,7 +242,12 @@ int sc_struct_sizes(int* config_bytes, int* diag_bytes);
  * kernel.  All arithmetic stays fp64: widening fp32 / fp16 / bf16 is exact for every bit
  * pattern (subnormals, +-0, +-inf; a NaN stays a NaN), so every result is bit for bit what the
  * caller would get from the values converted to double on the host. */
-enum { SC_DTYPE_F64 = 0, SC_DTYPE_F32 = 1, SC_DTYPE_F16 = 2, SC_DTYPE_BF16 = 3 };
+enum {
+  SC_DTYPE_F64 = 0, SC_DTYPE_F32 = 1, SC_DTYPE_F16 = 2, SC_DTYPE_BF16 = 3,
+  /* label arrays only (sc_cluster_centroids_arrays, sc_labels_egress): every other entry answers
+   * them as it answers any dtype it does not know, SC_ERR_INVALID "unknown dtype" */
+  SC_DTYPE_I64 = 4, SC_DTYPE_I32 = 5
+};
 enum { SC_MEM_HOST = 0, SC_MEM_DEVICE = 1 };
 typedef struct sc_array {
   const void* data;    /* first element (a byte offset of the owner already applied) */
@@ -1237,6 +1242,47 @@ int sc_stage_eig_array(sc_handle h, const sc_array* in, int count, int descend,
  * -- and leaves through the egress into `out` (rows, cols). */
 int sc_stage_egress(sc_handle h, const double* host_src, int rows, int cols, int column_major,
                     const sc_array* out);
+/*
+ * Labels and centroids where the caller wants them.
+ *
+ * A LABEL ARRAY is an sc_array of one row: rows = 1, cols = n, col_stride >= 0 the step between
+ * entries in elements (row_stride addresses nothing), in host memory or on the handle's device.
+ * As an input its dtype is SC_DTYPE_I64 or SC_DTYPE_I32, or SC_DTYPE_F64 / SC_DTYPE_F32 holding
+ * integral values (predict() returns float64 labels for a size-reduced utterance); as an output
+ * SC_DTYPE_I64 or SC_DTYPE_I32 with col_stride >= 1 (n > 1).
+ *
+ * sc_cluster_centroids_arrays: utils.get_cluster_centroids (reference utils.py:159-176) for
+ * `count` >= 1 members in one call.  Member i has embeddings xs[i] (whatever
+ * sc_set_embeddings_array takes; all members the same d; a device source is read in place, host
+ * sources of the call travel in one copy at their own width), labels labels[i] of xs[i].rows
+ * entries, and the result outs[i]: fp64 / fp32 / fp16 / bf16, host or device, outs[i].cols = d,
+ * outs[i].rows >= k_i = max(labels[i]) + 1, strides under sc_stage_*_array's rule.  Rows 0 .. k_i - 1
+ * of outs[i] are written and nothing else; ks[i] (ks may be NULL) returns k_i.  With outs = NULL
+ * (ks required) the call validates the labels and returns the k_i alone, for a caller that has to
+ * allocate first.
+ *   out[c][f] is the sum from 0.0 of the widened fp64 values x[r][f] over the rows r with
+ *   label c, in ascending r, divided by their number -- the bits of np.mean(x[labels == c],
+ *   axis=0) and of sc_cluster_centroids -- narrowed by sc_stage_*_array's rule.  A label in
+ *   0 .. k - 1 that no row carries gives a row of NaN (0 / 0, as the reference); rows with a
+ *   negative label belong to no cluster (the reference's `labels == c` never matches them).
+ * Two steps: one pass over all members' labels (validation, k_i; device labels by one kernel, host
+ * labels on the host), then a stable counting sort of each member's labels on the device and the
+ * means from each cluster's own rows.  At most three launches per 32768 members and two
+ * synchronisations of the stream, whatever `count` is.  SC_ERR_INVALID with a message that names
+ * the member's index, before a byte of any outs[i] is written: a label array that does not hold
+ * xs[i].rows entries; a float label that is not integral or not finite; a label of 2^31 - 1 or
+ * more; outs[i].cols != d; outs[i].rows < k_i; an outs[i] in device memory whose byte range
+ * overlaps a device xs[j] or labels[j] of the call.  Returns with the stream drained.
+ */
+int sc_cluster_centroids_arrays(sc_handle h, const sc_array* xs, const sc_array* labels, int count,
+                                const sc_array* outs, int32_t* ks);
+/* Labels out: labels[i] (int64, host, outs[i].cols entries -- what every predict entry returns)
+ * into the label array outs[i], for `count` >= 1 members.  Host destinations are written on the
+ * host; the device destinations of the call take one upload, one launch per 32768 of them and one
+ * synchronisation.  Every descriptor is checked before anything is written; only the entries of
+ * the views are written.  An int32 destination takes the low 32 bits (labels are cluster numbers
+ * below n). */
+int sc_labels_egress(sc_handle h, const int64_t* const* labels, int count, const sc_array* outs);
 /* numpy.random.RandomState(seed).random_sample(count): the MT19937 stream that
  * sklearn's KMeans(random_state=0) (custom_distance_kmeans.py:39-43) consumes.
  * Host-only; exported so the stream can be pinned without a GPU. */

@@ -8,7 +8,9 @@ a `Form`, ask for a `Plan` and `execute` it:
   described()  is the marshalling preamble of every family: the inputs described as `sc_array`s,
                the label, pointer and diagnostics arrays allocated, every source released on exit;
   execute()    runs the family's executor: what predict() would raise for an utterance, the ONE
-               library call with its arguments, the report, predict()'s result dtypes.
+               library call with its arguments, the report, predict()'s result dtypes;
+  labels_into() is the way out of every entry that was given `out=`: the destinations validated
+               before the executor runs, one `sc_labels_egress` call after it.
 
 Everything goes through `c._handle()`, `c.build_config()` and `c.predict(...)` on the instance.
 `tests/golden/batch_dispatch.json` records what each call of a grid of them does.
@@ -724,8 +726,68 @@ _EXECUTORS = {
 }
 
 
-def execute(c, plan: Plan, form: Form, inputs) -> typing.List[np.ndarray]:
-  return _EXECUTORS[plan.family](c, plan, form, inputs)
+def execute(c, plan: Plan, form: Form, inputs, out=None) -> typing.List:
+  """`out` (a list with one label destination per input, or None): every one is validated before
+  the executor runs, and receives its input's labels after it -- whatever the family."""
+  if out is None:
+    return _EXECUTORS[plan.family](c, plan, form, inputs)
+  if len(out) != len(inputs):
+    raise ValueError("out must be as long as the batch")
+  return labels_into(c, out, [rows_of(c, u) for u in inputs],
+                     lambda: _EXECUTORS[plan.family](c, plan, form, inputs))
+
+
+# ----------------------------------------------------------------- labels out
+def rows_of(c, array) -> int:
+  """n of an input of a predict entry: its `shape` where it has one (an ndarray, a tensor);
+  an object that only speaks DLPack is described, as the entry will describe it, and says n
+  that way; anything else is what predict() refuses."""
+  shape = getattr(array, "shape", None)
+  if shape is None and _dlpack.is_described(array):
+    with _lib.use_device(c.device):
+      src = _dlpack.describe(array, c._handle, strided=True)
+    try:
+      return src.shape[0]
+    finally:
+      src.release()
+  if shape is None or len(shape) == 0:
+    raise TypeError("embeddings must be a numpy array")
+  return int(shape[0])
+
+
+def exact_int64(labels) -> np.ndarray:
+  """The labels a predict entry returned, as contiguous int64: the float64 labels of a
+  size-reduced utterance (utils.chain_labels) are converted exactly."""
+  a = np.asarray(labels)
+  as_int = np.ascontiguousarray(a, dtype=np.int64)
+  if a.dtype.kind == "f" and not np.array_equal(as_int, a):
+    raise ValueError("labels are not integral")
+  return as_int
+
+
+def labels_into(c, outs: typing.Sequence, rows: typing.Sequence[int], run) -> typing.List:
+  """The label egress of every predict entry: `outs[i]` -- a 1-D int64 / int32 array of exactly
+  `rows[i]` entries, NumPy or DLPack, host or the clusterer's device, any stride >= 1 -- is
+  described (`_dlpack.describe_labels_out`: type, dtype, length, writeability, stride, device)
+  before `run()` launches anything, and receives the labels `run()` returns in ONE
+  `sc_labels_egress` call.  Returns `outs` as a list."""
+  held = []
+  try:
+    with _lib.use_device(c.device):
+      for i, (o, n) in enumerate(zip(outs, rows)):
+        held.append(_dlpack.describe_labels_out(o, c._handle, n,
+                                                "out" if len(outs) == 1 else "out %d" % i))
+    labels = [exact_int64(l) for l in run()]
+    count = len(held)
+    if count:
+      handle = c._handle()
+      lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
+      handle.check(handle.lib.sc_labels_egress(
+          handle.raw, lp, count, (_lib.ScArray * count)(*[src.array for src in held])))
+  finally:
+    for src in held:
+      src.release()
+  return list(outs)
 
 
 def execute_device(c, plan: Plan, form: Form, arrays: typing.Sequence[_lib.ScArray]):

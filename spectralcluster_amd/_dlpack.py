@@ -25,12 +25,25 @@ HOST_DEVICE_TYPES = (KDL_CPU, KDL_ROCM_HOST)
 # (a ROCm build of PyTorch may report its device memory as kDLCUDA)
 DEVICE_DEVICE_TYPES = (KDL_ROCM, KDL_CUDA)
 # DLDataTypeCode
-KDL_FLOAT, KDL_BFLOAT = 2, 4
+KDL_INT, KDL_FLOAT, KDL_BFLOAT = 0, 2, 4
 
 _NUMPY_DTYPES = {np.dtype(np.float64): _lib.SC_DTYPE_F64, np.dtype(np.float32): _lib.SC_DTYPE_F32,
                  np.dtype(np.float16): _lib.SC_DTYPE_F16}
 _DLPACK_DTYPES = {(KDL_FLOAT, 64): _lib.SC_DTYPE_F64, (KDL_FLOAT, 32): _lib.SC_DTYPE_F32,
                   (KDL_FLOAT, 16): _lib.SC_DTYPE_F16, (KDL_BFLOAT, 16): _lib.SC_DTYPE_BF16}
+# label arrays (`describe_labels` / `describe_labels_out`): int64 / int32; as an input also float64 /
+# float32 holding integral values (predict() returns float64 labels for a size-reduced utterance)
+_LABEL_NUMPY_DTYPES = {np.dtype(np.int64): _lib.SC_DTYPE_I64, np.dtype(np.int32): _lib.SC_DTYPE_I32}
+_LABEL_NUMPY_FLOATS = {np.dtype(np.float64): _lib.SC_DTYPE_F64,
+                       np.dtype(np.float32): _lib.SC_DTYPE_F32}
+_LABEL_DLPACK_DTYPES = {(KDL_INT, 64): _lib.SC_DTYPE_I64, (KDL_INT, 32): _lib.SC_DTYPE_I32}
+_LABEL_DLPACK_INPUTS = {(KDL_INT, 64): _lib.SC_DTYPE_I64, (KDL_INT, 32): _lib.SC_DTYPE_I32,
+                        (KDL_FLOAT, 64): _lib.SC_DTYPE_F64, (KDL_FLOAT, 32): _lib.SC_DTYPE_F32}
+# the largest label: k = max + 1 is an int32 as well
+MAX_LABEL = 2**31 - 2
+# bytes of an element, by sc_array.dtype
+ITEM_BYTES = {_lib.SC_DTYPE_F64: 8, _lib.SC_DTYPE_F32: 4, _lib.SC_DTYPE_F16: 2,
+              _lib.SC_DTYPE_BF16: 2, _lib.SC_DTYPE_I64: 8, _lib.SC_DTYPE_I32: 4}
 
 
 class DLDevice(ctypes.Structure):
@@ -147,8 +160,12 @@ def _from_numpy(a: np.ndarray, strided: bool = False) -> Source:
   return Source(arr, x, numpy=a)
 
 
-def _from_capsule(capsule, location: int, what: str = "embeddings", ndim: int = 2) -> Source:
-  """`ndim` 1 (an output vector): described as one row, (1, count)."""
+def _from_capsule(capsule, location: int, what: str = "embeddings", ndim: int = 2,
+                  dtypes=None, dtype_error=None) -> Source:
+  """`ndim` 1 (a vector): described as one row, (1, count).  `dtypes` / `dtype_error`: the DLPack
+  dtypes taken and the TypeError text for another one (default: the four float dtypes)."""
+  dtypes = _DLPACK_DTYPES if dtypes is None else dtypes
+  dtype_error = dtype_message if dtype_error is None else dtype_error
   address = _get_pointer(capsule, _NAME)  # raises ValueError for a capsule of another name
   managed = ctypes.cast(address, ctypes.POINTER(DLManagedTensor))
   _set_name(capsule, _USED_NAME)  # consumed: the deleter is ours to call now
@@ -157,10 +174,10 @@ def _from_capsule(capsule, location: int, what: str = "embeddings", ndim: int = 
     t = managed.contents.dl_tensor
     if t.ndim != ndim:
       raise ValueError("%s must be %d-dimensional" % (what, ndim))
-    dtype = _DLPACK_DTYPES.get((t.dtype.code, t.dtype.bits)) if t.dtype.lanes == 1 else None
+    dtype = dtypes.get((t.dtype.code, t.dtype.bits)) if t.dtype.lanes == 1 else None
     if dtype is None:
-      raise TypeError(dtype_message(what, "DLPack type code %d, %d bits, %d lanes"
-                                    % (t.dtype.code, t.dtype.bits, t.dtype.lanes)))
+      raise TypeError(dtype_error(what, "DLPack type code %d, %d bits, %d lanes"
+                                  % (t.dtype.code, t.dtype.bits, t.dtype.lanes)))
     if ndim == 1:
       rows, cols = 1, int(t.shape[0])
       row_stride, col_stride = 0, (int(t.strides[0]) if t.strides else 1)
@@ -293,3 +310,141 @@ def describe_out(out, get_handle: typing.Callable[[], "_lib.Handle"],
     src.release()
     raise
   return src
+
+
+# ---- label arrays --------------------------------------------------------------------------
+
+def label_dtype_message(what: str, detail: str) -> str:
+  """The TypeError text for a label array of a dtype that is not taken."""
+  return "%s must be int64 or int32 (%s)" % (what, detail)
+
+
+def label_input_dtype_message(what: str, detail: str) -> str:
+  return ("%s must be int64 or int32, or float64 / float32 holding integral values (%s)"
+          % (what, detail))
+
+
+def _label_capsule(obj, get_handle, what: str, dtypes, dtype_error) -> Source:
+  """A 1-D DLPack object in host memory or on the handle's device -> Source."""
+  device_type, device_id = obj.__dlpack_device__()
+  device_type = int(device_type)
+  try:
+    if device_type in HOST_DEVICE_TYPES:
+      return _from_capsule(obj.__dlpack__(), _lib.SC_MEM_HOST, what, 1, dtypes, dtype_error)
+    if device_type not in DEVICE_DEVICE_TYPES:
+      raise TypeError("%s lives on DLPack device type %d: host memory and ROCm device memory "
+                      "are supported" % (what, device_type))
+    handle = get_handle()
+    if int(device_id) != handle.device:
+      raise ValueError("%s is on device %d, the library runs on device %d"
+                       % (what, int(device_id), handle.device))
+    return _from_capsule(obj.__dlpack__(stream=handle.stream()), _lib.SC_MEM_DEVICE, what, 1,
+                         dtypes, dtype_error)
+  except BufferError as e:  # what a producer answers for memory it will not hand out
+    raise ValueError("%s cannot be exported: %s" % (what, e)) from e
+
+
+def _label_vector(a: np.ndarray, dtype: int, what: str) -> _lib.ScArray:
+  if a.strides[0] < 0:
+    raise ValueError(negative_strides_message(what))
+  if a.strides[0] % a.itemsize:
+    raise ValueError("%s: the stride must be a multiple of the item size" % what)
+  return _lib.ScArray(a.ctypes.data, dtype, _lib.SC_MEM_HOST, 1, a.shape[0], 0,
+                      a.strides[0] // a.itemsize)
+
+
+def describe_labels(labels, get_handle: typing.Callable[[], "_lib.Handle"], n: int,
+                    what: str = "labels") -> Source:
+  """A label array as an input -> Source: 1-D, `n` entries, a NumPy array (anything else that is
+  no DLPack object becomes one first) or a DLPack object, in host memory or on the handle's
+  device, any non-negative stride.  int64 / int32 are read as they are, and so are float64 /
+  float32 holding integral values; host arrays of other integer types are converted on the host.
+  The values of a host NumPy array are checked here (finite, integral, at most `MAX_LABEL`); those
+  of a DLPack object by the library.  TypeError / ValueError naming `what`, before any launch."""
+  if not isinstance(labels, np.ndarray) and not is_described(labels):
+    labels = np.asarray(labels)
+  if not isinstance(labels, np.ndarray):
+    src = _label_capsule(labels, get_handle, what, _LABEL_DLPACK_INPUTS, label_input_dtype_message)
+    if int(src.array.cols) != n:
+      got = int(src.array.cols)
+      src.release()
+      raise ValueError("%s must hold %d entries, not %d" % (what, n, got))
+    return src
+  if labels.ndim != 1:
+    raise ValueError("%s must be 1-dimensional" % what)
+  if labels.shape[0] != n:
+    raise ValueError("%s must hold %d entries, not %d" % (what, n, labels.shape[0]))
+  a = labels
+  dtype = _LABEL_NUMPY_DTYPES.get(a.dtype)
+  if dtype is None:
+    dtype = _LABEL_NUMPY_FLOATS.get(a.dtype)
+    if dtype is not None:
+      if not np.all(np.isfinite(a)) or not np.all(a == np.trunc(a)):
+        raise ValueError("%s: a float label array must hold finite integral values" % what)
+    elif a.dtype.kind in "iub":  # other widths, byte orders, bools: converted on the host
+      if a.dtype.kind == "u" and a.size and int(a.max()) > MAX_LABEL:
+        raise ValueError("%s: a label is above %d" % (what, MAX_LABEL))
+      a, dtype = a.astype(np.int64), _lib.SC_DTYPE_I64
+    else:
+      raise TypeError(label_input_dtype_message(what, "numpy %s" % a.dtype))
+  if a.size and a.max() > MAX_LABEL:
+    raise ValueError("%s: a label is above %d" % (what, MAX_LABEL))
+  return Source(_label_vector(a, dtype, what), a, numpy=a)
+
+
+def describe_labels_out(out, get_handle: typing.Callable[[], "_lib.Handle"], n: int,
+                        what: str = "out") -> Source:
+  """`out` for labels -> the Source they are written into: a writeable 1-D ndarray or DLPack
+  object of int64 or int32 with exactly `n` entries, in host memory or on the handle's device,
+  with a non-negative stride that gives every entry its own address.  TypeError / ValueError
+  naming `what` for anything else, before any launch."""
+  if isinstance(out, np.ndarray):
+    if not out.flags.writeable:
+      raise ValueError("%s is not writeable" % what)
+    dtype = _LABEL_NUMPY_DTYPES.get(out.dtype)
+    if dtype is None:
+      raise TypeError(label_dtype_message(what, "numpy %s" % out.dtype))
+    if out.shape != (n,):
+      raise ValueError("%s must have shape %s, not %s" % (what, (n,), out.shape))
+    src = Source(_label_vector(out, dtype, what), out, numpy=out)
+  elif hasattr(out, "__dlpack__") and hasattr(out, "__dlpack_device__"):
+    src = _label_capsule(out, get_handle, what, _LABEL_DLPACK_DTYPES, label_dtype_message)
+    if int(src.array.cols) != n:
+      got = int(src.array.cols)
+      src.release()
+      raise ValueError("%s must have shape %s, not %s" % (what, (n,), (got,)))
+  else:
+    raise TypeError("%s must be a numpy array or an object with __dlpack__" % what)
+  if n > 1 and int(src.array.col_stride) < 1:
+    src.release()
+    raise ValueError("%s maps two indices to one address (stride 0)" % what)
+  return src
+
+
+def device_overlap(outs: typing.Sequence[Source], sources: typing.Sequence[Source]
+                   ) -> typing.Optional[int]:
+  """The index of the first of `outs` in device memory whose byte range overlaps the byte range
+  of one of `sources` in device memory, or None.  `sc_cluster_centroids_arrays` makes this check
+  itself and is the authority (callers of the C ABI have no other); it is made here as well
+  because every argument error of the Python functions is raised before a library call, as
+  `describe_out` does for shapes and strides."""
+  def byte_range(a):
+    eb = ITEM_BYTES[int(a.dtype)]
+    last = (int(a.rows) - 1) * int(a.row_stride) + (int(a.cols) - 1) * int(a.col_stride)
+    lo = int(a.data or 0)
+    return lo, lo + (last + 1) * eb
+  read = sorted(byte_range(s.array) for s in sources
+                if s.array.location == _lib.SC_MEM_DEVICE and s.array.rows and s.array.cols)
+  if not read:
+    return None
+  starts = np.array([r[0] for r in read], dtype=np.uint64)
+  reach = np.maximum.accumulate(np.array([r[1] for r in read], dtype=np.uint64))
+  for i, out in enumerate(outs):
+    a = out.array
+    if a.location != _lib.SC_MEM_DEVICE or not (a.rows and a.cols):
+      continue
+    lo, hi = byte_range(a)
+    before = int(np.searchsorted(starts, np.uint64(hi), side="left"))
+    if before > 0 and int(reach[before - 1]) > lo:
+      return i
+  return None

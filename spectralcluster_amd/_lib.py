@@ -125,6 +125,8 @@ class ScDiag(ctypes.Structure):
 
 # sc_array.dtype / .location
 SC_DTYPE_F64, SC_DTYPE_F32, SC_DTYPE_F16, SC_DTYPE_BF16 = range(4)
+# label arrays only (sc_cluster_centroids_arrays, sc_labels_egress)
+SC_DTYPE_I64, SC_DTYPE_I32 = 4, 5
 SC_MEM_HOST, SC_MEM_DEVICE = range(2)
 # sc_pool_get: what
 SC_POOL_CACHE, SC_POOL_CENTROIDS = range(2)
@@ -552,6 +554,12 @@ PROTOTYPES = {
                                           ctypes.POINTER(ScArray), ctypes.POINTER(ctypes.c_int)]),
     "sc_stage_egress": (ctypes.c_int, [_handle_t, _c_double_p, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int, ctypes.POINTER(ScArray)]),
+    "sc_cluster_centroids_arrays": (ctypes.c_int, [_handle_t, ctypes.POINTER(ScArray),
+                                                   ctypes.POINTER(ScArray), ctypes.c_int,
+                                                   ctypes.POINTER(ScArray),
+                                                   ctypes.POINTER(ctypes.c_int32)]),
+    "sc_labels_egress": (ctypes.c_int, [_handle_t, ctypes.POINTER(_c_int64_p), ctypes.c_int,
+                                        ctypes.POINTER(ScArray)]),
     "sc_random_state_doubles": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_int,
                                                _c_double_p]),
     "sc_uniform_choice": (ctypes.c_int, [ctypes.c_int, ctypes.c_double]),

@@ -13,85 +13,17 @@
 // Narrowing is fp64 -> fp32 round to nearest even, then fp32 -> fp16 / bf16 round to nearest even
 // (what PyTorch's CPU tensor.to(dtype) computes), done on the bits: no dependence on a denormal
 // mode, as the ingest widens.
+// Labels leave the same way (sc_labels_egress, k_egress_labels): int64 on the host -> the int64 /
+// int32 vector, host or device, of any stride >= 1 that each member of a batch names.
 // The stage entries on described arrays (sc_stage_*_array) are at the end: ingest, the launches
 // of the double* entry, egress.
+#include <climits>
 #include <cstring>
 
 #include "array_layout.h"
 #include "handle.h"
 
 namespace {
-
-// ---- narrowing by bits --------------------------------------------------------------------
-__device__ __forceinline__ unsigned f64_to_f32_bits(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  const unsigned sign = (unsigned)(b >> 32) & 0x80000000u;
-  const unsigned long long a = b & 0x7fffffffffffffffull;
-  if (a >= 0x7ff0000000000000ull) return sign | (a > 0x7ff0000000000000ull ? 0x7fc00000u : 0x7f800000u);
-  const int e = (int)(a >> 52);  // biased by 1023; the fp32 exponent field is e - 896
-  const unsigned long long m = a & 0xfffffffffffffull;
-  if (e >= 897) {
-    if (e - 896 >= 255) return sign | 0x7f800000u;
-    // exponent and the upper 23 mantissa bits; a carry of the rounding runs into the exponent
-    // (up to infinity) as it should
-    unsigned r = ((unsigned)(e - 896) << 23) | (unsigned)(m >> 29);
-    const unsigned rem = (unsigned)m & 0x1fffffffu;
-    if (rem > 0x10000000u || (rem == 0x10000000u && (r & 1u))) ++r;
-    return sign | r;
-  }
-  // a subnormal fp32 (units of 2^-149) or zero: (2^52 + m) * 2^(e - 1075) / 2^-149
-  const int s = 926 - e;
-  if (e == 0 || s > 63) return sign;
-  const unsigned long long M = (1ull << 52) | m;
-  unsigned r = (unsigned)(M >> s);
-  const unsigned long long rem = M & ((1ull << s) - 1ull), half = 1ull << (s - 1);
-  if (rem > half || (rem == half && (r & 1u))) ++r;
-  return sign | r;
-}
-
-__device__ __forceinline__ unsigned short f32_bits_to_f16_bits(unsigned f) {
-  const unsigned sign = (f >> 16) & 0x8000u, a = f & 0x7fffffffu;
-  if (a >= 0x7f800000u) return (unsigned short)(sign | (a > 0x7f800000u ? 0x7e00u : 0x7c00u));
-  const int e = (int)(a >> 23);  // biased by 127; the fp16 exponent field is e - 112
-  const unsigned m = a & 0x7fffffu;
-  if (e >= 113) {
-    if (e - 112 >= 31) return (unsigned short)(sign | 0x7c00u);
-    unsigned r = ((unsigned)(e - 112) << 10) | (m >> 13);
-    const unsigned rem = m & 0x1fffu;
-    if (rem > 0x1000u || (rem == 0x1000u && (r & 1u))) ++r;  // (65520 -> 0x7c00, infinity)
-    return (unsigned short)(sign | r);
-  }
-  // a subnormal fp16 (units of 2^-24) or zero: (2^23 + m) * 2^(e - 150) / 2^-24
-  const int s = 126 - e;
-  if (e == 0 || s > 31) return (unsigned short)sign;
-  const unsigned M = (1u << 23) | m;
-  unsigned r = M >> s;
-  const unsigned rem = M & ((1u << s) - 1u), half = 1u << (s - 1);
-  if (rem > half || (rem == half && (r & 1u))) ++r;
-  return (unsigned short)(sign | r);
-}
-
-__device__ __forceinline__ unsigned short f32_bits_to_bf16_bits(unsigned f) {
-  if ((f & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((f >> 16) | 0x0040u);
-  return (unsigned short)((f + 0x7fffu + ((f >> 16) & 1u)) >> 16);
-}
-
-template <typename T>
-__device__ __forceinline__ T narrow(double v);
-template <>
-__device__ __forceinline__ double narrow<double>(double v) { return v; }
-template <>
-__device__ __forceinline__ float narrow<float>(double v) {
-  return __uint_as_float(f64_to_f32_bits(v));
-}
-template <>
-__device__ __forceinline__ F16Bits narrow<F16Bits>(double v) {
-  return F16Bits{f32_bits_to_f16_bits(f64_to_f32_bits(v))};
-}
-template <>
-__device__ __forceinline__ BF16Bits narrow<BF16Bits>(double v) {
-  return BF16Bits{f32_bits_to_bf16_bits(f64_to_f32_bits(v))};
-}
 
 // ---- destination memory along the source's lines ------------------------------------------
 // kFast (da == 1, base address and line pitch of the destination multiples of 16 bytes): a work
@@ -225,6 +157,26 @@ void launch_egress(hipStream_t s, int dtype, const double* src, int ld, int rows
     case SC_DTYPE_F32: launch_egress_typed<float>(s, src, ld, L, W, dst, dl, da); break;
     case SC_DTYPE_F16: launch_egress_typed<F16Bits>(s, src, ld, L, W, dst, dl, da); break;
     default: launch_egress_typed<BF16Bits>(s, src, ld, L, W, dst, dl, da); break;
+  }
+}
+
+// ---- labels out ----------------------------------------------------------------------------
+// The int64 labels of a batch (one packed array) into the int64 / int32 vector each member names in
+// device memory, any stride >= 1: blockIdx.y is the member, its entries go round the x-blocks.
+struct LabelEgressItem {
+  void* dst;
+  long long stride;  // elements
+  long long src_off; // this member's labels in the packed array
+  int n, dtype;
+};
+__global__ __launch_bounds__(256) void k_egress_labels(const LabelEgressItem* __restrict__ table,
+                                                       int first,
+                                                       const long long* __restrict__ packed) {
+  const LabelEgressItem it = table[first + (int)blockIdx.y];
+  const long long* __restrict__ src = packed + it.src_off;
+  for (int r = (int)(blockIdx.x * 256 + threadIdx.x); r < it.n; r += (int)gridDim.x * 256) {
+    if (it.dtype == SC_DTYPE_I64) static_cast<long long*>(it.dst)[r * it.stride] = src[r];
+    else static_cast<int*>(it.dst)[r * it.stride] = (int)src[r];
   }
 }
 
@@ -365,16 +317,10 @@ int validate_out_array(sc_handle h, const sc_array* a, const char* what, int row
     return fail(h, SC_ERR_INVALID, w + ": strides must not be negative");
   if (!view_is_injective(a->rows, a->cols, a->row_stride, a->col_stride))
     return fail(h, SC_ERR_INVALID, w + ": the view maps two indices to one address");
-  if (a->location == SC_MEM_DEVICE) {
-    hipPointerAttribute_t attr;
-    memset(&attr, 0, sizeof(attr));
-    const hipError_t e = hipPointerGetAttributes(&attr, a->data);
-    if (e != hipSuccess) (void)hipGetLastError();  // (the failed query is sticky otherwise)
-    if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != h->device)
-      return fail(h, SC_ERR_INVALID,
-                  w + ": location is SC_MEM_DEVICE but the pointer is not device memory of the "
-                      "handle's device");
-  }
+  if (a->location == SC_MEM_DEVICE && !is_device_memory_of(h, a->data))
+    return fail(h, SC_ERR_INVALID,
+                w + ": location is SC_MEM_DEVICE but the pointer is not device memory of the "
+                    "handle's device");
   return SC_OK;
 }
 
@@ -451,6 +397,68 @@ extern "C" int sc_stage_egress(sc_handle h, const double* host_src, int rows, in
   hipStreamSynchronize(h->stream);
   hipFree(buf);
   return rc;
+}
+
+extern "C" int sc_labels_egress(sc_handle h, const int64_t* const* labels, int count,
+                                const sc_array* outs) {
+  if (!h) return SC_ERR_INVALID;
+  if (!labels || !outs || count < 1) return fail(h, SC_ERR_INVALID, "labels egress: bad arguments");
+  long long to_device = 0;
+  int device_members = 0, max_n = 0;
+  for (int i = 0; i < count; ++i) {  // every descriptor before the first byte is written
+    if (!labels[i]) return fail(h, SC_ERR_INVALID, "NULL labels");
+    if (outs[i].cols < 0 || outs[i].cols > INT_MAX)
+      return fail(h, SC_ERR_INVALID, "out " + std::to_string(i) + ": bad length");
+    if (outs[i].cols == 0) continue;
+    SC_TRY(validate_label_array(h, outs + i, "out", i, outs[i].cols, true));
+    if (outs[i].location != SC_MEM_DEVICE) continue;
+    to_device += outs[i].cols;
+    ++device_members;
+    max_n = std::max(max_n, (int)outs[i].cols);
+  }
+  for (int i = 0; i < count; ++i) {  // host destinations: written here
+    const sc_array& o = outs[i];
+    if (o.location != SC_MEM_HOST) continue;
+    for (int64_t r = 0; r < o.cols; ++r) {
+      if (o.dtype == SC_DTYPE_I64)
+        static_cast<int64_t*>(const_cast<void*>(o.data))[r * o.col_stride] = labels[i][r];
+      else
+        static_cast<int32_t*>(const_cast<void*>(o.data))[r * o.col_stride] = (int32_t)labels[i][r];
+    }
+  }
+  if (!device_members) return SC_OK;
+  SC_HIP(h, hipSetDevice(h->device));
+  const size_t tab_bytes = ((size_t)device_members * sizeof(LabelEgressItem) + 15) / 16 * 16;
+  SC_TRY(grow(h, h->cen_in, tab_bytes + (size_t)to_device * sizeof(int64_t)));
+  LabelEgressItem* table_d = ptr<LabelEgressItem>(h->cen_in);
+  long long* packed_d = reinterpret_cast<long long*>(ptr<char>(h->cen_in) + tab_bytes);
+  std::vector<LabelEgressItem> table;
+  std::vector<long long> packed;
+  table.reserve(device_members);
+  packed.reserve((size_t)to_device);
+  for (int i = 0; i < count; ++i) {
+    const sc_array& o = outs[i];
+    if (o.location != SC_MEM_DEVICE || o.cols == 0) continue;
+    table.push_back(LabelEgressItem{const_cast<void*>(o.data), o.col_stride,
+                                    (long long)packed.size(), (int)o.cols, o.dtype});
+    packed.insert(packed.end(), labels[i], labels[i] + o.cols);
+  }
+  hipStream_t s = h->stream;
+  SC_HIP(h, hipMemcpyAsync(table_d, table.data(), table.size() * sizeof(LabelEgressItem),
+                           hipMemcpyHostToDevice, s));
+  SC_HIP(h, hipMemcpyAsync(packed_d, packed.data(), packed.size() * sizeof(long long),
+                           hipMemcpyHostToDevice, s));
+  constexpr int kGridY = 32768;  // members per launch where the member is blockIdx.y
+  for (int at = 0; at < device_members; at += kGridY)
+    hipLaunchKernelGGL(k_egress_labels,
+                       dim3((unsigned)std::min((max_n + 255) / 256, 64),
+                            std::min(kGridY, device_members - at)),
+                       dim3(256), 0, s, table_d, at, packed_d);
+  const int launched = check_last(h, "label egress launch");
+  const hipError_t drained = hipStreamSynchronize(s);  // (table and packed are locals)
+  SC_TRY(launched);
+  SC_HIP(h, drained);
+  return SC_OK;
 }
 
 extern "C" int sc_stage_affinity_array(sc_handle h, const sc_array* x, const sc_array* out) {

@@ -90,6 +90,10 @@ struct sc_handle_s {
   // (column-major), residual partials, restart codes, dense Laplacian scratch
   DevBuf crvec, thetai, Vre, Vim, gpart, gsrc, genL, gneg;
   DevBuf ahc_size, ahc_chain, ahc_Z, ahc_lab, ahc_cent;  // size reduction (AHC) scratch
+  // centroids on described arrays (centroids.hip): member table, label extents, packed labels and
+  // the upload of host embeddings | the CSRs and the staging of host outputs.  The label egress
+  // (egress.hip) keeps its table and the labels in the first.
+  DevBuf cen_in, cen_out;
   // batched size reduction (batch_reduce.hip): bytes a wave may take (0: a share of the free
   // memory, sc_set_reduce_wave_bytes), the pinned staging of a wave's tables, merge lists and CSR
   size_t reduce_wave_bytes = 0;
@@ -283,6 +287,8 @@ int predict_sequence(sc_handle h, const int* idx, int count, const sc_array* xs,
                      sc_diag* diags);
 // ---- described sources (ingest.hip) ---------------------------------------------------
 // every check of a descriptor, before any launch or copy (SC_ERR_INVALID + message)
+// is p memory of the handle's device?  (the one pointer query of every descriptor check)
+bool is_device_memory_of(sc_handle h, const void* p);
 int validate_array(sc_handle h, const sc_array* a);
 // ... of every utterance of a batch, and that they share one d: fills ns[i] = rows of xs[i], *d
 // (0 for an empty batch) and whether any source lies on the device (the caller then waits for its
@@ -334,6 +340,11 @@ int validate_out_array(sc_handle h, const sc_array* a, const char* what, int row
 // Returns with the stream drained (a host destination is complete, a device one as well).
 int egress_matrix(sc_handle h, const double* src, int ld, int rows, int cols, bool column_major,
                   const sc_array& out);
+// every check of the label array `what` of member i (centroids.hip): one row of n entries --
+// rows 1, cols n, the column stride >= 0 -- of SC_DTYPE_I64 / I32, as an input also F64 / F32; an
+// `output` has entries that share no address.  No launch, no copy.
+int validate_label_array(sc_handle h, const sc_array* a, const char* what, int i, int64_t n,
+                         bool output);
 // sc_stage_sym_eig / sc_stage_eig behind their upload (api.hip): the matrix is in B1, the values
 // land in `values` and the eigenvectors in E (column-major, pitch round_up(n, 16))
 int stage_sym_eig_resident(sc_handle h, int n, int count, int descend, double* values,

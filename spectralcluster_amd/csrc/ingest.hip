@@ -17,31 +17,6 @@
 
 namespace {
 
-// ---- exact widening ---------------------------------------------------------------------
-__device__ __forceinline__ double widen(double v) { return v; }
-__device__ __forceinline__ double widen(float v) { return (double)v; }
-// bf16 is the upper half of an fp32: place the bits, widen the fp32
-__device__ __forceinline__ double widen(BF16Bits b) {
-  return (double)__uint_as_float((unsigned)b.v << 16);
-}
-// fp16 by bits (no dependence on the fp16 denormal mode): normal numbers move exponent and
-// mantissa into the fp64 fields, subnormals are mantissa * 2^-24 (an exact integer conversion
-// and an exact scaling), exponent 31 becomes exponent 2047 with the payload kept
-__device__ __forceinline__ double widen(F16Bits b) {
-  const unsigned h = b.v;
-  const unsigned long long sign = (unsigned long long)(h >> 15) << 63;
-  const unsigned e = (h >> 10) & 31u, m = h & 1023u;
-  unsigned long long bits;
-  if (e == 31u) {
-    bits = sign | (0x7ffull << 52) | ((unsigned long long)m << 42);
-  } else if (e != 0u) {
-    bits = sign | ((unsigned long long)(e + 1008u) << 52) | ((unsigned long long)m << 42);
-  } else {
-    bits = sign | (unsigned long long)__double_as_longlong((double)(int)m * 0x1p-24);
-  }
-  return __longlong_as_double((long long)bits);
-}
-
 // One work item = 16 bytes of a source row = E elements = E doubles of X (E / 2 stores of 16
 // bytes).  A row of X has ldx = round_up(d, 16) doubles and E divides 16, so the items of a row
 // tile it exactly: items past column d write the zero padding, the item that straddles d reads
@@ -394,6 +369,14 @@ void launch_ingest_columns(hipStream_t s, int dtype, const void* src, long long 
 // ------------------------------------------------------------------------------
 // validation (no launch, no copy)
 // ------------------------------------------------------------------------------
+bool is_device_memory_of(sc_handle h, const void* p) {
+  hipPointerAttribute_t attr;
+  memset(&attr, 0, sizeof(attr));
+  const hipError_t e = hipPointerGetAttributes(&attr, p);
+  if (e != hipSuccess) (void)hipGetLastError();  // (the failed query is sticky otherwise)
+  return e == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == h->device;
+}
+
 int validate_array(sc_handle h, const sc_array* a) {
   if (!a) return fail(h, SC_ERR_INVALID, "embeddings descriptor is NULL");
   if (!a->data || a->rows <= 0 || a->cols <= 0)
@@ -406,16 +389,10 @@ int validate_array(sc_handle h, const sc_array* a) {
     return fail(h, SC_ERR_INVALID, "embeddings: unknown location (SC_MEM_HOST / SC_MEM_DEVICE)");
   if (a->row_stride < 0 || a->col_stride < 0)
     return fail(h, SC_ERR_INVALID, "embeddings: strides must not be negative");
-  if (a->location == SC_MEM_DEVICE) {
-    hipPointerAttribute_t attr;
-    memset(&attr, 0, sizeof(attr));
-    const hipError_t e = hipPointerGetAttributes(&attr, a->data);
-    if (e != hipSuccess) (void)hipGetLastError();  // (the failed query is sticky otherwise)
-    if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != h->device)
-      return fail(h, SC_ERR_INVALID,
-                  "embeddings: location is SC_MEM_DEVICE but the pointer is not device memory of "
-                  "the handle's device");
-  }
+  if (a->location == SC_MEM_DEVICE && !is_device_memory_of(h, a->data))
+    return fail(h, SC_ERR_INVALID,
+                "embeddings: location is SC_MEM_DEVICE but the pointer is not device memory of "
+                "the handle's device");
   return SC_OK;
 }
 

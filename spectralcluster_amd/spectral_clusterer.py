@@ -289,9 +289,15 @@ class SpectralClusterer:
     spectral_labels = self.predict(ahc_centroids)
     return utils.chain_labels(ahc_labels, spectral_labels)
 
-  def predict(self, embeddings, constraint_matrix=None) -> np.ndarray:
+  def predict(self, embeddings, constraint_matrix=None, *, out=None) -> np.ndarray:
     """Cluster `embeddings` (n_samples, n_features); returns int64 labels as a host array
     (reference spectral_clusterer.py:201-314).
+
+    `out` (keyword only): a 1-D int64 or int32 array of exactly n entries -- a NumPy array or an
+    object with `__dlpack__`, in host memory or on the clusterer's GPU, with a non-negative
+    stride -- receives the labels and is returned in the place of the new host array (the
+    float64 labels of a size-reduced utterance are converted exactly).  It is validated before
+    anything is launched.  The labels still pass through the host inside the call.
 
     `embeddings`: a NumPy array, or any object with `__dlpack__` / `__dlpack_device__` -- a
     PyTorch tensor, say -- of float64, float32, float16 or bfloat16, in host memory or on the
@@ -305,6 +311,9 @@ class SpectralClusterer:
     under the `FallbackClusterer` condition, predict() brings a device tensor to the host (up to
     three times when they meet).  `predict_batch([x], batch_multi_stage=True)` runs that regime
     on a single tensor without a host round trip, with the same labels."""
+    if out is not None:
+      return _batch.labels_into(self, [out], [_batch.rows_of(self, embeddings)],
+                                lambda: [self.predict(embeddings, constraint_matrix)])[0]
     with _lib.use_device(self.device):  # helpers without a device argument follow self.device
       source = _dlpack.describe(embeddings, self._handle)
       try:
@@ -430,7 +439,7 @@ class SpectralClusterer:
           "read the affinity")
     return n
 
-  def predict_affinity(self, affinity, constraint_matrix=None) -> np.ndarray:
+  def predict_affinity(self, affinity, constraint_matrix=None, *, out=None) -> np.ndarray:
     """Cluster from an (n, n) affinity the caller already holds -- PLDA or other learned scores,
     raw cosine in [-1, 1], a Gaussian kernel, what a model has just written on the GPU.
 
@@ -448,8 +457,13 @@ class SpectralClusterer:
 
     ValueError, before any device is touched: a matrix that is not 2-D or not square, and the
     options that read embeddings -- n below `fallback_options.spectral_min_embeddings`,
-    `max_spectral_size` below n, `min_clusters == 1` under the `FallbackClusterer` condition."""
+    `max_spectral_size` below n, `min_clusters == 1` under the `FallbackClusterer` condition.
+
+    `out` (keyword only): predict()'s -- the labels go into it and it is returned."""
     n = self._check_affinity_input(affinity)
+    if out is not None:
+      return _batch.labels_into(self, [out], [n],
+                                lambda: [self.predict_affinity(affinity, constraint_matrix)])[0]
     with _lib.use_device(self.device):
       source = _dlpack.describe(affinity, self._handle, strided=True)
       try:
@@ -476,7 +490,9 @@ class SpectralClusterer:
                              constraint_matrices: typing.Optional[typing.Sequence] = None,
                              group: typing.Optional[int] = None,
                              *,
-                             batch_any_metric: bool = False) -> typing.List[np.ndarray]:
+                             batch_any_metric: bool = False,
+                             out: typing.Optional[typing.Sequence] = None
+                             ) -> typing.List[np.ndarray]:
     """`[predict_affinity(a, c) for a, c in zip(affinities, constraint_matrices)]`; host and
     device matrices of any of the four dtypes may be mixed.
 
@@ -502,7 +518,9 @@ class SpectralClusterer:
 
     `batch_any_metric` (keyword only, default False): predict_batch's flag.  With it a
     `custom_dist` other than cosine that is on the device takes routes 1 and 2 as cosine does,
-    constrained or not; see there for how the labels then compare with predict_affinity's."""
+    constrained or not; see there for how the labels then compare with predict_affinity's.
+
+    `out` (keyword only): predict_batch's -- one label destination per matrix."""
     count = len(affinities)
     _batch.check_length(constraint_matrices, count)
     if constraint_matrices is None:
@@ -518,7 +536,7 @@ class SpectralClusterer:
     flags = _batch.Flags(any_metric=batch_any_metric)
     with self._permission_if(_batch.wants_permission(self, form, flags)):
       plan = _batch.plan_affinity(self, form, constraint_matrices, count)
-      return _batch.execute(self, plan, form, affinities)
+      return _batch.execute(self, plan, form, affinities, out)
 
   # -------------------------------------------------------------- batch (new)
   def predict_batch(self, utterances: typing.Sequence,
@@ -530,7 +548,8 @@ class SpectralClusterer:
                     batch_naive_fallback: bool = False,
                     *,
                     batch_multi_stage: bool = False,
-                    batch_any_metric: bool = False
+                    batch_any_metric: bool = False,
+                    out: typing.Optional[typing.Sequence] = None
                     ) -> typing.List[np.ndarray]:
     """Independent predict() calls (the reference has no batch API: a batch is a
     Python loop).
@@ -766,6 +785,13 @@ class SpectralClusterer:
     well, whose eigenvectors are otherwise predict()'s own.  Without the flag, with "cosine",
     or with `group=1` / `streams`, nothing changes; a metric that is not on the device raises
     what predict() raises.
+
+    `out` (keyword only; default None): a list with one entry per utterance, each what
+    predict()'s `out` is -- a 1-D int64 / int32 array of exactly n_i entries, NumPy or DLPack,
+    host or device, views into one flat tensor included.  All of them are validated before
+    anything is launched; after the call, whatever family ran it, the labels are written into
+    them in one `sc_labels_egress` call (one upload and one launch for the device destinations)
+    and the list of `out` entries is returned.
     """
     self.last_batch_single = None
     form = _batch.Form.make(group, streams)
@@ -773,7 +799,7 @@ class SpectralClusterer:
                          batch_naive_fallback, batch_multi_stage, batch_any_metric)
     with self._permission_if(_batch.wants_permission(self, form, flags)):
       plan = _batch.plan(self, form, flags, constraint_matrices, utterances)
-      return _batch.execute(self, plan, form, utterances)
+      return _batch.execute(self, plan, form, utterances, out)
 
   def predict_device_batch(self, arrays: typing.Sequence[_lib.ScArray],
                            group: int = 16,

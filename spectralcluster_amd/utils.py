@@ -193,10 +193,27 @@ def enforce_ordered_labels(labels: np.ndarray) -> np.ndarray:
   return out
 
 
-def get_cluster_centroids(embeddings: np.ndarray, labels: np.ndarray) -> np.ndarray:
+def get_cluster_centroids(embeddings, labels, out=None):
   """Mean embedding of every cluster, (max(labels) + 1, n_features) (reference
   utils.py:159-176); the segmented mean runs on the device and adds the members in index
-  order, as `np.mean(axis=0)` does."""
+  order, as `np.mean(axis=0)` does.
+
+  `embeddings` is whatever predict() takes and `labels` a 1-D array of n entries, each a NumPy
+  array or an object with `__dlpack__` in host memory or on the GPU (labels: int64 / int32, or
+  float64 / float32 holding integral values, any non-negative stride); device tensors are read
+  where they are.  `out`, when given, is a (rows >= k, n_features) array as
+  `compute_affinity_matrix` takes it: rows 0 .. k - 1 are written, nothing else, and `out[:k]` is
+  returned -- a caller who knows `max_clusters` preallocates and never waits to learn k.  `out`
+  in device memory must not overlap a device `embeddings` or `labels`.  The values are, bit for
+  bit, `np.mean(x64[labels == c], axis=0)` narrowed to `out`'s dtype: a label in range(k) that no
+  row carries gives a row of NaN, rows with a negative label belong to no cluster.  Without `out`
+  the result is a new host float64 array (for labels on the device that takes a second library
+  call, which returns k first).  NumPy `embeddings` and `labels` (or lists) with `out=None` run
+  `sc_cluster_centroids`, as they always have."""
+  from spectralcluster_amd import _dlpack  # (it imports this module's siblings)
+  if out is not None or _dlpack.is_described(embeddings) or _dlpack.is_described(labels):
+    return get_cluster_centroids_batch([embeddings], [labels],
+                                       None if out is None else [out])[0]
   x = np.ascontiguousarray(embeddings, dtype=np.float64)
   lab = np.ascontiguousarray(labels, dtype=np.int64)
   if x.ndim != 2 or lab.shape != (x.shape[0],):
@@ -208,6 +225,81 @@ def get_cluster_centroids(embeddings: np.ndarray, labels: np.ndarray) -> np.ndar
       handle.raw, _lib.as_double_p(x), x.shape[0], x.shape[1], _lib.as_int64_p(lab), k,
       _lib.as_double_p(out)))
   return out
+
+
+def get_cluster_centroids_batch(embeddings_list: typing.Sequence, labels_list: typing.Sequence,
+                                out: typing.Optional[typing.Sequence] = None) -> typing.List:
+  """`get_cluster_centroids(e, l, out=o)` for every member of the lists in ONE
+  `sc_cluster_centroids_arrays` call: members of any n, dtype and location may be mixed, all with
+  the same number of columns (as `cosine_agglomerative_clustering_batch`).  `out` is None or a
+  list of the same length; returns the list of `out[i][:k_i]` (new host float64 arrays without
+  `out`).  The library walks all labels once (validation and every k_i), sorts each member's rows
+  by cluster on the device and takes the means from each cluster's own rows: a fixed number of
+  launches and two synchronisations for the whole list.  Every argument is checked before
+  anything is launched; an error names the member's index and leaves every `out` untouched."""
+  from spectralcluster_amd import _dlpack  # (it imports this module's siblings)
+  count = len(embeddings_list)
+  if len(labels_list) != count:
+    raise ValueError("labels_list must be as long as embeddings_list")
+  if out is not None and len(out) != count:
+    raise ValueError("out must be as long as embeddings_list")
+  if count == 0:
+    return []
+  handle = _lib.default_handle()
+  held = []
+  try:
+    xs = []
+    for e in embeddings_list:
+      xs.append(_dlpack.describe_input(e, lambda: handle))
+      held.append(xs[-1])
+    d = xs[0].shape[1]
+    for i, x in enumerate(xs):
+      if x.shape[1] != d:
+        raise ValueError("member %d: all embeddings must be (n_i, d) with the same d" % i)
+    labs = []
+    for i, (x, l) in enumerate(zip(xs, labels_list)):
+      labs.append(_dlpack.describe_labels(l, lambda: handle, x.shape[0], "labels of member %d" % i))
+      held.append(labs[-1])
+    # k where the host can tell: a host label array has been checked and is read here
+    ks = [None if l.numpy is None else (int(l.numpy.max()) + 1 if l.numpy.size else 0)
+          for l in labs]
+    ks = [None if k is None else max(k, 0) for k in ks]
+    x_arr = (_lib.ScArray * count)(*[x.array for x in xs])
+    l_arr = (_lib.ScArray * count)(*[l.array for l in labs])
+    k_arr = (ctypes.c_int32 * count)()
+    if out is None:
+      if any(k is None for k in ks):  # labels on the device: the library says how many clusters
+        handle.check(handle.lib.sc_cluster_centroids_arrays(handle.raw, x_arr, l_arr, count, None,
+                                                            k_arr))
+        ks = [int(k) for k in k_arr]
+      results = [np.empty((k, d), dtype=np.float64) for k in ks]
+    else:
+      results = list(out)
+    outs = []
+    for i, (o, k) in enumerate(zip(results, ks)):
+      what = "out of member %d" % i
+      shape = tuple(int(e) for e in np.shape(o))
+      if len(shape) != 2 or shape[1] != d:
+        raise ValueError("%s must be (rows >= k, %d), not %s" % (what, d, shape))
+      if k is not None and shape[0] < k:
+        raise ValueError("%s has %d rows, the labels make %d clusters" % (what, shape[0], k))
+      if shape[0] == 0:  # room for no cluster (every label negative): nothing is written
+        outs.append(_dlpack.Source(_lib.ScArray(None, _lib.SC_DTYPE_F64, _lib.SC_MEM_HOST, 0, d,
+                                                d, 1), o))
+      else:
+        outs.append(_dlpack.describe_out(o, lambda: handle, shape, what))
+      held.append(outs[-1])
+    clash = _dlpack.device_overlap(outs, xs + labs)
+    if clash is not None:
+      raise ValueError("out of member %d overlaps embeddings or labels of the call in device "
+                       "memory: they are read in place" % clash)
+    o_arr = (_lib.ScArray * count)(*[o.array for o in outs])
+    handle.check(handle.lib.sc_cluster_centroids_arrays(handle.raw, x_arr, l_arr, count, o_arr,
+                                                        k_arr))
+  finally:
+    for src in held:
+      src.release()
+  return [o[:int(k)] for o, k in zip(results, k_arr)]
 
 
 def chain_labels(pre_labels: typing.Optional[np.ndarray],
