@@ -746,10 +746,8 @@ def rows_of(c, array) -> int:
   if shape is None and _dlpack.is_described(array):
     with _lib.use_device(c.device):
       src = _dlpack.describe(array, c._handle, strided=True)
-    try:
+    with src:
       return src.shape[0]
-    finally:
-      src.release()
   if shape is None or len(shape) == 0:
     raise TypeError("embeddings must be a numpy array")
   return int(shape[0])
@@ -771,22 +769,18 @@ def labels_into(c, outs: typing.Sequence, rows: typing.Sequence[int], run) -> ty
   described (`_dlpack.describe_labels_out`: type, dtype, length, writeability, stride, device)
   before `run()` launches anything, and receives the labels `run()` returns in ONE
   `sc_labels_egress` call.  Returns `outs` as a list."""
-  held = []
-  try:
+  with contextlib.ExitStack() as held:
     with _lib.use_device(c.device):
-      for i, (o, n) in enumerate(zip(outs, rows)):
-        held.append(_dlpack.describe_labels_out(o, c._handle, n,
-                                                "out" if len(outs) == 1 else "out %d" % i))
+      described_outs = [held.enter_context(_dlpack.describe_labels_out(
+          o, c._handle, n, "out" if len(outs) == 1 else "out %d" % i))
+                        for i, (o, n) in enumerate(zip(outs, rows))]
     labels = [exact_int64(l) for l in run()]
-    count = len(held)
+    count = len(described_outs)
     if count:
       handle = c._handle()
       lp = (ctypes.POINTER(ctypes.c_int64) * count)(*[_lib.as_int64_p(l) for l in labels])
       handle.check(handle.lib.sc_labels_egress(
-          handle.raw, lp, count, (_lib.ScArray * count)(*[src.array for src in held])))
-  finally:
-    for src in held:
-      src.release()
+          handle.raw, lp, count, (_lib.ScArray * count)(*[src.array for src in described_outs])))
   return list(outs)
 
 

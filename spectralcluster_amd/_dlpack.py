@@ -90,7 +90,8 @@ def negative_strides_message(what: str) -> str:
 
 
 class Source:
-  """An `sc_array` and what keeps its memory alive until `release()`.
+  """An `sc_array` and what keeps its memory alive until `release()` (a context manager: leaving
+  the `with` block releases).
 
   `array`    the descriptor (pass `ctypes.byref(src.array)`),
   `numpy`    the caller's ndarray when the input was one (host branches use it as it is),
@@ -133,6 +134,12 @@ class Source:
       managed.contents.deleter(managed)
     self.keep = None
 
+  def __enter__(self) -> "Source":
+    return self
+
+  def __exit__(self, *exc) -> None:
+    self.release()
+
   def __del__(self):
     try:
       self.release()
@@ -140,102 +147,20 @@ class Source:
       pass
 
 
-def _from_numpy(a: np.ndarray, strided: bool = False) -> Source:
-  if a.ndim != 2:
-    raise ValueError("embeddings must be 2-dimensional")
-  dtype = _NUMPY_DTYPES.get(a.dtype)
-  if (strided and dtype is not None and
-      all(s >= 0 and s % a.itemsize == 0 for s in a.strides)):
-    # a view (a .T, a [::2, ::2] slice) is described as it lies: no host copy of n x n values
-    arr = _lib.ScArray(a.ctypes.data, dtype, _lib.SC_MEM_HOST, a.shape[0], a.shape[1],
-                       a.strides[0] // a.itemsize, a.strides[1] // a.itemsize)
-    return Source(arr, a, numpy=a)
-  if dtype is None:  # ints, bools, longdouble, other byte orders: promoted on the host
-    x = np.ascontiguousarray(a, dtype=np.float64)
-    dtype = _lib.SC_DTYPE_F64
-  else:
-    x = np.ascontiguousarray(a)
-  arr = _lib.ScArray(x.ctypes.data, dtype, _lib.SC_MEM_HOST, x.shape[0], x.shape[1],
-                     x.shape[1], 1)
-  return Source(arr, x, numpy=a)
+def label_dtype_message(what: str, detail: str) -> str:
+  """The TypeError text for a label array of a dtype that is not taken."""
+  return "%s must be int64 or int32 (%s)" % (what, detail)
 
 
-def _from_capsule(capsule, location: int, what: str = "embeddings", ndim: int = 2,
-                  dtypes=None, dtype_error=None) -> Source:
-  """`ndim` 1 (a vector): described as one row, (1, count).  `dtypes` / `dtype_error`: the DLPack
-  dtypes taken and the TypeError text for another one (default: the four float dtypes)."""
-  dtypes = _DLPACK_DTYPES if dtypes is None else dtypes
-  dtype_error = dtype_message if dtype_error is None else dtype_error
-  address = _get_pointer(capsule, _NAME)  # raises ValueError for a capsule of another name
-  managed = ctypes.cast(address, ctypes.POINTER(DLManagedTensor))
-  _set_name(capsule, _USED_NAME)  # consumed: the deleter is ours to call now
-  src = Source(_lib.ScArray(), None, capsule=capsule, managed=managed)
-  try:
-    t = managed.contents.dl_tensor
-    if t.ndim != ndim:
-      raise ValueError("%s must be %d-dimensional" % (what, ndim))
-    dtype = dtypes.get((t.dtype.code, t.dtype.bits)) if t.dtype.lanes == 1 else None
-    if dtype is None:
-      raise TypeError(dtype_error(what, "DLPack type code %d, %d bits, %d lanes"
-                                  % (t.dtype.code, t.dtype.bits, t.dtype.lanes)))
-    if ndim == 1:
-      rows, cols = 1, int(t.shape[0])
-      row_stride, col_stride = 0, (int(t.strides[0]) if t.strides else 1)
-    else:
-      rows, cols = int(t.shape[0]), int(t.shape[1])
-      row_stride, col_stride = (int(t.strides[0]), int(t.strides[1])) if t.strides else (cols, 1)
-    if row_stride < 0 or col_stride < 0:
-      raise ValueError(negative_strides_message(what))
-    itemsize = t.dtype.bits // 8
-    assert int(t.byte_offset) % itemsize == 0
-    src.array = _lib.ScArray((t.data or 0) + int(t.byte_offset), dtype, location, rows, cols,
-                             row_stride, col_stride)
-  except Exception:
-    src.release()
-    raise
-  return src
+def label_input_dtype_message(what: str, detail: str) -> str:
+  return ("%s must be int64 or int32, or float64 / float32 holding integral values (%s)"
+          % (what, detail))
 
-
-def describe(embeddings, get_handle: typing.Callable[[], "_lib.Handle"],
-             strided: bool = False) -> Source:
-  """`embeddings` -> Source.  TypeError / ValueError for what cannot be taken, before any
-  device call (`get_handle` is only called for an object that says it lives on a GPU: its
-  device must be the handle's, and the handle's stream goes to `__dlpack__`).  `strided`: a
-  NumPy view keeps its strides (the affinity entry points take them); otherwise it is made
-  contiguous on the host, as the embeddings paths expect."""
-  if isinstance(embeddings, np.ndarray):
-    return _from_numpy(embeddings, strided)
-  if not (hasattr(embeddings, "__dlpack__") and hasattr(embeddings, "__dlpack_device__")):
-    raise TypeError("embeddings must be a numpy array")
-  device_type, device_id = embeddings.__dlpack_device__()
-  device_type = int(device_type)
-  if device_type in HOST_DEVICE_TYPES:
-    return _from_capsule(embeddings.__dlpack__(), _lib.SC_MEM_HOST)
-  if device_type not in DEVICE_DEVICE_TYPES:
-    raise TypeError("embeddings live on DLPack device type %d: host memory and ROCm device "
-                    "memory are supported" % device_type)
-  handle = get_handle()
-  if int(device_id) != handle.device:
-    raise ValueError("embeddings are on device %d, the clusterer runs on device %d"
-                     % (int(device_id), handle.device))
-  # the producer makes the library's stream wait for whatever still writes the tensor
-  return _from_capsule(embeddings.__dlpack__(stream=handle.stream()), _lib.SC_MEM_DEVICE)
-
-
-# ---- results where the caller wants them -------------------------------------------------------
 
 def is_described(obj) -> bool:
   """Not an ndarray, but something that can say where it is: it is read through DLPack."""
   return (not isinstance(obj, np.ndarray) and hasattr(obj, "__dlpack__") and
           hasattr(obj, "__dlpack_device__"))
-
-
-def describe_input(obj, get_handle: typing.Callable[[], "_lib.Handle"]) -> Source:
-  """`describe(..., strided=True)` for the building blocks: whatever is neither an ndarray nor a
-  DLPack object (a list, say) becomes an ndarray first, as `np.ascontiguousarray` made it one."""
-  if not isinstance(obj, np.ndarray) and not is_described(obj):
-    obj = np.asarray(obj)
-  return describe(obj, get_handle, strided=True)
 
 
 def view_is_injective(shape: typing.Sequence[int], strides: typing.Sequence[int]) -> bool:
@@ -250,6 +175,188 @@ def view_is_injective(shape: typing.Sequence[int], strides: typing.Sequence[int]
   return len(dims) == 1 or dims[1][0] >= dims[0][0] * dims[0][1]
 
 
+# ---- one description path ------------------------------------------------------------------
+
+def _promote_embeddings(a: np.ndarray, dtype, what: str):
+  """ints, bools, longdouble, other byte orders: promoted to float64 on the host."""
+  if dtype is None:
+    return np.ascontiguousarray(a, dtype=np.float64), _lib.SC_DTYPE_F64
+  return a, dtype
+
+
+class _Role(typing.NamedTuple):
+  """What one kind of argument asks of the object that is passed for it (`_describe`)."""
+  what: str
+  ndim: int
+  numpy_dtypes: dict
+  dlpack_dtypes: dict
+  dtype_error: typing.Callable[[str, str], str]  # (what, detail) -> the TypeError text
+  # ndarray only: (array, dtype or None, what) -> (array to describe, dtype); None: TypeError
+  host_values: typing.Optional[typing.Callable] = None
+  shape: typing.Optional[typing.Tuple[int, ...]] = None  # the shape it must have (None: any)
+  shape_error: str = "%s must have shape %s, not %s"
+  entries: bool = False     # a vector of n entries: the length is checked before the dtype
+  writeable: bool = False   # an output: writeable memory, no two indices at one address
+  alias_error: str = "%s maps two indices to one address (strides %s of shape %s)"
+  strided: bool = True      # a NumPy view keeps its strides ...
+  copies: bool = False      # ... and one that cannot is made contiguous on the host (no error)
+  stride_error: str = "%s: strides must be multiples of the item size"
+  not_array: str = "%s must be a numpy array or an object with __dlpack__"
+  foreign_device: str = ("%s lives on DLPack device type %d: host memory and ROCm device memory "
+                         "are supported")
+  other_device: str = "%s is on device %d, the library runs on device %d"
+  export_error: typing.Optional[str] = None  # a producer's BufferError as ValueError (None: as is)
+
+
+_EMBEDDINGS = _Role(
+    "embeddings", 2, _NUMPY_DTYPES, _DLPACK_DTYPES, dtype_message, _promote_embeddings,
+    copies=True, not_array="%s must be a numpy array",
+    foreign_device="%s live on DLPack device type %d: host memory and ROCm device memory are "
+                   "supported",
+    other_device="%s are on device %d, the clusterer runs on device %d")
+_OUT = _Role("out", 2, _NUMPY_DTYPES, _DLPACK_DTYPES, dtype_message, writeable=True,
+             export_error="%s cannot be exported as writeable memory: %s")
+_LABELS = _Role("labels", 1, _LABEL_NUMPY_DTYPES, _LABEL_DLPACK_INPUTS, label_input_dtype_message,
+                shape_error="%s must hold %s entries, not %s", entries=True,
+                stride_error="%s: the stride must be a multiple of the item size",
+                export_error="%s cannot be exported: %s")
+_LABELS_OUT = _Role("out", 1, _LABEL_NUMPY_DTYPES, _LABEL_DLPACK_DTYPES, label_dtype_message,
+                    writeable=True, alias_error="%s maps two indices to one address (stride 0)",
+                    stride_error=_LABELS.stride_error, export_error=_LABELS.export_error)
+
+
+def _alias_message(role: _Role, strides, shape) -> str:
+  text = role.alias_error
+  return text % ((role.what, tuple(strides), shape) if text.count("%s") == 3 else role.what)
+
+
+def _shape_message(role: _Role, got) -> str:
+  want = role.shape
+  if role.entries:
+    want, got = want[0], got[0]
+  return role.shape_error % (role.what, want, got)
+
+
+def _from_numpy(a: np.ndarray, role: _Role) -> Source:
+  what, given = role.what, a
+  if role.writeable and not a.flags.writeable:
+    raise ValueError("%s is not writeable" % what)
+  if role.host_values is not None and a.ndim != role.ndim:
+    raise ValueError("%s must be %d-dimensional" % (what, role.ndim))
+  if role.entries and a.shape != role.shape:
+    raise ValueError(_shape_message(role, a.shape))
+  dtype = role.numpy_dtypes.get(a.dtype)
+  if role.host_values is not None:
+    a, dtype = role.host_values(a, dtype, what)
+  elif dtype is None:
+    raise TypeError(role.dtype_error(what, "numpy %s" % a.dtype))
+  if role.shape is not None and a.shape != role.shape:
+    raise ValueError(_shape_message(role, a.shape))
+  lies = role.strided and all(s >= 0 and s % a.itemsize == 0 for s in a.strides)
+  if not lies and not role.copies:
+    if any(s < 0 for s in a.strides):
+      raise ValueError(negative_strides_message(what))
+    raise ValueError(role.stride_error % what)
+  shape, strides = a.shape, [s // a.itemsize for s in a.strides]
+  if not lies:
+    a = np.ascontiguousarray(a)
+    strides = [shape[1], 1]
+  if role.writeable and not view_is_injective(shape, strides):
+    raise ValueError(_alias_message(role, strides, shape))
+  if role.ndim == 1:  # a vector is described as one row
+    shape, strides = (1,) + shape, [0] + strides
+  arr = _lib.ScArray(a.ctypes.data, dtype, _lib.SC_MEM_HOST, shape[0], shape[1], strides[0],
+                     strides[1])
+  # (host branches compute on the caller's own embeddings, and on the labels as they were read)
+  return Source(arr, a, numpy=given if role.copies else a)
+
+
+def _from_capsule(capsule, location: int, role: _Role) -> Source:
+  """The legacy "dltensor" capsule of a DLPack object -> Source (a vector as one row)."""
+  what, ndim = role.what, role.ndim
+  address = _get_pointer(capsule, _NAME)  # raises ValueError for a capsule of another name
+  managed = ctypes.cast(address, ctypes.POINTER(DLManagedTensor))
+  _set_name(capsule, _USED_NAME)  # consumed: the deleter is ours to call now
+  src = Source(_lib.ScArray(), None, capsule=capsule, managed=managed)
+  try:
+    t = managed.contents.dl_tensor
+    if t.ndim != ndim:
+      raise ValueError("%s must be %d-dimensional" % (what, ndim))
+    dtype = role.dlpack_dtypes.get((t.dtype.code, t.dtype.bits)) if t.dtype.lanes == 1 else None
+    if dtype is None:
+      raise TypeError(role.dtype_error(what, "DLPack type code %d, %d bits, %d lanes"
+                                       % (t.dtype.code, t.dtype.bits, t.dtype.lanes)))
+    if ndim == 1:
+      rows, cols = 1, int(t.shape[0])
+      row_stride, col_stride = 0, (int(t.strides[0]) if t.strides else 1)
+    else:
+      rows, cols = int(t.shape[0]), int(t.shape[1])
+      row_stride, col_stride = (int(t.strides[0]), int(t.strides[1])) if t.strides else (cols, 1)
+    if row_stride < 0 or col_stride < 0:
+      raise ValueError(negative_strides_message(what))
+    itemsize = t.dtype.bits // 8
+    assert int(t.byte_offset) % itemsize == 0
+    src.array = _lib.ScArray((t.data or 0) + int(t.byte_offset), dtype, location, rows, cols,
+                             row_stride, col_stride)
+    got = (cols,) if ndim == 1 else (rows, cols)
+    if role.shape is not None and got != role.shape:
+      raise ValueError(_shape_message(role, got))
+    if role.writeable and not view_is_injective((rows, cols), (row_stride, col_stride)):
+      raise ValueError(_alias_message(role, (row_stride, col_stride), got))
+  except Exception:
+    src.release()
+    raise
+  return src
+
+
+def _describe(obj, get_handle: typing.Callable[[], "_lib.Handle"], role: _Role) -> Source:
+  """`obj` in `role` -> Source.  TypeError / ValueError naming `role.what` for what cannot be
+  taken, before any device call.  An ndarray is checked and described here; anything else has
+  to say where it lives (`__dlpack_device__`): host memory is read through its capsule as it is;
+  for the handle's device (`get_handle` is called for such an object only) the producer is handed
+  the library's stream, which it makes wait for whatever still uses the tensor."""
+  what = role.what
+  if isinstance(obj, np.ndarray):
+    return _from_numpy(obj, role)
+  if not (hasattr(obj, "__dlpack__") and hasattr(obj, "__dlpack_device__")):
+    raise TypeError(role.not_array % what)
+  device_type, device_id = obj.__dlpack_device__()
+  device_type = int(device_type)
+  try:
+    if device_type in HOST_DEVICE_TYPES:
+      return _from_capsule(obj.__dlpack__(), _lib.SC_MEM_HOST, role)
+    if device_type not in DEVICE_DEVICE_TYPES:
+      raise TypeError(role.foreign_device % (what, device_type))
+    handle = get_handle()
+    if int(device_id) != handle.device:
+      raise ValueError(role.other_device % (what, int(device_id), handle.device))
+    return _from_capsule(obj.__dlpack__(stream=handle.stream()), _lib.SC_MEM_DEVICE, role)
+  except BufferError as e:  # what a producer answers for memory it will not hand out
+    if role.export_error is None:
+      raise
+    raise ValueError(role.export_error % (what, e)) from e
+
+
+# ---- the roles' public names -----------------------------------------------------------------
+
+def describe(embeddings, get_handle: typing.Callable[[], "_lib.Handle"],
+             strided: bool = False) -> Source:
+  """`embeddings` -> Source.  TypeError / ValueError for what cannot be taken, before any
+  device call (`get_handle` is only called for an object that says it lives on a GPU: its
+  device must be the handle's, and the handle's stream goes to `__dlpack__`).  `strided`: a
+  NumPy view keeps its strides (the affinity entry points take them); otherwise it is made
+  contiguous on the host, as the embeddings paths expect."""
+  return _describe(embeddings, get_handle, _EMBEDDINGS._replace(strided=strided))
+
+
+def describe_input(obj, get_handle: typing.Callable[[], "_lib.Handle"]) -> Source:
+  """`describe(..., strided=True)` for the building blocks: whatever is neither an ndarray nor a
+  DLPack object (a list, say) becomes an ndarray first, as `np.ascontiguousarray` made it one."""
+  if not isinstance(obj, np.ndarray) and not is_described(obj):
+    obj = np.asarray(obj)
+  return describe(obj, get_handle, strided=True)
+
+
 def describe_out(out, get_handle: typing.Callable[[], "_lib.Handle"],
                  shape: typing.Tuple[int, ...], what: str = "out") -> Source:
   """`out` -> the Source the library writes into.  A writeable ndarray (float64 / float32 /
@@ -257,125 +364,12 @@ def describe_out(out, get_handle: typing.Callable[[], "_lib.Handle"],
   exactly `shape` (1-D or 2-D), with non-negative strides under which no two indices share an
   address.  TypeError / ValueError naming `what` for anything else, before any launch."""
   shape = tuple(int(e) for e in shape)
-  if isinstance(out, np.ndarray):
-    if not out.flags.writeable:
-      raise ValueError("%s is not writeable" % what)
-    dtype = _NUMPY_DTYPES.get(out.dtype)
-    if dtype is None:
-      raise TypeError(dtype_message(what, "numpy %s" % out.dtype))
-    if out.shape != shape:
-      raise ValueError("%s must have shape %s, not %s" % (what, shape, out.shape))
-    if any(s < 0 for s in out.strides):
-      raise ValueError(negative_strides_message(what))
-    if any(s % out.itemsize for s in out.strides):
-      raise ValueError("%s: strides must be multiples of the item size" % what)
-    strides = [s // out.itemsize for s in out.strides]
-    if not view_is_injective(shape, strides):
-      raise ValueError("%s maps two indices to one address (strides %s of shape %s)"
-                       % (what, tuple(strides), shape))
-    if len(shape) == 1:
-      shape, strides = (1,) + shape, [0] + strides
-    arr = _lib.ScArray(out.ctypes.data, dtype, _lib.SC_MEM_HOST, shape[0], shape[1],
-                       strides[0], strides[1])
-    return Source(arr, out, numpy=out)
-  if not (hasattr(out, "__dlpack__") and hasattr(out, "__dlpack_device__")):
-    raise TypeError("%s must be a numpy array or an object with __dlpack__" % what)
-  device_type, device_id = out.__dlpack_device__()
-  device_type = int(device_type)
-  try:
-    if device_type in HOST_DEVICE_TYPES:
-      src = _from_capsule(out.__dlpack__(), _lib.SC_MEM_HOST, what, len(shape))
-    elif device_type in DEVICE_DEVICE_TYPES:
-      handle = get_handle()
-      if int(device_id) != handle.device:
-        raise ValueError("%s is on device %d, the library runs on device %d"
-                         % (what, int(device_id), handle.device))
-      # the producer makes the library's stream wait for whatever still uses the tensor
-      src = _from_capsule(out.__dlpack__(stream=handle.stream()), _lib.SC_MEM_DEVICE, what,
-                          len(shape))
-    else:
-      raise TypeError("%s lives on DLPack device type %d: host memory and ROCm device memory "
-                      "are supported" % (what, device_type))
-  except BufferError as e:  # what a producer answers for memory it will not hand out writeable
-    raise ValueError("%s cannot be exported as writeable memory: %s" % (what, e)) from e
-  a = src.array
-  got = (int(a.cols),) if len(shape) == 1 else (int(a.rows), int(a.cols))
-  try:
-    if got != shape:
-      raise ValueError("%s must have shape %s, not %s" % (what, shape, got))
-    if not view_is_injective((a.rows, a.cols), (a.row_stride, a.col_stride)):
-      raise ValueError("%s maps two indices to one address (strides %s of shape %s)"
-                       % (what, (int(a.row_stride), int(a.col_stride)), got))
-  except Exception:
-    src.release()
-    raise
-  return src
+  return _describe(out, get_handle, _OUT._replace(what=what, ndim=len(shape), shape=shape))
 
 
-# ---- label arrays --------------------------------------------------------------------------
-
-def label_dtype_message(what: str, detail: str) -> str:
-  """The TypeError text for a label array of a dtype that is not taken."""
-  return "%s must be int64 or int32 (%s)" % (what, detail)
-
-
-def label_input_dtype_message(what: str, detail: str) -> str:
-  return ("%s must be int64 or int32, or float64 / float32 holding integral values (%s)"
-          % (what, detail))
-
-
-def _label_capsule(obj, get_handle, what: str, dtypes, dtype_error) -> Source:
-  """A 1-D DLPack object in host memory or on the handle's device -> Source."""
-  device_type, device_id = obj.__dlpack_device__()
-  device_type = int(device_type)
-  try:
-    if device_type in HOST_DEVICE_TYPES:
-      return _from_capsule(obj.__dlpack__(), _lib.SC_MEM_HOST, what, 1, dtypes, dtype_error)
-    if device_type not in DEVICE_DEVICE_TYPES:
-      raise TypeError("%s lives on DLPack device type %d: host memory and ROCm device memory "
-                      "are supported" % (what, device_type))
-    handle = get_handle()
-    if int(device_id) != handle.device:
-      raise ValueError("%s is on device %d, the library runs on device %d"
-                       % (what, int(device_id), handle.device))
-    return _from_capsule(obj.__dlpack__(stream=handle.stream()), _lib.SC_MEM_DEVICE, what, 1,
-                         dtypes, dtype_error)
-  except BufferError as e:  # what a producer answers for memory it will not hand out
-    raise ValueError("%s cannot be exported: %s" % (what, e)) from e
-
-
-def _label_vector(a: np.ndarray, dtype: int, what: str) -> _lib.ScArray:
-  if a.strides[0] < 0:
-    raise ValueError(negative_strides_message(what))
-  if a.strides[0] % a.itemsize:
-    raise ValueError("%s: the stride must be a multiple of the item size" % what)
-  return _lib.ScArray(a.ctypes.data, dtype, _lib.SC_MEM_HOST, 1, a.shape[0], 0,
-                      a.strides[0] // a.itemsize)
-
-
-def describe_labels(labels, get_handle: typing.Callable[[], "_lib.Handle"], n: int,
-                    what: str = "labels") -> Source:
-  """A label array as an input -> Source: 1-D, `n` entries, a NumPy array (anything else that is
-  no DLPack object becomes one first) or a DLPack object, in host memory or on the handle's
-  device, any non-negative stride.  int64 / int32 are read as they are, and so are float64 /
-  float32 holding integral values; host arrays of other integer types are converted on the host.
-  The values of a host NumPy array are checked here (finite, integral, at most `MAX_LABEL`); those
-  of a DLPack object by the library.  TypeError / ValueError naming `what`, before any launch."""
-  if not isinstance(labels, np.ndarray) and not is_described(labels):
-    labels = np.asarray(labels)
-  if not isinstance(labels, np.ndarray):
-    src = _label_capsule(labels, get_handle, what, _LABEL_DLPACK_INPUTS, label_input_dtype_message)
-    if int(src.array.cols) != n:
-      got = int(src.array.cols)
-      src.release()
-      raise ValueError("%s must hold %d entries, not %d" % (what, n, got))
-    return src
-  if labels.ndim != 1:
-    raise ValueError("%s must be 1-dimensional" % what)
-  if labels.shape[0] != n:
-    raise ValueError("%s must hold %d entries, not %d" % (what, n, labels.shape[0]))
-  a = labels
-  dtype = _LABEL_NUMPY_DTYPES.get(a.dtype)
+def _label_values(a: np.ndarray, dtype, what: str):
+  """The values of a host label array: finite, integral, at most `MAX_LABEL`; integer types the
+  library does not read are converted here."""
   if dtype is None:
     dtype = _LABEL_NUMPY_FLOATS.get(a.dtype)
     if dtype is not None:
@@ -389,7 +383,21 @@ def describe_labels(labels, get_handle: typing.Callable[[], "_lib.Handle"], n: i
       raise TypeError(label_input_dtype_message(what, "numpy %s" % a.dtype))
   if a.size and a.max() > MAX_LABEL:
     raise ValueError("%s: a label is above %d" % (what, MAX_LABEL))
-  return Source(_label_vector(a, dtype, what), a, numpy=a)
+  return a, dtype
+
+
+def describe_labels(labels, get_handle: typing.Callable[[], "_lib.Handle"], n: int,
+                    what: str = "labels") -> Source:
+  """A label array as an input -> Source: 1-D, `n` entries, a NumPy array (anything else that is
+  no DLPack object becomes one first) or a DLPack object, in host memory or on the handle's
+  device, any non-negative stride.  int64 / int32 are read as they are, and so are float64 /
+  float32 holding integral values; host arrays of other integer types are converted on the host.
+  The values of a host NumPy array are checked here (finite, integral, at most `MAX_LABEL`); those
+  of a DLPack object by the library.  TypeError / ValueError naming `what`, before any launch."""
+  if not isinstance(labels, np.ndarray) and not is_described(labels):
+    labels = np.asarray(labels)
+  return _describe(labels, get_handle,
+                   _LABELS._replace(what=what, shape=(n,), host_values=_label_values))
 
 
 def describe_labels_out(out, get_handle: typing.Callable[[], "_lib.Handle"], n: int,
@@ -398,27 +406,7 @@ def describe_labels_out(out, get_handle: typing.Callable[[], "_lib.Handle"], n: 
   object of int64 or int32 with exactly `n` entries, in host memory or on the handle's device,
   with a non-negative stride that gives every entry its own address.  TypeError / ValueError
   naming `what` for anything else, before any launch."""
-  if isinstance(out, np.ndarray):
-    if not out.flags.writeable:
-      raise ValueError("%s is not writeable" % what)
-    dtype = _LABEL_NUMPY_DTYPES.get(out.dtype)
-    if dtype is None:
-      raise TypeError(label_dtype_message(what, "numpy %s" % out.dtype))
-    if out.shape != (n,):
-      raise ValueError("%s must have shape %s, not %s" % (what, (n,), out.shape))
-    src = Source(_label_vector(out, dtype, what), out, numpy=out)
-  elif hasattr(out, "__dlpack__") and hasattr(out, "__dlpack_device__"):
-    src = _label_capsule(out, get_handle, what, _LABEL_DLPACK_DTYPES, label_dtype_message)
-    if int(src.array.cols) != n:
-      got = int(src.array.cols)
-      src.release()
-      raise ValueError("%s must have shape %s, not %s" % (what, (n,), (got,)))
-  else:
-    raise TypeError("%s must be a numpy array or an object with __dlpack__" % what)
-  if n > 1 and int(src.array.col_stride) < 1:
-    src.release()
-    raise ValueError("%s maps two indices to one address (stride 0)" % what)
-  return src
+  return _describe(out, get_handle, _LABELS_OUT._replace(what=what, shape=(n,)))
 
 
 def device_overlap(outs: typing.Sequence[Source], sources: typing.Sequence[Source]

@@ -67,13 +67,10 @@ def _device_adjust(affinity: np.ndarray, constraint_matrix, name: ConstraintName
   handle = _lib.default_handle()
   if dense:
     with _lib.use_device(handle.device):
-      source = constraint_matrix.describe(lambda: handle)
-      try:
+      with constraint_matrix.describe(lambda: handle) as source:
         handle.check(handle.lib.sc_stage_constraint_array(
             handle.raw, cfg, _lib.as_double_p(src), ctypes.byref(source.array), src.shape[0],
             _lib.as_double_p(out)), TypeError)
-      finally:
-        source.release()
     return out
   if paired:
     rows, cols, vals = constraint_matrix.entries()

@@ -1,13 +1,17 @@
-// What the ingest (ingest.hip: caller memory -> the handle's fp64 buffers) and the egress
-// (egress.hip: the way back) share: the 2-byte element types as bits, the 16-byte item, the
-// 64 x 64 LDS tile with its swizzle, the exact widening and the narrowing by bits (centroids.hip
-// reads and writes caller memory with them as well), and the rule that says which way a view's
-// memory runs.
+// The rules every reader and writer of caller memory shares (ingest.hip: caller memory -> the
+// handle's fp64 buffers; egress.hip: the way back; centroids.hip: both), each written once:
+//   dispatch_dtype      an sc_array dtype -> its element type (the 2-byte types are bits),
+//   Chunk / aligned16   the 16-byte item and the rule that says when an access may be one,
+//   align16             sizes and pitches of staging memory,
+//   aff_at              the 64 x 64 LDS tile with its swizzle,
+//   widen / narrow      the exact widening and the narrowing by bits,
+//   runs_along_columns  which way a view's memory runs.
 #ifndef SC_ARRAY_LAYOUT_H_
 #define SC_ARRAY_LAYOUT_H_
 
 #include <climits>
 #include <cstddef>
+#include <cstdint>
 
 #include <hip/hip_runtime.h>
 
@@ -27,6 +31,29 @@ struct alignas(16) Chunk {
 inline size_t dtype_bytes(int dtype) {
   return dtype == SC_DTYPE_F64 ? 8 : dtype == SC_DTYPE_F32 ? 4 : 2;
 }
+
+// f(T{}) for the element type T of one of the four float dtypes (a validated descriptor has no
+// other): `[&](auto t) { using T = decltype(t); ... }`
+template <typename F>
+__host__ __device__ __forceinline__ void dispatch_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case SC_DTYPE_F64: f(double{}); break;
+    case SC_DTYPE_F32: f(float{}); break;
+    case SC_DTYPE_F16: f(F16Bits{}); break;
+    default: f(BF16Bits{}); break;
+  }
+}
+
+// May the lines of a view (unit stride along a line, `pitch_elems` from one line to the next) be
+// read or written 16 bytes at a time?  The base address is a multiple of 16 and so is the pitch in
+// bytes -- or there is one line only, whose pitch addresses nothing.
+inline bool aligned16(const void* p, long long pitch_elems, size_t elem_bytes, long long lines) {
+  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 &&
+         (lines == 1 || (pitch_elems * (long long)elem_bytes) % 16 == 0);
+}
+
+// sizes and pitches of staging memory: the next multiple of 16 bytes
+inline size_t align16(size_t bytes) { return (bytes + 15) / 16 * 16; }
 
 // LDS rows of a tile are not padded (two fp64 tiles are the whole 64 KB): the pair index of a row
 // is XOR-ed with the row number instead, which keeps 16-byte pairs together and spreads a column

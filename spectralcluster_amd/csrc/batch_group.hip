@@ -1760,7 +1760,7 @@ extern "C" int sc_predict_batch_constraint_arrays(sc_handle h, const sc_array* x
     if (!dense[i].data) continue;
     if (cons && cons[i].kind != 0)
       return fail(h, SC_ERR_INVALID, "an utterance with a dense constraint has constraint kind 0");
-    SC_TRY(validate_constraint_array(h, dense + i));
+    SC_TRY(validate_affinity_array(h, dense + i, "constraint matrix"));
     if (dense[i].rows != ns[i])
       return fail(h, SC_ERR_INVALID, "affinity and constraint matrix must have the same shape");
     any_dense = true;

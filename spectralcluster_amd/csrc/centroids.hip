@@ -250,45 +250,6 @@ Range range_of(const sc_array& a, size_t eb, int index) {
   return Range{lo, lo + (uintptr_t)((last + 1) * eb), index};
 }
 
-void scatter_host(const unsigned char* packed, const sc_array& a, int rows) {
-  const size_t eb = dtype_bytes(a.dtype);
-  unsigned char* base = static_cast<unsigned char*>(const_cast<void*>(a.data));
-  for (int64_t r = 0; r < rows; ++r)
-    for (int64_t c = 0; c < a.cols; ++c, packed += eb)
-      memcpy(base + (size_t)(r * a.row_stride + c * a.col_stride) * eb, packed, eb);
-}
-
-size_t align16(size_t v) { return (v + 15) / 16 * 16; }
-
-}  // namespace
-
-// A label array `what` of member i: one row of `n` entries (rows 1, cols n; the row stride
-// addresses nothing).  `output`: int64 / int32 only, and entries that do not share an address.
-int validate_label_array(sc_handle h, const sc_array* a, const char* what, int i, int64_t n,
-                         bool output) {
-  const std::string w = member(what, i);
-  if (!a->data) return fail(h, SC_ERR_INVALID, w + ": data is NULL");
-  if (a->rows != 1 || a->cols != n)
-    return fail(h, SC_ERR_INVALID, w + " must hold " + std::to_string(n) + " entries, not " +
-                                       std::to_string(a->rows == 1 ? a->cols : a->rows * a->cols));
-  const bool ints = a->dtype == SC_DTYPE_I64 || a->dtype == SC_DTYPE_I32;
-  if (!ints && (output || (a->dtype != SC_DTYPE_F64 && a->dtype != SC_DTYPE_F32)))
-    return fail(h, SC_ERR_INVALID,
-                w + (output ? ": dtype must be SC_DTYPE_I64 or SC_DTYPE_I32"
-                            : ": dtype must be SC_DTYPE_I64, I32, F64 or F32"));
-  if (a->location != SC_MEM_HOST && a->location != SC_MEM_DEVICE)
-    return fail(h, SC_ERR_INVALID, w + ": unknown location (SC_MEM_HOST / SC_MEM_DEVICE)");
-  if (a->col_stride < 0) return fail(h, SC_ERR_INVALID, w + ": the stride must not be negative");
-  if (output && n > 1 && a->col_stride < 1)
-    return fail(h, SC_ERR_INVALID, w + ": the view maps two indices to one address");
-  if (a->location == SC_MEM_DEVICE && !is_device_memory_of(h, a->data))
-    return fail(h, SC_ERR_INVALID, w + ": location is SC_MEM_DEVICE but the pointer is not device "
-                                       "memory of the handle's device");
-  return SC_OK;
-}
-
-namespace {
-
 // the host side of the call's asynchronous copies: owned by the entry, which drains the stream
 // before they go when the run below fails half way
 struct CentroidScratch {
@@ -415,17 +376,7 @@ int centroids_run(sc_handle h, const sc_array* xs, const sc_array* labels, int c
       it.xrs = x.row_stride;
       it.xcs = x.col_stride;
     } else {
-      const unsigned char* base = static_cast<const unsigned char*>(x.data);
-      unsigned char* to = xpack.data() + xat;
-      for (int64_t r = 0; r < x.rows; ++r) {
-        const unsigned char* row = base + (size_t)(r * x.row_stride) * eb;
-        if (x.col_stride == 1) {
-          memcpy(to, row, (size_t)d * eb);
-          to += (size_t)d * eb;
-        } else {
-          for (int64_t c = 0; c < d; ++c, to += eb) memcpy(to, row + (size_t)(c * x.col_stride) * eb, eb);
-        }
-      }
+      pack_host_rows(x, x.rows, xpack.data() + xat);
       it.x = xstage_d + xat;
       it.xrs = d;
       it.xcs = 1;
@@ -469,7 +420,7 @@ int centroids_run(sc_handle h, const sc_array* xs, const sc_array* labels, int c
   oat = 0;
   for (int i = 0; i < count; ++i) {
     if (outs[i].location != SC_MEM_HOST || table[i].k == 0) continue;
-    scatter_host(opack.data() + oat, outs[i], table[i].k);
+    scatter_host_rows(opack.data() + oat, outs[i], table[i].k);
     oat += align16((size_t)table[i].k * d * dtype_bytes(outs[i].dtype));
   }
   return SC_OK;

@@ -399,20 +399,13 @@ extern "C" int sc_set_constraint(sc_handle h, const double* q, int n) {
   return SC_OK;
 }
 
-// validate_affinity_array's rules for a dense constraint source
-int validate_constraint_array(sc_handle h, const sc_array* q) {
-  SC_TRY(validate_array(h, q));
-  if (q->rows != q->cols) return fail(h, SC_ERR_INVALID, "constraint matrix must be (n, n)");
-  return SC_OK;
-}
-
 // sc_set_constraint for a described source: read where it is (a device source in place, a narrow
 // host source crossing the link at its own width), widened exactly into Cq by the ingest kernel,
 // whose own flag is the symmetry -- one pass.  (Host fp64 keeps sc_set_constraint's copy and the
 // separate pass: ingest_affinity_into.)
 extern "C" int sc_set_constraint_array(sc_handle h, const sc_array* q) {
   if (!h) return SC_ERR_INVALID;
-  SC_TRY(validate_constraint_array(h, q));
+  SC_TRY(validate_affinity_array(h, q, "constraint matrix"));
   SC_HIP(h, hipSetDevice(h->device));
   const int n = (int)q->rows, ld = matrix_ld(n);
   SC_TRY(grow(h, h->Cq, (size_t)n * ld * sizeof(double)));
@@ -555,7 +548,7 @@ extern "C" int sc_stage_constraint_array(sc_handle h, const sc_config* cfg, cons
   SC_TRY(validate_config(h, cfg));
   if (!affinity || !out || n <= 0)
     return fail(h, SC_ERR_INVALID, "affinity and constraint matrix must be (n, n)");
-  SC_TRY(validate_constraint_array(h, q));
+  SC_TRY(validate_affinity_array(h, q, "constraint matrix"));
   if (q->rows != n)
     return fail(h, SC_ERR_INVALID, "affinity and constraint matrix must have the same shape");
   SC_TRY(sc_set_affinity(h, affinity, n));

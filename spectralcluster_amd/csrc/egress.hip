@@ -17,6 +17,9 @@
 // int32 vector, host or device, of any stride >= 1 that each member of a batch names.
 // The stage entries on described arrays (sc_stage_*_array) are at the end: ingest, the launches
 // of the double* entry, egress.
+// What is shared with the way in lives there: the descriptor checks (validate_out_array and
+// view_is_injective), the staging buffer (ensure_stage) and the scatter of host rows are
+// ingest.hip's; dispatch_dtype, aligned16 and align16 are array_layout.h's.
 #include <climits>
 #include <cstring>
 
@@ -112,11 +115,6 @@ __global__ __launch_bounds__(256) void k_egress_tile(const double* __restrict__ 
   }
 }
 
-bool aligned16(const void* p, long long pitch_elems, size_t eb, int lines) {
-  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 &&
-         (lines == 1 || (pitch_elems * (long long)eb) % 16 == 0);
-}
-
 template <typename T>
 void launch_egress_typed(hipStream_t s, const double* src, int ld, int L, int W, void* dst,
                          long long dl, long long da) {
@@ -152,12 +150,9 @@ void launch_egress(hipStream_t s, int dtype, const double* src, int ld, int rows
   if (cols == 1) cs = std::max<long long>(rs, 1) * rows;
   const int L = column_major ? cols : rows, W = column_major ? rows : cols;
   const long long dl = column_major ? cs : rs, da = column_major ? rs : cs;
-  switch (dtype) {
-    case SC_DTYPE_F64: launch_egress_typed<double>(s, src, ld, L, W, dst, dl, da); break;
-    case SC_DTYPE_F32: launch_egress_typed<float>(s, src, ld, L, W, dst, dl, da); break;
-    case SC_DTYPE_F16: launch_egress_typed<F16Bits>(s, src, ld, L, W, dst, dl, da); break;
-    default: launch_egress_typed<BF16Bits>(s, src, ld, L, W, dst, dl, da); break;
-  }
+  dispatch_dtype(dtype, [&](auto t) {
+    launch_egress_typed<decltype(t)>(s, src, ld, L, W, dst, dl, da);
+  });
 }
 
 // ---- labels out ----------------------------------------------------------------------------
@@ -253,29 +248,6 @@ bool symmetric_within_tolerance(const unsigned long long* stats) {
   return dmax <= 1e-12 * std::max(amax, 1e-300);
 }
 
-// no two indices of a (rows, cols) view of element strides (rs, cs) share an address: over the
-// dimensions of more than one element, ordered by stride, small >= 1 and big >= small * extent
-bool view_is_injective(long long rows, long long cols, long long rs, long long cs) {
-  if (rows > 1 && cols > 1) {
-    const bool rows_small = rs < cs;
-    const long long small = rows_small ? rs : cs, big = rows_small ? cs : rs;
-    const long long extent = rows_small ? rows : cols;
-    return small >= 1 && big / extent >= small;  // (no overflow: big >= small * extent)
-  }
-  if (rows > 1) return rs >= 1;
-  if (cols > 1) return cs >= 1;
-  return true;
-}
-
-void scatter_host_rows(const std::vector<unsigned char>& packed, const sc_array& a) {
-  const size_t eb = dtype_bytes(a.dtype);
-  unsigned char* base = static_cast<unsigned char*>(const_cast<void*>(a.data));
-  const unsigned char* in = packed.data();
-  for (int64_t r = 0; r < a.rows; ++r)
-    for (int64_t c = 0; c < a.cols; ++c, in += eb)
-      memcpy(base + (size_t)(r * a.row_stride + c * a.col_stride) * eb, in, eb);
-}
-
 // Before the upload into B1: the union of what the double* stage entries do there.  All of them
 // drop the resident embeddings / affinity; the eigen entries also set n and ldn (the solvers read
 // them), the refine and Laplacian entries also clear n_vec.  Doing all of it for every entry is
@@ -301,30 +273,6 @@ int ingest_into_b1(sc_handle h, const sc_array& in, int n) {
 }  // namespace
 
 // ------------------------------------------------------------------------------
-// validation (no launch, no copy)
-// ------------------------------------------------------------------------------
-int validate_out_array(sc_handle h, const sc_array* a, const char* what, int rows, int cols) {
-  const std::string w(what);
-  if (!a) return fail(h, SC_ERR_INVALID, w + " descriptor is NULL");
-  if (!a->data || a->rows != rows || a->cols != cols)
-    return fail(h, SC_ERR_INVALID,
-                w + " must be (" + std::to_string(rows) + ", " + std::to_string(cols) + ")");
-  if (a->dtype < SC_DTYPE_F64 || a->dtype > SC_DTYPE_BF16)
-    return fail(h, SC_ERR_INVALID, w + ": unknown dtype (SC_DTYPE_F64 / F32 / F16 / BF16)");
-  if (a->location != SC_MEM_HOST && a->location != SC_MEM_DEVICE)
-    return fail(h, SC_ERR_INVALID, w + ": unknown location (SC_MEM_HOST / SC_MEM_DEVICE)");
-  if (a->row_stride < 0 || a->col_stride < 0)
-    return fail(h, SC_ERR_INVALID, w + ": strides must not be negative");
-  if (!view_is_injective(a->rows, a->cols, a->row_stride, a->col_stride))
-    return fail(h, SC_ERR_INVALID, w + ": the view maps two indices to one address");
-  if (a->location == SC_MEM_DEVICE && !is_device_memory_of(h, a->data))
-    return fail(h, SC_ERR_INVALID,
-                w + ": location is SC_MEM_DEVICE but the pointer is not device memory of the "
-                    "handle's device");
-  return SC_OK;
-}
-
-// ------------------------------------------------------------------------------
 // the one place results leave
 // ------------------------------------------------------------------------------
 int egress_matrix(sc_handle h, const double* src, int ld, int rows, int cols, bool column_major,
@@ -346,8 +294,8 @@ int egress_matrix(sc_handle h, const double* src, int ld, int rows, int cols, bo
   // width on a 16-byte pitch; hipMemcpy2D moves them when it can describe the view, otherwise they
   // are scattered from a packed temporary on the host (the reverse of the ingest's gather)
   const size_t eb = dtype_bytes(out.dtype), width = (size_t)cols * eb;
-  const size_t pitch = (width + 15) / 16 * 16;
-  SC_TRY(grow(h, h->Xstage, (size_t)rows * pitch));
+  const size_t pitch = align16(width);
+  SC_TRY(ensure_stage(h, (size_t)rows * pitch, s));
   launch_egress(s, out.dtype, src, ld, rows, cols, column_major, h->Xstage.p,
                 (long long)(pitch / eb), 1);
   SC_TRY(check_last(h, "egress launch"));
@@ -361,7 +309,7 @@ int egress_matrix(sc_handle h, const double* src, int ld, int rows, int cols, bo
   SC_HIP(h, hipMemcpy2DAsync(packed.data(), width, h->Xstage.p, pitch, width, rows,
                              hipMemcpyDeviceToHost, s));
   SC_HIP(h, hipStreamSynchronize(s));
-  scatter_host_rows(packed, out);
+  scatter_host_rows(packed.data(), out, rows);
   return SC_OK;
 }
 
@@ -428,7 +376,7 @@ extern "C" int sc_labels_egress(sc_handle h, const int64_t* const* labels, int c
   }
   if (!device_members) return SC_OK;
   SC_HIP(h, hipSetDevice(h->device));
-  const size_t tab_bytes = ((size_t)device_members * sizeof(LabelEgressItem) + 15) / 16 * 16;
+  const size_t tab_bytes = align16((size_t)device_members * sizeof(LabelEgressItem));
   SC_TRY(grow(h, h->cen_in, tab_bytes + (size_t)to_device * sizeof(int64_t)));
   LabelEgressItem* table_d = ptr<LabelEgressItem>(h->cen_in);
   long long* packed_d = reinterpret_cast<long long*>(ptr<char>(h->cen_in) + tab_bytes);

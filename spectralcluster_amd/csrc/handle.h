@@ -285,14 +285,30 @@ int ensure_tilemap(sc_handle h, int n);
 int predict_sequence(sc_handle h, const int* idx, int count, const sc_array* xs,
                      const int* ns, int d, const sc_config* cfg, int64_t* const* labels,
                      sc_diag* diags);
-// ---- described sources (ingest.hip) ---------------------------------------------------
-// every check of a descriptor, before any launch or copy (SC_ERR_INVALID + message)
+// ---- caller memory as described arrays (ingest.hip; the shared rules: array_layout.h) -------
+// One descriptor check (ingest.hip's validate_view), one role each; every check comes before any
+// launch or copy and answers SC_ERR_INVALID + message:
+//   validate_array           embeddings: (n, d) of any positive extents, the four float dtypes
+//   validate_kmeans_array    ... and rows * cols <= 2^31 - 1
+//   validate_affinity_array  ... and rows == cols (`what` names the matrix in that message)
+//   validate_out_array       an output `what` of exactly (rows, cols) whose view is injective
+//   validate_label_array     the label array `what` of member i: one row of n entries (rows 1,
+//                            cols n, column stride >= 0) of SC_DTYPE_I64 / I32, as an input also
+//                            F64 / F32; an `output` has entries that share no address
+int validate_array(sc_handle h, const sc_array* a);
+int validate_kmeans_array(sc_handle h, const sc_array* a);
+int validate_affinity_array(sc_handle h, const sc_array* a, const char* what = "affinity");
+int validate_out_array(sc_handle h, const sc_array* a, const char* what, int rows, int cols);
+int validate_label_array(sc_handle h, const sc_array* a, const char* what, int i, int64_t n,
+                         bool output);
 // is p memory of the handle's device?  (the one pointer query of every descriptor check)
 bool is_device_memory_of(sc_handle h, const void* p);
-int validate_array(sc_handle h, const sc_array* a);
-// ... of every utterance of a batch, and that they share one d: fills ns[i] = rows of xs[i], *d
-// (0 for an empty batch) and whether any source lies on the device (the caller then waits for its
-// stream before other streams read one).  `labels` (may be null): labels[i] is checked too.
+// no two indices of a (rows, cols) view of element strides (rs, cs) share an address
+bool view_is_injective(long long rows, long long cols, long long rs, long long cs);
+// validate_array for every utterance of a batch, and that they share one d: fills ns[i] = rows of
+// xs[i], *d (0 for an empty batch) and whether any source lies on the device (the caller then
+// waits for its stream before other streams read one).  `labels` (may be null): labels[i] is
+// checked too.
 int validate_batch_arrays(sc_handle h, const sc_array* xs, int count, std::vector<int>* ns, int* d,
                           bool* device_source, int64_t* const* labels = nullptr);
 // what the double* entry points describe: compact host fp64 rows
@@ -300,6 +316,22 @@ sc_array host_f64_array(const double* x, int n, int d);
 std::vector<sc_array> host_f64_arrays(const double* const* xs, const int* ns, int d, int count);
 // host fp64 rows that one hipMemcpy2DAsync moves (col_stride 1, rows that do not overlap)
 bool array_is_host_f64_rows(const sc_array& a);
+// compact host fp64 rows: what the double* k-means entries take (one copy + k_to_colmajor)
+bool array_is_compact_host_f64(const sc_array& a);
+// ---- one host staging path (ingest.hip) ------------------------------------------------------
+// the first `rows` rows of a host view <-> compact rows of the view's width (what hipMemcpy2D
+// cannot describe is gathered before the upload and scattered after the download)
+void pack_host_rows(const sc_array& a, int64_t rows, unsigned char* out);
+void scatter_host_rows(const unsigned char* in, const sc_array& a, int64_t rows);
+// h->Xstage holds `bytes`; before it is reallocated under a stream s that is not the handle's, s
+// is waited for
+int ensure_stage(sc_handle h, size_t bytes, hipStream_t s);
+// host rows at their own width -> device memory `stage` of row pitch `pitch` bytes on s: the only
+// place that decides between hipMemcpy2DAsync and gather-then-copy (into `packed`; *sync is set
+// then: wait for s while `packed` lives)
+int stage_host_rows(sc_handle h, const sc_array& a, void* stage, size_t pitch, hipStream_t s,
+                    std::vector<unsigned char>* packed, bool* sync);
+// ---- ingest: validated sources -> the handle's fp64 buffers (ingest.hip) ---------------------
 // sc_set_embeddings for a described source, on `stream` (nullptr: the handle's): sizes the
 // arena, sets the problem, widens the rows into h->X; `sync` waits for the stream
 int ingest_embeddings(sc_handle h, const sc_array& a, bool sync, hipStream_t stream = nullptr);
@@ -307,19 +339,12 @@ int ingest_embeddings(sc_handle h, const sc_array& a, bool sync, hipStream_t str
 // staging rows): *sync is set when the caller must wait for s before the source may go
 int ingest_rows_into(sc_handle h, const sc_array& a, double* X, int ldx, hipStream_t s,
                      bool* sync);
-// ---- a k-means input as a described source (ingest.hip, kmeans_api.hip) -------------------
-// validate_array and rows * cols <= 2^31 - 1
-int validate_kmeans_array(sc_handle h, const sc_array* a);
-// compact host fp64 rows: what the double* k-means entries take (one copy + k_to_colmajor)
-bool array_is_compact_host_f64(const sc_array& a);
-// the (n, dim) values, widened, into X[j * ld + r], ld = round_up(n, 16) (rows n .. ld - 1 of
-// every column zeroed) on stream s; the caller waits for s before the source may go
+// the (n, dim) values of a k-means input, widened, into X[j * ld + r], ld = round_up(n, 16) (rows
+// n .. ld - 1 of every column zeroed) on stream s; the caller waits for s before the source may go
 int ingest_columns_into(sc_handle h, const sc_array& a, double* X, int ld, hipStream_t s);
-// ---- a caller's affinity as a described source (ingest.hip, affinity_api.hip) -------------
-// validate_array and rows == cols
-int validate_affinity_array(sc_handle h, const sc_array* a);
-// the (n, n) values, widened, into dst (row pitch ld, padding columns zeroed) on stream s, and the
-// exact-symmetry flag into *flag (device memory); *sync as in ingest_rows_into
+// the (n, n) values of an affinity or constraint matrix, widened, into dst (row pitch ld, padding
+// columns zeroed) on stream s, and the exact-symmetry flag into *flag (device memory); *sync as
+// in ingest_rows_into
 int ingest_affinity_into(sc_handle h, const sc_array& a, double* dst, int ld, int* flag,
                          hipStream_t s, bool* sync);
 // 64 sources per launch (member z: dsts[z] of pitch matrix_ld(n_z), flags[z]); `stage`
@@ -331,20 +356,12 @@ size_t affinity_group_stage_bytes(const sc_array* as, int count);
 int ingest_affinity_group(sc_handle h, const sc_array* as, int count, double* const* dsts,
                           int* flags, void* stage, void* table, hipStream_t s,
                           int* host_flags = nullptr);
-// ---- results where the caller wants them (egress.hip) -----------------------------------
-// every check of an output descriptor `what`, before any launch or copy: validate_array's, the
-// exact shape, and that no two indices of the view share an address
-int validate_out_array(sc_handle h, const sc_array* a, const char* what, int rows, int cols);
+// ---- egress: results where the caller wants them (egress.hip) --------------------------------
 // The (rows, cols) fp64 values at src -- element (r, c) at src[r * ld + c], or with
 // `column_major` at src[c * ld + r] -- narrowed into the validated `out` on the handle's stream.
 // Returns with the stream drained (a host destination is complete, a device one as well).
 int egress_matrix(sc_handle h, const double* src, int ld, int rows, int cols, bool column_major,
                   const sc_array& out);
-// every check of the label array `what` of member i (centroids.hip): one row of n entries --
-// rows 1, cols n, the column stride >= 0 -- of SC_DTYPE_I64 / I32, as an input also F64 / F32; an
-// `output` has entries that share no address.  No launch, no copy.
-int validate_label_array(sc_handle h, const sc_array* a, const char* what, int i, int64_t n,
-                         bool output);
 // sc_stage_sym_eig / sc_stage_eig behind their upload (api.hip): the matrix is in B1, the values
 // land in `values` and the eigenvectors in E (column-major, pitch round_up(n, 16))
 int stage_sym_eig_resident(sc_handle h, int n, int count, int descend, double* values,
@@ -597,8 +614,6 @@ struct CpGroupMember {
 };
 int constraint_propagation_group(sc_handle lead, hipStream_t s, const CpGroupMember* mem,
                                  int count, double alpha);
-// validate_affinity_array's rules for a dense constraint source (sc_set_constraint_array)
-int validate_constraint_array(sc_handle h, const sc_array* q);
 // sc_set_constraint_pairs' checks of a host entry list, and whether it is symmetric
 int validate_constraint_pairs(sc_handle h, const int32_t* rows, const int32_t* cols,
                               const double* vals, int count, int n, bool* symmetric);

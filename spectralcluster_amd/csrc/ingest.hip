@@ -9,6 +9,12 @@
 // An (n, n) affinity or constraint matrix (k_ingest_affinity) and the (n, dim) input of the
 // k-means entries (k_ingest_columns: the column-major layout of the k-means kernels) come in the
 // same way, through the same widening and the same LDS tile.
+//
+// The file in order: the kernels and their launches (element type by dispatch_dtype, wide
+// accesses by aligned16: array_layout.h); the one host staging path (pack_host_rows /
+// scatter_host_rows, ensure_stage, stage_host_rows), which the egress and the centroids use as
+// well; the one descriptor check (validate_view) behind the validate_* roles of every
+// translation unit; then the three ways in (rows, columns, affinity) and the entry points.
 #include <climits>
 #include <cstddef>
 
@@ -57,8 +63,7 @@ void launch_ingest_typed(hipStream_t s, const void* src, long long row_stride, l
   constexpr int E = 16 / (int)sizeof(T);
   const long long total = (long long)n * (ldx / E);
   const unsigned blocks = (unsigned)std::min<long long>((total + 255) / 256, 1 << 20);
-  const bool fast = col_stride == 1 && (reinterpret_cast<uintptr_t>(src) & 15u) == 0 &&
-                    (n == 1 || (row_stride * (long long)sizeof(T)) % 16 == 0);
+  const bool fast = col_stride == 1 && aligned16(src, row_stride, sizeof(T), n);
   const T* p = static_cast<const T*>(src);
   if (fast)
     hipLaunchKernelGGL((k_ingest_rows<T, true>), dim3(blocks), dim3(256), 0, s, p, row_stride,
@@ -70,12 +75,9 @@ void launch_ingest_typed(hipStream_t s, const void* src, long long row_stride, l
 
 void launch_ingest_rows(hipStream_t s, int dtype, const void* src, long long row_stride,
                         long long col_stride, int n, int d, double* X, int ldx) {
-  switch (dtype) {
-    case SC_DTYPE_F64: launch_ingest_typed<double>(s, src, row_stride, col_stride, n, d, X, ldx); break;
-    case SC_DTYPE_F32: launch_ingest_typed<float>(s, src, row_stride, col_stride, n, d, X, ldx); break;
-    case SC_DTYPE_F16: launch_ingest_typed<F16Bits>(s, src, row_stride, col_stride, n, d, X, ldx); break;
-    default: launch_ingest_typed<BF16Bits>(s, src, row_stride, col_stride, n, d, X, ldx); break;
-  }
+  dispatch_dtype(dtype, [&](auto t) {
+    launch_ingest_typed<decltype(t)>(s, src, row_stride, col_stride, n, d, X, ldx);
+  });
 }
 
 // ---- an (n, n) affinity where it is -> fp64 rows of pitch ld, and its symmetry flag ----------
@@ -238,7 +240,7 @@ unsigned aff_blocks(int n) {
 
 AffIngestItem aff_item(int dtype, const void* src, long long row_stride, long long col_stride,
                        int n, double* dst, int ld, int* flag) {
-  const long long eb = (long long)dtype_bytes(dtype);
+  const size_t eb = dtype_bytes(dtype);
   AffIngestItem m;
   m.src = src;
   m.row_stride = row_stride;
@@ -248,47 +250,13 @@ AffIngestItem aff_item(int dtype, const void* src, long long row_stride, long lo
   m.n = n;
   m.ld = ld;
   m.dtype = dtype;
-  if (col_stride == 1 && (reinterpret_cast<uintptr_t>(src) & 15u) == 0 &&
-      (n == 1 || (row_stride * eb) % 16 == 0))
+  if (col_stride == 1 && aligned16(src, row_stride, eb, n))
     m.mode = kAffVec;
-  else if (row_stride == 1 && col_stride != 1 && (reinterpret_cast<uintptr_t>(src) & 15u) == 0 &&
-           (col_stride * eb) % 16 == 0)
+  else if (row_stride == 1 && aligned16(src, col_stride, eb, n))
     m.mode = kAffVecCols;
   else
     m.mode = col_stride > row_stride ? kAffCols : kAffRows;
   return m;
-}
-
-// Host rows that hipMemcpy2D cannot describe (a column stride, rows that overlap): gathered
-// into `tmp` at the source's width.
-void pack_host_rows(const sc_array& a, std::vector<unsigned char>* tmp) {
-  const size_t eb = dtype_bytes(a.dtype);
-  tmp->resize((size_t)a.rows * a.cols * eb);
-  const unsigned char* base = static_cast<const unsigned char*>(a.data);
-  unsigned char* out = tmp->data();
-  for (int64_t r = 0; r < a.rows; ++r)
-    for (int64_t c = 0; c < a.cols; ++c, out += eb)
-      memcpy(out, base + (size_t)(r * a.row_stride + c * a.col_stride) * eb, eb);
-}
-
-
-// Host rows at their own width into staging memory of a 16-byte pitch (device pointer `stage`),
-// gathered first where hipMemcpy2D cannot describe them.  *sync: `packed` is a local.
-int stage_host_rows(sc_handle h, const sc_array& a, void* stage, size_t pitch, hipStream_t s,
-                    std::vector<unsigned char>* packed, bool* sync) {
-  const int n = (int)a.rows;
-  const size_t eb = dtype_bytes(a.dtype), width = (size_t)a.cols * eb;
-  const void* src = a.data;
-  size_t spitch = (size_t)a.row_stride * eb;
-  if (a.col_stride != 1 || (a.row_stride < a.cols && n > 1)) {
-    pack_host_rows(a, packed);
-    src = packed->data();
-    spitch = width;
-    *sync = true;
-  }
-  if (n == 1) spitch = width;
-  SC_HIP(h, hipMemcpy2DAsync(stage, pitch, src, spitch, width, n, hipMemcpyHostToDevice, s));
-  return SC_OK;
 }
 
 // ---- an (n, dim) input where it is -> the k-means layout X[j * ld + r], fp64 -----------------
@@ -331,8 +299,7 @@ void launch_ingest_columns_typed(hipStream_t s, const void* src, long long row_s
                                  long long col_stride, int n, int dim, double* X, int ld) {
   const unsigned tiles = (unsigned)((n + kAffTile - 1) / kAffTile) *
                          (unsigned)((dim + kAffTile - 1) / kAffTile);
-  const bool vec = col_stride == 1 && (reinterpret_cast<uintptr_t>(src) & 15u) == 0 &&
-                   (n == 1 || (row_stride * (long long)sizeof(T)) % 16 == 0);
+  const bool vec = col_stride == 1 && aligned16(src, row_stride, sizeof(T), n);
   const T* p = static_cast<const T*>(src);
   if (vec)
     hipLaunchKernelGGL((k_ingest_columns<T, 16 / (int)sizeof(T)>), dim3(tiles), dim3(256), 0, s, p,
@@ -348,23 +315,69 @@ void launch_ingest_columns(hipStream_t s, int dtype, const void* src, long long 
     launch_ingest_rows(s, dtype, src, col_stride, row_stride, dim, n, X, ld);
     return;
   }
-  switch (dtype) {
-    case SC_DTYPE_F64:
-      launch_ingest_columns_typed<double>(s, src, row_stride, col_stride, n, dim, X, ld);
-      break;
-    case SC_DTYPE_F32:
-      launch_ingest_columns_typed<float>(s, src, row_stride, col_stride, n, dim, X, ld);
-      break;
-    case SC_DTYPE_F16:
-      launch_ingest_columns_typed<F16Bits>(s, src, row_stride, col_stride, n, dim, X, ld);
-      break;
-    default:
-      launch_ingest_columns_typed<BF16Bits>(s, src, row_stride, col_stride, n, dim, X, ld);
-      break;
-  }
+  dispatch_dtype(dtype, [&](auto t) {
+    launch_ingest_columns_typed<decltype(t)>(s, src, row_stride, col_stride, n, dim, X, ld);
+  });
 }
 
 }  // namespace
+
+// ------------------------------------------------------------------------------
+// host rows <-> device staging memory
+// ------------------------------------------------------------------------------
+// The first `rows` rows of a host view, gathered at the view's width into compact rows at `out`
+// -- and the way back.  (For what hipMemcpy2D cannot describe: a column stride, rows that overlap.)
+void pack_host_rows(const sc_array& a, int64_t rows, unsigned char* out) {
+  const size_t eb = dtype_bytes(a.dtype), width = (size_t)a.cols * eb;
+  const unsigned char* base = static_cast<const unsigned char*>(a.data);
+  for (int64_t r = 0; r < rows; ++r) {
+    const unsigned char* row = base + (size_t)(r * a.row_stride) * eb;
+    if (a.col_stride == 1) {
+      memcpy(out, row, width);
+      out += width;
+    } else {
+      for (int64_t c = 0; c < a.cols; ++c, out += eb) memcpy(out, row + (size_t)(c * a.col_stride) * eb, eb);
+    }
+  }
+}
+
+void scatter_host_rows(const unsigned char* in, const sc_array& a, int64_t rows) {
+  const size_t eb = dtype_bytes(a.dtype);
+  unsigned char* base = static_cast<unsigned char*>(const_cast<void*>(a.data));
+  for (int64_t r = 0; r < rows; ++r)
+    for (int64_t c = 0; c < a.cols; ++c, in += eb)
+      memcpy(base + (size_t)(r * a.row_stride + c * a.col_stride) * eb, in, eb);
+}
+
+// The handle's staging buffer holds `bytes` for work on stream s.  (What is queued on another
+// stream than the handle's may still read the buffer that a reallocation frees: waited for.)
+int ensure_stage(sc_handle h, size_t bytes, hipStream_t s) {
+  if (h->Xstage.bytes >= bytes) return SC_OK;
+  if (h->Xstage.p && s != h->stream) SC_HIP(h, hipStreamSynchronize(s));
+  return grow(h, h->Xstage, bytes);
+}
+
+// Host rows at their own width into device memory `stage` of row pitch `pitch` bytes on stream
+// s: one hipMemcpy2DAsync where it can describe them, gathered into `packed` first where it
+// cannot.  The one place that decides between the two.  *sync is set when `packed` feeds the
+// copy: the caller waits for s while `packed` lives.
+int stage_host_rows(sc_handle h, const sc_array& a, void* stage, size_t pitch, hipStream_t s,
+                    std::vector<unsigned char>* packed, bool* sync) {
+  const int n = (int)a.rows;
+  const size_t eb = dtype_bytes(a.dtype), width = (size_t)a.cols * eb;
+  const void* src = a.data;
+  size_t spitch = (size_t)a.row_stride * eb;
+  if (a.col_stride != 1 || (a.row_stride < a.cols && n > 1)) {
+    packed->resize((size_t)n * width);
+    pack_host_rows(a, n, packed->data());
+    src = packed->data();
+    spitch = width;
+    *sync = true;
+  }
+  if (n == 1) spitch = width;  // (the pitch of one row addresses nothing)
+  SC_HIP(h, hipMemcpy2DAsync(stage, pitch, src, spitch, width, n, hipMemcpyHostToDevice, s));
+  return SC_OK;
+}
 
 // ------------------------------------------------------------------------------
 // validation (no launch, no copy)
@@ -377,23 +390,97 @@ bool is_device_memory_of(sc_handle h, const void* p) {
   return e == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == h->device;
 }
 
-int validate_array(sc_handle h, const sc_array* a) {
-  if (!a) return fail(h, SC_ERR_INVALID, "embeddings descriptor is NULL");
-  if (!a->data || a->rows <= 0 || a->cols <= 0)
-    return fail(h, SC_ERR_INVALID, "embeddings must be (n, d)");
-  if (a->rows > INT_MAX || a->cols > INT_MAX)
-    return fail(h, SC_ERR_INVALID, "embeddings: rows and cols must fit an int");
-  if (a->dtype < SC_DTYPE_F64 || a->dtype > SC_DTYPE_BF16)
-    return fail(h, SC_ERR_INVALID, "embeddings: unknown dtype (SC_DTYPE_F64 / F32 / F16 / BF16)");
+// no two indices of a (rows, cols) view of element strides (rs, cs) share an address: over the
+// dimensions of more than one element, ordered by stride, small >= 1 and big >= small * extent
+bool view_is_injective(long long rows, long long cols, long long rs, long long cs) {
+  if (rows > 1 && cols > 1) {
+    const bool rows_small = rs < cs;
+    const long long small = rows_small ? rs : cs, big = rows_small ? cs : rs;
+    const long long extent = rows_small ? rows : cols;
+    return small >= 1 && big / extent >= small;  // (no overflow: big >= small * extent)
+  }
+  if (rows > 1) return rs >= 1;
+  if (cols > 1) return cs >= 1;
+  return true;
+}
+
+namespace {
+
+// What a role asks of its descriptor beyond the checks every descriptor gets.
+struct ViewRule {
+  unsigned dtypes;         // bit t: dtype t is taken
+  const char* dtype_text;  // the message when it is another one
+  int64_t rows, cols;      // the shape; rows < 0: any positive one whose extents fit an int
+  bool vector;             // one row of `cols` entries: the row stride addresses nothing
+  bool output;             // written: no two indices may share an address
+  bool fits_2_31;          // rows * cols <= 2^31 - 1
+};
+constexpr unsigned kFloatDtypes = 1u << SC_DTYPE_F64 | 1u << SC_DTYPE_F32 | 1u << SC_DTYPE_F16 |
+                                  1u << SC_DTYPE_BF16;
+constexpr unsigned kLabelDtypes = 1u << SC_DTYPE_I64 | 1u << SC_DTYPE_I32;
+constexpr const char* kFloatDtypeText = "unknown dtype (SC_DTYPE_F64 / F32 / F16 / BF16)";
+
+// Every check of the descriptor `what` (SC_ERR_INVALID + message), in the order: present, data
+// and shape, dtype, location, strides, injective, really device memory, and what the rule adds
+// about the sizes.
+int validate_view(sc_handle h, const sc_array* a, const std::string& what, const ViewRule& rule) {
+  auto refuse = [&](const std::string& msg) { return fail(h, SC_ERR_INVALID, what + msg); };
+  if (!a) return refuse(" descriptor is NULL");
+  const bool any = rule.rows < 0;
+  if (rule.vector) {
+    if (!a->data) return refuse(": data is NULL");
+    if (a->rows != 1 || a->cols != rule.cols)
+      return refuse(" must hold " + std::to_string(rule.cols) + " entries, not " +
+                    std::to_string(a->rows == 1 ? a->cols : a->rows * a->cols));
+  } else if (any) {
+    if (!a->data || a->rows <= 0 || a->cols <= 0) return refuse(" must be (n, d)");
+    if (a->rows > INT_MAX || a->cols > INT_MAX) return refuse(": rows and cols must fit an int");
+  } else if (!a->data || a->rows != rule.rows || a->cols != rule.cols) {
+    return refuse(" must be (" + std::to_string(rule.rows) + ", " + std::to_string(rule.cols) + ")");
+  }
+  if (a->dtype < 0 || a->dtype > 31 || !(rule.dtypes >> a->dtype & 1u))
+    return refuse(std::string(": ") + rule.dtype_text);
   if (a->location != SC_MEM_HOST && a->location != SC_MEM_DEVICE)
-    return fail(h, SC_ERR_INVALID, "embeddings: unknown location (SC_MEM_HOST / SC_MEM_DEVICE)");
-  if (a->row_stride < 0 || a->col_stride < 0)
-    return fail(h, SC_ERR_INVALID, "embeddings: strides must not be negative");
+    return refuse(": unknown location (SC_MEM_HOST / SC_MEM_DEVICE)");
+  if (a->col_stride < 0 || (!rule.vector && a->row_stride < 0))
+    return refuse(rule.vector ? ": the stride must not be negative"
+                              : ": strides must not be negative");
+  if (rule.output && !view_is_injective(a->rows, a->cols, a->row_stride, a->col_stride))
+    return refuse(": the view maps two indices to one address");
   if (a->location == SC_MEM_DEVICE && !is_device_memory_of(h, a->data))
-    return fail(h, SC_ERR_INVALID,
-                "embeddings: location is SC_MEM_DEVICE but the pointer is not device memory of "
-                "the handle's device");
+    return refuse(": location is SC_MEM_DEVICE but the pointer is not device memory of the "
+                  "handle's device");
+  if (rule.fits_2_31 && a->rows * a->cols > 0x7fffffffLL)
+    return fail(h, SC_ERR_INVALID, "k-means input larger than 2^31 elements");
   return SC_OK;
+}
+
+}  // namespace
+
+// the roles (handle.h says what each is for)
+int validate_array(sc_handle h, const sc_array* a) {
+  return validate_view(h, a, "embeddings", {kFloatDtypes, kFloatDtypeText, -1, -1});
+}
+int validate_kmeans_array(sc_handle h, const sc_array* a) {
+  return validate_view(h, a, "embeddings",
+                       {kFloatDtypes, kFloatDtypeText, -1, -1, false, false, true});
+}
+int validate_affinity_array(sc_handle h, const sc_array* a, const char* what) {
+  SC_TRY(validate_array(h, a));
+  if (a->rows != a->cols) return fail(h, SC_ERR_INVALID, std::string(what) + " must be (n, n)");
+  return SC_OK;
+}
+int validate_out_array(sc_handle h, const sc_array* a, const char* what, int rows, int cols) {
+  return validate_view(h, a, what, {kFloatDtypes, kFloatDtypeText, rows, cols, false, true});
+}
+int validate_label_array(sc_handle h, const sc_array* a, const char* what, int i, int64_t n,
+                         bool output) {
+  const unsigned floats = 1u << SC_DTYPE_F64 | 1u << SC_DTYPE_F32;
+  return validate_view(h, a, std::string(what) + " " + std::to_string(i),
+                       {output ? kLabelDtypes : kLabelDtypes | floats,
+                        output ? "dtype must be SC_DTYPE_I64 or SC_DTYPE_I32"
+                               : "dtype must be SC_DTYPE_I64, I32, F64 or F32",
+                        1, n, true, output});
 }
 
 int validate_batch_arrays(sc_handle h, const sc_array* xs, int count, std::vector<int>* ns, int* d,
@@ -458,56 +545,31 @@ int ingest_embeddings(sc_handle h, const sc_array& a, bool sync, hipStream_t str
 // caller must wait for s before it returns.  (A host fp64 source leaves the columns d..ldx of
 // X as they were; every other source zeroes them.)
 int ingest_rows_into(sc_handle h, const sc_array& a, double* X, int ldx, hipStream_t s,
-                     bool* sync_out) {
+                     bool* sync) {
   const int n = (int)a.rows, d = (int)a.cols;
-  bool sync = false;
   const size_t eb = dtype_bytes(a.dtype);
-  if (a.location == SC_MEM_DEVICE) {
-    launch_ingest_rows(s, a.dtype, a.data, a.row_stride, a.col_stride, n, d, X, ldx);
-    SC_TRY(check_last(h, "ingest launch"));
-  } else {
-    std::vector<unsigned char> packed;
-    const void* src = a.data;
-    size_t spitch = (size_t)a.row_stride * eb;
-    if (a.col_stride != 1 || (a.row_stride < a.cols && n > 1)) {
-      pack_host_rows(a, &packed);
-      src = packed.data();
-      spitch = (size_t)d * eb;
-      sync = true;  // (`packed` is a local)
-    }
-    if (n == 1) spitch = (size_t)d * eb;
-    if (a.dtype == SC_DTYPE_F64) {
-      SC_HIP(h, hipMemcpy2DAsync(X, (size_t)ldx * sizeof(double), src, spitch,
-                                 (size_t)d * sizeof(double), n, hipMemcpyHostToDevice, s));
-    } else {
-      // staging rows on a 16-byte pitch (the kernel's wide loads); sized with the X buffer, so
-      // an arena reserved for the largest member of a batch allocates it once
-      const size_t pitch = ((size_t)d * eb + 15) / 16 * 16;
-      const size_t need = std::max((size_t)n * pitch, h->X.bytes / sizeof(double) * eb);
-      if (h->Xstage.bytes < need) {
-        if (h->Xstage.p && s != h->stream) SC_HIP(h, hipStreamSynchronize(s));
-        SC_TRY(grow(h, h->Xstage, need));
-      }
-      SC_HIP(h, hipMemcpy2DAsync(h->Xstage.p, pitch, src, spitch, (size_t)d * eb, n,
-                                 hipMemcpyHostToDevice, s));
-      launch_ingest_rows(s, a.dtype, h->Xstage.p, (long long)(pitch / eb), 1, n, d, X, ldx);
-      SC_TRY(check_last(h, "ingest launch"));
-    }
+  std::vector<unsigned char> packed;
+  if (a.location == SC_MEM_HOST && a.dtype == SC_DTYPE_F64)  // straight into X, d doubles a row
+    return stage_host_rows(h, a, X, (size_t)ldx * sizeof(double), s, &packed, sync);
+  const void* src = a.data;
+  long long row_stride = a.row_stride, col_stride = a.col_stride;
+  if (a.location == SC_MEM_HOST) {
+    // staging rows on a 16-byte pitch (the kernel's wide loads); sized with the X buffer, so
+    // an arena reserved for the largest member of a batch allocates it once
+    const size_t pitch = align16((size_t)d * eb);
+    SC_TRY(ensure_stage(h, std::max((size_t)n * pitch, h->X.bytes / sizeof(double) * eb), s));
+    SC_TRY(stage_host_rows(h, a, h->Xstage.p, pitch, s, &packed, sync));
+    src = h->Xstage.p;
+    row_stride = (long long)(pitch / eb);
+    col_stride = 1;
   }
-  if (sync) *sync_out = true;
-  return SC_OK;
+  launch_ingest_rows(s, a.dtype, src, row_stride, col_stride, n, d, X, ldx);
+  return check_last(h, "ingest launch");
 }
 
 // ------------------------------------------------------------------------------
 // the one place a described k-means input enters
 // ------------------------------------------------------------------------------
-int validate_kmeans_array(sc_handle h, const sc_array* a) {
-  SC_TRY(validate_array(h, a));
-  if (a->rows * a->cols > 0x7fffffffLL)
-    return fail(h, SC_ERR_INVALID, "k-means input larger than 2^31 elements");
-  return SC_OK;
-}
-
 bool array_is_compact_host_f64(const sc_array& a) {
   return a.location == SC_MEM_HOST && a.dtype == SC_DTYPE_F64 &&
          (a.col_stride == 1 || a.cols == 1) && (a.row_stride == a.cols || a.rows == 1);
@@ -533,11 +595,8 @@ int ingest_columns_into(sc_handle h, const sc_array& a, double* X, int ld, hipSt
     v.row_stride = a.col_stride;
     v.col_stride = a.row_stride;
   }
-  const size_t pitch = ((size_t)v.cols * eb + 15) / 16 * 16;
-  if (h->Xstage.bytes < (size_t)v.rows * pitch) {
-    if (h->Xstage.p && s != h->stream) SC_HIP(h, hipStreamSynchronize(s));
-    SC_TRY(grow(h, h->Xstage, (size_t)v.rows * pitch));
-  }
+  const size_t pitch = align16((size_t)v.cols * eb);
+  SC_TRY(ensure_stage(h, (size_t)v.rows * pitch, s));
   std::vector<unsigned char> packed;
   bool sync = false;
   SC_TRY(stage_host_rows(h, v, h->Xstage.p, pitch, s, &packed, &sync));
@@ -551,12 +610,6 @@ int ingest_columns_into(sc_handle h, const sc_array& a, double* X, int ld, hipSt
 // ------------------------------------------------------------------------------
 // the one place a caller's affinity enters
 // ------------------------------------------------------------------------------
-int validate_affinity_array(sc_handle h, const sc_array* a) {
-  SC_TRY(validate_array(h, a));
-  if (a->rows != a->cols) return fail(h, SC_ERR_INVALID, "affinity must be (n, n)");
-  return SC_OK;
-}
-
 // The (n, n) values of a validated source, widened, into dst (row pitch ld doubles, padding
 // columns zeroed) on stream s, and *flag (device memory) = is it exactly symmetric.  *sync as in
 // ingest_rows_into.  A host fp64 source takes sc_set_affinity's copy and the separate symmetry
@@ -582,11 +635,8 @@ int ingest_affinity_into(sc_handle h, const sc_array& a, double* dst, int ld, in
     SC_TRY(check_last(h, "symmetry flag launch"));
     if (sync) SC_HIP(h, hipStreamSynchronize(s));  // (`packed` is a local)
   } else {
-    const size_t pitch = ((size_t)n * eb + 15) / 16 * 16;
-    if (h->Xstage.bytes < (size_t)n * pitch) {
-      if (h->Xstage.p && s != h->stream) SC_HIP(h, hipStreamSynchronize(s));
-      SC_TRY(grow(h, h->Xstage, (size_t)n * pitch));
-    }
+    const size_t pitch = align16((size_t)n * eb);
+    SC_TRY(ensure_stage(h, (size_t)n * pitch, s));
     std::vector<unsigned char> packed;
     SC_TRY(stage_host_rows(h, a, h->Xstage.p, pitch, s, &packed, &sync));
     hipLaunchKernelGGL(k_ingest_affinity, dim3(aff_blocks(n)), dim3(256), 0, s,
@@ -607,7 +657,7 @@ size_t affinity_group_stage_bytes(const sc_array* as, int count) {
   size_t total = 0;
   for (int z = 0; z < count; ++z)
     if (as[z].location == SC_MEM_HOST)
-      total += (size_t)as[z].rows * (((size_t)as[z].rows * dtype_bytes(as[z].dtype) + 15) / 16 * 16);
+      total += (size_t)as[z].rows * align16((size_t)as[z].rows * dtype_bytes(as[z].dtype));
   return total;
 }
 int ingest_affinity_group(sc_handle h, const sc_array* as, int count, double* const* dsts,
@@ -623,7 +673,7 @@ int ingest_affinity_group(sc_handle h, const sc_array* as, int count, double* co
     const int n = (int)a.rows;
     const size_t eb = dtype_bytes(a.dtype);
     if (a.location == SC_MEM_HOST) {
-      const size_t pitch = ((size_t)n * eb + 15) / 16 * 16;
+      const size_t pitch = align16((size_t)n * eb);
       SC_TRY(stage_host_rows(h, a, at, pitch, s, &packed[z], &sync));
       items[z] = aff_item(a.dtype, at, (long long)(pitch / eb), 1, n, dsts[z], matrix_ld(n),
                           flags + z);

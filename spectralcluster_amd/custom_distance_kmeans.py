@@ -13,6 +13,7 @@ a float64 array.  Anything else (lists, integer arrays) is promoted on the host,
 
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import typing
 from dataclasses import dataclass
@@ -96,7 +97,7 @@ def run_kmeans(spectral_embeddings, n_clusters: int,
   sklearn KMeans, :33-36, :51)."""
   metric = _lib.kmeans_metric_code(custom_dist)
   source = _describe(spectral_embeddings)
-  try:
+  with source or contextlib.nullcontext():
     e = _input(source, spectral_embeddings)
     if len(e.shape) != 2:
       raise ValueError("spectral_embeddings must be 2-dimensional")
@@ -116,9 +117,6 @@ def run_kmeans(spectral_embeddings, n_clusters: int,
           handle.raw, _lib.as_double_p(e), n, int(n_clusters), int(max_iter), metric,
           _lib.as_int64_p(labels), None, ctypes.byref(iters)))
     return labels
-  finally:
-    if source is not None:
-      source.release()
 
 
 def _custom_metric_code(custom_dist) -> int:
@@ -205,11 +203,8 @@ class CustomKMeans:
             "CustomKMeans.centroids of dtype %s: the device path updates float64 centroids "
             "only" % getattr(self.centroids, "dtype", type(self.centroids).__name__))
     source = _describe(embeddings)
-    try:
+    with source or contextlib.nullcontext():
       return self._predict(embeddings, source, drawn, None if drawn else metric)
-    finally:
-      if source is not None:
-        source.release()
 
   def _predict(self, embeddings, source, drawn, metric):
     if drawn:

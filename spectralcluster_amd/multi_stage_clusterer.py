@@ -359,8 +359,7 @@ class MultiStageStreamPool:
     de-flicker against."""
     state = self._session(session)
     with _lib.use_device(self.device):
-      source = _dlpack.describe(rows, self._handle)
-      try:
+      with _dlpack.describe(rows, self._handle) as source:
         k, d = source.shape
         if state.compression_labels is not None or state.num_embeddings + k > self.U2:
           raise ValueError("load() needs an uncompressed cache that stays within U2 = %d rows"
@@ -376,8 +375,6 @@ class MultiStageStreamPool:
           state.mirror = None
         state.num_embeddings = total
         state.previous_output = None
-      finally:
-        source.release()
 
   # -------------------------------------------------------------------- step
   def streaming_predict(self, sessions: typing.Sequence[int],
@@ -399,8 +396,7 @@ class MultiStageStreamPool:
       self.last_routes = []
       return []
     with _lib.use_device(self.device):
-      source = _dlpack.describe(embeddings, self._handle)
-      try:
+      with _dlpack.describe(embeddings, self._handle) as source:
         if source.shape[0] != len(sessions):
           raise ValueError("embeddings must be (len(sessions), d)")
         self._ensure_pool(source.shape[1])
@@ -409,8 +405,6 @@ class MultiStageStreamPool:
         host = None
         if not early and any(st.num_embeddings < self.U1 for st in states):
           host = np.asarray(source.host_f64(self._pool_handle), dtype=np.float64)
-      finally:
-        source.release()
       return self._step(sessions, states, host, early)
 
   def _mirror_row(self, session, st, row) -> None:

@@ -10,6 +10,7 @@ this object so that `predict_next` continues an earlier `predict`.
 
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import typing
 
@@ -100,19 +101,14 @@ class NaiveClusterer:
       if isinstance(u, np.ndarray) and u.ndim != 2:
         raise ValueError("embeddings must be 2-dimensional")
     handle = _lib.default_handle()
-    sources = []
-    try:
-      for u in utterances:
-        sources.append(_dlpack.describe(u, lambda: handle))
+    with contextlib.ExitStack() as held:
+      sources = [held.enter_context(_dlpack.describe(u, lambda: handle)) for u in utterances]
       d = sources[0].shape[1]
       if any(src.shape[1] != d for src in sources):
         raise ValueError("all utterances must be (n_i, d) with the same d")
       count = len(sources)
       arrays = (_lib.ScArray * count)(*[src.array for src in sources])
       return call(handle, arrays, count, [src.shape[0] for src in sources])
-    finally:
-      for src in sources:
-        src.release()
 
   def predict_batch(self, utterances: typing.Sequence,
                     return_state: bool = False):

@@ -160,12 +160,9 @@ class SpectralClusterer:
     if isinstance(constraint_matrix, constraint_lib.DenseConstraints):
       _batch.check_constraint(self, n, constraint_matrix)
       with _lib.use_device(self.device):
-        source = constraint_matrix.describe(self._handle)
-        try:
+        with constraint_matrix.describe(self._handle) as source:
           handle.check(handle.lib.sc_set_constraint_array(
               handle.raw, ctypes.byref(source.array)), TypeError)
-        finally:
-          source.release()
       return True
     if isinstance(constraint_matrix, constraint_lib.ConstraintMatrix):
       _batch.check_constraint(self, n, constraint_matrix)
@@ -182,11 +179,8 @@ class SpectralClusterer:
     """Embeddings (anything predict() takes, or an already described `_dlpack.Source`) ->
     resident affinity (device GEMM, or the user's function, which gets them as a host array)."""
     if not isinstance(embeddings, _dlpack.Source):
-      source = _dlpack.describe(embeddings, lambda: handle)
-      try:
+      with _dlpack.describe(embeddings, lambda: handle) as source:
         return self._upload(handle, source)
-      finally:
-        source.release()
     source = embeddings
     if self.affinity_function is utils.compute_affinity_matrix:
       handle.check(handle.lib.sc_set_embeddings_array(handle.raw, ctypes.byref(source.array)))
@@ -197,11 +191,8 @@ class SpectralClusterer:
       a = self.affinity_function(source.host_f64(handle))
       if not isinstance(a, np.ndarray) and not hasattr(a, "__dlpack__"):
         a = np.asarray(a, dtype=np.float64)
-      affinity = _dlpack.describe(a, lambda: handle, strided=True)
-      try:
+      with _dlpack.describe(a, lambda: handle, strided=True) as affinity:
         handle.check(handle.lib.sc_set_affinity_array(handle.raw, ctypes.byref(affinity.array)))
-      finally:
-        affinity.release()
 
   def _eig_resident(self, handle: _lib.Handle, p_percentile=None) -> _lib.ScDiag:
     diag = _lib.ScDiag()
@@ -315,11 +306,8 @@ class SpectralClusterer:
       return _batch.labels_into(self, [out], [_batch.rows_of(self, embeddings)],
                                 lambda: [self.predict(embeddings, constraint_matrix)])[0]
     with _lib.use_device(self.device):  # helpers without a device argument follow self.device
-      source = _dlpack.describe(embeddings, self._handle)
-      try:
+      with _dlpack.describe(embeddings, self._handle) as source:
         return self._predict(source, constraint_matrix)
-      finally:
-        source.release()
 
   def _predict(self, source: _dlpack.Source, constraint_matrix=None) -> np.ndarray:
     n = source.shape[0]
@@ -465,8 +453,7 @@ class SpectralClusterer:
       return _batch.labels_into(self, [out], [n],
                                 lambda: [self.predict_affinity(affinity, constraint_matrix)])[0]
     with _lib.use_device(self.device):
-      source = _dlpack.describe(affinity, self._handle, strided=True)
-      try:
+      with _dlpack.describe(affinity, self._handle, strided=True) as source:
         handle = self._handle()
         default_tail = (self.post_eigen_cluster_function is custom_distance_kmeans.run_kmeans)
         if default_tail:
@@ -483,8 +470,6 @@ class SpectralClusterer:
           return labels
         handle.check(handle.lib.sc_set_affinity_array(handle.raw, ctypes.byref(source.array)))
         return self._predict_resident(handle, n, constrained, single_check, default_tail)
-      finally:
-        source.release()
 
   def predict_affinity_batch(self, affinities: typing.Sequence,
                              constraint_matrices: typing.Optional[typing.Sequence] = None,

@@ -2,6 +2,7 @@
 
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import enum
 import typing
@@ -27,22 +28,16 @@ def _stage_on_arrays(inputs, out_specs, call):
   call.  Returns the list of results (each `out` object itself, or the new array)."""
   from spectralcluster_amd import _dlpack  # (it imports this module's siblings)
   handle = _lib.default_handle()
-  held = []
-  try:
-    sources = [_dlpack.describe_input(x, lambda: handle) for x in inputs]
-    held += sources
+  with contextlib.ExitStack() as held:
+    sources = [held.enter_context(_dlpack.describe_input(x, lambda: handle)) for x in inputs]
     results, outs = [], []
     for out, shape, what in out_specs:
       shape = shape(sources) if callable(shape) else shape
       if out is None:
         out = np.empty(shape, dtype=np.float64)
       results.append(out)
-      outs.append(_dlpack.describe_out(out, lambda: handle, shape, what))
-      held.append(outs[-1])
+      outs.append(held.enter_context(_dlpack.describe_out(out, lambda: handle, shape, what)))
     call(handle, sources, outs)
-  finally:
-    for src in held:
-      src.release()
   return results
 
 
@@ -246,20 +241,16 @@ def get_cluster_centroids_batch(embeddings_list: typing.Sequence, labels_list: t
   if count == 0:
     return []
   handle = _lib.default_handle()
-  held = []
-  try:
-    xs = []
-    for e in embeddings_list:
-      xs.append(_dlpack.describe_input(e, lambda: handle))
-      held.append(xs[-1])
+  with contextlib.ExitStack() as held:
+    xs = [held.enter_context(_dlpack.describe_input(e, lambda: handle)) for e in embeddings_list]
     d = xs[0].shape[1]
     for i, x in enumerate(xs):
       if x.shape[1] != d:
         raise ValueError("member %d: all embeddings must be (n_i, d) with the same d" % i)
     labs = []
     for i, (x, l) in enumerate(zip(xs, labels_list)):
-      labs.append(_dlpack.describe_labels(l, lambda: handle, x.shape[0], "labels of member %d" % i))
-      held.append(labs[-1])
+      labs.append(held.enter_context(
+          _dlpack.describe_labels(l, lambda: handle, x.shape[0], "labels of member %d" % i)))
     # k where the host can tell: a host label array has been checked and is read here
     ks = [None if l.numpy is None else (int(l.numpy.max()) + 1 if l.numpy.size else 0)
           for l in labs]
@@ -287,8 +278,7 @@ def get_cluster_centroids_batch(embeddings_list: typing.Sequence, labels_list: t
         outs.append(_dlpack.Source(_lib.ScArray(None, _lib.SC_DTYPE_F64, _lib.SC_MEM_HOST, 0, d,
                                                 d, 1), o))
       else:
-        outs.append(_dlpack.describe_out(o, lambda: handle, shape, what))
-      held.append(outs[-1])
+        outs.append(held.enter_context(_dlpack.describe_out(o, lambda: handle, shape, what)))
     clash = _dlpack.device_overlap(outs, xs + labs)
     if clash is not None:
       raise ValueError("out of member %d overlaps embeddings or labels of the call in device "
@@ -296,9 +286,6 @@ def get_cluster_centroids_batch(embeddings_list: typing.Sequence, labels_list: t
     o_arr = (_lib.ScArray * count)(*[o.array for o in outs])
     handle.check(handle.lib.sc_cluster_centroids_arrays(handle.raw, x_arr, l_arr, count, o_arr,
                                                         k_arr))
-  finally:
-    for src in held:
-      src.release()
   return [o[:int(k)] for o, k in zip(results, k_arr)]
 
 
@@ -372,10 +359,8 @@ def cosine_agglomerative_clustering_batch(embeddings_list: typing.Sequence,
   if count == 0:
     return ([], []) if return_centroids else []
   handle = _lib.default_handle()
-  sources = []
-  try:
-    for e in embeddings_list:
-      sources.append(_dlpack.describe(e, lambda: handle))
+  with contextlib.ExitStack() as held:
+    sources = [held.enter_context(_dlpack.describe(e, lambda: handle)) for e in embeddings_list]
     d = sources[0].shape[1]
     if any(src.shape[1] != d for src in sources):
       raise ValueError("all utterances must be (n_i, d) with the same d")
@@ -389,9 +374,6 @@ def cosine_agglomerative_clustering_batch(embeddings_list: typing.Sequence,
     handle.check(handle.lib.sc_batch_ahc(
         handle.raw, (_lib.ScArray * count)(*[src.array for src in sources]), count,
         LINKAGE_CODES[linkage], int(n_clusters or 0), float(distance_threshold or 0.0), lp, cp))
-  finally:
-    for src in sources:
-      src.release()
   if not return_centroids:
     return labels
   return labels, [c[:int(l.max()) + 1] for c, l in zip(centroids, labels)]
@@ -417,10 +399,8 @@ def cosine_single_cluster_check_batch(embeddings_list: typing.Sequence,
   if count == 0:
     return single.astype(bool), heights
   handle = _lib.default_handle()
-  sources = []
-  try:
-    for e in embeddings_list:
-      sources.append(_dlpack.describe(e, lambda: handle))
+  with contextlib.ExitStack() as held:
+    sources = [held.enter_context(_dlpack.describe(e, lambda: handle)) for e in embeddings_list]
     d = sources[0].shape[1]
     if any(src.shape[1] != d for src in sources):
       raise ValueError("all utterances must be (n_i, d) with the same d")
@@ -428,7 +408,4 @@ def cosine_single_cluster_check_batch(embeddings_list: typing.Sequence,
         handle.raw, (_lib.ScArray * count)(*[src.array for src in sources]), count,
         float(distance_threshold), _lib.as_double_p(heights),
         single.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
-  finally:
-    for src in sources:
-      src.release()
   return single.astype(bool), heights

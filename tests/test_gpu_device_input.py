@@ -25,7 +25,9 @@ DTYPES = [torch.float64, torch.float32, torch.float16, torch.bfloat16]
 # (1,1): one element; (5,3) / (7,17): rows shorter / a little longer than one 16-byte load and
 # than the 16-column padding; (33,257): a ragged tail after whole loads; (64,256): no tail at all;
 # (130,250): more rows than a workgroup has lanes per row, tail and padding together
-SHAPES = [(1, 1), (5, 3), (7, 17), (33, 257), (64, 256), (130, 250)]
+# (the last three: one row -- its pitch addresses nothing; 65 rows cross the 64-wide tile edge with
+#  17 columns, where the 16-byte item straddles the row end for every element width; one column)
+SHAPES = [(1, 1), (5, 3), (7, 17), (33, 257), (64, 256), (130, 250), (1, 17), (65, 17), (65, 1)]
 LAP = {0: None, 4: sca.LaplacianType.GraphCut}
 
 
@@ -92,6 +94,11 @@ def test_ingest_is_exact_for_every_layout_from_device_and_host(handle, dtype, sh
     assert same_bits(stage_ingest(handle, t), want), (name, "host")
     if dtype != torch.bfloat16:  # ... and as the NumPy array of the same dtype
       assert same_bits(stage_ingest(handle, t.numpy()), want), (name, "numpy")
+  # rows that overlap (row stride 1 < d): from the host they are gathered before the upload
+  flat = v.flatten()[:n + d - 1].contiguous()
+  for base in (flat, flat.cuda()):
+    rows = base.as_strided((n, d), (1, 1))
+    assert same_bits(stage_ingest(handle, rows), widened(rows.contiguous())), ("overlapping", base.device)
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16],

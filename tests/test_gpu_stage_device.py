@@ -6,6 +6,9 @@ kernels are those of the float64 path, so every check is an equality: `f(input, 
 bit, `_narrow_ref` of `f(the widened float64 ndarray)` (a NaN by position)."""
 
 import ctypes
+import importlib.util
+import json
+import os
 
 import numpy as np
 import pytest
@@ -23,6 +26,8 @@ from spectralcluster_amd import refinement
 from spectralcluster_amd import utils
 
 pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 FLOAT = {"float64": torch.float64, "float32": torch.float32, "float16": torch.float16,
          "bfloat16": torch.bfloat16}
@@ -393,3 +398,21 @@ def test_out_on_another_device_is_refused(handle):
     refinement.CropDiagonal().refine(x, out=o)
   with pytest.raises(ValueError, match="on device 1"):
     refinement.CropDiagonal().refine(x.to("cuda:1"))
+
+
+# ------------------------------------------------- bad descriptors, as recorded
+def test_every_entry_point_refuses_a_bad_descriptor_as_recorded(handle):
+  """Return code and sc_last_error text of every case of tools/make_descriptor_errors_golden.py
+  (raw ctypes calls that all fail in validation: nothing is launched) against the recorded file."""
+  spec = importlib.util.spec_from_file_location(
+      "make_descriptor_errors_golden",
+      os.path.join(ROOT, "tools", "make_descriptor_errors_golden.py"))
+  cases = importlib.util.module_from_spec(spec)
+  spec.loader.exec_module(cases)
+  with open(os.path.join(ROOT, "tests", "golden", "descriptor_errors.json")) as f:
+    want = json.load(f)
+  assert sorted(want) == sorted(cases.CASES)
+  assert all(v["code"] == _lib.SC_ERR_INVALID and v["error"] for v in want.values())
+  got = {key: cases.record(handle, key) for key in cases.CASES}
+  wrong = {key: (got[key], want[key]) for key in want if got[key] != want[key]}
+  assert not wrong, wrong

@@ -4,7 +4,9 @@ described as it lies or refused before anything is launched, and a call that tak
 (an ndarray or a list in, `out=None`) makes exactly today's library call."""
 
 import ctypes
+import importlib.util
 import inspect
+import json
 import os
 import re
 
@@ -299,3 +301,30 @@ def test_the_argument_checks_are_todays_whatever_the_route(recorder):
   with pytest.raises(ValueError, match=r"out must have shape \(6, 6\)"):
     utils.compute_affinity_matrix(np.zeros((6, 3)), out=np.zeros((6, 3)))
   assert recorder.calls == []
+
+
+# ------------------------------------------------- every role's answers, as recorded
+def _describe_cases():
+  spec = importlib.util.spec_from_file_location(
+      "make_describe_errors_golden", os.path.join(ROOT, "tools", "make_describe_errors_golden.py"))
+  module = importlib.util.module_from_spec(spec)
+  spec.loader.exec_module(module)
+  return module
+
+
+DESCRIBE_CASES = _describe_cases()
+with open(os.path.join(ROOT, "tests", "golden", "describe_errors.json")) as _f:
+  DESCRIBE_GOLDEN = json.load(_f)
+
+
+def test_the_recorded_grid_is_the_grid():
+  assert sorted(DESCRIBE_GOLDEN) == sorted(DESCRIBE_CASES.CASES)
+  roles = {key.split(":")[0] for key in DESCRIBE_GOLDEN}
+  assert roles == {"embeddings", "strided", "out1d", "out2d", "labels_in", "labels_out"}
+
+
+@pytest.mark.parametrize("key", sorted(DESCRIBE_GOLDEN))
+def test_every_role_answers_what_was_recorded(key):
+  """Exception type and full message, or the seven sc_array fields (the data pointer relative to
+  the object's memory), for each object of tools/make_describe_errors_golden.py."""
+  assert DESCRIBE_CASES.record(key) == DESCRIBE_GOLDEN[key]
